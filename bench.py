@@ -30,6 +30,19 @@ Unit of work ("cell-update"):
               own evaluation count (which includes octant-boundary planes twice).
   chemistry = one cell in one global_pass (N^3 per step).
 Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set up, SETTLE_S seconds of untimed iterations (then the time step is begun
+afresh), one first iteration of the time step, --warmup steps, ONE timed region of exactly --steps steps (value,
+ms_per_step; the per-kernel times and the roofline fields come from the HIP events of those same steps), --dump-outputs,
+the JSON line.  `--full` adds everything else: the median of --repeats (default 5) timed
+regions, the timed first iteration of a time step, the single-core and one-socket CPU baselines, `evolving_state` (default job),
+and at N>1 the one-GPU run of the same workload, the configs[4] block and the check that the ranks agree.  --repeats,
+--cpu-sources, --evolving-state, --one-gpu-reference and --configs4 ask for one of these without --full.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the timed path computed in its last step -- the two grids
+evolve3D hands back, DIR/xh_new.npy and DIR/phi_ion.npy (float64).  A pair of grids larger than 64 MB is written as a fixed
+sample of DUMP_SAMPLE_CELLS cells (flat C-order indices drawn by np.random.default_rng(DUMP_SEED), sorted), the same for both.
+The inputs depend on the arguments only.
 """
 import argparse
 import json
@@ -54,6 +67,10 @@ RT_BYTES_PER_UPDATE = 32                           # 8 ndens + 8
 CHEM_BYTES_PER_UPDATE = 56                         # 5 loads + 2 stores
 CHEM_FUSED_BYTES_PER_UPDATE = 88                   # the fused pass on a uniform-temperature grid (both workloads here): 5 loads
                                                    # + 6 stores; 96 with a temperature grid that has to be read
+DUMP_LIMIT_BYTES = 64 << 20                        # --dump-outputs: all files together
+DUMP_SAMPLE_CELLS = 1 << 21                        # cells per grid when the whole grids exceed that (2 x 16 MiB)
+DUMP_SEED = 20240601
+SETTLE_S = 0.25                                    # untimed iterations before the time step that is measured (main())
 
 
 def make_tables(numtau=NUMTAU):
@@ -677,6 +694,19 @@ def launch_check(fail_rank):
         raise SystemExit(1)
 
 
+def dump_outputs(dirname, grids):
+    """--dump-outputs: each grid of `grids` (name -> float64 (N,N,N)) as dirname/<name>.npy; whole if all of them fit
+    DUMP_LIMIT_BYTES, else the same seeded sample of DUMP_SAMPLE_CELLS flat C-order cells of each (module docstring)."""
+    os.makedirs(dirname, exist_ok=True)
+    flat = {name: np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for name, a in grids.items()}
+    idx = None
+    if sum(v.nbytes for v in flat.values()) > DUMP_LIMIT_BYTES:
+        n = min(v.size for v in flat.values())
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(n, DUMP_SAMPLE_CELLS), replace=False))
+    for name, v in flat.items():
+        np.save(os.path.join(dirname, name + ".npy"), grids[name] if idx is None else v[idx])
+
+
 def main():
     if "--cpu-worker" in sys.argv:
         return _cpu_worker()
@@ -689,9 +719,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else the benchmark measures and checks (module docstring): "
+                         "--repeats 5, the timed first iteration, CPU baselines, evolving_state, at N>1 the one-GPU run, "
+                         "configs4 and the agreement of the ranks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what their last step computed (xh_new, phi_ion) as DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the timed region of --steps steps is run this many times back to back; value / ms_per_step are the "
-                         "MEDIAN region, `spread` holds the fastest and the slowest")
+                         "MEDIAN region, `spread` holds the fastest and the slowest (default: 1; 5 with --full)")
     ap.add_argument("--N", type=int, default=256)
     ap.add_argument("--nsrc", type=int, default=1000, help="sources: in total (strong scaling) or per GPU (weak scaling)")
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong",
@@ -708,8 +744,9 @@ def main():
                          "reference's production parameter files")
     ap.add_argument("--workload", choices=["uniform", "cosmo"], default=None,
                     help="default: uniform (configs[2]) on one GPU, cosmo (configs[3]) on several")
-    ap.add_argument("--cpu-sources", type=int, default=512,
-                    help="sources in the single-core CPU-baseline sample (0 = skip): 512 = ~11 s of the reference Fortran + 1 s for its pass")
+    ap.add_argument("--cpu-sources", type=int, default=None,
+                    help="sources in the single-core CPU-baseline sample (0 = skip): 512 = ~11 s of the reference Fortran + 1 s for its pass "
+                         "(default: 0; 512 with --full)")
     ap.add_argument("--cpu-cores", type=int, default=0,
                     help="worker processes of the one-socket CPU figure (0 = the physical cores of one socket, as far as this "
                          "process may use them; 1 = skip it)")
@@ -720,18 +757,25 @@ def main():
                          "their first coordinate), 0 = trace, then all-reduce; default: env PYC2RAY_AMD_OVERLAP or 0")
     ap.add_argument("--sectors", type=int, default=0, help="decomposition of a source (ASORA_OPT_SECTORS): 0 auto, 1 octants, 2 sectors, 3 sector pairs, 5 octant pairs, 6 whole sphere, 7 half spheres, 8 all-sign sectors")
     ap.add_argument("--pair-sources", type=int, default=0, help="raytrace, two sources per workgroup: 0 auto, 1 never, 2 always")
-    ap.add_argument("--one-gpu-reference", type=int, default=1,
+    ap.add_argument("--one-gpu-reference", type=int, default=None,
                     help="N>1: before the multi-rank region rank 0 ALONE runs the same workload (all sources) through the one-GPU loop "
-                         "while the others wait -> one_gpu_same_workload_ms_per_step, speedup_vs_one_gpu (0 = skip)")
+                         "while the others wait -> one_gpu_same_workload_ms_per_step, speedup_vs_one_gpu (0 = skip; default: 0, "
+                         "1 with --full)")
     ap.add_argument("--configs4", type=int, default=-1,
                     help="N>1: after the metric's workload also a bounded pass of BASELINE configs[4] (512^3, 1e5 sources, the regime where "
-                         "sharding pays) -> `configs4`; -1 = on for the default N-rank job, 0 = off, 1 = on")
+                         "sharding pays) -> `configs4`; -1 = on for the default N-rank job with --full, 0 = off, 1 = on")
     ap.add_argument("--configs4-grid", type=int, default=512)
     ap.add_argument("--configs4-nsrc", type=int, default=100000)
     ap.add_argument("--evolving-state", type=int, default=-1,
                     help="one GPU: also time the trace and the fused pass on a grid WITH ionisation fronts (configs[3], fluxes x 1e3, "
-                         "second time step) -> `evolving_state`; default: on for the default job only")
+                         "second time step) -> `evolving_state`; default: on for the default job with --full")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.cpu_sources is None:
+        args.cpu_sources = 512 if args.full else 0
+    if args.one_gpu_reference is None:
+        args.one_gpu_reference = 1 if args.full else 0
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1053,11 +1097,32 @@ def main():
             fell_back = "first slab step"
             if exchange_model is not None:
                 exchange_model["choice"] = "allreduce (fallback)"
+    # settle: untimed iterations, timers on, for SETTLE_S seconds (one GPU; several ranks: min(K, 32) iterations, the same
+    # count on every rank).  The first timed region after a few warm-up steps is 2-3 % slower than those after it (kernel
+    # time as well); this brings the clocks and the library's pool of timing events to their steady state before the one
+    # region a plain run times.  The time step is then begun afresh: what the timed steps start from does not depend on it.
+    lib.set_option(_capi.OPT_TIMING, 1)
+    begin_time_step()
+    if comm is None:
+        t_settle, chunk = time.perf_counter(), 1
+        while True:
+            one_gpu_region(n_local, chunk)          # (ends with a poll: everything enqueued has run)
+            if time.perf_counter() - t_settle >= SETTLE_S:
+                break
+            chunk = min(2 * chunk, poll_every)
+    else:
+        for _ in range(min(K, 32)):
+            step()
+        fence()
+    lib.set_option(_capi.OPT_TIMING, 0)
+    lib.kernel_time_reset()
     # the FIRST iteration of a time step additionally forms nHI from xh and zeroes the accumulators on the whole grid
     begin_time_step(); step(); fence()
-    t0 = time.perf_counter()
-    begin_time_step(); step(); fence()
-    first_iteration_ms = (time.perf_counter() - t0) * 1e3
+    first_iteration_ms = None
+    if args.full:
+        t0 = time.perf_counter()
+        begin_time_step(); step(); fence()
+        first_iteration_ms = (time.perf_counter() - t0) * 1e3
     for _ in range(W):
         step()
     if comm is None:
@@ -1114,6 +1179,10 @@ def main():
         gamma_cells, eval_cells, zero_cells = gamma_cells // n_done, eval_cells // n_done, zero_cells // n_done
         rows = rows if len(rows) else last_rows
         conv = (rows[-1][0],) if len(rows) else (0,)
+    if args.dump_outputs and rank == 0:
+        # what evolve3D hands back after the last timed step (PHI_ION: folded by that step's poll)
+        dump_outputs(args.dump_outputs, {"xh_new": lib.grid_to_host(_capi.GRID_XH_INTERMED, np.empty((N, N, N))),
+                                         "phi_ion": lib.grid_to_host(_capi.GRID_PHI_ION, np.empty((N, N, N)))})
     rt_ms, rt_n = lib.kernel_time_ms(_capi.KERNEL_RAYTRACE)
     ch_ms, ch_n = lib.kernel_time_ms(_capi.KERNEL_CHEMISTRY)
     pr_ms, pr_n = lib.kernel_time_ms(_capi.KERNEL_PREP)
@@ -1133,7 +1202,7 @@ def main():
     elapsed = float(np.median(regions))
     # after the timed region: every rank must hold the same summed rates and the same chemistry result
     ranks_agree = None
-    if comm is not None:
+    if comm is not None and args.full:
         try:
             phi_h = lib.grid_to_host(_capi.GRID_PHI_ION, np.empty((N, N, N)))
             x_h = lib.grid_to_host(_capi.GRID_XH_INTERMED, np.empty((N, N, N)))
@@ -1148,8 +1217,8 @@ def main():
 
     grid_placement = lib.debug_placement()         # (of the metric's grids: the configs4 block below re-initialises the library)
     configs4 = None
-    if comm is not None and state["loop"] and (args.configs4 == 1 or (args.configs4 < 0 and args.workload == "cosmo" and N == 256 and
-                                                                      args.nsrc == 1000 and args.R == 32.0 and strong)):
+    if comm is not None and state["loop"] and (args.configs4 == 1 or (args.configs4 < 0 and args.full and args.workload == "cosmo" and
+                                                                      N == 256 and args.nsrc == 1000 and args.R == 32.0 and strong)):
         # every rank takes the same branch (same arguments, same exchange choice) -- and votes on the outcome, so that a failure
         # on one rank costs this block, not the line
         ok = True
@@ -1355,7 +1424,7 @@ def main():
                               "serial by construction), all-reduce path: wall clock between the host synchronisations of its three calls")
         out["measured_link_GBs"] = links
         out["configs4"] = configs4
-    if world == 1 and (args.evolving_state == 1 or (args.evolving_state < 0 and default_job)):
+    if world == 1 and (args.evolving_state == 1 or (args.evolving_state < 0 and args.full and default_job)):
         try:
             out["evolving_state"] = evolving_state(lib, p, _capi, N, args.R, thin, thick, dlog, numtau)
         except Exception as e:   # reporting only

@@ -58,27 +58,44 @@ def test_guards_before_device_init(built):
                         np.ones(5), np.ones(5), -20.0, 0.1, 4.0, 1e-18, quiet=True, logfile=None)
 
 
+def _without_a_gpu(body):
+    """Runs `body` (Python source, indented as a function body) in a fresh interpreter that sees no GPU
+    (HIP_VISIBLE_DEVICES=-1), so that what the library does without one is checked on every machine, one with a GPU
+    included.  An AssertionError there fails the test here, with the child's output."""
+    import subprocess
+    import sys
+    import textwrap
+    code = ("import sys\nsys.path.insert(0, %r)\nimport numpy as np\nimport pytest\n" % ROOT) + textwrap.dedent(body)
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+
+
 def test_cpu_semantics_path_has_no_cpu_fallback(built):
     """use_gpu=False selects the SEMANTICS of the reference's CPU raytracer (sub-boxes, photon loss); the work is
     still done by the HIP library.  Without a GPU the call fails loudly instead of computing on the host."""
-    import pyc2ray_amd as p
-    N = 8
-    g = np.ones((N, N, N)) * 0.5
-    with pytest.raises(RuntimeError, match="device_init_auto failed"):
-        p.evolve3D(1.0, 1.0, np.ones(1), np.ones((3, 1)), False, 10, 4, 0.01, g, g, g, np.ones(5), np.ones(5),
-                   -20.0, 0.1, 4.0, 1e-4, 1e-18, 1.0, 1.0, 1.0, 1.0, 1.0, quiet=True, logfile=None)
-    with pytest.raises(RuntimeError, match="do_all_sources failed"):
-        p.do_raytracing(1.0, np.ones(1), np.ones((3, 1)), False, 10, 4, 0.01, g, g, np.ones(5), np.ones(5),
-                        np.ones(5), np.ones(5), -20.0, 0.1, 4.0, 1e-18, quiet=True, logfile=None)
+    _without_a_gpu("""
+        import pyc2ray_amd as p
+        N = 8
+        g = np.ones((N, N, N)) * 0.5
+        with pytest.raises(RuntimeError, match="device_init_auto failed"):
+            p.evolve3D(1.0, 1.0, np.ones(1), np.ones((3, 1)), False, 10, 4, 0.01, g, g, g, np.ones(5), np.ones(5),
+                       -20.0, 0.1, 4.0, 1e-4, 1e-18, 1.0, 1.0, 1.0, 1.0, 1.0, quiet=True, logfile=None)
+        with pytest.raises(RuntimeError, match="do_all_sources failed"):
+            p.do_raytracing(1.0, np.ones(1), np.ones((3, 1)), False, 10, 4, 0.01, g, g, np.ones(5), np.ones(5),
+                            np.ones(5), np.ones(5), -20.0, 0.1, 4.0, 1e-18, quiet=True, logfile=None)
+    """)
 
 
 def test_errors_come_back_as_runtime_errors_with_message(built):
-    from pyc2ray_amd.load_extensions import load_asora
-    lib = load_asora()
-    with pytest.raises(RuntimeError, match="not initialised"):
-        lib.density_to_device(np.zeros(8), 2)
-    with pytest.raises(RuntimeError):          # no GPU here: hipSetDevice fails, message carried over
-        lib.device_init(8, 1)
+    _without_a_gpu("""
+        from pyc2ray_amd.load_extensions import load_asora
+        lib = load_asora()
+        with pytest.raises(RuntimeError, match="not initialised"):
+            lib.density_to_device(np.zeros(8), 2)
+        with pytest.raises(RuntimeError):          # no GPU here: hipSetDevice fails, message carried over
+            lib.device_init(8, 1)
+    """)
 
 
 def test_format_sources_layout():

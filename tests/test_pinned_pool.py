@@ -33,7 +33,13 @@ class MallocLib:
 
 
 @pytest.fixture
-def lib():
+def lib(monkeypatch):
+    # the pool is one per process: buffers that earlier tests of the same run left on its free list came from the real
+    # library (hipHostMalloc) and must never reach MallocLib.  Each test here starts from an empty pool; the earlier one is
+    # put back afterwards.
+    gc.collect()
+    monkeypatch.setattr(_pinned, "_free", {})
+    monkeypatch.setattr(_pinned, "_pinned_bytes", 0)
     lib = MallocLib()
     yield lib
     gc.collect()

@@ -6,11 +6,11 @@ timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; echo
 fi
 if [[ $PART == *w* ]]; then
 for i in 1 2; do
-  PYC2RAY_AMD_FORCE_COLLECTIVE=1 timeout -k 10 300 python bench.py --gpus 1 --workload cosmo --steps 20 --warmup 5 --cpu-sources 0 > $O/world1_slab_$i.json 2> $O/world1_slab_$i.err; echo "world-1 slab rc=$?"
+  PYC2RAY_AMD_FORCE_COLLECTIVE=1 timeout -k 10 300 python bench.py --full --gpus 1 --workload cosmo --steps 20 --warmup 5 --cpu-sources 0 > $O/world1_slab_$i.json 2> $O/world1_slab_$i.err; echo "world-1 slab rc=$?"
 done
-PYC2RAY_AMD_FORCE_COLLECTIVE=1 timeout -k 10 300 python bench.py --gpus 1 --workload cosmo --steps 20 --warmup 5 --cpu-sources 0 --exchange allreduce > $O/world1_allreduce.json 2> $O/world1_allreduce.err; echo "world-1 allreduce rc=$?"
+PYC2RAY_AMD_FORCE_COLLECTIVE=1 timeout -k 10 300 python bench.py --full --gpus 1 --workload cosmo --steps 20 --warmup 5 --cpu-sources 0 --exchange allreduce > $O/world1_allreduce.json 2> $O/world1_allreduce.err; echo "world-1 allreduce rc=$?"
 timeout -k 10 300 python bench.py --gpus 1 --workload cosmo --steps 20 --warmup 5 --cpu-sources 0 > $O/cosmo_1gpu.json 2> $O/cosmo_1gpu.err
-PYC2RAY_AMD_BENCH_BACKEND=gloo PYC2RAY_AMD_BENCH_DEVICE=0 timeout -k 10 300 python bench.py --gpus 2 --steps 3 --warmup 1 --exchange slab > $O/selflaunch_2ranks_gloo.json 2> $O/selflaunch_2ranks_gloo.err; echo "self-launched 2 ranks rc=$?"
+PYC2RAY_AMD_BENCH_BACKEND=gloo PYC2RAY_AMD_BENCH_DEVICE=0 timeout -k 10 300 python bench.py --full --gpus 2 --steps 3 --warmup 1 --exchange slab > $O/selflaunch_2ranks_gloo.json 2> $O/selflaunch_2ranks_gloo.err; echo "self-launched 2 ranks rc=$?"
 fi
 if [[ $PART == *n* ]]; then
 timeout -k 10 300 python bench.py --N 576 --steps 10 --warmup 3 --repeats 3 --cpu-sources 0 --evolving-state 0 > $O/bench_576.json 2> $O/bench_576.err; echo "576 rc=$?"

@@ -10,7 +10,7 @@ import sys; sys.path.insert(0,'$R')
 from pyc2ray_amd.load_extensions import load_asora; print('build_id', load_asora().build_id())" > $O/build_id.txt 2>/dev/null
 if [[ $PART == *1* ]]; then
 timeout -k 10 1000 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1; echo "pytest exit $?" >> $O/pytest_gpu.log; tail -3 $O/pytest_gpu.log
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $O/bench_uniform_R32.json 2> $O/bench_uniform_R32.err; echo "bench exit $?"
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $O/bench_uniform_R32.json 2> $O/bench_uniform_R32.err; echo "bench exit $?"
 timeout -k 10 300 python bench.py --steps 20 --warmup 5 --numtau 2000 --evolving-state 1 --cpu-sources 0 > $O/bench_uniform_R32_numtau2000.json 2> $O/bench_numtau2000.err
 for RR in 16 64; do timeout -k 10 300 python bench.py --steps 10 --warmup 3 --R $RR --cpu-sources 0 > $O/bench_uniform_R$RR.json 2> $O/bench_uniform_R$RR.err; done
 timeout -k 10 400 python bench.py --steps 10 --warmup 3 --workload cosmo --cpu-sources 0 > $O/bench_cosmo_R32.json 2> $O/bench_cosmo_R32.err
@@ -39,13 +39,13 @@ timeout -k 10 300 python tools/time_steps_resident.py --out $O/time_steps_reside
 timeout -k 10 300 python tools/time_steps_resident.py --cosmological 1 --out $O/time_steps_resident_cosmological.json > /dev/null 2>> $O/tsr.err
 fi
 if [[ $PART == *4* ]]; then
-PYC2RAY_AMD_FORCE_COLLECTIVE=1 timeout -k 10 300 python bench.py --gpus 1 --workload cosmo --steps 20 --warmup 5 --cpu-sources 0 > $O/world1_rccl_slab_path.json 2> $O/world1_slab.err; echo "world-1 slab exit $?"
-PYC2RAY_AMD_FORCE_COLLECTIVE=1 timeout -k 10 300 python bench.py --gpus 1 --workload cosmo --steps 20 --warmup 5 --cpu-sources 0 --exchange allreduce > $O/world1_rccl_allreduce_path.json 2> $O/world1_allreduce.err
+PYC2RAY_AMD_FORCE_COLLECTIVE=1 timeout -k 10 300 python bench.py --full --gpus 1 --workload cosmo --steps 20 --warmup 5 --cpu-sources 0 > $O/world1_rccl_slab_path.json 2> $O/world1_slab.err; echo "world-1 slab exit $?"
+PYC2RAY_AMD_FORCE_COLLECTIVE=1 timeout -k 10 300 python bench.py --full --gpus 1 --workload cosmo --steps 20 --warmup 5 --cpu-sources 0 --exchange allreduce > $O/world1_rccl_allreduce_path.json 2> $O/world1_allreduce.err
 export PYC2RAY_AMD_BENCH_BACKEND=gloo PYC2RAY_AMD_BENCH_DEVICE=0
 for P in 2 4; do     # no launcher around them: bench.py starts its own ranks; the configs4 block runs at its full size
-  timeout -k 10 600 python bench.py --gpus $P --steps 3 --warmup 1 --repeats 2 --exchange slab > $O/selflaunch_${P}ranks_gloo.json 2> $O/selflaunch_$P.err; echo "self-launched $P ranks exit $?"
+  timeout -k 10 600 python bench.py --full --gpus $P --steps 3 --warmup 1 --repeats 2 --exchange slab > $O/selflaunch_${P}ranks_gloo.json 2> $O/selflaunch_$P.err; echo "self-launched $P ranks exit $?"
 done
-timeout -k 10 600 python bench.py --gpus 2 --steps 3 --warmup 1 --repeats 2 --exchange allreduce > $O/selflaunch_2ranks_allreduce_gloo.json 2> $O/selflaunch_2a.err
+timeout -k 10 600 python bench.py --full --gpus 2 --steps 3 --warmup 1 --repeats 2 --exchange allreduce > $O/selflaunch_2ranks_allreduce_gloo.json 2> $O/selflaunch_2a.err
 unset PYC2RAY_AMD_BENCH_BACKEND PYC2RAY_AMD_BENCH_DEVICE
 timeout -k 10 300 python tools/slab_compute_model.py --chunks 1 > $O/slab_compute_model_cosmo.json 2> $O/slab_model.err; echo "slab model exit $?"
 timeout -k 10 500 python tools/slab_compute_model.py --N 512 --nsrc 100000 --reps 2 --chunks 1 > $O/slab_compute_model_cfg4.json 2>> $O/slab_model.err
