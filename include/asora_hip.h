@@ -124,7 +124,8 @@ enum {
     ASORA_GRID_XH = 4,          /* ionised fraction at start of the step                */
     ASORA_GRID_XH_INTERMED = 5, /* end-of-step ionised fraction                         */
     ASORA_GRID_PHI_HEAT = 6,    /* photo-heating rate (only filled when heating is on)  */
-    ASORA_GRID_COUNT = 7
+    ASORA_GRID_TEMP_END = 7,    /* end-of-step temperature (thermal mode only)          */
+    ASORA_GRID_COUNT = 8
 };
 
 /* Upload / download one N^3 grid.  order = 'C': buffer is logical [i][j][k] C-contiguous;
@@ -281,6 +282,26 @@ int asora_evolve_slab_close(const double *host_sums);
  * What multi-GPU ranks exchange are such runs: the planes a rank's sources reach, the planes whose chemistry it owns. */
 int asora_planes_to_host(int which, int i_begin, int i_count, double *host);
 int asora_planes_to_device(int which, int i_begin, int i_count, const double *host);
+
+/* Non-isothermal chemistry ("Thermal mode").  enable != 0 switches asora_chemistry_device and the
+ * asora_evolve_* loop to the thermal form: per cell the temperature is integrated over the step from photo-heating
+ * (ASORA_GRID_PHI_HEAT, erg/s per HI atom) and radiative cooling inside do_chemistry's inner iteration
+ * (src/c2ray/chemistry.f90:164,171-176,182-189); TEMP holds the start-of-step temperature and stays untouched, the
+ * end-of-step temperature goes to ASORA_GRID_TEMP_END.  The device loop traces with heating into accumulators of its
+ * own and asora_evolve_poll folds the last iteration's heating into PHI_HEAT.
+ *   relative_denergy  largest relative change of the thermal energy per substep (> 0)
+ *   t_floor           lower bound of the temperature (K, >= 0)
+ *   max_substeps      substeps per integration (>= 1); the last one takes the remainder of the step
+ *   cooling_mask      bit 0 recombination, 1 collisional ionisation, 2 collisional excitation, 3 bremsstrahlung,
+ *                     4 Compton exchange with the CMB (only while `compton` != 0)
+ *   t_cmb             CMB temperature at the current redshift (K)
+ * Fails with code 4 when no heating tables are on the device (asora_heat_table_to_device) or grey opacity is on.
+ * enable = 0 returns to the isothermal form.  Single GPU: asora_evolve_begin_slab fails while thermal mode is on. */
+int asora_thermal_params(int enable, double relative_denergy, double t_floor, int max_substeps, unsigned cooling_mask,
+                         int compton, double t_cmb);
+/* Substep statistics of the thermal passes since the last asora_chemistry_device / asora_evolve_begin (summed over the
+ * passes of a step): cells whose integration hit max_substeps, cells clamped to t_floor, most substeps of one integration. */
+int asora_thermal_stats(long long *cells_max_substeps, long long *cells_floored, int *max_substeps_used);
 
 /* ------------------------------------------------------------------------------------------ */
 /* C. Options, measurement and diagnostics                                                     */

@@ -15,6 +15,8 @@ Differences from the reference:
   * ``use_mpi`` may be ``pyc2ray_amd.dist.MPI`` (torch.distributed/RCCL) as well as mpi4py's ``MPI``.
   * ``device_resident`` (default True; single GPU): ``ndens``, ``temp``, ``xh`` and ``phi_ion`` stay on the MI355X
     between time steps and cross PCIe only when the host touches them; see :class:`C2Ray`.
+  * ``Material: isothermal: false`` (optional key, default true) evolves the temperature from photo-heating and radiative
+    cooling (pyc2ray_amd/thermal.py); it needs ``compute_heating_rates: 1``, ``use_gpu`` and no ``use_mpi``.
 """
 import atexit
 import re
@@ -33,6 +35,7 @@ from .evolve import evolve3D, evolve3D_MPI, evolve3D_resident
 from .load_extensions import load_asora
 from .radiation import BlackBodySource, make_tau_table
 from .raytracing import do_raytracing
+from .thermal import ThermalParams
 from .utils.logutils import printlog
 
 __all__ = ['C2Ray', 'FlatLambdaCDMLite', 'YEAR', 'Mpc']
@@ -122,7 +125,7 @@ class _DeviceGrid:
         if self.name in obj._device_newer:                   # results of the last step(s) still only on the device
             lib = load_asora()
             order = 'F' if (arr.flags.f_contiguous and not arr.flags.c_contiguous) else 'C'
-            if self.name in ("xh", "phi_ion"):
+            if self.name in ("xh", "phi_ion", "temp"):      # (temp: only a non-isothermal run changes it on the device)
                 # into a FRESH array, as the reference binds a fresh array per step (c2ray_base.py:205-226): a caller that keeps
                 # `prev = sim.xh` or appends sim.xh to a history must not see it change under its feet
                 arr = lib.grid_to_host(self.which, lib.host_empty(arr.shape, order=order))
@@ -188,6 +191,7 @@ class C2Ray:
             self.nprocs = 1
 
         self._read_paramfile(paramfile)
+        self._thermal_mode_init(use_gpu, use_mpi)
         self.N = Nmesh
         self.shape = (Nmesh, Nmesh, Nmesh)
 
@@ -226,10 +230,39 @@ class C2Ray:
         t2 = self._lookback_s(z2)
         return (t1 - t2) / num_timesteps
 
+    def _thermal_mode_init(self, use_gpu, use_mpi):
+        """The optional key ``Material: isothermal`` (absent: true, the reference's behaviour).  A non-isothermal run evolves
+        the temperature from the photo-heating rates, which only the single-GPU path computes."""
+        self.isothermal = bool(self._ld.get('Material', {}).get('isothermal', True))
+        if self.isothermal:
+            return
+        if not self._ld.get('Photo', {}).get('compute_heating_rates', 0):
+            raise ValueError("Material: isothermal: false needs the photo-heating rates (Photo: compute_heating_rates: 1)")
+        if not use_gpu:
+            raise ValueError("Material: isothermal: false needs use_gpu=True (the use_gpu=False raytracer has no thermal form)")
+        if use_mpi:
+            raise ValueError("Material: isothermal: false is single-GPU only (no use_mpi)")
+
+    def _thermal_params(self):
+        """The ThermalParams of the current step (None when isothermal); Compton exchange with the CMB at self.zred in
+        cosmological runs."""
+        if self.isothermal:
+            return None
+        return ThermalParams(self.heat_thin_table, self.heat_thick_table,
+                             zred=float(self.zred) if self.cosmological else None,
+                             tcmb0=float(self._ld['Cosmology']['cmbtemp']))
+
     def evolve3D(self, dt, src_flux, src_pos):
         """Evolve the grid over one time step (c2ray_base.py:170-226)."""
         if self.device_resident and self.gpu and not self.mpi:
             return self._evolve3D_resident(dt, src_flux, src_pos)
+        if not self.isothermal:
+            self.xh, self.phi_ion, self.temp = evolve3D(
+                dt, self.dr, src_flux, src_pos, self.gpu, self.max_subbox, self.subboxsize, self.loss_fraction, self.temp,
+                self.ndens, self.xh, self.photo_thin_table, self.photo_thick_table, self.minlogtau, self.dlogtau,
+                self.R_max_LLS, self.convergence_fraction, self.sig, self.bh00, self.albpow, self.colh0, self.temph0,
+                self.abu_c, self.logfile, thermal=self._thermal_params())
+            return
         args = (self.temp, self.ndens, self.xh, self.photo_thin_table, self.photo_thick_table, self.minlogtau,
                 self.dlogtau, self.R_max_LLS, self.convergence_fraction, self.sig, self.bh00, self.albpow,
                 self.colh0, self.temph0, self.abu_c, self.logfile)
@@ -295,9 +328,9 @@ class C2Ray:
             d["_grid_phi_ion"] = np.zeros(self.shape)           # the GPU path returns C-ordered rates (evolve.py:200)
         evolve3D_resident(dt, self.dr, src_flux, src_pos, uploads, self.N, self.photo_thin_table, self.minlogtau, self.dlogtau,
                           self.R_max_LLS, self.convergence_fraction, self.sig, self.bh00, self.albpow, self.colh0, self.temph0,
-                          self.abu_c, self.logfile)
+                          self.abu_c, self.logfile, thermal=self._thermal_params())
         self._host_newer -= {"ndens", "temp", "xh", "phi_ion"}
-        self._device_newer |= {"xh", "phi_ion"}
+        self._device_newer |= {"xh", "phi_ion"} if self.isothermal else {"xh", "phi_ion", "temp"}
 
     def cosmo_evolve(self, dt):
         """Advance time and redshift by dt, diluting density and rescaling the cell size when the run is
@@ -316,6 +349,15 @@ class C2Ray:
                 self._device_newer.add("ndens")
             else:
                 self.ndens *= dilution_factor
+            if not self.isothermal:
+                # adiabatic cooling of the gas with the expansion, T ~ (1+z)^2
+                cooling_factor = ((1 + z_half) / (1 + self.zred)) ** 2
+                if (self.device_resident and self.gpu and not self.mpi and cuda_is_init() and "temp" not in self._host_newer
+                        and "temp" in self.__dict__.get("_grid_fingerprints", {}) and not self._written_behind_the_attribute("temp")):
+                    load_asora().grid_scale(_capi.GRID_TEMP, cooling_factor)
+                    self._device_newer.add("temp")
+                else:
+                    self.temp *= cooling_factor
             self.dr = self.dr_c * self._scale_factor(z_half)
         self.zred = z_half
         self.time = t_after

@@ -139,12 +139,35 @@ static int ensure_heat_grid()
     return 0;
 }
 
+// Thermal mode only (asora_thermal_params): the end-of-step temperature, and the device loop's heating accumulators (two pairs
+// like State::acc, 4 N^3 doubles, zeroed when allocated).  An isothermal run allocates neither.
+static int ensure_temp_end_grid()
+{
+    State &st = g_state;
+    if (st.grid[ASORA_GRID_TEMP_END]) return 0;
+    ASORA_HIP_TRY(hipMalloc(&st.grid[ASORA_GRID_TEMP_END], st.ncell * sizeof(double)));
+    st.grid_valid[ASORA_GRID_TEMP_END] = false;
+    return 0;
+}
+static int ensure_heat_acc()
+{
+    State &st = g_state;
+    if (st.heat_acc) return 0;
+    ASORA_HIP_TRY(hipMalloc(&st.heat_acc, 4 * st.ncell * sizeof(double)));
+    ASORA_HIP_TRY(hipMemsetAsync(st.heat_acc, 0, 4 * st.ncell * sizeof(double), st.stream));
+    st.heat_clean[0] = st.heat_clean[1] = true;
+    return 0;
+}
+
 static int release_all()
 {
     State &st = g_state;
     auto drop = [](auto *&ptr) { if (ptr) { (void)hipFree(ptr); ptr = nullptr; } };
     // (the grids of the hot loop are parts of the arena; the heating grid is an allocation of its own)
     drop(st.grid[ASORA_GRID_PHI_HEAT]);
+    drop(st.grid[ASORA_GRID_TEMP_END]); drop(st.heat_acc); drop(st.th_stats_dev);
+    st.heat_clean[0] = st.heat_clean[1] = false;
+    st.th_on = false; st.th = ThermalConsts();
     for (int g = 0; g < ASORA_GRID_COUNT; ++g) { st.grid[g] = nullptr; st.grid_valid[g] = false; }
     st.nhi = st.staging = st.acc = nullptr;
     drop(st.arena); st.arena_bytes = 0;
@@ -826,7 +849,7 @@ int asora_device_init_ex(int N, int num_src_par, int device_id)
         st.staging = take(1);
     }
     for (int g = 0; g < ASORA_GRID_COUNT; ++g)
-        if (g != ASORA_GRID_PHI_HEAT && !st.grid[g]) return fail(11, "device_init: a grid without a place in the arena (internal error)");
+        if (g != ASORA_GRID_PHI_HEAT && g != ASORA_GRID_TEMP_END && !st.grid[g]) return fail(11, "device_init: a grid without a place in the arena (internal error)");
     st.nhi_t = st.nhi + st.ncell;
     st.phi_t = st.grid[ASORA_GRID_PHI_ION] + st.ncell;
     st.heat_t = nullptr;
@@ -869,6 +892,7 @@ int asora_grid_to_device(int which, const double *host, int N, char order)
     if (!host) return fail(3, "grid_to_device: null host pointer");
     State &st = g_state;
     if (which == ASORA_GRID_PHI_HEAT) { if (int rc = ensure_heat_grid()) return rc; }
+    if (which == ASORA_GRID_TEMP_END) { if (int rc = ensure_temp_end_grid()) return rc; }
     st.zero_since_probe = std::max(st.zero_since_probe, 48);   // new medium: look again for cells beyond the table soon (launch_raytrace: at 64)
     const size_t bytes = st.ncell * sizeof(double);
     if (order == 'C' || order == 'c') {
@@ -914,6 +938,7 @@ int asora_grid_copy(int dst, int src)
     State &st = g_state;
     if (!st.grid_valid[src]) return fail(3, "grid_copy: source grid holds no data");
     if (dst == ASORA_GRID_PHI_HEAT) { if (int rc = ensure_heat_grid()) return rc; }
+    if (dst == ASORA_GRID_TEMP_END) { if (int rc = ensure_temp_end_grid()) return rc; }
     ASORA_HIP_TRY(hipMemcpyAsync(st.grid[dst], st.grid[src], st.ncell * sizeof(double), hipMemcpyDeviceToDevice,
                                  st.stream));
     st.grid_valid[dst] = true;
@@ -1170,6 +1195,11 @@ int asora_chemistry_device(double dt, double bh00, double albpow, double colh0, 
     static const int need[] = {ASORA_GRID_NDENS, ASORA_GRID_TEMP, ASORA_GRID_XH, ASORA_GRID_XH_AV, ASORA_GRID_PHI_ION};
     for (int g : need)
         if (!st.grid_valid[g]) return fail(4, "chemistry_device: grid " + std::to_string(g) + " holds no data");
+    if (st.th_on) {      // thermal form: the heating rates in, the end-of-step temperature out
+        if (!st.grid[ASORA_GRID_PHI_HEAT] || !st.grid_valid[ASORA_GRID_PHI_HEAT])
+            return fail(4, "chemistry_device: thermal mode needs the heating rates (ASORA_GRID_PHI_HEAT) on the device");
+        if (int rc = ensure_temp_end_grid()) return rc;
+    }
     st.grid_valid[ASORA_GRID_XH_INTERMED] = true;
     ChemParams p;
     p.ncell = st.ncell;
@@ -1178,6 +1208,12 @@ int asora_chemistry_device(double dt, double bh00, double albpow, double colh0, 
     p.phi = st.grid[ASORA_GRID_PHI_ION];
     p.xh_av = st.grid[ASORA_GRID_XH_AV]; p.xh_intermed = st.grid[ASORA_GRID_XH_INTERMED];
     p.red_partial = st.red_partial; p.red_final = st.red_final; p.red_blocks = st.red_blocks;
+    if (st.th_on) {
+        p.thermal = true; p.th = st.th;
+        p.phi_heat = st.grid[ASORA_GRID_PHI_HEAT]; p.temp_end = st.grid[ASORA_GRID_TEMP_END]; p.th_stats = st.th_stats_dev;
+        ASORA_HIP_TRY(hipMemsetAsync(st.th_stats_dev, 0, 3 * sizeof(unsigned long long), st.stream));
+        st.grid_valid[ASORA_GRID_TEMP_END] = true;
+    }
     if (int rc = launch_chemistry(st, p, st.stream)) return rc;
     ASORA_HIP_TRY(hipMemcpyAsync(st.red_host, st.red_final, sizeof(double) * 3, hipMemcpyDeviceToHost, st.stream));
     ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
@@ -1193,6 +1229,7 @@ int asora_chemistry_range(double dt, double bh00, double albpow, double colh0, d
     clear_error();
     if (int rc = require_init("chemistry_range")) return rc;
     State &st = g_state;
+    if (st.th_on) return fail(4, "chemistry_range: not available in thermal mode (single GPU: asora_chemistry_device or asora_evolve_*)");
     // (xh_intermed is only ever written by the pass: chemistry.f90:107)
     static const int need[] = {ASORA_GRID_NDENS, ASORA_GRID_TEMP, ASORA_GRID_XH, ASORA_GRID_XH_AV, ASORA_GRID_PHI_ION};
     for (int g : need)
@@ -1423,6 +1460,8 @@ static int evolve_begin_impl(double dt, double bh00, double albpow, double colh0
     if (int rc = require_init("evolve_begin")) return rc;
     State &st = g_state;
     st.ev_open = false;
+    if (slab && st.th_on)
+        return fail(4, "evolve_begin_slab: thermal mode is single-GPU only (asora_thermal_params(0, ...) first)");
     if (slab) {
         if (own_begin < 0 || own_count < 0 || own_begin + own_count > st.N) return fail(4, "evolve_begin_slab: bad range of own planes");
         if (!st.opt[ASORA_OPT_Z_TRANSPOSED]) return fail(4, "evolve_begin_slab: needs the [k][j][i] twins (ASORA_OPT_Z_TRANSPOSED = 1)");
@@ -1437,6 +1476,14 @@ static int evolve_begin_impl(double dt, double bh00, double albpow, double colh0
     if (src_begin < 0 || src_count < 0 || src_begin + src_count > st.num_src)
         return fail(4, "evolve_begin: source range outside the " + std::to_string(st.num_src) + " uploaded sources");
     if (st.opt[ASORA_OPT_HEATING]) return fail(4, "evolve_begin: the fused loop carries no heating rates (use raytrace_device)");
+    if (st.th_on) {
+        if (!st.have_heat_tables || st.opt[ASORA_OPT_GREY_NOTABLES])
+            return fail(4, "evolve_begin: thermal mode needs heating tables on the device (heat_table_to_device)");
+        if (!st.opt[ASORA_OPT_Z_TRANSPOSED]) return fail(4, "evolve_begin: thermal mode needs the [k][j][i] twins (ASORA_OPT_Z_TRANSPOSED = 1)");
+        if (int rc = ensure_heat_grid()) return rc;
+        if (int rc = ensure_temp_end_grid()) return rc;
+        if (int rc = ensure_heat_acc()) return rc;
+    }
 
     if (int rc = ensure_temp_probe(bh00, albpow, colh0, temph0)) return rc;
     const size_t bytes = st.ncell * sizeof(double);
@@ -1501,6 +1548,15 @@ static int evolve_begin_impl(double dt, double bh00, double albpow, double colh0
     }
     if (!st.ev_clean[0] && !st.ev_clean[1]) return fail(11, "evolve_begin: no clean accumulator pair (internal error)");
     st.ev_base = st.ev_clean[0] ? 0 : 1;
+    if (st.th_on) {
+        // the heating pairs start every thermal step all zero (the pass zeroes only the lines the step's sources reach)
+        for (int q = 0; q < 2; ++q)
+            if (!st.heat_clean[q]) {
+                ASORA_HIP_TRY(hipMemsetAsync(st.heat_acc + (size_t)q * 2 * st.ncell, 0, 2 * bytes, st.stream));
+                st.heat_clean[q] = true;
+            }
+        ASORA_HIP_TRY(hipMemsetAsync(st.th_stats_dev, 0, 3 * sizeof(unsigned long long), st.stream));
+    }
     st.ev_folded_iter = 0;
     if (!st.ev_status) {
         ASORA_HIP_TRY(hipMalloc(&st.ev_status, sizeof(EvolveStatus)));
@@ -1767,10 +1823,13 @@ int asora_evolve_enqueue(int iterations)
         // iteration k = ev_enqueued + it + 1 of the step (as long as the step has not converged: then nothing runs anyway)
         const int set = (st.ev_base + st.ev_enqueued + it) & 1;
         double *acc_cur = st.acc + (size_t)set * 2 * st.ncell, *acc_next = st.acc + (size_t)(set ^ 1) * 2 * st.ncell;
+        double *heat_cur = st.th_on ? st.heat_acc + (size_t)set * 2 * st.ncell : nullptr;
+        double *heat_next = st.th_on ? st.heat_acc + (size_t)(set ^ 1) * 2 * st.ncell : nullptr;
         if (st.ev_src_count > 0) {
             RtParams p = st.ev_rt;
             p.phi = acc_cur;
-            if (int rc = launch_raytrace(st, p, false, false)) return rc;
+            if (st.th_on) p.heat = heat_cur;          // thermal mode: the HEAT forms, into the iteration's heating pair
+            if (int rc = launch_raytrace(st, p, false, st.th_on)) return rc;
         }
         ChemTileParams c;
         c.N = st.N; c.i_begin = 0; c.i_end = st.N;
@@ -1791,8 +1850,19 @@ int asora_evolve_enqueue(int iterations)
         c.status = st.ev_status;
         c.fold = true; c.emit = true;
         set_uniform_temperature(c);
+        if (st.th_on) {
+            c.thermal = true; c.uniform = 0; c.th = st.th;
+            c.heat = heat_cur; c.heat_t = heat_cur + st.ncell;
+            c.zero_ha = heat_next; c.zero_ht = heat_next + st.ncell;
+            c.temp_end = st.grid[ASORA_GRID_TEMP_END]; c.th_stats = st.th_stats_dev;
+        }
         if (int rc = launch_chemistry_tiles(st, c, st.stream)) return rc;
         st.ev_first = false;
+    }
+    if (st.th_on) {
+        st.heat_clean[0] = st.heat_clean[1] = false;     // until the poll tells which pair the last iteration used
+        st.grid_valid[ASORA_GRID_TEMP_END] = true;
+        st.grid_valid[ASORA_GRID_PHI_HEAT] = false;
     }
     st.ev_enqueued += iterations;
     st.grid_valid[ASORA_GRID_XH_AV] = st.grid_valid[ASORA_GRID_XH_INTERMED] = true;
@@ -1817,10 +1887,18 @@ int asora_evolve_poll(int *niter, int *converged, double *history, int history_r
         if (st.ev_folded_iter != h.niter) {
             const double *a = st.acc + (size_t)set * 2 * st.ncell;
             if (int rc = launch_fold_sum(st, a, a + st.ncell, st.grid[ASORA_GRID_PHI_ION])) return rc;
+            if (st.th_on && !st.ev_slab) {       // thermal mode: the last iteration's heating as well
+                const double *hsum = st.heat_acc + (size_t)set * 2 * st.ncell;
+                if (int rc = launch_fold_sum(st, hsum, hsum + st.ncell, st.grid[ASORA_GRID_PHI_HEAT])) return rc;
+            }
             st.ev_folded_iter = h.niter;
         }
         st.grid_valid[ASORA_GRID_PHI_ION] = true;
         st.ev_clean[set] = false; st.ev_clean[set ^ 1] = true;
+        if (st.th_on && !st.ev_slab) {
+            st.grid_valid[ASORA_GRID_PHI_HEAT] = true;
+            st.heat_clean[set] = false; st.heat_clean[set ^ 1] = true;
+        }
     }
     st.ev_sets_known = true;
     int rows = 0;
@@ -1833,6 +1911,46 @@ int asora_evolve_poll(int *niter, int *converged, double *history, int history_r
     if (rows_written) *rows_written = rows;
     if (niter) *niter = h.niter;
     if (converged) *converged = h.done;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Thermal mode (include/asora_hip.h; chemistry.hip: chemistry_cell_thermal)
+// ---------------------------------------------------------------------------------------------
+int asora_thermal_params(int enable, double relative_denergy, double t_floor, int max_substeps, unsigned cooling_mask,
+                         int compton, double t_cmb)
+{
+    clear_error();
+    if (int rc = require_init("thermal_params")) return rc;
+    State &st = g_state;
+    if (!enable) { st.th_on = false; return 0; }
+    if (!st.have_heat_tables || st.opt[ASORA_OPT_GREY_NOTABLES])
+        return fail(4, "thermal_params: thermal mode needs heating tables on the device (heat_table_to_device) and table rates");
+    if (!(relative_denergy > 0.0) || !(t_floor >= 0.0) || max_substeps < 1 || !(t_cmb >= 0.0) || cooling_mask > 31u)
+        return fail(3, "thermal_params: need relative_denergy > 0, t_floor >= 0, max_substeps >= 1, t_cmb >= 0, cooling_mask < 32");
+    if (!st.th_stats_dev) {
+        ASORA_HIP_TRY(hipMalloc(&st.th_stats_dev, 3 * sizeof(unsigned long long)));
+        ASORA_HIP_TRY(hipMemsetAsync(st.th_stats_dev, 0, 3 * sizeof(unsigned long long), st.stream));
+    }
+    st.th.relative_denergy = relative_denergy; st.th.t_floor = t_floor; st.th.max_substeps = max_substeps;
+    st.th.cooling_mask = cooling_mask; st.th.compton = compton ? 1 : 0; st.th.t_cmb = t_cmb;
+    st.th_on = true;
+    return 0;
+}
+
+int asora_thermal_stats(long long *cells_max_substeps, long long *cells_floored, int *max_substeps_used)
+{
+    clear_error();
+    if (int rc = require_init("thermal_stats")) return rc;
+    State &st = g_state;
+    unsigned long long h[3] = {0, 0, 0};
+    if (st.th_stats_dev) {
+        ASORA_HIP_TRY(hipMemcpyAsync(h, st.th_stats_dev, sizeof h, hipMemcpyDeviceToHost, st.stream));
+        ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
+    }
+    if (cells_max_substeps) *cells_max_substeps = (long long)h[0];
+    if (cells_floored) *cells_floored = (long long)h[1];
+    if (max_substeps_used) *max_substeps_used = (int)h[2];
     return 0;
 }
 
@@ -1865,6 +1983,7 @@ int asora_planes_to_device(int which, int i_begin, int i_count, const double *ho
     if (i_count == 0) return 0;
     if (!host) return fail(3, "planes_to_device: null host pointer");
     if (which == ASORA_GRID_PHI_HEAT) { if (int rc = ensure_heat_grid()) return rc; }
+    if (which == ASORA_GRID_TEMP_END) { if (int rc = ensure_temp_end_grid()) return rc; }
     const size_t plane = (size_t)st.N * st.N;
     ASORA_HIP_TRY(hipMemcpyAsync(st.grid[which] + (size_t)i_begin * plane, host, (size_t)i_count * plane * sizeof(double),
                                  hipMemcpyHostToDevice, st.stream));

@@ -91,6 +91,18 @@ struct RtParams {
     double *sb_trail;           // per (source, unit): the last shell swept, handed to the next sub-box's launch
 };
 
+// Constants of the thermal form of the chemistry pass (asora_thermal_params; chemistry.hip: thermal_integrate)
+struct ThermalConsts {
+    double relative_denergy = 0.1;   // largest relative change of the thermal energy per substep
+    double t_floor = 1.0;            // K
+    double t_cmb = 0.0;              // K, at the current redshift
+    int max_substeps = 10000;
+    unsigned cooling_mask = 31u;     // THERMAL_COOL_* bits
+    int compton = 0;                 // Compton exchange only with a redshift
+};
+constexpr unsigned THERMAL_COOL_RECOMB = 1u, THERMAL_COOL_COLION = 2u, THERMAL_COOL_COLEXC = 4u, THERMAL_COOL_BREMS = 8u,
+                   THERMAL_COOL_COMPTON = 16u;
+
 // Device-side bookkeeping of the evolve loop (asora_evolve_begin / _enqueue / _poll): the convergence test of
 // pyc2ray/evolve.py:216-236 is evaluated on the device right behind the chemistry reductions, so that several outer
 // iterations can be enqueued at once; launches that come after convergence see `done` and do nothing.
@@ -115,8 +127,8 @@ struct State {
     int num_src_par = 0;           // accepted, unused (no per-source N^3 scratch in this build)
     int cu_count = 256;
 
-    double *grid[ASORA_GRID_COUNT] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    bool grid_valid[ASORA_GRID_COUNT] = {false, false, false, false, false, false, false};
+    double *grid[ASORA_GRID_COUNT] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool grid_valid[ASORA_GRID_COUNT] = {false, false, false, false, false, false, false, false};
 
     // derived per raytrace call
     // each of these is the second half of a 2 N^3 allocation whose first half is the [i][j][k] grid
@@ -262,6 +274,13 @@ struct State {
     double reach_R = -1.0;
     long src_generation = 0;                // counts asora_source_data_to_device calls
 
+    // thermal mode (asora_thermal_params): TEMP_END and the heating accumulators of the device loop are allocated on first use
+    bool th_on = false;
+    ThermalConsts th;
+    double *heat_acc = nullptr;             // two pairs like `acc`, [i][j][k] then [k][j][i] each (4 N^3 doubles)
+    bool heat_clean[2] = {false, false};    // pair known to be all zero
+    unsigned long long *th_stats_dev = nullptr;   // [3]: cells at max_substeps, cells floored, most substeps
+
     hipStream_t stream = nullptr;
     struct PendingTimer { int which; hipEvent_t e0, e1; };
     std::vector<PendingTimer> pending_timers;     // recorded, not yet resolved
@@ -380,6 +399,12 @@ struct ChemParams {
     double *red_partial, *red_final;
     int red_blocks;
     int accumulate = 0;        // 1: add this launch's reductions to red_final (slab-wise passes) instead of replacing it
+    // thermal form (launch_chemistry with `thermal`): heating rate per HI atom in, end-of-step temperature out
+    bool thermal = false;
+    const double *phi_heat = nullptr;
+    double *temp_end = nullptr;
+    unsigned long long *th_stats = nullptr;
+    ThermalConsts th;
 };
 int launch_chemistry(State &st, ChemParams &p, hipStream_t stream);
 int chemistry_reduction_blocks(const State &st);
@@ -410,6 +435,13 @@ struct ChemTileParams {
     // the grid has one temperature (launch_temp_probe): its factors, evaluated on the device, travel with the parameters
     int uniform = 0, uniform_t_ok = 0;
     double uniform_T = 0, uniform_brech0 = 0, uniform_acolh0 = 0;
+    // thermal form (fold + emit only): the heating accumulators are folded like the rates, the other heating pair zeroed
+    bool thermal = false;
+    double *heat = nullptr, *heat_t = nullptr;
+    double *zero_ha = nullptr, *zero_ht = nullptr;
+    double *temp_end = nullptr;
+    unsigned long long *th_stats = nullptr;
+    ThermalConsts th;
 };
 int launch_grid_sum(State &st, const double *a, size_t n, double *out_dev);
 int launch_scale(State &st, double *a, size_t n, double factor);

@@ -77,7 +77,159 @@ __device__ __forceinline__ void chemistry_cell(const ChemParams &p, double n, do
         nconv += 1;                                                  // chemistry.f90:100-104
 }
 
+// ---------------------------------------------------------------------------------------------
+// Thermal form (asora_thermal_params; DESIGN.md "Thermal mode"): the temperature of a cell is integrated over the step from
+// photo-heating and radiative cooling inside do_chemistry's inner iteration, where the reference keeps the placeholders
+// (chemistry.f90:164 ini_rec_colion_factors, :171-176 thermal, :182-189 the temperature term of the exit test).
+// Contraction into FMA is off in these functions: tests/thermal_reference.py restates them in numpy, operation for operation.
+// ---------------------------------------------------------------------------------------------
+constexpr double THERMAL_KB = 1.381e-16;                       // erg/K, the rounded value of radiation/blackbody.py
+// Compton coupling 4 sigma_T a_rad k_B / (m_e c) from CODATA 2018 (cgs); pyc2ray_amd/thermal.py evaluates the same expression
+constexpr double CODATA_SIGMA_T = 6.6524587321e-25, CODATA_SIGMA_SB = 5.670374419e-5, CODATA_C = 2.99792458e10,
+                 CODATA_KB = 1.380649e-16, CODATA_ME = 9.1093837015e-28;
+constexpr double COMPTON_A_RAD = 4.0 * CODATA_SIGMA_SB / CODATA_C;
+constexpr double COMPTON_C = 4.0 * CODATA_SIGMA_T * COMPTON_A_RAD * CODATA_KB / (CODATA_ME * CODATA_C);
+
+// Lambda(T) in erg s^-1 cm^-3
+__device__ __forceinline__ double thermal_cooling(const ThermalConsts &c, double T, double n_e, double n_HII, double n_HI,
+                                                  double colh0, double temph0)
+{
+#pragma clang fp contract(off)
+    double L = 0.0;
+    if (c.cooling_mask & THERMAL_COOL_RECOMB) {            // case-B recombination, Hui & Gnedin (1997)
+        const double lam = 2.0 * 157807.0 / T;
+        L += 3.435e-30 * T * pow(lam, 1.970) / pow(1.0 + pow(lam / 2.25, 0.376), 3.720) * n_e * n_HII;
+    }
+    if (c.cooling_mask & THERMAL_COOL_COLION)              // collisional ionisation: doric's rate (chemistry.f90:262) x the ionisation energy
+        L += THERMAL_KB * temph0 * colh0 * sqrt(T) * exp(-temph0 / T) * n_e * n_HI;
+    if (c.cooling_mask & THERMAL_COOL_COLEXC)              // collisional excitation, Cen (1992)
+        L += 7.5e-19 * exp(-118348.0 / T) / (1.0 + sqrt(T / 1e5)) * n_e * n_HI;
+    if (c.cooling_mask & THERMAL_COOL_BREMS) {             // bremsstrahlung, Cen (1992)
+        const double u = 5.5 - log10(T);
+        const double gff = 1.1 + 0.34 * exp(-(u * u) / 3.0);
+        L += 1.42e-27 * gff * sqrt(T) * n_e * n_HII;
+    }
+    if ((c.cooling_mask & THERMAL_COOL_COMPTON) && c.compton) {   // Compton exchange with the CMB (heats below T_cmb)
+        const double tg = c.t_cmb;
+        L += COMPTON_C * ((tg * tg) * (tg * tg)) * (T - tg) * n_e;
+    }
+    return L;
+}
+
+struct ThermalTally {
+    unsigned capped = 0, floored = 0;   // cells
+    int max_sub = 0;
+};
+
+// thermal(T_start, x, phi_heat) -> (T_end, T_av): explicit substeps limited to a relative change `relative_denergy` of the
+// thermal energy 1.5 k_B n_p T, n_p held at its value for x; the last substep ends exactly at dt.
+__device__ __forceinline__ void thermal_integrate(const ThermalConsts &c, double dt, double abu_c, double colh0, double temph0,
+                                                  double n, double x, double phi_heat, double T_start, double &T_end,
+                                                  double &T_av, bool &capped, bool &floored, int &max_sub)
+{
+#pragma clang fp contract(off)
+    const double n_e = n * (x + abu_c), n_HII = n * x, n_HI = n * (1.0 - x);
+    const double n_p = n * (1.0 + x + abu_c);
+    const double cv = 1.5 * THERMAL_KB * n_p;
+    const double H = n_HI * phi_heat;
+    double T = T_start, e = cv * T_start, t = 0.0, intT = 0.0;
+    int k = 0;
+    for (;;) {
+        k += 1;
+        const double r = H - thermal_cooling(c, T, n_e, n_HII, n_HI, colh0, temph0);
+        double h = dt - t;
+        bool last = true;
+        if (k < c.max_substeps && r != 0.0) {
+            const double hl = c.relative_denergy * e / fabs(r);
+            if (hl < h) { h = hl; last = false; }
+        }
+        double Tn = (e + h * r) / cv;
+        if (Tn < c.t_floor) { Tn = c.t_floor; floored = true; }
+        e = cv * Tn;
+        intT += h * (T + Tn) * 0.5;
+        T = Tn;
+        if (last) break;
+        t += h;
+    }
+    if (k >= c.max_substeps) capped = true;
+    if (k > max_sub) max_sub = k;
+    T_end = T;
+    T_av = intT / dt;
+}
+
+// One cell of the thermal pass: do_chemistry with the placeholders filled in, + the convergence test of evolve0D_global.
+// The rate factors follow the average temperature of the previous inner iteration (T_start for the first); the exit test
+// takes the change of the end-of-step temperature as well.
+// (the loop state lives in locals; the references are written once, at the end)
+__device__ __forceinline__ void chemistry_cell_thermal(const ChemParams &p, double n, double x0, double gamma, double phi_heat,
+                                                       double T_start, double &xav_io, double &xint_out, double &T_end_out,
+                                                       unsigned int &nconv, ThermalTally &tally)
+{
+#pragma clang fp contract(off)
+    const double min_frac_change = (double)1.0e-3f;
+    const double min_frac_atoms = (double)1.0e-8f;
+    const double eps = 1e-14;
+
+    double xav = xav_io, xint = 0.0;
+    const double xav_start = xav;
+    const double yh_av = 1.0 - xav;
+    double T_av = T_start, T_end = T_start;
+    bool capped = false, floored = false;
+    int max_sub = tally.max_sub;
+
+    int nit = 0;
+    for (;;) {
+        nit += 1;
+        const double xav_old = xav, T_prev = T_end;
+        const double de = n * (xav + p.abu_c);
+        const double brech0 = 1.0 * p.bh00 * pow(T_av / 1e4, p.albpow);     // ini_rec_colion_factors(T_av)
+        const double acolh0 = p.colh0 * sqrt(T_av) * exp(-p.temph0 / T_av);
+        const double aih0 = gamma + de * acolh0;
+        const double delth = aih0 + de * brech0;
+        const double eqxh = aih0 / delth;
+        const double deltht = delth * p.dt;
+        const double ee = exp(-deltht);
+        xint = (x0 - eqxh) * ee + eqxh;
+        if (xint < eps) xint = eps;
+        const double avg = (deltht < (double)1.0e-8f) ? 1.0 : (1.0 - ee) / deltht;
+        xav = eqxh + (x0 - eqxh) * avg;
+        if (xav < eps) xav = eps;
+        thermal_integrate(p.th, p.dt, p.abu_c, p.colh0, p.temph0, n, xav, phi_heat, T_start, T_end, T_av, capped, floored,
+                          max_sub);
+        const bool t_ok = fabs((T_end - T_prev) / T_end) < min_frac_change;
+        if ((fabs((xav - xav_old) / (1.0 - xav)) < min_frac_change || (1.0 - xav < min_frac_atoms)) && t_ok)
+            break;
+        if (nit > 400) break;
+    }
+    if (fabs(xav - xav_start) > min_frac_change && fabs((xav - xav_start) / yh_av) > min_frac_change &&
+        yh_av > min_frac_atoms)
+        nconv += 1;
+    tally.capped += capped ? 1u : 0u;
+    tally.floored += floored ? 1u : 0u;
+    tally.max_sub = max_sub;
+    xav_io = xav; xint_out = xint; T_end_out = T_end;
+}
+
+// the lanes' tallies into stats[3] = {cells at max_substeps, cells floored, most substeps}: one atomic per wave and field
+__device__ __forceinline__ void thermal_tally_flush(unsigned long long *stats, ThermalTally t)
+{
+    unsigned c = t.capped, f = t.floored;
+    int m = t.max_sub;
+    for (int o = 32; o > 0; o >>= 1) {
+        c += __shfl_xor(c, o);
+        f += __shfl_xor(f, o);
+        m = max(m, __shfl_xor(m, o));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (c) atomicAdd(&stats[0], (unsigned long long)c);
+        if (f) atomicAdd(&stats[1], (unsigned long long)f);
+        atomicMax(&stats[2], (unsigned long long)m);
+    }
+}
+
 // Two consecutive cells per lane: 16-byte loads and stores (the grids are 256-byte aligned).
+// THERMAL: chemistry_cell_thermal, with the heating rates and the start temperature in and the end temperature out.
+template <bool THERMAL>
 __global__ void __launch_bounds__(CH_THREADS) chemistry_kernel(const ChemParams p)
 {
     double sum1 = 0.0, sum0 = 0.0;
@@ -92,7 +244,21 @@ __global__ void __launch_bounds__(CH_THREADS) chemistry_kernel(const ChemParams 
     const double2 *ph2 = reinterpret_cast<const double2 *>(p.phi);
     double2 *xa2 = reinterpret_cast<double2 *>(p.xh_av);
     double2 *xi2 = reinterpret_cast<double2 *>(p.xh_intermed);
-    for (size_t q = (size_t)blockIdx.x * CH_THREADS + threadIdx.x; q < npair; q += stride) {
+    ThermalTally tally;
+    if (THERMAL) {
+        // one cell per lane and trip, the loop kept rolled: ONE inlined copy of the thermal cell (the pair form of the loop
+        // below, with two copies, gave wrong results for the second cell of a pair on gfx950)
+#pragma unroll 1
+        for (size_t i = (size_t)blockIdx.x * CH_THREADS + threadIdx.x; i < p.ncell; i += stride) {
+            double xav = p.xh_av[i], xint, te;
+            chemistry_cell_thermal(p, p.ndens[i], p.xh[i], p.phi[i], p.phi_heat[i], p.temp[i], xav, xint, te, nconv, tally);
+            p.xh_intermed[i] = xint;
+            p.xh_av[i] = xav;
+            p.temp_end[i] = te;
+            sum1 += xint; sum0 += 1.0 - xint;
+        }
+    }
+    for (size_t q = (size_t)blockIdx.x * CH_THREADS + threadIdx.x; !THERMAL && q < npair; q += stride) {
         const double2 n = nd2[q], T = tp2[q], x0 = x02[q], g = ph2[q];
         double2 xav = xa2[q], xint;
         temperature_factors(p, T.x, tf);
@@ -104,7 +270,7 @@ __global__ void __launch_bounds__(CH_THREADS) chemistry_kernel(const ChemParams 
         sum1 += xint.x; sum0 += 1.0 - xint.x;                        // evolve.py:216-217
         sum1 += xint.y; sum0 += 1.0 - xint.y;
     }
-    if ((p.ncell & 1) && blockIdx.x == 0 && threadIdx.x == 0) {      // odd cell count: the last cell
+    if (!THERMAL && (p.ncell & 1) && blockIdx.x == 0 && threadIdx.x == 0) {      // odd cell count: the last cell
         const size_t idx = p.ncell - 1;
         double xav = p.xh_av[idx], xint;
         temperature_factors(p, p.temp[idx], tf);
@@ -113,6 +279,7 @@ __global__ void __launch_bounds__(CH_THREADS) chemistry_kernel(const ChemParams 
         p.xh_av[idx] = xav;
         sum1 += xint; sum0 += 1.0 - xint;
     }
+    if (THERMAL) thermal_tally_flush(p.th_stats, tally);
 
     // block reduction in a fixed order
     __shared__ double r1[CH_THREADS], r0[CH_THREADS];
@@ -214,11 +381,16 @@ __device__ __forceinline__ double stream_load(const double *q)
 #endif
 }
 
-template <bool FOLD, bool EMIT, bool UNIFORM_T>
+// THERMAL (with FOLD and EMIT, not UNIFORM_T): chemistry_cell_thermal; the heating accumulators are folded like the rates
+// (tile_h: their [k][j][i] twin), the other heating pair is zeroed for the next trace, the end temperature goes to temp_end.
+// Per cell 8 loads and 9 stores = 136 B.
+template <bool FOLD, bool EMIT, bool UNIFORM_T, bool THERMAL = false>
 __global__ void __launch_bounds__(CH_THREADS, ASORA_CHEM_MIN_WAVES) chemistry_tile_kernel(const ChemTileParams p)
 {
+    static_assert(!THERMAL || (FOLD && EMIT && !UNIFORM_T), "thermal pass: the device loop's fold + emit form only");
     if (p.status && p.status->done) return;
     __shared__ double tile_g[32][33], tile_n[32][33];
+    __shared__ double tile_h[THERMAL ? 32 : 1][33];
     __shared__ double r1[CH_THREADS], r0[CH_THREADS];
     __shared__ unsigned int rc[CH_THREADS];
 
@@ -228,9 +400,11 @@ __global__ void __launch_bounds__(CH_THREADS, ASORA_CHEM_MIN_WAVES) chemistry_ti
     const int kb = blockIdx.x * 32, ib = p.i_begin + blockIdx.z * 32;
     ChemParams cp;
     cp.dt = p.dt; cp.bh00 = p.bh00; cp.albpow = p.albpow; cp.colh0 = p.colh0; cp.temph0 = p.temph0; cp.abu_c = p.abu_c;
+    if (THERMAL) cp.th = p.th;
 
     double sum1 = 0.0, sum0 = 0.0;
     unsigned int nconv = 0;
+    ThermalTally tally;
     // UNIFORM_T: the whole grid has ONE temperature (probed when the grid was uploaded, temp_probe_kernel): its factors
     // come with the parameters -- no temperature load (96 B per cell instead of 104), no pow / sqrt / exp code in the
     // kernel (fewer registers: more waves in flight)
@@ -247,6 +421,10 @@ __global__ void __launch_bounds__(CH_THREADS, ASORA_CHEM_MIN_WAVES) chemistry_ti
                     const bool reached = !p.reach_t || p.reach_t[((size_t)k * N + j) * NL + (i >> 3)] != 0;
                     tile_g[r][tx] = reached ? stream_load(p.gamma_t + o) : 0.0;
                     if (EMIT && reached) p.zero_t[o] = 0.0;
+                    if (THERMAL) {
+                        tile_h[r][tx] = reached ? stream_load(p.heat_t + o) : 0.0;
+                        if (reached) p.zero_ht[o] = 0.0;
+                    }
                 }
             }
             __syncthreads();
@@ -262,8 +440,17 @@ __global__ void __launch_bounds__(CH_THREADS, ASORA_CHEM_MIN_WAVES) chemistry_ti
                 if (EMIT && reached) p.zero_a[idx] = 0.0;
                 const double n = stream_load(p.ndens + idx);
                 double xav = stream_load(p.xh_av_in + idx), xint;
-                if (!UNIFORM_T) temperature_factors(cp, stream_load(p.temp + idx), tf);
-                chemistry_cell(cp, n, stream_load(p.xh + idx), g, xav, xint, nconv, tf);
+                if (THERMAL) {
+                    double hr = reached ? stream_load(p.heat + idx) : 0.0;
+                    hr += tile_h[tx][r];
+                    if (reached) p.zero_ha[idx] = 0.0;
+                    double te;
+                    chemistry_cell_thermal(cp, n, stream_load(p.xh + idx), g, hr, stream_load(p.temp + idx), xav, xint, te, nconv, tally);
+                    p.temp_end[idx] = te;
+                } else {
+                    if (!UNIFORM_T) temperature_factors(cp, stream_load(p.temp + idx), tf);
+                    chemistry_cell(cp, n, stream_load(p.xh + idx), g, xav, xint, nconv, tf);
+                }
                 p.xh_intermed[idx] = xint;                           // chemistry.f90:107-108
                 p.xh_av[idx] = xav;
                 sum1 += xint; sum0 += 1.0 - xint;                    // evolve.py:216-217
@@ -283,6 +470,7 @@ __global__ void __launch_bounds__(CH_THREADS, ASORA_CHEM_MIN_WAVES) chemistry_ti
         }
     }
 
+    if (THERMAL) thermal_tally_flush(p.th_stats, tally);
     r1[threadIdx.x] = sum1; r0[threadIdx.x] = sum0; rc[threadIdx.x] = nconv;
     __syncthreads();
     for (int off = CH_THREADS / 2; off > 0; off >>= 1) {
@@ -425,7 +613,8 @@ int launch_chemistry(State &st, ChemParams &p, hipStream_t stream)
     q.red_blocks = blocks;
     {
         KernelTimer kt(ASORA_KERNEL_CHEMISTRY);
-        hipLaunchKernelGGL(chemistry_kernel, dim3(blocks), dim3(CH_THREADS), 0, stream, q);
+        if (p.thermal) hipLaunchKernelGGL(chemistry_kernel<true>, dim3(blocks), dim3(CH_THREADS), 0, stream, q);
+        else           hipLaunchKernelGGL(chemistry_kernel<false>, dim3(blocks), dim3(CH_THREADS), 0, stream, q);
         ASORA_HIP_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(chemistry_reduce_kernel, dim3(1), dim3(RED_THREADS), 0, stream,
@@ -463,7 +652,10 @@ int launch_chemistry_tiles(State &st, ChemTileParams &p, hipStream_t stream)
     {
         KernelTimer kt(ASORA_KERNEL_CHEMISTRY, stream);
         const bool u = p.uniform != 0;
-        if (p.fold && p.emit) {
+        if (p.thermal) {
+            if (!(p.fold && p.emit)) return fail(11, "chemistry: the thermal pass exists in the fold + emit form only (internal error)");
+            hipLaunchKernelGGL((chemistry_tile_kernel<true, true, false, true>), grid, dim3(CH_THREADS), 0, stream, q);
+        } else if (p.fold && p.emit) {
             if (u) hipLaunchKernelGGL((chemistry_tile_kernel<true, true, true>), grid, dim3(CH_THREADS), 0, stream, q);
             else   hipLaunchKernelGGL((chemistry_tile_kernel<true, true, false>), grid, dim3(CH_THREADS), 0, stream, q);
         } else if (!p.fold && !p.emit) {

@@ -215,13 +215,30 @@ def _device_loop(libasora, chem, R_max_LLS, sig, dr, minlogtau, dlogtau, NumTau,
     return niter, float(sum_xh1)
 
 
+def _thermal_loop(libasora, thermal, loop, logfile, quiet):
+    """Run `loop()` (a device loop of one step) in the library's thermal mode, and leave the library isothermal again."""
+    thermal.apply(libasora)
+    try:
+        result = loop()
+        capped, _floored, most = libasora.thermal_stats()
+    finally:
+        libasora.thermal_params(False)
+    if capped:
+        printlog(f"Warning: the temperature integration of {capped:n} cell(s) hit max_substeps = {thermal.max_substeps:n} "
+                 f"(most substeps used: {most:n}); their last substep took the rest of the time step.", logfile, quiet)
+    return result
+
+
 def evolve3D_resident(dt, dr, src_flux, src_pos, uploads, N, photo_thin_table, minlogtau, dlogtau, R_max_LLS,
-                      convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile="pyC2Ray.log", quiet=False):
+                      convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile="pyC2Ray.log", quiet=False,
+                      thermal=None):
     """evolve3D for a caller that keeps the grids on the device between time steps (the C2Ray class with
     ``device_resident = True``): same loop, log lines and results as :func:`evolve3D` with ``use_gpu=True``, but only the
     grids in ``uploads`` ({grid selector: host array}, those the caller changed on the host) cross PCIe, and nothing
     comes back: afterwards XH_INTERMED == XH == the new ionised fraction and PHI_ION the rates, on the device
-    (``libasora.grid_to_host`` fetches them when someone looks).  Returns the number of outer iterations."""
+    (``libasora.grid_to_host`` fetches them when someone looks).  Returns the number of outer iterations.
+    With ``thermal`` (a :class:`pyc2ray_amd.thermal.ThermalParams`) the temperature is evolved as well: TEMP holds the
+    end-of-step temperature afterwards, PHI_HEAT the heating rates."""
     if not cuda_is_init():
         raise RuntimeError("GPU not initialized. Please initialize it by calling device_init(N)")
     libasora = load_asora()
@@ -242,17 +259,21 @@ def evolve3D_resident(dt, dr, src_flux, src_pos, uploads, N, photo_thin_table, m
     mean_xh = libasora.grid_sum(_capi.GRID_XH) / NumCells
     printlog(f"Mean density (cgs): {mean_ndens:.3e}, Mean ionized fraction: {mean_xh:.3e}", logfile, quiet)
     printlog(f"Convergence Criterion (Number of points): {conv_criterion : n}", logfile, quiet, end='\n\n')
-    niter, _ = _device_loop(libasora, (dt, bh00, albpow, colh0, temph0, abu_c), R_max_LLS, sig, dr, minlogtau, dlogtau,
+    def loop():
+        return _device_loop(libasora, (dt, bh00, albpow, colh0, temph0, abu_c), R_max_LLS, sig, dr, minlogtau, dlogtau,
                             NumTau, NumSrc, conv_criterion, convergence_fraction, NumCells, logfile, quiet)
+    niter, _ = loop() if thermal is None else _thermal_loop(libasora, thermal, loop, logfile, quiet)
     printlog("Multiple source convergence reached.", logfile, quiet)
     libasora.grid_copy(_capi.GRID_XH, _capi.GRID_XH_INTERMED)       # the next step starts from the new ionised fraction
+    if thermal is not None:
+        libasora.grid_copy(_capi.GRID_TEMP, _capi.GRID_TEMP_END)    # ... and from the new temperature
     _evolve.last_niter = niter
     return niter
 
 
 def _evolve(dt, dr, src_flux, src_pos, use_gpu, temp, ndens, xh, photo_thin_table, minlogtau, dlogtau,
             R_max_LLS, convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile, quiet,
-            use_mpi=None, comm=None, rank=0, nprocs=1):
+            use_mpi=None, comm=None, rank=0, nprocs=1, thermal=None):
     if use_gpu and not cuda_is_init():
         raise RuntimeError("GPU not initialized. Please initialize it by calling device_init(N)")
     _residency.reclaim()              # this step overwrites device grids a resident C2Ray object may be relying on
@@ -330,8 +351,10 @@ def _evolve(dt, dr, src_flux, src_pos, use_gpu, temp, ndens, xh, photo_thin_tabl
 
     chem = (dt, bh00, albpow, colh0, temph0, abu_c)
     if not distributed:
-        niter, _ = _device_loop(libasora, chem, R_max_LLS, sig, dr, minlogtau, dlogtau, NumTau, NumSrc_local, conv_criterion,
+        def loop():
+            return _device_loop(libasora, chem, R_max_LLS, sig, dr, minlogtau, dlogtau, NumTau, NumSrc_local, conv_criterion,
                                 convergence_fraction, NumCells, logfile, quiet)
+        niter, _ = loop() if thermal is None else _thermal_loop(libasora, thermal, loop, logfile, quiet)
         converged = True
 
     if slab:
@@ -450,6 +473,9 @@ def _evolve(dt, dr, src_flux, src_pos, use_gpu, temp, ndens, xh, photo_thin_tabl
     xh_new = libasora.grid_to_host(_capi.GRID_XH_INTERMED, libasora.host_empty((N, N, N), order=like_xh))
     phi_ion = libasora.grid_to_host(_capi.GRID_PHI_ION, libasora.host_empty((N, N, N)))
     _evolve.last_niter = niter
+    if thermal is not None:
+        temp_new = libasora.grid_to_host(_capi.GRID_TEMP_END, libasora.host_empty((N, N, N), order=like_xh))
+        return xh_new, phi_ion, temp_new
     return xh_new, phi_ion
 
 
@@ -461,7 +487,7 @@ def evolve3D(dt, dr,
              minlogtau, dlogtau,
              R_max_LLS, convergence_fraction,
              sig, bh00, albpow, colh0, temph0, abu_c,
-             logfile="pyC2Ray.log", quiet=False):
+             logfile="pyC2Ray.log", quiet=False, *, thermal=None):
     """Evolve the ionised fraction of the whole grid over one time step.
 
     Parameters have the reference's meaning (pyc2ray/evolve.py:49-109): dt [s], dr [cm],
@@ -475,13 +501,22 @@ def evolve3D(dt, dr,
     Returns (xh_new, phi_ion): end-of-step ionised fraction (laid out like `xh`) and the summed
     photo-ionisation rate (C-ordered with use_gpu=True, Fortran-ordered with use_gpu=False, as in the
     reference, evolve.py:178,200,244-245).
+
+    thermal : None (isothermal, as the reference) or a :class:`pyc2ray_amd.thermal.ThermalParams`: the temperature is
+    evolved from photo-heating and radiative cooling as well (use_gpu=True only; the photo tables must be on the device, the
+    heating tables are uploaded here).  Returns (xh_new, phi_ion, temp_new) then, temp_new laid out like `xh`.
     """
     if not use_gpu:
+        if thermal is not None:
+            raise ValueError("evolve3D: the thermal mode needs use_gpu=True (the use_gpu=False raytracer has no thermal form)")
         return _evolve_cpu_semantics(dt, dr, src_flux, src_pos, max_subbox, subboxsize, loss_fraction, temp, ndens,
                                      xh, photo_thin_table, photo_thick_table, minlogtau, dlogtau, R_max_LLS,
                                      convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile, quiet)
+    if thermal is None:
+        return _evolve(dt, dr, src_flux, src_pos, use_gpu, temp, ndens, xh, photo_thin_table, minlogtau, dlogtau,
+                       R_max_LLS, convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile, quiet)
     return _evolve(dt, dr, src_flux, src_pos, use_gpu, temp, ndens, xh, photo_thin_table, minlogtau, dlogtau,
-                   R_max_LLS, convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile, quiet)
+                   R_max_LLS, convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile, quiet, thermal=thermal)
 
 
 def evolve3D_MPI(dt, dr,
@@ -493,7 +528,7 @@ def evolve3D_MPI(dt, dr,
                  minlogtau, dlogtau,
                  R_max_LLS, convergence_fraction,
                  sig, bh00, albpow, colh0, temph0, abu_c,
-                 logfile="pyC2Ray.log", quiet=False):
+                 logfile="pyC2Ray.log", quiet=False, *, thermal=None):
     """Source-sharded variant (pyc2ray/evolve.py:249-498): rank r traces the contiguous block
     [r*(Ns//nprocs), (r+1)*(Ns//nprocs)) of the source list, the last rank to the end
     (evolve.py:362-367); the per-rank rate grids are summed across ranks each iteration.
@@ -502,7 +537,11 @@ def evolve3D_MPI(dt, dr,
     them (host-staged Reduce+Bcast), or ``pyc2ray_amd.dist.MPI`` and a ``pyc2ray_amd.dist.TorchComm``
     (one process per GPU under torch.distributed: RCCL all-reduce over xGMI directly on the
     device-resident grid).  All ranks return the same (xh_new, phi_ion).
+    The thermal mode is single-GPU only: ``thermal`` must be None here.
     """
+    if thermal is not None:
+        raise ValueError("evolve3D_MPI: the thermal mode is single-GPU only (no slab exchange of heating rates and "
+                         "temperatures); use evolve3D with use_gpu=True")
     if not use_gpu:
         return _evolve_cpu_semantics(dt, dr, src_flux, src_pos, max_subbox, subboxsize, loss_fraction, temp, ndens,
                                      xh, photo_thin_table, photo_thick_table, minlogtau, dlogtau, R_max_LLS,

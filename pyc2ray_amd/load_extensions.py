@@ -314,6 +314,19 @@ class _LibAsora:
         _capi.check(self._lib.asora_planes_to_device(int(which), int(i_begin), int(a.shape[0]), _capi.dptr(a)),
                     "planes_to_device")
 
+    def thermal_params(self, enable, relative_denergy=0.1, t_floor=1.0, max_substeps=10000, cooling_mask=31, compton=False,
+                       t_cmb=0.0):
+        """Switch asora_chemistry_device and the asora_evolve_* loop to the thermal form (enable) or back (include/asora_hip.h)."""
+        _capi.check(self._lib.asora_thermal_params(int(bool(enable)), float(relative_denergy), float(t_floor), int(max_substeps),
+                                                   int(cooling_mask), int(bool(compton)), float(t_cmb)), "thermal_params")
+
+    def thermal_stats(self):
+        """(cells that hit max_substeps, cells clamped to t_floor, most substeps of one integration) since the last
+        chemistry_device / evolve_begin."""
+        capped, floored, most = C.c_longlong(0), C.c_longlong(0), C.c_int(0)
+        _capi.check(self._lib.asora_thermal_stats(C.byref(capped), C.byref(floored), C.byref(most)), "thermal_stats")
+        return capped.value, floored.value, most.value
+
     def set_option(self, option, value):
         _capi.check(self._lib.asora_set_option(int(option), int(value)), "set_option")
 
