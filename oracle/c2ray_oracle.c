@@ -184,7 +184,9 @@ static void photo_rates(double normflux, double cd_in, double cd_out, double vfa
         double targ = (flags & ORACLE_THIN_TAU_OUT) ? tau_out : tau_in;
         *phi_cell = prefact * (tau_out - tau_in) * table_lookup(t->thin, targ, t);
         *phi_out = phi_in - *phi_cell;
-        *heat_cell = t->hthin ? prefact * (tau_out - tau_in) * table_lookup(t->hthin, tau_in, t) : 0.0;
+        /* (heating at the photo rate's optical depth: the Fortran's tau_in, photorates.f90:124; tau_out where the photo
+            rate takes it, as this library's HEAT kernels do in their default constants) */
+        *heat_cell = t->hthin ? prefact * (tau_out - tau_in) * table_lookup(t->hthin, targ, t) : 0.0;
     }
 }
 
@@ -346,7 +348,7 @@ void oracle_do_all_sources(const double *normflux, const int32_t *srcpos, int ma
 /* LAST source processed (cells it visited), for column-density parity tests. */
 /* ------------------------------------------------------------------------- */
 static void a_cell(int di, int dj, int dk, const int s0[3], double flux, double R, double sig, double dr,
-                   const double *ndens, const double *xh_av, double *phi_ion, double *scratch,
+                   const double *ndens, const double *xh_av, double *phi_ion, double *phi_heat, double *scratch,
                    int N, const rate_tables *tab, int flags, int last_l, int last_r, long *visited)
 {
     if (di < last_l || di > last_r || dj < last_l || dj > last_r || dk < last_l || dk > last_r) return; /* cu:241 */
@@ -374,23 +376,31 @@ static void a_cell(int di, int dj, int dk, const int s0[3], double flux, double 
         double phi, phi_out, heat;
         photo_rates(flux, cd_in, cd_out, vol, sig, tab, flags, &phi, &phi_out, &heat);
         phi_ion[idx] += phi / nHI;                                      /* cu:324,328 */
+        if (phi_heat) phi_heat[idx] += heat / nHI;                      /* (no heating in the CUDA library) */
     }
 }
 
-void oracle_asora_do_all_sources(double R, double sig, double dr, const double *ndens, const double *xh_av,
-                                 double *phi_ion, const int32_t *src_pos, const double *src_flux,
-                                 int NumSrc, int N, const double *thin, const double *thick,
-                                 double minlogtau, double dlogtau, int NumTau, int table_len, int flags,
-                                 double *coldens_dump, long *cells_visited)
+/* oracle_asora_do_all_sources with heating.  hthin, hthick, phi_heat (optional, all three or none): heating tables and the
+ * heating rate per HI atom, accumulated like the photo-ionisation rate (this library's HEAT kernels, raytrace.hip): the same
+ * table index and residual, thin cells looked up at the same optical depth as the photo rate (tau_out with
+ * ORACLE_THIN_TAU_OUT, tau_in otherwise).  A function of its own, so that the ABI of oracle_asora_do_all_sources stays. */
+void oracle_asora_do_all_sources_heat(double R, double sig, double dr, const double *ndens, const double *xh_av,
+                                      double *phi_ion, const int32_t *src_pos, const double *src_flux,
+                                      int NumSrc, int N, const double *thin, const double *thick,
+                                      double minlogtau, double dlogtau, int NumTau, int table_len, int flags,
+                                      double *coldens_dump, long *cells_visited,
+                                      const double *hthin, const double *hthick, double *phi_heat)
 {
     size_t n = (size_t)N * N * N;
-    rate_tables tab = { thin, thick, NULL, NULL, minlogtau, dlogtau, NumTau, table_len };
+    if (!phi_heat) hthin = hthick = NULL;
+    rate_tables tab = { thin, thick, hthin, hthick, minlogtau, dlogtau, NumTau, table_len };
     int max_q = (int)ceil(1.73205080757 * fmin(R, 1.73205080757 * N / 2.0));   /* cu:14,101 */
     int last_r = N / 2 - 1 + pmod(N, 2);                                       /* cu:122 */
     int last_l = -(N / 2);                                                     /* cu:123 */
     double *scratch = coldens_dump ? coldens_dump : (double *)calloc(n, sizeof(double));
     if (coldens_dump) memset(coldens_dump, 0, n * sizeof(double));
     memset(phi_ion, 0, n * sizeof(double));                                    /* cu:113 */
+    if (phi_heat) memset(phi_heat, 0, n * sizeof(double));
     long visited = 0;
     for (int ns = 0; ns < NumSrc; ++ns) {
         int s0[3] = { src_pos[3 * ns], src_pos[3 * ns + 1], src_pos[3 * ns + 2] };
@@ -401,10 +411,10 @@ void oracle_asora_do_all_sources(double R, double sig, double dr, const double *
                 int rem = q - abs(di);
                 for (int dj = -rem; dj <= rem; ++dj) {
                     int dk = rem - abs(dj);
-                    a_cell(di, dj, dk, s0, flux, R, sig, dr, ndens, xh_av, phi_ion, scratch, N, &tab,
+                    a_cell(di, dj, dk, s0, flux, R, sig, dr, ndens, xh_av, phi_ion, phi_heat, scratch, N, &tab,
                            flags, last_l, last_r, &visited);
                     if (dk != 0)
-                        a_cell(di, dj, -dk, s0, flux, R, sig, dr, ndens, xh_av, phi_ion, scratch, N, &tab,
+                        a_cell(di, dj, -dk, s0, flux, R, sig, dr, ndens, xh_av, phi_ion, phi_heat, scratch, N, &tab,
                                flags, last_l, last_r, &visited);
                 }
             }
@@ -412,6 +422,17 @@ void oracle_asora_do_all_sources(double R, double sig, double dr, const double *
     }
     if (cells_visited) *cells_visited = visited;
     if (!coldens_dump) free(scratch);
+}
+
+void oracle_asora_do_all_sources(double R, double sig, double dr, const double *ndens, const double *xh_av,
+                                 double *phi_ion, const int32_t *src_pos, const double *src_flux,
+                                 int NumSrc, int N, const double *thin, const double *thick,
+                                 double minlogtau, double dlogtau, int NumTau, int table_len, int flags,
+                                 double *coldens_dump, long *cells_visited)
+{
+    oracle_asora_do_all_sources_heat(R, sig, dr, ndens, xh_av, phi_ion, src_pos, src_flux, NumSrc, N, thin, thick,
+                                     minlogtau, dlogtau, NumTau, table_len, flags, coldens_dump, cells_visited,
+                                     NULL, NULL, NULL);
 }
 
 /* ------------------------------------------------------------------------- */

@@ -2,7 +2,7 @@
 
 Function names mirror the reference entry points they restate:
   do_all_sources        <- src/c2ray/raytracing.f90:52   (Fortran CPU path, cubic traversal)
-  asora_do_all_sources  <- src/asora/raytracing.cu:79    (GPU path semantics, shell traversal)
+  asora_do_all_sources  <- src/asora/raytracing.cu:79    (GPU path semantics, shell traversal; optional heating)
   global_pass           <- src/c2ray/chemistry.f90:13
   doric / do_chemistry  <- src/c2ray/chemistry.f90:221 / :117
 """
@@ -87,10 +87,12 @@ def do_all_sources(normflux, srcpos, max_subbox, subboxsize, sig, dr, ndens, xh_
 
 
 def asora_do_all_sources(R, sig, dr, ndens, xh_av, src_pos0, src_flux, thin, thick,
-                         minlogtau, dlogtau, NumTau=None, flags=ASORA_MODE, want_coldens=False):
+                         minlogtau, dlogtau, NumTau=None, flags=ASORA_MODE, want_coldens=False,
+                         heat_thin=None, heat_thick=None):
     """ASORA-semantics raytrace.  ndens/xh_av: (N,N,N) logical [i,j,k]; src_pos0: flat int32
     0-based [x0,y0,z0,x1,...] (format_sources layout).  Returns dict(phi_ion (N,N,N) C-order,
-    coldens (last source, if requested), visited)."""
+    coldens (last source, if requested), visited), and phi_heat (N,N,N) C-order when both heating
+    tables are given (the heating rate per HI atom of this library's HEAT kernels)."""
     N = ndens.shape[0]
     nd = np.ascontiguousarray(ndens, dtype=np.float64)
     xh = np.ascontiguousarray(xh_av, dtype=np.float64)
@@ -100,15 +102,28 @@ def asora_do_all_sources(R, sig, dr, ndens, xh_av, src_pos0, src_flux, thin, thi
     thick = np.ascontiguousarray(thick, dtype=np.float64)
     if NumTau is None:
         NumTau = thin.shape[0]
+    if (heat_thin is None) != (heat_thick is None):
+        raise ValueError("asora_do_all_sources: give both heating tables or neither")
+    heat = heat_thin is not None
+    if heat:
+        ht = np.ascontiguousarray(heat_thin, dtype=np.float64)
+        hk = np.ascontiguousarray(heat_thick, dtype=np.float64)
+        if ht.shape != thin.shape or hk.shape != thin.shape:
+            raise ValueError("asora_do_all_sources: heating tables must have the photo tables' length")
     phi = np.zeros((N, N, N))
+    phi_heat = np.zeros((N, N, N)) if heat else None
     cd = np.zeros((N, N, N)) if want_coldens else None
     visited = C.c_long(0)
-    lib().oracle_asora_do_all_sources(
+    lib().oracle_asora_do_all_sources_heat(
         C.c_double(R), C.c_double(sig), C.c_double(dr), _d(nd), _d(xh), _d(phi),
         pos.ctypes.data_as(_ip), _d(flux), C.c_int(flux.shape[0]), C.c_int(N), _d(thin), _d(thick),
         C.c_double(minlogtau), C.c_double(dlogtau), C.c_int(NumTau), C.c_int(thin.shape[0]),
-        C.c_int(flags), _opt(cd), C.byref(visited))
-    return dict(phi_ion=phi, coldens=cd, visited=visited.value)
+        C.c_int(flags), _opt(cd), C.byref(visited),
+        _d(ht) if heat else None, _d(hk) if heat else None, _opt(phi_heat))
+    out = dict(phi_ion=phi, coldens=cd, visited=visited.value)
+    if heat:
+        out["phi_heat"] = phi_heat
+    return out
 
 
 def global_pass(dt, ndens, temp, xh, xh_av, xh_intermed, phi_ion, bh00, albpow, colh0, temph0, abu_c):

@@ -194,3 +194,23 @@ def evolve_case(name):
              dlogtau=dlog, use_gpu=s["use_gpu"], order=order, steps=s["steps"], convergence_fraction=1e-4,
              heat_thin=1e-11 * thin * np.linspace(1.0, 2.0, n), heat_thick=0.7e-11 * thick * np.linspace(2.0, 1.0, n))
     return c
+
+
+_BB_CACHE = {}
+
+
+def blackbody_photo_and_heat_tables(teff=5e4, num_tau=2000):
+    """(thin, thick, heat_thin, heat_thick, dlog): the black-body tables of blackbody_tables with the matching
+    photo-heating tables (BlackBodySource.make_heat_table, erg s^-1).  The heating tables are not proportional to the
+    photo tables (the energy per ionisation grows with the optical depth), so a heating lookup at a wrong index or
+    optical depth shows.  Cached: the integration takes a few seconds."""
+    key = (teff, num_tau)
+    if key not in _BB_CACHE:
+        from pyc2ray_amd.radiation import BlackBodySource, make_tau_table
+        ev2fr = 0.241838e15
+        tau, dlog = make_tau_table(MINLOGTAU, MAXLOGTAU, num_tau)
+        src = BlackBodySource(teff, False, ev2fr * 13.598, 2.8)
+        thin, thick = src.make_photo_table(tau, ev2fr * 13.598, 10 * ev2fr * 54.416, 1e48)
+        hthin, hthick = src.make_heat_table(tau, ev2fr * 13.598, 10 * ev2fr * 54.416, 1e48)
+        _BB_CACHE[key] = (thin, thick, hthin, hthick, dlog)
+    return tuple(np.array(a, copy=True) if isinstance(a, np.ndarray) else a for a in _BB_CACHE[key])

@@ -489,8 +489,9 @@ def test_mesh_576_both_atomic_families_at_real_size(asora):
     del many, glob
 
     # heating and grey opacity beyond N = 512 (round 6): one source per workgroup, a buffer descriptor per layout of the rate grid AND
-    # of the heating grid -- the same arithmetic as the global-atomic family (parity of both with the oracle: tests/test_gpu_parity.py),
-    # so the two must agree to the order of the additions
+    # of the heating grid -- the same arithmetic as the global-atomic family, so the two must agree to the order of the additions
+    # (the rates of both against the oracle above and in tests/test_gpu_parity.py; heating against the oracle below N = 512 in
+    # tests/test_gpu_heating.py, and here by the power-of-two identity after this block)
     lib.heat_table_to_device(2e-11 * thin * np.linspace(1.0, 3.0, thin.shape[0]), 1e-11 * thick, thin.shape[0])
     for opt, grids in ((capi.OPT_HEATING, (capi.GRID_PHI_ION, capi.GRID_PHI_HEAT)), (capi.OPT_GREY_NOTABLES, (capi.GRID_PHI_ION,))):
         res = {}
@@ -510,6 +511,33 @@ def test_mesh_576_both_atomic_families_at_real_size(asora):
             np.testing.assert_allclose(a[w], b[w], rtol=1e-11, atol=0)
         del res
     del w
+    # the power-of-two identity at this size: heating tables = 2^-35 x photo tables and 27 sources whose spheres do not overlap
+    # (one on the corner, so that they wrap) -> PHI_HEAT == 2^-35 PHI_ION bit for bit in both families (the three all-sign
+    # sectors x 512 threads with SPLIT descriptors, the form the 600 sources above take; and global atomics)
+    p2 = 2.0 ** -35
+    lpos = np.array([(i, j, k) for i in (1, 193, 385) for j in (1, 193, 385) for k in (1, 193, 385)]).T
+    l0, lf0 = cases.flat_sources(lpos, np.linspace(0.5e3, 2.0e3, lpos.shape[1]))
+    lib.source_data_to_device(l0, lf0, lpos.shape[1])
+    lib.heat_table_to_device(p2 * thin, p2 * thick, thin.shape[0])
+    for glob_atomics in (0, 1):
+        lib.set_option(capi.OPT_HEATING, 1)
+        lib.set_option(capi.OPT_GLOBAL_ATOMICS, glob_atomics)
+        lib.set_option(capi.OPT_SECTORS, 8)
+        lib.set_option(capi.OPT_BLOCK_THREADS, 512)
+        try:
+            lib.raytrace_device(R, cases.SIG, dr, 0, lpos.shape[1], cases.MINLOGTAU, dlog, numtau)
+            v = lib.last_raytrace_variant()
+            lphi = lib.grid_to_host(capi.GRID_PHI_ION, np.empty((N, N, N)))
+            lheat = lib.grid_to_host(capi.GRID_PHI_HEAT, np.empty((N, N, N)))
+        finally:
+            lib.set_option(capi.OPT_HEATING, 0)
+            lib.set_option(capi.OPT_GLOBAL_ATOMICS, 0)
+            lib.set_option(capi.OPT_SECTORS, 0)
+            lib.set_option(capi.OPT_BLOCK_THREADS, 0)
+        assert v["units"] == 3 and v["threads"] == 512 and v["split_descriptors"] == (not glob_atomics) and not v["paired"], v
+        assert int((lphi != 0).sum()) == lpos.shape[1] * _lattice_points_within(R)
+        assert np.array_equal(lheat, p2 * lphi) and not np.signbit(lheat).any()
+        del lphi, lheat
 
     # the production forms beyond N = 512 (round 5).  At r_RT = 30 a source is cut into six sectors, whose rated cells lie on one
     # face each, so the rate atomics of a workgroup go through a buffer descriptor over ONE layout of the grid (8 N^3 bytes
