@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PYC2RAY_AMD_LIBASORA selects another BUILD of the same HIP library (diagnostic variants made by
-# `make -C pyc2ray_amd/csrc EXTRA=... OUT=...`, tools/ab_prebuilt.sh): never a fallback -- a path that does not exist raises.
+# `make -C pyc2ray_amd/csrc EXTRA=... OUT=...`, tools/ab_options.sh): never a fallback -- a path that does not exist raises.
 LIB_PATH = os.environ.get("PYC2RAY_AMD_LIBASORA") or os.path.join(_HERE, "lib", "libasora_hip.so")
 
 # grid selectors / options / kernels, as in include/asora_hip.h

@@ -233,9 +233,6 @@ static void fill_rt_params(RtParams &p, double R, double sig, double dr, double 
     p.src_pos = st.src_pos; p.src_flux = st.src_flux;
     p.counters = st.counters;
     p.radius_stays = note_call_radius(st, R, radius_path) ? 1 : 0;
-#ifdef ASORA_ENABLE_ABLATION
-    { const char *ab = getenv("ASORA_ABLATE"); p.ablate = ab ? atoi(ab) : 0; }
-#endif
 }
 
 // A raytrace call in three parts, so that a caller can overlap the multi-GPU sum of finished slabs of the
@@ -1838,10 +1835,6 @@ int asora_evolve_enqueue(int iterations)
         c.ndens = st.grid[ASORA_GRID_NDENS]; c.temp = st.grid[ASORA_GRID_TEMP]; c.xh = st.grid[ASORA_GRID_XH];
         c.xh_av_in = st.ev_first ? st.grid[ASORA_GRID_XH] : st.grid[ASORA_GRID_XH_AV];
         c.gamma = acc_cur; c.gamma_t = acc_cur + st.ncell; c.phi_out = nullptr;
-        {   // A/B only (tools/ab_chem_store.sh): also store the folded rates every iteration, as round 2 did
-            static const bool store_always = getenv("ASORA_DIAG_STORE_PHI") != nullptr;
-            if (store_always) c.phi_out = st.grid[ASORA_GRID_PHI_ION];
-        }
         c.zero_a = acc_next; c.zero_t = acc_next + st.ncell;
         if (st.reach_in_use) { c.reach_a = st.reach_mask; c.reach_t = st.reach_mask + st.reach_bytes; }
         c.xh_av = st.grid[ASORA_GRID_XH_AV]; c.xh_intermed = st.grid[ASORA_GRID_XH_INTERMED];

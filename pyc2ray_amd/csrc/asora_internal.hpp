@@ -59,15 +59,14 @@ struct RtParams {
     int shape_src_count;   // source count the launch shape is chosen for (the whole call's, not a pipelined range's)
     int split_desc;        // 1: N > 512 -- the buffer descriptors of the rate atomics span ONE layout of the grid each (raytrace.hip)
     int radius_stays;      // decided once per call (note_call_radius): the line-aligned tables may be built for this radius
-    int ablate;            // diagnostics only (env ASORA_ABLATE): 1 = no rate atomics, 2 = no rates
     OctGeomDev geom[MAX_UNITS]; // by value: pointers read from the kernarg segment are known-global to the compiler
     int units;                  // workgroups per source: 8 octants, 24 octant-sectors, 12 mirrored sector pairs, 96 sector wedges
     int spread;                 // 1: block b = (source b / units, unit b % units) -- a source's units on different XCDs
-    const double2 *logtab;      // 128 x {1/c, log2 c}
+    const double2 *logtab;      // log2 table of log2_pos (ensure_logtab)
     unsigned ncell;             // N^3: the [k][j][i] copy of a grid starts ncell elements after its [i][j][k] form
     const double *nhi;          // nHI, [i][j][k] then [k][j][i]
     double *phi;                // Gamma accumulator, [i][j][k] then [k][j][i]
-    const double2 *tables;      // pairs {T[i], T[i+1]-T[i]}: thick at [0, len), thin at [len, 2 len), heat thick at [2 len, 3 len), heat thin at [3 len, 4 len)
+    const double2 *tables;      // thick, thin, heat thick, heat thin, each table_stride(len) doubles (pack_rate_table, rates_device.hpp)
     double *heat;               // heating accumulator (HEAT kernels), [i][j][k] then [k][j][i]
     const int32_t *src_pos;
     const double *src_flux;
@@ -139,7 +138,7 @@ struct State {
     bool have_heat_tables = false;
     double *staging = nullptr; // N^3 staging grid for 'F'-order transfers / debug dumps
 
-    double2 *tables = nullptr;     // [thick | thin | heat thick | heat thin] as pairs {T[i], T[i+1]-T[i]}, each table_len long
+    double2 *tables = nullptr;     // [thick | thin | heat thick | heat thin] (pack_rate_table)
     int table_len = 0;
 
     int32_t *src_pos = nullptr;
@@ -367,7 +366,7 @@ struct SubboxParams {
     int edge_r, edge_l;         // faces of the current sub-box: last_r - src, src - last_l (f90:199-200)
     double sig, dr, R;          // R = R_max_LLS in cells
     double numtau_f, lut_k1, lut_k0;
-    int table_len, ablate;
+    int table_len;
     int grey, heat, add_zero;   // add_zero = 0: ASORA_OPT_SKIP_ZERO_RATES
     int src_begin, src_count;   // batch of sources
     int flux_src;               // >= 0: every source shines with the flux of this one (f90:500,503); -1: its own

@@ -359,33 +359,18 @@ __global__ void __launch_bounds__(RED_THREADS) chemistry_reduce_kernel(const dou
 // The folded rate itself is NOT stored: the pass leaves the accumulators it read intact and zeroes the OTHER pair for the
 // next raytrace (ChemTileParams.zero_a / zero_t), so the rates of the last iteration can be folded when someone asks.
 // The [k][j][i] twins are read and written through LDS tiles so that their rows are contiguous as well.
-// waves per SIMD the register allocation of the tiled pass must leave room for (a streaming pass: more waves, more
-// bytes in flight)
-#ifndef ASORA_CHEM_MIN_WAVES
-#define ASORA_CHEM_MIN_WAVES 1
-#endif
 // The grids the pass reads are streams: every element once, nothing another workgroup wants again.  Loaded non-temporal they do not
 // take the place of the lines the seven write streams are being combined in: a bare kernel with the pass's 5 read and 7 write streams
 // moves 6.3 TB/s instead of 5.3 (tools/micro/stream_peak.hip; non-temporal STORES cost 2-5 % there, and in the pass itself -- any of
 // its three groups of write streams -- change nothing beyond the noise: profiles/r05_ab_chem_ntstores.txt).  The pass: -8 % in either
 // state of a box (0.248 -> 0.229 ms, 0.306 -> 0.281 ms; profiles/r05_ab_chem_ntloads.txt).
-#ifndef ASORA_CHEM_NT_LOADS
-#define ASORA_CHEM_NT_LOADS 1
-#endif
-__device__ __forceinline__ double stream_load(const double *q)
-{
-#if ASORA_CHEM_NT_LOADS
-    return __builtin_nontemporal_load(q);
-#else
-    return *q;
-#endif
-}
+__device__ __forceinline__ double stream_load(const double *q) { return __builtin_nontemporal_load(q); }
 
 // THERMAL (with FOLD and EMIT, not UNIFORM_T): chemistry_cell_thermal; the heating accumulators are folded like the rates
 // (tile_h: their [k][j][i] twin), the other heating pair is zeroed for the next trace, the end temperature goes to temp_end.
 // Per cell 8 loads and 9 stores = 136 B.
 template <bool FOLD, bool EMIT, bool UNIFORM_T, bool THERMAL = false>
-__global__ void __launch_bounds__(CH_THREADS, ASORA_CHEM_MIN_WAVES) chemistry_tile_kernel(const ChemTileParams p)
+__global__ void __launch_bounds__(CH_THREADS, 1) chemistry_tile_kernel(const ChemTileParams p)
 {
     static_assert(!THERMAL || (FOLD && EMIT && !UNIFORM_T), "thermal pass: the device loop's fold + emit form only");
     if (p.status && p.status->done) return;

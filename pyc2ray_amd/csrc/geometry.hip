@@ -369,20 +369,16 @@ int upload(const std::vector<T> &v, const T *&dev_out, std::vector<void *> &owne
 
 } // namespace
 
-// log2 table of log2_pos: interval centres c = 1 + (i + 1/2)/128, entries {1/c, log2 c}
+// log2 table of log2_pos: interval centres c = 1 + (i + 1/2)/LOG_TABLE_SIZE, entries {2/c, log2 c - 1}
+// (the mantissa comes as m in [0.5, 1): c/2 is its interval centre, rates_device.hpp)
 int ensure_logtab(State &st)
 {
     if (st.logtab_dev) return 0;
     std::vector<double2> lt(LOG_TABLE_SIZE);
     for (int i = 0; i < LOG_TABLE_SIZE; ++i) {
         const long double c = 1.0L + ((long double)i + 0.5L) / (long double)LOG_TABLE_SIZE;
-#if ASORA_FREXP_LOG       // the mantissa comes as m in [0.5, 1): c/2 is its interval centre (rates_device.hpp)
         lt[i].x = (double)(2.0L / c);
         lt[i].y = (double)(std::log2(c) - 1.0L);
-#else
-        lt[i].x = (double)(1.0L / c);
-        lt[i].y = (double)std::log2(c);
-#endif
     }
     double2 *d = nullptr;
     ASORA_HIP_TRY(hipMalloc(&d, lt.size() * sizeof(double2)));

@@ -129,18 +129,11 @@ __device__ __forceinline__ double photo_rate_per_atom(double flux, double cd_in,
 // entry k*RT_THREADS + lane is what `lane` does in step k and the tables can be prefetched blindly.
 //   cellA[e] = { abc, own slot | VALID | LAST_OF_SHELL, path (double, 2 words) }
 //   cellB[e] = { slots of the four upstream corners in the previous shell's buffer }
-// Dynamic LDS: [log table: 128 x {1/c, log2 c}][1/s: TABCAP doubles][wrapped i(a), j(b), k(c), mirrored: 4*TABCAP ints]
+// Dynamic LDS: [log table: LOG_TABLE_SIZE x {2/c, log2 c - 1}][1/s: TABCAP doubles][wrapped i(a), j(b), k(c), mirrored: 4*TABCAP ints]
 //              [shell buffer 0: max_cells+1 doubles][shell buffer 1: same]   (the last two unless GLOBAL_SCRATCH)
 // TABCAP = 64 (S <= 63, workgroups of 64 or 128 threads: small traces, where LDS decides how many workgroups a CU
 // holds), 256 (S <= 255) or 1024.
 // Slot max_cells of each shell buffer holds 0.0: upstream corners of weight 0 point there.
-// Diagnostic builds only (make EXTRA=-DASORA_ENABLE_ABLATION, tools/ablate.sh): ASORA_ABLATE=1 skips the rate
-// atomics, 2 the rates, 4 the shell barriers, to attribute kernel time.  Production builds contain none of it.
-#ifdef ASORA_ENABLE_ABLATION
-#define ASORA_ABLATED(bit) ((p.ablate & (bit)) != 0)
-#else
-#define ASORA_ABLATED(bit) false
-#endif
 
 // buffer_atomic_add_f64 through a raw buffer descriptor: a lane whose offset lies beyond the descriptor's range is dropped
 // by the hardware, so "this lane has nothing to add" is an offset of -1 and the instruction needs no branch around it
@@ -151,71 +144,31 @@ __device__ __forceinline__ double photo_rate_per_atom(double flux, double cd_in,
 extern "C" __device__ double asora_buffer_atomic_fadd_f64(double, __amdgpu_buffer_rsrc_t, int, int, int)
     __asm("llvm.amdgcn.raw.ptr.buffer.atomic.fadd.f64");
 
-// 1: the rate atomic of a step is issued in the NEXT step, right behind that step's table-lookup loads.  Vector
-// memory operations complete in issue order, so a lookup issued after an atomic cannot return before the atomic has
-// gone through the memory-side atomic unit (thousands of cycles under load); issued the other way round the lookup
-// only waits for the atomic of the step before.  Costs 3 VGPRs.
-#ifndef ASORA_LATE_ATOMIC
-#define ASORA_LATE_ATOMIC 1
-#endif
-
-// 1: the table lookups of a step are CONSUMED in the next step (their rate is formed there, right before that step's
-// own lookups are issued, and added behind them): a whole step of arithmetic hides their latency.  Pays where the
-// kernel is latency-bound; costs 14 VGPRs (the kernel as a whole needs 96 with buffer atomics).  Measured on MI355X, 1000 sources,
-// 256^3 (tools/ab_macro.sh ASORA_LATE_LOOKUP "0 1" ...): R = 16 -1.0 %, 24 -3.5 %, 32 -1.9 %, 48 -1.7 %, 64 -1.7 %.
-#ifndef ASORA_LATE_LOOKUP
-#define ASORA_LATE_LOOKUP 1
-#endif
-
-// 1: within a group of 8 sources the units are dispatched largest first (the z-sector units hold the most cells), so
-// that the workgroups still running when the grid drains are the short ones.  Measured (tools/ab_macro.sh, 1000 sources,
-// 256^3): R = 24 -2.6 %, 32 -1.8 %, 48 -1.7 %, 64 -0.5 %.
-#ifndef ASORA_UNITS_LARGEST_FIRST
-#define ASORA_UNITS_LARGEST_FIRST 1
-#endif
-
-// A wave whose 64 table entries of a step are all padding: 1 = skips the step's arithmetic and lookups, 2 = skips the
-// interpolation only and issues the (unused) lookups like every other wave, 0 = runs the whole step.  With 1 the number
-// of vector-memory operations in flight differs between the two paths, and where they meet the compiler waits as the
-// shorter one demands (three operations too early on every wait of every step).
-#ifndef ASORA_SKIP_EMPTY_WAVES
-#define ASORA_SKIP_EMPTY_WAVES 2
-#endif
-
-// 1: see the comment at the loop entry of the kernel
-#ifndef ASORA_PRIME_PIPELINE
-#define ASORA_PRIME_PIPELINE 1
-#endif
-
-// 1: a scheduling barrier between the unrolled steps.  Without it the compiler hoists the decoding of a table entry (the
-// address of the NEXT step's nHI) into the step that loaded the entry, i.e. waits for a load issued 250 instructions ago
-// with two newer ones in flight instead of a whole step later.
-#ifndef ASORA_STEP_SCHED_BARRIER
-#define ASORA_STEP_SCHED_BARRIER 1
-#endif
-
-// 1: the two divisions of a cell (interpolation, flux / volume) through div_newton (rates_device.hpp) instead of the IEEE
-// sequence.  Pays since the work counters stopped serialising the launch and the kernel runs at ~80 % of VALU issue.
-#ifndef ASORA_NEWTON_DIVISION
-#define ASORA_NEWTON_DIVISION 1
-#endif
-#if ASORA_NEWTON_DIVISION
-#define ASORA_DIV(x, y) div_newton((x), (y))
-#else
-#define ASORA_DIV(x, y) ((x) / (y))
-#endif
-
-// waves per SIMD the register allocation must leave room for (2nd argument of __launch_bounds__; workgroups of up to 512
-// threads).  Left alone the kernel takes 100 VGPRs (4 waves per SIMD); asked for 5 it fits 96 with three dwords spilled
-// outside the loop, and is slower (R = 16 +5 %, R = 32 +2 %: profiles/r02_ab_work_counters.txt).
-#ifndef ASORA_MIN_WAVES
-#define ASORA_MIN_WAVES 1
-#endif
-
-// the same for the paired-sources variant (NSRC = 2): left alone it takes 134 VGPRs (3 waves per SIMD)
-#ifndef ASORA_PAIR_MIN_WAVES
-#define ASORA_PAIR_MIN_WAVES 1
-#endif
+// Choices of the step loop, each measured on MI355X (LABNOTES; 1000 sources, 256^3 unless stated):
+// - The table lookups of a step are CONSUMED in the next step (their rate is formed there, right before that step's own
+//   lookups are issued, and added behind them): a whole step of arithmetic hides their latency.  Pays where the kernel is
+//   latency-bound; costs 14 VGPRs (the kernel as a whole needs 96 with buffer atomics).  Round 2: R = 16 -1.0 %, 24 -3.5 %,
+//   32 -1.9 %, 48 -1.7 %, 64 -1.7 %.
+// - The rate atomic of a step is thereby issued in the NEXT step, right behind that step's table-lookup loads.  Vector
+//   memory operations complete in issue order, so a lookup issued after an atomic cannot return before the atomic has
+//   gone through the memory-side atomic unit (thousands of cycles under load); issued the other way round the lookup
+//   only waits for the atomic of the step before.
+// - Within a group of 8 sources the units are dispatched largest first (the z-sector units hold the most cells), so that
+//   the workgroups still running when the grid drains are the short ones.  Round 2: R = 24 -2.6 %, 32 -1.8 %, 48 -1.7 %,
+//   64 -0.5 %.
+// - A wave whose 64 table entries of a step are all padding skips the interpolation only and issues the (unused) lookups
+//   like every other wave.  Skipping the lookups as well makes the number of vector-memory operations in flight differ
+//   between the two paths, and where they meet the compiler waits as the shorter one demands (three operations too early
+//   on every wait of every step).
+// - A scheduling barrier between the unrolled steps.  Without it the compiler hoists the decoding of a table entry (the
+//   address of the NEXT step's nHI) into the step that loaded the entry, i.e. waits for a load issued 250 instructions ago
+//   with two newer ones in flight instead of a whole step later.
+// - The two divisions of a cell (interpolation, flux / volume) go through div_newton (rates_device.hpp) instead of the IEEE
+//   sequence.  Pays since the work counters stopped serialising the launch and the kernel runs at ~80 % of VALU issue.
+// - No minimum of waves per SIMD in __launch_bounds__ (1; workgroups of up to 512 threads).  Left alone the kernel takes
+//   100 VGPRs (4 waves per SIMD); asked for 5 it fits 96 with three dwords spilled outside the loop, and is slower (R = 16
+//   +5 %, R = 32 +2 %: profiles/r02_ab_work_counters.txt).  The paired-sources variant (NSRC = 2) left alone takes 134
+//   VGPRs (3 waves per SIMD).
 
 // (round 6: the thick and thin rate table in LDS -- NumTau <= 2048, 2 x 16 KB, lookups as ds_read2_b64 gathers -- was measured on
 //  twelve sector pairs with two workgroups per CU and is 11-14 % SLOWER than the global-memory lookups on the quiet medium and on an
@@ -261,11 +214,11 @@ __device__ __forceinline__ bool ztr_desc(const RtParams &p, int uinfo) { return 
 
 template <int RT_THREADS, bool GLOBAL_SCRATCH, bool DUMP, bool HEAT, int TABCAP, bool SKIP_ZERO = false, bool GREY = false,
           bool BUFATOM = false, int NSRC = 1, bool SUBBOX = false, bool SPLIT = false>
-__global__ void __launch_bounds__(RT_THREADS, (RT_THREADS <= 512 ? (NSRC == 2 ? ASORA_PAIR_MIN_WAVES : ASORA_MIN_WAVES) : 1)) raytrace_octant_kernel(const RtParams p)
+__global__ void __launch_bounds__(RT_THREADS, 1) raytrace_octant_kernel(const RtParams p)
 {
     extern __shared__ double lds_raw[];
-    static_assert(NSRC == 1 || (ASORA_LATE_LOOKUP && !GLOBAL_SCRATCH && !DUMP && BUFATOM), "paired sources: production variant only");
-    static_assert(!SUBBOX || (ASORA_LATE_LOOKUP && !GLOBAL_SCRATCH && !DUMP && !SKIP_ZERO && !GREY), "sub-box sweep: table rates, shells in LDS");
+    static_assert(NSRC == 1 || (!GLOBAL_SCRATCH && !DUMP && BUFATOM), "paired sources: production variant only");
+    static_assert(!SUBBOX || (!GLOBAL_SCRATCH && !DUMP && !SKIP_ZERO && !GREY), "sub-box sweep: table rates, shells in LDS");
     static_assert(!SPLIT || (BUFATOM && !SUBBOX && !DUMP && (NSRC == 1 || (!HEAT && !GREY)) && !(SKIP_ZERO && (HEAT || GREY))),
                   "descriptors per layout: the production forms for 512 < N <= 645, and the single-source form with heating or grey opacity");
 
@@ -284,9 +237,7 @@ __global__ void __launch_bounds__(RT_THREADS, (RT_THREADS <= 512 ? (NSRC == 2 ? 
         src_local = (blk & 7) + 8 * (blk / (8 * p.units));
         unit = (blk >> 3) % p.units;
     }
-#if ASORA_UNITS_LARGEST_FIRST
     unit = p.units - 1 - unit;   // sector units: z (most cells) first, x (fewest) last in dispatch order
-#endif
     const int uinfo = p.geom[unit].info;           // sign bits of the unit | merged axes << 3 | rates-source << 6 | (face + 1) << 8
     // p.aligned: the unit's tables come in eight forms, by the source's position modulo 8 along the memory-contiguous axis of
     // the unit's face; the two sources of a workgroup agree in it (the host paired them so: p.pairs)
@@ -399,8 +350,6 @@ __global__ void __launch_bounds__(RT_THREADS, (RT_THREADS <= 512 ? (NSRC == 2 ? 
     __amdgpu_buffer_rsrc_t rs_phi = __builtin_amdgcn_make_buffer_rsrc(p.phi + (unit_in_twin ? p.ncell : 0u), 0, BUFATOM ? (int)(8u * desc_cells) : 0, 0x00020000);
     __amdgpu_buffer_rsrc_t rs_heat = __builtin_amdgcn_make_buffer_rsrc((HEAT ? p.heat : p.phi) + (unit_in_twin ? p.ncell : 0u), 0, (BUFATOM && HEAT) ? (int)(8u * desc_cells) : 0, 0x00020000);
     auto add_phi = [&](bool ok, unsigned idx, double v) {
-        if (ASORA_ABLATED(1)) ok = ok && v == 1.2345e-300;
-        if (ASORA_ABLATED(64)) idx &= 0xFFFFu;            // diagnostic: all rates into a 512 KiB window (wrong results)
         if (BUFATOM) (void)asora_buffer_atomic_fadd_f64(v, rs_phi, ok ? (int)(idx * 8u - desc_off8) : ASORA_OOB_OFFSET, 0, 0);
         else if (ok) unsafeAtomicAdd(p.phi + idx, v);
     };
@@ -410,11 +359,7 @@ __global__ void __launch_bounds__(RT_THREADS, (RT_THREADS <= 512 ? (NSRC == 2 ? 
     };
     // BUFATOM: a pending rate is carried as the byte offset its atomic will use -- ASORA_OOB_OFFSET when the lane has nothing
     // to add -- instead of an index and a flag (a flag that lives across the step costs a select to make and a compare to use)
-    auto add_phi_at = [&](int off, double v) {
-        if (ASORA_ABLATED(1)) off = v == 1.2345e-300 ? off : ASORA_OOB_OFFSET;
-        if (ASORA_ABLATED(64)) off &= 0x7FFF8;
-        (void)asora_buffer_atomic_fadd_f64(v, rs_phi, off, 0, 0);
-    };
+    auto add_phi_at = [&](int off, double v) { (void)asora_buffer_atomic_fadd_f64(v, rs_phi, off, 0, 0); };
     auto add_heat_at = [&](int off, double v) { (void)asora_buffer_atomic_fadd_f64(v, rs_heat, off, 0, 0); };
 
     // ---- SUBBOX, a later box of the source: continue from the trailing shell of the box before ------------
@@ -453,7 +398,7 @@ __global__ void __launch_bounds__(RT_THREADS, (RT_THREADS <= 512 ? (NSRC == 2 ? 
     // The tables of a step do not depend on the medium, and the address of a cell's nHI only on
     // its table entry, so both are fetched ahead of the dependent arithmetic: tables two steps
     // ahead, nHI one step ahead.  The rate lookups of a step are issued after its shell barrier, so
-    // their latency never holds the barrier up, and consumed a step later (ASORA_LATE_LOOKUP).
+    // their latency never holds the barrier up, and consumed a step later.
     // (The tables carry two all-invalid steps of padding at the end: prefetches stay in bounds.)
     auto nhi_address = [&](int q, unsigned abc, unsigned flags, unsigned &idx) -> const double * {
         const int *w = wtab + q * 6 * TABCAP;
@@ -471,7 +416,6 @@ __global__ void __launch_bounds__(RT_THREADS, (RT_THREADS <= 512 ? (NSRC == 2 ? 
         asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(row) : "v"(outer), "s"(N), "v"(j));
         asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(cell) : "v"(row), "s"(N), "v"(inner));
         idx = cell + (zt ? p.ncell : 0u);
-        if (ASORA_ABLATED(128)) return p.nhi + (idx & 0xFFFFu);   // diagnostic: nHI from a 512 KiB window (wrong results)
         return p.nhi + idx;
     };
 
@@ -481,27 +425,18 @@ __global__ void __launch_bounds__(RT_THREADS, (RT_THREADS <= 512 ? (NSRC == 2 ? 
     // step's (its nHI is requested here), `pf_*` the register set the entry two steps ahead is
     // loaded into.  The loop below is unrolled three times with the three register sets rotating,
     // so the pipeline needs no register-to-register copies.
-    bool late_ok[NSRC];                // a rate computed in the previous step, not yet added (ASORA_LATE_ATOMIC)
-#if !ASORA_LATE_LOOKUP
-    double late_v[NSRC], late_h[NSRC];
-#endif
+    bool late_ok[NSRC];                // a rate computed in the previous step, not yet added
     unsigned late_idx[NSRC];
     int late_off[NSRC];                // BUFATOM: byte offset of the pending rate's atomic, or ASORA_OOB_OFFSET
-#if ASORA_LATE_LOOKUP
     Lookup pend_A[NSRC], pend_B[NSRC];             // lookups issued in the previous step, consumed in this one
     bool pend_thick[NSRC];
     double pend_pref[NSRC], pend_dtau[NSRC];
-#endif
 #pragma unroll
     for (int q = 0; q < NSRC; ++q) {
         late_ok[q] = false; late_idx[q] = 0; late_off[q] = ASORA_OOB_OFFSET;
-#if !ASORA_LATE_LOOKUP
-        late_v[q] = 0.0; late_h[q] = 0.0;
-#else
         pend_A[q].t = pend_B[q].t = pend_A[q].h = pend_B[q].h = double2{0.0, 0.0};
         pend_A[q].residual = pend_B[q].residual = 0.0;
         pend_thick[q] = false; pend_pref[q] = 0.0; pend_dtau[q] = 0.0;
-#endif
     }
 
     // SUBBOX: photons through the faces of the current sub-box (f90:541-543), per lane; the faces on the unit's own side
@@ -519,27 +454,15 @@ __global__ void __launch_bounds__(RT_THREADS, (RT_THREADS <= 512 ? (NSRC == 2 ? 
     auto step = [&](auto first_c, int k_pf, unsigned e_pf, const uint4 &cur_A, const uint4 &cur_B, const double (&cur_nhi)[NSRC], const unsigned (&cur_idx)[NSRC],
                     const uint4 &nxt_A, double (&nxt_nhi)[NSRC], unsigned (&nxt_idx)[NSRC], uint4 &pf_A, uint4 &pf_B) {
         constexpr bool FIRST_TRIPLE = decltype(first_c)::value;
-#if ASORA_STEP_SCHED_BARRIER
-        __builtin_amdgcn_sched_barrier(0);      // nothing of this step is scheduled into the previous one (see the macro)
-#endif
+        __builtin_amdgcn_sched_barrier(0);      // nothing of this step is scheduled into the previous one (see above the kernel)
         pf_A = (k_pf < inner_steps ? innerA : cellA)[e_pf];                      // two steps ahead (step k_pf)
         pf_B = (k_pf < inner_steps ? innerB : cellB)[e_pf];
-#ifdef ASORA_DIAG_EXTRA_TABLE_LOAD      // diagnostic build only: 16 more bytes per lane and step from ANOTHER unit's table (equal sizes: octants)
-        {
-            const uint4 extra = p.geom[(unit + 1) % p.units].cellA[e_pf];
-            n_eval += (extra.x == 0xdeadbeefu && extra.w == 0x12345u) ? 1u : 0u;
-        }
-#endif
 #pragma unroll
         for (int q = 0; q < NSRC; ++q) nxt_nhi[q] = *nhi_address(q, nxt_A.x, nxt_A.y, nxt_idx[q]);          // one step ahead
 
         const bool valid = (cur_A.y & CELL_VALID) != 0;
         // waves whose 64 entries are all padding skip the arithmetic (wave-uniform branch)
-#if ASORA_SKIP_EMPTY_WAVES
         const bool wave_has_work = __builtin_amdgcn_ballot_w64(valid) != 0ull;
-#else
-        const bool wave_has_work = true;
-#endif
         bool rated[NSRC];
         double cd_in[NSRC], cd_out[NSRC], vol_nhi[NSRC];
         unsigned dst_idx[NSRC];
@@ -599,11 +522,7 @@ __global__ void __launch_bounds__(RT_THREADS, (RT_THREADS <= 512 ? (NSRC == 2 ? 
             const double m12 = m1 * m2, m34 = m3 * m4;
             const double q1 = w1 * (m2 * m34), q2 = w2 * (m1 * m34);
             const double q3 = w3 * (m12 * m4), q4 = w4 * (m12 * m3);
-#ifdef ASORA_DIAG_NO_DIVISION        // diagnostic build only (wrong values): what the two divisions of a cell cost
-            double cdi = (x1 * q1 + x2 * q2 + x3 * q3 + x4 * q4) * __builtin_amdgcn_rcp(q1 + q2 + q3 + q4);
-#else
-            double cdi = ASORA_DIV(x1 * q1 + x2 * q2 + x3 * q3 + x4 * q4, q1 + q2 + q3 + q4);     // (the weights sum to 1, each max() is >= 0.6)
-#endif
+            double cdi = div_newton(x1 * q1 + x2 * q2 + x3 * q3 + x4 * q4, q1 + q2 + q3 + q4);     // (the weights sum to 1, each max() is >= 0.6)
             if (FIRST_TRIPLE && s == 1) {                    // diagonal neighbours of the source, cu:431-441
                 // (round 3: a wave's entries belong to one shell, so this could be a scalar branch instead of the dozen selects
                 //  the compiler makes of it -- measured: no gain at R = 16 / 32, +5 % at R = 64: the branch splits the
@@ -629,7 +548,7 @@ __global__ void __launch_bounds__(RT_THREADS, (RT_THREADS <= 512 ? (NSRC == 2 ? 
                 }
             }
             const bool ok = owner && cdi <= maxcd && (NSRC == 1 || have[q]);
-            rated[q] = ok && !ASORA_ABLATED(2);
+            rated[q] = ok;
             n_gamma += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(ok));
             vol_nhi[q] = volfac * nHI;
             dst_idx[q] = cur_idx[q];
@@ -637,7 +556,7 @@ __global__ void __launch_bounds__(RT_THREADS, (RT_THREADS <= 512 ? (NSRC == 2 ? 
         }
 
         if (__builtin_amdgcn_readfirstlane(cur_A.y) & CELL_LAST) {   // shell finished: publish it
-            if (!ASORA_ABLATED(4)) __syncthreads();
+            __syncthreads();
             double *tmp = prev; prev = cur; cur = tmp;
         }
 
@@ -646,7 +565,7 @@ __global__ void __launch_bounds__(RT_THREADS, (RT_THREADS <= 512 ? (NSRC == 2 ? 
 #pragma unroll
             for (int q = 0; q < NSRC; ++q)
                 add_phi(rated[q], dst_idx[q], grey_rate_per_atom(flux[q], cd_in[q], cd_out[q], vol_nhi[q], p));
-        } else if (wave_has_work || ASORA_SKIP_EMPTY_WAVES == 2) {
+        } else {    // (waves without work issue their unused lookups as well: see above the kernel)
             // (lanes without a rate run the lookups on whatever they hold: the index is clamped for any input)
             // TAU_PHOTO_LIMIT: rates.cu:7 (double 1e-7) or photorates.f90:69 (single 1e-7 promoted)
             const double limit = p.fortran_consts ? (double)1.0e-7f : 1.0e-7;
@@ -668,7 +587,6 @@ __global__ void __launch_bounds__(RT_THREADS, (RT_THREADS <= 512 ? (NSRC == 2 ? 
             }
             // SUBBOX: the second lookup of a THIN cell is the THICK table at tau_in: phi_in = pref T_thick(tau_in), which
             // the photon loss needs (phi_out = phi_in - phi, photorates.f90:120-125); its rate only uses the first
-#if ASORA_LATE_LOOKUP
             // SKIP_ZERO (ASORA_OPT_SKIP_ZERO_RATES): a thick cell whose tau_in lies beyond the last table entry gets
             // pref * (T_last - T_last) = exactly +0; adding it changes nothing, so the atomic is not issued -- and when no
             // lane of the wave has anything to add, neither are the division, the logarithms and the lookups.  (pref must
@@ -720,12 +638,8 @@ __global__ void __launch_bounds__(RT_THREADS, (RT_THREADS <= 512 ? (NSRC == 2 ? 
                 if (wave_adds) {
 #pragma unroll
                     for (int q = 0; q < NSRC; ++q) {
-#ifdef ASORA_DIAG_NO_DIVISION
-                        pref[q] = flux[q] * __builtin_amdgcn_rcp(vol_nhi[q]);
-#else
                         // (nHI = 0 -- a fully ionised or empty cell: the reference divides by zero; flux / +0 = flux * inf)
-                        pref[q] = vol_nhi[q] == 0.0 ? flux[q] * INFINITY : ASORA_DIV(flux[q], vol_nhi[q]);
-#endif
+                        pref[q] = vol_nhi[q] == 0.0 ? flux[q] * INFINITY : div_newton(flux[q], vol_nhi[q]);
                         A2[q] = lookup_issue<HEAT>(tab, arg_A[q], p, logtab, toff[q]);
                         B2[q] = lookup_issue<HEAT>(tab, arg_B[q], p, logtab, SUBBOX ? 0 : toff[q]);
                     }
@@ -785,36 +699,6 @@ __global__ void __launch_bounds__(RT_THREADS, (RT_THREADS <= 512 ? (NSRC == 2 ? 
                     else { late_idx[q] = dst_idx[q]; late_ok[q] = add[q]; }
                 }
             }
-#elif ASORA_LATE_ATOMIC
-            const double pref = flux[0] / vol_nhi[0];
-            const Lookup A = lookup_issue<HEAT>(tab, arg_A[0], p, logtab, toff[0]);
-            const Lookup B = lookup_issue<HEAT>(tab, arg_B[0], p, logtab, toff[0]);
-            // the previous step's rate, behind this step's lookups in the memory pipeline
-            add_phi(late_ok[0], late_idx[0], late_v[0]);
-            if (HEAT) add_heat(late_ok[0], late_idx[0], late_h[0]);
-            {
-                const double ta = lookup_value(A), tb = lookup_value(B);
-                late_v[0] = thick[0] ? pref * (ta - tb) : pref * dtau[0] * ta;     // see rate_value on the form of the difference
-                if (HEAT) {      // photorates.f90:118,124 with the same table index and residual
-                    const double ha = lookup_heat(A), hb = lookup_heat(B);
-                    late_h[0] = thick[0] ? pref * (ha - hb) : pref * dtau[0] * ha;
-                }
-                late_idx[0] = dst_idx[0];
-                late_ok[0] = rated[0];
-            }
-#else
-            const double pref = flux[0] / vol_nhi[0];
-            const Lookup A = lookup_issue<HEAT>(tab, arg_A[0], p, logtab, toff[0]);
-            const Lookup B = lookup_issue<HEAT>(tab, arg_B[0], p, logtab, toff[0]);
-            {
-                const double ta = lookup_value(A), tb = lookup_value(B);
-                add_phi(rated[0], dst_idx[0], thick[0] ? pref * (ta - tb) : pref * dtau[0] * ta);
-                if (HEAT) {      // photorates.f90:118,124 with the same table index and residual
-                    const double ha = lookup_heat(A), hb = lookup_heat(B);
-                    add_heat(rated[0], dst_idx[0], thick[0] ? pref * (ha - hb) : pref * dtau[0] * ha);
-                }
-            }
-#endif
         }
     };
 
@@ -831,7 +715,6 @@ __global__ void __launch_bounds__(RT_THREADS, (RT_THREADS <= 512 ? (NSRC == 2 ? 
         idx1[q] = idx2[q] = 0; nhi1[q] = nhi2[q] = 0.0;
         nhi0[q] = *nhi_address(q, A0.x, A0.y, idx0[q]);
     }
-#if ASORA_LATE_LOOKUP && ASORA_PRIME_PIPELINE
     // The loop is entered with the loads in flight that a step leaves behind, in the same order (tables, nHI, two lookups):
     // the compiler merges the counts of outstanding operations of the loop entry with those of the back edge and waits as
     // the SHORTER history demands, so without these two (unused) lookups every first step of the unrolled three waited
@@ -856,7 +739,6 @@ __global__ void __launch_bounds__(RT_THREADS, (RT_THREADS <= 512 ? (NSRC == 2 ? 
             }
         }
     }
-#endif
 
     // nsteps is a multiple of 3 (the tables are padded to it) and is followed by two more
     // all-invalid steps, so every look-ahead stays inside the tables.
@@ -875,7 +757,6 @@ __global__ void __launch_bounds__(RT_THREADS, (RT_THREADS <= 512 ? (NSRC == 2 ? 
     }
 #pragma unroll
     for (int q = 0; q < NSRC; ++q) {
-#if ASORA_LATE_LOOKUP
         const double ta = lookup_value(pend_A[q]), tb = lookup_value(pend_B[q]);
         const double v_last = pend_thick[q] ? pend_pref[q] * (ta - tb) : pend_pref[q] * pend_dtau[q] * ta;
         if (BUFATOM) add_phi_at(late_off[q], v_last); else add_phi(late_ok[q], late_idx[q], v_last);
@@ -884,10 +765,6 @@ __global__ void __launch_bounds__(RT_THREADS, (RT_THREADS <= 512 ? (NSRC == 2 ? 
             const double h_last = pend_thick[q] ? pend_pref[q] * (ha - hb) : pend_pref[q] * pend_dtau[q] * ha;
             if (BUFATOM) add_heat_at(late_off[q], h_last); else add_heat(late_ok[q], late_idx[q], h_last);
         }
-#else
-        add_phi(late_ok[q], late_idx[q], late_v[q]);
-        if (HEAT) add_heat(late_ok[q], late_idx[q], late_h[q]);
-#endif
     }
 
     if (SUBBOX) {
@@ -1255,10 +1132,7 @@ int launch_raytrace(State &st, RtParams &p, bool dump, bool heat, hipStream_t si
         fixed_bytes = lds_table_bytes(pairs_tiny ? 32 : pairs_small ? 64 : 256, 2);
         shell_bytes *= 2;
     }
-    size_t lds_bytes = (use_lds ? shell_bytes : 0) + fixed_bytes;
-#ifdef ASORA_ENABLE_ABLATION        // diagnostic builds only: unused LDS per workgroup, to lower the occupancy (ASORA_DIAG_EXTRA_LDS bytes)
-    if (const char *e = getenv("ASORA_DIAG_EXTRA_LDS")) lds_bytes = std::min<size_t>(LDS_LIMIT_BYTES, lds_bytes + (size_t)atol(e));
-#endif
+    const size_t lds_bytes = (use_lds ? shell_bytes : 0) + fixed_bytes;
     // launches that share the global shell scratch stay on the main stream (one at a time)
     hipStream_t stream = (side && use_lds) ? side : st.stream;
     if (side && !use_lds) {       // ... behind whatever the side streams still run, and the side streams behind it

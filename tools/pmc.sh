@@ -1,8 +1,7 @@
 # usage: bash tools/pmc.sh TAG [bench.py arguments...]  -- PMC passes of bench.py (2 timed steps), one counter group per pass
 # (FETCH_SIZE and WRITE_SIZE in passes of their own, never combined with trace domains); per-kernel means of every counter
-# land in gpurun_out/pmc_TAG_summary.txt.  ASORA_ABLATE in the environment is passed through (diagnostic builds only).
+# land in pmc_TAG_summary.txt in the output directory under the repository root.
 export TMPDIR=/tmp; R=${GRAFT_REPO_ROOT:?set GRAFT_REPO_ROOT (gpurun exports it) to the repository root}; TAG=$1; shift
-export ASORA_ABLATE=${ASORA_ABLATE:-0}
 cd /tmp
 i=0
 for C in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_LDS" \

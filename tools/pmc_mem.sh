@@ -1,9 +1,8 @@
 # usage: bash tools/pmc_mem.sh TAG [bench.py arguments...]  -- like tools/pmc.sh, for the vector-memory pipeline (TA, TCP = L1, TCC = L2):
 # request counts, summed latencies (mean latency = LATENCY / REQ, in cycles) and stall cycles, one counter group per pass
 # (FETCH_SIZE and WRITE_SIZE in passes of their own, never combined with trace domains); per-kernel means of every counter
-# land in gpurun_out/pmc_TAG_summary.txt.  ASORA_ABLATE in the environment is passed through (diagnostic builds only).
+# land in pmcmem_TAG_summary.txt in the output directory under the repository root.
 export TMPDIR=/tmp; R=${GRAFT_REPO_ROOT:?set GRAFT_REPO_ROOT (gpurun exports it) to the repository root}; TAG=$1; shift
-export ASORA_ABLATE=${ASORA_ABLATE:-0}
 cd /tmp
 i=0
 for C in "TCP_TCC_READ_REQ_LATENCY_sum TCP_TCC_READ_REQ_sum TCP_TCC_WRITE_REQ_LATENCY_sum TCP_TCC_WRITE_REQ_sum" \
