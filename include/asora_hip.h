@@ -125,7 +125,8 @@ enum {
     ASORA_GRID_XH_INTERMED = 5, /* end-of-step ionised fraction                         */
     ASORA_GRID_PHI_HEAT = 6,    /* photo-heating rate (only filled when heating is on)  */
     ASORA_GRID_TEMP_END = 7,    /* end-of-step temperature (thermal mode only)          */
-    ASORA_GRID_COUNT = 8
+    ASORA_GRID_CLUMP = 8,       /* sub-grid clumping factor <n^2>/<n>^2 (asora_clumping mode 2 only) */
+    ASORA_GRID_COUNT = 9
 };
 
 /* Upload / download one N^3 grid.  order = 'C': buffer is logical [i][j][k] C-contiguous;
@@ -302,6 +303,21 @@ int asora_thermal_params(int enable, double relative_denergy, double t_floor, in
 /* Substep statistics of the thermal passes since the last asora_chemistry_device / asora_evolve_begin (summed over the
  * passes of a step): cells whose integration hit max_substeps, cells clamped to t_floor, most substeps of one integration. */
 int asora_thermal_stats(long long *cells_max_substeps, long long *cells_floored, int *max_substeps_used);
+
+/* Sub-grid clumping factor C = <n^2>/<n>^2 of the case-B recombination rate: doric's
+ * brech0 = C bh00 (T/1e4)^albpow (src/c2ray/chemistry.f90:257), the slot the reference fills with 1.  Nothing else is
+ * clumped: collisional and photo-ionisation, the raytrace and c2ray_global_pass are not; in thermal mode the case-B
+ * recombination cooling is (the same n_e n_HII process).
+ *   mode 0  off (the default, and the reference's behaviour); `constant` is ignored
+ *   mode 1  one factor `constant` for the whole grid
+ *   mode 2  per cell, from ASORA_GRID_CLUMP (uploaded with asora_grid_to_device in either order; allocated on first
+ *           upload, so a run without it allocates nothing); `constant` is ignored
+ * Every chemistry entry honours the mode: asora_chemistry_device, asora_chemistry_range, asora_evolve_begin /
+ * _enqueue, the asora_evolve_slab_* loop and the thermal passes.  Set it before asora_evolve_begin(_slab): the uniform-
+ * temperature pass takes its recombination factor from the probe made there.  Fails with code 3 for a constant that is not
+ * finite and > 0 (mode 1) or an unknown mode, with code 4 for mode 2 without ASORA_GRID_CLUMP on the device.  The mode
+ * holds until it is set again or the device is re-initialised. */
+int asora_clumping(int mode, double constant);
 
 /* ------------------------------------------------------------------------------------------ */
 /* C. Options, measurement and diagnostics                                                     */

@@ -17,6 +17,8 @@ Differences from the reference:
     between time steps and cross PCIe only when the host touches them; see :class:`C2Ray`.
   * ``Material: isothermal: false`` (optional key, default true) evolves the temperature from photo-heating and radiative
     cooling (pyc2ray_amd/thermal.py); it needs ``compute_heating_rates: 1``, ``use_gpu`` and no ``use_mpi``.
+  * ``Material: clumping: C`` (optional key, default 1) and the attribute ``clumping`` (a float, or an (N, N, N) grid assigned
+    between steps) set the sub-grid clumping factor of the recombination rate (evolve3D's ``clumping=``).
 """
 import atexit
 import re
@@ -192,6 +194,7 @@ class C2Ray:
 
         self._read_paramfile(paramfile)
         self._thermal_mode_init(use_gpu, use_mpi)
+        self._clumping_init()
         self.N = Nmesh
         self.shape = (Nmesh, Nmesh, Nmesh)
 
@@ -252,6 +255,34 @@ class C2Ray:
                              zred=float(self.zred) if self.cosmological else None,
                              tcmb0=float(self._ld['Cosmology']['cmbtemp']))
 
+    def _clumping_init(self):
+        """The optional key ``Material: clumping`` (absent: 1, the reference's behaviour): one sub-grid clumping factor
+        C = <n^2>/<n>^2 of the recombination rate for the whole run, until ``clumping`` is assigned."""
+        c = self._ld.get('Material', {}).get('clumping', 1.0)
+        if isinstance(c, bool) or not isinstance(c, (int, float)) or not (np.isfinite(c) and c > 0):
+            raise ValueError(f"Material: clumping must be a finite number > 0, not {c!r}")
+        self.__dict__["_clumping"] = float(c)
+
+    @property
+    def clumping(self):
+        """The clumping factor of the next steps: a float (1: off), or an (N, N, N) float64 grid of factors.  A driver may assign
+        either between steps (a redshift-dependent fit, a clumping field of its own).  On the device-resident path a grid stays on
+        the device across steps and is uploaded again only when the attribute was assigned or READ since the last step (a read
+        hands out the array, which may be written into)."""
+        c = self.__dict__.get("_clumping", 1.0)
+        if isinstance(c, np.ndarray):
+            self._host_newer.add("clumping")
+        return c
+
+    @clumping.setter
+    def clumping(self, value):
+        from .evolve import _clumping_spec
+        _clumping_spec(value, self.N)                          # ValueError for what evolve3D would refuse, now
+        if not (isinstance(value, np.ndarray) and value.ndim == 3):
+            value = 1.0 if value is None else float(value)
+        self.__dict__["_clumping"] = value
+        self._host_newer.add("clumping")
+
     def evolve3D(self, dt, src_flux, src_pos):
         """Evolve the grid over one time step (c2ray_base.py:170-226)."""
         if self.device_resident and self.gpu and not self.mpi:
@@ -261,7 +292,7 @@ class C2Ray:
                 dt, self.dr, src_flux, src_pos, self.gpu, self.max_subbox, self.subboxsize, self.loss_fraction, self.temp,
                 self.ndens, self.xh, self.photo_thin_table, self.photo_thick_table, self.minlogtau, self.dlogtau,
                 self.R_max_LLS, self.convergence_fraction, self.sig, self.bh00, self.albpow, self.colh0, self.temph0,
-                self.abu_c, self.logfile, thermal=self._thermal_params())
+                self.abu_c, self.logfile, thermal=self._thermal_params(), clumping=self.__dict__["_clumping"])
             return
         args = (self.temp, self.ndens, self.xh, self.photo_thin_table, self.photo_thick_table, self.minlogtau,
                 self.dlogtau, self.R_max_LLS, self.convergence_fraction, self.sig, self.bh00, self.albpow,
@@ -269,10 +300,10 @@ class C2Ray:
         if self.mpi and src_flux.shape[0] >= self.nprocs:
             self.xh, self.phi_ion = evolve3D_MPI(dt, self.dr, src_flux, src_pos, self.gpu, self.max_subbox,
                                                  self.subboxsize, self.loss_fraction, self.mpi, self.comm, self.rank,
-                                                 self.nprocs, *args)
+                                                 self.nprocs, *args, clumping=self.__dict__["_clumping"])
         else:
             self.xh, self.phi_ion = evolve3D(dt, self.dr, src_flux, src_pos, self.gpu, self.max_subbox,
-                                             self.subboxsize, self.loss_fraction, *args)
+                                             self.subboxsize, self.loss_fraction, *args, clumping=self.__dict__["_clumping"])
 
     @classmethod
     def _fingerprint(cls, arr):
@@ -305,7 +336,7 @@ class C2Ray:
             if name in self._device_newer and ("_grid_" + name) in self.__dict__:
                 getattr(self, name)                              # (downloads; marks the host copy as the newer one)
         self._device_newer.clear()
-        self._host_newer |= {"ndens", "temp", "xh"}
+        self._host_newer |= {"ndens", "temp", "xh", "clumping"}
         self.__dict__.pop("_grid_fingerprints", None)
 
     def _evolve3D_resident(self, dt, src_flux, src_pos):
@@ -323,13 +354,16 @@ class C2Ray:
                 uploads[which] = host
                 if name != "xh":
                     prints[name] = self._fingerprint(host)
+        clumping = d["_clumping"]
+        if isinstance(clumping, np.ndarray) and "clumping" in self._host_newer:
+            uploads[_capi.GRID_CLUMP] = clumping                # (else GRID_CLUMP holds it from an earlier step)
         phi_host = d.get("_grid_phi_ion")                       # (a subclass may never have assigned phi_ion)
         if phi_host is None or (phi_host.flags.f_contiguous and not phi_host.flags.c_contiguous):
             d["_grid_phi_ion"] = np.zeros(self.shape)           # the GPU path returns C-ordered rates (evolve.py:200)
         evolve3D_resident(dt, self.dr, src_flux, src_pos, uploads, self.N, self.photo_thin_table, self.minlogtau, self.dlogtau,
                           self.R_max_LLS, self.convergence_fraction, self.sig, self.bh00, self.albpow, self.colh0, self.temph0,
-                          self.abu_c, self.logfile, thermal=self._thermal_params())
-        self._host_newer -= {"ndens", "temp", "xh", "phi_ion"}
+                          self.abu_c, self.logfile, thermal=self._thermal_params(), clumping=clumping)
+        self._host_newer -= {"ndens", "temp", "xh", "phi_ion", "clumping"}
         self._device_newer |= {"xh", "phi_ion"} if self.isothermal else {"xh", "phi_ion", "temp"}
 
     def cosmo_evolve(self, dt):

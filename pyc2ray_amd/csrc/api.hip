@@ -94,16 +94,21 @@ static int ensure_runtime()
 
 // One temperature for the whole grid?  Probed once per upload of TEMP and set of chemistry constants (one pass over the
 // grid + a 40-byte read-back); the tiled chemistry pass then needs neither the temperature loads nor pow/sqrt/exp.
+// Clumping mode 1 (asora_clumping) folds its constant into bh00 first, as the launchers do for the per-cell path: brech0 =
+// (C bh00) (T/1e4)^albpow, doric's order.
 static int ensure_temp_probe(double bh00, double albpow, double colh0, double temph0)
 {
     State &st = g_state;
-    const double c[4] = {bh00, albpow, colh0, temph0};
-    if (st.temp_probe_valid && std::memcmp(c, st.temp_consts, sizeof c) == 0) return 0;
+    const double clump = st.clump_mode == 1 ? st.clump_c : 1.0;
+    const double b = clump * bh00;
+    const double c[4] = {b, albpow, colh0, temph0};
+    if (st.temp_probe_valid && std::memcmp(c, st.temp_consts, sizeof c) == 0 && st.temp_probe_clump == clump) return 0;
     if (!st.temp_probe_dev) ASORA_HIP_TRY(hipMalloc(&st.temp_probe_dev, sizeof(double) * 8));
-    if (int rc = launch_temp_probe(st, st.grid[ASORA_GRID_TEMP], st.ncell, bh00, albpow, colh0, temph0, st.temp_probe_dev)) return rc;
+    if (int rc = launch_temp_probe(st, st.grid[ASORA_GRID_TEMP], st.ncell, b, albpow, colh0, temph0, st.temp_probe_dev)) return rc;
     ASORA_HIP_TRY(hipMemcpyAsync(st.temp_probe, st.temp_probe_dev, sizeof(double) * 5, hipMemcpyDeviceToHost, st.stream));
     ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
     std::memcpy(st.temp_consts, c, sizeof c);
+    st.temp_probe_clump = clump;
     st.temp_probe_valid = true;
     return 0;
 }
@@ -149,6 +154,15 @@ static int ensure_temp_end_grid()
     st.grid_valid[ASORA_GRID_TEMP_END] = false;
     return 0;
 }
+// Clumping mode 2 only (asora_clumping): the per-cell factors, allocated on their first upload
+static int ensure_clump_grid()
+{
+    State &st = g_state;
+    if (st.grid[ASORA_GRID_CLUMP]) return 0;
+    ASORA_HIP_TRY(hipMalloc(&st.grid[ASORA_GRID_CLUMP], st.ncell * sizeof(double)));
+    st.grid_valid[ASORA_GRID_CLUMP] = false;
+    return 0;
+}
 static int ensure_heat_acc()
 {
     State &st = g_state;
@@ -168,6 +182,8 @@ static int release_all()
     drop(st.grid[ASORA_GRID_TEMP_END]); drop(st.heat_acc); drop(st.th_stats_dev);
     st.heat_clean[0] = st.heat_clean[1] = false;
     st.th_on = false; st.th = ThermalConsts();
+    drop(st.grid[ASORA_GRID_CLUMP]);
+    st.clump_mode = 0; st.clump_c = 1.0;
     for (int g = 0; g < ASORA_GRID_COUNT; ++g) { st.grid[g] = nullptr; st.grid_valid[g] = false; }
     st.nhi = st.staging = st.acc = nullptr;
     drop(st.arena); st.arena_bytes = 0;
@@ -846,7 +862,7 @@ int asora_device_init_ex(int N, int num_src_par, int device_id)
         st.staging = take(1);
     }
     for (int g = 0; g < ASORA_GRID_COUNT; ++g)
-        if (g != ASORA_GRID_PHI_HEAT && g != ASORA_GRID_TEMP_END && !st.grid[g]) return fail(11, "device_init: a grid without a place in the arena (internal error)");
+        if (g != ASORA_GRID_PHI_HEAT && g != ASORA_GRID_TEMP_END && g != ASORA_GRID_CLUMP && !st.grid[g]) return fail(11, "device_init: a grid without a place in the arena (internal error)");
     st.nhi_t = st.nhi + st.ncell;
     st.phi_t = st.grid[ASORA_GRID_PHI_ION] + st.ncell;
     st.heat_t = nullptr;
@@ -890,6 +906,7 @@ int asora_grid_to_device(int which, const double *host, int N, char order)
     State &st = g_state;
     if (which == ASORA_GRID_PHI_HEAT) { if (int rc = ensure_heat_grid()) return rc; }
     if (which == ASORA_GRID_TEMP_END) { if (int rc = ensure_temp_end_grid()) return rc; }
+    if (which == ASORA_GRID_CLUMP) { if (int rc = ensure_clump_grid()) return rc; }
     st.zero_since_probe = std::max(st.zero_since_probe, 48);   // new medium: look again for cells beyond the table soon (launch_raytrace: at 64)
     const size_t bytes = st.ncell * sizeof(double);
     if (order == 'C' || order == 'c') {
@@ -936,6 +953,7 @@ int asora_grid_copy(int dst, int src)
     if (!st.grid_valid[src]) return fail(3, "grid_copy: source grid holds no data");
     if (dst == ASORA_GRID_PHI_HEAT) { if (int rc = ensure_heat_grid()) return rc; }
     if (dst == ASORA_GRID_TEMP_END) { if (int rc = ensure_temp_end_grid()) return rc; }
+    if (dst == ASORA_GRID_CLUMP) { if (int rc = ensure_clump_grid()) return rc; }
     ASORA_HIP_TRY(hipMemcpyAsync(st.grid[dst], st.grid[src], st.ncell * sizeof(double), hipMemcpyDeviceToDevice,
                                  st.stream));
     st.grid_valid[dst] = true;
@@ -1293,7 +1311,7 @@ int c2ray_global_pass(double dt, const double *ndens, const double *temp, const 
     p.dt = dt; p.bh00 = bh00; p.albpow = albpow; p.colh0 = colh0; p.temph0 = temph0; p.abu_c = abu_c;
     p.ndens = d[0]; p.temp = d[1]; p.xh = d[2]; p.xh_av = d[3]; p.xh_intermed = d[4]; p.phi = d[5];
     p.red_partial = st.red_partial; p.red_final = st.red_final; p.red_blocks = st.red_blocks;
-    rc = launch_chemistry(st, p, st.stream);
+    rc = launch_chemistry(st, p, st.stream, false);     // (the reference's f2py boundary: no clumping argument)
     if (!rc) {
         hipError_t e = hipMemcpyAsync(xh_av, d[3], bytes, hipMemcpyDeviceToHost, st.stream);
         if (e == hipSuccess) e = hipMemcpyAsync(xh_intermed, d[4], bytes, hipMemcpyDeviceToHost, st.stream);
@@ -1931,6 +1949,29 @@ int asora_thermal_params(int enable, double relative_denergy, double t_floor, in
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Clumping of the recombination rate (include/asora_hip.h; chemistry.hip: clumping_of)
+// ---------------------------------------------------------------------------------------------
+int asora_clumping(int mode, double constant)
+{
+    clear_error();
+    State &st = g_state;
+    if (mode == 0) { st.clump_mode = 0; st.clump_c = 1.0; return 0; }     // (also without a device: nothing to switch off)
+    if (int rc = require_init("clumping")) return rc;
+    if (mode == 1) {
+        if (!(std::isfinite(constant) && constant > 0.0)) return fail(3, "clumping: the constant must be finite and > 0");
+        st.clump_mode = 1; st.clump_c = constant;
+        return 0;
+    }
+    if (mode == 2) {
+        if (!st.grid[ASORA_GRID_CLUMP] || !st.grid_valid[ASORA_GRID_CLUMP])
+            return fail(4, "clumping: mode 2 needs the factors on the device (asora_grid_to_device(ASORA_GRID_CLUMP, ...))");
+        st.clump_mode = 2; st.clump_c = 1.0;
+        return 0;
+    }
+    return fail(3, "clumping: mode must be 0 (off), 1 (constant) or 2 (per cell)");
+}
+
 int asora_thermal_stats(long long *cells_max_substeps, long long *cells_floored, int *max_substeps_used)
 {
     clear_error();
@@ -1977,6 +2018,7 @@ int asora_planes_to_device(int which, int i_begin, int i_count, const double *ho
     if (!host) return fail(3, "planes_to_device: null host pointer");
     if (which == ASORA_GRID_PHI_HEAT) { if (int rc = ensure_heat_grid()) return rc; }
     if (which == ASORA_GRID_TEMP_END) { if (int rc = ensure_temp_end_grid()) return rc; }
+    if (which == ASORA_GRID_CLUMP) { if (int rc = ensure_clump_grid()) return rc; }
     const size_t plane = (size_t)st.N * st.N;
     ASORA_HIP_TRY(hipMemcpyAsync(st.grid[which] + (size_t)i_begin * plane, host, (size_t)i_count * plane * sizeof(double),
                                  hipMemcpyHostToDevice, st.stream));

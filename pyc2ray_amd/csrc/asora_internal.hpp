@@ -126,8 +126,8 @@ struct State {
     int num_src_par = 0;           // accepted, unused (no per-source N^3 scratch in this build)
     int cu_count = 256;
 
-    double *grid[ASORA_GRID_COUNT] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    bool grid_valid[ASORA_GRID_COUNT] = {false, false, false, false, false, false, false, false};
+    double *grid[ASORA_GRID_COUNT] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool grid_valid[ASORA_GRID_COUNT] = {false, false, false, false, false, false, false, false, false};
 
     // derived per raytrace call
     // each of these is the second half of a 2 N^3 allocation whose first half is the [i][j][k] grid
@@ -280,6 +280,13 @@ struct State {
     bool heat_clean[2] = {false, false};    // pair known to be all zero
     unsigned long long *th_stats_dev = nullptr;   // [3]: cells at max_substeps, cells floored, most substeps
 
+    // sub-grid clumping of the recombination rate (asora_clumping): 0 off, 1 one constant, 2 per cell (ASORA_GRID_CLUMP, allocated
+    // on first upload).  The launchers of the chemistry passes apply it (chemistry.hip); temp_probe_clump is the factor the
+    // uniform-temperature probe folded into its brech0 (the constant in mode 1, else 1)
+    int clump_mode = 0;
+    double clump_c = 1.0;
+    double temp_probe_clump = 1.0;
+
     hipStream_t stream = nullptr;
     struct PendingTimer { int which; hipEvent_t e0, e1; };
     std::vector<PendingTimer> pending_timers;     // recorded, not yet resolved
@@ -404,8 +411,13 @@ struct ChemParams {
     double *temp_end = nullptr;
     unsigned long long *th_stats = nullptr;
     ThermalConsts th;
+    // clumping (set by launch_chemistry from State::clump_mode; appended, so the fields above keep their offsets): the per-cell
+    // factors, or nullptr with the one factor clump_c (thermal form only: the isothermal constant scales bh00 instead)
+    const double *clump = nullptr;
+    double clump_c = 1.0;
 };
-int launch_chemistry(State &st, ChemParams &p, hipStream_t stream);
+// clumped = false: State::clump_mode is not applied (c2ray_global_pass, the reference's f2py boundary, has no clumping argument)
+int launch_chemistry(State &st, ChemParams &p, hipStream_t stream, bool clumped = true);
 int chemistry_reduction_blocks(const State &st);
 
 // The same pass over the planes [i_begin, i_end) of the N^3 grids, tiled so that the [k][j][i] twins can be read and
@@ -441,6 +453,9 @@ struct ChemTileParams {
     double *temp_end = nullptr;
     unsigned long long *th_stats = nullptr;
     ThermalConsts th;
+    // clumping: set by launch_chemistry_tiles from State::clump_mode, as ChemParams::clump / clump_c
+    const double *clump = nullptr;
+    double clump_c = 1.0;
 };
 int launch_grid_sum(State &st, const double *a, size_t n, double *out_dev);
 int launch_scale(State &st, double *a, size_t n, double factor);

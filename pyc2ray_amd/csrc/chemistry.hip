@@ -38,8 +38,11 @@ __device__ __forceinline__ void temperature_factors(const ChemParams &p, double 
 }
 
 // One cell: do_chemistry + the convergence test of evolve0D_global.
+// CLUMP: the recombination rate of the cell is clump x tf.brech0 (asora_clumping mode 2)
+template <bool CLUMP = false>
 __device__ __forceinline__ void chemistry_cell(const ChemParams &p, double n, double x0, double gamma,
-                                               double &xav, double &xint, unsigned int &nconv, const TempFactors &tf)
+                                               double &xav, double &xint, unsigned int &nconv, const TempFactors &tf,
+                                               double clump = 1.0)
 {
     // single-precision parameters promoted to double, chemistry.f90:9-10
     const double min_frac_change = (double)1.0e-3f;
@@ -49,7 +52,7 @@ __device__ __forceinline__ void chemistry_cell(const ChemParams &p, double n, do
     const double xav_start = xav;                                    // chemistry.f90:91,99
     const double yh_av = 1.0 - xav;                                  // chemistry.f90:93
 
-    const double brech0 = tf.brech0, acolh0 = tf.acolh0;
+    const double brech0 = CLUMP ? clump * tf.brech0 : tf.brech0, acolh0 = tf.acolh0;
     const bool t_ok = tf.t_ok;
 
     int nit = 0;
@@ -91,14 +94,18 @@ constexpr double COMPTON_A_RAD = 4.0 * CODATA_SIGMA_SB / CODATA_C;
 constexpr double COMPTON_C = 4.0 * CODATA_SIGMA_T * COMPTON_A_RAD * CODATA_KB / (CODATA_ME * CODATA_C);
 
 // Lambda(T) in erg s^-1 cm^-3
+// CLUMP: the case-B recombination channel is clumped like the recombination rate (x clump, last); the other channels are not
+template <bool CLUMP = false>
 __device__ __forceinline__ double thermal_cooling(const ThermalConsts &c, double T, double n_e, double n_HII, double n_HI,
-                                                  double colh0, double temph0)
+                                                  double colh0, double temph0, double clump = 1.0)
 {
 #pragma clang fp contract(off)
     double L = 0.0;
     if (c.cooling_mask & THERMAL_COOL_RECOMB) {            // case-B recombination, Hui & Gnedin (1997)
         const double lam = 2.0 * 157807.0 / T;
-        L += 3.435e-30 * T * pow(lam, 1.970) / pow(1.0 + pow(lam / 2.25, 0.376), 3.720) * n_e * n_HII;
+        double rec = 3.435e-30 * T * pow(lam, 1.970) / pow(1.0 + pow(lam / 2.25, 0.376), 3.720) * n_e * n_HII;
+        if (CLUMP) rec = rec * clump;
+        L += rec;
     }
     if (c.cooling_mask & THERMAL_COOL_COLION)              // collisional ionisation: doric's rate (chemistry.f90:262) x the ionisation energy
         L += THERMAL_KB * temph0 * colh0 * sqrt(T) * exp(-temph0 / T) * n_e * n_HI;
@@ -123,9 +130,10 @@ struct ThermalTally {
 
 // thermal(T_start, x, phi_heat) -> (T_end, T_av): explicit substeps limited to a relative change `relative_denergy` of the
 // thermal energy 1.5 k_B n_p T, n_p held at its value for x; the last substep ends exactly at dt.
+template <bool CLUMP = false>
 __device__ __forceinline__ void thermal_integrate(const ThermalConsts &c, double dt, double abu_c, double colh0, double temph0,
                                                   double n, double x, double phi_heat, double T_start, double &T_end,
-                                                  double &T_av, bool &capped, bool &floored, int &max_sub)
+                                                  double &T_av, bool &capped, bool &floored, int &max_sub, double clump = 1.0)
 {
 #pragma clang fp contract(off)
     const double n_e = n * (x + abu_c), n_HII = n * x, n_HI = n * (1.0 - x);
@@ -136,7 +144,7 @@ __device__ __forceinline__ void thermal_integrate(const ThermalConsts &c, double
     int k = 0;
     for (;;) {
         k += 1;
-        const double r = H - thermal_cooling(c, T, n_e, n_HII, n_HI, colh0, temph0);
+        const double r = H - thermal_cooling<CLUMP>(c, T, n_e, n_HII, n_HI, colh0, temph0, clump);
         double h = dt - t;
         bool last = true;
         if (k < c.max_substeps && r != 0.0) {
@@ -161,9 +169,11 @@ __device__ __forceinline__ void thermal_integrate(const ThermalConsts &c, double
 // The rate factors follow the average temperature of the previous inner iteration (T_start for the first); the exit test
 // takes the change of the end-of-step temperature as well.
 // (the loop state lives in locals; the references are written once, at the end)
+// CLUMP: recombination rate and recombination cooling x clump (asora_clumping mode 1 or 2)
+template <bool CLUMP = false>
 __device__ __forceinline__ void chemistry_cell_thermal(const ChemParams &p, double n, double x0, double gamma, double phi_heat,
                                                        double T_start, double &xav_io, double &xint_out, double &T_end_out,
-                                                       unsigned int &nconv, ThermalTally &tally)
+                                                       unsigned int &nconv, ThermalTally &tally, double clump = 1.0)
 {
 #pragma clang fp contract(off)
     const double min_frac_change = (double)1.0e-3f;
@@ -182,7 +192,8 @@ __device__ __forceinline__ void chemistry_cell_thermal(const ChemParams &p, doub
         nit += 1;
         const double xav_old = xav, T_prev = T_end;
         const double de = n * (xav + p.abu_c);
-        const double brech0 = 1.0 * p.bh00 * pow(T_av / 1e4, p.albpow);     // ini_rec_colion_factors(T_av)
+        double brech0 = 1.0 * p.bh00 * pow(T_av / 1e4, p.albpow);           // ini_rec_colion_factors(T_av)
+        if (CLUMP) brech0 = clump * brech0;
         const double acolh0 = p.colh0 * sqrt(T_av) * exp(-p.temph0 / T_av);
         const double aih0 = gamma + de * acolh0;
         const double delth = aih0 + de * brech0;
@@ -194,8 +205,8 @@ __device__ __forceinline__ void chemistry_cell_thermal(const ChemParams &p, doub
         const double avg = (deltht < (double)1.0e-8f) ? 1.0 : (1.0 - ee) / deltht;
         xav = eqxh + (x0 - eqxh) * avg;
         if (xav < eps) xav = eps;
-        thermal_integrate(p.th, p.dt, p.abu_c, p.colh0, p.temph0, n, xav, phi_heat, T_start, T_end, T_av, capped, floored,
-                          max_sub);
+        thermal_integrate<CLUMP>(p.th, p.dt, p.abu_c, p.colh0, p.temph0, n, xav, phi_heat, T_start, T_end, T_av, capped, floored,
+                                 max_sub, clump);
         const bool t_ok = fabs((T_end - T_prev) / T_end) < min_frac_change;
         if ((fabs((xav - xav_old) / (1.0 - xav)) < min_frac_change || (1.0 - xav < min_frac_atoms)) && t_ok)
             break;
@@ -229,7 +240,9 @@ __device__ __forceinline__ void thermal_tally_flush(unsigned long long *stats, T
 
 // Two consecutive cells per lane: 16-byte loads and stores (the grids are 256-byte aligned).
 // THERMAL: chemistry_cell_thermal, with the heating rates and the start temperature in and the end temperature out.
-template <bool THERMAL>
+// CLUMP: clumped recombination (launch_chemistry): the factors of p.clump, one more 8-byte load per cell; thermal form also
+// p.clump_c when p.clump is nullptr
+template <bool THERMAL, bool CLUMP = false>
 __global__ void __launch_bounds__(CH_THREADS) chemistry_kernel(const ChemParams p)
 {
     double sum1 = 0.0, sum0 = 0.0;
@@ -244,6 +257,7 @@ __global__ void __launch_bounds__(CH_THREADS) chemistry_kernel(const ChemParams 
     const double2 *ph2 = reinterpret_cast<const double2 *>(p.phi);
     double2 *xa2 = reinterpret_cast<double2 *>(p.xh_av);
     double2 *xi2 = reinterpret_cast<double2 *>(p.xh_intermed);
+    const double2 *cl2 = reinterpret_cast<const double2 *>(p.clump);
     ThermalTally tally;
     if (THERMAL) {
         // one cell per lane and trip, the loop kept rolled: ONE inlined copy of the thermal cell (the pair form of the loop
@@ -251,7 +265,8 @@ __global__ void __launch_bounds__(CH_THREADS) chemistry_kernel(const ChemParams 
 #pragma unroll 1
         for (size_t i = (size_t)blockIdx.x * CH_THREADS + threadIdx.x; i < p.ncell; i += stride) {
             double xav = p.xh_av[i], xint, te;
-            chemistry_cell_thermal(p, p.ndens[i], p.xh[i], p.phi[i], p.phi_heat[i], p.temp[i], xav, xint, te, nconv, tally);
+            const double c = !CLUMP ? 1.0 : p.clump ? p.clump[i] : p.clump_c;
+            chemistry_cell_thermal<CLUMP>(p, p.ndens[i], p.xh[i], p.phi[i], p.phi_heat[i], p.temp[i], xav, xint, te, nconv, tally, c);
             p.xh_intermed[i] = xint;
             p.xh_av[i] = xav;
             p.temp_end[i] = te;
@@ -261,10 +276,11 @@ __global__ void __launch_bounds__(CH_THREADS) chemistry_kernel(const ChemParams 
     for (size_t q = (size_t)blockIdx.x * CH_THREADS + threadIdx.x; !THERMAL && q < npair; q += stride) {
         const double2 n = nd2[q], T = tp2[q], x0 = x02[q], g = ph2[q];
         double2 xav = xa2[q], xint;
+        const double2 c = CLUMP ? cl2[q] : make_double2(1.0, 1.0);
         temperature_factors(p, T.x, tf);
-        chemistry_cell(p, n.x, x0.x, g.x, xav.x, xint.x, nconv, tf);
+        chemistry_cell<CLUMP>(p, n.x, x0.x, g.x, xav.x, xint.x, nconv, tf, c.x);
         temperature_factors(p, T.y, tf);
-        chemistry_cell(p, n.y, x0.y, g.y, xav.y, xint.y, nconv, tf);
+        chemistry_cell<CLUMP>(p, n.y, x0.y, g.y, xav.y, xint.y, nconv, tf, c.y);
         xi2[q] = xint;                                               // chemistry.f90:107-108
         xa2[q] = xav;
         sum1 += xint.x; sum0 += 1.0 - xint.x;                        // evolve.py:216-217
@@ -274,7 +290,7 @@ __global__ void __launch_bounds__(CH_THREADS) chemistry_kernel(const ChemParams 
         const size_t idx = p.ncell - 1;
         double xav = p.xh_av[idx], xint;
         temperature_factors(p, p.temp[idx], tf);
-        chemistry_cell(p, p.ndens[idx], p.xh[idx], p.phi[idx], xav, xint, nconv, tf);
+        chemistry_cell<CLUMP>(p, p.ndens[idx], p.xh[idx], p.phi[idx], xav, xint, nconv, tf, CLUMP ? p.clump[idx] : 1.0);
         p.xh_intermed[idx] = xint;
         p.xh_av[idx] = xav;
         sum1 += xint; sum0 += 1.0 - xint;
@@ -369,7 +385,9 @@ __device__ __forceinline__ double stream_load(const double *q) { return __builti
 // THERMAL (with FOLD and EMIT, not UNIFORM_T): chemistry_cell_thermal; the heating accumulators are folded like the rates
 // (tile_h: their [k][j][i] twin), the other heating pair is zeroed for the next trace, the end temperature goes to temp_end.
 // Per cell 8 loads and 9 stores = 136 B.
-template <bool FOLD, bool EMIT, bool UNIFORM_T, bool THERMAL = false>
+// CLUMP (every form; launch_chemistry_tiles): clumped recombination, the factor of the cell streamed from p.clump like the other
+// grids (+8 B per cell) -- or, in the thermal form with p.clump == nullptr, the one factor p.clump_c
+template <bool FOLD, bool EMIT, bool UNIFORM_T, bool THERMAL = false, bool CLUMP = false>
 __global__ void __launch_bounds__(CH_THREADS, 1) chemistry_tile_kernel(const ChemTileParams p)
 {
     static_assert(!THERMAL || (FOLD && EMIT && !UNIFORM_T), "thermal pass: the device loop's fold + emit form only");
@@ -425,16 +443,19 @@ __global__ void __launch_bounds__(CH_THREADS, 1) chemistry_tile_kernel(const Che
                 if (EMIT && reached) p.zero_a[idx] = 0.0;
                 const double n = stream_load(p.ndens + idx);
                 double xav = stream_load(p.xh_av_in + idx), xint;
+                double c = 1.0;
+                if (CLUMP) c = (THERMAL && !p.clump) ? p.clump_c : stream_load(p.clump + idx);
                 if (THERMAL) {
                     double hr = reached ? stream_load(p.heat + idx) : 0.0;
                     hr += tile_h[tx][r];
                     if (reached) p.zero_ha[idx] = 0.0;
                     double te;
-                    chemistry_cell_thermal(cp, n, stream_load(p.xh + idx), g, hr, stream_load(p.temp + idx), xav, xint, te, nconv, tally);
+                    chemistry_cell_thermal<CLUMP>(cp, n, stream_load(p.xh + idx), g, hr, stream_load(p.temp + idx), xav, xint, te, nconv,
+                                                  tally, c);
                     p.temp_end[idx] = te;
                 } else {
                     if (!UNIFORM_T) temperature_factors(cp, stream_load(p.temp + idx), tf);
-                    chemistry_cell(cp, n, stream_load(p.xh + idx), g, xav, xint, nconv, tf);
+                    chemistry_cell<CLUMP>(cp, n, stream_load(p.xh + idx), g, xav, xint, nconv, tf, c);
                 }
                 p.xh_intermed[idx] = xint;                           // chemistry.f90:107-108
                 p.xh_av[idx] = xav;
@@ -590,16 +611,45 @@ int launch_grid_sum(State &st, const double *a, size_t n, double *out_dev)
 
 int chemistry_reduction_blocks(const State &st) { return st.cu_count * 8; }
 
-int launch_chemistry(State &st, ChemParams &p, hipStream_t stream)
+// Clumping (State::clump_mode, asora_clumping) is applied here, for every pass that comes through a launcher:
+//   mode 1, isothermal : bh00 -> C bh00, the unclumped kernel -- doric's own order, (C bh00) (T/1e4)^albpow (chemistry.f90:257)
+//   mode 2, isothermal : the CLUMP form, brech0 of the cell = c x bh00 (T/1e4)^albpow (the cached / probed factor times c)
+//   thermal, mode 1 / 2: the CLUMP form with the constant / the grid (recombination rate and recombination cooling x c)
+// Returns 1 for the CLUMP form, 0 for the unclumped one (bh00 x bh00_factor), or the error code of a failure.
+static int clumping_of(const State &st, bool thermal, size_t ncell, const double *&clump, double &clump_c, double &bh00_factor)
+{
+    clump = nullptr; clump_c = 1.0; bh00_factor = 1.0;
+    if (st.clump_mode == 0) return 0;
+    if (st.clump_mode == 2) {
+        if (!st.grid[ASORA_GRID_CLUMP] || !st.grid_valid[ASORA_GRID_CLUMP] || ncell != st.ncell)
+            return fail(4, "chemistry: clumping mode 2 needs ASORA_GRID_CLUMP on the device");
+        clump = st.grid[ASORA_GRID_CLUMP];
+        return 1;
+    }
+    if (!thermal) { bh00_factor = st.clump_c; return 0; }
+    clump_c = st.clump_c;
+    return 1;
+}
+
+int launch_chemistry(State &st, ChemParams &p, hipStream_t stream, bool clumped)
 {
     const size_t want = std::max<size_t>(1, (p.ncell / 2 + CH_THREADS - 1) / CH_THREADS);
     const int blocks = (int)std::min<size_t>(want, (size_t)p.red_blocks);
     ChemParams q = p;
     q.red_blocks = blocks;
+    int ck = 0;
+    if (clumped) {
+        double f;
+        ck = clumping_of(st, p.thermal, p.ncell, q.clump, q.clump_c, f);
+        if (ck > 1) return ck;
+        q.bh00 = f * p.bh00;
+    }
     {
         KernelTimer kt(ASORA_KERNEL_CHEMISTRY);
-        if (p.thermal) hipLaunchKernelGGL(chemistry_kernel<true>, dim3(blocks), dim3(CH_THREADS), 0, stream, q);
-        else           hipLaunchKernelGGL(chemistry_kernel<false>, dim3(blocks), dim3(CH_THREADS), 0, stream, q);
+        if (p.thermal && ck) hipLaunchKernelGGL((chemistry_kernel<true, true>), dim3(blocks), dim3(CH_THREADS), 0, stream, q);
+        else if (p.thermal)  hipLaunchKernelGGL(chemistry_kernel<true>, dim3(blocks), dim3(CH_THREADS), 0, stream, q);
+        else if (ck)         hipLaunchKernelGGL((chemistry_kernel<false, true>), dim3(blocks), dim3(CH_THREADS), 0, stream, q);
+        else                 hipLaunchKernelGGL(chemistry_kernel<false>, dim3(blocks), dim3(CH_THREADS), 0, stream, q);
         ASORA_HIP_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(chemistry_reduce_kernel, dim3(1), dim3(RED_THREADS), 0, stream,
@@ -625,6 +675,26 @@ size_t chemistry_tile_blocks(const State &st, int N, int planes)
     return (size_t)g.x * g.y * g.z;
 }
 
+template <bool CLUMP>
+static int launch_tile_form(const ChemTileParams &q, dim3 grid, hipStream_t stream)
+{
+    const bool u = q.uniform != 0;
+    if (q.thermal) {
+        if (!(q.fold && q.emit)) return fail(11, "chemistry: the thermal pass exists in the fold + emit form only (internal error)");
+        hipLaunchKernelGGL((chemistry_tile_kernel<true, true, false, true, CLUMP>), grid, dim3(CH_THREADS), 0, stream, q);
+    } else if (q.fold && q.emit) {
+        if (u) hipLaunchKernelGGL((chemistry_tile_kernel<true, true, true, false, CLUMP>), grid, dim3(CH_THREADS), 0, stream, q);
+        else   hipLaunchKernelGGL((chemistry_tile_kernel<true, true, false, false, CLUMP>), grid, dim3(CH_THREADS), 0, stream, q);
+    } else if (!q.fold && !q.emit) {
+        if (u) hipLaunchKernelGGL((chemistry_tile_kernel<false, false, true, false, CLUMP>), grid, dim3(CH_THREADS), 0, stream, q);
+        else   hipLaunchKernelGGL((chemistry_tile_kernel<false, false, false, false, CLUMP>), grid, dim3(CH_THREADS), 0, stream, q);
+    } else if (!q.fold && q.emit) {       // rates already summed over both layouts (and over the ranks): asora_evolve_slab_fold_all
+        if (u) hipLaunchKernelGGL((chemistry_tile_kernel<false, true, true, false, CLUMP>), grid, dim3(CH_THREADS), 0, stream, q);
+        else   hipLaunchKernelGGL((chemistry_tile_kernel<false, true, false, false, CLUMP>), grid, dim3(CH_THREADS), 0, stream, q);
+    } else return fail(11, "chemistry: unsupported fold/emit combination (internal error)");
+    return 0;
+}
+
 int launch_chemistry_tiles(State &st, ChemTileParams &p, hipStream_t stream)
 {
     const int planes = p.i_end - p.i_begin;
@@ -634,22 +704,16 @@ int launch_chemistry_tiles(State &st, ChemTileParams &p, hipStream_t stream)
     if (3 * blocks > st.red_cap) return fail(11, "chemistry: reduction buffer too small (internal error)");
     ChemTileParams q = p;
     q.red_stride = (int)blocks;
+    double f;
+    const int ck = clumping_of(st, p.thermal, st.ncell, q.clump, q.clump_c, f);
+    if (ck > 1) return ck;
+    q.bh00 = f * p.bh00;
+    // the uniform-temperature forms take brech0 from the probe (api.hip: ensure_temp_probe), which folds in the mode-1 constant
+    if (p.uniform && !p.thermal && st.temp_probe_clump != f)
+        return fail(4, "chemistry: the temperature probe was made for another clumping mode (set asora_clumping before asora_evolve_begin)");
     {
         KernelTimer kt(ASORA_KERNEL_CHEMISTRY, stream);
-        const bool u = p.uniform != 0;
-        if (p.thermal) {
-            if (!(p.fold && p.emit)) return fail(11, "chemistry: the thermal pass exists in the fold + emit form only (internal error)");
-            hipLaunchKernelGGL((chemistry_tile_kernel<true, true, false, true>), grid, dim3(CH_THREADS), 0, stream, q);
-        } else if (p.fold && p.emit) {
-            if (u) hipLaunchKernelGGL((chemistry_tile_kernel<true, true, true>), grid, dim3(CH_THREADS), 0, stream, q);
-            else   hipLaunchKernelGGL((chemistry_tile_kernel<true, true, false>), grid, dim3(CH_THREADS), 0, stream, q);
-        } else if (!p.fold && !p.emit) {
-            if (u) hipLaunchKernelGGL((chemistry_tile_kernel<false, false, true>), grid, dim3(CH_THREADS), 0, stream, q);
-            else   hipLaunchKernelGGL((chemistry_tile_kernel<false, false, false>), grid, dim3(CH_THREADS), 0, stream, q);
-        } else if (!p.fold && p.emit) {       // rates already summed over both layouts (and over the ranks): asora_evolve_slab_fold_all
-            if (u) hipLaunchKernelGGL((chemistry_tile_kernel<false, true, true>), grid, dim3(CH_THREADS), 0, stream, q);
-            else   hipLaunchKernelGGL((chemistry_tile_kernel<false, true, false>), grid, dim3(CH_THREADS), 0, stream, q);
-        } else return fail(11, "chemistry: unsupported fold/emit combination (internal error)");
+        if (int rc = ck ? launch_tile_form<true>(q, grid, stream) : launch_tile_form<false>(q, grid, stream)) return rc;
         ASORA_HIP_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(chemistry_reduce_kernel, dim3(1), dim3(RED_THREADS), 0, stream,

@@ -85,7 +85,7 @@ def _agree_on_convergence(comm, converged):
 def _evolve_cpu_semantics(dt, dr, src_flux, src_pos, max_subbox, subboxsize, loss_fraction, temp, ndens, xh,
                           photo_thin_table, photo_thick_table, minlogtau, dlogtau, R_max_LLS, convergence_fraction,
                           sig, bh00, albpow, colh0, temph0, abu_c, logfile, quiet,
-                          use_mpi=None, comm=None, rank=0, nprocs=1):
+                          use_mpi=None, comm=None, rank=0, nprocs=1, clump=None):
     """The use_gpu=False branch of the reference (pyc2ray/evolve.py:168-245, :401-498): per iteration one pass of
     the CPU library's raytracer -- cubic sub-boxes grown until the photon loss is below loss_fraction, photon-loss
     statistics, Fortran-flavoured constants, every source rated with the flux of the last one as the Fortran does
@@ -124,6 +124,8 @@ def _evolve_cpu_semantics(dt, dr, src_flux, src_pos, max_subbox, subboxsize, los
     libasora.grid_to_device(_capi.GRID_XH, xh)
     libasora.grid_copy(_capi.GRID_XH_AV, _capi.GRID_XH)          # xh_av = copy(xh)        evolve.py:136
     libasora.grid_copy(_capi.GRID_XH_INTERMED, _capi.GRID_XH)    # xh_intermed = copy(xh)  evolve.py:137
+    if clump is not None:
+        clump.apply(libasora)
     if rank == 0:
         printlog("Calling evolve3D...", logfile, quiet)
         printlog(f"dr [Mpc]: {dr/3.086e24:.3e}", logfile, quiet)
@@ -132,6 +134,8 @@ def _evolve_cpu_semantics(dt, dr, src_flux, src_pos, max_subbox, subboxsize, los
         mean_ndens = libasora.grid_sum(_capi.GRID_NDENS) / NumCells
         mean_xh = libasora.grid_sum(_capi.GRID_XH) / NumCells
         printlog(f"Mean density (cgs): {mean_ndens:.3e}, Mean ionized fraction: {mean_xh:.3e}", logfile, quiet)
+        if clump is not None:
+            clump.log(libasora, NumCells, logfile, quiet)
         printlog(f"Convergence Criterion (Number of points): {conv_criterion : n}", logfile, quiet, end='\n\n')
     while not converged:
         niter += 1
@@ -229,18 +233,87 @@ def _thermal_loop(libasora, thermal, loop, logfile, quiet):
     return result
 
 
+class _Clumping:
+    """A validated ``clumping=`` argument: ``constant`` (a float != 1) or ``grid`` (an (N, N, N)
+    float64 array), the sub-grid clumping factor C = <n^2>/<n>^2 of the case-B recombination rate."""
+
+    def __init__(self, constant=None, grid=None):
+        self.constant, self.grid = constant, grid
+
+    def apply(self, libasora, upload=True):
+        """Set the library's mode; upload=False: GRID_CLUMP already holds the grid."""
+        if self.grid is None:
+            libasora.clumping(1, self.constant)
+            return
+        if upload:
+            libasora.grid_to_device(_capi.GRID_CLUMP, self.grid)
+        libasora.clumping(2)
+
+    def log(self, libasora, NumCells, logfile, quiet):
+        if self.grid is None:
+            printlog(f"Clumping factor: constant {self.constant:.3e}", logfile, quiet)
+        else:
+            printlog(f"Clumping factor: grid, mean {libasora.grid_sum(_capi.GRID_CLUMP) / NumCells:.3e}", logfile, quiet)
+
+
+def _clumping_spec(clumping, N, check_values=True):
+    """``clumping=`` of evolve3D / evolve3D_MPI / evolve3D_resident -> None (off: None or 1.0) or a _Clumping.  Raises
+    ValueError -- before any GPU work -- for anything but a finite float > 0 or an (N, N, N) grid of such values
+    (check_values=False: the grid's shape only, for a grid the caller has already checked)."""
+    if clumping is None:
+        return None
+    if isinstance(clumping, np.ndarray) and clumping.ndim == 3:
+        if clumping.shape != (N, N, N):
+            raise ValueError(f"clumping: a grid must have the mesh's shape {(N, N, N)}, not {clumping.shape}")
+        if clumping.dtype != np.float64:
+            raise ValueError(f"clumping: a grid must be float64, not {clumping.dtype}")
+        if check_values and not (np.all(np.isfinite(clumping)) and np.all(clumping > 0.0)):
+            raise ValueError("clumping: every factor of the grid must be finite and > 0")
+        return _Clumping(grid=clumping)
+    if isinstance(clumping, np.ndarray) and clumping.ndim == 0:
+        clumping = clumping.item()
+    if isinstance(clumping, (bool, np.bool_)) or not isinstance(clumping, (int, float, np.integer, np.floating)):
+        raise ValueError(f"clumping: None, a float > 0 or an (N, N, N) float64 grid, not {type(clumping).__name__}")
+    c = float(clumping)
+    if not (np.isfinite(c) and c > 0.0):
+        raise ValueError(f"clumping: the factor must be finite and > 0, not {c!r}")
+    return None if c == 1.0 else _Clumping(constant=c)
+
+
+def _clumping_reset(clump, run):
+    """Run `run()` and leave the library unclumped afterwards, whatever happens (nothing at all when clumping is off)."""
+    if clump is None:
+        return run()
+    try:
+        return run()
+    finally:
+        load_asora().clumping(0)
+
+
 def evolve3D_resident(dt, dr, src_flux, src_pos, uploads, N, photo_thin_table, minlogtau, dlogtau, R_max_LLS,
                       convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile="pyC2Ray.log", quiet=False,
-                      thermal=None):
+                      thermal=None, clumping=None):
     """evolve3D for a caller that keeps the grids on the device between time steps (the C2Ray class with
     ``device_resident = True``): same loop, log lines and results as :func:`evolve3D` with ``use_gpu=True``, but only the
     grids in ``uploads`` ({grid selector: host array}, those the caller changed on the host) cross PCIe, and nothing
     comes back: afterwards XH_INTERMED == XH == the new ionised fraction and PHI_ION the rates, on the device
     (``libasora.grid_to_host`` fetches them when someone looks).  Returns the number of outer iterations.
     With ``thermal`` (a :class:`pyc2ray_amd.thermal.ThermalParams`) the temperature is evolved as well: TEMP holds the
-    end-of-step temperature afterwards, PHI_HEAT the heating rates."""
+    end-of-step temperature afterwards, PHI_HEAT the heating rates.
+    ``clumping`` as in :func:`evolve3D`; like the other grids, an (N, N, N) grid crosses PCIe only when ``uploads`` holds it
+    (under ``_capi.GRID_CLUMP``, checked then): otherwise GRID_CLUMP must still hold it from an earlier step."""
+    clump = _clumping_spec(clumping, N, check_values=_capi.GRID_CLUMP in uploads)
+    if clump is not None and clump.grid is not None and _capi.GRID_CLUMP in uploads and uploads[_capi.GRID_CLUMP] is not clumping:
+        raise ValueError("evolve3D_resident: uploads[GRID_CLUMP] and clumping must be the same grid")
     if not cuda_is_init():
         raise RuntimeError("GPU not initialized. Please initialize it by calling device_init(N)")
+    return _clumping_reset(clump, lambda: _evolve_resident(dt, dr, src_flux, src_pos, uploads, N, photo_thin_table, minlogtau,
+                                                           dlogtau, R_max_LLS, convergence_fraction, sig, bh00, albpow, colh0,
+                                                           temph0, abu_c, logfile, quiet, thermal, clump))
+
+
+def _evolve_resident(dt, dr, src_flux, src_pos, uploads, N, photo_thin_table, minlogtau, dlogtau, R_max_LLS,
+                     convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile, quiet, thermal, clump):
     libasora = load_asora()
     NumSrc = src_flux.shape[0]
     NumCells = N * N * N
@@ -258,6 +331,9 @@ def evolve3D_resident(dt, dr, src_flux, src_pos, uploads, N, photo_thin_table, m
     mean_ndens = libasora.grid_sum(_capi.GRID_NDENS) / NumCells
     mean_xh = libasora.grid_sum(_capi.GRID_XH) / NumCells
     printlog(f"Mean density (cgs): {mean_ndens:.3e}, Mean ionized fraction: {mean_xh:.3e}", logfile, quiet)
+    if clump is not None:
+        clump.apply(libasora, upload=False)          # (a grid came with `uploads`)
+        clump.log(libasora, NumCells, logfile, quiet)
     printlog(f"Convergence Criterion (Number of points): {conv_criterion : n}", logfile, quiet, end='\n\n')
     def loop():
         return _device_loop(libasora, (dt, bh00, albpow, colh0, temph0, abu_c), R_max_LLS, sig, dr, minlogtau, dlogtau,
@@ -273,7 +349,7 @@ def evolve3D_resident(dt, dr, src_flux, src_pos, uploads, N, photo_thin_table, m
 
 def _evolve(dt, dr, src_flux, src_pos, use_gpu, temp, ndens, xh, photo_thin_table, minlogtau, dlogtau,
             R_max_LLS, convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile, quiet,
-            use_mpi=None, comm=None, rank=0, nprocs=1, thermal=None):
+            use_mpi=None, comm=None, rank=0, nprocs=1, thermal=None, clump=None):
     if use_gpu and not cuda_is_init():
         raise RuntimeError("GPU not initialized. Please initialize it by calling device_init(N)")
     _residency.reclaim()              # this step overwrites device grids a resident C2Ray object may be relying on
@@ -334,6 +410,8 @@ def _evolve(dt, dr, src_flux, src_pos, use_gpu, temp, ndens, xh, photo_thin_tabl
         libasora.grid_copy(_capi.GRID_XH_INTERMED, _capi.GRID_XH)    # xh_intermed = copy(xh)  evolve.py:137
     else:
         printlog("Copied source data to device.", logfile, quiet)
+    if clump is not None:
+        clump.apply(libasora)                                          # (every rank uploads the whole grid, as ndens)
 
     if rank == 0:
         if distributed:
@@ -347,6 +425,8 @@ def _evolve(dt, dr, src_flux, src_pos, use_gpu, temp, ndens, xh, photo_thin_tabl
         mean_ndens = libasora.grid_sum(_capi.GRID_NDENS) / NumCells
         mean_xh = libasora.grid_sum(_capi.GRID_XH) / NumCells
         printlog(f"Mean density (cgs): {mean_ndens:.3e}, Mean ionized fraction: {mean_xh:.3e}", logfile, quiet)
+        if clump is not None:
+            clump.log(libasora, NumCells, logfile, quiet)
         printlog(f"Convergence Criterion (Number of points): {conv_criterion : n}", logfile, quiet, end='\n\n')
 
     chem = (dt, bh00, albpow, colh0, temph0, abu_c)
@@ -487,7 +567,7 @@ def evolve3D(dt, dr,
              minlogtau, dlogtau,
              R_max_LLS, convergence_fraction,
              sig, bh00, albpow, colh0, temph0, abu_c,
-             logfile="pyC2Ray.log", quiet=False, *, thermal=None):
+             logfile="pyC2Ray.log", quiet=False, *, thermal=None, clumping=None):
     """Evolve the ionised fraction of the whole grid over one time step.
 
     Parameters have the reference's meaning (pyc2ray/evolve.py:49-109): dt [s], dr [cm],
@@ -505,18 +585,26 @@ def evolve3D(dt, dr,
     thermal : None (isothermal, as the reference) or a :class:`pyc2ray_amd.thermal.ThermalParams`: the temperature is
     evolved from photo-heating and radiative cooling as well (use_gpu=True only; the photo tables must be on the device, the
     heating tables are uploaded here).  Returns (xh_new, phi_ion, temp_new) then, temp_new laid out like `xh`.
+
+    clumping : the sub-grid clumping factor C = <n^2>/<n>^2 of the case-B recombination rate: None or
+    1.0 (off, the reference's behaviour), a float > 0 for the whole grid, or an (N, N, N) float64 grid (C or Fortran order) of
+    factors > 0.  Anything else raises ValueError before any GPU work.  Works with use_gpu=False and with `thermal` (then the
+    recombination cooling is clumped as well).
     """
+    clump = _clumping_spec(clumping, np.shape(temp)[0])
     if not use_gpu:
         if thermal is not None:
             raise ValueError("evolve3D: the thermal mode needs use_gpu=True (the use_gpu=False raytracer has no thermal form)")
-        return _evolve_cpu_semantics(dt, dr, src_flux, src_pos, max_subbox, subboxsize, loss_fraction, temp, ndens,
-                                     xh, photo_thin_table, photo_thick_table, minlogtau, dlogtau, R_max_LLS,
-                                     convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile, quiet)
-    if thermal is None:
+        return _clumping_reset(clump, lambda: _evolve_cpu_semantics(
+            dt, dr, src_flux, src_pos, max_subbox, subboxsize, loss_fraction, temp, ndens, xh, photo_thin_table,
+            photo_thick_table, minlogtau, dlogtau, R_max_LLS, convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c,
+            logfile, quiet, clump=clump))
+    if thermal is None and clump is None:
         return _evolve(dt, dr, src_flux, src_pos, use_gpu, temp, ndens, xh, photo_thin_table, minlogtau, dlogtau,
                        R_max_LLS, convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile, quiet)
-    return _evolve(dt, dr, src_flux, src_pos, use_gpu, temp, ndens, xh, photo_thin_table, minlogtau, dlogtau,
-                   R_max_LLS, convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile, quiet, thermal=thermal)
+    return _clumping_reset(clump, lambda: _evolve(
+        dt, dr, src_flux, src_pos, use_gpu, temp, ndens, xh, photo_thin_table, minlogtau, dlogtau, R_max_LLS,
+        convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile, quiet, thermal=thermal, clump=clump))
 
 
 def evolve3D_MPI(dt, dr,
@@ -528,7 +616,7 @@ def evolve3D_MPI(dt, dr,
                  minlogtau, dlogtau,
                  R_max_LLS, convergence_fraction,
                  sig, bh00, albpow, colh0, temph0, abu_c,
-                 logfile="pyC2Ray.log", quiet=False, *, thermal=None):
+                 logfile="pyC2Ray.log", quiet=False, *, thermal=None, clumping=None):
     """Source-sharded variant (pyc2ray/evolve.py:249-498): rank r traces the contiguous block
     [r*(Ns//nprocs), (r+1)*(Ns//nprocs)) of the source list, the last rank to the end
     (evolve.py:362-367); the per-rank rate grids are summed across ranks each iteration.
@@ -538,15 +626,22 @@ def evolve3D_MPI(dt, dr,
     (one process per GPU under torch.distributed: RCCL all-reduce over xGMI directly on the
     device-resident grid).  All ranks return the same (xh_new, phi_ion).
     The thermal mode is single-GPU only: ``thermal`` must be None here.
+    ``clumping`` as in :func:`evolve3D`; every rank passes (and uploads) the whole grid, as it does ``ndens``.
     """
     if thermal is not None:
         raise ValueError("evolve3D_MPI: the thermal mode is single-GPU only (no slab exchange of heating rates and "
                          "temperatures); use evolve3D with use_gpu=True")
+    clump = _clumping_spec(clumping, np.shape(temp)[0])
     if not use_gpu:
-        return _evolve_cpu_semantics(dt, dr, src_flux, src_pos, max_subbox, subboxsize, loss_fraction, temp, ndens,
-                                     xh, photo_thin_table, photo_thick_table, minlogtau, dlogtau, R_max_LLS,
-                                     convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile, quiet,
-                                     use_mpi=use_mpi, comm=comm, rank=rank, nprocs=nprocs)
-    return _evolve(dt, dr, src_flux, src_pos, use_gpu, temp, ndens, xh, photo_thin_table, minlogtau, dlogtau,
-                   R_max_LLS, convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile, quiet,
-                   use_mpi=use_mpi, comm=comm, rank=rank, nprocs=nprocs)
+        return _clumping_reset(clump, lambda: _evolve_cpu_semantics(
+            dt, dr, src_flux, src_pos, max_subbox, subboxsize, loss_fraction, temp, ndens, xh, photo_thin_table,
+            photo_thick_table, minlogtau, dlogtau, R_max_LLS, convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c,
+            logfile, quiet, use_mpi=use_mpi, comm=comm, rank=rank, nprocs=nprocs, clump=clump))
+    if clump is None:
+        return _evolve(dt, dr, src_flux, src_pos, use_gpu, temp, ndens, xh, photo_thin_table, minlogtau, dlogtau,
+                       R_max_LLS, convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile, quiet,
+                       use_mpi=use_mpi, comm=comm, rank=rank, nprocs=nprocs)
+    return _clumping_reset(clump, lambda: _evolve(
+        dt, dr, src_flux, src_pos, use_gpu, temp, ndens, xh, photo_thin_table, minlogtau, dlogtau, R_max_LLS,
+        convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile, quiet,
+        use_mpi=use_mpi, comm=comm, rank=rank, nprocs=nprocs, clump=clump))

@@ -320,6 +320,11 @@ class _LibAsora:
         _capi.check(self._lib.asora_thermal_params(int(bool(enable)), float(relative_denergy), float(t_floor), int(max_substeps),
                                                    int(cooling_mask), int(bool(compton)), float(t_cmb)), "thermal_params")
 
+    def clumping(self, mode, constant=1.0):
+        """Clumping of the recombination rate (include/asora_hip.h, asora_clumping): 0 off, 1 the one factor `constant`, 2 per
+        cell from GRID_CLUMP (upload it first)."""
+        _capi.check(self._lib.asora_clumping(int(mode), float(constant)), "clumping")
+
     def thermal_stats(self):
         """(cells that hit max_substeps, cells clamped to t_floor, most substeps of one integration) since the last
         chemistry_device / evolve_begin."""
