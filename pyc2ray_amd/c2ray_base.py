@@ -287,23 +287,19 @@ class C2Ray:
         """Evolve the grid over one time step (c2ray_base.py:170-226)."""
         if self.device_resident and self.gpu and not self.mpi:
             return self._evolve3D_resident(dt, src_flux, src_pos)
-        if not self.isothermal:
-            self.xh, self.phi_ion, self.temp = evolve3D(
-                dt, self.dr, src_flux, src_pos, self.gpu, self.max_subbox, self.subboxsize, self.loss_fraction, self.temp,
-                self.ndens, self.xh, self.photo_thin_table, self.photo_thick_table, self.minlogtau, self.dlogtau,
-                self.R_max_LLS, self.convergence_fraction, self.sig, self.bh00, self.albpow, self.colh0, self.temph0,
-                self.abu_c, self.logfile, thermal=self._thermal_params(), clumping=self.__dict__["_clumping"])
-            return
-        args = (self.temp, self.ndens, self.xh, self.photo_thin_table, self.photo_thick_table, self.minlogtau,
-                self.dlogtau, self.R_max_LLS, self.convergence_fraction, self.sig, self.bh00, self.albpow,
-                self.colh0, self.temph0, self.abu_c, self.logfile)
-        if self.mpi and src_flux.shape[0] >= self.nprocs:
-            self.xh, self.phi_ion = evolve3D_MPI(dt, self.dr, src_flux, src_pos, self.gpu, self.max_subbox,
-                                                 self.subboxsize, self.loss_fraction, self.mpi, self.comm, self.rank,
-                                                 self.nprocs, *args, clumping=self.__dict__["_clumping"])
+        head = (dt, self.dr, src_flux, src_pos, self.gpu, self.max_subbox, self.subboxsize, self.loss_fraction)
+        tail = (self.temp, self.ndens, self.xh, self.photo_thin_table, self.photo_thick_table, self.minlogtau, self.dlogtau,
+                self.R_max_LLS, self.convergence_fraction, self.sig, self.bh00, self.albpow, self.colh0, self.temph0, self.abu_c,
+                self.logfile)
+        thermal = self._thermal_params()
+        # (the thermal mode is single-GPU only: a run that evolves the temperature takes the one-process form)
+        if thermal is None and self.mpi and src_flux.shape[0] >= self.nprocs:
+            result = evolve3D_MPI(*head, self.mpi, self.comm, self.rank, self.nprocs, *tail, clumping=self.__dict__["_clumping"])
         else:
-            self.xh, self.phi_ion = evolve3D(dt, self.dr, src_flux, src_pos, self.gpu, self.max_subbox,
-                                             self.subboxsize, self.loss_fraction, *args, clumping=self.__dict__["_clumping"])
+            result = evolve3D(*head, *tail, thermal=thermal, clumping=self.__dict__["_clumping"])
+        self.xh, self.phi_ion = result[:2]
+        if thermal is not None:
+            self.temp = result[2]
 
     @classmethod
     def _fingerprint(cls, arr):

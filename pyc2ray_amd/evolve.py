@@ -8,6 +8,9 @@ xh_intermed and phi_ion stay on the MI355X for the whole step, the chemistry is 
 three scalars (conv_flag, sum x, sum 1-x) cross PCIe per iteration.
 """
 import array
+import contextlib
+import dataclasses
+import functools
 import os
 import time
 
@@ -82,96 +85,267 @@ def _agree_on_convergence(comm, converged):
     return bool(flag[0])
 
 
-def _evolve_cpu_semantics(dt, dr, src_flux, src_pos, max_subbox, subboxsize, loss_fraction, temp, ndens, xh,
-                          photo_thin_table, photo_thick_table, minlogtau, dlogtau, R_max_LLS, convergence_fraction,
-                          sig, bh00, albpow, colh0, temph0, abu_c, logfile, quiet,
-                          use_mpi=None, comm=None, rank=0, nprocs=1, clump=None):
-    """The use_gpu=False branch of the reference (pyc2ray/evolve.py:168-245, :401-498): per iteration one pass of
-    the CPU library's raytracer -- cubic sub-boxes grown until the photon loss is below loss_fraction, photon-loss
-    statistics, Fortran-flavoured constants, every source rated with the flux of the last one as the Fortran does
-    -- and one global_pass.  Both are evaluated on the GPU, and like the use_gpu=True loop this one keeps the grids
-    on the device for the whole step (the reference's host round trips are what
-    ``libc2ray.raytracing.do_all_sources`` / ``libc2ray.chemistry.global_pass`` of this package still offer)."""
-    _residency.reclaim()              # this step overwrites device grids a resident C2Ray object may be relying on
-    libasora = load_asora()
-    distributed = bool(use_mpi) and comm is not None and nprocs > 1
-    NumSrc = src_flux.shape[0]
-    N = temp.shape[0]
-    NumCells = N * N * N
-    NumTau = photo_thin_table.shape[0]
-    conv_criterion = min(int(convergence_fraction * NumCells), (NumSrc - 1) / 3)        # evolve.py:127
-    prev_sum_xh1_int = 2 * NumCells
-    prev_sum_xh0_int = 2 * NumCells
-    converged = False
-    niter = 0
-    if distributed:                                                                     # evolve.py:360-371
-        perrank = NumSrc // nprocs
-        i_start = int(rank * perrank)
-        i_end = int((rank + 1) * perrank) if rank != nprocs - 1 else NumSrc
-        my_flux, my_pos = src_flux[i_start:i_end], np.asarray(src_pos)[:, i_start:i_end]
-        printlog(f"...rank={rank:n} has {i_end - i_start:n} sources.", logfile, quiet)
-    else:
-        my_flux, my_pos = src_flux, np.asarray(src_pos)
-    n_local = my_flux.shape[0]
+@dataclasses.dataclass(frozen=True)
+class _Step:
+    """The scalars of one time step that the loops need; built once, by :func:`_prologue`."""
+    dt: float
+    dr: float
+    R_max_LLS: float
+    sig: float
+    minlogtau: float
+    dlogtau: float
+    NumTau: int                     # evolve.py:124 (the table LENGTH is what the reference passes)
+    chem: tuple                     # (dt, bh00, albpow, colh0, temph0, abu_c): the arguments of the chemistry
+    convergence_fraction: float
+    conv_criterion: float           # evolve.py:127
+    N: int
+    NumCells: int
+    n_local: int                    # sources on this rank's device
+    rank: int
+    logfile: object
+    quiet: bool
 
-    # this branch has no device_init of its own in the reference: the library sets itself up for the mesh
-    libasora.device_init_auto(N)
-    libasora.photo_table_to_device(photo_thin_table, photo_thick_table, NumTau)
+    def report(self, conv_flag, rel_change_xh1):
+        """The line of evolve.py:227-228 about one outer iteration."""
+        return (f"Number of non-converged points: {conv_flag} of {self.NumCells} ({conv_flag / self.NumCells * 100 : .3f} % ), "
+                f"Relative change in ionfrac: {rel_change_xh1 : .2e}")
+
+
+#: `ranks` of a step on one GPU: (use_mpi, comm, rank, nprocs) as evolve3D_MPI takes them
+_ONE_RANK = (None, None, 0, 1)
+
+
+def _is_distributed(ranks):
+    use_mpi, comm, _, nprocs = ranks
+    return bool(use_mpi) and comm is not None and nprocs > 1
+
+
+def _contiguous_shard(src_pos, src_flux, ranks):
+    """The sources that this rank traces (evolve.py:360-371): a contiguous block of NumSrc // nprocs of the list, the last rank to
+    the end; all of them when the step is not distributed."""
+    _, _, rank, nprocs = ranks
+    pos, NumSrc = np.asarray(src_pos), src_flux.shape[0]
+    if not _is_distributed(ranks):
+        return pos, src_flux
+    perrank = NumSrc // nprocs
+    i_start = int(rank * perrank)
+    i_end = int((rank + 1) * perrank) if rank != nprocs - 1 else NumSrc
+    return pos[:, i_start:i_end], src_flux[i_start:i_end]
+
+
+def _prologue(libasora, scalars, N, NumTau, src_flux, my_pos, my_flux, uploads, clump, *, ranks=_ONE_RANK,
+              calling="Calling evolve3D...", xh_copies=False, say_copied=False, clump_upload=True, tables=None):
+    """What every form of the step does before its loop: the convergence criterion, this rank's sources (`my_pos`, `my_flux`)
+    and the grids of `uploads` ({grid selector: host array}) to the device, the clumping mode, and the header lines of
+    evolve.py:156-162 on rank 0.  Returns the :class:`_Step`.  The forms differ in: `calling`, the first header line;
+    `xh_copies`, xh_av = xh_intermed = xh made here (the one-GPU device loop makes its own); `say_copied`, the line of the
+    reference's one-process GPU branch; `clump_upload=False`, a clumping grid is among `uploads` or on the device already;
+    `tables` = (thin, thick), use_gpu=False: that branch has no device_init of its own in the reference, so the library sets itself
+    up for the mesh here."""
+    NumSrc, n_local, NumCells = src_flux.shape[0], my_flux.shape[0], N * N * N
+    logfile, quiet, rank = scalars["logfile"], scalars["quiet"], ranks[2]
+    # evolve.py:127 (computed from the TOTAL source count, evolve.py:346)
+    conv_criterion = min(int(scalars["convergence_fraction"] * NumCells), (NumSrc - 1) / 3)
+    step = _Step(NumTau=NumTau, conv_criterion=conv_criterion, N=N, NumCells=NumCells, n_local=n_local, rank=rank, **scalars)
+    if _is_distributed(ranks):
+        printlog(f"...rank={rank:n} has {n_local:n} sources.", logfile, quiet)
+    if tables is not None:
+        libasora.device_init_auto(N)
+        libasora.photo_table_to_device(*tables, NumTau)
+
+    # Everything the step needs goes to the device once (evolve.py:136-155 keeps host copies instead)
     srcpos_flat, normflux_flat = format_sources(my_pos, my_flux)
     libasora.source_data_to_device(srcpos_flat, normflux_flat, n_local)
-    libasora.grid_to_device(_capi.GRID_NDENS, ndens)
-    libasora.grid_to_device(_capi.GRID_TEMP, temp)
-    libasora.grid_to_device(_capi.GRID_XH, xh)
-    libasora.grid_copy(_capi.GRID_XH_AV, _capi.GRID_XH)          # xh_av = copy(xh)        evolve.py:136
-    libasora.grid_copy(_capi.GRID_XH_INTERMED, _capi.GRID_XH)    # xh_intermed = copy(xh)  evolve.py:137
+    for which, grid in uploads.items():
+        libasora.grid_to_device(which, grid)
+    if xh_copies:
+        libasora.grid_copy(_capi.GRID_XH_AV, _capi.GRID_XH)          # xh_av = copy(xh)        evolve.py:136
+        libasora.grid_copy(_capi.GRID_XH_INTERMED, _capi.GRID_XH)    # xh_intermed = copy(xh)  evolve.py:137
+    if say_copied:
+        printlog("Copied source data to device.", logfile, quiet)
     if clump is not None:
-        clump.apply(libasora)
+        clump.apply(libasora, upload=clump_upload)                     # (every rank uploads the whole grid, as ndens)
+
     if rank == 0:
-        printlog("Calling evolve3D...", logfile, quiet)
-        printlog(f"dr [Mpc]: {dr/3.086e24:.3e}", logfile, quiet)
-        printlog(f"dt [years]: {dt/3.15576E+07:.3e}", logfile, quiet)
+        printlog(calling, logfile, quiet)
+        printlog(f"dr [Mpc]: {step.dr/3.086e24:.3e}", logfile, quiet)
+        printlog(f"dt [years]: {step.dt/3.15576E+07:.3e}", logfile, quiet)
         printlog(f"Running on {NumSrc:n} source(s), total normalized ionizing flux: {src_flux.sum():.2e}", logfile, quiet)
+        # the two means of evolve.py:160, summed on the device from the grids just uploaded
         mean_ndens = libasora.grid_sum(_capi.GRID_NDENS) / NumCells
         mean_xh = libasora.grid_sum(_capi.GRID_XH) / NumCells
         printlog(f"Mean density (cgs): {mean_ndens:.3e}, Mean ionized fraction: {mean_xh:.3e}", logfile, quiet)
         if clump is not None:
             clump.log(libasora, NumCells, logfile, quiet)
         printlog(f"Convergence Criterion (Number of points): {conv_criterion : n}", logfile, quiet, end='\n\n')
+    return step
+
+
+def _loop_strategy(libasora, comm, distributed):
+    """Which loop runs the outer iterations of a use_gpu=True step: "one GPU", or across ranks "slab", "pipelined", "all-reduce"
+    or "three calls" (what an mpi4py communicator gets).  The two device loops across ranks need the [k][j][i] twins of the
+    grids (asora_evolve_begin_slab fails without: ASORA_OPT_Z_TRANSPOSED = 0 is a diagnostic setting)."""
+    if not distributed:
+        return "one GPU"
+    overlap = getattr(comm, "overlap", False)
+    if hasattr(comm, "slab_enqueue") and getattr(comm, "exchange", "") == "slab" and not overlap and _has_transposed_twins(libasora):
+        return "slab"
+    if overlap and hasattr(comm, "raytrace_and_allreduce"):
+        return "pipelined"
+    if (getattr(comm, "device_loop", False) and hasattr(comm, "reduce_begin") and hasattr(libasora, "evolve_slab_fold_all")
+            and _has_transposed_twins(libasora)):
+        return "all-reduce"
+    return "three calls"
+
+
+def _device_loop(step, enqueue, poll, batch_max, label=None):
+    """A loop of outer iterations that lives on the device (include/asora_hip.h, asora_evolve_*): an iteration is the raytrace
+    plus ONE pass over the grids (rates folded, chemistry, nHI for the next trace, accumulators zeroed), and the convergence test of
+    evolve.py:216-236 is evaluated on the device, so a batch of iterations is enqueued per host round trip and those beyond
+    convergence do nothing.  `enqueue(n)` and `poll(n)` are the library's (one GPU) or the communicator's (across ranks).
+    label=None, one GPU: batches of batch_max, the reference's log lines.  Across ranks `label` begins each rank's line, and as the
+    collectives of an iteration are not gated by the device's `done` flag the batch shrinks as the test comes within reach
+    (:func:`_next_batch`).  Returns the number of outer iterations."""
+    history, converged = [], False
+    while not converged:
+        t0 = time.time()
+        batch = batch_max if label is None else _next_batch(history, batch_max, step.conv_criterion, step.convergence_fraction)
+        enqueue(batch)
+        _, converged, rows = poll(batch)
+        history += list(rows)
+        per_iteration = (time.time() - t0) / max(len(rows), 1)
+        lines = []
+        for conv_flag, _s1, _s0, rel_change_xh1, _rel0 in rows:
+            if label is None:
+                lines += [("Doing Raytracing...", ' '), (f"took {per_iteration : .1f} s.", '\n'), ("Doing Chemistry...", ' '),
+                          ("took  0.0 s. (fused with the raytrace on the device: the time above is for both)", '\n')]
+            else:
+                lines += [(f"{label} (rank={step.rank:n})...", ' '), (f"rank={step.rank:n} took {per_iteration : .1e} s.", '\n')]
+            if label is None or step.rank == 0:
+                lines.append((step.report(int(conv_flag), rel_change_xh1), '\n'))
+        printlog_lines(lines, step.logfile, step.quiet)
+    return len(history)
+
+
+def _one_gpu_loop(libasora, step, thermal=None):
+    """One GPU: the whole loop of a time step on the device, EVOLVE_BATCH iterations per host round trip; with `thermal` in the
+    library's thermal mode.  NDENS, TEMP, XH and the sources must be on the device."""
+    def loop():
+        libasora.evolve_begin(*step.chem, step.R_max_LLS, step.sig, step.dr, step.minlogtau, step.dlogtau, step.NumTau, 0,
+                              step.n_local, step.conv_criterion, step.convergence_fraction)
+        return _device_loop(step, libasora.evolve_enqueue, libasora.evolve_poll, max(1, min(EVOLVE_BATCH, 32)))
+    return loop() if thermal is None else _thermal_loop(libasora, thermal, loop, step)
+
+
+def _thermal_loop(libasora, thermal, loop, step):
+    """Run `loop()` (a device loop of one step) in the library's thermal mode, and leave the library isothermal again."""
+    thermal.apply(libasora)
+    try:
+        result = loop()
+        capped, _floored, most = libasora.thermal_stats()
+    finally:
+        libasora.thermal_params(False)
+    if capped:
+        printlog(f"Warning: the temperature integration of {capped:n} cell(s) hit max_substeps = {thermal.max_substeps:n} "
+                 f"(most substeps used: {most:n}); their last substep took the rest of the time step.", step.logfile, step.quiet)
+    return result
+
+
+def _ranks_device_loop(libasora, step, comm, begin, label):
+    """The device-resident loop across ranks (pyc2ray_amd.dist.TorchComm), begun by `begin`:
+    comm.slab_begin -- sharded: per iteration the trace, the rates to the owners of the planes, ONE fused pass on the own slab,
+    xh_av back, and the convergence test on the device behind the in-place all-reduce of its three sums -- identical bits, hence
+    the same decision, on every rank; or
+    comm.reduce_begin -- trace, fold, all-reduce of the whole rate grid in place, ONE fused pass on the whole grid on every rank,
+    test on the device.
+    With RCCL a batch of iterations is enqueued per host round trip (launches beyond convergence do nothing); with gloo every
+    exchange goes through the host anyway and the batch is one."""
+    begin(step.N, step.R_max_LLS, step.sig, step.dr, step.n_local, step.minlogtau, step.dlogtau, step.NumTau, step.chem,
+          step.conv_criterion, step.convergence_fraction)
+    batch_max = max(1, min(EVOLVE_BATCH, 32)) if _comm_backend(comm) == "nccl" else 1
+    return _device_loop(step, functools.partial(comm.slab_enqueue, libasora), functools.partial(comm.slab_poll, libasora),
+                        batch_max, label)
+
+
+def _host_test_loop(step, iteration, comm=None):
+    """Outer iterations with the global convergence test of evolve.py:216-236 on the host: `iteration()` traces, sums over the
+    ranks, solves the chemistry and returns (conv_flag, sum x, sum 1-x).  With `comm` (a distributed step) the ranks agree on the
+    outcome.  Returns the number of outer iterations."""
+    prev_sum_xh1_int = prev_sum_xh0_int = 2 * step.NumCells
+    niter, converged = 0, False
     while not converged:
         niter += 1
-        trt0 = time.time()
-        printlog("Doing Raytracing...", logfile, quiet, ' ')
-        nsubbox, photonloss = libasora.subbox_raytrace_device(max_subbox, subboxsize, loss_fraction, R_max_LLS, sig, dr,
-                                                              minlogtau, dlogtau, NumTau, 0, n_local)
-        printlog(f"took {(time.time()-trt0) : .1f} s.", logfile, quiet)
-        printlog(f"Average number of subboxes: {nsubbox/max(n_local, 1):n}, Total photon loss: {photonloss:.3e}",
-                 logfile, quiet)
-        if distributed:                                                                 # evolve.py:433-437
-            _allreduce_phi(libasora, N, use_mpi, comm, rank)
-        tch0 = time.time()
-        if rank == 0:
-            printlog("Doing Chemistry...", logfile, quiet, ' ')
-        conv_flag, sum_xh1_int, sum_xh0_int = libasora.chemistry_device(dt, bh00, albpow, colh0, temph0, abu_c)
-        if rank == 0:
-            printlog(f"took {(time.time()-tch0) : .1f} s.", logfile, quiet)
+        conv_flag, sum_xh1_int, sum_xh0_int = iteration()
         rel_change_xh1 = np.abs((sum_xh1_int - prev_sum_xh1_int) / sum_xh1_int) if sum_xh1_int > 0.0 else 1.0
         rel_change_xh0 = np.abs((sum_xh0_int - prev_sum_xh0_int) / sum_xh0_int) if sum_xh0_int > 0.0 else 1.0
-        if rank == 0:
-            printlog(f"Number of non-converged points: {conv_flag} of {NumCells} ({conv_flag / NumCells * 100 : .3f} % ), "
-                     f"Relative change in ionfrac: {rel_change_xh1 : .2e}", logfile, quiet)
-        converged = (conv_flag < conv_criterion) or ((rel_change_xh1 < convergence_fraction) and
-                                                     (rel_change_xh0 < convergence_fraction))
-        if distributed:
-            converged = _agree_on_convergence(comm, converged)
-        prev_sum_xh1_int = sum_xh1_int
-        prev_sum_xh0_int = sum_xh0_int
-    if rank == 0:
-        printlog("Multiple source convergence reached.", logfile, quiet)
-    # Fortran-ordered results, as the reference's CPU branch returns them (evolve.py:178)
-    xh_new = libasora.grid_to_host(_capi.GRID_XH_INTERMED, libasora.host_empty((N, N, N), order='F'))
-    phi_ion = libasora.grid_to_host(_capi.GRID_PHI_ION, libasora.host_empty((N, N, N), order='F'))
-    _evolve.last_niter = niter
-    return xh_new, phi_ion
+        if step.rank == 0:
+            printlog(step.report(conv_flag, rel_change_xh1), step.logfile, step.quiet)
+        converged = (conv_flag < step.conv_criterion) or ((rel_change_xh1 < step.convergence_fraction) and
+                                                          (rel_change_xh0 < step.convergence_fraction))
+        if comm is not None:
+            converged = _agree_on_convergence(comm, converged)            # evolve.py:484-489
+        prev_sum_xh1_int, prev_sum_xh0_int = sum_xh1_int, sum_xh0_int
+    return niter
+
+
+def _chemistry(libasora, step):
+    """One global pass of the chemistry on the device (evolve.py:207-211), timed in the log of rank 0."""
+    tch0 = time.time()
+    if step.rank == 0:
+        printlog("Doing Chemistry...", step.logfile, step.quiet, ' ')
+    sums = libasora.chemistry_device(*step.chem)
+    if step.rank == 0:
+        printlog(f"took {(time.time()-tch0) : .1f} s.", step.logfile, step.quiet)
+    return sums
+
+
+def _three_call_loop(libasora, step, use_mpi, comm):
+    """Across ranks as the reference does it (evolve.py:401-498): raytrace, sum of the rate grids, chemistry, and three scalars
+    read back, per iteration.  Every rank runs the chemistry on the identical summed rates (the reference runs it on rank 0 and
+    broadcasts two N^3 grids, evolve.py:439-481)."""
+    def iteration():
+        trt0 = time.time()
+        printlog(f"Doing Raytracing (rank={step.rank:n})...", step.logfile, step.quiet, ' ')
+        libasora.raytrace_device(step.R_max_LLS, step.sig, step.dr, 0, step.n_local, step.minlogtau, step.dlogtau, step.NumTau)
+        libasora.synchronize()
+        printlog(f"rank={step.rank:n} took {(time.time()-trt0) : .1e} s.", step.logfile, step.quiet)
+        _allreduce_phi(libasora, step.N, use_mpi, comm, step.rank)
+        return _chemistry(libasora, step)
+    return _host_test_loop(step, iteration, comm)
+
+
+def _pipelined_loop(libasora, step, comm, src_i0):
+    """Raytrace, sum over ranks and chemistry slab by slab (pyc2ray_amd.dist, opt-in); `src_i0`: the first coordinates of the
+    rank's sources, which are traced in that order."""
+    def iteration():
+        trt0 = time.time()
+        printlog(f"Doing Raytracing and Chemistry, pipelined (rank={step.rank:n})...", step.logfile, step.quiet, ' ')
+        sums = comm.raytrace_and_allreduce(libasora, step.N, step.R_max_LLS, step.sig, step.dr, step.n_local, step.minlogtau,
+                                           step.dlogtau, step.NumTau, src_i0=src_i0, chemistry=step.chem)
+        printlog(f"rank={step.rank:n} took {(time.time()-trt0) : .1e} s.", step.logfile, step.quiet)
+        return sums
+    return _host_test_loop(step, iteration, comm)
+
+
+def _subbox_loop(libasora, step, subbox, ranks):
+    """use_gpu=False (evolve.py:168-245, :401-498): per iteration one pass of the CPU library's raytracer -- cubic sub-boxes
+    grown until the photon loss is below loss_fraction, photon-loss statistics, Fortran-flavoured constants, every source rated with
+    the flux of the last one as the Fortran does -- and one global pass, both evaluated on the GPU."""
+    use_mpi, comm, _, _ = ranks
+    distributed = _is_distributed(ranks)
+
+    def iteration():
+        trt0 = time.time()
+        printlog("Doing Raytracing...", step.logfile, step.quiet, ' ')
+        nsubbox, photonloss = libasora.subbox_raytrace_device(*subbox, step.R_max_LLS, step.sig, step.dr, step.minlogtau,
+                                                              step.dlogtau, step.NumTau, 0, step.n_local)
+        printlog(f"took {(time.time()-trt0) : .1f} s.", step.logfile, step.quiet)
+        printlog(f"Average number of subboxes: {nsubbox/max(step.n_local, 1):n}, Total photon loss: {photonloss:.3e}",
+                 step.logfile, step.quiet)
+        if distributed:                                                                 # evolve.py:433-437
+            _allreduce_phi(libasora, step.N, use_mpi, comm, step.rank)
+        return _chemistry(libasora, step)
+    return _host_test_loop(step, iteration, comm if distributed else None)
 
 
 def _allreduce_phi(libasora, N, use_mpi, comm, rank):
@@ -188,49 +362,6 @@ def _allreduce_phi(libasora, N, use_mpi, comm, rank):
         comm.Reduce([phi, use_mpi.DOUBLE], None, op=use_mpi.SUM, root=0)
     comm.Bcast([phi, use_mpi.DOUBLE], root=0)
     libasora.grid_to_device(_capi.GRID_PHI_ION, phi)
-
-
-def _device_loop(libasora, chem, R_max_LLS, sig, dr, minlogtau, dlogtau, NumTau, NumSrc_local, conv_criterion,
-                 convergence_fraction, NumCells, logfile, quiet):
-    """One GPU: the whole loop of a time step on the device (include/asora_hip.h, asora_evolve_*).  An iteration is
-    the raytrace plus ONE pass over the grids (rates folded, chemistry, nHI for the next trace, accumulators zeroed); the
-    convergence test of evolve.py:216-236 is evaluated on the device, so EVOLVE_BATCH iterations are enqueued per host
-    round trip and those beyond convergence do nothing.  NDENS, TEMP, XH and the sources must be on the device.
-    Returns (outer iterations, sum of xh_intermed of the last iteration)."""
-    libasora.evolve_begin(*chem, R_max_LLS, sig, dr, minlogtau, dlogtau, NumTau, 0, NumSrc_local,
-                          conv_criterion, convergence_fraction)
-    batch = max(1, min(EVOLVE_BATCH, 32))
-    niter, converged, sum_xh1 = 0, False, 0.0
-    while not converged:
-        t0 = time.time()
-        libasora.evolve_enqueue(batch)
-        _, converged, rows = libasora.evolve_poll(batch)
-        per_iteration = (time.time() - t0) / max(len(rows), 1)
-        lines = []
-        for conv_flag, sum_xh1, _s0, rel_change_xh1, _rel0 in rows:
-            niter += 1
-            conv_flag = int(conv_flag)
-            lines += [("Doing Raytracing...", ' '), (f"took {per_iteration : .1f} s.", '\n'),
-                      ("Doing Chemistry...", ' '),
-                      ("took  0.0 s. (fused with the raytrace on the device: the time above is for both)", '\n'),
-                      (f"Number of non-converged points: {conv_flag} of {NumCells} ({conv_flag / NumCells * 100 : .3f} % ), "
-                       f"Relative change in ionfrac: {rel_change_xh1 : .2e}", '\n')]
-        printlog_lines(lines, logfile, quiet)
-    return niter, float(sum_xh1)
-
-
-def _thermal_loop(libasora, thermal, loop, logfile, quiet):
-    """Run `loop()` (a device loop of one step) in the library's thermal mode, and leave the library isothermal again."""
-    thermal.apply(libasora)
-    try:
-        result = loop()
-        capped, _floored, most = libasora.thermal_stats()
-    finally:
-        libasora.thermal_params(False)
-    if capped:
-        printlog(f"Warning: the temperature integration of {capped:n} cell(s) hit max_substeps = {thermal.max_substeps:n} "
-                 f"(most substeps used: {most:n}); their last substep took the rest of the time step.", logfile, quiet)
-    return result
 
 
 class _Clumping:
@@ -280,14 +411,21 @@ def _clumping_spec(clumping, N, check_values=True):
     return None if c == 1.0 else _Clumping(constant=c)
 
 
-def _clumping_reset(clump, run):
-    """Run `run()` and leave the library unclumped afterwards, whatever happens (nothing at all when clumping is off)."""
-    if clump is None:
-        return run()
+@contextlib.contextmanager
+def _clumping_reset(clump):
+    """Leave the library unclumped after the block, whatever happens (nothing at all when clumping is off)."""
     try:
-        return run()
+        yield
     finally:
-        load_asora().clumping(0)
+        if clump is not None:
+            load_asora().clumping(0)
+
+
+def _scalars(dt, dr, R_max_LLS, convergence_fraction, sig, minlogtau, dlogtau, chem_constants, logfile, quiet):
+    """The arguments of an entry form that go into the :class:`_Step` as they are; chem_constants = (bh00, albpow, colh0, temph0,
+    abu_c)."""
+    return dict(dt=dt, dr=dr, R_max_LLS=R_max_LLS, convergence_fraction=convergence_fraction, sig=sig, minlogtau=minlogtau,
+                dlogtau=dlogtau, chem=(dt, *chem_constants), logfile=logfile, quiet=quiet)
 
 
 def evolve3D_resident(dt, dr, src_flux, src_pos, uploads, N, photo_thin_table, minlogtau, dlogtau, R_max_LLS,
@@ -307,39 +445,18 @@ def evolve3D_resident(dt, dr, src_flux, src_pos, uploads, N, photo_thin_table, m
         raise ValueError("evolve3D_resident: uploads[GRID_CLUMP] and clumping must be the same grid")
     if not cuda_is_init():
         raise RuntimeError("GPU not initialized. Please initialize it by calling device_init(N)")
-    return _clumping_reset(clump, lambda: _evolve_resident(dt, dr, src_flux, src_pos, uploads, N, photo_thin_table, minlogtau,
-                                                           dlogtau, R_max_LLS, convergence_fraction, sig, bh00, albpow, colh0,
-                                                           temph0, abu_c, logfile, quiet, thermal, clump))
+    scalars = _scalars(dt, dr, R_max_LLS, convergence_fraction, sig, minlogtau, dlogtau, (bh00, albpow, colh0, temph0, abu_c),
+                       logfile, quiet)
+    with _clumping_reset(clump):
+        return _evolve_resident(scalars, src_flux, src_pos, uploads, N, photo_thin_table, thermal, clump)
 
 
-def _evolve_resident(dt, dr, src_flux, src_pos, uploads, N, photo_thin_table, minlogtau, dlogtau, R_max_LLS,
-                     convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile, quiet, thermal, clump):
+def _evolve_resident(scalars, src_flux, src_pos, uploads, N, photo_thin_table, thermal, clump):
     libasora = load_asora()
-    NumSrc = src_flux.shape[0]
-    NumCells = N * N * N
-    NumTau = photo_thin_table.shape[0]
-    conv_criterion = min(int(convergence_fraction * NumCells), (NumSrc - 1) / 3)          # evolve.py:127
-    srcpos_flat, normflux_flat = format_sources(np.asarray(src_pos), src_flux)
-    libasora.source_data_to_device(srcpos_flat, normflux_flat, NumSrc)
-    for which, grid in uploads.items():
-        libasora.grid_to_device(which, grid)
-    printlog("Copied source data to device.", logfile, quiet)
-    printlog("Calling evolve3D...", logfile, quiet)
-    printlog(f"dr [Mpc]: {dr/3.086e24:.3e}", logfile, quiet)
-    printlog(f"dt [years]: {dt/3.15576E+07:.3e}", logfile, quiet)
-    printlog(f"Running on {NumSrc:n} source(s), total normalized ionizing flux: {src_flux.sum():.2e}", logfile, quiet)
-    mean_ndens = libasora.grid_sum(_capi.GRID_NDENS) / NumCells
-    mean_xh = libasora.grid_sum(_capi.GRID_XH) / NumCells
-    printlog(f"Mean density (cgs): {mean_ndens:.3e}, Mean ionized fraction: {mean_xh:.3e}", logfile, quiet)
-    if clump is not None:
-        clump.apply(libasora, upload=False)          # (a grid came with `uploads`)
-        clump.log(libasora, NumCells, logfile, quiet)
-    printlog(f"Convergence Criterion (Number of points): {conv_criterion : n}", logfile, quiet, end='\n\n')
-    def loop():
-        return _device_loop(libasora, (dt, bh00, albpow, colh0, temph0, abu_c), R_max_LLS, sig, dr, minlogtau, dlogtau,
-                            NumTau, NumSrc, conv_criterion, convergence_fraction, NumCells, logfile, quiet)
-    niter, _ = loop() if thermal is None else _thermal_loop(libasora, thermal, loop, logfile, quiet)
-    printlog("Multiple source convergence reached.", logfile, quiet)
+    step = _prologue(libasora, scalars, N, photo_thin_table.shape[0], src_flux, np.asarray(src_pos), src_flux, uploads, clump,
+                     say_copied=True, clump_upload=False)
+    niter = _one_gpu_loop(libasora, step, thermal)
+    printlog("Multiple source convergence reached.", step.logfile, step.quiet)
     libasora.grid_copy(_capi.GRID_XH, _capi.GRID_XH_INTERMED)       # the next step starts from the new ionised fraction
     if thermal is not None:
         libasora.grid_copy(_capi.GRID_TEMP, _capi.GRID_TEMP_END)    # ... and from the new temperature
@@ -347,205 +464,53 @@ def _evolve_resident(dt, dr, src_flux, src_pos, uploads, N, photo_thin_table, mi
     return niter
 
 
-def _evolve(dt, dr, src_flux, src_pos, use_gpu, temp, ndens, xh, photo_thin_table, minlogtau, dlogtau,
-            R_max_LLS, convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile, quiet,
-            use_mpi=None, comm=None, rank=0, nprocs=1, thermal=None, clump=None):
-    if use_gpu and not cuda_is_init():
+def _evolve(scalars, src_flux, src_pos, grids, photo_thin_table, ranks=_ONE_RANK, thermal=None, clump=None):
+    """A use_gpu=True step on host arrays, grids = (temp, ndens, xh), on one GPU or across `ranks`; `thermal` on one GPU only."""
+    if not cuda_is_init():
         raise RuntimeError("GPU not initialized. Please initialize it by calling device_init(N)")
     _residency.reclaim()              # this step overwrites device grids a resident C2Ray object may be relying on
-    distributed = bool(use_mpi) and comm is not None and nprocs > 1
+    use_mpi, comm, rank, nprocs = ranks
+    distributed = _is_distributed(ranks)
     libasora = load_asora()
-
-    NumSrc = src_flux.shape[0]          # number of sources
+    temp, ndens, xh = grids
     N = temp.shape[0]                   # mesh size
-    NumCells = N * N * N
-    NumTau = photo_thin_table.shape[0]  # evolve.py:124 (the table LENGTH is what the reference passes)
-
-    # Convergence criterion, evolve.py:127 (computed from the TOTAL source count, evolve.py:346)
-    conv_criterion = min(int(convergence_fraction * NumCells), (NumSrc - 1) / 3)
-
-    prev_sum_xh1_int = 2 * NumCells
-    prev_sum_xh0_int = 2 * NumCells
-    converged = False
-    niter = 0
+    strategy = _loop_strategy(libasora, comm, distributed)
 
     # source shard of this rank, evolve.py:360-371
-    # (the sharded device loop needs the [k][j][i] twins, asora_evolve_begin_slab: not with ASORA_OPT_Z_TRANSPOSED = 0)
-    slab = (distributed and hasattr(comm, "slab_enqueue") and getattr(comm, "exchange", "") == "slab"
-            and not getattr(comm, "overlap", False) and _has_transposed_twins(libasora))
-    plan = None
-    all_pos, all_flux = np.asarray(src_pos), src_flux
-    if slab:
+    plan = src_i0 = None
+    if strategy == "slab":
         # the same contiguous blocks, of the list ordered by the first coordinate: a rank's rates then live on the
         # planes within R of its slab of sources, and only those planes are exchanged (pyc2ray_amd.dist.SlabPlan)
         from .dist import SlabPlan
-        all_pos, all_flux, bounds = comm.shard_sources_by_slab(all_pos, all_flux, nprocs)
-        i_start, i_end = bounds[rank], bounds[rank + 1]
-        plan = SlabPlan(N, nprocs, R_max_LLS, [all_pos[0, bounds[r]:bounds[r + 1]] - 1 for r in range(nprocs)])
-    elif distributed:
-        perrank = NumSrc // nprocs
-        i_start = int(rank * perrank)
-        i_end = int((rank + 1) * perrank) if rank != nprocs - 1 else NumSrc
+        all_pos, all_flux, bounds = comm.shard_sources_by_slab(np.asarray(src_pos), src_flux, nprocs)
+        my_pos, my_flux = all_pos[:, bounds[rank]:bounds[rank + 1]], all_flux[bounds[rank]:bounds[rank + 1]]
+        plan = SlabPlan(N, nprocs, scalars["R_max_LLS"], [all_pos[0, bounds[r]:bounds[r + 1]] - 1 for r in range(nprocs)])
     else:
-        i_start, i_end = 0, NumSrc
-    NumSrc_local = i_end - i_start
-    my_pos, my_flux = all_pos[:, i_start:i_end], all_flux[i_start:i_end]
-    # pipelined raytrace + all-reduce (pyc2ray_amd.dist, opt-in): the shard is traced in order of the first coordinate
-    pipelined = distributed and getattr(comm, "overlap", False) and hasattr(comm, "raytrace_and_allreduce")
-    src_i0 = None
-    if pipelined:
+        my_pos, my_flux = _contiguous_shard(src_pos, src_flux, ranks)
+    if strategy == "pipelined":         # the shard is traced in order of the first coordinate
         my_pos, my_flux = comm.sort_sources_for_overlap(my_pos, my_flux)
         src_i0 = np.asarray(my_pos[0]).astype(np.int64) - 1
-    srcpos_flat, normflux_flat = format_sources(my_pos, my_flux)
-    if distributed:
-        printlog(f"...rank={rank:n} has {NumSrc_local:n} sources.", logfile, quiet)
 
-    # Everything the step needs goes to the device once (evolve.py:136-155 keeps host copies instead)
-    libasora.source_data_to_device(srcpos_flat, normflux_flat, NumSrc_local)
-    libasora.grid_to_device(_capi.GRID_NDENS, ndens)
-    libasora.grid_to_device(_capi.GRID_TEMP, temp)
-    libasora.grid_to_device(_capi.GRID_XH, xh)
-    if distributed:
-        libasora.grid_copy(_capi.GRID_XH_AV, _capi.GRID_XH)          # xh_av = copy(xh)        evolve.py:136
-        libasora.grid_copy(_capi.GRID_XH_INTERMED, _capi.GRID_XH)    # xh_intermed = copy(xh)  evolve.py:137
+    step = _prologue(libasora, scalars, N, photo_thin_table.shape[0], src_flux, my_pos, my_flux,
+                     {_capi.GRID_NDENS: ndens, _capi.GRID_TEMP: temp, _capi.GRID_XH: xh}, clump, ranks=ranks,
+                     calling=f"Calling evolve3D with {nprocs:n} MPI-processors..." if distributed else "Calling evolve3D...",
+                     xh_copies=distributed, say_copied=not distributed)
+    if strategy == "one GPU":
+        niter = _one_gpu_loop(libasora, step, thermal)
+    elif strategy == "slab":
+        niter = _ranks_device_loop(libasora, step, comm, functools.partial(comm.slab_begin, libasora, plan),
+                                   "Doing Raytracing and Chemistry, slab-wise")
+    elif strategy == "all-reduce":
+        niter = _ranks_device_loop(libasora, step, comm, functools.partial(comm.reduce_begin, libasora),
+                                   "Doing Raytracing, all-reduce and Chemistry")
+    elif strategy == "pipelined":
+        niter = _pipelined_loop(libasora, step, comm, src_i0)
     else:
-        printlog("Copied source data to device.", logfile, quiet)
-    if clump is not None:
-        clump.apply(libasora)                                          # (every rank uploads the whole grid, as ndens)
+        niter = _three_call_loop(libasora, step, use_mpi, comm)
 
     if rank == 0:
-        if distributed:
-            printlog(f"Calling evolve3D with {nprocs:n} MPI-processors...", logfile, quiet)
-        else:
-            printlog("Calling evolve3D...", logfile, quiet)
-        printlog(f"dr [Mpc]: {dr/3.086e24:.3e}", logfile, quiet)
-        printlog(f"dt [years]: {dt/3.15576E+07:.3e}", logfile, quiet)
-        printlog(f"Running on {NumSrc:n} source(s), total normalized ionizing flux: {src_flux.sum():.2e}", logfile, quiet)
-        # the two means of evolve.py:160, summed on the device from the grids just uploaded
-        mean_ndens = libasora.grid_sum(_capi.GRID_NDENS) / NumCells
-        mean_xh = libasora.grid_sum(_capi.GRID_XH) / NumCells
-        printlog(f"Mean density (cgs): {mean_ndens:.3e}, Mean ionized fraction: {mean_xh:.3e}", logfile, quiet)
-        if clump is not None:
-            clump.log(libasora, NumCells, logfile, quiet)
-        printlog(f"Convergence Criterion (Number of points): {conv_criterion : n}", logfile, quiet, end='\n\n')
-
-    chem = (dt, bh00, albpow, colh0, temph0, abu_c)
-    if not distributed:
-        def loop():
-            return _device_loop(libasora, chem, R_max_LLS, sig, dr, minlogtau, dlogtau, NumTau, NumSrc_local, conv_criterion,
-                                convergence_fraction, NumCells, logfile, quiet)
-        niter, _ = loop() if thermal is None else _thermal_loop(libasora, thermal, loop, logfile, quiet)
-        converged = True
-
-    if slab:
-        # the device-resident loop, sharded (pyc2ray_amd.dist.TorchComm.slab_*): per iteration the trace, the rates to the
-        # owners of the planes, ONE fused pass on the own slab, xh_av back, and the convergence test on the device behind the
-        # in-place all-reduce of its three sums -- identical bits, hence the same decision, on every rank.  With RCCL a batch of
-        # iterations is enqueued per host round trip (launches beyond convergence do nothing); with gloo every exchange
-        # goes through the host anyway and the batch is one.
-        comm.slab_begin(libasora, plan, N, R_max_LLS, sig, dr, NumSrc_local, minlogtau, dlogtau, NumTau, chem,
-                        conv_criterion, convergence_fraction)
-        batch_max = max(1, min(EVOLVE_BATCH, 32)) if _comm_backend(comm) == "nccl" else 1
-        history = []
-        while not converged:
-            trt0 = time.time()
-            batch = _next_batch(history, batch_max, conv_criterion, convergence_fraction)
-            comm.slab_enqueue(libasora, batch)
-            _, converged, rows = comm.slab_poll(libasora, batch)
-            history += list(rows)
-            per_iteration = (time.time() - trt0) / max(len(rows), 1)
-            lines = []
-            for conv_flag, _s1, _s0, rel_change_xh1, _rel0 in rows:
-                niter += 1
-                conv_flag = int(conv_flag)
-                lines += [(f"Doing Raytracing and Chemistry, slab-wise (rank={rank:n})...", ' '),
-                          (f"rank={rank:n} took {per_iteration : .1e} s.", '\n')]
-                if rank == 0:
-                    lines += [(f"Number of non-converged points: {conv_flag} of {NumCells} ({conv_flag / NumCells * 100 : .3f} % ), "
-                               f"Relative change in ionfrac: {rel_change_xh1 : .2e}", '\n')]
-            printlog_lines(lines, logfile, quiet)
-
-    # full-grid all-reduce on the same device-resident loop (TorchComm.reduce_begin): trace, fold, all-reduce of the rate grid in
-    # place, ONE fused pass on the whole grid on every rank, test on the device -- batches of iterations per host round trip
-    # (asora_evolve_begin_slab needs the [k][j][i] twins: with ASORA_OPT_Z_TRANSPOSED = 0 the three-call loop below runs)
-    reduce_loop = (distributed and not slab and not pipelined and getattr(comm, "device_loop", False)
-                   and hasattr(comm, "reduce_begin") and hasattr(libasora, "evolve_slab_fold_all")
-                   and _has_transposed_twins(libasora))
-    if reduce_loop:
-        comm.reduce_begin(libasora, N, R_max_LLS, sig, dr, NumSrc_local, minlogtau, dlogtau, NumTau, chem, conv_criterion,
-                          convergence_fraction)
-        batch_max = max(1, min(EVOLVE_BATCH, 32)) if _comm_backend(comm) == "nccl" else 1
-        history = []
-        while not converged:
-            trt0 = time.time()
-            # (an all-reduce is not gated by the device's `done` flag: every iteration enqueued beyond convergence still sums
-            #  the N^3 out-box over the ranks, so the batch shrinks as the test comes within reach)
-            batch = _next_batch(history, batch_max, conv_criterion, convergence_fraction)
-            comm.slab_enqueue(libasora, batch)
-            _, converged, rows = comm.slab_poll(libasora, batch)
-            history += list(rows)
-            per_iteration = (time.time() - trt0) / max(len(rows), 1)
-            lines = []
-            for conv_flag, _s1, _s0, rel_change_xh1, _rel0 in rows:
-                niter += 1
-                conv_flag = int(conv_flag)
-                lines += [(f"Doing Raytracing, all-reduce and Chemistry (rank={rank:n})...", ' '),
-                          (f"rank={rank:n} took {per_iteration : .1e} s.", '\n')]
-                if rank == 0:
-                    lines += [(f"Number of non-converged points: {conv_flag} of {NumCells} ({conv_flag / NumCells * 100 : .3f} % ), "
-                               f"Relative change in ionfrac: {rel_change_xh1 : .2e}", '\n')]
-            printlog_lines(lines, logfile, quiet)
-
-    while distributed and not slab and not reduce_loop and not converged:
-        niter += 1
-
-        # (1) raytracing, evolve.py:174-196
-        trt0 = time.time()
-        if pipelined:
-            # raytrace, sum over ranks and chemistry slab by slab (pyc2ray_amd.dist): steps (1) and (2) in one
-            printlog(f"Doing Raytracing and Chemistry, pipelined (rank={rank:n})...", logfile, quiet, ' ')
-            conv_flag, sum_xh1_int, sum_xh0_int = comm.raytrace_and_allreduce(
-                libasora, N, R_max_LLS, sig, dr, NumSrc_local, minlogtau, dlogtau, NumTau, src_i0=src_i0, chemistry=chem)
-            printlog(f"rank={rank:n} took {(time.time()-trt0) : .1e} s.", logfile, quiet)
-        else:
-            printlog(f"Doing Raytracing (rank={rank:n})...", logfile, quiet, ' ')
-            libasora.raytrace_device(R_max_LLS, sig, dr, 0, NumSrc_local, minlogtau, dlogtau, NumTau)
-            libasora.synchronize()
-            printlog(f"rank={rank:n} took {(time.time()-trt0) : .1e} s.", logfile, quiet)
-            _allreduce_phi(libasora, N, use_mpi, comm, rank)
-
-            # (2) chemistry, evolve.py:207-211.  Every rank runs it on the identical summed rates
-            # (the reference runs it on rank 0 and broadcasts two N^3 grids, evolve.py:439-481).
-            tch0 = time.time()
-            if rank == 0:
-                printlog("Doing Chemistry...", logfile, quiet, ' ')
-            conv_flag, sum_xh1_int, sum_xh0_int = libasora.chemistry_device(*chem)
-            if rank == 0:
-                printlog(f"took {(time.time()-tch0) : .1f} s.", logfile, quiet)
-
-        # (3) global convergence, evolve.py:216-236
-        if sum_xh1_int > 0.0:
-            rel_change_xh1 = np.abs((sum_xh1_int - prev_sum_xh1_int) / sum_xh1_int)
-        else:
-            rel_change_xh1 = 1.0
-        if sum_xh0_int > 0.0:
-            rel_change_xh0 = np.abs((sum_xh0_int - prev_sum_xh0_int) / sum_xh0_int)
-        else:
-            rel_change_xh0 = 1.0
-
-        if rank == 0:
-            printlog(f"Number of non-converged points: {conv_flag} of {NumCells} ({conv_flag / NumCells * 100 : .3f} % ), "
-                     f"Relative change in ionfrac: {rel_change_xh1 : .2e}", logfile, quiet)
-
-        converged = (conv_flag < conv_criterion) or ((rel_change_xh1 < convergence_fraction) and
-                                                     (rel_change_xh0 < convergence_fraction))
-        converged = _agree_on_convergence(comm, converged)            # evolve.py:484-489
-        prev_sum_xh1_int = sum_xh1_int
-        prev_sum_xh0_int = sum_xh0_int
-
-    if rank == 0:
-        printlog("Multiple source convergence reached.", logfile, quiet)
-    if slab:       # every rank returns the whole fields (evolve.py:480-481,497): collect the owners' slabs
+        printlog("Multiple source convergence reached.", step.logfile, step.quiet)
+    if strategy == "slab":       # every rank returns the whole fields (evolve.py:480-481,497): collect the owners' slabs
         comm.slab_gather(libasora, plan, _capi.GRID_XH_INTERMED, N)
         comm.slab_gather(libasora, plan, _capi.GRID_PHI_ION, N)
     # laid out like `xh`, as np.empty_like would; in page-locked memory (pyc2ray_amd/_pinned.py)
@@ -556,6 +521,29 @@ def _evolve(dt, dr, src_flux, src_pos, use_gpu, temp, ndens, xh, photo_thin_tabl
     if thermal is not None:
         temp_new = libasora.grid_to_host(_capi.GRID_TEMP_END, libasora.host_empty((N, N, N), order=like_xh))
         return xh_new, phi_ion, temp_new
+    return xh_new, phi_ion
+
+
+def _evolve_cpu_semantics(scalars, src_flux, src_pos, grids, tables, subbox, ranks=_ONE_RANK, clump=None):
+    """The use_gpu=False branch of the reference on host arrays: the loop of :func:`_subbox_loop`, subbox = (max_subbox,
+    subboxsize, loss_fraction).  Like the use_gpu=True loop this one keeps the grids on the device for the whole step (the
+    reference's host round trips are what ``libc2ray.raytracing.do_all_sources`` / ``libc2ray.chemistry.global_pass`` of this
+    package still offer)."""
+    _residency.reclaim()              # this step overwrites device grids a resident C2Ray object may be relying on
+    libasora = load_asora()
+    temp, ndens, xh = grids
+    N = temp.shape[0]
+    my_pos, my_flux = _contiguous_shard(src_pos, src_flux, ranks)
+    step = _prologue(libasora, scalars, N, tables[0].shape[0], src_flux, my_pos, my_flux,
+                     {_capi.GRID_NDENS: ndens, _capi.GRID_TEMP: temp, _capi.GRID_XH: xh}, clump,
+                     ranks=ranks, xh_copies=True, tables=tables)
+    niter = _subbox_loop(libasora, step, subbox, ranks)
+    if step.rank == 0:
+        printlog("Multiple source convergence reached.", step.logfile, step.quiet)
+    # Fortran-ordered results, as the reference's CPU branch returns them (evolve.py:178)
+    xh_new = libasora.grid_to_host(_capi.GRID_XH_INTERMED, libasora.host_empty((N, N, N), order='F'))
+    phi_ion = libasora.grid_to_host(_capi.GRID_PHI_ION, libasora.host_empty((N, N, N), order='F'))
+    _evolve.last_niter = niter
     return xh_new, phi_ion
 
 
@@ -592,19 +580,15 @@ def evolve3D(dt, dr,
     recombination cooling is clumped as well).
     """
     clump = _clumping_spec(clumping, np.shape(temp)[0])
-    if not use_gpu:
-        if thermal is not None:
-            raise ValueError("evolve3D: the thermal mode needs use_gpu=True (the use_gpu=False raytracer has no thermal form)")
-        return _clumping_reset(clump, lambda: _evolve_cpu_semantics(
-            dt, dr, src_flux, src_pos, max_subbox, subboxsize, loss_fraction, temp, ndens, xh, photo_thin_table,
-            photo_thick_table, minlogtau, dlogtau, R_max_LLS, convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c,
-            logfile, quiet, clump=clump))
-    if thermal is None and clump is None:
-        return _evolve(dt, dr, src_flux, src_pos, use_gpu, temp, ndens, xh, photo_thin_table, minlogtau, dlogtau,
-                       R_max_LLS, convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile, quiet)
-    return _clumping_reset(clump, lambda: _evolve(
-        dt, dr, src_flux, src_pos, use_gpu, temp, ndens, xh, photo_thin_table, minlogtau, dlogtau, R_max_LLS,
-        convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile, quiet, thermal=thermal, clump=clump))
+    if not use_gpu and thermal is not None:
+        raise ValueError("evolve3D: the thermal mode needs use_gpu=True (the use_gpu=False raytracer has no thermal form)")
+    scalars = _scalars(dt, dr, R_max_LLS, convergence_fraction, sig, minlogtau, dlogtau, (bh00, albpow, colh0, temph0, abu_c),
+                       logfile, quiet)
+    with _clumping_reset(clump):
+        if use_gpu:
+            return _evolve(scalars, src_flux, src_pos, (temp, ndens, xh), photo_thin_table, thermal=thermal, clump=clump)
+        return _evolve_cpu_semantics(scalars, src_flux, src_pos, (temp, ndens, xh), (photo_thin_table, photo_thick_table),
+                                     (max_subbox, subboxsize, loss_fraction), clump=clump)
 
 
 def evolve3D_MPI(dt, dr,
@@ -632,16 +616,11 @@ def evolve3D_MPI(dt, dr,
         raise ValueError("evolve3D_MPI: the thermal mode is single-GPU only (no slab exchange of heating rates and "
                          "temperatures); use evolve3D with use_gpu=True")
     clump = _clumping_spec(clumping, np.shape(temp)[0])
-    if not use_gpu:
-        return _clumping_reset(clump, lambda: _evolve_cpu_semantics(
-            dt, dr, src_flux, src_pos, max_subbox, subboxsize, loss_fraction, temp, ndens, xh, photo_thin_table,
-            photo_thick_table, minlogtau, dlogtau, R_max_LLS, convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c,
-            logfile, quiet, use_mpi=use_mpi, comm=comm, rank=rank, nprocs=nprocs, clump=clump))
-    if clump is None:
-        return _evolve(dt, dr, src_flux, src_pos, use_gpu, temp, ndens, xh, photo_thin_table, minlogtau, dlogtau,
-                       R_max_LLS, convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile, quiet,
-                       use_mpi=use_mpi, comm=comm, rank=rank, nprocs=nprocs)
-    return _clumping_reset(clump, lambda: _evolve(
-        dt, dr, src_flux, src_pos, use_gpu, temp, ndens, xh, photo_thin_table, minlogtau, dlogtau, R_max_LLS,
-        convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile, quiet,
-        use_mpi=use_mpi, comm=comm, rank=rank, nprocs=nprocs, clump=clump))
+    scalars = _scalars(dt, dr, R_max_LLS, convergence_fraction, sig, minlogtau, dlogtau, (bh00, albpow, colh0, temph0, abu_c),
+                       logfile, quiet)
+    ranks = (use_mpi, comm, rank, nprocs)
+    with _clumping_reset(clump):
+        if use_gpu:
+            return _evolve(scalars, src_flux, src_pos, (temp, ndens, xh), photo_thin_table, ranks, clump=clump)
+        return _evolve_cpu_semantics(scalars, src_flux, src_pos, (temp, ndens, xh), (photo_thin_table, photo_thick_table),
+                                     (max_subbox, subboxsize, loss_fraction), ranks, clump=clump)
