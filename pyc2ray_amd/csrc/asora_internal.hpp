@@ -1,8 +1,13 @@
 // Internal declarations shared by the translation units of libasora_hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -263,14 +268,20 @@ struct State {
     // line of 8 cells, [i][j][k >> 3] for the plain layout and, behind it, [k][j][i >> 3] for the transposed one.  The fused
     // pass neither reads nor zeroes the lines no source reaches (they are zero and stay zero): 32 of its 88 bytes per cell.
     // Valid for (source upload, source range, R); nullptr in the pass = every line is reachable.
-    unsigned char *reach_mask = nullptr;
-    size_t reach_bytes = 0;                 // of ONE layout
-    bool reach_valid = false, reach_in_use = false;
-    bool reach_pays = false;                // enough lines out of reach for the mask to pay (counted when the mask is built)
-    unsigned long long *reach_count_dev = nullptr;
-    long reach_src_generation = -1;
-    int reach_src_begin = 0, reach_src_count = 0;
-    double reach_R = -1.0;
+    struct ReachMask {
+        unsigned char *mask = nullptr;
+        size_t bytes = 0;                   // of ONE layout
+        unsigned long long *count_dev = nullptr;
+        bool in_use = false;
+        bool pays = false;                  // enough lines out of reach for the mask to pay (counted when the mask is built)
+        struct Key {                        // what `pays` (and the mask, where one was built) has been decided for
+            bool valid = false;
+            long src_generation = -1;
+            int src_begin = 0, src_count = 0;
+            double R = -1.0;
+            bool operator==(const Key &o) const { return valid == o.valid && src_generation == o.src_generation && src_begin == o.src_begin && src_count == o.src_count && R == o.R; }
+        } key;
+    } reach;
     long src_generation = 0;                // counts asora_source_data_to_device calls
 
     // thermal mode (asora_thermal_params): TEMP_END and the heating accumulators of the device loop are allocated on first use
@@ -441,7 +452,7 @@ struct ChemTileParams {
     EvolveStatus *status = nullptr;
     bool local_sums = false;                         // status only gates the launch: the reductions stop at red_final, the convergence
                                                      // test follows later, on the sums over all ranks (launch_convergence_test)
-    const unsigned char *reach_a = nullptr, *reach_t = nullptr;   // fold + emit: lines of the accumulators any source reaches (State::reach_mask), or nullptr
+    const unsigned char *reach_a = nullptr, *reach_t = nullptr;   // fold + emit: lines of the accumulators any source reaches (State::reach), or nullptr
     bool fold = false, emit = false;
     // the grid has one temperature (launch_temp_probe): its factors, evaluated on the device, travel with the parameters
     int uniform = 0, uniform_t_ok = 0;
@@ -474,5 +485,27 @@ int launch_convergence_test(State &st, const double *sums, EvolveStatus *status)
 // mask[0 .. N*N*NL) for [i][j][k >> 3], mask[N*N*NL .. ) for [k][j][i >> 3], NL = (N + 7) / 8: 1 where a source of the range reaches
 int launch_reach_mask(State &st, const int32_t *src_pos, int src_begin, int src_count, double R, unsigned char *mask, size_t bytes_one_layout);
 int launch_reach_count(State &st, const unsigned char *mask, size_t bytes_both_layouts, unsigned long long *out_dev);
+
+// ---------------------------------------------------------------------------------------------
+// Host API layer (api.hip and the *_api.hip units): what more than one of them needs
+// ---------------------------------------------------------------------------------------------
+// api.hip
+int ensure_runtime();                           // stream, events, reduction buffers: needed with or without device_init
+int require_init(const char *who);
+int check_N(const char *who, int N);
+// fail(code, who + ": " + tail) unless the planes lie in the mesh / the sources among the uploaded ones
+int check_planes(const char *who, int code, const char *tail, int i_begin, int i_count);
+int check_sources(const char *who, int code, const std::string &tail, int src_begin, int src_count);
+int require_grids(const char *who, std::initializer_list<int> grids);     // code 4 unless every one of them holds data
+// grids_api.hip
+int ensure_optional_grid(int which);            // PHI_HEAT, TEMP_END, CLUMP: allocated on first use; any other grid: nothing to do
+// raytrace_api.hip
+int reset_counters();
+int require_raytrace_inputs(const char *who, double R, int NumTau, bool density, bool xh_av);
+void fill_rt_params(RtParams &p, double R, double sig, double dr, double minlogtau, double dlogtau, int NumTau, int radius_path = 0);
+// chemistry_api.hip
+int ensure_red_capacity(size_t entries);
+int ensure_temp_probe(double bh00, double albpow, double colh0, double temph0);
+ChemTileParams chem_tile_common(int i_begin, int i_count, const double chem[6]);
 
 } // namespace asora

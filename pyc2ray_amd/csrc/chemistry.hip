@@ -708,7 +708,7 @@ int launch_chemistry_tiles(State &st, ChemTileParams &p, hipStream_t stream)
     const int ck = clumping_of(st, p.thermal, st.ncell, q.clump, q.clump_c, f);
     if (ck > 1) return ck;
     q.bh00 = f * p.bh00;
-    // the uniform-temperature forms take brech0 from the probe (api.hip: ensure_temp_probe), which folds in the mode-1 constant
+    // the uniform-temperature forms take brech0 from the probe (chemistry_api.hip: ensure_temp_probe), which folds in the mode-1 constant
     if (p.uniform && !p.thermal && st.temp_probe_clump != f)
         return fail(4, "chemistry: the temperature probe was made for another clumping mode (set asora_clumping before asora_evolve_begin)");
     {

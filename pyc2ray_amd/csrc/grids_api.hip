@@ -1,0 +1,285 @@
+// grids_api.hip -- grids, rate tables and sources between the host and the device (asora_grid_*, asora_planes_to_*, the table and
+// source uploads of src/asora/memory.cu).  An upload has left the host buffer when its call returns
+// (a synchronise or a blocking copy: the buffer may be pageable).
+#include "asora_internal.hpp"
+#include "rates_device.hpp"
+
+
+namespace asora {
+
+// The grids that exist only once something needs them, allocated on first use:
+//   PHI_HEAT  with its [k][j][i] twin (2 N^3 doubles: 2 GiB at 512^3): the heating tables are uploaded, or a caller hands the
+//             grid over (evolve3D never does)
+//   TEMP_END  thermal mode only (asora_thermal_params): the end-of-step temperature
+//   CLUMP     clumping mode 2 only (asora_clumping): the per-cell factors, with their first upload
+// Every other grid is a part of the arena.
+int ensure_optional_grid(int which)
+{
+    State &st = state();
+    if ((which != ASORA_GRID_PHI_HEAT && which != ASORA_GRID_TEMP_END && which != ASORA_GRID_CLUMP) || st.grid[which]) return 0;
+    const bool twin = which == ASORA_GRID_PHI_HEAT;
+    ASORA_HIP_TRY(hipMalloc(&st.grid[which], (twin ? 2 : 1) * st.ncell * sizeof(double)));
+    if (twin) st.heat_t = st.grid[which] + st.ncell;
+    st.grid_valid[which] = false;
+    return 0;
+}
+
+} // namespace asora
+
+using namespace asora;
+
+extern "C" {
+
+int asora_grid_to_device(int which, const double *host, int N, char order)
+{
+    clear_error();
+    if (int rc = require_init("grid_to_device")) return rc;
+    if (int rc = check_N("grid_to_device", N)) return rc;
+    if (which < 0 || which >= ASORA_GRID_COUNT) return fail(3, "grid_to_device: bad grid selector");
+    if (!host) return fail(3, "grid_to_device: null host pointer");
+    State &st = state();
+    if (int rc = ensure_optional_grid(which)) return rc;
+    st.zero_since_probe = std::max(st.zero_since_probe, 48);   // new medium: look again for cells beyond the table soon (launch_raytrace: at 64)
+    const size_t bytes = st.ncell * sizeof(double);
+    if (order == 'C' || order == 'c') {
+        ASORA_HIP_TRY(hipMemcpyAsync(st.grid[which], host, bytes, hipMemcpyHostToDevice, st.stream));
+    } else if (order == 'F' || order == 'f') {
+        ASORA_HIP_TRY(hipMemcpyAsync(st.staging, host, bytes, hipMemcpyHostToDevice, st.stream));
+        if (int rc = launch_transpose(st, st.staging, st.grid[which], N)) return rc;
+    } else
+        return fail(3, "grid_to_device: order must be 'C' or 'F'");
+    ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
+    st.grid_valid[which] = true;
+    if (which == ASORA_GRID_TEMP) st.temp_probe_valid = false;
+    return 0;
+}
+
+int asora_grid_to_host(int which, double *host, int N, char order)
+{
+    clear_error();
+    if (int rc = require_init("grid_to_host")) return rc;
+    if (int rc = check_N("grid_to_host", N)) return rc;
+    if (which < 0 || which >= ASORA_GRID_COUNT) return fail(3, "grid_to_host: bad grid selector");
+    if (!host) return fail(3, "grid_to_host: null host pointer");
+    State &st = state();
+    if (!st.grid[which] || !st.grid_valid[which]) return fail(3, "grid_to_host: grid " + std::to_string(which) + " holds no data");
+    const size_t bytes = st.ncell * sizeof(double);
+    if (order == 'C' || order == 'c') {
+        ASORA_HIP_TRY(hipMemcpyAsync(host, st.grid[which], bytes, hipMemcpyDeviceToHost, st.stream));
+    } else if (order == 'F' || order == 'f') {
+        if (int rc = launch_transpose(st, st.grid[which], st.staging, N)) return rc;
+        ASORA_HIP_TRY(hipMemcpyAsync(host, st.staging, bytes, hipMemcpyDeviceToHost, st.stream));
+    } else
+        return fail(3, "grid_to_host: order must be 'C' or 'F'");
+    ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
+    return 0;
+}
+
+int asora_grid_copy(int dst, int src)
+{
+    clear_error();
+    if (int rc = require_init("grid_copy")) return rc;
+    if (dst < 0 || dst >= ASORA_GRID_COUNT || src < 0 || src >= ASORA_GRID_COUNT || dst == src)
+        return fail(3, "grid_copy: bad grid selectors");
+    State &st = state();
+    if (!st.grid_valid[src]) return fail(3, "grid_copy: source grid holds no data");
+    if (int rc = ensure_optional_grid(dst)) return rc;
+    ASORA_HIP_TRY(hipMemcpyAsync(st.grid[dst], st.grid[src], st.ncell * sizeof(double), hipMemcpyDeviceToDevice,
+                                 st.stream));
+    st.grid_valid[dst] = true;
+    if (dst == ASORA_GRID_TEMP) st.temp_probe_valid = false;
+    return 0;
+}
+
+int asora_grid_scale(int which, double factor)
+{
+    clear_error();
+    if (int rc = require_init("grid_scale")) return rc;
+    if (which < 0 || which >= ASORA_GRID_COUNT) return fail(3, "grid_scale: bad grid selector");
+    State &st = state();
+    if (!st.grid_valid[which]) return fail(3, "grid_scale: grid " + std::to_string(which) + " holds no data");
+    if (int rc = launch_scale(st, st.grid[which], st.ncell, factor)) return rc;
+    if (which == ASORA_GRID_TEMP) st.temp_probe_valid = false;
+    return 0;
+}
+
+int asora_grid_sum(int which, double *sum)
+{
+    clear_error();
+    if (int rc = require_init("grid_sum")) return rc;
+    if (which < 0 || which >= ASORA_GRID_COUNT) return fail(3, "grid_sum: bad grid selector");
+    if (!sum) return fail(3, "grid_sum: null output pointer");
+    State &st = state();
+    if (!st.grid_valid[which]) return fail(3, "grid_sum: grid " + std::to_string(which) + " holds no data");
+    if (!st.temp_probe_dev) ASORA_HIP_TRY(hipMalloc(&st.temp_probe_dev, sizeof(double) * 8));
+    if (int rc = launch_grid_sum(st, st.grid[which], st.ncell, st.temp_probe_dev + 5)) return rc;
+    ASORA_HIP_TRY(hipMemcpyAsync(sum, st.temp_probe_dev + 5, sizeof(double), hipMemcpyDeviceToHost, st.stream));
+    ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
+    return 0;
+}
+
+int asora_host_alloc(size_t bytes, void **host)
+{
+    clear_error();
+    if (!host || bytes == 0) return fail(3, "host_alloc: null pointer or zero size");
+    *host = nullptr;
+    ASORA_HIP_TRY(hipHostMalloc(host, bytes, hipHostMallocDefault));
+    return 0;
+}
+
+int asora_host_free(void *host)
+{
+    clear_error();
+    if (!host) return 0;
+    ASORA_HIP_TRY(hipHostFree(host));
+    return 0;
+}
+
+void *asora_device_ptr(int which)
+{
+    if (!state().init || which < 0 || which >= ASORA_GRID_COUNT) return nullptr;
+    return state().grid[which];
+}
+
+int asora_density_to_device(const double *ndens, int N)
+{
+    return asora_grid_to_device(ASORA_GRID_NDENS, ndens, N, 'C');
+}
+
+int asora_photo_table_to_device(const double *thin_table, const double *thick_table, int NumTau)
+{
+    clear_error();
+    if (int rc = require_init("photo_table_to_device")) return rc;
+    if (NumTau < 1 || !thin_table || !thick_table) return fail(3, "photo_table_to_device: empty table");
+    State &st = state();
+    st.zero_since_probe = std::max(st.zero_since_probe, 48);
+    if (st.tables) { (void)hipFree(st.tables); st.tables = nullptr; }
+    // device layout: rates_device.hpp (one 16-byte load serves the linear interpolation of photo_lookuptable, rates.cu:82)
+    // (at least 16 elements: the kernels' pipeline-priming loads read a few fixed small offsets whatever the table's length)
+    std::vector<double2> pairs(std::max<size_t>(4 * (size_t)NumTau, 16), double2{0.0, 0.0});   // [thick | thin | heat thick | heat thin]
+    pack_rate_table(pairs.data(), 0, thick_table, NumTau);
+    pack_rate_table(pairs.data(), 1, thin_table, NumTau);
+    ASORA_HIP_TRY(hipMalloc(&st.tables, pairs.size() * sizeof(double2)));
+    ASORA_HIP_TRY(hipMemcpy(st.tables, pairs.data(), pairs.size() * sizeof(double2), hipMemcpyHostToDevice));
+    st.table_len = NumTau;
+    st.have_heat_tables = false;
+    return 0;
+}
+
+int asora_heat_table_to_device(const double *heat_thin_table, const double *heat_thick_table, int NumTau)
+{
+    clear_error();
+    if (int rc = require_init("heat_table_to_device")) return rc;
+    State &st = state();
+    if (!st.tables) return fail(4, "heat_table_to_device: upload the photo tables first (photo_table_to_device)");
+    if (NumTau != st.table_len || !heat_thin_table || !heat_thick_table)
+        return fail(3, "heat_table_to_device: the heating tables must have the length of the photo tables (" +
+                           std::to_string(st.table_len) + ")");
+    if (int rc = ensure_optional_grid(ASORA_GRID_PHI_HEAT)) return rc;
+    std::vector<double2> pairs(4 * (size_t)NumTau, double2{0.0, 0.0});
+    pack_rate_table(pairs.data(), 2, heat_thick_table, NumTau);
+    pack_rate_table(pairs.data(), 3, heat_thin_table, NumTau);
+    const size_t lo = rate_table_byte_offset(2, NumTau), hi = rate_table_byte_offset(4, NumTau);
+    ASORA_HIP_TRY(hipMemcpy(reinterpret_cast<char *>(st.tables) + lo, reinterpret_cast<const char *>(pairs.data()) + lo, hi - lo,
+                            hipMemcpyHostToDevice));
+    st.have_heat_tables = true;
+    return 0;
+}
+
+int asora_source_data_to_device(const int32_t *pos, const double *flux, int NumSrc)
+{
+    clear_error();
+    if (int rc = require_init("source_data_to_device")) return rc;
+    if (NumSrc < 0 || (NumSrc > 0 && (!pos || !flux))) return fail(3, "source_data_to_device: bad arguments");
+    State &st = state();
+    st.zero_since_probe = std::max(st.zero_since_probe, 48);
+    // validate on the host before anything reaches a kernel: positions index the grid directly
+    for (int s = 0; s < NumSrc; ++s)
+        for (int ax = 0; ax < 3; ++ax)
+            if (pos[3 * s + ax] < 0 || pos[3 * s + ax] >= st.N)
+                return fail(3, "source_data_to_device: source " + std::to_string(s) + " lies outside the mesh (0-based " +
+                                   std::to_string(pos[3 * s + ax]) + " on axis " + std::to_string(ax) + ")");
+    if (st.src_pos) { (void)hipFree(st.src_pos); st.src_pos = nullptr; }          // memory.cu:102-103
+    if (st.src_flux) { (void)hipFree(st.src_flux); st.src_flux = nullptr; }
+    if (st.src_pos_sorted) { (void)hipFree(st.src_pos_sorted); st.src_pos_sorted = nullptr; }
+    if (st.src_flux_sorted) { (void)hipFree(st.src_flux_sorted); st.src_flux_sorted = nullptr; }
+    st.src_i0_sorted.clear();
+    st.src_pos_host.clear(); st.src_pos_sorted_host.clear();
+    release_pair_lists(st);
+    st.num_src = 0;
+    if (NumSrc == 0) return 0;
+    ASORA_HIP_TRY(hipMalloc(&st.src_pos, sizeof(int32_t) * 3 * (size_t)NumSrc));
+    ASORA_HIP_TRY(hipMalloc(&st.src_flux, sizeof(double) * (size_t)NumSrc));
+    ASORA_HIP_TRY(hipMemcpy(st.src_pos, pos, sizeof(int32_t) * 3 * (size_t)NumSrc, hipMemcpyHostToDevice));
+    ASORA_HIP_TRY(hipMemcpy(st.src_flux, flux, sizeof(double) * (size_t)NumSrc, hipMemcpyHostToDevice));
+    {   // a second copy in lexicographic order of the position (the sum over sources does not depend on their order): what
+        // a call that traces the WHOLE list works from -- sources that run side by side are then neighbours in space and
+        // share nHI and rate lines (measured -2 % on the trace at r_RT = 16 and 32) -- and, ordered by the first
+        // coordinate, what the pipelined asora_do_all_sources cuts into slabs
+        std::vector<int> order((size_t)NumSrc);
+        for (int s = 0; s < NumSrc; ++s) order[s] = s;
+        std::stable_sort(order.begin(), order.end(), [pos](int a, int b) {
+            if (pos[3 * a] != pos[3 * b]) return pos[3 * a] < pos[3 * b];
+            if (pos[3 * a + 1] != pos[3 * b + 1]) return pos[3 * a + 1] < pos[3 * b + 1];
+            return pos[3 * a + 2] < pos[3 * b + 2];
+        });
+        std::vector<int32_t> ps(3 * (size_t)NumSrc);
+        std::vector<double> fs((size_t)NumSrc);
+        st.src_i0_sorted.resize((size_t)NumSrc);
+        for (int s = 0; s < NumSrc; ++s) {
+            const int o = order[s];
+            ps[3 * s] = pos[3 * o]; ps[3 * s + 1] = pos[3 * o + 1]; ps[3 * s + 2] = pos[3 * o + 2];
+            fs[s] = flux[o];
+            st.src_i0_sorted[s] = pos[3 * o];
+        }
+        ASORA_HIP_TRY(hipMalloc(&st.src_pos_sorted, sizeof(int32_t) * 3 * (size_t)NumSrc));
+        ASORA_HIP_TRY(hipMalloc(&st.src_flux_sorted, sizeof(double) * (size_t)NumSrc));
+        ASORA_HIP_TRY(hipMemcpy(st.src_pos_sorted, ps.data(), sizeof(int32_t) * 3 * (size_t)NumSrc, hipMemcpyHostToDevice));
+        ASORA_HIP_TRY(hipMemcpy(st.src_flux_sorted, fs.data(), sizeof(double) * (size_t)NumSrc, hipMemcpyHostToDevice));
+        st.src_pos_sorted_host.swap(ps);
+    }
+    st.src_pos_host.assign(pos, pos + 3 * (size_t)NumSrc);
+    st.num_src = NumSrc;
+    st.src_generation += 1;
+    return 0;
+}
+
+// Contiguous runs of i-planes of a grid to / from the host (C order: plane i is N*N consecutive doubles).  What a
+// multi-GPU rank exchanges are such runs (the planes its sources reach, the planes whose chemistry it owns).
+int asora_planes_to_host(int which, int i_begin, int i_count, double *host)
+{
+    clear_error();
+    if (int rc = require_init("planes_to_host")) return rc;
+    State &st = state();
+    if (which < 0 || which >= ASORA_GRID_COUNT) return fail(3, "planes_to_host: bad grid selector");
+    if (int rc = check_planes("planes_to_host", 3, "bad plane range", i_begin, i_count)) return rc;
+    if (i_count == 0) return 0;
+    if (!host) return fail(3, "planes_to_host: null host pointer");
+    if (!st.grid_valid[which]) return fail(3, "planes_to_host: grid " + std::to_string(which) + " holds no data");
+    const size_t plane = (size_t)st.N * st.N;
+    ASORA_HIP_TRY(hipMemcpyAsync(host, st.grid[which] + (size_t)i_begin * plane, (size_t)i_count * plane * sizeof(double),
+                                 hipMemcpyDeviceToHost, st.stream));
+    ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
+    return 0;
+}
+
+int asora_planes_to_device(int which, int i_begin, int i_count, const double *host)
+{
+    clear_error();
+    if (int rc = require_init("planes_to_device")) return rc;
+    State &st = state();
+    if (which < 0 || which >= ASORA_GRID_COUNT) return fail(3, "planes_to_device: bad grid selector");
+    if (int rc = check_planes("planes_to_device", 3, "bad plane range", i_begin, i_count)) return rc;
+    if (i_count == 0) return 0;
+    if (!host) return fail(3, "planes_to_device: null host pointer");
+    if (int rc = ensure_optional_grid(which)) return rc;
+    const size_t plane = (size_t)st.N * st.N;
+    ASORA_HIP_TRY(hipMemcpyAsync(st.grid[which] + (size_t)i_begin * plane, host, (size_t)i_count * plane * sizeof(double),
+                                 hipMemcpyHostToDevice, st.stream));
+    ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
+    st.grid_valid[which] = true;             // (the caller vouches for the planes it did not write)
+    if (which == ASORA_GRID_TEMP) st.temp_probe_valid = false;
+    return 0;
+}
+
+} // extern "C"

@@ -976,6 +976,63 @@ def test_sharded_device_loop_refuses_calls_out_of_order_or_out_of_range(asora):
     p.device_close()
 
 
+def test_one_gpu_device_loop_refuses_calls_out_of_order_or_out_of_range(asora):
+    """The preconditions of asora_evolve_begin / _enqueue / _poll and of the stand-alone chemistry calls (include/asora_hip.h):
+    no step begun, a source range beyond the upload, a grid that holds no data, too many iterations per call or between two
+    polls, the sliced pass in thermal mode -- error codes with messages, nothing launched."""
+    p, lib, capi = asora
+    N = 16
+    nd, xh, dr = cases.grid(N, "lognormal", 5, 0.1)
+    thin, thick, dlog = cases.soft_tables()
+    pos, flux = cases.sources(N, 3, 6, flux=1.0)
+    if p.cuda_is_init():
+        p.device_close()
+    p.device_init(N, 8)
+    p.photo_table_to_device(thin, thick)
+    p0, f0 = cases.flat_sources(pos, flux)
+    lib.source_data_to_device(p0, f0, 3)
+    lib.grid_to_device(capi.GRID_NDENS, nd)
+    lib.grid_to_device(capi.GRID_XH, xh)
+    chem = (3.15576e13, cases.BH00, cases.ALBPOW, cases.COLH0, cases.TEMPH0, cases.ABU_C)
+    rt = (4.0, cases.SIG, dr, cases.MINLOGTAU, dlog, thin.shape[0])
+    with pytest.raises(RuntimeError, match="no evolve step in progress"):
+        lib.evolve_enqueue(1)
+    with pytest.raises(RuntimeError, match="no evolve step in progress"):
+        lib.evolve_poll(4)
+    with pytest.raises(RuntimeError, match="holds no data"):           # TEMP not uploaded
+        lib.evolve_begin(*chem, *rt, 0, 3, -1.0, 0.0)
+    lib.grid_to_device(capi.GRID_TEMP, np.full((N, N, N), 1e4))
+    lib.grid_copy(capi.GRID_XH_AV, capi.GRID_XH)
+    with pytest.raises(RuntimeError, match="holds no data"):           # PHI_ION never written
+        lib.chemistry_device(*chem)
+    with pytest.raises(RuntimeError, match="outside the 3 uploaded sources"):
+        lib.evolve_begin(*chem, *rt, 1, 3, -1.0, 0.0)
+    with pytest.raises(RuntimeError, match="no evolve step in progress"):      # a refused begin opens no step
+        lib.evolve_enqueue(1)
+    lib.evolve_begin(*chem, *rt, 0, 3, -1.0, 0.0)                      # (a criterion no iteration meets: every one is carried out)
+    for bad in (0, 33):
+        with pytest.raises(RuntimeError, match="between 1 and 32"):
+            lib.evolve_enqueue(bad)
+    lib.evolve_enqueue(32)
+    lib.evolve_enqueue(32)
+    with pytest.raises(RuntimeError, match="poll first"):
+        lib.evolve_enqueue(1)
+    n, done, rows = lib.evolve_poll(0)
+    assert (n, done) == (64, False)
+    lib.evolve_enqueue(1)
+    n, done, rows = lib.evolve_poll(0)
+    assert (n, done) == (65, False)
+    # the sliced pass has no thermal form (the thermal fixtures of test_gpu_thermal.py: heating tables, default parameters)
+    lib.heat_table_to_device(thin, thick, thin.shape[0])
+    lib.thermal_params(True)
+    try:
+        with pytest.raises(RuntimeError, match="not available in thermal mode"):
+            lib.chemistry_range(*chem, 0, N, True)
+    finally:
+        lib.thermal_params(False)
+    p.device_close()
+
+
 def test_beyond_the_last_table_entry_rates_are_exactly_zero(asora):
     """A medium so thick that the optical depth passes the last table entry (10^maxlogtau) a dozen cells from the
     source -- the reference benchmark's own medium does (tau = 228 per cell at 256^3).  Both table lookups then
@@ -1291,7 +1348,7 @@ def test_device_resident_loop_equals_the_step_by_step_loop(asora, N, ns, R, monk
 
 def test_fused_pass_skips_only_lines_no_source_reaches(asora):
     """Round 4: the fused pass neither reads nor zeroes the 64-byte lines of the rate accumulators that no source of the step can
-    touch (State::reach_mask, built per (source upload, source range, R)).  A sequence of time steps ON ONE DEVICE STATE that
+    touch (State::reach, built per (source upload, source range, R)).  A sequence of time steps ON ONE DEVICE STATE that
     walks through every transition -- same sources again (mask and accumulators reused as they stand), another source range, another
     radius, a radius that covers the box (mask off), back to a small one, a new upload, sources at the corners (wrap) -- each
     step through the device-resident loop against raytrace_device + chemistry_device called separately from the same start:
