@@ -260,6 +260,25 @@ int asora_evolve_begin_slab(double dt, double bh00, double albpow, double colh0,
                             double R, double sig, double dr, double minlogtau, double dlogtau, int NumTau,
                             int src_begin, int src_count, double conv_criterion, double convergence_fraction,
                             int own_begin, int own_count);
+/* The same step in thermal mode (asora_thermal_params below).  Fails with code 4 without asora_thermal_params(1, ...), without
+ * heating tables on the device, or without the [k][j][i] twins.  Beginning through this entry is how a caller declares that it
+ * exchanges the heating rates together with the photo-ionisation rates; every call of the sequence then carries both fields:
+ *   asora_evolve_slab_trace       traces with heating, into the iteration's rate pair and heating pair
+ *   asora_evolve_slab_fold_out    also sums the heating traced onto the foreign planes into the heating out-box
+ *                                 (asora_evolve_slab_heat_outbox(): N^3 doubles, plane i at i*N*N, allocated by the first such
+ *                                 step) and zeroes the next iteration's heating accumulators there -- one launch for both fields
+ *   asora_evolve_slab_add_heat    heating received for OWN planes (_add_heat_host: from a host buffer), added in call order
+ *   asora_evolve_slab_pass        the thermal fused pass on the own planes: writes ASORA_GRID_TEMP_END there and adds to this
+ *                                 rank's asora_thermal_stats counters
+ *   asora_evolve_slab_fold_all    sums the heating of all planes into the heating out-box as well; the caller all-reduces BOTH
+ *                                 out-boxes, and the pass keeps the sums in ASORA_GRID_PHI_ION and ASORA_GRID_PHI_HEAT
+ *   asora_evolve_poll             folds the last iteration's heating into ASORA_GRID_PHI_HEAT (complete on the own planes)
+ * Temperatures do not travel between iterations: the trace reads nHI only, every rank holds the start-of-step TEMP, and TEMP_END
+ * is collected from the owners once, at the end of the step. */
+int asora_evolve_begin_slab_thermal(double dt, double bh00, double albpow, double colh0, double temph0, double abu_c,
+                                    double R, double sig, double dr, double minlogtau, double dlogtau, int NumTau,
+                                    int src_begin, int src_count, double conv_criterion, double convergence_fraction,
+                                    int own_begin, int own_count);
 int asora_evolve_slab_trace(int src_begin, int src_count);
 int asora_evolve_slab_fold_out(int i_begin, int i_count);
 /* The full-grid exchange of the reference (pyc2ray/evolve.py:433-437: MPI Allreduce of the rate grid, chemistry on identical data)
@@ -275,6 +294,12 @@ int asora_evolve_slab_outbox_to_host(int i_begin, int i_count, double *host);
 int asora_evolve_slab_outbox_from_host(int i_begin, int i_count, const double *host);
 int asora_evolve_slab_add(int i_begin, int i_count, const double *dev_planes);
 int asora_evolve_slab_add_host(int i_begin, int i_count, const double *host_planes);
+/* the heating rates of a step begun with asora_evolve_begin_slab_thermal: the twins of the five calls above */
+void *asora_evolve_slab_heat_outbox(void);
+int asora_evolve_slab_heat_outbox_to_host(int i_begin, int i_count, double *host);
+int asora_evolve_slab_heat_outbox_from_host(int i_begin, int i_count, const double *host);
+int asora_evolve_slab_add_heat(int i_begin, int i_count, const double *dev_planes);
+int asora_evolve_slab_add_heat_host(int i_begin, int i_count, const double *host_planes);
 int asora_evolve_slab_pass(void);
 int asora_evolve_slab_nhi(int i_begin, int i_count);
 int asora_evolve_slab_close(const double *host_sums);
@@ -297,7 +322,9 @@ int asora_planes_to_device(int which, int i_begin, int i_count, const double *ho
  *                     4 Compton exchange with the CMB (only while `compton` != 0)
  *   t_cmb             CMB temperature at the current redshift (K)
  * Fails with code 4 when no heating tables are on the device (asora_heat_table_to_device) or grey opacity is on.
- * enable = 0 returns to the isothermal form.  Single GPU: asora_evolve_begin_slab fails while thermal mode is on. */
+ * enable = 0 returns to the isothermal form.  Across ranks a thermal step is begun with asora_evolve_begin_slab_thermal;
+ * asora_evolve_begin_slab, the isothermal entry, fails while thermal mode is on (its caller exchanges no heating rates).
+ * asora_chemistry_range and the pipelined loop built on it stay isothermal. */
 int asora_thermal_params(int enable, double relative_denergy, double t_floor, int max_substeps, unsigned cooling_mask,
                          int compton, double t_cmb);
 /* Substep statistics of the thermal passes since the last asora_chemistry_device / asora_evolve_begin (summed over the

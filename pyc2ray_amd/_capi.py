@@ -71,6 +71,7 @@ SIGNATURES = {
     "asora_evolve_enqueue": (C.c_int, [C.c_int]),
     "asora_evolve_poll": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int), _dp, C.c_int, C.POINTER(C.c_int)]),
     "asora_evolve_begin_slab": (C.c_int, [C.c_double] * 11 + [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int]),
+    "asora_evolve_begin_slab_thermal": (C.c_int, [C.c_double] * 11 + [C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int]),
     "asora_evolve_slab_trace": (C.c_int, [C.c_int, C.c_int]),
     "asora_evolve_slab_fold_out": (C.c_int, [C.c_int, C.c_int]),
     "asora_evolve_slab_outbox": (C.c_void_p, []),
@@ -81,6 +82,11 @@ SIGNATURES = {
     "asora_debug_init_cost": (None, [_dp, _dp]),
     "asora_evolve_slab_add": (C.c_int, [C.c_int, C.c_int, C.c_void_p]),
     "asora_evolve_slab_add_host": (C.c_int, [C.c_int, C.c_int, _dp]),
+    "asora_evolve_slab_heat_outbox": (C.c_void_p, []),
+    "asora_evolve_slab_heat_outbox_to_host": (C.c_int, [C.c_int, C.c_int, _dp]),
+    "asora_evolve_slab_heat_outbox_from_host": (C.c_int, [C.c_int, C.c_int, _dp]),
+    "asora_evolve_slab_add_heat": (C.c_int, [C.c_int, C.c_int, C.c_void_p]),
+    "asora_evolve_slab_add_heat_host": (C.c_int, [C.c_int, C.c_int, _dp]),
     "asora_evolve_slab_pass": (C.c_int, []),
     "asora_evolve_slab_nhi": (C.c_int, [C.c_int, C.c_int]),
     "asora_evolve_slab_close": (C.c_int, [_dp]),

@@ -16,7 +16,8 @@ Differences from the reference:
   * ``device_resident`` (default True; single GPU): ``ndens``, ``temp``, ``xh`` and ``phi_ion`` stay on the MI355X
     between time steps and cross PCIe only when the host touches them; see :class:`C2Ray`.
   * ``Material: isothermal: false`` (optional key, default true) evolves the temperature from photo-heating and radiative
-    cooling (pyc2ray_amd/thermal.py); it needs ``compute_heating_rates: 1``, ``use_gpu`` and no ``use_mpi``.
+    cooling (pyc2ray_amd/thermal.py); it needs ``compute_heating_rates: 1`` and ``use_gpu``, and across ranks
+    ``use_mpi = pyc2ray_amd.dist.MPI`` (the heating rates are exchanged on the TorchComm's device loops only).
   * ``Material: clumping: C`` (optional key, default 1) and the attribute ``clumping`` (a float, or an (N, N, N) grid assigned
     between steps) set the sub-grid clumping factor of the recombination rate (evolve3D's ``clumping=``).
 """
@@ -235,7 +236,8 @@ class C2Ray:
 
     def _thermal_mode_init(self, use_gpu, use_mpi):
         """The optional key ``Material: isothermal`` (absent: true, the reference's behaviour).  A non-isothermal run evolves
-        the temperature from the photo-heating rates, which only the single-GPU path computes."""
+        the temperature from the photo-heating rates: on one GPU, or across ranks with pyc2ray_amd.dist.MPI, whose communicator
+        exchanges the heating rates with the photo-ionisation rates; with any other MPI module it is single-GPU only."""
         self.isothermal = bool(self._ld.get('Material', {}).get('isothermal', True))
         if self.isothermal:
             return
@@ -243,8 +245,10 @@ class C2Ray:
             raise ValueError("Material: isothermal: false needs the photo-heating rates (Photo: compute_heating_rates: 1)")
         if not use_gpu:
             raise ValueError("Material: isothermal: false needs use_gpu=True (the use_gpu=False raytracer has no thermal form)")
-        if use_mpi:
-            raise ValueError("Material: isothermal: false is single-GPU only (no use_mpi)")
+        from . import dist
+        if use_mpi and use_mpi is not dist.MPI:
+            raise ValueError("Material: isothermal: false is single-GPU only with this use_mpi (across ranks: "
+                             "use_mpi = pyc2ray_amd.dist.MPI)")
 
     def _thermal_params(self):
         """The ThermalParams of the current step (None when isothermal); Compton exchange with the CMB at self.zred in
@@ -292,9 +296,9 @@ class C2Ray:
                 self.R_max_LLS, self.convergence_fraction, self.sig, self.bh00, self.albpow, self.colh0, self.temph0, self.abu_c,
                 self.logfile)
         thermal = self._thermal_params()
-        # (the thermal mode is single-GPU only: a run that evolves the temperature takes the one-process form)
-        if thermal is None and self.mpi and src_flux.shape[0] >= self.nprocs:
-            result = evolve3D_MPI(*head, self.mpi, self.comm, self.rank, self.nprocs, *tail, clumping=self.__dict__["_clumping"])
+        if self.mpi and src_flux.shape[0] >= self.nprocs:
+            result = evolve3D_MPI(*head, self.mpi, self.comm, self.rank, self.nprocs, *tail, thermal=thermal,
+                                  clumping=self.__dict__["_clumping"])
         else:
             result = evolve3D(*head, *tail, thermal=thermal, clumping=self.__dict__["_clumping"])
         self.xh, self.phi_ion = result[:2]

@@ -93,7 +93,7 @@ static int release_all()
     auto drop = [](auto *&ptr) { if (ptr) { (void)hipFree(ptr); ptr = nullptr; } };
     // (the grids of the hot loop are parts of the arena; the heating grid is an allocation of its own)
     drop(st.grid[ASORA_GRID_PHI_HEAT]);
-    drop(st.grid[ASORA_GRID_TEMP_END]); drop(st.heat_acc); drop(st.th_stats_dev);
+    drop(st.grid[ASORA_GRID_TEMP_END]); drop(st.heat_acc); drop(st.heat_outbox); drop(st.th_stats_dev);
     st.heat_clean[0] = st.heat_clean[1] = false;
     st.th_on = false; st.th = ThermalConsts();
     drop(st.grid[ASORA_GRID_CLUMP]);

@@ -264,6 +264,7 @@ struct State {
     bool ev_slab_passed = false;            // the current iteration's pass has been enqueued (close comes next)
     bool ev_folded_all = false;             // ... and this iteration's has been enqueued
     bool ev_rates_in_outbox = false;        // asora_evolve_slab_fold_all: the passes of this step read the out-box and keep PHI_ION
+    bool ev_slab_thermal = false;           // begun with asora_evolve_begin_slab_thermal: every slab call carries the heating rates too
     // Which 64-byte lines of the rate accumulators the sources of the current step can touch at all (round 4): one byte per
     // line of 8 cells, [i][j][k >> 3] for the plain layout and, behind it, [k][j][i >> 3] for the transposed one.  The fused
     // pass neither reads nor zeroes the lines no source reaches (they are zero and stay zero): 32 of its 88 bytes per cell.
@@ -289,6 +290,8 @@ struct State {
     ThermalConsts th;
     double *heat_acc = nullptr;             // two pairs like `acc`, [i][j][k] then [k][j][i] each (4 N^3 doubles)
     bool heat_clean[2] = {false, false};    // pair known to be all zero
+    double *heat_outbox = nullptr;          // thermal step across ranks: the heating planes to send / the summed heating (N^3 doubles,
+                                            // the twin of `staging`'s role as rate out-box; allocated by the first such step)
     unsigned long long *th_stats_dev = nullptr;   // [3]: cells at max_substeps, cells floored, most substeps
 
     // sub-grid clumping of the recombination rate (asora_clumping): 0 off, 1 one constant, 2 per cell (ASORA_GRID_CLUMP, allocated
@@ -457,7 +460,7 @@ struct ChemTileParams {
     // the grid has one temperature (launch_temp_probe): its factors, evaluated on the device, travel with the parameters
     int uniform = 0, uniform_t_ok = 0;
     double uniform_T = 0, uniform_brech0 = 0, uniform_acolh0 = 0;
-    // thermal form (fold + emit only): the heating accumulators are folded like the rates, the other heating pair zeroed
+    // thermal form (emit only): the heating accumulators are folded like the rates, the other heating pair zeroed
     bool thermal = false;
     double *heat = nullptr, *heat_t = nullptr;
     double *zero_ha = nullptr, *zero_ht = nullptr;
@@ -467,6 +470,9 @@ struct ChemTileParams {
     // clumping: set by launch_chemistry_tiles from State::clump_mode, as ChemParams::clump / clump_c
     const double *clump = nullptr;
     double clump_c = 1.0;
+    // thermal form without fold (heating already summed over both layouts and over the ranks: the all-reduce loop): where the pass
+    // keeps it, as phi_out keeps the rates (appended, so the fields above keep their offsets)
+    double *heat_out = nullptr;
 };
 int launch_grid_sum(State &st, const double *a, size_t n, double *out_dev);
 int launch_scale(State &st, double *a, size_t n, double factor);
@@ -479,6 +485,9 @@ int launch_prepare_range(State &st, int i_begin, int i_count, bool zero_acc, dou
 // multi-GPU device loop: foreign planes folded into the out-box (+ the other accumulator pair zeroed there); received planes added
 int launch_fold_out(State &st, const double *a, const double *a_t, double *out, double *z_a, double *z_t, int i_begin, int i_count,
                     const int *done);
+// the same for the rates and the heating rates of a thermal step in ONE launch (h, h_t -> hout; zh_a, zh_t zeroed)
+int launch_fold_out_pair(State &st, const double *a, const double *a_t, double *out, double *z_a, double *z_t, const double *h,
+                         const double *h_t, double *hout, double *zh_a, double *zh_t, int i_begin, int i_count, const int *done);
 int launch_add_planes(State &st, double *dst, const double *src, size_t n, const int *done);
 // the convergence test of evolve.py:216-236 on sums[3] = {sum x, sum 1-x, conv_flag} (summed over the ranks beforehand)
 int launch_convergence_test(State &st, const double *sums, EvolveStatus *status);

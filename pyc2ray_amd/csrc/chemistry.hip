@@ -382,18 +382,19 @@ __global__ void __launch_bounds__(RED_THREADS) chemistry_reduce_kernel(const dou
 // state of a box (0.248 -> 0.229 ms, 0.306 -> 0.281 ms; profiles/r05_ab_chem_ntloads.txt).
 __device__ __forceinline__ double stream_load(const double *q) { return __builtin_nontemporal_load(q); }
 
-// THERMAL (with FOLD and EMIT, not UNIFORM_T): chemistry_cell_thermal; the heating accumulators are folded like the rates
+// THERMAL (with EMIT, not UNIFORM_T): chemistry_cell_thermal; the heating accumulators are folded like the rates
 // (tile_h: their [k][j][i] twin), the other heating pair is zeroed for the next trace, the end temperature goes to temp_end.
-// Per cell 8 loads and 9 stores = 136 B.
+// Per cell 8 loads and 9 stores = 136 B.  Without FOLD (the all-reduce loop across ranks: rates and heating arrive summed over both
+// layouts and over the ranks) one layout of each is read, and both sums are kept (phi_out, heat_out): 7 loads, 9 stores = 128 B.
 // CLUMP (every form; launch_chemistry_tiles): clumped recombination, the factor of the cell streamed from p.clump like the other
 // grids (+8 B per cell) -- or, in the thermal form with p.clump == nullptr, the one factor p.clump_c
 template <bool FOLD, bool EMIT, bool UNIFORM_T, bool THERMAL = false, bool CLUMP = false>
 __global__ void __launch_bounds__(CH_THREADS, 1) chemistry_tile_kernel(const ChemTileParams p)
 {
-    static_assert(!THERMAL || (FOLD && EMIT && !UNIFORM_T), "thermal pass: the device loop's fold + emit form only");
+    static_assert(!THERMAL || (EMIT && !UNIFORM_T), "thermal pass: the device loop's emit forms only (with or without fold), never UNIFORM_T");
     if (p.status && p.status->done) return;
     __shared__ double tile_g[32][33], tile_n[32][33];
-    __shared__ double tile_h[THERMAL ? 32 : 1][33];
+    __shared__ double tile_h[(THERMAL && FOLD) ? 32 : 1][33];
     __shared__ double r1[CH_THREADS], r0[CH_THREADS];
     __shared__ unsigned int rc[CH_THREADS];
 
@@ -447,7 +448,8 @@ __global__ void __launch_bounds__(CH_THREADS, 1) chemistry_tile_kernel(const Che
                 if (CLUMP) c = (THERMAL && !p.clump) ? p.clump_c : stream_load(p.clump + idx);
                 if (THERMAL) {
                     double hr = reached ? stream_load(p.heat + idx) : 0.0;
-                    hr += tile_h[tx][r];
+                    if (FOLD) hr += tile_h[tx][r];
+                    else p.heat_out[idx] = hr;                // (the summed heating, kept like the summed rates: all-reduce loop)
                     if (reached) p.zero_ha[idx] = 0.0;
                     double te;
                     chemistry_cell_thermal<CLUMP>(cp, n, stream_load(p.xh + idx), g, hr, stream_load(p.temp + idx), xav, xint, te, nconv,
@@ -680,8 +682,10 @@ static int launch_tile_form(const ChemTileParams &q, dim3 grid, hipStream_t stre
 {
     const bool u = q.uniform != 0;
     if (q.thermal) {
-        if (!(q.fold && q.emit)) return fail(11, "chemistry: the thermal pass exists in the fold + emit form only (internal error)");
-        hipLaunchKernelGGL((chemistry_tile_kernel<true, true, false, true, CLUMP>), grid, dim3(CH_THREADS), 0, stream, q);
+        if (!q.emit) return fail(11, "chemistry: the thermal pass exists in the emit forms only (internal error)");
+        if (!q.fold && !q.heat_out) return fail(11, "chemistry: the thermal pass without fold keeps the summed heating (internal error)");
+        if (q.fold) hipLaunchKernelGGL((chemistry_tile_kernel<true, true, false, true, CLUMP>), grid, dim3(CH_THREADS), 0, stream, q);
+        else        hipLaunchKernelGGL((chemistry_tile_kernel<false, true, false, true, CLUMP>), grid, dim3(CH_THREADS), 0, stream, q);
     } else if (q.fold && q.emit) {
         if (u) hipLaunchKernelGGL((chemistry_tile_kernel<true, true, true, false, CLUMP>), grid, dim3(CH_THREADS), 0, stream, q);
         else   hipLaunchKernelGGL((chemistry_tile_kernel<true, true, false, false, CLUMP>), grid, dim3(CH_THREADS), 0, stream, q);

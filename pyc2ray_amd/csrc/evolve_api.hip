@@ -20,6 +20,16 @@ static int ensure_heat_acc()
     return 0;
 }
 
+// The heating out-box of a thermal step across ranks (asora_evolve_begin_slab_thermal): N^3 doubles like the rate out-box
+// (State::staging), allocated with the first such step
+static int ensure_heat_outbox()
+{
+    State &st = state();
+    if (st.heat_outbox) return 0;
+    ASORA_HIP_TRY(hipMalloc(&st.heat_outbox, st.ncell * sizeof(double)));
+    return 0;
+}
+
 // Make both pairs all zero, without storing where that is known already.  The rate pairs are zeroed in one piece (raytracing.cu:113)
 // and count as dirty when iterations were enqueued and never polled: which pair holds what is then not known.  heating: the
 // heating pairs instead, pair by pair (after a poll one of them is clean).
@@ -101,6 +111,17 @@ static ChemTileParams evolve_pass_params(int i_begin, int i_count, int set)
     return c;
 }
 
+// The thermal block of such a pass (one GPU, and the sharded step begun with asora_evolve_begin_slab_thermal): the heating pair of
+// `set` is folded like the rates, the other heating pair zeroed, the end-of-step temperature and the substep counters written
+static void evolve_pass_thermal(ChemTileParams &c, int set)
+{
+    State &st = state();
+    c.thermal = true; c.uniform = 0; c.th = st.th;
+    c.heat = heat_pair(set); c.heat_t = c.heat + st.ncell;
+    c.zero_ha = heat_pair(set ^ 1); c.zero_ht = c.zero_ha + st.ncell;
+    c.temp_end = st.grid[ASORA_GRID_TEMP_END]; c.th_stats = st.th_stats_dev;
+}
+
 } // namespace asora
 
 using namespace asora;
@@ -114,15 +135,20 @@ extern "C" {
 static int evolve_begin_impl(double dt, double bh00, double albpow, double colh0, double temph0, double abu_c,
                              double R, double sig, double dr, double minlogtau, double dlogtau, int NumTau,
                              int src_begin, int src_count, double conv_criterion, double convergence_fraction,
-                             bool slab, int own_begin, int own_count)
+                             bool slab, int own_begin, int own_count, bool slab_thermal = false)
 {
     clear_error();
     if (int rc = require_init("evolve_begin")) return rc;
     State &st = state();
     st.ev_open = false;
     // 1. what the step needs
-    if (slab && st.th_on)
-        return fail(4, "evolve_begin_slab: thermal mode is single-GPU only (asora_thermal_params(0, ...) first)");
+    if (slab && st.th_on && !slab_thermal)
+        return fail(4, "evolve_begin_slab: thermal mode is on, and this entry begins an isothermal step (single-GPU thermal loop: "
+                       "asora_evolve_begin; across ranks, with the heating rates exchanged as well: asora_evolve_begin_slab_thermal)");
+    if (slab_thermal && (!st.have_heat_tables || st.opt[ASORA_OPT_GREY_NOTABLES]))
+        return fail(4, "evolve_begin_slab_thermal: needs heating tables on the device (heat_table_to_device)");
+    if (slab_thermal && !st.th_on)
+        return fail(4, "evolve_begin_slab_thermal: needs the thermal mode (asora_thermal_params(1, ...) first)");
     if (slab) {
         if (int rc = check_planes("evolve_begin_slab", 4, "bad range of own planes", own_begin, own_count)) return rc;
         if (!st.opt[ASORA_OPT_Z_TRANSPOSED]) return fail(4, "evolve_begin_slab: needs the [k][j][i] twins (ASORA_OPT_Z_TRANSPOSED = 1)");
@@ -138,6 +164,7 @@ static int evolve_begin_impl(double dt, double bh00, double albpow, double colh0
         if (int rc = ensure_optional_grid(ASORA_GRID_PHI_HEAT)) return rc;
         if (int rc = ensure_optional_grid(ASORA_GRID_TEMP_END)) return rc;
         if (int rc = ensure_heat_acc()) return rc;
+        if (slab) { if (int rc = ensure_heat_outbox()) return rc; }
     }
     if (int rc = ensure_temp_probe(bh00, albpow, colh0, temph0)) return rc;
 
@@ -189,6 +216,7 @@ static int evolve_begin_impl(double dt, double bh00, double albpow, double colh0
     st.ev_reported = 0;
     st.ev_enqueued = 0;
     st.ev_slab = slab; st.ev_own_begin = own_begin; st.ev_own_count = own_count; st.ev_slab_passed = false;
+    st.ev_slab_thermal = slab && st.th_on;
     st.ev_rates_in_outbox = false; st.ev_folded_all = false;
     st.ev_open = true;
     return 0;
@@ -223,6 +251,19 @@ int asora_evolve_begin_slab(double dt, double bh00, double albpow, double colh0,
                              conv_criterion, convergence_fraction, true, own_begin, own_count);
 }
 
+// The same step in thermal mode (asora_thermal_params(1, ...), heating tables, the [k][j][i] twins: code 4 without).  Beginning
+// through this entry is how a caller declares that it exchanges the heating rates with the photo-ionisation rates: every slab call
+// then carries both fields (trace, fold_out, fold_all, pass, poll), and what arrives from other ranks is added with
+// asora_evolve_slab_add (rates) AND asora_evolve_slab_add_heat (heating), from asora_evolve_slab_heat_outbox() on the sender's side.
+int asora_evolve_begin_slab_thermal(double dt, double bh00, double albpow, double colh0, double temph0, double abu_c,
+                                    double R, double sig, double dr, double minlogtau, double dlogtau, int NumTau,
+                                    int src_begin, int src_count, double conv_criterion, double convergence_fraction,
+                                    int own_begin, int own_count)
+{
+    return evolve_begin_impl(dt, bh00, albpow, colh0, temph0, abu_c, R, sig, dr, minlogtau, dlogtau, NumTau, src_begin, src_count,
+                             conv_criterion, convergence_fraction, true, own_begin, own_count, true);
+}
+
 static int require_slab(const char *who)
 {
     if (int rc = require_init(who)) return rc;
@@ -234,6 +275,14 @@ static int require_slab(const char *who)
 }
 static int slab_set() { return (state().ev_base + state().ev_enqueued) & 1; }     // the pair the current iteration traces into
 static double *slab_pair(int which) { return acc_pair(slab_set() ^ which); }     // 0: that pair, 1: the other one
+static double *slab_heat_pair(int which) { return heat_pair(slab_set() ^ which); }
+static int require_slab_thermal(const char *who)
+{
+    if (int rc = require_slab(who)) return rc;
+    if (!state().ev_slab_thermal)
+        return fail(4, std::string(who) + ": the step carries no heating rates (begin it with asora_evolve_begin_slab_thermal)");
+    return 0;
+}
 
 int asora_evolve_slab_trace(int src_begin, int src_count)
 {
@@ -249,7 +298,11 @@ int asora_evolve_slab_trace(int src_begin, int src_count)
     p.phi = slab_pair(0);
     p.src_begin = src_begin; p.src_count = src_count;          // (shape_src_count stays the rank's whole share: one launch shape)
     if (!(src_begin == 0 && src_count == st.num_src)) { p.src_pos = st.src_pos; p.src_flux = st.src_flux; }
-    return launch_raytrace(st, p, false, false);
+    if (st.ev_slab_thermal) {                 // the HEAT forms, into the iteration's heating pair
+        p.heat = slab_heat_pair(0);
+        st.heat_clean[0] = st.heat_clean[1] = false;
+    }
+    return launch_raytrace(st, p, false, st.ev_slab_thermal);
 }
 
 int asora_evolve_slab_fold_out(int i_begin, int i_count)
@@ -262,6 +315,11 @@ int asora_evolve_slab_fold_out(int i_begin, int i_count)
         return fail(4, "evolve_slab_fold_out: the range holds planes this rank owns (their rates stay: the pass folds them)");
     st.ev_sets_known = false;
     double *cur = slab_pair(0), *nxt = slab_pair(1);
+    if (st.ev_slab_thermal) {                 // both fields in one launch
+        double *hcur = slab_heat_pair(0), *hnxt = slab_heat_pair(1);
+        return launch_fold_out_pair(st, cur, cur + st.ncell, st.staging, nxt, nxt + st.ncell, hcur, hcur + st.ncell, st.heat_outbox,
+                                    hnxt, hnxt + st.ncell, i_begin, i_count, &st.ev_status->done);
+    }
     return launch_fold_out(st, cur, cur + st.ncell, st.staging, nxt, nxt + st.ncell, i_begin, i_count, &st.ev_status->done);
 }
 
@@ -281,64 +339,104 @@ int asora_evolve_slab_fold_all(void)
     st.ev_rates_in_outbox = true; st.ev_folded_all = true;
     double *cur = slab_pair(0), *nxt = slab_pair(1);
     // (the pass zeroes the other pair's [i][j][k] layout as it goes; the transposed layout is zeroed here)
+    if (st.ev_slab_thermal) {
+        double *hcur = slab_heat_pair(0), *hnxt = slab_heat_pair(1);
+        return launch_fold_out_pair(st, cur, cur + st.ncell, st.staging, nullptr, nxt + st.ncell, hcur, hcur + st.ncell, st.heat_outbox,
+                                    nullptr, hnxt + st.ncell, 0, st.N, &st.ev_status->done);
+    }
     return launch_fold_out(st, cur, cur + st.ncell, st.staging, nullptr, nxt + st.ncell, 0, st.N, &st.ev_status->done);
 }
 
 void *asora_evolve_slab_outbox(void) { return state().init ? (void *)state().staging : nullptr; }
+// (nullptr until a thermal step across ranks has been begun: the heating out-box is allocated then)
+void *asora_evolve_slab_heat_outbox(void) { return state().init ? (void *)state().heat_outbox : nullptr; }
+
+// planes [i_begin, i_begin + i_count) of an out-box (`box`: the rate out-box, or the heating out-box) from / to the host
+static int outbox_copy(const char *who, double *box, int i_begin, int i_count, double *host, bool to_host)
+{
+    clear_error();
+    if (int rc = require_init(who)) return rc;
+    State &st = state();
+    if (i_begin < 0 || i_count < 0 || i_begin + i_count > st.N || (i_count > 0 && !host)) return fail(3, std::string(who) + ": bad arguments");
+    if (i_count == 0) return 0;
+    if (!box) return fail(4, std::string(who) + ": no heating out-box (begin a step with asora_evolve_begin_slab_thermal)");
+    const size_t plane = (size_t)st.N * st.N;
+    double *dev = box + (size_t)i_begin * plane;
+    if (to_host) ASORA_HIP_TRY(hipMemcpyAsync(host, dev, (size_t)i_count * plane * sizeof(double), hipMemcpyDeviceToHost, st.stream));
+    else         ASORA_HIP_TRY(hipMemcpyAsync(dev, host, (size_t)i_count * plane * sizeof(double), hipMemcpyHostToDevice, st.stream));
+    ASORA_HIP_TRY(hipStreamSynchronize(st.stream));              // (the host buffer may be pageable)
+    return 0;
+}
 
 int asora_evolve_slab_outbox_from_host(int i_begin, int i_count, const double *host)
 {
-    clear_error();
-    if (int rc = require_init("evolve_slab_outbox_from_host")) return rc;
-    State &st = state();
-    if (i_begin < 0 || i_count < 0 || i_begin + i_count > st.N || (i_count > 0 && !host)) return fail(3, "evolve_slab_outbox_from_host: bad arguments");
-    if (i_count == 0) return 0;
-    const size_t plane = (size_t)st.N * st.N;
-    ASORA_HIP_TRY(hipMemcpyAsync(st.staging + (size_t)i_begin * plane, host, (size_t)i_count * plane * sizeof(double), hipMemcpyHostToDevice, st.stream));
-    ASORA_HIP_TRY(hipStreamSynchronize(st.stream));              // (the host buffer may be pageable)
-    return 0;
+    return outbox_copy("evolve_slab_outbox_from_host", state().staging, i_begin, i_count, const_cast<double *>(host), false);
 }
 
 int asora_evolve_slab_outbox_to_host(int i_begin, int i_count, double *host)
 {
+    return outbox_copy("evolve_slab_outbox_to_host", state().staging, i_begin, i_count, host, true);
+}
+
+int asora_evolve_slab_heat_outbox_from_host(int i_begin, int i_count, const double *host)
+{
+    return outbox_copy("evolve_slab_heat_outbox_from_host", state().heat_outbox, i_begin, i_count, const_cast<double *>(host), false);
+}
+
+int asora_evolve_slab_heat_outbox_to_host(int i_begin, int i_count, double *host)
+{
+    return outbox_copy("evolve_slab_heat_outbox_to_host", state().heat_outbox, i_begin, i_count, host, true);
+}
+
+// planes received from another rank added on the own planes of the iteration's pair: heating = false the rates, true the heating
+static int slab_add(const char *who, bool heating, int i_begin, int i_count, const double *dev_planes)
+{
     clear_error();
-    if (int rc = require_init("evolve_slab_outbox_to_host")) return rc;
+    if (int rc = heating ? require_slab_thermal(who) : require_slab(who)) return rc;
     State &st = state();
-    if (i_begin < 0 || i_count < 0 || i_begin + i_count > st.N || (i_count > 0 && !host)) return fail(3, "evolve_slab_outbox_to_host: bad arguments");
-    if (i_count == 0) return 0;
+    if (i_begin < 0 || i_count < 0 || i_begin + i_count > st.N || (i_count > 0 && !dev_planes)) return fail(4, std::string(who) + ": bad arguments");
+    if (st.ev_slab_passed) return fail(4, std::string(who) + ": the iteration's pass has been enqueued already");
+    if (i_count > 0 && (i_begin < st.ev_own_begin || i_begin + i_count > st.ev_own_begin + st.ev_own_count))
+        return fail(4, std::string(who) + ": rates received for planes this rank does not own");
+    st.ev_sets_known = false;
     const size_t plane = (size_t)st.N * st.N;
-    ASORA_HIP_TRY(hipMemcpyAsync(host, st.staging + (size_t)i_begin * plane, (size_t)i_count * plane * sizeof(double), hipMemcpyDeviceToHost, st.stream));
-    ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
-    return 0;
+    double *pair = heating ? slab_heat_pair(0) : slab_pair(0);
+    return launch_add_planes(st, pair + (size_t)i_begin * plane, dev_planes, (size_t)i_count * plane, &st.ev_status->done);
+}
+
+static int slab_add_host(const char *who, bool heating, int i_begin, int i_count, const double *host_planes)
+{
+    clear_error();
+    if (int rc = heating ? require_slab_thermal(who) : require_slab(who)) return rc;
+    State &st = state();
+    if (i_begin < 0 || i_count < 0 || i_begin + i_count > st.N || (i_count > 0 && !host_planes)) return fail(4, std::string(who) + ": bad arguments");
+    if (i_count == 0) return 0;
+    // through the out-box: what is added belongs to planes this rank owns, what the out-box holds to planes it does not
+    const size_t plane = (size_t)st.N * st.N;
+    double *tmp = (heating ? st.heat_outbox : st.staging) + (size_t)i_begin * plane;
+    ASORA_HIP_TRY(hipMemcpyAsync(tmp, host_planes, (size_t)i_count * plane * sizeof(double), hipMemcpyHostToDevice, st.stream));
+    ASORA_HIP_TRY(hipStreamSynchronize(st.stream));              // (the host buffer may be pageable)
+    return slab_add(who, heating, i_begin, i_count, tmp);
 }
 
 int asora_evolve_slab_add(int i_begin, int i_count, const double *dev_planes)
 {
-    clear_error();
-    if (int rc = require_slab("evolve_slab_add")) return rc;
-    State &st = state();
-    if (i_begin < 0 || i_count < 0 || i_begin + i_count > st.N || (i_count > 0 && !dev_planes)) return fail(4, "evolve_slab_add: bad arguments");
-    if (st.ev_slab_passed) return fail(4, "evolve_slab_add: the iteration's pass has been enqueued already");
-    if (i_count > 0 && (i_begin < st.ev_own_begin || i_begin + i_count > st.ev_own_begin + st.ev_own_count))
-        return fail(4, "evolve_slab_add: rates received for planes this rank does not own");
-    st.ev_sets_known = false;
-    const size_t plane = (size_t)st.N * st.N;
-    return launch_add_planes(st, slab_pair(0) + (size_t)i_begin * plane, dev_planes, (size_t)i_count * plane, &st.ev_status->done);
+    return slab_add("evolve_slab_add", false, i_begin, i_count, dev_planes);
 }
 
 int asora_evolve_slab_add_host(int i_begin, int i_count, const double *host_planes)
 {
-    clear_error();
-    if (int rc = require_slab("evolve_slab_add_host")) return rc;
-    State &st = state();
-    if (i_begin < 0 || i_count < 0 || i_begin + i_count > st.N || (i_count > 0 && !host_planes)) return fail(4, "evolve_slab_add_host: bad arguments");
-    if (i_count == 0) return 0;
-    // through the out-box: what is added belongs to planes this rank owns, what the out-box holds to planes it does not
-    const size_t plane = (size_t)st.N * st.N;
-    double *tmp = st.staging + (size_t)i_begin * plane;
-    ASORA_HIP_TRY(hipMemcpyAsync(tmp, host_planes, (size_t)i_count * plane * sizeof(double), hipMemcpyHostToDevice, st.stream));
-    ASORA_HIP_TRY(hipStreamSynchronize(st.stream));              // (the host buffer may be pageable)
-    return asora_evolve_slab_add(i_begin, i_count, tmp);
+    return slab_add_host("evolve_slab_add_host", false, i_begin, i_count, host_planes);
+}
+
+int asora_evolve_slab_add_heat(int i_begin, int i_count, const double *dev_planes)
+{
+    return slab_add("evolve_slab_add_heat", true, i_begin, i_count, dev_planes);
+}
+
+int asora_evolve_slab_add_heat_host(int i_begin, int i_count, const double *host_planes)
+{
+    return slab_add_host("evolve_slab_add_heat_host", true, i_begin, i_count, host_planes);
 }
 
 int asora_evolve_slab_pass(void)
@@ -353,6 +451,11 @@ int asora_evolve_slab_pass(void)
     st.ev_slab_passed = true;
     st.grid_valid[ASORA_GRID_XH_AV] = st.grid_valid[ASORA_GRID_XH_INTERMED] = true;
     st.grid_valid[ASORA_GRID_PHI_ION] = false;
+    if (st.ev_slab_thermal) {
+        st.heat_clean[0] = st.heat_clean[1] = false;     // until the poll tells which pair the last iteration used
+        st.grid_valid[ASORA_GRID_TEMP_END] = true;
+        st.grid_valid[ASORA_GRID_PHI_HEAT] = false;
+    }
     if (st.ev_own_count == 0) {           // nothing to own (more ranks than planes): this rank's share of the sums is zero
         ASORA_HIP_TRY(hipMemsetAsync(st.red_final, 0, sizeof(double) * 3, st.stream));
         return 0;
@@ -360,7 +463,12 @@ int asora_evolve_slab_pass(void)
     if (int rc = ensure_red_capacity(3 * chemistry_tile_blocks(st, st.N, st.ev_own_count))) return rc;    // (sized for every range at init)
     ChemTileParams c = evolve_pass_params(st.ev_own_begin, st.ev_own_count, slab_set());
     c.local_sums = true;
-    if (st.ev_rates_in_outbox) { c.gamma = st.staging; c.gamma_t = nullptr; c.phi_out = st.grid[ASORA_GRID_PHI_ION]; c.fold = false; }
+    if (st.ev_slab_thermal) evolve_pass_thermal(c, slab_set());
+    if (st.ev_rates_in_outbox) {
+        c.gamma = st.staging; c.gamma_t = nullptr; c.phi_out = st.grid[ASORA_GRID_PHI_ION]; c.fold = false;
+        // (thermal: the summed heating likewise from its out-box, kept in PHI_HEAT)
+        if (st.ev_slab_thermal) { c.heat = st.heat_outbox; c.heat_t = nullptr; c.heat_out = st.grid[ASORA_GRID_PHI_HEAT]; }
+    }
     return launch_chemistry_tiles(st, c, st.stream);
 }
 
@@ -416,12 +524,7 @@ int asora_evolve_enqueue(int iterations)
         }
         ChemTileParams c = evolve_pass_params(0, st.N, set);
         if (st.reach.in_use) { c.reach_a = st.reach.mask; c.reach_t = st.reach.mask + st.reach.bytes; }
-        if (st.th_on) {
-            c.thermal = true; c.uniform = 0; c.th = st.th;
-            c.heat = heat_pair(set); c.heat_t = c.heat + st.ncell;
-            c.zero_ha = heat_pair(set ^ 1); c.zero_ht = c.zero_ha + st.ncell;
-            c.temp_end = st.grid[ASORA_GRID_TEMP_END]; c.th_stats = st.th_stats_dev;
-        }
+        if (st.th_on) evolve_pass_thermal(c, set);
         if (int rc = launch_chemistry_tiles(st, c, st.stream)) return rc;
         st.ev_first = false;
     }
@@ -445,15 +548,16 @@ int asora_evolve_poll(int *niter, int *converged, double *history, int history_r
     ASORA_HIP_TRY(hipMemcpyAsync(st.ev_host, st.ev_status, sizeof(EvolveStatus), hipMemcpyDeviceToHost, st.stream));
     ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
     const EvolveStatus &h = *st.ev_host;
+    const bool thermal = st.ev_slab ? st.ev_slab_thermal : st.th_on;
     // The rates of the last iteration carried out sit, unfolded, in its accumulator pair; the other pair is zero (the pass
     // of that iteration zeroed it; iterations enqueued beyond convergence did nothing).  Fold them into PHI_ION now.
     if (h.niter > 0) {
         const int set = (st.ev_base + h.niter - 1) & 1;
-        if (st.ev_slab && st.ev_rates_in_outbox) st.ev_folded_iter = h.niter;      // (the pass has kept the summed rates in PHI_ION)
+        if (st.ev_slab && st.ev_rates_in_outbox) st.ev_folded_iter = h.niter;      // (the pass has kept the summed rates in PHI_ION, and the heating in PHI_HEAT)
         if (st.ev_folded_iter != h.niter) {
             const double *a = acc_pair(set);
             if (int rc = launch_fold_sum(st, a, a + st.ncell, st.grid[ASORA_GRID_PHI_ION])) return rc;
-            if (st.th_on && !st.ev_slab) {       // thermal mode: the last iteration's heating as well
+            if (thermal) {       // thermal mode: the last iteration's heating as well (a sharded step: complete on the own planes)
                 const double *hsum = heat_pair(set);
                 if (int rc = launch_fold_sum(st, hsum, hsum + st.ncell, st.grid[ASORA_GRID_PHI_HEAT])) return rc;
             }
@@ -461,7 +565,7 @@ int asora_evolve_poll(int *niter, int *converged, double *history, int history_r
         }
         st.grid_valid[ASORA_GRID_PHI_ION] = true;
         st.ev_clean[set] = false; st.ev_clean[set ^ 1] = true;
-        if (st.th_on && !st.ev_slab) {
+        if (thermal) {
             st.grid_valid[ASORA_GRID_PHI_HEAT] = true;
             st.heat_clean[set] = false; st.heat_clean[set ^ 1] = true;
         }

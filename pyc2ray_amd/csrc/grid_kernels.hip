@@ -188,6 +188,53 @@ int launch_fold_out(State &st, const double *a, const double *a_t, double *out, 
     return 0;
 }
 
+// A thermal step (asora_evolve_begin_slab_thermal): the same sweep for the photo-ionisation rates AND the heating rates in one
+// launch -- hout[i][j][k] = h[i][j][k] + h_t[k][j][i], the other heating pair zeroed on those planes.  The kernel moves twice the
+// bytes of fold_out_kernel and is bandwidth-bound like it; what one launch saves is the host's second
+// enqueue per run of planes.
+__global__ void __launch_bounds__(256) fold_out_pair_kernel(const double *__restrict__ a, const double *__restrict__ a_t, double *__restrict__ out,
+                                                            double *__restrict__ z_a, double *__restrict__ z_t,
+                                                            const double *__restrict__ h, const double *__restrict__ h_t, double *__restrict__ hout,
+                                                            double *__restrict__ zh_a, double *__restrict__ zh_t, int N, int i_begin, int i_end,
+                                                            const int *__restrict__ done)
+{
+    if (done && *done) return;
+    __shared__ double tile[32][33], tile_h[32][33];
+    const int j = blockIdx.y;
+    const int kb = blockIdx.z * 32, ib = i_begin + blockIdx.x * 32;       // a_t / h_t tiles: rows k, columns i
+    for (int r = threadIdx.y; r < 32; r += 8) {
+        const int k = kb + r, i = ib + threadIdx.x;
+        if (k < N && i < i_end) {
+            const size_t o = ((size_t)k * N + j) * N + i;
+            tile[r][threadIdx.x] = a_t[o]; tile_h[r][threadIdx.x] = h_t[o];
+            if (z_t) z_t[o] = 0.0;
+            if (zh_t) zh_t[o] = 0.0;
+        }
+    }
+    __syncthreads();
+    for (int r = threadIdx.y; r < 32; r += 8) {
+        const int i = ib + r, k = kb + threadIdx.x;
+        if (i < i_end && k < N) {
+            const size_t o = ((size_t)i * N + j) * N + k;
+            out[o] = a[o] + tile[threadIdx.x][r]; hout[o] = h[o] + tile_h[threadIdx.x][r];
+            if (z_a) z_a[o] = 0.0;
+            if (zh_a) zh_a[o] = 0.0;
+        }
+    }
+}
+
+int launch_fold_out_pair(State &st, const double *a, const double *a_t, double *out, double *z_a, double *z_t, const double *h,
+                         const double *h_t, double *hout, double *zh_a, double *zh_t, int i_begin, int i_count, const int *done)
+{
+    if (i_count <= 0) return 0;
+    KernelTimer kt(ASORA_KERNEL_FINISH);
+    const unsigned tk = (st.N + 31) / 32, ti = (i_count + 31) / 32;
+    hipLaunchKernelGGL(fold_out_pair_kernel, dim3(ti, st.N, tk), dim3(32, 8), 0, st.stream, a, a_t, out, z_a, z_t, h, h_t, hout, zh_a, zh_t,
+                       st.N, i_begin, i_begin + i_count, done);
+    ASORA_HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // dst[q] += src[q], q < n (n even: whole planes of an even N^2, or handled by the tail): the rates another rank sent for planes
 // this rank owns, added to its own accumulator in the order the host issues the calls
 __global__ void __launch_bounds__(256) add_planes_kernel(double *__restrict__ dst, const double *__restrict__ src, size_t n,

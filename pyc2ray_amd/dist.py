@@ -214,16 +214,26 @@ class SlabPlan:
     def reach_runs(self, r):
         return _runs_of(self.reach[r])
 
-    def bytes_per_rank(self, r):
-        """(sent, received) by rank r in ONE of the two exchanges of an iteration, in bytes."""
-        plane = 8 * self.N * self.N
+    @staticmethod
+    def _fields(thermal, exchange):
+        """Grids that travel per plane: the rate exchange of a thermal step carries the heating rates too, the xh_av exchange never."""
+        if exchange not in ("rates", "xh_av"):
+            raise ValueError(f"exchange: 'rates' or 'xh_av', not {exchange!r}")
+        return 2 if (thermal and exchange == "rates") else 1
+
+    def bytes_per_rank(self, r, thermal=False, exchange="rates"):
+        """(sent, received) by rank r in ONE of the two exchanges of an iteration, in bytes: `exchange` = "rates" (to the owners)
+        or "xh_av" (back).  Isothermal, both move the same planes; in a `thermal` step every plane of the rate direction travels
+        twice, as photo-ionisation and as heating rates, and the xh_av direction is unchanged."""
+        plane = 8 * self.N * self.N * self._fields(thermal, exchange)
         sent = sum((b - a) for q in range(self.P) if q != r for a, b in self.runs[r][q])
         recv = sum((b - a) for q in range(self.P) if q != r for a, b in self.runs[q][r])
         return sent * plane, recv * plane
 
-    def largest_transfer(self):
-        """Bytes of the largest rank-to-rank transfer of one exchange (what a single xGMI link carries in one direction)."""
-        plane = 8 * self.N * self.N
+    def largest_transfer(self, thermal=False, exchange="rates"):
+        """Bytes of the largest rank-to-rank transfer of one exchange (what a single xGMI link carries in one direction);
+        `thermal`, `exchange` as in ``bytes_per_rank``."""
+        plane = 8 * self.N * self.N * self._fields(thermal, exchange)
         return plane * max([sum(b - a for a, b in self.runs[r][q]) for r in range(self.P) for q in range(self.P) if q != r] or [0])
 
 
@@ -610,22 +620,42 @@ class TorchComm:
 
     # -- the device-resident loop over several ranks (asora_evolve_slab_*, include/asora_hip.h) ------------------------
     def slab_begin(self, libasora, plan, N, R, sig, dr, num_src_local, minlogtau, dlogtau, NumTau, chemistry,
-                   conv_criterion, convergence_fraction):
+                   conv_criterion, convergence_fraction, thermal=False):
         """Start a time step of the sharded loop: NDENS, TEMP, XH and this rank's sources are on the device.  `chemistry` =
-        (dt, bh00, albpow, colh0, temph0, abu_c); conv_criterion from the TOTAL source count (pyc2ray/evolve.py:127,346)."""
+        (dt, bh00, albpow, colh0, temph0, abu_c); conv_criterion from the TOTAL source count (pyc2ray/evolve.py:127,346).
+        thermal = True: the library is in thermal mode (``ThermalParams.apply``), the step is begun through
+        asora_evolve_begin_slab_thermal and the first exchange carries the heating planes with the rate planes."""
         a, b = plan.own[self.Get_rank()]
-        libasora.evolve_begin_slab(*chemistry, R, sig, dr, minlogtau, dlogtau, NumTau, 0, num_src_local, conv_criterion,
-                                   convergence_fraction, a, b - a)
-        self._slab = (plan, int(N), int(num_src_local))
+        begin = libasora.evolve_begin_slab_thermal if thermal else libasora.evolve_begin_slab
+        begin(*chemistry, R, sig, dr, minlogtau, dlogtau, NumTau, 0, num_src_local, conv_criterion, convergence_fraction, a, b - a)
+        self._slab, self._slab_thermal = (plan, int(N), int(num_src_local)), bool(thermal)
 
     def reduce_begin(self, libasora, N, R, sig, dr, num_src_local, minlogtau, dlogtau, NumTau, chemistry, conv_criterion,
-                     convergence_fraction):
+                     convergence_fraction, thermal=False):
         """Start a time step of the same device-resident loop with the reference's exchange (pyc2ray/evolve.py:433-437): every
         rank traces its sources, the rate grid is all-reduced, every rank runs the chemistry of the WHOLE grid on identical
-        rates (and so takes the same decisions without exchanging anything else).  ``slab_enqueue`` / ``slab_poll`` drive it."""
-        libasora.evolve_begin_slab(*chemistry, R, sig, dr, minlogtau, dlogtau, NumTau, 0, num_src_local, conv_criterion,
-                                   convergence_fraction, 0, N)
-        self._slab = (None, int(N), int(num_src_local))
+        rates (and so takes the same decisions without exchanging anything else).  ``slab_enqueue`` / ``slab_poll`` drive it.
+        thermal = True (the library in thermal mode): both out-boxes, rates and heating, are all-reduced."""
+        begin = libasora.evolve_begin_slab_thermal if thermal else libasora.evolve_begin_slab
+        begin(*chemistry, R, sig, dr, minlogtau, dlogtau, NumTau, 0, num_src_local, conv_criterion, convergence_fraction, 0, N)
+        self._slab, self._slab_thermal = (None, int(N), int(num_src_local)), bool(thermal)
+
+    def thermal_stats(self, libasora):
+        """asora_thermal_stats of the thermal step just run, for the whole grid and the same on every rank: (cells that hit
+        max_substeps, cells clamped to t_floor, most substeps of one integration).  Slab exchange: every rank has integrated its
+        own planes, so the two counts are summed over the ranks and the third is their maximum (a collective: every rank calls
+        it).  All-reduce loop: every rank has computed the whole grid on identical rates, its own numbers are the answer."""
+        import torch
+        capped, floored, most = libasora.thermal_stats()
+        if self._slab[0] is None or self.Get_size() == 1:
+            return capped, floored, most
+        dev = "cuda" if self._backend() == "nccl" else "cpu"
+        counts = torch.tensor([capped, floored], dtype=torch.int64, device=dev)
+        top = torch.tensor([most], dtype=torch.int64, device=dev)
+        self._dist.all_reduce(counts, op=self._dist.ReduceOp.SUM, group=self._group)
+        self._dist.all_reduce(top, op=self._dist.ReduceOp.MAX, group=self._group)
+        c = counts.cpu().tolist()
+        return int(c[0]), int(c[1]), int(top.cpu().item())
 
     def _reduce_one(self, libasora):
         """One iteration of the loop begun with ``reduce_begin``: trace -> both accumulator layouts of all planes folded into
@@ -638,14 +668,21 @@ class TorchComm:
         libasora.evolve_slab_trace(0, num_src_local)
         libasora.evolve_slab_fold_all()
         if ph: ph.mark("trace_fold")
+        thermal = getattr(self, "_slab_thermal", False)
         if self.Get_size() > 1 or os.environ.get("PYC2RAY_AMD_FORCE_COLLECTIVE", "0") == "1":
             if self._backend() == "nccl":
                 with torch.cuda.stream(self._library_stream(libasora)):
                     self._dist.all_reduce(self._outbox_view(libasora, N), op=self._dist.ReduceOp.SUM, group=self._group)
+                    if thermal:
+                        self._dist.all_reduce(self._outbox_view(libasora, N, heat=True), op=self._dist.ReduceOp.SUM, group=self._group)
             else:
                 host = libasora.evolve_slab_outbox_to_host(0, N, N)
                 self._dist.all_reduce(torch.from_numpy(host), op=self._dist.ReduceOp.SUM, group=self._group)
                 libasora.evolve_slab_outbox_from_host(0, host)
+                if thermal:
+                    host = libasora.evolve_slab_heat_outbox_to_host(0, N, N)
+                    self._dist.all_reduce(torch.from_numpy(host), op=self._dist.ReduceOp.SUM, group=self._group)
+                    libasora.evolve_slab_heat_outbox_from_host(0, host)
         if ph: ph.mark("rate_allreduce")
         libasora.evolve_slab_pass()
         libasora.evolve_slab_close(None)             # (the pass's sums are those of the whole grid, the same on every rank)
@@ -676,41 +713,46 @@ class TorchComm:
         (complete on the own planes; ``slab_gather`` collects the owners' slabs at the end of the step)."""
         return libasora.evolve_poll(max_rows)
 
-    def _outbox_view(self, libasora, N):
+    def _outbox_view(self, libasora, N, heat=False):
+        """Zero-copy (N, N*N) view of the rate out-box, or (heat) of the heating out-box of a thermal step."""
         import torch
-        ptr = libasora.evolve_slab_outbox_ptr()
+        ptr = libasora.evolve_slab_heat_outbox_ptr() if heat else libasora.evolve_slab_outbox_ptr()
         cache = self.__dict__.setdefault("_views", {})
         if (ptr, N) not in cache:
             cache[(ptr, N)] = torch.as_tensor(_DevicePointer(ptr, N ** 3), device="cuda").view(N, N * N)
         return cache[(ptr, N)]
 
-    def _post_rates(self, libasora, N, sends, recvs, tag):
-        """The first exchange: out-box planes to their owners, foreign contributions to the own planes into receive buffers."""
+    def _post_rates(self, libasora, N, sends, recvs, tag, thermal=False):
+        """The first exchange: out-box planes to their owners, foreign contributions to the own planes into receive buffers.
+        thermal: for every (peer, run of planes) the heating planes travel behind the rate planes, in the same round."""
         import torch
         dist = self._dist
         if not sends and not recvs:
             return None
+        fields = (False, True) if thermal else (False,)                # heat? -- rates first, then heating, per run
         if self._backend() == "nccl":
             with torch.cuda.stream(self._library_stream(libasora)):
-                box = self._outbox_view(libasora, N)
-                key = ("rates", tag, N, tuple(sends), tuple(recvs), box.data_ptr())
+                boxes = [self._outbox_view(libasora, N, heat=h) for h in fields]
+                key = ("rates", tag, N, tuple(sends), tuple(recvs), tuple(b.data_ptr() for b in boxes))
                 cache = self.__dict__.setdefault("_rounds", {})
                 if key not in cache:
-                    targets = [torch.empty((b - a, N * N), dtype=torch.float64, device="cuda") for _, a, b in recvs]
-                    ops = [dist.P2POp(dist.isend, box[a:b], q, group=self._group) for q, a, b in sends]
-                    ops += [dist.P2POp(dist.irecv, t, q, group=self._group) for (q, _, _), t in zip(recvs, targets)]
+                    targets = [[torch.empty((b - a, N * N), dtype=torch.float64, device="cuda") for _ in fields] for _, a, b in recvs]
+                    ops = [dist.P2POp(dist.isend, box[a:b], q, group=self._group) for q, a, b in sends for box in boxes]
+                    ops += [dist.P2POp(dist.irecv, t, q, group=self._group) for (q, _, _), ts in zip(recvs, targets) for t in ts]
                     cache[key] = (targets, ops)
                 targets, ops = cache[key]
                 works = dist.batch_isend_irecv(ops)
             return ("nccl", works, recvs, targets)
-        out = [torch.from_numpy(libasora.evolve_slab_outbox_to_host(a, b - a, N)) for _, a, b in sends]
-        inc = [torch.empty((b - a, N, N), dtype=torch.float64) for _, a, b in recvs]
-        ops = [dist.P2POp(dist.isend, t, q, group=self._group) for (q, _, _), t in zip(sends, out)]
-        ops += [dist.P2POp(dist.irecv, t, q, group=self._group) for (q, _, _), t in zip(recvs, inc)]
+        to_host = (libasora.evolve_slab_outbox_to_host,) + ((libasora.evolve_slab_heat_outbox_to_host,) if thermal else ())
+        out = [[torch.from_numpy(f(a, b - a, N)) for f in to_host] for _, a, b in sends]
+        inc = [[torch.empty((b - a, N, N), dtype=torch.float64) for _ in fields] for _, a, b in recvs]
+        ops = [dist.P2POp(dist.isend, t, q, group=self._group) for (q, _, _), ts in zip(sends, out) for t in ts]
+        ops += [dist.P2POp(dist.irecv, t, q, group=self._group) for (q, _, _), ts in zip(recvs, inc) for t in ts]
         return ("gloo", dist.batch_isend_irecv(ops), recvs, inc, out)
 
     def _complete_rates(self, libasora, handle):
-        """Wait for a round of ``_post_rates`` and add what arrived, in the order of `recvs` (rank order)."""
+        """Wait for a round of ``_post_rates`` and add what arrived, in the order of `recvs` (rank order); per run the rates,
+        then (thermal step) the heating."""
         import torch
         if handle is None:
             return
@@ -719,13 +761,17 @@ class TorchComm:
             with torch.cuda.stream(self._library_stream(libasora)):
                 for w in works:
                     w.wait()                                   # the library's stream waits, not the host
-            for (_, a, b), t in zip(recvs, targets):
-                libasora.evolve_slab_add(a, b - a, t.data_ptr())
+            for (_, a, b), ts in zip(recvs, targets):
+                libasora.evolve_slab_add(a, b - a, ts[0].data_ptr())
+                if len(ts) > 1:
+                    libasora.evolve_slab_add_heat(a, b - a, ts[1].data_ptr())
             return
         for w in works:
             w.wait()
-        for (_, a, b), t in zip(recvs, targets):
-            libasora.evolve_slab_add_host(a, t.numpy())
+        for (_, a, b), ts in zip(recvs, targets):
+            libasora.evolve_slab_add_host(a, ts[0].numpy())
+            if len(ts) > 1:
+                libasora.evolve_slab_add_heat_host(a, ts[1].numpy())
 
     def _close_iteration(self, libasora):
         """The three sums of this rank's pass summed over the ranks, then the convergence test on the device."""
@@ -760,7 +806,7 @@ class TorchComm:
             libasora.evolve_slab_trace(bounds[c], bounds[c + 1] - bounds[c])
             for _, a, b in sched[c]:
                 libasora.evolve_slab_fold_out(a, b - a)                 # the planes that leave now
-            handles.append(self._post_rates(libasora, N, sched[c], rsched[c], c))
+            handles.append(self._post_rates(libasora, N, sched[c], rsched[c], c, getattr(self, "_slab_thermal", False)))
         if ph: ph.mark("trace_fold_post")
         for h in handles:                                               # chunk order, then rank order: a fixed order of additions
             self._complete_rates(libasora, h)
@@ -793,7 +839,8 @@ class TorchComm:
         return int(rows[-1][0]), float(rows[-1][1]), float(rows[-1][2])
 
     def slab_gather(self, libasora, plan, which, N):
-        """Every rank gets every owner's slab of grid `which` (end of a time step: xh_intermed, phi_ion)."""
+        """Every rank gets every owner's slab of grid `which` (end of a time step: xh_intermed, phi_ion; a thermal step:
+        temp_end and phi_heat as well)."""
         import torch
         me = self.Get_rank()
         if self._backend() == "nccl":

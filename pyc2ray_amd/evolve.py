@@ -237,22 +237,26 @@ def _one_gpu_loop(libasora, step, thermal=None):
     return loop() if thermal is None else _thermal_loop(libasora, thermal, loop, step)
 
 
-def _thermal_loop(libasora, thermal, loop, step):
-    """Run `loop()` (a device loop of one step) in the library's thermal mode, and leave the library isothermal again."""
+def _thermal_loop(libasora, thermal, loop, step, stats=None):
+    """Run `loop()` (a device loop of one step, on one GPU or across ranks) in the library's thermal mode, and leave the library
+    isothermal again.  `stats`: where the step's substep statistics come from -- the library's own counters (one GPU), or the
+    communicator's, which makes them those of the whole grid on every rank (pyc2ray_amd.dist.TorchComm.thermal_stats)."""
     thermal.apply(libasora)
     try:
         result = loop()
-        capped, _floored, most = libasora.thermal_stats()
+        capped, floored, most = (stats or libasora.thermal_stats)()
     finally:
         libasora.thermal_params(False)
-    if capped:
+    _evolve.last_thermal_stats = (capped, floored, most)
+    if capped and step.rank == 0:
         printlog(f"Warning: the temperature integration of {capped:n} cell(s) hit max_substeps = {thermal.max_substeps:n} "
                  f"(most substeps used: {most:n}); their last substep took the rest of the time step.", step.logfile, step.quiet)
     return result
 
 
-def _ranks_device_loop(libasora, step, comm, begin, label):
-    """The device-resident loop across ranks (pyc2ray_amd.dist.TorchComm), begun by `begin`:
+def _ranks_device_loop(libasora, step, comm, begin, label, thermal=None):
+    """The device-resident loop across ranks (pyc2ray_amd.dist.TorchComm), begun by `begin`; with `thermal` in the library's
+    thermal mode, the heating rates exchanged with the photo-ionisation rates:
     comm.slab_begin -- sharded: per iteration the trace, the rates to the owners of the planes, ONE fused pass on the own slab,
     xh_av back, and the convergence test on the device behind the in-place all-reduce of its three sums -- identical bits, hence
     the same decision, on every rank; or
@@ -260,11 +264,19 @@ def _ranks_device_loop(libasora, step, comm, begin, label):
     test on the device.
     With RCCL a batch of iterations is enqueued per host round trip (launches beyond convergence do nothing); with gloo every
     exchange goes through the host anyway and the batch is one."""
-    begin(step.N, step.R_max_LLS, step.sig, step.dr, step.n_local, step.minlogtau, step.dlogtau, step.NumTau, step.chem,
-          step.conv_criterion, step.convergence_fraction)
-    batch_max = max(1, min(EVOLVE_BATCH, 32)) if _comm_backend(comm) == "nccl" else 1
-    return _device_loop(step, functools.partial(comm.slab_enqueue, libasora), functools.partial(comm.slab_poll, libasora),
-                        batch_max, label)
+    def loop():
+        if thermal is not None:
+            begin(step.N, step.R_max_LLS, step.sig, step.dr, step.n_local, step.minlogtau, step.dlogtau, step.NumTau, step.chem,
+                  step.conv_criterion, step.convergence_fraction, thermal=True)
+        else:
+            begin(step.N, step.R_max_LLS, step.sig, step.dr, step.n_local, step.minlogtau, step.dlogtau, step.NumTau, step.chem,
+                  step.conv_criterion, step.convergence_fraction)
+        batch_max = max(1, min(EVOLVE_BATCH, 32)) if _comm_backend(comm) == "nccl" else 1
+        return _device_loop(step, functools.partial(comm.slab_enqueue, libasora), functools.partial(comm.slab_poll, libasora),
+                            batch_max, label)
+    if thermal is None:
+        return loop()
+    return _thermal_loop(libasora, thermal, loop, step, functools.partial(comm.thermal_stats, libasora))
 
 
 def _host_test_loop(step, iteration, comm=None):
@@ -464,8 +476,22 @@ def _evolve_resident(scalars, src_flux, src_pos, uploads, N, photo_thin_table, t
     return niter
 
 
+def _thermal_ranks_refusal(comm):
+    """Why a thermal step cannot run across ranks with this communicator, or None when it can.  The heating rates travel with the
+    photo-ionisation rates on the two device loops of a pyc2ray_amd.dist.TorchComm only; decided from the communicator alone,
+    before any GPU work."""
+    if comm is None or not (hasattr(comm, "slab_enqueue") and hasattr(comm, "reduce_begin") and hasattr(comm, "thermal_stats")):
+        return "it needs a pyc2ray_amd.dist.TorchComm, which exchanges the heating rates with the photo-ionisation rates"
+    if getattr(comm, "overlap", False):
+        return "the pipelined loop (overlap=True) is isothermal"
+    if getattr(comm, "exchange", "") != "slab" and not getattr(comm, "device_loop", False):
+        return "the three-call loop (device_loop=False) is isothermal"
+    return None
+
+
 def _evolve(scalars, src_flux, src_pos, grids, photo_thin_table, ranks=_ONE_RANK, thermal=None, clump=None):
-    """A use_gpu=True step on host arrays, grids = (temp, ndens, xh), on one GPU or across `ranks`; `thermal` on one GPU only."""
+    """A use_gpu=True step on host arrays, grids = (temp, ndens, xh), on one GPU or across `ranks`; `thermal` on one GPU, or
+    across ranks on the "slab" and "all-reduce" device loops."""
     if not cuda_is_init():
         raise RuntimeError("GPU not initialized. Please initialize it by calling device_init(N)")
     _residency.reclaim()              # this step overwrites device grids a resident C2Ray object may be relying on
@@ -475,6 +501,9 @@ def _evolve(scalars, src_flux, src_pos, grids, photo_thin_table, ranks=_ONE_RANK
     temp, ndens, xh = grids
     N = temp.shape[0]                   # mesh size
     strategy = _loop_strategy(libasora, comm, distributed)
+    if thermal is not None and strategy not in ("one GPU", "slab", "all-reduce"):
+        raise ValueError(f"evolve3D_MPI: the thermal mode across ranks runs on the slab and all-reduce device loops; this step would "
+                         f"take the {strategy} loop (the [k][j][i] twins are off?), where it is single-GPU only")
 
     # source shard of this rank, evolve.py:360-371
     plan = src_i0 = None
@@ -499,10 +528,10 @@ def _evolve(scalars, src_flux, src_pos, grids, photo_thin_table, ranks=_ONE_RANK
         niter = _one_gpu_loop(libasora, step, thermal)
     elif strategy == "slab":
         niter = _ranks_device_loop(libasora, step, comm, functools.partial(comm.slab_begin, libasora, plan),
-                                   "Doing Raytracing and Chemistry, slab-wise")
+                                   "Doing Raytracing and Chemistry, slab-wise", thermal)
     elif strategy == "all-reduce":
         niter = _ranks_device_loop(libasora, step, comm, functools.partial(comm.reduce_begin, libasora),
-                                   "Doing Raytracing, all-reduce and Chemistry")
+                                   "Doing Raytracing, all-reduce and Chemistry", thermal)
     elif strategy == "pipelined":
         niter = _pipelined_loop(libasora, step, comm, src_i0)
     else:
@@ -513,6 +542,9 @@ def _evolve(scalars, src_flux, src_pos, grids, photo_thin_table, ranks=_ONE_RANK
     if strategy == "slab":       # every rank returns the whole fields (evolve.py:480-481,497): collect the owners' slabs
         comm.slab_gather(libasora, plan, _capi.GRID_XH_INTERMED, N)
         comm.slab_gather(libasora, plan, _capi.GRID_PHI_ION, N)
+        if thermal is not None:      # TEMP_END travels once, here; between iterations no temperature does
+            comm.slab_gather(libasora, plan, _capi.GRID_TEMP_END, N)
+            comm.slab_gather(libasora, plan, _capi.GRID_PHI_HEAT, N)
     # laid out like `xh`, as np.empty_like would; in page-locked memory (pyc2ray_amd/_pinned.py)
     like_xh = 'F' if (xh.flags.f_contiguous and not xh.flags.c_contiguous) else 'C'
     xh_new = libasora.grid_to_host(_capi.GRID_XH_INTERMED, libasora.host_empty((N, N, N), order=like_xh))
@@ -609,18 +641,29 @@ def evolve3D_MPI(dt, dr,
     them (host-staged Reduce+Bcast), or ``pyc2ray_amd.dist.MPI`` and a ``pyc2ray_amd.dist.TorchComm``
     (one process per GPU under torch.distributed: RCCL all-reduce over xGMI directly on the
     device-resident grid).  All ranks return the same (xh_new, phi_ion).
-    The thermal mode is single-GPU only: ``thermal`` must be None here.
+
+    ``thermal`` (a :class:`pyc2ray_amd.thermal.ThermalParams`, as in :func:`evolve3D`): with a ``TorchComm`` on one of its two
+    device loops -- the slab exchange or the full-grid all-reduce (``exchange``; not ``overlap=True``, not
+    ``device_loop=False``) -- the temperature is evolved as well.  The heating rates travel with the photo-ionisation rates
+    (slab exchange: the same planes, in the same round; all-reduce: a second grid), temperatures do not travel between
+    iterations, and every rank returns identical (xh_new, phi_ion, temp_new); PHI_HEAT on the device holds the summed heating
+    rates.  With any other communicator (None, mpi4py) the thermal mode is single-GPU only and a ValueError says so before any GPU
+    work; use_gpu=False has no thermal form.
     ``clumping`` as in :func:`evolve3D`; every rank passes (and uploads) the whole grid, as it does ``ndens``.
     """
     if thermal is not None:
-        raise ValueError("evolve3D_MPI: the thermal mode is single-GPU only (no slab exchange of heating rates and "
-                         "temperatures); use evolve3D with use_gpu=True")
+        if not use_gpu:
+            raise ValueError("evolve3D_MPI: the thermal mode needs use_gpu=True (the use_gpu=False raytracer has no thermal form)")
+        refusal = _thermal_ranks_refusal(comm)
+        if refusal is not None:
+            raise ValueError(f"evolve3D_MPI: with this communicator the thermal mode is single-GPU only ({refusal}); use evolve3D "
+                             "with use_gpu=True, or a TorchComm on the slab or all-reduce device loop")
     clump = _clumping_spec(clumping, np.shape(temp)[0])
     scalars = _scalars(dt, dr, R_max_LLS, convergence_fraction, sig, minlogtau, dlogtau, (bh00, albpow, colh0, temph0, abu_c),
                        logfile, quiet)
     ranks = (use_mpi, comm, rank, nprocs)
     with _clumping_reset(clump):
         if use_gpu:
-            return _evolve(scalars, src_flux, src_pos, (temp, ndens, xh), photo_thin_table, ranks, clump=clump)
+            return _evolve(scalars, src_flux, src_pos, (temp, ndens, xh), photo_thin_table, ranks, thermal=thermal, clump=clump)
         return _evolve_cpu_semantics(scalars, src_flux, src_pos, (temp, ndens, xh), (photo_thin_table, photo_thick_table),
                                      (max_subbox, subboxsize, loss_fraction), ranks, clump=clump)

@@ -250,6 +250,15 @@ class _LibAsora:
                                                       float(conv_criterion), float(convergence_fraction), int(own_begin),
                                                       int(own_count)), "evolve_begin_slab")
 
+    def evolve_begin_slab_thermal(self, dt, bh00, albpow, colh0, temph0, abu_c, R, sig, dr, minlogtau, dlogtau, NumTau,
+                                  src_begin, src_count, conv_criterion, convergence_fraction, own_begin, own_count):
+        """The same step in thermal mode (thermal_params(True, ...) first): the caller exchanges the heating rates as well."""
+        _capi.check(self._lib.asora_evolve_begin_slab_thermal(float(dt), float(bh00), float(albpow), float(colh0), float(temph0),
+                                                              float(abu_c), float(R), float(sig), float(dr), float(minlogtau),
+                                                              float(dlogtau), int(NumTau), int(src_begin), int(src_count),
+                                                              float(conv_criterion), float(convergence_fraction), int(own_begin),
+                                                              int(own_count)), "evolve_begin_slab_thermal")
+
     def evolve_slab_trace(self, src_begin, src_count):
         _capi.check(self._lib.asora_evolve_slab_trace(int(src_begin), int(src_count)), "evolve_slab_trace")
 
@@ -287,6 +296,28 @@ class _LibAsora:
     def evolve_slab_add_host(self, i_begin, planes):
         a = np.ascontiguousarray(planes, dtype=np.float64)
         _capi.check(self._lib.asora_evolve_slab_add_host(int(i_begin), int(a.shape[0]), _capi.dptr(a)), "evolve_slab_add_host")
+
+    # the heating rates of a step begun with evolve_begin_slab_thermal: the twins of the out-box and add calls above
+    def evolve_slab_heat_outbox_ptr(self):
+        return self._lib.asora_evolve_slab_heat_outbox()
+
+    def evolve_slab_heat_outbox_to_host(self, i_begin, i_count, N):
+        out = np.empty((int(i_count), N, N))
+        _capi.check(self._lib.asora_evolve_slab_heat_outbox_to_host(int(i_begin), int(i_count), _capi.dptr(out)),
+                    "evolve_slab_heat_outbox_to_host")
+        return out
+
+    def evolve_slab_heat_outbox_from_host(self, i_begin, planes):
+        a = np.ascontiguousarray(planes, dtype=np.float64)
+        _capi.check(self._lib.asora_evolve_slab_heat_outbox_from_host(int(i_begin), int(a.shape[0]), _capi.dptr(a)),
+                    "evolve_slab_heat_outbox_from_host")
+
+    def evolve_slab_add_heat(self, i_begin, i_count, dev_ptr):
+        _capi.check(self._lib.asora_evolve_slab_add_heat(int(i_begin), int(i_count), C.c_void_p(int(dev_ptr))), "evolve_slab_add_heat")
+
+    def evolve_slab_add_heat_host(self, i_begin, planes):
+        a = np.ascontiguousarray(planes, dtype=np.float64)
+        _capi.check(self._lib.asora_evolve_slab_add_heat_host(int(i_begin), int(a.shape[0]), _capi.dptr(a)), "evolve_slab_add_heat_host")
 
     def evolve_slab_pass(self):
         _capi.check(self._lib.asora_evolve_slab_pass(), "evolve_slab_pass")

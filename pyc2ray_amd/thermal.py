@@ -3,7 +3,8 @@
 With a :class:`ThermalParams` handed to ``evolve3D(..., thermal=...)`` the temperature of every cell is integrated over the
 time step from photo-heating and radiative cooling, inside the inner iteration of the chemistry where the reference keeps
 the placeholders (src/c2ray/chemistry.f90:164,171-176,182-189).  The hot path is the thermal form of the fused chemistry
-pass (pyc2ray_amd/csrc/chemistry.hip) and the heating form of the raytrace; single GPU only.
+pass (pyc2ray_amd/csrc/chemistry.hip) and the heating form of the raytrace.  ``evolve3D_MPI(..., thermal=...)`` runs it across
+ranks on the two device loops of a ``pyc2ray_amd.dist.TorchComm``, the heating rates exchanged with the photo-ionisation rates.
 """
 from dataclasses import dataclass
 from typing import Optional
