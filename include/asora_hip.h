@@ -60,6 +60,25 @@ int asora_heat_table_to_device(const double *heat_thin_table, const double *heat
 /* libasora.source_data_to_device(pos, flux, NumSrc)     python_module.cu:133-148 -> memory.cu:99-114 */
 int asora_source_data_to_device(const int32_t *pos, const double *flux, int NumSrc);
 
+/* Per-source spectra (no counterpart in the reference, where every source shines with one spectrum).
+ * asora_spectra_to_device replaces the rate tables by NumSpec sets, 1 <= NumSpec <= 16: the arrays are [NumSpec][NumTau] in C
+ * order, all sets share NumTau and the tau grid of the raytrace calls.  Both heating pointers may be null: no heating tables, as
+ * after asora_photo_table_to_device alone.  asora_photo_table_to_device / asora_heat_table_to_device mean NumSpec = 1.
+ * asora_source_spectra_to_device gives source s of the last asora_source_data_to_device (which resets every source to set 0) the
+ * set spec[s]; null or all zeros: every source set 0.  An index outside [0, NumSpec) fails with code 3 here, or with code 4 in the
+ * first raytrace when the tables are replaced by fewer sets afterwards: no index reaches a kernel unchecked.  While any source
+ * has a set other than 0, the sub-box calls (asora_subbox_raytrace_device, c2ray_do_all_sources) and grey opacity
+ * (ASORA_OPT_GREY_NOTABLES) fail with code 4.
+ * asora_debug_sort_sources: host only, no device needed -- the position-ordered copy of a source list exactly as
+ * asora_source_data_to_device forms it, with the set of each source carried along (spec / spec_out may be null). */
+#define ASORA_MAX_SPECTRA 16
+int asora_spectra_to_device(int NumSpec, int NumTau, const double *photo_thin, const double *photo_thick,
+                            const double *heat_thin, const double *heat_thick);
+int asora_source_spectra_to_device(const int32_t *spec, int NumSrc);
+int asora_num_spectra(void);
+int asora_debug_sort_sources(const int32_t *pos, const double *flux, const int32_t *spec, int NumSrc, int32_t *pos_out,
+                             double *flux_out, int32_t *spec_out);
+
 /* libasora.do_all_sources(R, coldensh_out, sig, dr, ndens, xh_av, phi_ion, NumSrc, m1,
  *                         minlogtau, dlogtau, NumTau)   python_module.cu:21-68 -> raytracing.cu:79-148.
  * coldensh_out and ndens are ignored, as in the reference (raytracing.cu:116: the density must

@@ -19,6 +19,7 @@ GRID_CLUMP = 8
  OPT_HEATING, OPT_C2RAY_OWN_FLUX, OPT_NO_UNIFORM_T, OPT_SUBBOX_GLOBAL_SHELLS, OPT_PIPELINED_COPIES,
  OPT_SKIP_ZERO_RATES, OPT_GLOBAL_ATOMICS, OPT_PAIR_SOURCES, OPT_SUBBOX_TABLES, OPT_ALIGNED_ROWS, OPT_GEOMETRY_ON_HOST,
  OPT_PLACEMENT_CANDIDATES) = range(18)
+MAX_SPECTRA = 16
 KERNEL_RAYTRACE, KERNEL_CHEMISTRY, KERNEL_PREP, KERNEL_FINISH = range(4)
 VARIANT_PAIRED, VARIANT_ALIGNED, VARIANT_BUFFER_ATOMICS, VARIANT_SPLIT_DESCRIPTORS, VARIANT_SKIP_ZERO, VARIANT_GLOBAL_SHELLS = 1, 2, 4, 8, 16, 32
 
@@ -34,6 +35,10 @@ SIGNATURES = {
     "asora_photo_table_to_device": (C.c_int, [_dp, _dp, C.c_int]),
     "asora_heat_table_to_device": (C.c_int, [_dp, _dp, C.c_int]),
     "asora_source_data_to_device": (C.c_int, [_ip, _dp, C.c_int]),
+    "asora_spectra_to_device": (C.c_int, [C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
+    "asora_source_spectra_to_device": (C.c_int, [_ip, C.c_int]),
+    "asora_num_spectra": (C.c_int, []),
+    "asora_debug_sort_sources": (C.c_int, [_ip, _dp, _ip, C.c_int, _ip, _dp, _ip]),
     "asora_do_all_sources": (C.c_int, [C.c_double, _dp, C.c_double, C.c_double, _dp, _dp, _dp, C.c_int, C.c_int,
                                        C.c_double, C.c_double, C.c_int]),
     "c2ray_global_pass": (C.c_int, [C.c_double, _dp, _dp, _dp, _dp, _dp, _dp, C.c_double, C.c_double, C.c_double,

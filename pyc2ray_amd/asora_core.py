@@ -7,7 +7,8 @@ behind it is an MI355X driven through HIP.
 from . import _pinned, _residency
 from .load_extensions import load_asora
 
-__all__ = ['cuda_is_init', 'device_init', 'device_close', 'photo_table_to_device']
+__all__ = ['cuda_is_init', 'device_init', 'device_close', 'photo_table_to_device', 'spectra_to_device',
+           'source_spectra_to_device', 'num_spectra']
 
 _NOT_READY = "GPU not initialized. Please initialize it by calling device_init(N)"
 
@@ -52,3 +53,20 @@ def photo_table_to_device(thin_table, thick_table):
     """Upload the optically thin and thick photo-ionisation tables.  The library is told the number of table
     elements, which is what the reference passes as NumTau (asora_core.py:54)."""
     _Lifecycle.library().photo_table_to_device(thin_table, thick_table, thin_table.shape[0])
+
+
+def spectra_to_device(photo_thin, photo_thick, heat_thin=None, heat_thick=None):
+    """Upload K table sets, one per source spectrum: 2-D (K, NumTau) float64 arrays on one tau grid, the heating tables both or
+    not at all.  Replaces what photo_table_to_device uploaded (which is the case K = 1).  Which set a source takes:
+    ``src_spectrum=`` of evolve3D / do_raytracing, or :func:`source_spectra_to_device`."""
+    _Lifecycle.library().spectra_to_device(photo_thin, photo_thick, heat_thin, heat_thick)
+
+
+def source_spectra_to_device(spec):
+    """The table set of each source on the device, an integer array in the order of the last source upload (None: all 0)."""
+    _Lifecycle.library().source_spectra_to_device(spec)
+
+
+def num_spectra():
+    """How many table sets the device holds (0 before any table upload)."""
+    return _Lifecycle.library().num_spectra()

@@ -32,7 +32,7 @@ try:
 except ImportError:  # pragma: no cover
     from yaml import SafeLoader
 
-from .asora_core import cuda_is_init, device_close, device_init, photo_table_to_device
+from .asora_core import cuda_is_init, device_close, device_init, photo_table_to_device, spectra_to_device
 from . import _capi, _residency
 from .evolve import evolve3D, evolve3D_MPI, evolve3D_resident
 from .load_extensions import load_asora
@@ -287,10 +287,11 @@ class C2Ray:
         self.__dict__["_clumping"] = value
         self._host_newer.add("clumping")
 
-    def evolve3D(self, dt, src_flux, src_pos):
-        """Evolve the grid over one time step (c2ray_base.py:170-226)."""
+    def evolve3D(self, dt, src_flux, src_pos, src_spectrum=None):
+        """Evolve the grid over one time step (c2ray_base.py:170-226).  src_spectrum: with ``BlackBodySource: Teff`` a list, the
+        index into it of each source's temperature (None: every source the first one); see pyc2ray_amd.evolve3D."""
         if self.device_resident and self.gpu and not self.mpi:
-            return self._evolve3D_resident(dt, src_flux, src_pos)
+            return self._evolve3D_resident(dt, src_flux, src_pos, src_spectrum)
         head = (dt, self.dr, src_flux, src_pos, self.gpu, self.max_subbox, self.subboxsize, self.loss_fraction)
         tail = (self.temp, self.ndens, self.xh, self.photo_thin_table, self.photo_thick_table, self.minlogtau, self.dlogtau,
                 self.R_max_LLS, self.convergence_fraction, self.sig, self.bh00, self.albpow, self.colh0, self.temph0, self.abu_c,
@@ -298,9 +299,9 @@ class C2Ray:
         thermal = self._thermal_params()
         if self.mpi and src_flux.shape[0] >= self.nprocs:
             result = evolve3D_MPI(*head, self.mpi, self.comm, self.rank, self.nprocs, *tail, thermal=thermal,
-                                  clumping=self.__dict__["_clumping"])
+                                  clumping=self.__dict__["_clumping"], src_spectrum=src_spectrum)
         else:
-            result = evolve3D(*head, *tail, thermal=thermal, clumping=self.__dict__["_clumping"])
+            result = evolve3D(*head, *tail, thermal=thermal, clumping=self.__dict__["_clumping"], src_spectrum=src_spectrum)
         self.xh, self.phi_ion = result[:2]
         if thermal is not None:
             self.temp = result[2]
@@ -339,7 +340,7 @@ class C2Ray:
         self._host_newer |= {"ndens", "temp", "xh", "clumping"}
         self.__dict__.pop("_grid_fingerprints", None)
 
-    def _evolve3D_resident(self, dt, src_flux, src_pos):
+    def _evolve3D_resident(self, dt, src_flux, src_pos, src_spectrum=None):
         """The same step with the grids left on the device (see `device_resident`)."""
         d = self.__dict__
         _residency.reclaim(except_for=self)                     # (another object's device copies, should there be one)
@@ -362,7 +363,7 @@ class C2Ray:
             d["_grid_phi_ion"] = np.zeros(self.shape)           # the GPU path returns C-ordered rates (evolve.py:200)
         evolve3D_resident(dt, self.dr, src_flux, src_pos, uploads, self.N, self.photo_thin_table, self.minlogtau, self.dlogtau,
                           self.R_max_LLS, self.convergence_fraction, self.sig, self.bh00, self.albpow, self.colh0, self.temph0,
-                          self.abu_c, self.logfile, thermal=self._thermal_params(), clumping=clumping)
+                          self.abu_c, self.logfile, thermal=self._thermal_params(), clumping=clumping, src_spectrum=src_spectrum)
         self._host_newer -= {"ndens", "temp", "xh", "phi_ion", "clumping"}
         self._device_newer |= {"xh", "phi_ion"} if self.isothermal else {"xh", "phi_ion", "temp"}
 
@@ -491,6 +492,9 @@ class C2Ray:
             freq_max = 10 * ion_freq_HeII
             self.bb_Teff = self._ld['BlackBodySource']['Teff']
             self.cs_pl_idx_h = self._ld['BlackBodySource']['cross_section_pl_index']
+            if isinstance(self.bb_Teff, (list, tuple)):
+                self._radiation_init_spectra(ion_freq_HI, freq_min, freq_max)
+                return
             radsource = BlackBodySource(self.bb_Teff, self.grey, ion_freq_HI, self.cs_pl_idx_h)
             if self.rank == 0:
                 self.printlog(f"Using Black-Body sources with effective temperature T = {radsource.temp :.1e} K")
@@ -510,6 +514,42 @@ class C2Ray:
             photo_table_to_device(self.photo_thin_table, self.photo_thick_table)
             if self.rank == 0:
                 self.printlog("Successfully copied radiation tables to GPU memory.")
+
+    def _radiation_init_spectra(self, ion_freq_HI, freq_min, freq_max):
+        """``BlackBodySource: Teff`` is a list: one table set per temperature from the builder of the scalar form, heating tables
+        included with compute_heating_rates, uploaded together (spectra_to_device).  ``spectra_*_table`` are (K, NumTau + 1); the
+        plain ``photo_*_table`` / ``heat_*_table`` attributes are those of the first temperature.  Which set a source takes:
+        ``evolve3D(dt, src_flux, src_pos, src_spectrum)``."""
+        teffs = [float(t) for t in self.bb_Teff]
+        if not 1 <= len(teffs) <= _capi.MAX_SPECTRA:
+            raise ValueError(f"BlackBodySource: Teff lists {len(teffs)} temperatures; 1 to {_capi.MAX_SPECTRA} are possible")
+        if self.rank == 0:
+            self.printlog("Using Black-Body sources with effective temperatures T = " + ", ".join(f"{t:.1e}" for t in teffs) + " K")
+            self.printlog(f"Spectrum Frequency Range: {freq_min:.3e} to {freq_max:.3e} Hz")
+            self.printlog("Integrating photoionization rates tables...")
+        sources = [BlackBodySource(t, self.grey, ion_freq_HI, self.cs_pl_idx_h) for t in teffs]
+        photo = [s.make_photo_table(self.tau, freq_min, freq_max, 1e48) for s in sources]
+        self.spectra_photo_thin_table = np.stack([t[0] for t in photo])
+        self.spectra_photo_thick_table = np.stack([t[1] for t in photo])
+        if self.compute_heating_rates:
+            self.printlog("Integrating photoheating rates tables...")
+            heat = [s.make_heat_table(self.tau, freq_min, freq_max, 1e48) for s in sources]
+            self.spectra_heat_thin_table = np.stack([t[0] for t in heat])
+            self.spectra_heat_thick_table = np.stack([t[1] for t in heat])
+        else:
+            self.printlog("INFO: No heating rates")
+            self.spectra_heat_thin_table = self.spectra_heat_thick_table = None
+        self.photo_thin_table, self.photo_thick_table = self.spectra_photo_thin_table[0], self.spectra_photo_thick_table[0]
+        if self.compute_heating_rates:
+            self.heat_thin_table, self.heat_thick_table = self.spectra_heat_thin_table[0], self.spectra_heat_thick_table[0]
+        else:
+            self.heat_thin_table = np.zeros(self.NumTau + 1)
+            self.heat_thick_table = np.zeros(self.NumTau + 1)
+        if self.gpu:
+            spectra_to_device(self.spectra_photo_thin_table, self.spectra_photo_thick_table, self.spectra_heat_thin_table,
+                              self.spectra_heat_thick_table)
+            if self.rank == 0:
+                self.printlog(f"Successfully copied {len(teffs):n} sets of radiation tables to GPU memory.")
 
     def _grid_init(self):
         self.boxsize_c = self._ld['Grid']['boxsize'] * Mpc

@@ -107,7 +107,8 @@ static int release_all()
     st.temp_probe_valid = false;
     st.nhi_t = st.phi_t = st.heat_t = nullptr;    // second halves of nhi / phi_ion / phi_heat
     st.have_heat_tables = false;
-    drop(st.tables); st.table_len = 0;
+    drop(st.tables); st.table_len = 0; st.num_spec = 1; st.spec_stride = 0;
+    drop(st.src_spec); drop(st.src_spec_sorted); st.src_spec_max = 0;
     drop(st.src_pos); drop(st.src_flux); drop(st.src_pos_sorted); drop(st.src_flux_sorted); st.src_i0_sorted.clear(); st.num_src = 0;
     st.src_pos_host.clear(); st.src_pos_sorted_host.clear();
     release_pair_lists(st);

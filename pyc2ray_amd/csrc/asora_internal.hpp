@@ -93,6 +93,9 @@ struct RtParams {
     const int *sb_active;       // per source of the batch: still growing?
     double *sb_loss;            // per source of the batch: photons through the faces of the current sub-box
     double *sb_trail;           // per (source, unit): the last shell swept, handed to the next sub-box's launch
+    // ---- per-source spectra (asora_spectra_to_device; appended, so the fields above keep their offsets) ----
+    const int32_t *src_spec;    // table set of each source, indexed like src_pos / src_flux; nullptr: every source set 0
+    unsigned spec_stride;       // double2 entries from one set's [thick | thin | heat thick | heat thin] block to the next
 };
 
 // Constants of the thermal form of the chemistry pass (asora_thermal_params; chemistry.hip: thermal_integrate)
@@ -143,8 +146,10 @@ struct State {
     bool have_heat_tables = false;
     double *staging = nullptr; // N^3 staging grid for 'F'-order transfers / debug dumps
 
-    double2 *tables = nullptr;     // [thick | thin | heat thick | heat thin] (pack_rate_table)
+    double2 *tables = nullptr;     // num_spec blocks of [thick | thin | heat thick | heat thin] (pack_rate_table), spec_stride apart
     int table_len = 0;
+    int num_spec = 1;              // table sets on the device (asora_spectra_to_device; the one-set uploads: 1)
+    size_t spec_stride = 0;        // double2 entries of one set's block (rate_block_entries)
 
     int32_t *src_pos = nullptr;
     double *src_flux = nullptr;
@@ -153,6 +158,10 @@ struct State {
     int32_t *src_pos_sorted = nullptr;
     double *src_flux_sorted = nullptr;
     std::vector<int> src_i0_sorted;
+    // table set of each source (asora_source_spectra_to_device), in the order of src_pos and of src_pos_sorted; nullptr while
+    // every source has set 0.  src_spec_max: the largest index uploaded, checked against num_spec before every trace
+    int32_t *src_spec = nullptr, *src_spec_sorted = nullptr;
+    int src_spec_max = 0;
     std::vector<hipEvent_t> pipe_events;
 
     // raytracing geometry tables (built once per (N, R, dr), see raytrace.hip)
@@ -512,6 +521,17 @@ int ensure_optional_grid(int which);            // PHI_HEAT, TEMP_END, CLUMP: al
 int reset_counters();
 int require_raytrace_inputs(const char *who, double R, int NumTau, bool density, bool xh_av);
 void fill_rt_params(RtParams &p, double R, double sig, double dr, double minlogtau, double dlogtau, int NumTau, int radius_path = 0);
+// the source list a trace works from: as uploaded, or its position-ordered copy -- positions, fluxes and table sets together
+inline void use_source_list(RtParams &p, const State &st, bool sorted)
+{
+    p.src_pos = sorted ? st.src_pos_sorted : st.src_pos;
+    p.src_flux = sorted ? st.src_flux_sorted : st.src_flux;
+    p.src_spec = sorted ? st.src_spec_sorted : st.src_spec;
+}
+// code 4 while a source has a table set the device does not hold, or a set other than 0 under grey opacity (no tables)
+int check_source_spectra(const char *who);
+// grids_api.hip: order[s] = index of the s-th source in lexicographic order of the position (stable)
+void sort_sources_by_position(const int32_t *pos, int NumSrc, std::vector<int> &order);
 // chemistry_api.hip
 int ensure_red_capacity(size_t entries);
 int ensure_temp_probe(double bh00, double albpow, double colh0, double temph0);

@@ -208,7 +208,7 @@ static int evolve_begin_impl(double dt, double bh00, double albpow, double colh0
     st.ev_rt.phi = acc_pair(st.ev_base);       // (each iteration sets its own pair, asora_evolve_enqueue)
     st.ev_rt.done_flag = &st.ev_status->done;
     st.ev_rt.src_begin = src_begin; st.ev_rt.src_count = src_count; st.ev_rt.shape_src_count = src_count;
-    if (src_begin == 0 && src_count == st.num_src && st.src_pos_sorted) { st.ev_rt.src_pos = st.src_pos_sorted; st.ev_rt.src_flux = st.src_flux_sorted; }
+    if (src_begin == 0 && src_count == st.num_src && st.src_pos_sorted) use_source_list(st.ev_rt, st, true);
     st.ev_src_begin = src_begin; st.ev_src_count = src_count;
     st.ev_chem[0] = dt; st.ev_chem[1] = bh00; st.ev_chem[2] = albpow; st.ev_chem[3] = colh0; st.ev_chem[4] = temph0;
     st.ev_chem[5] = abu_c;
@@ -297,7 +297,7 @@ int asora_evolve_slab_trace(int src_begin, int src_count)
     RtParams p = st.ev_rt;
     p.phi = slab_pair(0);
     p.src_begin = src_begin; p.src_count = src_count;          // (shape_src_count stays the rank's whole share: one launch shape)
-    if (!(src_begin == 0 && src_count == st.num_src)) { p.src_pos = st.src_pos; p.src_flux = st.src_flux; }
+    if (!(src_begin == 0 && src_count == st.num_src)) use_source_list(p, st, false);
     if (st.ev_slab_thermal) {                 // the HEAT forms, into the iteration's heating pair
         p.heat = slab_heat_pair(0);
         st.heat_clean[0] = st.heat_clean[1] = false;

@@ -146,24 +146,48 @@ int asora_density_to_device(const double *ndens, int N)
     return asora_grid_to_device(ASORA_GRID_NDENS, ndens, N, 'C');
 }
 
+// One set's block on the device: rates_device.hpp (one 16-byte load serves the linear interpolation of photo_lookuptable,
+// rates.cu:82), [thick | thin | heat thick | heat thin]; at least 16 entries: the kernels' pipeline-priming loads read a few fixed
+// small offsets whatever the table's length.  Several sets (asora_spectra_to_device) are consecutive blocks.
+static size_t rate_block_entries(int NumTau) { return std::max<size_t>(4 * (size_t)NumTau, 16); }
+
+// heat_*: both null = no heating tables.  Arrays [NumSpec][NumTau].
+static int upload_rate_tables(const char *who, int NumSpec, int NumTau, const double *thin, const double *thick, const double *heat_thin,
+                              const double *heat_thick)
+{
+    State &st = state();
+    const bool heat = heat_thin && heat_thick;
+    if (heat) { if (int rc = ensure_optional_grid(ASORA_GRID_PHI_HEAT)) return rc; }
+    st.zero_since_probe = std::max(st.zero_since_probe, 48);
+    if (st.tables) { (void)hipFree(st.tables); st.tables = nullptr; }
+    st.table_len = 0; st.num_spec = 1; st.spec_stride = 0; st.have_heat_tables = false;
+    const size_t block = rate_block_entries(NumTau);
+    std::vector<double2> pairs(block * (size_t)NumSpec, double2{0.0, 0.0});
+    for (int k = 0; k < NumSpec; ++k) {
+        double2 *b = pairs.data() + block * (size_t)k;
+        pack_rate_table(b, 0, thick + (size_t)k * NumTau, NumTau);
+        pack_rate_table(b, 1, thin + (size_t)k * NumTau, NumTau);
+        if (heat) {
+            pack_rate_table(b, 2, heat_thick + (size_t)k * NumTau, NumTau);
+            pack_rate_table(b, 3, heat_thin + (size_t)k * NumTau, NumTau);
+        }
+    }
+    (void)who;
+    ASORA_HIP_TRY(hipMalloc(&st.tables, pairs.size() * sizeof(double2)));
+    ASORA_HIP_TRY(hipMemcpy(st.tables, pairs.data(), pairs.size() * sizeof(double2), hipMemcpyHostToDevice));
+    st.table_len = NumTau;
+    st.num_spec = NumSpec;
+    st.spec_stride = block;
+    st.have_heat_tables = heat;
+    return 0;
+}
+
 int asora_photo_table_to_device(const double *thin_table, const double *thick_table, int NumTau)
 {
     clear_error();
     if (int rc = require_init("photo_table_to_device")) return rc;
     if (NumTau < 1 || !thin_table || !thick_table) return fail(3, "photo_table_to_device: empty table");
-    State &st = state();
-    st.zero_since_probe = std::max(st.zero_since_probe, 48);
-    if (st.tables) { (void)hipFree(st.tables); st.tables = nullptr; }
-    // device layout: rates_device.hpp (one 16-byte load serves the linear interpolation of photo_lookuptable, rates.cu:82)
-    // (at least 16 elements: the kernels' pipeline-priming loads read a few fixed small offsets whatever the table's length)
-    std::vector<double2> pairs(std::max<size_t>(4 * (size_t)NumTau, 16), double2{0.0, 0.0});   // [thick | thin | heat thick | heat thin]
-    pack_rate_table(pairs.data(), 0, thick_table, NumTau);
-    pack_rate_table(pairs.data(), 1, thin_table, NumTau);
-    ASORA_HIP_TRY(hipMalloc(&st.tables, pairs.size() * sizeof(double2)));
-    ASORA_HIP_TRY(hipMemcpy(st.tables, pairs.data(), pairs.size() * sizeof(double2), hipMemcpyHostToDevice));
-    st.table_len = NumTau;
-    st.have_heat_tables = false;
-    return 0;
+    return upload_rate_tables("photo_table_to_device", 1, NumTau, thin_table, thick_table, nullptr, nullptr);
 }
 
 int asora_heat_table_to_device(const double *heat_thin_table, const double *heat_thick_table, int NumTau)
@@ -172,6 +196,9 @@ int asora_heat_table_to_device(const double *heat_thin_table, const double *heat
     if (int rc = require_init("heat_table_to_device")) return rc;
     State &st = state();
     if (!st.tables) return fail(4, "heat_table_to_device: upload the photo tables first (photo_table_to_device)");
+    if (st.num_spec != 1)
+        return fail(4, "heat_table_to_device: " + std::to_string(st.num_spec) + " table sets are on the device; their heating tables go "
+                       "up with them (spectra_to_device)");
     if (NumTau != st.table_len || !heat_thin_table || !heat_thick_table)
         return fail(3, "heat_table_to_device: the heating tables must have the length of the photo tables (" +
                            std::to_string(st.table_len) + ")");
@@ -185,6 +212,59 @@ int asora_heat_table_to_device(const double *heat_thin_table, const double *heat
     st.have_heat_tables = true;
     return 0;
 }
+
+int asora_spectra_to_device(int NumSpec, int NumTau, const double *photo_thin, const double *photo_thick, const double *heat_thin,
+                            const double *heat_thick)
+{
+    clear_error();
+    if (int rc = require_init("spectra_to_device")) return rc;
+    if (NumSpec < 1 || NumSpec > ASORA_MAX_SPECTRA)
+        return fail(3, "spectra_to_device: NumSpec=" + std::to_string(NumSpec) + " outside [1, " + std::to_string(ASORA_MAX_SPECTRA) + "]");
+    if (NumTau < 1 || !photo_thin || !photo_thick) return fail(3, "spectra_to_device: empty table");
+    if ((heat_thin == nullptr) != (heat_thick == nullptr)) return fail(3, "spectra_to_device: one heating table without the other");
+    return upload_rate_tables("spectra_to_device", NumSpec, NumTau, photo_thin, photo_thick, heat_thin, heat_thick);
+}
+
+int asora_num_spectra(void) { return state().tables ? state().num_spec : 0; }
+
+} // extern "C"
+
+namespace asora {
+
+void sort_sources_by_position(const int32_t *pos, int NumSrc, std::vector<int> &order)
+{
+    order.resize((size_t)std::max(NumSrc, 0));
+    for (int s = 0; s < NumSrc; ++s) order[s] = s;
+    std::stable_sort(order.begin(), order.end(), [pos](int a, int b) {
+        if (pos[3 * a] != pos[3 * b]) return pos[3 * a] < pos[3 * b];
+        if (pos[3 * a + 1] != pos[3 * b + 1]) return pos[3 * a + 1] < pos[3 * b + 1];
+        return pos[3 * a + 2] < pos[3 * b + 2];
+    });
+}
+
+static void drop_source_spectra(State &st)
+{
+    if (st.src_spec) { (void)hipFree(st.src_spec); st.src_spec = nullptr; }
+    if (st.src_spec_sorted) { (void)hipFree(st.src_spec_sorted); st.src_spec_sorted = nullptr; }
+    st.src_spec_max = 0;
+}
+
+int check_source_spectra(const char *who)
+{
+    State &st = state();
+    if (!st.src_spec) return 0;
+    if (st.opt[ASORA_OPT_GREY_NOTABLES])
+        return fail(4, std::string(who) + ": grey opacity uses no tables, so sources cannot have table sets of their own "
+                                          "(source_spectra_to_device with zeros, or ASORA_OPT_GREY_NOTABLES = 0)");
+    if (st.src_spec_max >= st.num_spec)
+        return fail(4, std::string(who) + ": a source has table set " + std::to_string(st.src_spec_max) + " but the device holds " +
+                           std::to_string(st.num_spec) + " (spectra_to_device)");
+    return 0;
+}
+
+} // namespace asora
+
+extern "C" {
 
 int asora_source_data_to_device(const int32_t *pos, const double *flux, int NumSrc)
 {
@@ -203,6 +283,7 @@ int asora_source_data_to_device(const int32_t *pos, const double *flux, int NumS
     if (st.src_flux) { (void)hipFree(st.src_flux); st.src_flux = nullptr; }
     if (st.src_pos_sorted) { (void)hipFree(st.src_pos_sorted); st.src_pos_sorted = nullptr; }
     if (st.src_flux_sorted) { (void)hipFree(st.src_flux_sorted); st.src_flux_sorted = nullptr; }
+    drop_source_spectra(st);              // every source back to table set 0
     st.src_i0_sorted.clear();
     st.src_pos_host.clear(); st.src_pos_sorted_host.clear();
     release_pair_lists(st);
@@ -216,13 +297,8 @@ int asora_source_data_to_device(const int32_t *pos, const double *flux, int NumS
         // a call that traces the WHOLE list works from -- sources that run side by side are then neighbours in space and
         // share nHI and rate lines (measured -2 % on the trace at r_RT = 16 and 32) -- and, ordered by the first
         // coordinate, what the pipelined asora_do_all_sources cuts into slabs
-        std::vector<int> order((size_t)NumSrc);
-        for (int s = 0; s < NumSrc; ++s) order[s] = s;
-        std::stable_sort(order.begin(), order.end(), [pos](int a, int b) {
-            if (pos[3 * a] != pos[3 * b]) return pos[3 * a] < pos[3 * b];
-            if (pos[3 * a + 1] != pos[3 * b + 1]) return pos[3 * a + 1] < pos[3 * b + 1];
-            return pos[3 * a + 2] < pos[3 * b + 2];
-        });
+        std::vector<int> order;
+        sort_sources_by_position(pos, NumSrc, order);
         std::vector<int32_t> ps(3 * (size_t)NumSrc);
         std::vector<double> fs((size_t)NumSrc);
         st.src_i0_sorted.resize((size_t)NumSrc);
@@ -241,6 +317,55 @@ int asora_source_data_to_device(const int32_t *pos, const double *flux, int NumS
     st.src_pos_host.assign(pos, pos + 3 * (size_t)NumSrc);
     st.num_src = NumSrc;
     st.src_generation += 1;
+    return 0;
+}
+
+int asora_source_spectra_to_device(const int32_t *spec, int NumSrc)
+{
+    clear_error();
+    if (int rc = require_init("source_spectra_to_device")) return rc;
+    State &st = state();
+    if (NumSrc != st.num_src)
+        return fail(3, "source_spectra_to_device: " + std::to_string(NumSrc) + " table sets for the " + std::to_string(st.num_src) +
+                           " sources on the device (source_data_to_device first)");
+    drop_source_spectra(st);
+    if (!spec || NumSrc == 0) return 0;
+    // validated on the host: the index becomes an offset on the table pointer.  Against the sets on the device now, if any; a
+    // table upload that follows is met by check_source_spectra before the first trace
+    const int limit = st.tables ? st.num_spec : ASORA_MAX_SPECTRA;
+    int top = 0;
+    for (int s = 0; s < NumSrc; ++s) {
+        if (spec[s] < 0 || spec[s] >= limit)
+            return fail(3, "source_spectra_to_device: source " + std::to_string(s) + " has table set " + std::to_string(spec[s]) +
+                               ", outside [0, " + std::to_string(limit) + ")");
+        top = std::max(top, (int)spec[s]);
+    }
+    if (top == 0) return 0;               // all set 0: the launches carry no array at all
+    std::vector<int> order;
+    sort_sources_by_position(st.src_pos_host.data(), NumSrc, order);
+    std::vector<int32_t> sorted((size_t)NumSrc);
+    for (int s = 0; s < NumSrc; ++s) sorted[s] = spec[order[s]];
+    ASORA_HIP_TRY(hipMalloc(&st.src_spec, sizeof(int32_t) * (size_t)NumSrc));
+    ASORA_HIP_TRY(hipMalloc(&st.src_spec_sorted, sizeof(int32_t) * (size_t)NumSrc));
+    ASORA_HIP_TRY(hipMemcpy(st.src_spec, spec, sizeof(int32_t) * (size_t)NumSrc, hipMemcpyHostToDevice));
+    ASORA_HIP_TRY(hipMemcpy(st.src_spec_sorted, sorted.data(), sizeof(int32_t) * (size_t)NumSrc, hipMemcpyHostToDevice));
+    st.src_spec_max = top;
+    return 0;
+}
+
+int asora_debug_sort_sources(const int32_t *pos, const double *flux, const int32_t *spec, int NumSrc, int32_t *pos_out,
+                             double *flux_out, int32_t *spec_out)
+{
+    clear_error();
+    if (NumSrc < 0 || (NumSrc > 0 && (!pos || !flux || !pos_out || !flux_out))) return fail(3, "debug_sort_sources: bad arguments");
+    std::vector<int> order;
+    sort_sources_by_position(pos, NumSrc, order);
+    for (int s = 0; s < NumSrc; ++s) {
+        const int o = order[s];
+        for (int ax = 0; ax < 3; ++ax) pos_out[3 * s + ax] = pos[3 * o + ax];
+        flux_out[s] = flux[o];
+        if (spec && spec_out) spec_out[s] = spec[o];
+    }
     return 0;
 }
 

@@ -57,8 +57,9 @@ struct RateJob {
     Lookup A, B;             // thick: T(tau_in), T(tau_out);  thin: T_thin(tau*), unused
     bool thick;
 };
+// `tab`: the [thick | thin | heat thick | heat thin] block of the source's table set (RtParams::src_spec)
 __device__ __forceinline__ RateJob rate_issue(double flux, double cd_in, double cd_out, double vol_nhi,
-                                              const RtParams &p, const double2 *__restrict__ logtab)
+                                              const RtParams &p, const double2 *__restrict__ logtab, const double2 *__restrict__ tab)
 {
     // (un-fused products: tau_out - tau_in must be the difference of the two ROUNDED optical depths, as in the
     //  reference; fused into fma(cd_out, sig, -tau_in) it would carry the rounding error of one product -- a speck
@@ -75,8 +76,8 @@ __device__ __forceinline__ RateJob rate_issue(double flux, double cd_in, double 
     // one code path for both kinds of cell: per-lane table and arguments
     // thick table at [0, table_len), thin table at [table_len, 2*table_len) of one allocation
     const int toff = J.thick ? 0 : table_stride(p.table_len);
-    J.A = lookup_issue(p.tables, J.thick ? tau_in : tau_thin, p, logtab, toff);
-    J.B = lookup_issue(p.tables, J.thick ? tau_out : tau_thin, p, logtab, toff);
+    J.A = lookup_issue(tab, J.thick ? tau_in : tau_thin, p, logtab, toff);
+    J.B = lookup_issue(tab, J.thick ? tau_out : tau_thin, p, logtab, toff);
     return J;
 }
 __device__ __forceinline__ double rate_value(const RateJob &J)
@@ -101,7 +102,7 @@ __device__ __forceinline__ double grey_rate_per_atom(double flux, double cd_in, 
 
 // heating rate of one cell per atom (photorates.f90:118,124), used for the source cell only
 __device__ __forceinline__ double heat_rate_per_atom(double flux, double cd_in, double cd_out, double vol_nhi,
-                                                     const RtParams &p, const double2 *__restrict__ logtab)
+                                                     const RtParams &p, const double2 *__restrict__ logtab, const double2 *__restrict__ tab)
 {
     const double tau_in = mul_unfused(cd_in, p.sig), tau_out = mul_unfused(cd_out, p.sig);   // un-fused, see rate_issue
     const double limit = p.fortran_consts ? (double)1.0e-7f : 1.0e-7;
@@ -109,16 +110,16 @@ __device__ __forceinline__ double heat_rate_per_atom(double flux, double cd_in, 
     const bool thick = fabs(tau_out - tau_in) > limit;
     const double tau_thin = p.fortran_consts ? tau_in : tau_out;
     const int toff = thick ? 0 : table_stride(p.table_len);
-    const Lookup A = lookup_issue<true>(p.tables, thick ? tau_in : tau_thin, p, logtab, toff);
-    const Lookup B = lookup_issue<true>(p.tables, thick ? tau_out : tau_thin, p, logtab, toff);
+    const Lookup A = lookup_issue<true>(tab, thick ? tau_in : tau_thin, p, logtab, toff);
+    const Lookup B = lookup_issue<true>(tab, thick ? tau_out : tau_thin, p, logtab, toff);
     return thick ? pref * (lookup_heat(A) - lookup_heat(B)) : pref * (tau_out - tau_in) * lookup_heat(A);
 }
 
 __device__ __forceinline__ double photo_rate_per_atom(double flux, double cd_in, double cd_out, double vol_nhi,
-                                                      const RtParams &p, const double2 *__restrict__ logtab)
+                                                      const RtParams &p, const double2 *__restrict__ logtab, const double2 *__restrict__ tab)
 {
     if (p.grey) return grey_rate_per_atom(flux, cd_in, cd_out, vol_nhi, p);
-    return rate_value(rate_issue(flux, cd_in, cd_out, vol_nhi, p, logtab));
+    return rate_value(rate_issue(flux, cd_in, cd_out, vol_nhi, p, logtab, tab));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -209,16 +210,20 @@ extern "C" __device__ double asora_buffer_atomic_fadd_f64(double, __amdgpu_buffe
 //   sub-box sweep                  {256,512} x 256                                 f    f    f/t  f         f    t       1|2  t        launch_subbox_tables_variant
 //   descriptors per layout (SPLIT) paired {256x32, 256x64, 256x256, 512x256}; single {256,512}x256            f    f    f/t  f/t       f/t  t       1|2  f        launch_variant_pairs / _split
 //   (SKIP_ZERO with HEAT or GREY, NSRC = 2 with HEAT, DUMP, GREY or global atomics, SUBBOX with NSRC = 2 and HEAT: not built)
+// SPEC: the kernel reads the table set of its source(s) (RtParams::src_spec; a scalar load and a scalar multiply-add per source).
+// Every form is built with it, at no VGPR; only the paired SPLIT family tips from 128 to 129 VGPRs (four waves per SIMD to three),
+// so that family alone is ALSO built without (SPEC = false) and launches without table sets take that form: launch_variant_pairs.
 // split descriptors: does this unit's face write the [k][j][i] twin?  (the z-sector with the twins in use)
 __device__ __forceinline__ bool ztr_desc(const RtParams &p, int uinfo) { return p.z_transposed != 0 && ((uinfo >> 8) & 3) == 3; }
 
 template <int RT_THREADS, bool GLOBAL_SCRATCH, bool DUMP, bool HEAT, int TABCAP, bool SKIP_ZERO = false, bool GREY = false,
-          bool BUFATOM = false, int NSRC = 1, bool SUBBOX = false, bool SPLIT = false>
+          bool BUFATOM = false, int NSRC = 1, bool SUBBOX = false, bool SPLIT = false, bool SPEC = true>
 __global__ void __launch_bounds__(RT_THREADS, 1) raytrace_octant_kernel(const RtParams p)
 {
     extern __shared__ double lds_raw[];
     static_assert(NSRC == 1 || (!GLOBAL_SCRATCH && !DUMP && BUFATOM), "paired sources: production variant only");
     static_assert(!SUBBOX || (!GLOBAL_SCRATCH && !DUMP && !SKIP_ZERO && !GREY), "sub-box sweep: table rates, shells in LDS");
+    static_assert(SPEC || (SPLIT && NSRC == 2), "the form without per-source table sets is kept for the paired SPLIT family only");
     static_assert(!SPLIT || (BUFATOM && !SUBBOX && !DUMP && (NSRC == 1 || (!HEAT && !GREY)) && !(SKIP_ZERO && (HEAT || GREY))),
                   "descriptors per layout: the production forms for 512 < N <= 645, and the single-source form with heating or grey opacity");
 
@@ -250,6 +255,9 @@ __global__ void __launch_bounds__(RT_THREADS, 1) raytrace_octant_kernel(const Rt
     int i0[NSRC], j0[NSRC], k0[NSRC];
     int loc[NSRC];            // SUBBOX: the source's index within the batch (activity, photon loss, trailing shell)
     double flux[NSRC];
+    // the rate tables of each source: its table set's block (asora_spectra_to_device).  Workgroup-uniform like the source itself:
+    // a scalar offset on a kernel argument, read where the position and the flux are read, by the same index
+    const double2 *tab[NSRC];
     bool have[NSRC];
     unsigned nreal = 0;
     int2 listed_pair = {0, -1};
@@ -272,6 +280,8 @@ __global__ void __launch_bounds__(RT_THREADS, 1) raytrace_octant_kernel(const Rt
         j0[q] = p.src_pos[3 * ns + 1];
         k0[q] = p.src_pos[3 * ns + 2];
         flux[q] = p.src_flux[(SUBBOX && p.flux_src >= 0) ? p.flux_src : ns];
+        tab[q] = p.tables;
+        if (SPEC && !GREY && !SUBBOX && p.src_spec) tab[q] += (size_t)p.src_spec[ns] * p.spec_stride;
         nreal += have[q] ? 1u : 0u;
     }
     if (SUBBOX && nreal == 0) return;
@@ -385,9 +395,9 @@ __global__ void __launch_bounds__(RT_THREADS, 1) raytrace_octant_kernel(const Rt
             src_cell_eval += have[q] ? 1u : 0u;
             if ((uinfo & 64) && have[q]) {                 // the source cell is rated by exactly one unit
                 if (DUMP) p.dump[idx] = cd_out;
-                const double phi = photo_rate_per_atom(flux[q], 0.0, cd_out, dr * dr * dr * nHI, p, logtab);
+                const double phi = photo_rate_per_atom(flux[q], 0.0, cd_out, dr * dr * dr * nHI, p, logtab, tab[q]);
                 unsafeAtomicAdd(&p.phi[idx], phi);
-                if (HEAT && !p.grey) unsafeAtomicAdd(&p.heat[idx], heat_rate_per_atom(flux[q], 0.0, cd_out, dr * dr * dr * nHI, p, logtab));
+                if (HEAT && !p.grey) unsafeAtomicAdd(&p.heat[idx], heat_rate_per_atom(flux[q], 0.0, cd_out, dr * dr * dr * nHI, p, logtab, tab[q]));
                 src_cell_gamma += 1;
             }
         }
@@ -569,7 +579,6 @@ __global__ void __launch_bounds__(RT_THREADS, 1) raytrace_octant_kernel(const Rt
             // (lanes without a rate run the lookups on whatever they hold: the index is clamped for any input)
             // TAU_PHOTO_LIMIT: rates.cu:7 (double 1e-7) or photorates.f90:69 (single 1e-7 promoted)
             const double limit = p.fortran_consts ? (double)1.0e-7f : 1.0e-7;
-            const double2 *tab = p.tables;
             bool thick[NSRC];
             double dtau[NSRC], arg_A[NSRC], arg_B[NSRC], tau_at_entry[NSRC];
             int toff[NSRC];
@@ -640,14 +649,14 @@ __global__ void __launch_bounds__(RT_THREADS, 1) raytrace_octant_kernel(const Rt
                     for (int q = 0; q < NSRC; ++q) {
                         // (nHI = 0 -- a fully ionised or empty cell: the reference divides by zero; flux / +0 = flux * inf)
                         pref[q] = vol_nhi[q] == 0.0 ? flux[q] * INFINITY : div_newton(flux[q], vol_nhi[q]);
-                        A2[q] = lookup_issue<HEAT>(tab, arg_A[q], p, logtab, toff[q]);
-                        B2[q] = lookup_issue<HEAT>(tab, arg_B[q], p, logtab, SUBBOX ? 0 : toff[q]);
+                        A2[q] = lookup_issue<HEAT>(tab[q], arg_A[q], p, logtab, toff[q]);
+                        B2[q] = lookup_issue<HEAT>(tab[q], arg_B[q], p, logtab, SUBBOX ? 0 : toff[q]);
                     }
                 }
                 else if (BUFATOM && SKIP_ZERO) {
 #pragma unroll
                     for (int q = 0; q < NSRC; ++q) {     // (distinct addresses, or the loads would be merged)
-                        const double2 *__restrict__ dummy = tab + (threadIdx.x & 1) + 4 * q;
+                        const double2 *__restrict__ dummy = tab[q] + (threadIdx.x & 1) + 4 * q;
                         A2[q].t = dummy[0]; A2[q].residual = 0.0;
                         B2[q].t = dummy[2]; B2[q].residual = 0.0;
                         if (HEAT) { A2[q].h = dummy[2 * p.table_len]; B2[q].h = dummy[2 * p.table_len + 2]; }
@@ -721,7 +730,7 @@ __global__ void __launch_bounds__(RT_THREADS, 1) raytrace_octant_kernel(const Rt
     // for its nHI and its predecessor's lookups as if nothing else were in flight.
     if (!GREY) {
         __builtin_amdgcn_sched_barrier(0);          // behind the nHI load, as in a step
-        const double2 *__restrict__ prime = p.tables + (threadIdx.x & 1);
+        const double2 *__restrict__ prime = tab[0] + (threadIdx.x & 1);
 #pragma unroll
         for (int q = 0; q < NSRC; ++q) {
             // (distinct addresses, or the loads would be merged; a further source's come from the 128-entry log table)
@@ -926,17 +935,23 @@ constexpr size_t lds_table_bytes(int tabcap, int nsrc = 1) { return LOG_TABLE_SI
 template <int T, int TABCAP, bool SPLIT = false>
 static int launch_variant_pairs(State &st, const RtParams &q, unsigned grid, size_t lds_bytes, hipStream_t stream, bool skip_zero)
 {
-    if (skip_zero) {
-        ASORA_HIP_TRY(hipFuncSetAttribute((const void *)raytrace_octant_kernel<T, false, false, false, TABCAP, true, false, true, 2, false, SPLIT>,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        hipLaunchKernelGGL((raytrace_octant_kernel<T, false, false, false, TABCAP, true, false, true, 2, false, SPLIT>), dim3(grid), dim3(T),
-                           lds_bytes, stream, q);
-    } else {
-        ASORA_HIP_TRY(hipFuncSetAttribute((const void *)raytrace_octant_kernel<T, false, false, false, TABCAP, false, false, true, 2, false, SPLIT>,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        hipLaunchKernelGGL((raytrace_octant_kernel<T, false, false, false, TABCAP, false, false, true, 2, false, SPLIT>), dim3(grid), dim3(T),
-                           lds_bytes, stream, q);
+#define ASORA_LAUNCH_PAIRS(SZ, SP)                                                                                                          \
+    do {                                                                                                                                \
+        ASORA_HIP_TRY(hipFuncSetAttribute((const void *)raytrace_octant_kernel<T, false, false, false, TABCAP, SZ, false, true, 2, false, SPLIT, SP>, \
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));                                 \
+        hipLaunchKernelGGL((raytrace_octant_kernel<T, false, false, false, TABCAP, SZ, false, true, 2, false, SPLIT, SP>), dim3(grid), dim3(T), \
+                           lds_bytes, stream, q);                                                                                       \
+    } while (0)
+    // (SPLIT without table sets per source: the form that does not read them -- see the kernel's SPEC)
+    if constexpr (SPLIT) {
+        if (!q.src_spec) {
+            if (skip_zero) ASORA_LAUNCH_PAIRS(true, false); else ASORA_LAUNCH_PAIRS(false, false);
+            ASORA_HIP_TRY(hipGetLastError());
+            return 0;
+        }
     }
+    if (skip_zero) ASORA_LAUNCH_PAIRS(true, true); else ASORA_LAUNCH_PAIRS(false, true);
+#undef ASORA_LAUNCH_PAIRS
     ASORA_HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1058,6 +1073,8 @@ bool note_call_radius(State &st, double R, int path)
 
 int launch_raytrace(State &st, RtParams &p, bool dump, bool heat, hipStream_t side)
 {
+    // (per-source spectra: checked by the entry points already; here so that no launch can carry an unchecked index)
+    if (p.src_spec) { if (int rc = check_source_spectra("raytrace")) return rc; }
     int units, threads;   // one workgroup per (source, octant) or per (source, octant, sector)
     pick_launch_shape(st, p.R, p.N, p.shape_src_count > 0 ? p.shape_src_count : p.src_count, dump, units, threads);
     {   // number of shells, known before the tables are built: the 1024-entry LDS tables exist for 256/512 threads

@@ -22,7 +22,7 @@ int require_raytrace_inputs(const char *who, double R, int NumTau, bool density,
     if (!st.opt[ASORA_OPT_GREY_NOTABLES] && !st.tables) return fail(4, w + "radiation tables not on device (photo_table_to_device)");
     if (!(R >= 0.0)) return fail(4, w + "R must be >= 0");
     if (NumTau < 1 && !st.opt[ASORA_OPT_GREY_NOTABLES]) return fail(4, w + "NumTau must be >= 1");
-    return 0;
+    return check_source_spectra(who);
 }
 
 static int check_rt_sources(int src_begin, int src_count)
@@ -51,7 +51,9 @@ void fill_rt_params(RtParams &p, double R, double sig, double dr, double minlogt
     p.phi = st.grid[ASORA_GRID_PHI_ION];
     p.tables = st.tables;
     p.heat = st.grid[ASORA_GRID_PHI_HEAT];
-    p.src_pos = st.src_pos; p.src_flux = st.src_flux;
+    // (per-source spectra: the two fields every entry point built on this block inherits)
+    p.spec_stride = (unsigned)st.spec_stride;
+    use_source_list(p, st, false);
     p.counters = st.counters;
     p.radius_stays = note_call_radius(st, R, radius_path) ? 1 : 0;
 }
@@ -107,9 +109,8 @@ static int rt_range(int src_begin, int src_count)
     if (int rc = check_rt_sources(src_begin, src_count)) return rc;
     if (src_count == 0) return 0;
     RtParams p = st.rt_params;
-    p.src_pos = st.src_pos; p.src_flux = st.src_flux;
     // the whole list: in the spatially ordered copy (a column-density dump is of the caller's LAST source: caller's order)
-    if (src_begin == 0 && src_count == st.num_src && st.src_pos_sorted && !p.dump) { p.src_pos = st.src_pos_sorted; p.src_flux = st.src_flux_sorted; }
+    use_source_list(p, st, src_begin == 0 && src_count == st.num_src && st.src_pos_sorted && !p.dump);
     p.src_begin = src_begin; p.src_count = src_count;
     // one launch shape (one set of geometry tables) per call: a call that traces its sources in several ranges (pipelined
     // all-reduce, chunked slab exchange) is sized by all of the rank's sources
@@ -234,7 +235,7 @@ static int do_all_sources_pipelined(double R, double sig, double dr, const doubl
     if (int rc = reset_counters()) return rc;
     RtParams base;
     fill_rt_params(base, R, sig, dr, minlogtau, dlogtau, NumTau);
-    base.src_pos = st.src_pos_sorted; base.src_flux = st.src_flux_sorted;
+    use_source_list(base, st, true);
     base.shape_src_count = NumSrc;
     st.rt_open = false;
     // the copy streams start behind whatever the main stream has done so far (earlier calls may still own the grids)

@@ -24,6 +24,15 @@ struct SubboxCall {
     double *dump;                   // N^3 grid receiving the column densities of the last source, or nullptr
 };
 
+// The sub-box semantics rate every source with the flux of the call's last one (f90:500,503): there is no meaningful spectrum
+// per source, so the calls fail while the uploaded sources carry table sets of their own.
+static int refuse_source_spectra(const char *who)
+{
+    if (!state().src_spec) return 0;
+    return fail(4, std::string(who) + ": the sub-box raytracer has one spectrum for all sources, and the sources on the device "
+                                      "carry table sets of their own (source_spectra_to_device); use raytrace_device / evolve3D");
+}
+
 static int subbox_core(const SubboxCall &c, long long &total_nbox, double &total_loss)
 {
     State &st = state();
@@ -80,6 +89,7 @@ static int subbox_core(const SubboxCall &c, long long &total_nbox, double &total
     tp.fortran_consts = 1; tp.grey = grey ? 1 : 0; tp.z_transposed = 1;
     tp.logtab = st.logtab_dev;
     tp.src_pos = c.src_pos; tp.src_flux = c.src_flux;
+    tp.src_spec = nullptr;                // (one spectrum: the entry points refuse sources with table sets of their own)
     tp.flux_src = p.flux_src;
     const bool has_dump = c.dump != nullptr;
     SubboxTables tab;
@@ -224,6 +234,7 @@ int c2ray_do_all_sources(const double *normflux, const int32_t *srcpos, int max_
     const bool grey = st.opt[ASORA_OPT_GREY_NOTABLES] != 0;
     if (!grey && (NumTau < 1 || !photo_thin_table || !photo_thick_table))
         return fail(3, std::string(who) + ": empty photo-ionisation tables");
+    if (int rc = refuse_source_spectra(who)) return rc;
     // Heating tables that are identically zero (what the reference's evolve3D passes, pyc2ray/evolve.py:193: "eventually
     // we'll add heating tables here") add exactly 0 to phi_heat: the grid is then neither uploaded, nor rated, nor
     // downloaded -- two 128 MiB transfers at 256^3 and the slower kernel variant for nothing.
@@ -321,6 +332,7 @@ int asora_subbox_raytrace_device(int max_subbox, int subboxsize, float loss_frac
     const bool grey = st.opt[ASORA_OPT_GREY_NOTABLES] != 0;
     if (!grey && (!st.tables || NumTau < 1)) return fail(4, std::string(who) + ": radiation tables not on device");
     if (int rc = check_sources(who, 4, "source range outside the uploaded sources", src_begin, src_count)) return rc;
+    if (int rc = refuse_source_spectra(who)) return rc;
     const bool heat = !grey && st.opt[ASORA_OPT_HEATING] != 0;
     if (heat && !st.have_heat_tables) return fail(4, std::string(who) + ": heating requested but no heating tables on device");
     SubboxCall c;

@@ -530,15 +530,18 @@ class TorchComm:
 
     # -- slab exchange: rates to the owners of the planes, ionised fraction back (see SlabPlan) -------------------
     @staticmethod
-    def shard_sources_by_slab(src_pos, src_flux, nprocs):
+    def shard_sources_by_slab(src_pos, src_flux, nprocs, src_spectrum=None):
         """Order the source list by its first coordinate and cut it into the reference's contiguous blocks
         (pyc2ray/evolve.py:362-367: perrank = NumSrc // nprocs, the last rank takes the remainder).  Returns
-        (src_pos, src_flux, bounds) with rank r holding [bounds[r], bounds[r+1]) of the reordered list."""
+        (src_pos, src_flux, bounds) with rank r holding [bounds[r], bounds[r+1]) of the reordered list; with `src_spectrum`
+        (the spectrum of each source) a fourth element, reordered like the other two."""
         pos, flux = np.asarray(src_pos), np.asarray(src_flux)
         order = np.argsort(pos[0], kind="stable")
         n = flux.shape[0]
         per = n // nprocs
         bounds = [r * per for r in range(nprocs)] + [n]
+        if src_spectrum is not None:
+            return pos[:, order], flux[order], bounds, np.asarray(src_spectrum)[order]
         return pos[:, order], flux[order], bounds
 
     def _planes_view(self, libasora, which, N):
@@ -862,11 +865,13 @@ class TorchComm:
 
     # -- raytrace + sum over ranks, optionally pipelined ------------------------------------------------
     @staticmethod
-    def sort_sources_for_overlap(src_pos, src_flux):
+    def sort_sources_for_overlap(src_pos, src_flux, src_spectrum=None):
         """Order a rank's sources by their first coordinate (what the pipelined path needs).  src_pos is
-        (3, n) 1-based; returns (src_pos, src_flux) reordered.  The sum over sources is order-independent
-        up to floating-point rounding."""
+        (3, n) 1-based; returns (src_pos, src_flux) reordered -- and `src_spectrum`, the spectrum of each source, when
+        given.  The sum over sources is order-independent up to floating-point rounding."""
         order = np.argsort(np.asarray(src_pos)[0], kind="stable")
+        if src_spectrum is not None:
+            return np.asarray(src_pos)[:, order], np.asarray(src_flux)[order], np.asarray(src_spectrum)[order]
         return np.asarray(src_pos)[:, order], np.asarray(src_flux)[order]
 
     @staticmethod

@@ -19,6 +19,7 @@ import numpy as np
 from . import _capi, _residency
 from .asora_core import cuda_is_init
 from .load_extensions import load_asora, load_c2ray
+from .spectra import source_spectrum_spec
 from .utils import printlog
 from .utils.logutils import printlog_lines
 from .utils.sourceutils import format_sources
@@ -120,28 +121,28 @@ def _is_distributed(ranks):
     return bool(use_mpi) and comm is not None and nprocs > 1
 
 
-def _contiguous_shard(src_pos, src_flux, ranks):
+def _contiguous_shard(src_pos, src_flux, ranks, spec=None):
     """The sources that this rank traces (evolve.py:360-371): a contiguous block of NumSrc // nprocs of the list, the last rank to
-    the end; all of them when the step is not distributed."""
+    the end; all of them when the step is not distributed.  `spec` (their spectra, or None) is cut the same way."""
     _, _, rank, nprocs = ranks
     pos, NumSrc = np.asarray(src_pos), src_flux.shape[0]
     if not _is_distributed(ranks):
-        return pos, src_flux
+        return pos, src_flux, spec
     perrank = NumSrc // nprocs
     i_start = int(rank * perrank)
     i_end = int((rank + 1) * perrank) if rank != nprocs - 1 else NumSrc
-    return pos[:, i_start:i_end], src_flux[i_start:i_end]
+    return pos[:, i_start:i_end], src_flux[i_start:i_end], None if spec is None else spec[i_start:i_end]
 
 
 def _prologue(libasora, scalars, N, NumTau, src_flux, my_pos, my_flux, uploads, clump, *, ranks=_ONE_RANK,
-              calling="Calling evolve3D...", xh_copies=False, say_copied=False, clump_upload=True, tables=None):
+              calling="Calling evolve3D...", xh_copies=False, say_copied=False, clump_upload=True, tables=None, spec=None):
     """What every form of the step does before its loop: the convergence criterion, this rank's sources (`my_pos`, `my_flux`)
     and the grids of `uploads` ({grid selector: host array}) to the device, the clumping mode, and the header lines of
     evolve.py:156-162 on rank 0.  Returns the :class:`_Step`.  The forms differ in: `calling`, the first header line;
     `xh_copies`, xh_av = xh_intermed = xh made here (the one-GPU device loop makes its own); `say_copied`, the line of the
     reference's one-process GPU branch; `clump_upload=False`, a clumping grid is among `uploads` or on the device already;
     `tables` = (thin, thick), use_gpu=False: that branch has no device_init of its own in the reference, so the library sets itself
-    up for the mesh here."""
+    up for the mesh here; `spec`, the spectra of `my_pos` (None: all 0, nothing more is uploaded)."""
     NumSrc, n_local, NumCells = src_flux.shape[0], my_flux.shape[0], N * N * N
     logfile, quiet, rank = scalars["logfile"], scalars["quiet"], ranks[2]
     # evolve.py:127 (computed from the TOTAL source count, evolve.py:346)
@@ -156,6 +157,8 @@ def _prologue(libasora, scalars, N, NumTau, src_flux, my_pos, my_flux, uploads, 
     # Everything the step needs goes to the device once (evolve.py:136-155 keeps host copies instead)
     srcpos_flat, normflux_flat = format_sources(my_pos, my_flux)
     libasora.source_data_to_device(srcpos_flat, normflux_flat, n_local)
+    if spec is not None:
+        libasora.source_spectra_to_device(spec)
     for which, grid in uploads.items():
         libasora.grid_to_device(which, grid)
     if xh_copies:
@@ -442,7 +445,7 @@ def _scalars(dt, dr, R_max_LLS, convergence_fraction, sig, minlogtau, dlogtau, c
 
 def evolve3D_resident(dt, dr, src_flux, src_pos, uploads, N, photo_thin_table, minlogtau, dlogtau, R_max_LLS,
                       convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile="pyC2Ray.log", quiet=False,
-                      thermal=None, clumping=None):
+                      thermal=None, clumping=None, src_spectrum=None):
     """evolve3D for a caller that keeps the grids on the device between time steps (the C2Ray class with
     ``device_resident = True``): same loop, log lines and results as :func:`evolve3D` with ``use_gpu=True``, but only the
     grids in ``uploads`` ({grid selector: host array}, those the caller changed on the host) cross PCIe, and nothing
@@ -451,7 +454,9 @@ def evolve3D_resident(dt, dr, src_flux, src_pos, uploads, N, photo_thin_table, m
     With ``thermal`` (a :class:`pyc2ray_amd.thermal.ThermalParams`) the temperature is evolved as well: TEMP holds the
     end-of-step temperature afterwards, PHI_HEAT the heating rates.
     ``clumping`` as in :func:`evolve3D`; like the other grids, an (N, N, N) grid crosses PCIe only when ``uploads`` holds it
-    (under ``_capi.GRID_CLUMP``, checked then): otherwise GRID_CLUMP must still hold it from an earlier step."""
+    (under ``_capi.GRID_CLUMP``, checked then): otherwise GRID_CLUMP must still hold it from an earlier step.
+    ``src_spectrum`` as in :func:`evolve3D`."""
+    spec = source_spectrum_spec(src_spectrum, src_flux.shape[0], True, lambda: load_asora().num_spectra(), "evolve3D_resident")
     clump = _clumping_spec(clumping, N, check_values=_capi.GRID_CLUMP in uploads)
     if clump is not None and clump.grid is not None and _capi.GRID_CLUMP in uploads and uploads[_capi.GRID_CLUMP] is not clumping:
         raise ValueError("evolve3D_resident: uploads[GRID_CLUMP] and clumping must be the same grid")
@@ -460,13 +465,13 @@ def evolve3D_resident(dt, dr, src_flux, src_pos, uploads, N, photo_thin_table, m
     scalars = _scalars(dt, dr, R_max_LLS, convergence_fraction, sig, minlogtau, dlogtau, (bh00, albpow, colh0, temph0, abu_c),
                        logfile, quiet)
     with _clumping_reset(clump):
-        return _evolve_resident(scalars, src_flux, src_pos, uploads, N, photo_thin_table, thermal, clump)
+        return _evolve_resident(scalars, src_flux, src_pos, uploads, N, photo_thin_table, thermal, clump, spec)
 
 
-def _evolve_resident(scalars, src_flux, src_pos, uploads, N, photo_thin_table, thermal, clump):
+def _evolve_resident(scalars, src_flux, src_pos, uploads, N, photo_thin_table, thermal, clump, spec=None):
     libasora = load_asora()
     step = _prologue(libasora, scalars, N, photo_thin_table.shape[0], src_flux, np.asarray(src_pos), src_flux, uploads, clump,
-                     say_copied=True, clump_upload=False)
+                     say_copied=True, clump_upload=False, spec=spec)
     niter = _one_gpu_loop(libasora, step, thermal)
     printlog("Multiple source convergence reached.", step.logfile, step.quiet)
     libasora.grid_copy(_capi.GRID_XH, _capi.GRID_XH_INTERMED)       # the next step starts from the new ionised fraction
@@ -489,9 +494,10 @@ def _thermal_ranks_refusal(comm):
     return None
 
 
-def _evolve(scalars, src_flux, src_pos, grids, photo_thin_table, ranks=_ONE_RANK, thermal=None, clump=None):
+def _evolve(scalars, src_flux, src_pos, grids, photo_thin_table, ranks=_ONE_RANK, thermal=None, clump=None, spec=None):
     """A use_gpu=True step on host arrays, grids = (temp, ndens, xh), on one GPU or across `ranks`; `thermal` on one GPU, or
-    across ranks on the "slab" and "all-reduce" device loops."""
+    across ranks on the "slab" and "all-reduce" device loops; `spec`, the spectrum of each source of the whole list (None: all 0),
+    which follows its source through every re-ordering and sharding below."""
     if not cuda_is_init():
         raise RuntimeError("GPU not initialized. Please initialize it by calling device_init(N)")
     _residency.reclaim()              # this step overwrites device grids a resident C2Ray object may be relying on
@@ -511,19 +517,27 @@ def _evolve(scalars, src_flux, src_pos, grids, photo_thin_table, ranks=_ONE_RANK
         # the same contiguous blocks, of the list ordered by the first coordinate: a rank's rates then live on the
         # planes within R of its slab of sources, and only those planes are exchanged (pyc2ray_amd.dist.SlabPlan)
         from .dist import SlabPlan
-        all_pos, all_flux, bounds = comm.shard_sources_by_slab(np.asarray(src_pos), src_flux, nprocs)
+        if spec is None:
+            all_pos, all_flux, bounds = comm.shard_sources_by_slab(np.asarray(src_pos), src_flux, nprocs)
+            my_spec = None
+        else:
+            all_pos, all_flux, bounds, all_spec = comm.shard_sources_by_slab(np.asarray(src_pos), src_flux, nprocs, spec)
+            my_spec = all_spec[bounds[rank]:bounds[rank + 1]]
         my_pos, my_flux = all_pos[:, bounds[rank]:bounds[rank + 1]], all_flux[bounds[rank]:bounds[rank + 1]]
         plan = SlabPlan(N, nprocs, scalars["R_max_LLS"], [all_pos[0, bounds[r]:bounds[r + 1]] - 1 for r in range(nprocs)])
     else:
-        my_pos, my_flux = _contiguous_shard(src_pos, src_flux, ranks)
+        my_pos, my_flux, my_spec = _contiguous_shard(src_pos, src_flux, ranks, spec)
     if strategy == "pipelined":         # the shard is traced in order of the first coordinate
-        my_pos, my_flux = comm.sort_sources_for_overlap(my_pos, my_flux)
+        if my_spec is None:
+            my_pos, my_flux = comm.sort_sources_for_overlap(my_pos, my_flux)
+        else:
+            my_pos, my_flux, my_spec = comm.sort_sources_for_overlap(my_pos, my_flux, my_spec)
         src_i0 = np.asarray(my_pos[0]).astype(np.int64) - 1
 
     step = _prologue(libasora, scalars, N, photo_thin_table.shape[0], src_flux, my_pos, my_flux,
                      {_capi.GRID_NDENS: ndens, _capi.GRID_TEMP: temp, _capi.GRID_XH: xh}, clump, ranks=ranks,
                      calling=f"Calling evolve3D with {nprocs:n} MPI-processors..." if distributed else "Calling evolve3D...",
-                     xh_copies=distributed, say_copied=not distributed)
+                     xh_copies=distributed, say_copied=not distributed, spec=my_spec)
     if strategy == "one GPU":
         niter = _one_gpu_loop(libasora, step, thermal)
     elif strategy == "slab":
@@ -565,7 +579,7 @@ def _evolve_cpu_semantics(scalars, src_flux, src_pos, grids, tables, subbox, ran
     libasora = load_asora()
     temp, ndens, xh = grids
     N = temp.shape[0]
-    my_pos, my_flux = _contiguous_shard(src_pos, src_flux, ranks)
+    my_pos, my_flux, _ = _contiguous_shard(src_pos, src_flux, ranks)
     step = _prologue(libasora, scalars, N, tables[0].shape[0], src_flux, my_pos, my_flux,
                      {_capi.GRID_NDENS: ndens, _capi.GRID_TEMP: temp, _capi.GRID_XH: xh}, clump,
                      ranks=ranks, xh_copies=True, tables=tables)
@@ -587,7 +601,7 @@ def evolve3D(dt, dr,
              minlogtau, dlogtau,
              R_max_LLS, convergence_fraction,
              sig, bh00, albpow, colh0, temph0, abu_c,
-             logfile="pyC2Ray.log", quiet=False, *, thermal=None, clumping=None):
+             logfile="pyC2Ray.log", quiet=False, *, thermal=None, clumping=None, src_spectrum=None):
     """Evolve the ionised fraction of the whole grid over one time step.
 
     Parameters have the reference's meaning (pyc2ray/evolve.py:49-109): dt [s], dr [cm],
@@ -610,7 +624,13 @@ def evolve3D(dt, dr,
     1.0 (off, the reference's behaviour), a float > 0 for the whole grid, or an (N, N, N) float64 grid (C or Fortran order) of
     factors > 0.  Anything else raises ValueError before any GPU work.  Works with use_gpu=False and with `thermal` (then the
     recombination cooling is clumped as well).
+
+    src_spectrum : which of the table sets on the device (``spectra_to_device``) each source shines with:
+    None or all zeros (the reference's one spectrum: nothing more is uploaded), or an integer array of length numsrc with values
+    in [0, num_spectra()).  Anything else, or a non-zero entry with use_gpu=False, raises ValueError before any GPU work.  With
+    `thermal` the heating tables of every set must have gone up with ``spectra_to_device``.
     """
+    spec = source_spectrum_spec(src_spectrum, src_flux.shape[0], use_gpu, lambda: load_asora().num_spectra(), "evolve3D")
     clump = _clumping_spec(clumping, np.shape(temp)[0])
     if not use_gpu and thermal is not None:
         raise ValueError("evolve3D: the thermal mode needs use_gpu=True (the use_gpu=False raytracer has no thermal form)")
@@ -618,7 +638,7 @@ def evolve3D(dt, dr,
                        logfile, quiet)
     with _clumping_reset(clump):
         if use_gpu:
-            return _evolve(scalars, src_flux, src_pos, (temp, ndens, xh), photo_thin_table, thermal=thermal, clump=clump)
+            return _evolve(scalars, src_flux, src_pos, (temp, ndens, xh), photo_thin_table, thermal=thermal, clump=clump, spec=spec)
         return _evolve_cpu_semantics(scalars, src_flux, src_pos, (temp, ndens, xh), (photo_thin_table, photo_thick_table),
                                      (max_subbox, subboxsize, loss_fraction), clump=clump)
 
@@ -632,7 +652,7 @@ def evolve3D_MPI(dt, dr,
                  minlogtau, dlogtau,
                  R_max_LLS, convergence_fraction,
                  sig, bh00, albpow, colh0, temph0, abu_c,
-                 logfile="pyC2Ray.log", quiet=False, *, thermal=None, clumping=None):
+                 logfile="pyC2Ray.log", quiet=False, *, thermal=None, clumping=None, src_spectrum=None):
     """Source-sharded variant (pyc2ray/evolve.py:249-498): rank r traces the contiguous block
     [r*(Ns//nprocs), (r+1)*(Ns//nprocs)) of the source list, the last rank to the end
     (evolve.py:362-367); the per-rank rate grids are summed across ranks each iteration.
@@ -650,7 +670,9 @@ def evolve3D_MPI(dt, dr,
     rates.  With any other communicator (None, mpi4py) the thermal mode is single-GPU only and a ValueError says so before any GPU
     work; use_gpu=False has no thermal form.
     ``clumping`` as in :func:`evolve3D`; every rank passes (and uploads) the whole grid, as it does ``ndens``.
+    ``src_spectrum`` as in :func:`evolve3D`, for the whole source list; a rank's shard of the sources takes its shard of it.
     """
+    spec = source_spectrum_spec(src_spectrum, src_flux.shape[0], use_gpu, lambda: load_asora().num_spectra(), "evolve3D_MPI")
     if thermal is not None:
         if not use_gpu:
             raise ValueError("evolve3D_MPI: the thermal mode needs use_gpu=True (the use_gpu=False raytracer has no thermal form)")
@@ -664,6 +686,7 @@ def evolve3D_MPI(dt, dr,
     ranks = (use_mpi, comm, rank, nprocs)
     with _clumping_reset(clump):
         if use_gpu:
-            return _evolve(scalars, src_flux, src_pos, (temp, ndens, xh), photo_thin_table, ranks, thermal=thermal, clump=clump)
+            return _evolve(scalars, src_flux, src_pos, (temp, ndens, xh), photo_thin_table, ranks, thermal=thermal, clump=clump,
+                           spec=spec)
         return _evolve_cpu_semantics(scalars, src_flux, src_pos, (temp, ndens, xh), (photo_thin_table, photo_thick_table),
                                      (max_subbox, subboxsize, loss_fraction), ranks, clump=clump)

@@ -95,6 +95,58 @@ class _LibAsora:
         _capi.check(self._lib.asora_source_data_to_device(_capi.iptr(p), _capi.dptr(f), int(NumSrc)),
                     "source_data_to_device")
 
+    # ---- per-source spectra (extension; include/asora_hip.h) -------------------------------------
+    def spectra_to_device(self, photo_thin, photo_thick, heat_thin=None, heat_thick=None):
+        """K table sets at once: (K, NumTau) float64 arrays, set k for the sources of spectrum k
+        (:meth:`source_spectra_to_device`).  The heating tables come both or not at all."""
+        t = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in (photo_thin, photo_thick, heat_thin, heat_thick)]
+        if t[0] is None or t[1] is None or t[0].ndim != 2:
+            raise ValueError("spectra_to_device: the photo tables must be 2-D, (K, NumTau)")
+        K, NumTau = t[0].shape
+        if not 1 <= K <= _capi.MAX_SPECTRA or NumTau < 1:
+            raise ValueError(f"spectra_to_device: {K} spectra of {NumTau} entries; 1 to {_capi.MAX_SPECTRA} spectra of >= 1 entries")
+        if (t[2] is None) != (t[3] is None):
+            raise ValueError("spectra_to_device: one heating table without the other")
+        for a, name in zip(t, ("photo_thin", "photo_thick", "heat_thin", "heat_thick")):
+            if a is not None and a.shape != (K, NumTau):
+                raise ValueError(f"spectra_to_device: {name} has shape {a.shape}, expected {(K, NumTau)}")
+        _capi.check(self._lib.asora_spectra_to_device(K, NumTau, _capi.dptr(t[0]), _capi.dptr(t[1]),
+                                                      None if t[2] is None else _capi.dptr(t[2]),
+                                                      None if t[3] is None else _capi.dptr(t[3])), "spectra_to_device")
+
+    def source_spectra_to_device(self, spec):
+        """The table set of each source of the last source_data_to_device (which resets them all to 0); None: all 0."""
+        if spec is None:
+            _capi.check(self._lib.asora_source_spectra_to_device(None, 0), "source_spectra_to_device")
+            return
+        s = np.asarray(spec)
+        if s.ndim != 1 or s.dtype.kind not in "iu":
+            raise ValueError("source_spectra_to_device: a 1-D integer array, one table set per source")
+        s = np.ascontiguousarray(s, dtype=np.int32)
+        _capi.check(self._lib.asora_source_spectra_to_device(_capi.iptr(s), int(s.size)), "source_spectra_to_device")
+
+    def num_spectra(self):
+        """Table sets on the device (0: none uploaded)."""
+        return int(self._lib.asora_num_spectra())
+
+    def sort_sources(self, pos, flux, spec=None):
+        """The position-ordered copy of a source list as source_data_to_device forms it (host only, no device needed):
+        (pos, flux, spec) reordered, `pos` flat int32 xyz-interleaved as format_sources makes it."""
+        p = np.ascontiguousarray(pos, dtype=np.int32).ravel()
+        f = np.ascontiguousarray(flux, dtype=np.float64)
+        n = int(f.size)
+        if p.size != 3 * n:
+            raise ValueError("sort_sources: 3 coordinates per source")
+        s = None if spec is None else np.ascontiguousarray(spec, dtype=np.int32)
+        if s is not None and s.size != n:
+            raise ValueError("sort_sources: one table set per source")
+        po, fo = np.empty_like(p), np.empty_like(f)
+        so = None if s is None else np.empty_like(s)
+        _capi.check(self._lib.asora_debug_sort_sources(_capi.iptr(p), _capi.dptr(f), None if s is None else _capi.iptr(s), n,
+                                                       _capi.iptr(po), _capi.dptr(fo), None if so is None else _capi.iptr(so)),
+                    "sort_sources")
+        return po, fo, so
+
     def do_all_sources(self, R, coldensh_out, sig, dr, ndens, xh_av, phi_ion, NumSrc, m1,
                        minlogtau, dlogtau, NumTau):
         n = int(m1) ** 3

@@ -6,6 +6,7 @@ import numpy as np
 from . import _capi, _residency
 from .asora_core import cuda_is_init
 from .load_extensions import load_asora, load_c2ray
+from .spectra import source_spectrum_spec
 from .utils import printlog
 from .utils.sourceutils import format_sources
 
@@ -21,7 +22,7 @@ def do_raytracing(dr,
                   minlogtau, dlogtau,
                   R_max_LLS,
                   sig,
-                  logfile="pyC2Ray.log", quiet=False, stats=False):
+                  logfile="pyC2Ray.log", quiet=False, stats=False, src_spectrum=None):
     """Raytrace all sources once and return the photo-ionisation rate grid.
 
     Same 17 positional arguments as the reference (pyc2ray/raytracing.py:34-43).  Returns
@@ -34,7 +35,12 @@ def do_raytracing(dr,
     until the photon loss is below loss_fraction, raytracing.py:89-95) -- evaluated on the GPU through
     ``libc2ray.raytracing.do_all_sources``: returns ``(phi_ion, phi_heat)`` in Fortran order, or
     ``(phi_ion, nsubbox, photonloss)`` with ``stats=True`` (raytracing.py:105-108).
+
+    ``src_spectrum``: as in :func:`pyc2ray_amd.evolve3D` -- which table set on the device (``spectra_to_device``) each source
+    shines with.  With several sets on the device the heating tables went up with them: heat_*_table only say whether the heating
+    rate is wanted.
     """
+    spec = source_spectrum_spec(src_spectrum, src_flux.shape[0], use_gpu, lambda: load_asora().num_spectra(), "do_raytracing")
     if use_gpu and not cuda_is_init():
         raise RuntimeError("GPU not initialized. Please initialize it by calling device_init(N)")
     _residency.reclaim()              # this call overwrites device grids a resident C2Ray object may be relying on
@@ -65,6 +71,8 @@ def do_raytracing(dr,
     libasora = load_asora()
     srcpos_flat, normflux_flat = format_sources(src_pos, src_flux)
     libasora.source_data_to_device(srcpos_flat, normflux_flat, NumSrc)
+    if spec is not None:
+        libasora.source_spectra_to_device(spec)
     libasora.grid_to_device(_capi.GRID_NDENS, ndens)
     libasora.grid_to_device(_capi.GRID_XH_AV, xh_av)
     # the reference prints the means before the copies (raytracing.py:72-76); here they are summed on the device
@@ -76,7 +84,7 @@ def do_raytracing(dr,
     # compute_heating_rates is off, c2ray_base.py:430-431)
     want_heat = (heat_thin_table is not None and heat_thick_table is not None
                  and (np.any(heat_thin_table) or np.any(heat_thick_table)))
-    if want_heat:
+    if want_heat and libasora.num_spectra() <= 1:
         libasora.heat_table_to_device(heat_thin_table, heat_thick_table, NumTau)
     libasora.set_option(_capi.OPT_HEATING, 1 if want_heat else 0)
 

@@ -59,9 +59,12 @@ class ThermalParams:
         return 0.0 if self.zred is None else float(self.tcmb0) * (1.0 + float(self.zred))
 
     def apply(self, libasora):
-        """Upload the heating tables and switch the library to the thermal form (photo tables must be on the device)."""
-        thin = np.ascontiguousarray(self.heat_thin_table, dtype=np.float64)
-        thick = np.ascontiguousarray(self.heat_thick_table, dtype=np.float64)
-        libasora.heat_table_to_device(thin, thick, thin.shape[0])
+        """Upload the heating tables and switch the library to the thermal form (photo tables must be on the device).  With
+        several table sets on the device (spectra_to_device) the heating tables of every set went up with them and stay as they
+        are: heat_thin_table / heat_thick_table are not used then."""
+        if getattr(libasora, "num_spectra", lambda: 1)() <= 1:
+            thin = np.ascontiguousarray(self.heat_thin_table, dtype=np.float64)
+            thick = np.ascontiguousarray(self.heat_thick_table, dtype=np.float64)
+            libasora.heat_table_to_device(thin, thick, thin.shape[0])
         libasora.thermal_params(True, self.relative_denergy, self.t_floor, self.max_substeps, int(self.cooling),
                                 self.zred is not None, self.t_cmb)
