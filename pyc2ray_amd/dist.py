@@ -16,9 +16,14 @@ planes the last chunks touch are summed after the trace.
 (Get_rank, Get_size, Reduce, Bcast, Allreduce, Barrier), and ``MPI`` the constants it reads, so
 reference-style driver code can pass ``use_mpi=dist.MPI, comm=dist.TorchComm()``.
 """
+import collections
+import contextlib
 import os
+import time
 
 import numpy as np
+
+from . import _capi
 
 __all__ = ["MPI", "TorchComm", "SlabPlan", "init_process_group_from_env"]
 
@@ -62,7 +67,6 @@ def init_process_group_from_env(backend=None):
         timeout = datetime.timedelta(seconds=float(os.environ.get("PYC2RAY_AMD_DIST_TIMEOUT_S", "300")))
         dist.init_process_group(backend=backend, rank=rank, world_size=world, timeout=timeout)
     return rank, world, local_rank
-
 
 
 def _runs_of(mask):
@@ -131,6 +135,8 @@ class SlabPlan:
                     else:
                         merged.append((s0, s1))
                 self.runs[r][q] = [(a + s0, a + s1) for s0, s1 in merged]
+        # memos of the schedules below: an iteration must not pay for them again
+        self._send_cache, self._recv_cache, self._work_cache, self._back_cache = {}, {}, {}, {}
 
     def _reach_of(self, i0):
         """Planes the sources at first coordinates i0 can rate."""
@@ -161,10 +167,9 @@ class SlabPlan:
         0..c -- the planes no later chunk reaches, not sent before; the last chunk sends everything that is left.  Every
         plane of every run is sent exactly once.  (Memoised: an iteration must not pay for this again.)"""
         K = max(1, int(K))
-        cache = self.__dict__.setdefault("_send_cache", {})
-        if (r, K) not in cache:
-            cache[(r, K)] = self._send_schedule(r, K)
-        return cache[(r, K)]
+        if (r, K) not in self._send_cache:
+            self._send_cache[(r, K)] = self._send_schedule(r, K)
+        return self._send_cache[(r, K)]
 
     def _send_schedule(self, r, K):
         n = self.i0[r].size
@@ -187,10 +192,9 @@ class SlabPlan:
 
     def recv_schedule(self, q, K):
         """rsched[c] = [(r, a, b), ...]: what the other ranks send to q after their chunk c (rank order).  Memoised."""
-        cache = self.__dict__.setdefault("_recv_cache", {})
-        if (q, int(K)) not in cache:
-            cache[(q, int(K))] = self._recv_schedule(q, K)
-        return cache[(q, int(K))]
+        if (q, int(K)) not in self._recv_cache:
+            self._recv_cache[(q, int(K))] = self._recv_schedule(q, K)
+        return self._recv_cache[(q, int(K))]
 
     def _recv_schedule(self, q, K):
         out = [[] for _ in range(max(1, int(K)))]
@@ -203,13 +207,21 @@ class SlabPlan:
 
     def work_runs(self, r):
         """Planes rank r zeroes its accumulators on and forms nHI on: what its sources reach plus what it owns.  Memoised."""
-        cache = self.__dict__.setdefault("_work_cache", {})
-        if r not in cache:
+        if r not in self._work_cache:
             mask = self.reach[r].copy()
             a, b = self.own[r]
             mask[a:b] = True
-            cache[r] = _runs_of(mask)
-        return cache[r]
+            self._work_cache[r] = _runs_of(mask)
+        return self._work_cache[r]
+
+    def back_runs(self, r):
+        """(sends, recvs) of rank r in the second exchange, each [(peer, a, b), ...] in rank order: the runs travel back -- r, as
+        the owner, sends the new xh_av of runs[q][r] to every q that traces through them, and expects runs[r][q] from its owner q.
+        Memoised."""
+        if r not in self._back_cache:
+            self._back_cache[r] = ([(q, a, b) for q in range(self.P) if q != r for a, b in self.runs[q][r]],
+                                   [(q, a, b) for q in range(self.P) if q != r for a, b in self.runs[r][q]])
+        return self._back_cache[r]
 
     def reach_runs(self, r):
         return _runs_of(self.reach[r])
@@ -246,6 +258,183 @@ class _DevicePointer:
         }
 
 
+#: A grid that travels between ranks, as the NAMES of the library methods that reach it; `add`, `add_host` where planes that arrive
+#: are ADDED instead of replacing what is there.  `args` go in front of the first three calls (the selector of a library grid).
+_Field = collections.namedtuple("_Field", "ptr to_host from_host add add_host args", defaults=(None, None, ()))
+
+#: the out-boxes of the device-resident loop; a thermal step sends both, per run of planes the rates first
+_RATES = _Field("evolve_slab_outbox_ptr", "evolve_slab_outbox_to_host", "evolve_slab_outbox_from_host",
+                "evolve_slab_add", "evolve_slab_add_host")
+_HEAT = _Field("evolve_slab_heat_outbox_ptr", "evolve_slab_heat_outbox_to_host", "evolve_slab_heat_outbox_from_host",
+               "evolve_slab_add_heat", "evolve_slab_add_heat_host")
+
+
+def _grid(which):
+    """The library grid `which`; planes that arrive replace what is there."""
+    return _Field("device_ptr", "planes_to_host", "planes_to_device", args=(int(which),))
+
+
+def _call(lib, name, *args):
+    return getattr(lib, name)(*args)
+
+
+class _Rccl:
+    """RCCL ("nccl"): the library's buffers are zero-copy views and everything is ordered on the library's stream -- sends start
+    behind the kernels that produced the planes, the stream waits for a transfer, never the host."""
+    device = "cuda"
+
+    def __init__(self, dist, group):
+        import torch
+        self._torch, self._dist, self._group = torch, dist, group
+        self._views, self._sums, self._rounds = {}, {}, {}
+        self._lib_stream = self._lib_stream_ptr = self._comm_stream = None
+
+    def fence(self, libasora=None):
+        """The host waits for the library's stream, or for the device."""
+        if libasora is not None:
+            libasora.synchronize()
+        else:
+            self._torch.cuda.synchronize()
+
+    def phase_stream(self, libasora):
+        """The library's stream; its events delimit the phases of an iteration."""
+        ptr = libasora.stream_ptr()
+        if self._lib_stream_ptr != ptr:
+            self._lib_stream, self._lib_stream_ptr = self._torch.cuda.ExternalStream(ptr), ptr
+        return self._lib_stream
+
+    def stream(self, libasora):
+        return self._torch.cuda.stream(self.phase_stream(libasora))
+
+    def _view(self, libasora, field, N):
+        """Zero-copy (N, N*N) view of a field; kept per (address, N): the grids do not move between iterations."""
+        ptr = _call(libasora, field.ptr, *field.args)
+        if (ptr, N) not in self._views:
+            self._views[(ptr, N)] = self._torch.as_tensor(_DevicePointer(ptr, N ** 3), device="cuda").view(N, N * N)
+        return self._views[(ptr, N)]
+
+    def round(self, libasora, fields, N, key, build):
+        """build() once per `key` and addresses of the fields: buffers, targets and P2POp list are the same every iteration."""
+        key += tuple((f, self._view(libasora, f, N).data_ptr()) for f in fields)
+        if key not in self._rounds:
+            self._rounds[key] = build()
+        return self._rounds[key]
+
+    def outgoing(self, libasora, field, a, b, N):
+        return self._view(libasora, field, N)[a:b]
+
+    def incoming(self, libasora, field, a, b, N):
+        if field.add:
+            return self._torch.empty((b - a, N * N), dtype=self._torch.float64, device="cuda")
+        return self._view(libasora, field, N)[a:b]
+
+    def deliver(self, libasora, field, a, b, t):
+        if field.add:
+            _call(libasora, field.add, a, b - a, t.data_ptr())
+
+    def all_reduce_field(self, libasora, field, N):
+        self._dist.all_reduce(self._view(libasora, field, N), op=self._dist.ReduceOp.SUM, group=self._group)
+
+    def broadcast_planes(self, libasora, field, a, b, N, src):
+        self._dist.broadcast(self._view(libasora, field, N)[a:b], src=src, group=self._group)
+
+    def sum_and_close(self, libasora):
+        """The three sums of this rank's pass all-reduced in place where the library keeps them."""
+        ptr = libasora.reduction_ptr()
+        if ptr not in self._sums:
+            self._sums[ptr] = self._torch.as_tensor(_DevicePointer(ptr, 3), device="cuda")
+        with self.stream(libasora):
+            self._dist.all_reduce(self._sums[ptr], op=self._dist.ReduceOp.SUM, group=self._group)
+        libasora.evolve_slab_close(None)
+
+    @contextlib.contextmanager
+    def beside_trace(self, libasora, field, N):
+        """Yields reduce(a, b, gate): the planes [a, b) summed on a second stream once the library's stream gets to the call, while
+        the trace goes on; `gate`: the library's stream then waits for the sum.  On leaving it waits for every sum."""
+        torch = self._torch
+        lib_stream = self.phase_stream(libasora)
+        if self._comm_stream is None:
+            self._comm_stream = torch.cuda.Stream()
+        comm_stream, view = self._comm_stream, self._view(libasora, field, N)
+
+        def reduce(a, b, gate):
+            done = torch.cuda.Event()
+            done.record(lib_stream)                        # the planes are final once the library stream gets here
+            comm_stream.wait_event(done)
+            with torch.cuda.stream(comm_stream):
+                self._dist.all_reduce(view[a:b], op=self._dist.ReduceOp.SUM, group=self._group)
+            if gate:
+                summed = torch.cuda.Event()
+                summed.record(comm_stream)
+                lib_stream.wait_event(summed)
+        yield reduce
+        lib_stream.wait_stream(comm_stream)                # whatever follows on the library stream needs the sums
+
+
+class _Gloo:
+    """gloo (CPU tests, several ranks on one GPU): everything is staged through the host, which waits for every transfer."""
+    device = "cpu"
+
+    def __init__(self, dist, group):
+        import torch
+        self._torch, self._dist, self._group = torch, dist, group
+        self._me = dist.get_rank(group)
+
+    def fence(self, libasora=None):
+        pass
+
+    def phase_stream(self, libasora):
+        return None                                        # the phases are wall-clock spans between host synchronisations
+
+    def stream(self, libasora):
+        return contextlib.nullcontext()
+
+    def round(self, libasora, fields, N, key, build):
+        return build()                                     # what leaves is copied to the host anew every iteration
+
+    def outgoing(self, libasora, field, a, b, N):
+        return self._torch.from_numpy(_call(libasora, field.to_host, *field.args, a, b - a, N))
+
+    def incoming(self, libasora, field, a, b, N):
+        return self._torch.empty((b - a, N, N), dtype=self._torch.float64)
+
+    def deliver(self, libasora, field, a, b, t):
+        if field.add_host:
+            _call(libasora, field.add_host, a, t.numpy())
+        else:
+            _call(libasora, field.from_host, *field.args, a, t.numpy())
+
+    def all_reduce_field(self, libasora, field, N):
+        self._round_trip_sum(libasora, field, N, 0, N)
+
+    def _round_trip_sum(self, libasora, field, N, a, b):
+        """The planes [a, b) summed over the ranks; the whole grid makes the round trip through the host."""
+        # (a library grid has calls of its own for the whole of it)
+        host = libasora.grid_to_host(*field.args, np.empty((N, N, N))) if field.args else _call(libasora, field.to_host, 0, N, N)
+        self._dist.all_reduce(self._torch.from_numpy(host[a:b]), op=self._dist.ReduceOp.SUM, group=self._group)
+        if field.args:
+            libasora.grid_to_device(*field.args, host)
+        else:
+            _call(libasora, field.from_host, 0, host)
+
+    def broadcast_planes(self, libasora, field, a, b, N, src):
+        t = self.outgoing(libasora, field, a, b, N) if src == self._me else self.incoming(libasora, field, a, b, N)
+        self._dist.broadcast(t, src=src, group=self._group)
+        if src != self._me:
+            self.deliver(libasora, field, a, b, t)
+
+    def sum_and_close(self, libasora):
+        part = libasora.chemistry_finish()                      # (conv_flag, sum x, sum 1-x) of this rank
+        t = self._torch.tensor([float(part[0]), float(part[1]), float(part[2])], dtype=self._torch.float64)
+        self._dist.all_reduce(t, op=self._dist.ReduceOp.SUM, group=self._group)
+        v = t.tolist()
+        libasora.evolve_slab_close((v[0], v[1], v[2]))
+
+    @contextlib.contextmanager
+    def beside_trace(self, libasora, field, N):
+        yield lambda a, b, gate: self._round_trip_sum(libasora, field, N, a, b)
+
+
 class _Phases:
     """Where one multi-rank iteration spends its time (``TorchComm.phase_timing``; bench.py's ``phases_ms``).
 
@@ -256,13 +445,12 @@ class _Phases:
     through the host and every phase ends with a host synchronisation and a wall-clock reading."""
 
     def __init__(self, comm, libasora):
-        import time
         self._comm, self._lib, self._clock = comm, libasora, time.perf_counter
-        self._device = comm._backend() == "nccl"
+        self._stream = comm._t.phase_stream(libasora)
+        self._device = self._stream is not None
         if self._device:
             import torch
             self._torch = torch
-            self._stream = comm._library_stream(libasora)
             self._events = [("", self._record())]
         else:
             libasora.synchronize()
@@ -292,7 +480,7 @@ class _Phases:
 
 
 class TorchComm:
-    """Communicator over a torch.distributed process group."""
+    """Communicator over a torch.distributed process group; what RCCL and gloo do differently is in ``_Rccl`` / ``_Gloo``."""
 
     def __init__(self, group=None, overlap=None, chunks=8, pipeline_chemistry=None):
         import torch.distributed as dist
@@ -301,6 +489,7 @@ class TorchComm:
                                "(call pyc2ray_amd.dist.init_process_group_from_env() first)")
         self._dist = dist
         self._group = group
+        self._t = (_Rccl if self._backend() == "nccl" else _Gloo)(dist, group)
         if overlap is None:
             overlap = os.environ.get("PYC2RAY_AMD_OVERLAP", "0") == "1"
         self.overlap = bool(overlap)
@@ -310,7 +499,6 @@ class TorchComm:
         if pipeline_chemistry is None:
             pipeline_chemistry = os.environ.get("PYC2RAY_AMD_OVERLAP_CHEMISTRY", "0") == "1"
         self.pipeline_chemistry = bool(pipeline_chemistry)
-        self._comm_stream = None
         #: how the per-rank rate grids are summed: "slab" (SlabPlan: planes to their owners, slab chemistry, xh_av
         #: back) or "allreduce" (full-grid all-reduce, chemistry replicated on every rank)
         self.exchange = os.environ.get("PYC2RAY_AMD_EXCHANGE", "slab")
@@ -327,14 +515,12 @@ class TorchComm:
         #: True: every iteration books where its time went (``_Phases``); read with ``phase_report``
         self.phase_timing = False
         self._phase_ms, self._phase_n, self._phase_pending = {}, 0, []
+        # the step of the device-resident loop that is under way (``_begin``): (plan or None, N, local sources), the out-boxes that travel
+        self._slab, self._rate_fields = None, (_RATES,)
         # Bring the communicator up with a collective EVERY rank takes part in.  The slab exchange is point-to-point
         # and a rank with nothing to send or receive skips it; if that were the first operation on the process group,
         # the ranks that do take part would wait for the others in the communicator's set-up.
-        import torch
-        t = torch.zeros(1, dtype=torch.float64)
-        if self._backend() == "nccl":
-            t = t.cuda()
-        dist.all_reduce(t, group=self._group)
+        dist.all_reduce(self._tensor([0.0]), group=self._group)
 
     # -- mpi4py-flavoured surface ---------------------------------------------------------------
     def Get_rank(self):
@@ -358,10 +544,14 @@ class TorchComm:
         """"nccl" (RCCL: exchanges on the device, batches of iterations per host round trip) or "gloo" (through the host)."""
         return self._backend()
 
+    def _tensor(self, values, dtype=None):
+        """A few scalars where this backend's collectives take them; float64 unless told otherwise."""
+        import torch
+        return torch.tensor(values, dtype=dtype or torch.float64, device=self._t.device)
+
     def _tensor_of(self, arr):
         import torch
-        t = torch.from_numpy(np.ascontiguousarray(arr))
-        return t.cuda() if self._backend() == "nccl" else t
+        return torch.from_numpy(np.ascontiguousarray(arr)).to(self._t.device)
 
     def Allreduce(self, sendbuf, recvbuf, op=None):
         """Sum-allreduce of a numpy buffer (mpi4py calling convention, IN_PLACE supported)."""
@@ -395,22 +585,19 @@ class TorchComm:
                 arr[i] = v.item()
 
     # -- the data-path collective -------------------------------------------------------------------
-    def allreduce_device_grid(self, libasora, which, N):
-        """In-place sum over ranks of the device-resident grid `which` (N^3 float64)."""
-        import torch
-        if self.Get_size() == 1 and os.environ.get("PYC2RAY_AMD_FORCE_COLLECTIVE", "0") != "1":
-            return          # nothing to sum (the env switch lets a 1-GPU box exercise the collective path)
-        if self._backend() == "nccl":
-            libasora.synchronize()                     # the library works on its own stream
-            view = torch.as_tensor(_DevicePointer(libasora.device_ptr(which), N ** 3), device="cuda")
-            self._dist.all_reduce(view, op=self._dist.ReduceOp.SUM, group=self._group)
-            torch.cuda.synchronize()
-        else:
-            host = libasora.grid_to_host(which, np.empty((N, N, N)))
-            t = torch.from_numpy(host)
-            self._dist.all_reduce(t, op=self._dist.ReduceOp.SUM, group=self._group)
-            libasora.grid_to_device(which, host)
+    def _collective(self):
+        """Whether a sum over the ranks is carried out: always with more than one; PYC2RAY_AMD_FORCE_COLLECTIVE=1 lets a 1-GPU
+        box exercise the collective path."""
+        return self.Get_size() > 1 or os.environ.get("PYC2RAY_AMD_FORCE_COLLECTIVE", "0") == "1"
 
+    def allreduce_device_grid(self, libasora, which, N):
+        """In-place sum over ranks of the device-resident grid `which` (N^3 float64); the host waits for it."""
+        if not self._collective():
+            return
+        self._t.fence(libasora)
+        with self._t.stream(libasora):
+            self._t.all_reduce_field(libasora, _grid(which), N)
+        self._t.fence()
 
     # -- diagnostics: per-phase times of an iteration, measured link rates ----------------------------------------
     def _phase_add(self, name, ms):
@@ -435,40 +622,39 @@ class TorchComm:
         `reduce_max` (a collective: every rank must call it), plus "iterations".  Phase names: slab exchange --
         trace_fold_post, wait_rates_add, slab_pass, xh_av_exchange_nhi, scalar_allreduce_test; all-reduce loop -- trace_fold,
         rate_allreduce, pass_test; pipelined all-reduce (raytrace_and_allreduce) -- trace, rate_allreduce, chemistry."""
-        import torch
         self._phase_resolve()
         names = sorted(self._phase_ms)
         n = max(self._phase_n, 1)
         vals = [self._phase_ms[k] / n for k in names]
         if reduce_max and self.Get_size() > 1:
             # (ranks on different exchange paths would book different names: the caller keeps them on one path)
-            t = torch.tensor(vals, dtype=torch.float64)
-            if self._backend() == "nccl":
-                t = t.cuda()
+            t = self._tensor(vals)
             self._dist.all_reduce(t, op=self._dist.ReduceOp.MAX, group=self._group)
             vals = t.cpu().tolist()
         out = dict(zip(names, vals))
         out["iterations"] = self._phase_n
         return out
 
+    def _ring(self, snd, rcv):
+        """One round of the neighbour ring: every rank sends `snd` to its right neighbour and receives `rcv` from its left one,
+        through ``batch_isend_irecv`` as the slab exchange does."""
+        dist = self._dist
+        P, me = self.Get_size(), self.Get_rank()
+        ops = [dist.P2POp(dist.isend, snd, (me + 1) % P, group=self._group),
+               dist.P2POp(dist.irecv, rcv, (me - 1) % P, group=self._group)]
+        for w in dist.batch_isend_irecv(ops):
+            w.wait()
+
     def measure_links(self, p2p_bytes=16 << 20, allreduce_bytes=128 << 20, reps=3, p2p=True):
         """What the links of THIS job deliver, through the calls the data path uses: a ring of point-to-point transfers of
-        `p2p_bytes` (every rank sends to its right neighbour and receives from its left one with ``batch_isend_irecv``, as the
-        slab exchange does) and an in-place sum all-reduce of `allreduce_bytes` (the full-grid exchange).  One untimed round
+        `p2p_bytes` (``_ring``) and an in-place sum all-reduce of `allreduce_bytes` (the full-grid exchange).  One untimed round
         each, then the fastest of `reps`; times are the MAXIMUM over the ranks, so every rank returns the same numbers and
         derives the same choice from them.  p2p = False leaves the ring out (a caller whose point-to-point preflight failed:
         the all-reduce time is still worth having).  Returns {"p2p_bytes", "p2p_ms", "p2p_GBs" (per link and direction),
         "allreduce_bytes", "allreduce_ms", "allreduce_busbw_GBs" (2 (P-1)/P bytes / time, the ring's per-link rate)}."""
-        import time
         import torch
-        dist = self._dist
+        dist, fence, dev = self._dist, self._t.fence, self._t.device
         P, me = self.Get_size(), self.Get_rank()
-        nccl = self._backend() == "nccl"
-        dev = "cuda" if nccl else "cpu"
-
-        def fence():
-            if nccl:
-                torch.cuda.synchronize()
 
         def timed(fn):
             best = None
@@ -481,7 +667,7 @@ class TorchComm:
                 dt = time.perf_counter() - t0
                 if rep > 0:
                     best = dt if best is None else min(best, dt)
-            t = torch.tensor([best], dtype=torch.float64, device=dev)
+            t = self._tensor([best])
             dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self._group)
             return float(t.item())
 
@@ -492,13 +678,7 @@ class TorchComm:
         n1 = max(1, int(p2p_bytes) // 8)
         snd = torch.full((n1,), float(me + 1), dtype=torch.float64, device=dev)
         rcv = torch.zeros((n1,), dtype=torch.float64, device=dev)
-
-        def ring():
-            ops = [dist.P2POp(dist.isend, snd, (me + 1) % P, group=self._group),
-                   dist.P2POp(dist.irecv, rcv, (me - 1) % P, group=self._group)]
-            for w in dist.batch_isend_irecv(ops):
-                w.wait()
-        t_p2p = timed(ring) if p2p else None
+        t_p2p = timed(lambda: self._ring(snd, rcv)) if p2p else None
         n2 = max(1, int(allreduce_bytes) // 8)
         buf = torch.zeros((n2,), dtype=torch.float64, device=dev)
         t_ar = timed(lambda: dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self._group))
@@ -508,24 +688,18 @@ class TorchComm:
         return out
 
     def preflight_p2p(self, nelem=65536):
-        """One small point-to-point round (every rank sends to its right neighbour and receives from its left one) through
-        the same call the slab exchange uses.  The exchange has never run between real GPUs on the build box; a caller
-        that gets an exception here (or False from any rank, after a MIN-reduce of the results) takes the all-reduce path.
-        Returns True when the round went through on this rank and the payload arrived intact."""
+        """One small round of the neighbour ring (``_ring``) through the same call the slab exchange uses.  The exchange has
+        never run between real GPUs on the build box; a caller that gets an exception here (or False from any rank, after a
+        MIN-reduce of the results) takes the all-reduce path.  Returns True when the round went through on this rank and the
+        payload arrived intact."""
         import torch
-        dist = self._dist
         P, me = self.Get_size(), self.Get_rank()
         if P < 2:
             return True
-        dev = "cuda" if self._backend() == "nccl" else "cpu"
-        out = torch.full((nelem,), float(me + 1), dtype=torch.float64, device=dev)
-        inc = torch.zeros((nelem,), dtype=torch.float64, device=dev)
-        ops = [dist.P2POp(dist.isend, out, (me + 1) % P, group=self._group),
-               dist.P2POp(dist.irecv, inc, (me - 1) % P, group=self._group)]
-        for w in dist.batch_isend_irecv(ops):
-            w.wait()
-        if dev == "cuda":
-            torch.cuda.synchronize()
+        out = torch.full((nelem,), float(me + 1), dtype=torch.float64, device=self._t.device)
+        inc = torch.zeros((nelem,), dtype=torch.float64, device=self._t.device)
+        self._ring(out, inc)
+        self._t.fence()
         return bool((inc == float((me - 1) % P + 1)).all().item())
 
     # -- slab exchange: rates to the owners of the planes, ionised fraction back (see SlabPlan) -------------------
@@ -540,98 +714,58 @@ class TorchComm:
         n = flux.shape[0]
         per = n // nprocs
         bounds = [r * per for r in range(nprocs)] + [n]
-        if src_spectrum is not None:
-            return pos[:, order], flux[order], bounds, np.asarray(src_spectrum)[order]
-        return pos[:, order], flux[order], bounds
+        spectra = () if src_spectrum is None else (np.asarray(src_spectrum)[order],)
+        return (pos[:, order], flux[order], bounds) + spectra
 
-    def _planes_view(self, libasora, which, N):
-        """Zero-copy (N, N*N) view of a library grid; kept per (address, N): the grids do not move between iterations."""
-        import torch
-        ptr = libasora.device_ptr(which)
-        cache = self.__dict__.setdefault("_views", {})
-        if (ptr, N) not in cache:
-            cache[(ptr, N)] = torch.as_tensor(_DevicePointer(ptr, N ** 3), device="cuda").view(N, N * N)
-        return cache[(ptr, N)]
-
-    def _library_stream(self, libasora):
-        import torch
-        ptr = libasora.stream_ptr()
-        if getattr(self, "_lib_stream_ptr", None) != ptr:
-            self._lib_stream, self._lib_stream_ptr = torch.cuda.ExternalStream(ptr), ptr
-        return self._lib_stream
-
-    def _post(self, libasora, which, N, sends, recvs, add, tag):
-        """Start one round of plane transfers of grid `which`: `sends` = [(peer, a, b)] planes [a, b) to peer, `recvs` =
-        [(peer, a, b)] planes from peer.  Returns a handle for ``_complete``.  With RCCL everything is ordered on the
-        library's stream: the sends start behind the kernels that produced the planes, and nothing waits on the host; the
-        transfers themselves run on RCCL's stream, beside whatever the library's stream does next.  add = True: what is
-        received is ADDED to the planes (in ``_complete``, in the order of `recvs`), else it replaces them."""
-        import torch
-        dist = self._dist
+    def _post(self, libasora, fields, N, sends, recvs, tag):
+        """Start one round of plane transfers: `sends` = [(peer, a, b)] planes [a, b) to peer, `recvs` likewise from peer; per
+        run every field travels, in the order of `fields`.  Returns a handle for ``_complete``; `tag` tells an iteration's rounds apart."""
         if not sends and not recvs:
             return None
-        if self._backend() == "nccl":
-            lib_stream = self._library_stream(libasora)
-            with torch.cuda.stream(lib_stream):
-                grid = self._planes_view(libasora, which, N)
-                # staging buffers, receive targets and the P2POp list are the same every iteration: built once per round
-                key = (tag, which, N, add, tuple(sends), tuple(recvs), grid.data_ptr())
-                cache = self.__dict__.setdefault("_rounds", {})
-                if key not in cache:
-                    if add:
-                        targets = [torch.empty((b - a, N * N), dtype=torch.float64, device="cuda") for _, a, b in recvs]
-                    else:
-                        targets = [grid[a:b] for _, a, b in recvs]
-                    ops = [dist.P2POp(dist.isend, grid[a:b], q, group=self._group) for q, a, b in sends]
-                    ops += [dist.P2POp(dist.irecv, t, q, group=self._group) for (q, _, _), t in zip(recvs, targets)]
-                    cache[key] = (targets, ops)
-                targets, ops = cache[key]
-                works = dist.batch_isend_irecv(ops)
-            return ("nccl", works, recvs, targets, add)
-        # gloo (CPU tests, several ranks on one GPU): staged through the host
-        out = [torch.from_numpy(libasora.planes_to_host(which, a, b - a, N)) for _, a, b in sends]
-        inc = [torch.empty((b - a, N, N), dtype=torch.float64) for _, a, b in recvs]
-        ops = [dist.P2POp(dist.isend, t, q, group=self._group) for (q, _, _), t in zip(sends, out)]
-        ops += [dist.P2POp(dist.irecv, t, q, group=self._group) for (q, _, _), t in zip(recvs, inc)]
-        works = dist.batch_isend_irecv(ops)
-        return ("gloo", works, recvs, inc, add, out)
+        dist, t = self._dist, self._t
 
-    def _complete(self, libasora, which, N, handle):
-        """Wait for a round started by ``_post`` and put what was received in place (fixed order: same bits on every run)."""
-        import torch
+        def build():
+            out = [[t.outgoing(libasora, f, a, b, N) for f in fields] for _, a, b in sends]
+            targets = [[t.incoming(libasora, f, a, b, N) for f in fields] for _, a, b in recvs]
+            ops = [dist.P2POp(dist.isend, x, q, group=self._group) for (q, _, _), xs in zip(sends, out) for x in xs]
+            ops += [dist.P2POp(dist.irecv, x, q, group=self._group) for (q, _, _), xs in zip(recvs, targets) for x in xs]
+            return targets, ops
+        with t.stream(libasora):
+            targets, ops = t.round(libasora, fields, N, (tag, N, tuple(sends), tuple(recvs)), build)
+            works = dist.batch_isend_irecv(ops)
+        return works, ops, fields, recvs, targets
+
+    def _complete(self, libasora, handle):
+        """Wait for a round started by ``_post`` and deliver what arrived: in the order of `recvs` (rank order), per run in the
+        order of the fields -- a fixed order of additions, the same bits on every run."""
         if handle is None:
             return
-        kind, works, recvs, targets, add = handle[:5]
-        if kind == "nccl":
-            lib_stream = self._library_stream(libasora)
-            with torch.cuda.stream(lib_stream):
-                for w in works:
-                    w.wait()                       # the library's stream waits, not the host
-                if add:
-                    grid = self._planes_view(libasora, which, N)
-                    for (q, a, b), t in zip(recvs, targets):
-                        grid[a:b] += t
-            return
-        for w in works:
-            w.wait()
-        for (q, a, b), t in zip(recvs, targets):
-            if add:
-                mine = libasora.planes_to_host(which, a, b - a, N)
-                libasora.planes_to_device(which, a, mine + t.numpy())
-            else:
-                libasora.planes_to_device(which, a, t.numpy())
+        works, _, fields, recvs, targets = handle
+        with self._t.stream(libasora):
+            for w in works:
+                w.wait()
+        for (_, a, b), ts in zip(recvs, targets):
+            for f, x in zip(fields, ts):
+                self._t.deliver(libasora, f, a, b, x)
 
     # -- the device-resident loop over several ranks (asora_evolve_slab_*, include/asora_hip.h) ------------------------
+    def _begin(self, libasora, plan, own, N, R, sig, dr, num_src_local, minlogtau, dlogtau, NumTau, chemistry, conv_criterion,
+               convergence_fraction, thermal):
+        """A time step of the device-resident loop on the planes own = [a, b) of this rank."""
+        a, b = own
+        begin = libasora.evolve_begin_slab_thermal if thermal else libasora.evolve_begin_slab
+        begin(*chemistry, R, sig, dr, minlogtau, dlogtau, NumTau, 0, num_src_local, conv_criterion, convergence_fraction, a, b - a)
+        self._slab = (plan, int(N), int(num_src_local))
+        self._rate_fields = (_RATES, _HEAT) if thermal else (_RATES,)
+
     def slab_begin(self, libasora, plan, N, R, sig, dr, num_src_local, minlogtau, dlogtau, NumTau, chemistry,
                    conv_criterion, convergence_fraction, thermal=False):
         """Start a time step of the sharded loop: NDENS, TEMP, XH and this rank's sources are on the device.  `chemistry` =
         (dt, bh00, albpow, colh0, temph0, abu_c); conv_criterion from the TOTAL source count (pyc2ray/evolve.py:127,346).
         thermal = True: the library is in thermal mode (``ThermalParams.apply``), the step is begun through
         asora_evolve_begin_slab_thermal and the first exchange carries the heating planes with the rate planes."""
-        a, b = plan.own[self.Get_rank()]
-        begin = libasora.evolve_begin_slab_thermal if thermal else libasora.evolve_begin_slab
-        begin(*chemistry, R, sig, dr, minlogtau, dlogtau, NumTau, 0, num_src_local, conv_criterion, convergence_fraction, a, b - a)
-        self._slab, self._slab_thermal = (plan, int(N), int(num_src_local)), bool(thermal)
+        self._begin(libasora, plan, plan.own[self.Get_rank()], N, R, sig, dr, num_src_local, minlogtau, dlogtau, NumTau, chemistry,
+                    conv_criterion, convergence_fraction, thermal)
 
     def reduce_begin(self, libasora, N, R, sig, dr, num_src_local, minlogtau, dlogtau, NumTau, chemistry, conv_criterion,
                      convergence_fraction, thermal=False):
@@ -639,9 +773,8 @@ class TorchComm:
         rank traces its sources, the rate grid is all-reduced, every rank runs the chemistry of the WHOLE grid on identical
         rates (and so takes the same decisions without exchanging anything else).  ``slab_enqueue`` / ``slab_poll`` drive it.
         thermal = True (the library in thermal mode): both out-boxes, rates and heating, are all-reduced."""
-        begin = libasora.evolve_begin_slab_thermal if thermal else libasora.evolve_begin_slab
-        begin(*chemistry, R, sig, dr, minlogtau, dlogtau, NumTau, 0, num_src_local, conv_criterion, convergence_fraction, 0, N)
-        self._slab, self._slab_thermal = (None, int(N), int(num_src_local)), bool(thermal)
+        self._begin(libasora, None, (0, N), N, R, sig, dr, num_src_local, minlogtau, dlogtau, NumTau, chemistry, conv_criterion,
+                    convergence_fraction, thermal)
 
     def thermal_stats(self, libasora):
         """asora_thermal_stats of the thermal step just run, for the whole grid and the same on every rank: (cells that hit
@@ -652,9 +785,7 @@ class TorchComm:
         capped, floored, most = libasora.thermal_stats()
         if self._slab[0] is None or self.Get_size() == 1:
             return capped, floored, most
-        dev = "cuda" if self._backend() == "nccl" else "cpu"
-        counts = torch.tensor([capped, floored], dtype=torch.int64, device=dev)
-        top = torch.tensor([most], dtype=torch.int64, device=dev)
+        counts, top = self._tensor([capped, floored], torch.int64), self._tensor([most], torch.int64)
         self._dist.all_reduce(counts, op=self._dist.ReduceOp.SUM, group=self._group)
         self._dist.all_reduce(top, op=self._dist.ReduceOp.MAX, group=self._group)
         c = counts.cpu().tolist()
@@ -662,30 +793,19 @@ class TorchComm:
 
     def _reduce_one(self, libasora):
         """One iteration of the loop begun with ``reduce_begin``: trace -> both accumulator layouts of all planes folded into
-        the out-box -> the out-box summed over the ranks in place -> the fused pass on the whole grid reading the out-box (it
-        keeps the summed rates in PHI_ION) -> convergence test on the pass's own sums.  With RCCL the all-reduce is ordered on
-        the library's stream and nothing waits on the host; with gloo the out-box goes through the host."""
-        import torch
+        the out-box -> the out-box (a thermal step: then the heating out-box) summed over the ranks in place -> the fused pass
+        on the whole grid reading the out-box (it keeps the summed rates in PHI_ION) -> convergence test on the pass's own
+        sums.  With RCCL the all-reduce is ordered on the library's stream and nothing waits on the host; with gloo the out-box
+        goes through the host."""
         _, N, num_src_local = self._slab
         ph = _Phases(self, libasora) if self.phase_timing else None
         libasora.evolve_slab_trace(0, num_src_local)
         libasora.evolve_slab_fold_all()
         if ph: ph.mark("trace_fold")
-        thermal = getattr(self, "_slab_thermal", False)
-        if self.Get_size() > 1 or os.environ.get("PYC2RAY_AMD_FORCE_COLLECTIVE", "0") == "1":
-            if self._backend() == "nccl":
-                with torch.cuda.stream(self._library_stream(libasora)):
-                    self._dist.all_reduce(self._outbox_view(libasora, N), op=self._dist.ReduceOp.SUM, group=self._group)
-                    if thermal:
-                        self._dist.all_reduce(self._outbox_view(libasora, N, heat=True), op=self._dist.ReduceOp.SUM, group=self._group)
-            else:
-                host = libasora.evolve_slab_outbox_to_host(0, N, N)
-                self._dist.all_reduce(torch.from_numpy(host), op=self._dist.ReduceOp.SUM, group=self._group)
-                libasora.evolve_slab_outbox_from_host(0, host)
-                if thermal:
-                    host = libasora.evolve_slab_heat_outbox_to_host(0, N, N)
-                    self._dist.all_reduce(torch.from_numpy(host), op=self._dist.ReduceOp.SUM, group=self._group)
-                    libasora.evolve_slab_heat_outbox_from_host(0, host)
+        if self._collective():
+            with self._t.stream(libasora):
+                for f in self._rate_fields:
+                    self._t.all_reduce_field(libasora, f, N)
         if ph: ph.mark("rate_allreduce")
         libasora.evolve_slab_pass()
         libasora.evolve_slab_close(None)             # (the pass's sums are those of the whole grid, the same on every rank)
@@ -716,91 +836,12 @@ class TorchComm:
         (complete on the own planes; ``slab_gather`` collects the owners' slabs at the end of the step)."""
         return libasora.evolve_poll(max_rows)
 
-    def _outbox_view(self, libasora, N, heat=False):
-        """Zero-copy (N, N*N) view of the rate out-box, or (heat) of the heating out-box of a thermal step."""
-        import torch
-        ptr = libasora.evolve_slab_heat_outbox_ptr() if heat else libasora.evolve_slab_outbox_ptr()
-        cache = self.__dict__.setdefault("_views", {})
-        if (ptr, N) not in cache:
-            cache[(ptr, N)] = torch.as_tensor(_DevicePointer(ptr, N ** 3), device="cuda").view(N, N * N)
-        return cache[(ptr, N)]
-
-    def _post_rates(self, libasora, N, sends, recvs, tag, thermal=False):
-        """The first exchange: out-box planes to their owners, foreign contributions to the own planes into receive buffers.
-        thermal: for every (peer, run of planes) the heating planes travel behind the rate planes, in the same round."""
-        import torch
-        dist = self._dist
-        if not sends and not recvs:
-            return None
-        fields = (False, True) if thermal else (False,)                # heat? -- rates first, then heating, per run
-        if self._backend() == "nccl":
-            with torch.cuda.stream(self._library_stream(libasora)):
-                boxes = [self._outbox_view(libasora, N, heat=h) for h in fields]
-                key = ("rates", tag, N, tuple(sends), tuple(recvs), tuple(b.data_ptr() for b in boxes))
-                cache = self.__dict__.setdefault("_rounds", {})
-                if key not in cache:
-                    targets = [[torch.empty((b - a, N * N), dtype=torch.float64, device="cuda") for _ in fields] for _, a, b in recvs]
-                    ops = [dist.P2POp(dist.isend, box[a:b], q, group=self._group) for q, a, b in sends for box in boxes]
-                    ops += [dist.P2POp(dist.irecv, t, q, group=self._group) for (q, _, _), ts in zip(recvs, targets) for t in ts]
-                    cache[key] = (targets, ops)
-                targets, ops = cache[key]
-                works = dist.batch_isend_irecv(ops)
-            return ("nccl", works, recvs, targets)
-        to_host = (libasora.evolve_slab_outbox_to_host,) + ((libasora.evolve_slab_heat_outbox_to_host,) if thermal else ())
-        out = [[torch.from_numpy(f(a, b - a, N)) for f in to_host] for _, a, b in sends]
-        inc = [[torch.empty((b - a, N, N), dtype=torch.float64) for _ in fields] for _, a, b in recvs]
-        ops = [dist.P2POp(dist.isend, t, q, group=self._group) for (q, _, _), ts in zip(sends, out) for t in ts]
-        ops += [dist.P2POp(dist.irecv, t, q, group=self._group) for (q, _, _), ts in zip(recvs, inc) for t in ts]
-        return ("gloo", dist.batch_isend_irecv(ops), recvs, inc, out)
-
-    def _complete_rates(self, libasora, handle):
-        """Wait for a round of ``_post_rates`` and add what arrived, in the order of `recvs` (rank order); per run the rates,
-        then (thermal step) the heating."""
-        import torch
-        if handle is None:
-            return
-        kind, works, recvs, targets = handle[:4]
-        if kind == "nccl":
-            with torch.cuda.stream(self._library_stream(libasora)):
-                for w in works:
-                    w.wait()                                   # the library's stream waits, not the host
-            for (_, a, b), ts in zip(recvs, targets):
-                libasora.evolve_slab_add(a, b - a, ts[0].data_ptr())
-                if len(ts) > 1:
-                    libasora.evolve_slab_add_heat(a, b - a, ts[1].data_ptr())
-            return
-        for w in works:
-            w.wait()
-        for (_, a, b), ts in zip(recvs, targets):
-            libasora.evolve_slab_add_host(a, ts[0].numpy())
-            if len(ts) > 1:
-                libasora.evolve_slab_add_heat_host(a, ts[1].numpy())
-
-    def _close_iteration(self, libasora):
-        """The three sums of this rank's pass summed over the ranks, then the convergence test on the device."""
-        import torch
-        if self._backend() == "nccl" and hasattr(libasora, "reduction_ptr"):
-            ptr = libasora.reduction_ptr()
-            cache = self.__dict__.setdefault("_views", {})
-            if (ptr, 3) not in cache:
-                cache[(ptr, 3)] = torch.as_tensor(_DevicePointer(ptr, 3), device="cuda")
-            with torch.cuda.stream(self._library_stream(libasora)):
-                self._dist.all_reduce(cache[(ptr, 3)], op=self._dist.ReduceOp.SUM, group=self._group)
-            libasora.evolve_slab_close(None)
-            return
-        part = libasora.chemistry_finish()                      # (conv_flag, sum x, sum 1-x) of this rank
-        t = torch.tensor([float(part[0]), float(part[1]), float(part[2])], dtype=torch.float64)
-        self._dist.all_reduce(t, op=self._dist.ReduceOp.SUM, group=self._group)
-        v = t.tolist()
-        libasora.evolve_slab_close((v[0], v[1], v[2]))
-
     def _slab_one(self, libasora):
-        from . import _capi
         plan, N, num_src_local = self._slab
         me = self.Get_rank()
         # every rank walks through the same number of rounds and derives every other rank's schedule: the chunk count is a
         # function of the plan, never of this rank alone
-        K = plan.common_chunks(getattr(self, "slab_chunks", 1))
+        K = plan.common_chunks(self.slab_chunks)
         ph = _Phases(self, libasora) if self.phase_timing else None
         sched, rsched = plan.send_schedule(me, K), plan.recv_schedule(me, K)
         bounds = plan.chunk_bounds(num_src_local, K)
@@ -809,24 +850,21 @@ class TorchComm:
             libasora.evolve_slab_trace(bounds[c], bounds[c + 1] - bounds[c])
             for _, a, b in sched[c]:
                 libasora.evolve_slab_fold_out(a, b - a)                 # the planes that leave now
-            handles.append(self._post_rates(libasora, N, sched[c], rsched[c], c, getattr(self, "_slab_thermal", False)))
+            # out-box planes to their owners, foreign contributions to the own planes into receive buffers
+            handles.append(self._post(libasora, self._rate_fields, N, sched[c], rsched[c], c))
         if ph: ph.mark("trace_fold_post")
         for h in handles:                                               # chunk order, then rank order: a fixed order of additions
-            self._complete_rates(libasora, h)
+            self._complete(libasora, h)
         if ph: ph.mark("wait_rates_add")
         libasora.evolve_slab_pass()
         if ph: ph.mark("slab_pass")
         # xh_av back: the owner q of a run sends it to the rank r that traces through it; nHI there once it has arrived
-        back = plan.__dict__.setdefault("_back_cache", {})
-        if me not in back:
-            back[me] = ([(r, s0, s1) for r in range(plan.P) if r != me for s0, s1 in plan.runs[r][me]],
-                        [(q, s0, s1) for q in range(plan.P) if q != me for s0, s1 in plan.runs[me][q]])
-        sends, recvs = back[me]
-        self._complete(libasora, _capi.GRID_XH_AV, N, self._post(libasora, _capi.GRID_XH_AV, N, sends, recvs, False, "xh_av"))
+        sends, recvs = plan.back_runs(me)
+        self._complete(libasora, self._post(libasora, (_grid(_capi.GRID_XH_AV),), N, sends, recvs, "xh_av"))
         for _, a, b in recvs:
             libasora.evolve_slab_nhi(a, b - a)
         if ph: ph.mark("xh_av_exchange_nhi")
-        self._close_iteration(libasora)
+        self._t.sum_and_close(libasora)       # the three sums of this rank's pass summed over the ranks, then the test on the device
         if ph:
             ph.mark("scalar_allreduce_test")
             ph.close()
@@ -844,24 +882,10 @@ class TorchComm:
     def slab_gather(self, libasora, plan, which, N):
         """Every rank gets every owner's slab of grid `which` (end of a time step: xh_intermed, phi_ion; a thermal step:
         temp_end and phi_heat as well)."""
-        import torch
-        me = self.Get_rank()
-        if self._backend() == "nccl":
-            lib_stream = torch.cuda.ExternalStream(libasora.stream_ptr())
-            with torch.cuda.stream(lib_stream):
-                grid = self._planes_view(libasora, which, N)
-                for q, (a, b) in enumerate(plan.own):
-                    if b > a:
-                        self._dist.broadcast(grid[a:b], src=q, group=self._group)
-            return
-        for q, (a, b) in enumerate(plan.own):
-            if b <= a:
-                continue
-            t = torch.from_numpy(libasora.planes_to_host(which, a, b - a, N)) if q == me else \
-                torch.empty((b - a, N, N), dtype=torch.float64)
-            self._dist.broadcast(t, src=q, group=self._group)
-            if q != me:
-                libasora.planes_to_device(which, a, t.numpy())
+        with self._t.stream(libasora):
+            for q, (a, b) in enumerate(plan.own):
+                if b > a:
+                    self._t.broadcast_planes(libasora, _grid(which), a, b, N, q)
 
     # -- raytrace + sum over ranks, optionally pipelined ------------------------------------------------
     @staticmethod
@@ -870,9 +894,8 @@ class TorchComm:
         (3, n) 1-based; returns (src_pos, src_flux) reordered -- and `src_spectrum`, the spectrum of each source, when
         given.  The sum over sources is order-independent up to floating-point rounding."""
         order = np.argsort(np.asarray(src_pos)[0], kind="stable")
-        if src_spectrum is not None:
-            return np.asarray(src_pos)[:, order], np.asarray(src_flux)[order], np.asarray(src_spectrum)[order]
-        return np.asarray(src_pos)[:, order], np.asarray(src_flux)[order]
+        spectra = () if src_spectrum is None else (np.asarray(src_spectrum)[order],)
+        return (np.asarray(src_pos)[:, order], np.asarray(src_flux)[order]) + spectra
 
     @staticmethod
     def final_plane_runs(N, chunks, R, c, reduced):
@@ -890,17 +913,7 @@ class TorchComm:
             if hi > lo:
                 want[lo:hi] = True
             want &= ~reduced
-        runs, i = [], 0
-        while i < N:
-            if want[i]:
-                j = i
-                while j < N and want[j]:
-                    j += 1
-                runs.append((i, j))
-                i = j
-            else:
-                i += 1
-        return runs
+        return _runs_of(want)
 
     def raytrace_and_allreduce(self, libasora, N, R, sig, dr, num_src_local, minlogtau, dlogtau, NumTau,
                                src_i0=None, chemistry=None):
@@ -911,28 +924,25 @@ class TorchComm:
         With `chemistry` = (dt, bh00, albpow, colh0, temph0, abu_c) the chemistry pass is run as well and its
         (conv_flag, sum x, sum 1-x) returned; with self.pipeline_chemistry each slab's chemistry starts as soon as its
         rates are summed, under the remaining trace and all-reduces."""
-        from . import _capi
         if not self.overlap or src_i0 is None:
-            if not self.phase_timing:
-                libasora.raytrace_device(R, sig, dr, 0, num_src_local, minlogtau, dlogtau, NumTau)
-                self.allreduce_device_grid(libasora, _capi.GRID_PHI_ION, N)
-                return libasora.chemistry_device(*chemistry) if chemistry is not None else None
-            # the same three calls between wall-clock readings (each of them ends with a host synchronisation anyway)
-            import time
-            t0 = time.perf_counter()
+            # three calls; with `phase_timing`, between wall-clock readings (all but the trace end with a host synchronisation anyway)
+            stamps = []
+
+            def mark(sync=False):
+                if self.phase_timing:
+                    if sync: libasora.synchronize()
+                    stamps.append(time.perf_counter())
+            mark()
             libasora.raytrace_device(R, sig, dr, 0, num_src_local, minlogtau, dlogtau, NumTau)
-            libasora.synchronize()
-            t1 = time.perf_counter()
+            mark(sync=True)
             self.allreduce_device_grid(libasora, _capi.GRID_PHI_ION, N)
-            t2 = time.perf_counter()
+            mark()
             res = libasora.chemistry_device(*chemistry) if chemistry is not None else None
-            t3 = time.perf_counter()
-            self._phase_add("trace", (t1 - t0) * 1e3)
-            self._phase_add("rate_allreduce", (t2 - t1) * 1e3)
-            self._phase_add("chemistry", (t3 - t2) * 1e3)
-            self._phase_n += 1
+            mark()
+            for name, t0, t1 in zip(("trace", "rate_allreduce", "chemistry"), stamps, stamps[1:]):
+                self._phase_add(name, (t1 - t0) * 1e3)
+            self._phase_n += bool(stamps)
             return res
-        import torch
         src_i0 = np.asarray(src_i0)
         if src_i0.size and np.any(np.diff(src_i0) < 0):
             raise ValueError("raytrace_and_allreduce: sources must be uploaded in ascending order of their first "
@@ -940,44 +950,24 @@ class TorchComm:
         K = max(1, min(self.chunks, N))
         starts = np.searchsorted(src_i0, [c * N // K for c in range(K + 1)], side="left")
         starts[-1] = src_i0.size
-        nccl = self._backend() == "nccl"
-        force = os.environ.get("PYC2RAY_AMD_FORCE_COLLECTIVE", "0") == "1"
-        collective = self.Get_size() > 1 or force
-        if nccl and collective:
-            lib_stream = torch.cuda.ExternalStream(libasora.stream_ptr())
-            if self._comm_stream is None:
-                self._comm_stream = torch.cuda.Stream()
-            view = torch.as_tensor(_DevicePointer(libasora.device_ptr(_capi.GRID_PHI_ION), N ** 3), device="cuda")
         reduced = np.zeros(N, dtype=bool)
         first_slab = True
         slab_chemistry = chemistry is not None and self.pipeline_chemistry
-        libasora.raytrace_begin(R, sig, dr, minlogtau, dlogtau, NumTau)
-        for c in range(K):
-            libasora.raytrace_range(int(starts[c]), int(starts[c + 1] - starts[c]))
-            for a, b in self.final_plane_runs(N, K, R, c, reduced):
-                libasora.raytrace_fold(a, b - a)
-                reduced[a:b] = True
-                if collective and nccl:
-                    done = torch.cuda.Event()
-                    done.record(lib_stream)                    # the slab is final once the library stream gets here
-                    self._comm_stream.wait_event(done)
-                    with torch.cuda.stream(self._comm_stream):
-                        self._dist.all_reduce(view[a * N * N:b * N * N], op=self._dist.ReduceOp.SUM, group=self._group)
-                    if slab_chemistry:                         # the slab's chemistry goes behind its sum
-                        summed = torch.cuda.Event()
-                        summed.record(self._comm_stream)
-                        lib_stream.wait_event(summed)
-                elif collective:                               # gloo (CPU tests): staged through the host
-                    host = libasora.grid_to_host(_capi.GRID_PHI_ION, np.empty((N, N, N)))
-                    t = torch.from_numpy(host[a:b])
-                    self._dist.all_reduce(t, op=self._dist.ReduceOp.SUM, group=self._group)
-                    libasora.grid_to_device(_capi.GRID_PHI_ION, host)
-                if slab_chemistry:
-                    libasora.chemistry_range(*chemistry, a, b - a, first_slab)
-                    first_slab = False
-        assert reduced.all()
-        if nccl and collective:
-            lib_stream.wait_stream(self._comm_stream)         # whatever follows on the library stream needs the sums
+        # reduce(a, b, gate): the planes [a, b), final now, summed over the ranks beside the rest of the trace
+        sums = self._t.beside_trace(libasora, _grid(_capi.GRID_PHI_ION), N) if self._collective() else contextlib.nullcontext()
+        with sums as reduce:
+            libasora.raytrace_begin(R, sig, dr, minlogtau, dlogtau, NumTau)
+            for c in range(K):
+                libasora.raytrace_range(int(starts[c]), int(starts[c + 1] - starts[c]))
+                for a, b in self.final_plane_runs(N, K, R, c, reduced):
+                    libasora.raytrace_fold(a, b - a)
+                    reduced[a:b] = True
+                    if reduce is not None:
+                        reduce(a, b, slab_chemistry)           # the slab's chemistry goes behind its sum
+                    if slab_chemistry:
+                        libasora.chemistry_range(*chemistry, a, b - a, first_slab)
+                        first_slab = False
+            assert reduced.all()
         if chemistry is None:
             return None
         return libasora.chemistry_finish() if slab_chemistry else libasora.chemistry_device(*chemistry)

@@ -134,6 +134,13 @@ def _contiguous_shard(src_pos, src_flux, ranks, spec=None):
     return pos[:, i_start:i_end], src_flux[i_start:i_end], None if spec is None else spec[i_start:i_end]
 
 
+def _spectra_along(reorder, *args, spec):
+    """reorder(*args, src_spectrum=spec) of the communicator's two source re-orderings, which return the re-ordered spectra last
+    only when given any: always with that last element, None where there are none."""
+    out = tuple(reorder(*args, src_spectrum=spec))
+    return out if spec is not None else out + (None,)
+
+
 def _prologue(libasora, scalars, N, NumTau, src_flux, my_pos, my_flux, uploads, clump, *, ranks=_ONE_RANK,
               calling="Calling evolve3D...", xh_copies=False, say_copied=False, clump_upload=True, tables=None, spec=None):
     """What every form of the step does before its loop: the convergence criterion, this rank's sources (`my_pos`, `my_flux`)
@@ -517,21 +524,14 @@ def _evolve(scalars, src_flux, src_pos, grids, photo_thin_table, ranks=_ONE_RANK
         # the same contiguous blocks, of the list ordered by the first coordinate: a rank's rates then live on the
         # planes within R of its slab of sources, and only those planes are exchanged (pyc2ray_amd.dist.SlabPlan)
         from .dist import SlabPlan
-        if spec is None:
-            all_pos, all_flux, bounds = comm.shard_sources_by_slab(np.asarray(src_pos), src_flux, nprocs)
-            my_spec = None
-        else:
-            all_pos, all_flux, bounds, all_spec = comm.shard_sources_by_slab(np.asarray(src_pos), src_flux, nprocs, spec)
-            my_spec = all_spec[bounds[rank]:bounds[rank + 1]]
+        all_pos, all_flux, bounds, all_spec = _spectra_along(comm.shard_sources_by_slab, np.asarray(src_pos), src_flux, nprocs, spec=spec)
         my_pos, my_flux = all_pos[:, bounds[rank]:bounds[rank + 1]], all_flux[bounds[rank]:bounds[rank + 1]]
+        my_spec = None if all_spec is None else all_spec[bounds[rank]:bounds[rank + 1]]
         plan = SlabPlan(N, nprocs, scalars["R_max_LLS"], [all_pos[0, bounds[r]:bounds[r + 1]] - 1 for r in range(nprocs)])
     else:
         my_pos, my_flux, my_spec = _contiguous_shard(src_pos, src_flux, ranks, spec)
     if strategy == "pipelined":         # the shard is traced in order of the first coordinate
-        if my_spec is None:
-            my_pos, my_flux = comm.sort_sources_for_overlap(my_pos, my_flux)
-        else:
-            my_pos, my_flux, my_spec = comm.sort_sources_for_overlap(my_pos, my_flux, my_spec)
+        my_pos, my_flux, my_spec = _spectra_along(comm.sort_sources_for_overlap, my_pos, my_flux, spec=my_spec)
         src_i0 = np.asarray(my_pos[0]).astype(np.int64) - 1
 
     step = _prologue(libasora, scalars, N, photo_thin_table.shape[0], src_flux, my_pos, my_flux,

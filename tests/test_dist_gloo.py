@@ -187,11 +187,8 @@ def test_bench_refuses_a_world_size_that_contradicts_gpus():
 
 
 # ---- slab exchange (pyc2ray_amd.dist.SlabPlan): rates to the owners of the planes, slab chemistry, xh_av back -------
-def test_slab_plan_covers_what_the_sources_reach():
-    """Pure bookkeeping: for random source sets, radii and rank counts, every plane a rank's sources can rate lies in
-    its reach, every reached plane of a foreign slab lies in the run sent to that slab's owner, the slabs partition
-    the planes, and the byte counts are symmetric between the two exchanges."""
-    from pyc2ray_amd.dist import SlabPlan, TorchComm
+def _random_plan_inputs():
+    """(trial, N, P, R, pos, flux): random meshes, rank counts, radii and source sets for the bookkeeping of SlabPlan."""
     rng = np.random.default_rng(7)
     for trial in range(60):
         N = int(rng.choice([16, 17, 24, 33, 64, 256]))
@@ -201,7 +198,39 @@ def test_slab_plan_covers_what_the_sources_reach():
         pos = 1 + rng.integers(0, N, size=(3, ns))
         if trial % 3 == 0:
             pos[0] = 1 + (pos[0] % max(2, N // 5))                  # all sources in a thin slab near the periodic seam
-        flux = rng.uniform(0.5, 2.0, size=ns)
+        yield trial, N, P, R, pos, rng.uniform(0.5, 2.0, size=ns)
+
+
+def test_slab_plan_back_runs_are_the_rate_runs_reversed():
+    """The second exchange of an iteration (xh_av back to the ranks that trace through the planes): what the owner q sends back to
+    r is exactly runs[r][q], r expects that same list from q, and both lists of a rank, in rank order, are what the iteration
+    used to spell out in place."""
+    from pyc2ray_amd.dist import SlabPlan, TorchComm
+    for trial, N, P, R, pos, flux in _random_plan_inputs():
+        spos, _, bounds = TorchComm.shard_sources_by_slab(pos, flux, P)
+        plan = SlabPlan(N, P, R, [spos[0, bounds[r]:bounds[r + 1]] - 1 for r in range(P)])
+        back = [plan.back_runs(r) for r in range(P)]
+        for r in range(P):
+            for q in range(P):
+                if q == r:
+                    continue
+                sent_back = [(a, b) for dest, a, b in back[q][0] if dest == r]
+                expected = [(a, b) for src, a, b in back[r][1] if src == q]
+                assert sent_back == plan.runs[r][q] and expected == plan.runs[r][q], (trial, r, q)
+            me = r
+            assert back[me] == ([(r_, s0, s1) for r_ in range(plan.P) if r_ != me for s0, s1 in plan.runs[r_][me]],
+                                [(q, s0, s1) for q in range(plan.P) if q != me for s0, s1 in plan.runs[me][q]]), (trial, me)
+            assert all(peer != me for peer, _, _ in back[me][0] + back[me][1])
+            assert plan.back_runs(me) is back[me]                                          # memoised: an iteration does not rebuild it
+
+
+def test_slab_plan_covers_what_the_sources_reach():
+    """Pure bookkeeping: for random source sets, radii and rank counts, every plane a rank's sources can rate lies in
+    its reach, every reached plane of a foreign slab lies in the run sent to that slab's owner, the slabs partition
+    the planes, and the byte counts are symmetric between the two exchanges."""
+    from pyc2ray_amd.dist import SlabPlan, TorchComm
+    for trial, N, P, R, pos, flux in _random_plan_inputs():
+        ns = flux.shape[0]
         spos, sflux, bounds = TorchComm.shard_sources_by_slab(pos, flux, P)
         assert sorted(map(tuple, spos.T)) == sorted(map(tuple, pos.T)) and np.all(np.diff(spos[0]) >= 0)
         assert bounds[0] == 0 and bounds[-1] == ns and all(bounds[r + 1] - bounds[r] >= ns // P for r in range(P))
