@@ -365,6 +365,25 @@ int asora_thermal_stats(long long *cells_max_substeps, long long *cells_floored,
  * holds until it is set again or the device is re-initialised. */
 int asora_clumping(int mode, double constant);
 
+/* Lyman-limit-system (LLS) opacity: unresolved absorbers as a distributed photon sink of the raytrace (DESIGN.md section
+ * 4.1b).  The absorber density the raytrace sees becomes
+ *   n_abs = ndens ((1 - xh_av) + per_density) + n_const
+ * where it was ndens (1 - xh_av):
+ *   n_const      a uniform absorber density in cm^-3 (a proper mean free path lambda: n_const = 1 / (sig lambda))
+ *   per_density  absorbers per atom of the local density (dimensionless)
+ * Column densities accumulate the added opacity, and a cell's rate stays the photon-conserving share per absorber, so
+ * hydrogen receives n_HI / n_abs of the photons absorbed in the cell (the heating rate per HI atom likewise).  The
+ * chemistry keeps ndens and the rates per atom; R_max_LLS and the column-density cap apply to the total column.
+ * Every entry that forms the absorber density honours it: asora_raytrace_device, asora_raytrace_begin / _begin_planes,
+ * asora_do_all_sources, asora_debug_coldens, both sub-box entries, asora_evolve_begin / _enqueue and the
+ * asora_evolve_slab_* loop (asora_evolve_slab_nhi and the fused pass).  Set it before asora_evolve_begin(_slab) /
+ * asora_raytrace_begin: a step in progress forms its next nHI with the values of the moment.  (0, 0) is off, bit for bit
+ * the rates without the call.  Fails with code 3 for a value that is negative or not finite, with code 4 while grey opacity
+ * (ASORA_OPT_GREY_NOTABLES) is on; a trace begun with both on fails with code 4 as well.  The values hold until they are set
+ * again or the device is re-initialised. */
+int asora_lls_opacity(double n_const, double per_density);
+int asora_get_lls_opacity(double *n_const, double *per_density);
+
 /* ------------------------------------------------------------------------------------------ */
 /* C. Options, measurement and diagnostics                                                     */
 /* ------------------------------------------------------------------------------------------ */

@@ -100,6 +100,8 @@ SIGNATURES = {
     "asora_thermal_params": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, C.c_uint, C.c_int, C.c_double]),
     "asora_thermal_stats": (C.c_int, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
     "asora_clumping": (C.c_int, [C.c_int, C.c_double]),
+    "asora_lls_opacity": (C.c_int, [C.c_double, C.c_double]),
+    "asora_get_lls_opacity": (C.c_int, [_dp, _dp]),
     "asora_set_option": (C.c_int, [C.c_int, C.c_int]),
     "asora_get_option": (C.c_int, [C.c_int]),
     "asora_kernel_time_ms": (C.c_int, [C.c_int, _dp, C.POINTER(C.c_long)]),

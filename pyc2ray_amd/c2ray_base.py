@@ -20,6 +20,8 @@ Differences from the reference:
     ``use_mpi = pyc2ray_amd.dist.MPI`` (the heating rates are exchanged on the TorchComm's device loops only).
   * ``Material: clumping: C`` (optional key, default 1) and the attribute ``clumping`` (a float, or an (N, N, N) grid assigned
     between steps) set the sub-grid clumping factor of the recombination rate (evolve3D's ``clumping=``).
+  * ``Photo: LLS_mfp_pMpc`` / ``LLS_mfp_zref`` / ``LLS_mfp_index`` / ``LLS_per_density`` (optional keys) and the attribute ``lls``
+    add the opacity of unresolved Lyman-limit systems to the raytrace (pyc2ray_amd/lls.py; evolve3D's ``lls=``).
 """
 import atexit
 import re
@@ -35,6 +37,7 @@ except ImportError:  # pragma: no cover
 from .asora_core import cuda_is_init, device_close, device_init, photo_table_to_device, spectra_to_device
 from . import _capi, _residency
 from .evolve import evolve3D, evolve3D_MPI, evolve3D_resident
+from .lls import LLSOpacity, LLSSchedule, lls_spec
 from .load_extensions import load_asora
 from .radiation import BlackBodySource, make_tau_table
 from .raytracing import do_raytracing
@@ -215,6 +218,7 @@ class C2Ray:
         self._material_init()
         self._sources_init()
         self._radiation_init()
+        self._lls_init()
         if self.rank == 0:
             if self.gpu:
                 q_max = np.ceil(1.73205080757 * min(self.R_max_LLS, 1.73205080757 * self.N / 2))
@@ -287,6 +291,29 @@ class C2Ray:
         self.__dict__["_clumping"] = value
         self._host_newer.add("clumping")
 
+    def _lls_init(self):
+        """The optional ``Photo`` keys of :class:`pyc2ray_amd.lls.LLSSchedule` (none present: no LLS opacity, the reference's
+        behaviour): ``lls_schedule``, and from it the opacity at the run's starting redshift."""
+        self.lls_schedule = LLSSchedule.from_photo_keys(self._ld.get('Photo', {}), self.sig, self.zred_0)
+        self.__dict__["_lls"] = None
+        if self.lls_schedule is not None:
+            self.__dict__["_lls"] = self.lls_schedule.at(self.zred_0)
+            if self.rank == 0:
+                self.printlog(f"LLS opacity at z = {self.zred_0:.3f}: n_const = {self._lls.n_const:.3e} cm^-3, "
+                              f"per_density = {self._lls.per_density:.3e}")
+
+    @property
+    def lls(self):
+        """The LLS opacity of the next steps: None (off) or a :class:`pyc2ray_amd.lls.LLSOpacity`.  A driver may assign either
+        between steps.  In a cosmological run with the ``Photo: LLS_*`` keys, cosmo_evolve re-evaluates ``lls_schedule`` at the new
+        redshift and replaces it; set ``lls_schedule = None`` to keep an assigned value."""
+        return self.__dict__.get("_lls")
+
+    @lls.setter
+    def lls(self, value):
+        lls_spec(value, "C2Ray.lls")                            # ValueError for what evolve3D would refuse, now
+        self.__dict__["_lls"] = value
+
     def evolve3D(self, dt, src_flux, src_pos, src_spectrum=None):
         """Evolve the grid over one time step (c2ray_base.py:170-226).  src_spectrum: with ``BlackBodySource: Teff`` a list, the
         index into it of each source's temperature (None: every source the first one); see pyc2ray_amd.evolve3D."""
@@ -299,9 +326,10 @@ class C2Ray:
         thermal = self._thermal_params()
         if self.mpi and src_flux.shape[0] >= self.nprocs:
             result = evolve3D_MPI(*head, self.mpi, self.comm, self.rank, self.nprocs, *tail, thermal=thermal,
-                                  clumping=self.__dict__["_clumping"], src_spectrum=src_spectrum)
+                                  clumping=self.__dict__["_clumping"], src_spectrum=src_spectrum, lls=self.lls)
         else:
-            result = evolve3D(*head, *tail, thermal=thermal, clumping=self.__dict__["_clumping"], src_spectrum=src_spectrum)
+            result = evolve3D(*head, *tail, thermal=thermal, clumping=self.__dict__["_clumping"], src_spectrum=src_spectrum,
+                              lls=self.lls)
         self.xh, self.phi_ion = result[:2]
         if thermal is not None:
             self.temp = result[2]
@@ -363,7 +391,8 @@ class C2Ray:
             d["_grid_phi_ion"] = np.zeros(self.shape)           # the GPU path returns C-ordered rates (evolve.py:200)
         evolve3D_resident(dt, self.dr, src_flux, src_pos, uploads, self.N, self.photo_thin_table, self.minlogtau, self.dlogtau,
                           self.R_max_LLS, self.convergence_fraction, self.sig, self.bh00, self.albpow, self.colh0, self.temph0,
-                          self.abu_c, self.logfile, thermal=self._thermal_params(), clumping=clumping, src_spectrum=src_spectrum)
+                          self.abu_c, self.logfile, thermal=self._thermal_params(), clumping=clumping, src_spectrum=src_spectrum,
+                          lls=self.lls)
         self._host_newer -= {"ndens", "temp", "xh", "phi_ion", "clumping"}
         self._device_newer |= {"xh", "phi_ion"} if self.isothermal else {"xh", "phi_ion", "temp"}
 
@@ -396,6 +425,8 @@ class C2Ray:
             self.dr = self.dr_c * self._scale_factor(z_half)
         self.zred = z_half
         self.time = t_after
+        if self.cosmological and self.__dict__.get("lls_schedule") is not None:
+            self.__dict__["_lls"] = self.lls_schedule.at(self.zred)
 
     def printlog(self, s, quiet=False):
         if self.logfile is None:
@@ -434,7 +465,7 @@ class C2Ray:
         gamma = do_raytracing(self.dr, src_flux, src_pos, self.gpu, self.max_subbox, self.subboxsize,
                               self.loss_fraction, self.ndens, self.xh, self.photo_thin_table,
                               self.photo_thick_table, self.heat_thin_table, self.heat_thick_table, self.minlogtau,
-                              self.dlogtau, self.R_max_LLS, self.sig, self.logfile)
+                              self.dlogtau, self.R_max_LLS, self.sig, self.logfile, lls=self.lls)
         self.phi_ion = gamma[0]
         if gamma[1] is not None:
             self.phi_heat = gamma[1]

@@ -310,6 +310,12 @@ struct State {
     double clump_c = 1.0;
     double temp_probe_clump = 1.0;
 
+    // Lyman-limit-system opacity (asora_lls_opacity): the raytrace's absorber density is
+    // ndens ((1 - xh_av) + lls_b) + lls_a, formed wherever nHI is (launch_prepare_nhi*, launch_prepare_range, the emit forms of
+    // the fused pass through chem_tile_common).  Both 0: off.  coldens_only: asora_debug_coldens has borrowed the grey form
+    double lls_a = 0.0, lls_b = 0.0;
+    bool coldens_only = false;
+
     hipStream_t stream = nullptr;
     struct PendingTimer { int which; hipEvent_t e0, e1; };
     std::vector<PendingTimer> pending_timers;     // recorded, not yet resolved
@@ -482,6 +488,8 @@ struct ChemTileParams {
     // thermal form without fold (heating already summed over both layouts and over the ranks: the all-reduce loop): where the pass
     // keeps it, as phi_out keeps the rates (appended, so the fields above keep their offsets)
     double *heat_out = nullptr;
+    // emit: the Lyman-limit absorbers in the next trace's nHI (State::lls_a / lls_b, set by chem_tile_common)
+    double lls_a = 0.0, lls_b = 0.0;
 };
 int launch_grid_sum(State &st, const double *a, size_t n, double *out_dev);
 int launch_scale(State &st, double *a, size_t n, double factor);

@@ -10,7 +10,7 @@
 //
 // The reductions are two-stage and order-fixed (per-block partials, then one block), so every
 // rank of a multi-GPU run derives bit-identical convergence scalars from the same grids.
-#include "asora_internal.hpp"
+#include "rates_device.hpp"
 
 #include <algorithm>
 
@@ -463,7 +463,7 @@ __global__ void __launch_bounds__(CH_THREADS, 1) chemistry_tile_kernel(const Che
                 p.xh_av[idx] = xav;
                 sum1 += xint; sum0 += 1.0 - xint;                    // evolve.py:216-217
                 if (EMIT) {
-                    const double v = n * (1.0 - xav);                // raytracing.cu:276, for the next raytrace
+                    const double v = absorber_density(n, xav, p.lls_a, p.lls_b);   // raytracing.cu:276, for the next raytrace
                     p.nhi[idx] = v;
                     tile_n[r][tx] = v;
                 }

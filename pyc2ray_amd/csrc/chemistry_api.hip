@@ -1,5 +1,5 @@
 // chemistry_api.hip -- the chemistry passes as calls of their own (whole grid, a range of planes, the reference's global_pass),
-// their reductions, and the switches of the pass: thermal mode and clumping.
+// their reductions, and the switches of the pass: thermal mode, clumping and the Lyman-limit absorbers of the nHI it emits.
 #include "asora_internal.hpp"
 
 namespace asora {
@@ -40,6 +40,7 @@ ChemTileParams chem_tile_common(int i_begin, int i_count, const double chem[6])
     p.uniform = (st.temp_probe_valid && st.temp_probe[0] != 0.0 && !st.opt[ASORA_OPT_NO_UNIFORM_T]) ? 1 : 0;
     p.uniform_T = st.temp_probe[1]; p.uniform_brech0 = st.temp_probe[2]; p.uniform_acolh0 = st.temp_probe[3];
     p.uniform_t_ok = st.temp_probe[4] != 0.0 ? 1 : 0;
+    p.lls_a = st.lls_a; p.lls_b = st.lls_b;          // (the emit forms: nHI of the next trace as launch_prepare_nhi forms it)
     return p;
 }
 
@@ -221,6 +222,31 @@ int asora_clumping(int mode, double constant)
         return 0;
     }
     return fail(3, "clumping: mode must be 0 (off), 1 (constant) or 2 (per cell)");
+}
+
+// ---------------------------------------------------------------------------------------------
+// Lyman-limit-system opacity (include/asora_hip.h; rates_device.hpp: absorber_density)
+// ---------------------------------------------------------------------------------------------
+int asora_lls_opacity(double n_const, double per_density)
+{
+    clear_error();
+    State &st = state();
+    if (!(std::isfinite(n_const) && n_const >= 0.0 && std::isfinite(per_density) && per_density >= 0.0))
+        return fail(3, "lls_opacity: n_const and per_density must be finite and >= 0");
+    if (n_const == 0.0 && per_density == 0.0) { st.lls_a = st.lls_b = 0.0; return 0; }   // (also without a device: nothing to switch off)
+    if (int rc = require_init("lls_opacity")) return rc;
+    if (st.opt[ASORA_OPT_GREY_NOTABLES])
+        return fail(4, "lls_opacity: needs table rates (grey opacity, ASORA_OPT_GREY_NOTABLES, is on)");
+    st.lls_a = n_const; st.lls_b = per_density;
+    return 0;
+}
+
+int asora_get_lls_opacity(double *n_const, double *per_density)
+{
+    clear_error();
+    if (n_const) *n_const = state().lls_a;
+    if (per_density) *per_density = state().lls_b;
+    return 0;
 }
 
 int asora_thermal_stats(long long *cells_max_substeps, long long *cells_floored, int *max_substeps_used)

@@ -1,6 +1,6 @@
 // grid_kernels.hip -- the N^3 helper passes around the raytrace: nHI = ndens (1 - xh_av) in both layouts, the [i][j][k] <-> [k][j][i]
 // transposes, the folds of the z-faces' transposed rate accumulator.  All streaming, tiled 32 x 32 through LDS.
-#include "asora_internal.hpp"
+#include "rates_device.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -11,14 +11,15 @@ namespace asora {
 // N^3 helper kernels
 // ---------------------------------------------------------------------------------------------
 
-// nhi[i][j][k] = ndens*(1-xh_av);  nhi_t[k][j][i] = same (tiled transpose of the (i,k) planes), for the planes
-// [i_begin, i_end).  block (32,8): tile 32(i) x 32(k) of one j.  ZERO: also zero both layouts of an accumulator
+// nhi[i][j][k] = ndens*(1-xh_av), plus the Lyman-limit absorbers lls_a + lls_b*ndens of asora_lls_opacity (absorber_density);
+// nhi_t[k][j][i] = same (tiled transpose of the (i,k) planes), for the planes [i_begin, i_end).
+// block (32,8): tile 32(i) x 32(k) of one j.  ZERO: also zero both layouts of an accumulator
 // on those planes (a multi-GPU rank only touches the planes its sources reach).
 template <bool WITH_T, bool ZERO>
 __global__ void __launch_bounds__(256) prepare_nhi_kernel(const double *__restrict__ nd, const double *__restrict__ xh,
                                                           double *__restrict__ nhi, double *__restrict__ nhi_t, int N,
                                                           int i_begin, int i_end, double *__restrict__ acc, size_t ncell,
-                                                          const int *__restrict__ done = nullptr)
+                                                          double lls_a, double lls_b, const int *__restrict__ done = nullptr)
 {
     if (done && *done) return;                                  // device loop: the time step has converged
     __shared__ double tile[32][33];
@@ -28,7 +29,7 @@ __global__ void __launch_bounds__(256) prepare_nhi_kernel(const double *__restri
         const int i = ib + r, k = kb + threadIdx.x;
         if (i < i_end && k < N) {
             const size_t idx = ((size_t)i * N + j) * N + k;
-            const double v = nd[idx] * (1.0 - xh[idx]);       // raytracing.cu:276
+            const double v = absorber_density(nd[idx], xh[idx], lls_a, lls_b);     // raytracing.cu:276
             nhi[idx] = v;
             if (ZERO) acc[idx] = 0.0;
             if (WITH_T) tile[r][threadIdx.x] = v;
@@ -70,16 +71,28 @@ __global__ void __launch_bounds__(256) transpose_ik_kernel(const double *__restr
 
 static dim3 tile_grid(int N) { const unsigned t = (N + 31) / 32; return dim3(t, N, t); }
 
+// Lyman-limit absorbers (asora_lls_opacity) go with table rates only: the grey rates' share per absorber is neither derived nor
+// tested.  (asora_debug_coldens borrows the grey form when no tables are loaded and keeps its column densities alone.)
+static int check_lls_form(const State &st)
+{
+    if ((st.lls_a != 0.0 || st.lls_b != 0.0) && st.opt[ASORA_OPT_GREY_NOTABLES] && !st.coldens_only)
+        return fail(4, "raytrace: Lyman-limit-system opacity (asora_lls_opacity) needs table rates (ASORA_OPT_GREY_NOTABLES = 0)");
+    return 0;
+}
+
 int launch_prepare_nhi_from(State &st, const double *xh_av, bool need_transposed)
 {
+    if (int rc = check_lls_form(st)) return rc;
     KernelTimer kt(ASORA_KERNEL_PREP);
     const int N = st.N;
     if (need_transposed)
         hipLaunchKernelGGL((prepare_nhi_kernel<true, false>), tile_grid(N), dim3(32, 8), 0, st.stream,
-                           st.grid[ASORA_GRID_NDENS], xh_av, st.nhi, st.nhi_t, N, 0, N, (double *)nullptr, st.ncell, (const int *)nullptr);
+                           st.grid[ASORA_GRID_NDENS], xh_av, st.nhi, st.nhi_t, N, 0, N, (double *)nullptr, st.ncell, st.lls_a, st.lls_b,
+                           (const int *)nullptr);
     else
         hipLaunchKernelGGL((prepare_nhi_kernel<false, false>), tile_grid(N), dim3(32, 8), 0, st.stream,
-                           st.grid[ASORA_GRID_NDENS], xh_av, st.nhi, st.nhi_t, N, 0, N, (double *)nullptr, st.ncell, (const int *)nullptr);
+                           st.grid[ASORA_GRID_NDENS], xh_av, st.nhi, st.nhi_t, N, 0, N, (double *)nullptr, st.ncell, st.lls_a, st.lls_b,
+                           (const int *)nullptr);
     ASORA_HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -93,16 +106,19 @@ int launch_prepare_nhi(State &st, bool need_transposed)
 int launch_prepare_range(State &st, int i_begin, int i_count, bool zero_acc, double *acc, const int *done)
 {
     if (i_count <= 0) return 0;
+    if (int rc = check_lls_form(st)) return rc;
     KernelTimer kt(ASORA_KERNEL_PREP);
     const int N = st.N;
     const unsigned t = (N + 31) / 32;
     const dim3 grid(t, N, (i_count + 31) / 32);
     if (zero_acc)
         hipLaunchKernelGGL((prepare_nhi_kernel<true, true>), grid, dim3(32, 8), 0, st.stream, st.grid[ASORA_GRID_NDENS],
-                           st.grid[ASORA_GRID_XH_AV], st.nhi, st.nhi_t, N, i_begin, i_begin + i_count, acc, st.ncell, done);
+                           st.grid[ASORA_GRID_XH_AV], st.nhi, st.nhi_t, N, i_begin, i_begin + i_count, acc, st.ncell,
+                           st.lls_a, st.lls_b, done);
     else
         hipLaunchKernelGGL((prepare_nhi_kernel<true, false>), grid, dim3(32, 8), 0, st.stream, st.grid[ASORA_GRID_NDENS],
-                           st.grid[ASORA_GRID_XH_AV], st.nhi, st.nhi_t, N, i_begin, i_begin + i_count, acc, st.ncell, done);
+                           st.grid[ASORA_GRID_XH_AV], st.nhi, st.nhi_t, N, i_begin, i_begin + i_count, acc, st.ncell,
+                           st.lls_a, st.lls_b, done);
     ASORA_HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -107,6 +107,16 @@ __device__ __forceinline__ double add_unfused(double a, double b)
     return a + b;
 }
 
+// The absorber density the raytrace sees: neutral hydrogen plus the unresolved Lyman-limit systems of
+// asora_lls_opacity, n_abs = n ((1 - x) + b) + a.  Written once, for prepare_nhi_kernel and the fused pass alike, and without
+// contraction: each of the four operations is rounded on its own, so both sites -- and a host restatement -- form the same bits.
+// a = b = 0 gives n (1 - x) exactly: (1 - x) + 0 and n (1 - x) + 0 change no bit of a value >= +0, and NaN stays NaN.
+__device__ __forceinline__ double absorber_density(double n, double x, double a, double b)
+{
+#pragma clang fp contract(off)
+    return n * ((1.0 - x) + b) + a;
+}
+
 // x / y for finite y != 0 of ordinary magnitude: hardware reciprocal, Newton on the reciprocal, one correction of the
 // quotient -- 6 instructions instead of the 12 of the IEEE sequence (v_div_scale x 2, v_div_fmas, v_div_fixup guard against
 // operands near the ends of the exponent range, which column densities, interpolation weights and cell volumes are not).

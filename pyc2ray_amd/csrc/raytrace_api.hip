@@ -444,9 +444,9 @@ int asora_debug_coldens(double R, double sig, double dr, int source_index, doubl
     // the column density does not depend on the tables: trace with whatever is loaded
     const int numtau = st.table_len > 0 ? st.table_len : 1;
     const int grey_save = st.opt[ASORA_OPT_GREY_NOTABLES];
-    if (!st.tables) st.opt[ASORA_OPT_GREY_NOTABLES] = 1;
+    if (!st.tables) { st.opt[ASORA_OPT_GREY_NOTABLES] = 1; st.coldens_only = true; }
     int rc = do_raytrace(R, sig, dr, source_index, 1, -20.0, 1.0, numtau, st.staging);
-    st.opt[ASORA_OPT_GREY_NOTABLES] = grey_save;
+    st.opt[ASORA_OPT_GREY_NOTABLES] = grey_save; st.coldens_only = false;
     if (rc) return rc;
     ASORA_HIP_TRY(hipMemcpyAsync(coldens_out, st.staging, bytes, hipMemcpyDeviceToHost, st.stream));
     ASORA_HIP_TRY(hipStreamSynchronize(st.stream));

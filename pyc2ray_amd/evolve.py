@@ -18,6 +18,7 @@ import numpy as np
 
 from . import _capi, _residency
 from .asora_core import cuda_is_init
+from .lls import lls_reset, lls_spec
 from .load_extensions import load_asora, load_c2ray
 from .spectra import source_spectrum_spec
 from .utils import printlog
@@ -142,14 +143,16 @@ def _spectra_along(reorder, *args, spec):
 
 
 def _prologue(libasora, scalars, N, NumTau, src_flux, my_pos, my_flux, uploads, clump, *, ranks=_ONE_RANK,
-              calling="Calling evolve3D...", xh_copies=False, say_copied=False, clump_upload=True, tables=None, spec=None):
+              calling="Calling evolve3D...", xh_copies=False, say_copied=False, clump_upload=True, tables=None, spec=None,
+              lls=None):
     """What every form of the step does before its loop: the convergence criterion, this rank's sources (`my_pos`, `my_flux`)
     and the grids of `uploads` ({grid selector: host array}) to the device, the clumping mode, and the header lines of
     evolve.py:156-162 on rank 0.  Returns the :class:`_Step`.  The forms differ in: `calling`, the first header line;
     `xh_copies`, xh_av = xh_intermed = xh made here (the one-GPU device loop makes its own); `say_copied`, the line of the
     reference's one-process GPU branch; `clump_upload=False`, a clumping grid is among `uploads` or on the device already;
     `tables` = (thin, thick), use_gpu=False: that branch has no device_init of its own in the reference, so the library sets itself
-    up for the mesh here; `spec`, the spectra of `my_pos` (None: all 0, nothing more is uploaded)."""
+    up for the mesh here; `spec`, the spectra of `my_pos` (None: all 0, nothing more is uploaded); `lls`, the LLS opacity of the
+    raytrace (None: off), set like the clumping mode: after the uploads, the same on every rank."""
     NumSrc, n_local, NumCells = src_flux.shape[0], my_flux.shape[0], N * N * N
     logfile, quiet, rank = scalars["logfile"], scalars["quiet"], ranks[2]
     # evolve.py:127 (computed from the TOTAL source count, evolve.py:346)
@@ -175,6 +178,8 @@ def _prologue(libasora, scalars, N, NumTau, src_flux, my_pos, my_flux, uploads, 
         printlog("Copied source data to device.", logfile, quiet)
     if clump is not None:
         clump.apply(libasora, upload=clump_upload)                     # (every rank uploads the whole grid, as ndens)
+    if lls is not None:
+        lls.apply(libasora)
 
     if rank == 0:
         printlog(calling, logfile, quiet)
@@ -187,6 +192,8 @@ def _prologue(libasora, scalars, N, NumTau, src_flux, my_pos, my_flux, uploads, 
         printlog(f"Mean density (cgs): {mean_ndens:.3e}, Mean ionized fraction: {mean_xh:.3e}", logfile, quiet)
         if clump is not None:
             clump.log(libasora, NumCells, logfile, quiet)
+        if lls is not None:
+            lls.log(logfile, quiet)
         printlog(f"Convergence Criterion (Number of points): {conv_criterion : n}", logfile, quiet, end='\n\n')
     return step
 
@@ -452,7 +459,7 @@ def _scalars(dt, dr, R_max_LLS, convergence_fraction, sig, minlogtau, dlogtau, c
 
 def evolve3D_resident(dt, dr, src_flux, src_pos, uploads, N, photo_thin_table, minlogtau, dlogtau, R_max_LLS,
                       convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile="pyC2Ray.log", quiet=False,
-                      thermal=None, clumping=None, src_spectrum=None):
+                      thermal=None, clumping=None, src_spectrum=None, lls=None):
     """evolve3D for a caller that keeps the grids on the device between time steps (the C2Ray class with
     ``device_resident = True``): same loop, log lines and results as :func:`evolve3D` with ``use_gpu=True``, but only the
     grids in ``uploads`` ({grid selector: host array}, those the caller changed on the host) cross PCIe, and nothing
@@ -462,7 +469,8 @@ def evolve3D_resident(dt, dr, src_flux, src_pos, uploads, N, photo_thin_table, m
     end-of-step temperature afterwards, PHI_HEAT the heating rates.
     ``clumping`` as in :func:`evolve3D`; like the other grids, an (N, N, N) grid crosses PCIe only when ``uploads`` holds it
     (under ``_capi.GRID_CLUMP``, checked then): otherwise GRID_CLUMP must still hold it from an earlier step.
-    ``src_spectrum`` as in :func:`evolve3D`."""
+    ``src_spectrum`` and ``lls`` as in :func:`evolve3D`."""
+    lls = lls_spec(lls, "evolve3D_resident")
     spec = source_spectrum_spec(src_spectrum, src_flux.shape[0], True, lambda: load_asora().num_spectra(), "evolve3D_resident")
     clump = _clumping_spec(clumping, N, check_values=_capi.GRID_CLUMP in uploads)
     if clump is not None and clump.grid is not None and _capi.GRID_CLUMP in uploads and uploads[_capi.GRID_CLUMP] is not clumping:
@@ -471,14 +479,14 @@ def evolve3D_resident(dt, dr, src_flux, src_pos, uploads, N, photo_thin_table, m
         raise RuntimeError("GPU not initialized. Please initialize it by calling device_init(N)")
     scalars = _scalars(dt, dr, R_max_LLS, convergence_fraction, sig, minlogtau, dlogtau, (bh00, albpow, colh0, temph0, abu_c),
                        logfile, quiet)
-    with _clumping_reset(clump):
-        return _evolve_resident(scalars, src_flux, src_pos, uploads, N, photo_thin_table, thermal, clump, spec)
+    with _clumping_reset(clump), lls_reset(lls, load_asora):
+        return _evolve_resident(scalars, src_flux, src_pos, uploads, N, photo_thin_table, thermal, clump, spec, lls)
 
 
-def _evolve_resident(scalars, src_flux, src_pos, uploads, N, photo_thin_table, thermal, clump, spec=None):
+def _evolve_resident(scalars, src_flux, src_pos, uploads, N, photo_thin_table, thermal, clump, spec=None, lls=None):
     libasora = load_asora()
     step = _prologue(libasora, scalars, N, photo_thin_table.shape[0], src_flux, np.asarray(src_pos), src_flux, uploads, clump,
-                     say_copied=True, clump_upload=False, spec=spec)
+                     say_copied=True, clump_upload=False, spec=spec, lls=lls)
     niter = _one_gpu_loop(libasora, step, thermal)
     printlog("Multiple source convergence reached.", step.logfile, step.quiet)
     libasora.grid_copy(_capi.GRID_XH, _capi.GRID_XH_INTERMED)       # the next step starts from the new ionised fraction
@@ -501,7 +509,7 @@ def _thermal_ranks_refusal(comm):
     return None
 
 
-def _evolve(scalars, src_flux, src_pos, grids, photo_thin_table, ranks=_ONE_RANK, thermal=None, clump=None, spec=None):
+def _evolve(scalars, src_flux, src_pos, grids, photo_thin_table, ranks=_ONE_RANK, thermal=None, clump=None, spec=None, lls=None):
     """A use_gpu=True step on host arrays, grids = (temp, ndens, xh), on one GPU or across `ranks`; `thermal` on one GPU, or
     across ranks on the "slab" and "all-reduce" device loops; `spec`, the spectrum of each source of the whole list (None: all 0),
     which follows its source through every re-ordering and sharding below."""
@@ -537,7 +545,7 @@ def _evolve(scalars, src_flux, src_pos, grids, photo_thin_table, ranks=_ONE_RANK
     step = _prologue(libasora, scalars, N, photo_thin_table.shape[0], src_flux, my_pos, my_flux,
                      {_capi.GRID_NDENS: ndens, _capi.GRID_TEMP: temp, _capi.GRID_XH: xh}, clump, ranks=ranks,
                      calling=f"Calling evolve3D with {nprocs:n} MPI-processors..." if distributed else "Calling evolve3D...",
-                     xh_copies=distributed, say_copied=not distributed, spec=my_spec)
+                     xh_copies=distributed, say_copied=not distributed, spec=my_spec, lls=lls)
     if strategy == "one GPU":
         niter = _one_gpu_loop(libasora, step, thermal)
     elif strategy == "slab":
@@ -570,7 +578,7 @@ def _evolve(scalars, src_flux, src_pos, grids, photo_thin_table, ranks=_ONE_RANK
     return xh_new, phi_ion
 
 
-def _evolve_cpu_semantics(scalars, src_flux, src_pos, grids, tables, subbox, ranks=_ONE_RANK, clump=None):
+def _evolve_cpu_semantics(scalars, src_flux, src_pos, grids, tables, subbox, ranks=_ONE_RANK, clump=None, lls=None):
     """The use_gpu=False branch of the reference on host arrays: the loop of :func:`_subbox_loop`, subbox = (max_subbox,
     subboxsize, loss_fraction).  Like the use_gpu=True loop this one keeps the grids on the device for the whole step (the
     reference's host round trips are what ``libc2ray.raytracing.do_all_sources`` / ``libc2ray.chemistry.global_pass`` of this
@@ -582,7 +590,7 @@ def _evolve_cpu_semantics(scalars, src_flux, src_pos, grids, tables, subbox, ran
     my_pos, my_flux, _ = _contiguous_shard(src_pos, src_flux, ranks)
     step = _prologue(libasora, scalars, N, tables[0].shape[0], src_flux, my_pos, my_flux,
                      {_capi.GRID_NDENS: ndens, _capi.GRID_TEMP: temp, _capi.GRID_XH: xh}, clump,
-                     ranks=ranks, xh_copies=True, tables=tables)
+                     ranks=ranks, xh_copies=True, tables=tables, lls=lls)
     niter = _subbox_loop(libasora, step, subbox, ranks)
     if step.rank == 0:
         printlog("Multiple source convergence reached.", step.logfile, step.quiet)
@@ -601,7 +609,7 @@ def evolve3D(dt, dr,
              minlogtau, dlogtau,
              R_max_LLS, convergence_fraction,
              sig, bh00, albpow, colh0, temph0, abu_c,
-             logfile="pyC2Ray.log", quiet=False, *, thermal=None, clumping=None, src_spectrum=None):
+             logfile="pyC2Ray.log", quiet=False, *, thermal=None, clumping=None, src_spectrum=None, lls=None):
     """Evolve the ionised fraction of the whole grid over one time step.
 
     Parameters have the reference's meaning (pyc2ray/evolve.py:49-109): dt [s], dr [cm],
@@ -629,18 +637,25 @@ def evolve3D(dt, dr,
     None or all zeros (the reference's one spectrum: nothing more is uploaded), or an integer array of length numsrc with values
     in [0, num_spectra()).  Anything else, or a non-zero entry with use_gpu=False, raises ValueError before any GPU work.  With
     `thermal` the heating tables of every set must have gone up with ``spectra_to_device``.
+
+    lls : None (off) or a :class:`pyc2ray_amd.lls.LLSOpacity`: unresolved Lyman-limit systems as a distributed photon sink of the
+    raytrace (DESIGN.md section 4.1b).  The absorber density of the raytrace becomes ndens ((1 - xh_av) + per_density) + n_const;
+    the chemistry is unchanged.  Anything else, a negative or a non-finite value raises ValueError before any GPU work.  Works with
+    use_gpu=False, `thermal`, `clumping` and `src_spectrum`.
     """
+    lls = lls_spec(lls, "evolve3D")
     spec = source_spectrum_spec(src_spectrum, src_flux.shape[0], use_gpu, lambda: load_asora().num_spectra(), "evolve3D")
     clump = _clumping_spec(clumping, np.shape(temp)[0])
     if not use_gpu and thermal is not None:
         raise ValueError("evolve3D: the thermal mode needs use_gpu=True (the use_gpu=False raytracer has no thermal form)")
     scalars = _scalars(dt, dr, R_max_LLS, convergence_fraction, sig, minlogtau, dlogtau, (bh00, albpow, colh0, temph0, abu_c),
                        logfile, quiet)
-    with _clumping_reset(clump):
+    with _clumping_reset(clump), lls_reset(lls, load_asora):
         if use_gpu:
-            return _evolve(scalars, src_flux, src_pos, (temp, ndens, xh), photo_thin_table, thermal=thermal, clump=clump, spec=spec)
+            return _evolve(scalars, src_flux, src_pos, (temp, ndens, xh), photo_thin_table, thermal=thermal, clump=clump, spec=spec,
+                           lls=lls)
         return _evolve_cpu_semantics(scalars, src_flux, src_pos, (temp, ndens, xh), (photo_thin_table, photo_thick_table),
-                                     (max_subbox, subboxsize, loss_fraction), clump=clump)
+                                     (max_subbox, subboxsize, loss_fraction), clump=clump, lls=lls)
 
 
 def evolve3D_MPI(dt, dr,
@@ -652,7 +667,7 @@ def evolve3D_MPI(dt, dr,
                  minlogtau, dlogtau,
                  R_max_LLS, convergence_fraction,
                  sig, bh00, albpow, colh0, temph0, abu_c,
-                 logfile="pyC2Ray.log", quiet=False, *, thermal=None, clumping=None, src_spectrum=None):
+                 logfile="pyC2Ray.log", quiet=False, *, thermal=None, clumping=None, src_spectrum=None, lls=None):
     """Source-sharded variant (pyc2ray/evolve.py:249-498): rank r traces the contiguous block
     [r*(Ns//nprocs), (r+1)*(Ns//nprocs)) of the source list, the last rank to the end
     (evolve.py:362-367); the per-rank rate grids are summed across ranks each iteration.
@@ -671,7 +686,9 @@ def evolve3D_MPI(dt, dr,
     work; use_gpu=False has no thermal form.
     ``clumping`` as in :func:`evolve3D`; every rank passes (and uploads) the whole grid, as it does ``ndens``.
     ``src_spectrum`` as in :func:`evolve3D`, for the whole source list; a rank's shard of the sources takes its shard of it.
+    ``lls`` as in :func:`evolve3D`; every rank passes the same one and sets the same state, on every loop.
     """
+    lls = lls_spec(lls, "evolve3D_MPI")
     spec = source_spectrum_spec(src_spectrum, src_flux.shape[0], use_gpu, lambda: load_asora().num_spectra(), "evolve3D_MPI")
     if thermal is not None:
         if not use_gpu:
@@ -684,9 +701,9 @@ def evolve3D_MPI(dt, dr,
     scalars = _scalars(dt, dr, R_max_LLS, convergence_fraction, sig, minlogtau, dlogtau, (bh00, albpow, colh0, temph0, abu_c),
                        logfile, quiet)
     ranks = (use_mpi, comm, rank, nprocs)
-    with _clumping_reset(clump):
+    with _clumping_reset(clump), lls_reset(lls, load_asora):
         if use_gpu:
             return _evolve(scalars, src_flux, src_pos, (temp, ndens, xh), photo_thin_table, ranks, thermal=thermal, clump=clump,
-                           spec=spec)
+                           spec=spec, lls=lls)
         return _evolve_cpu_semantics(scalars, src_flux, src_pos, (temp, ndens, xh), (photo_thin_table, photo_thick_table),
-                                     (max_subbox, subboxsize, loss_fraction), ranks, clump=clump)
+                                     (max_subbox, subboxsize, loss_fraction), ranks, clump=clump, lls=lls)

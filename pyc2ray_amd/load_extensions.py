@@ -408,6 +408,16 @@ class _LibAsora:
         cell from GRID_CLUMP (upload it first)."""
         _capi.check(self._lib.asora_clumping(int(mode), float(constant)), "clumping")
 
+    def lls_opacity(self, n_const, per_density):
+        """Lyman-limit-system opacity of the raytrace (include/asora_hip.h, asora_lls_opacity): the absorber density becomes
+        ndens ((1 - xh_av) + per_density) + n_const; (0, 0) is off."""
+        _capi.check(self._lib.asora_lls_opacity(float(n_const), float(per_density)), "lls_opacity")
+
+    def get_lls_opacity(self):
+        a, b = C.c_double(0.0), C.c_double(0.0)
+        _capi.check(self._lib.asora_get_lls_opacity(C.byref(a), C.byref(b)), "get_lls_opacity")
+        return a.value, b.value
+
     def thermal_stats(self):
         """(cells that hit max_substeps, cells clamped to t_floor, most substeps of one integration) since the last
         chemistry_device / evolve_begin."""

@@ -5,6 +5,7 @@ import numpy as np
 
 from . import _capi, _residency
 from .asora_core import cuda_is_init
+from .lls import lls_reset, lls_spec
 from .load_extensions import load_asora, load_c2ray
 from .spectra import source_spectrum_spec
 from .utils import printlog
@@ -22,7 +23,7 @@ def do_raytracing(dr,
                   minlogtau, dlogtau,
                   R_max_LLS,
                   sig,
-                  logfile="pyC2Ray.log", quiet=False, stats=False, src_spectrum=None):
+                  logfile="pyC2Ray.log", quiet=False, stats=False, src_spectrum=None, lls=None):
     """Raytrace all sources once and return the photo-ionisation rate grid.
 
     Same 17 positional arguments as the reference (pyc2ray/raytracing.py:34-43).  Returns
@@ -39,12 +40,25 @@ def do_raytracing(dr,
     ``src_spectrum``: as in :func:`pyc2ray_amd.evolve3D` -- which table set on the device (``spectra_to_device``) each source
     shines with.  With several sets on the device the heating tables went up with them: heat_*_table only say whether the heating
     rate is wanted.
+
+    ``lls``: as in :func:`pyc2ray_amd.evolve3D` -- None or a :class:`pyc2ray_amd.lls.LLSOpacity`, the unresolved Lyman-limit
+    systems among the absorbers the rays cross.
     """
+    lls = lls_spec(lls, "do_raytracing")
     spec = source_spectrum_spec(src_spectrum, src_flux.shape[0], use_gpu, lambda: load_asora().num_spectra(), "do_raytracing")
     if use_gpu and not cuda_is_init():
         raise RuntimeError("GPU not initialized. Please initialize it by calling device_init(N)")
     _residency.reclaim()              # this call overwrites device grids a resident C2Ray object may be relying on
 
+    with lls_reset(lls, load_asora):
+        return _do_raytracing(dr, src_flux, src_pos, use_gpu, max_subbox, subboxsize, loss_fraction, ndens, xh_av, photo_thin_table,
+                              photo_thick_table, heat_thin_table, heat_thick_table, minlogtau, dlogtau, R_max_LLS, sig, logfile,
+                              quiet, stats, spec, lls)
+
+
+def _do_raytracing(dr, src_flux, src_pos, use_gpu, max_subbox, subboxsize, loss_fraction, ndens, xh_av, photo_thin_table,
+                   photo_thick_table, heat_thin_table, heat_thick_table, minlogtau, dlogtau, R_max_LLS, sig, logfile, quiet, stats,
+                   spec, lls):
     NumSrc = src_flux.shape[0]
     N = ndens.shape[0]
     NumTau = photo_thin_table.shape[0]
@@ -53,6 +67,11 @@ def do_raytracing(dr,
     printlog(f"Running on {NumSrc:n} source(s), total normalized ionizing flux: {src_flux.sum():.2e}", logfile, quiet)
     if not use_gpu:
         printlog(f"Mean density (cgs): {ndens.mean():.3e}, Mean ionized fraction: {xh_av.mean():.3e}", logfile, quiet)
+        if lls is not None:
+            # the library call below sets the device up for the mesh only where nothing is set up yet, which would reset the state
+            load_asora().device_init_auto(N)
+            lls.apply(load_asora())
+            lls.log(logfile, quiet)
         trt0 = time.time()
         printlog("Doing Raytracing...", logfile, quiet, ' ')
         phi_ion = np.zeros((N, N, N), order='F')                      # raytracing.py:80-83
@@ -79,6 +98,9 @@ def do_raytracing(dr,
     printlog(f"Mean density (cgs): {libasora.grid_sum(_capi.GRID_NDENS) / N ** 3:.3e}, "
              f"Mean ionized fraction: {libasora.grid_sum(_capi.GRID_XH_AV) / N ** 3:.3e}", logfile, quiet)
     printlog("Copied source data to device.", logfile, quiet)
+    if lls is not None:
+        lls.apply(libasora)
+        lls.log(logfile, quiet)
 
     # photo-heating: only when real heating tables are passed (the reference's callers pass zeros when
     # compute_heating_rates is off, c2ray_base.py:430-431)
