@@ -415,8 +415,10 @@ __global__ void __launch_bounds__(CH_THREADS, 1) chemistry_tile_kernel(const Che
     TempFactors tf;
     if (UNIFORM_T) { tf.T = p.uniform_T; tf.brech0 = p.uniform_brech0; tf.acolh0 = p.uniform_acolh0; tf.t_ok = p.uniform_t_ok != 0; }
     for (int j = blockIdx.y; j < N; j += gridDim.y) {
+        // the tiles of the previous j have been consumed: tile_g / tile_h by the main loop (FOLD), tile_n by the transposed
+        // nhi_t store that ends a trip (EMIT) -- without FOLD that store is the last LDS read before the next trip's writes
+        if ((FOLD || EMIT) && j != (int)blockIdx.y) __syncthreads();
         if (FOLD) {
-            if (j != (int)blockIdx.y) __syncthreads();             // the tiles of the previous j have been consumed
             for (int r = ty; r < 32; r += 8) {
                 const int k = kb + r, i = ib + tx;
                 if (k < N && i < p.i_end) {

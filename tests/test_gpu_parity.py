@@ -47,6 +47,14 @@ def _setup(p, lib, c, N):
     return pos0, flux
 
 
+def _cells_within(N, R):
+    """Cells one source rates: offsets within R inside the periodic window -floor(N/2) .. floor(N/2) - 1 + N % 2 of each axis
+    (raytracing.cu:122-123,315), as tests/test_gpu_configs.py counts them for R < N / 2."""
+    m = int(np.floor(R)) if np.isfinite(R) else N
+    d = np.arange(-min(m, N // 2), min(m, N // 2 - 1 + N % 2) + 1)
+    return int(((d[:, None, None] ** 2 + d[None, :, None] ** 2 + d[None, None, :] ** 2) <= R * R).sum())
+
+
 def _asora_call(lib, c, N, numtau):
     xh_flat = np.ravel(c["xh"]).astype("float64", copy=True)
     phi_flat = np.ravel(np.zeros((N, N, N)))
@@ -77,7 +85,10 @@ def test_raytrace_matches_oracle_and_reference(asora, name, tables):
     np.testing.assert_allclose(phi, ref["phi_ion"], rtol=GAMMA_RTOL, atol=0)
     np.testing.assert_allclose(phi, gold, rtol=1e-5, atol=0)            # north-star bar vs the Fortran
     gam, ev = lib.last_raytrace_counts()
-    assert gam == int((ref["phi_ion"] != 0).sum()) or flux.shape[0] > 1
+    # every (source, cell) pair that receives a rate: the cells within R inside the periodic window, per source
+    assert gam == flux.shape[0] * _cells_within(N, c["R"])
+    if flux.shape[0] == 1:
+        assert gam == int((ref["phi_ion"] != 0).sum())
     assert ev >= gam
 
     # Fortran constants: agrees with the reference Fortran output to rounding
