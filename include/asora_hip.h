@@ -475,7 +475,17 @@ enum {
      * stays within an eighth of the free device memory, and the probe stops once it holds a placement 7 % faster than another.
      * Same results on any placement. */
     ASORA_OPT_PLACEMENT_CANDIDATES = 17,
-    ASORA_OPT_COUNT = 18
+    /* 1: open (non-periodic) boundaries for the whole-box raytrace.  A cell whose unwrapped position i0 + di, j0 + dj, k0 + dk
+     *    lies outside [0, N) on any axis receives no rate from that source and is not counted -- the reference's CUDA kernel
+     *    built without -D PERIODIC (in_box_gpu, src/asora/raytracing.cu:264-267).  0 (default): every trace wraps around the box.
+     *    Read when a trace or a step of the device loop begins (asora_raytrace_device, asora_raytrace_begin[_planes],
+     *    asora_do_all_sources, asora_evolve_begin[_slab[_thermal]]).  The reach stays the periodic window's, offsets
+     *    -N/2 ... N/2 - 1 + N % 2 per axis, as in the reference.  Built for table rates through buffer atomics on meshes of
+     *    N <= 512; refused with code 4 before anything is launched: larger meshes, ASORA_OPT_GREY_NOTABLES,
+     *    ASORA_OPT_GLOBAL_ATOMICS, asora_debug_coldens and the sub-box sweep (c2ray_do_all_sources,
+     *    asora_subbox_raytrace_device: the reference's Fortran has no such mode). */
+    ASORA_OPT_OPEN_BOUNDARIES = 18,
+    ASORA_OPT_COUNT = 19
 };
 int asora_set_option(int option, int value);
 int asora_get_option(int option);
@@ -511,7 +521,8 @@ enum {
     ASORA_VARIANT_BUFFER_ATOMICS = 4,     /* rate atomics through buffer descriptors (else global_atomic_add_f64 under a branch) */
     ASORA_VARIANT_SPLIT_DESCRIPTORS = 8,  /* N > 512: one descriptor per layout of the rate grid */
     ASORA_VARIANT_SKIP_ZERO = 16,         /* the form that leaves exact-zero rates out */
-    ASORA_VARIANT_GLOBAL_SHELLS = 32      /* shell buffers in global memory (they exceed LDS) */
+    ASORA_VARIANT_GLOBAL_SHELLS = 32,     /* shell buffers in global memory (they exceed LDS) */
+    ASORA_VARIANT_OPEN_BOUNDARIES = 64    /* the open-boundary form (ASORA_OPT_OPEN_BOUNDARIES) */
 };
 int asora_last_raytrace_variant(void);
 

@@ -22,6 +22,8 @@ Differences from the reference:
     between steps) set the sub-grid clumping factor of the recombination rate (evolve3D's ``clumping=``).
   * ``Photo: LLS_mfp_pMpc`` / ``LLS_mfp_zref`` / ``LLS_mfp_index`` / ``LLS_per_density`` (optional keys) and the attribute ``lls``
     add the opacity of unresolved Lyman-limit systems to the raytrace (pyc2ray_amd/lls.py; evolve3D's ``lls=``).
+  * ``Raytracing: periodic: 0|1`` (optional key, default 1) and the attribute ``periodic`` (a bool, assignable between steps)
+    choose between traces that wrap around the box and open boundaries (evolve3D's ``periodic=``; use_gpu only).
 """
 import atexit
 import re
@@ -37,6 +39,7 @@ except ImportError:  # pragma: no cover
 from .asora_core import cuda_is_init, device_close, device_init, photo_table_to_device, spectra_to_device
 from . import _capi, _residency
 from .evolve import evolve3D, evolve3D_MPI, evolve3D_resident
+from .boundaries import periodic_spec
 from .lls import LLSOpacity, LLSSchedule, lls_spec
 from .load_extensions import load_asora
 from .radiation import BlackBodySource, make_tau_table
@@ -219,6 +222,7 @@ class C2Ray:
         self._sources_init()
         self._radiation_init()
         self._lls_init()
+        self._boundaries_init()
         if self.rank == 0:
             if self.gpu:
                 q_max = np.ceil(1.73205080757 * min(self.R_max_LLS, 1.73205080757 * self.N / 2))
@@ -314,6 +318,28 @@ class C2Ray:
         lls_spec(value, "C2Ray.lls")                            # ValueError for what evolve3D would refuse, now
         self.__dict__["_lls"] = value
 
+    def _boundaries_init(self):
+        """The optional key ``Raytracing: periodic`` (0 | 1; absent: 1, the reference's behaviour): whether the traces wrap around
+        the box, until ``periodic`` is assigned."""
+        v = self._ld.get('Raytracing', {}).get('periodic', 1)
+        if isinstance(v, (bool, np.bool_)):
+            v = int(v)
+        if not isinstance(v, (int, np.integer)) or v not in (0, 1):
+            raise ValueError(f"Raytracing: periodic must be 0 or 1, not {v!r}")
+        self.__dict__["_periodic"] = periodic_spec(bool(v), "Raytracing: periodic: 0", self.gpu)     # (0 needs use_gpu: said now)
+        if not self.__dict__["_periodic"] and self.rank == 0:
+            self.printlog("Open (non-periodic) boundaries for the raytrace")
+
+    @property
+    def periodic(self):
+        """Do the traces of the next steps wrap around the box (True, the default) or end at its faces (False: open boundaries,
+        use_gpu=True only: on an object without, False is refused at the assignment)?  A driver may assign either between steps."""
+        return self.__dict__.get("_periodic", True)
+
+    @periodic.setter
+    def periodic(self, value):
+        self.__dict__["_periodic"] = periodic_spec(value, "C2Ray.periodic", self.gpu)      # ValueError for what evolve3D would refuse, now
+
     def evolve3D(self, dt, src_flux, src_pos, src_spectrum=None):
         """Evolve the grid over one time step (c2ray_base.py:170-226).  src_spectrum: with ``BlackBodySource: Teff`` a list, the
         index into it of each source's temperature (None: every source the first one); see pyc2ray_amd.evolve3D."""
@@ -326,10 +352,11 @@ class C2Ray:
         thermal = self._thermal_params()
         if self.mpi and src_flux.shape[0] >= self.nprocs:
             result = evolve3D_MPI(*head, self.mpi, self.comm, self.rank, self.nprocs, *tail, thermal=thermal,
-                                  clumping=self.__dict__["_clumping"], src_spectrum=src_spectrum, lls=self.lls)
+                                  clumping=self.__dict__["_clumping"], src_spectrum=src_spectrum, lls=self.lls,
+                                  periodic=self.periodic)
         else:
             result = evolve3D(*head, *tail, thermal=thermal, clumping=self.__dict__["_clumping"], src_spectrum=src_spectrum,
-                              lls=self.lls)
+                              lls=self.lls, periodic=self.periodic)
         self.xh, self.phi_ion = result[:2]
         if thermal is not None:
             self.temp = result[2]
@@ -392,7 +419,7 @@ class C2Ray:
         evolve3D_resident(dt, self.dr, src_flux, src_pos, uploads, self.N, self.photo_thin_table, self.minlogtau, self.dlogtau,
                           self.R_max_LLS, self.convergence_fraction, self.sig, self.bh00, self.albpow, self.colh0, self.temph0,
                           self.abu_c, self.logfile, thermal=self._thermal_params(), clumping=clumping, src_spectrum=src_spectrum,
-                          lls=self.lls)
+                          lls=self.lls, periodic=self.periodic)
         self._host_newer -= {"ndens", "temp", "xh", "phi_ion", "clumping"}
         self._device_newer |= {"xh", "phi_ion"} if self.isothermal else {"xh", "phi_ion", "temp"}
 
@@ -465,7 +492,7 @@ class C2Ray:
         gamma = do_raytracing(self.dr, src_flux, src_pos, self.gpu, self.max_subbox, self.subboxsize,
                               self.loss_fraction, self.ndens, self.xh, self.photo_thin_table,
                               self.photo_thick_table, self.heat_thin_table, self.heat_thick_table, self.minlogtau,
-                              self.dlogtau, self.R_max_LLS, self.sig, self.logfile, lls=self.lls)
+                              self.dlogtau, self.R_max_LLS, self.sig, self.logfile, lls=self.lls, periodic=self.periodic)
         self.phi_ion = gamma[0]
         if gamma[1] is not None:
             self.phi_heat = gamma[1]

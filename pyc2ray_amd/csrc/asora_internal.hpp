@@ -96,6 +96,8 @@ struct RtParams {
     // ---- per-source spectra (asora_spectra_to_device; appended, so the fields above keep their offsets) ----
     const int32_t *src_spec;    // table set of each source, indexed like src_pos / src_flux; nullptr: every source set 0
     unsigned spec_stride;       // double2 entries from one set's [thick | thin | heat thick | heat thin] block to the next
+    // ---- open boundaries (ASORA_OPT_OPEN_BOUNDARIES as it stood when the call began; read by the launcher, not by the kernels) ----
+    int open_bc;
 };
 
 // Constants of the thermal form of the chemistry pass (asora_thermal_params; chemistry.hip: thermal_integrate)
@@ -320,7 +322,7 @@ struct State {
     struct PendingTimer { int which; hipEvent_t e0, e1; };
     std::vector<PendingTimer> pending_timers;     // recorded, not yet resolved
     std::vector<hipEvent_t> free_events;
-    int opt[ASORA_OPT_COUNT] = {0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0};
+    int opt[ASORA_OPT_COUNT] = {0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0};
     double k_ms[ASORA_KERNEL_COUNT] = {0, 0, 0, 0};
     long k_n[ASORA_KERNEL_COUNT] = {0, 0, 0, 0};
 };
@@ -381,6 +383,8 @@ int launch_fold_range(State &st, const double *src_t, double *dst, int i_begin, 
 int ensure_logtab(State &st);
 int launch_prepare_nhi(State &st, bool need_transposed);
 int launch_finish_phi(State &st);
+// open boundaries: what they are not built for (N > 512, grey opacity, global atomics, the column-density dump), code 4
+int check_open_boundaries(const State &st, const char *who, bool open, bool dump);
 int launch_raytrace(State &st, RtParams &p, bool dump, bool heat, hipStream_t side = nullptr);   // side: stream to launch on when no shared scratch is needed
 // The sub-box sweep on tabulated geometry (raytrace.hip): prepare -> tables for (N, R, range, box size), then one launch per
 // sub-box.  `shells` = (s_begin, s_end] of the box; returns without launching when the tables hold nothing there.

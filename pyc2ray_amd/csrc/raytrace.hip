@@ -142,6 +142,8 @@ __device__ __forceinline__ double photo_rate_per_atom(double flux, double cd_in,
 // The offset of such a lane is 2 GiB, and the descriptors never span more than 2 GiB: the range check is
 // offset + 8 > num_records in 32-bit arithmetic, so an offset near 2^32 would wrap around and pass it.
 #define ASORA_OOB_OFFSET ((int)0x80000000u)
+// OPEN kernels: mark of a wrapped-coordinate entry (and of the cell index made of three) whose unwrapped position is outside the box
+constexpr unsigned WTAB_OUTSIDE = 0x80000000u;
 extern "C" __device__ double asora_buffer_atomic_fadd_f64(double, __amdgpu_buffer_rsrc_t, int, int, int)
     __asm("llvm.amdgcn.raw.ptr.buffer.atomic.fadd.f64");
 
@@ -209,7 +211,19 @@ extern "C" __device__ double asora_buffer_atomic_fadd_f64(double, __amdgpu_buffe
 //   column-density dump            256 x {256,1024}                                f/t  t    f    f         f/t  f       1    f        launch_variant
 //   sub-box sweep                  {256,512} x 256                                 f    f    f/t  f         f    t       1|2  t        launch_subbox_tables_variant
 //   descriptors per layout (SPLIT) paired {256x32, 256x64, 256x256, 512x256}; single {256,512}x256            f    f    f/t  f/t       f/t  t       1|2  f        launch_variant_pairs / _split
+//   open boundaries (OPEN)         paired {256,512}x256; single {256,512}x{256,1024} f/t(1) f    f/t(1) f       f    t       1|2  f        launch_variant_open
 //   (SKIP_ZERO with HEAT or GREY, NSRC = 2 with HEAT, DUMP, GREY or global atomics, SUBBOX with NSRC = 2 and HEAT: not built)
+// OPEN (ASORA_OPT_OPEN_BOUNDARIES): a cell whose unwrapped position i0 +- a, j0 +- b, k0 +- c lies outside [0, N)
+// on any axis is swept like every other -- its upstream neighbours and whatever reads it lie outside as well, since every
+// upstream neighbour of an in-box cell lies in the bounding box of that cell and the source -- but receives no rate and is not
+// counted (in_box_gpu of the reference's build without PERIODIC, raytracing.cu:264-267).  The per-source wrapped-coordinate
+// tables carry the verdict per axis and offset in their top bit, nhi_address hands the OR of the three on in the top bit of the
+// cell index, and the lane's pending atomic gets the out-of-range offset of a lane without a rate.  A compile-time variant: with
+// OPEN = false every instantiation is what it was (register counts line for line); the last row of the table is all that is
+// built with it -- 18 forms -- and launch_raytrace maps every launch shape onto them (64 ... 256 threads -> 256, 512 and 1024
+// -> 512; 256-entry LDS tables unless there are more than 256 shells; no exact-zero skipping); N > 512, grey opacity, global
+// atomics, the column-density dump and the sub-box sweep are refused (check_open_boundaries).  138 VGPRs paired (three waves
+// per SIMD against four), 100 single (four against five), 108 with heating.
 // SPEC: the kernel reads the table set of its source(s) (RtParams::src_spec; a scalar load and a scalar multiply-add per source).
 // Every form is built with it, at no VGPR; only the paired SPLIT family tips from 128 to 129 VGPRs (four waves per SIMD to three),
 // so that family alone is ALSO built without (SPEC = false) and launches without table sets take that form: launch_variant_pairs.
@@ -217,7 +231,7 @@ extern "C" __device__ double asora_buffer_atomic_fadd_f64(double, __amdgpu_buffe
 __device__ __forceinline__ bool ztr_desc(const RtParams &p, int uinfo) { return p.z_transposed != 0 && ((uinfo >> 8) & 3) == 3; }
 
 template <int RT_THREADS, bool GLOBAL_SCRATCH, bool DUMP, bool HEAT, int TABCAP, bool SKIP_ZERO = false, bool GREY = false,
-          bool BUFATOM = false, int NSRC = 1, bool SUBBOX = false, bool SPLIT = false, bool SPEC = true>
+          bool BUFATOM = false, int NSRC = 1, bool SUBBOX = false, bool SPLIT = false, bool SPEC = true, bool OPEN = false>
 __global__ void __launch_bounds__(RT_THREADS, 1) raytrace_octant_kernel(const RtParams p)
 {
     extern __shared__ double lds_raw[];
@@ -226,6 +240,8 @@ __global__ void __launch_bounds__(RT_THREADS, 1) raytrace_octant_kernel(const Rt
     static_assert(SPEC || (SPLIT && NSRC == 2), "the form without per-source table sets is kept for the paired SPLIT family only");
     static_assert(!SPLIT || (BUFATOM && !SUBBOX && !DUMP && (NSRC == 1 || (!HEAT && !GREY)) && !(SKIP_ZERO && (HEAT || GREY))),
                   "descriptors per layout: the production forms for 512 < N <= 645, and the single-source form with heating or grey opacity");
+    static_assert(!OPEN || (BUFATOM && !DUMP && !SKIP_ZERO && !GREY && !SUBBOX && !SPLIT && SPEC && (NSRC == 1 || !HEAT)),
+                  "open boundaries: table rates through buffer atomics over one descriptor (N <= 512), see the variant table");
 
     if (p.done_flag && *p.done_flag) return;   // evolve loop: an iteration enqueued beyond convergence does nothing
     const int blk = blockIdx.x;
@@ -321,12 +337,16 @@ __global__ void __launch_bounds__(RT_THREADS, 1) raytrace_octant_kernel(const Rt
 #pragma unroll
         for (int q = 0; q < NSRC; ++q) {
             int *w = wtab + q * 6 * TABCAP;
-            w[t] = wrap_once(i0[q] + sa * t, N);      // periodic position of offset t along each axis
-            w[TABCAP + t] = wrap_once(i0[q] - sa * t, N);      // (|offset| <= N/2: one wrap suffices, raytracing.cu:270-272)
-            w[2 * TABCAP + t] = wrap_once(j0[q] + sb * t, N);
-            w[3 * TABCAP + t] = wrap_once(j0[q] - sb * t, N);
-            w[4 * TABCAP + t] = wrap_once(k0[q] + sc * t, N);
-            w[5 * TABCAP + t] = wrap_once(k0[q] - sc * t, N);
+            // OPEN: an entry also says whether the unwrapped position lies outside [0, N) (WTAB_OUTSIDE; in_box_gpu of the
+            // reference's build without PERIODIC, raytracing.cu:264-267).  The wrapped position stays: the cell is still swept,
+            // on whatever nHI it finds there, and only its rate is dropped (nhi_address, `ok`)
+            auto entry = [&](int x) -> int { return wrap_once(x, N) | ((OPEN && (unsigned)x >= (unsigned)N) ? (int)WTAB_OUTSIDE : 0); };
+            w[t] = entry(i0[q] + sa * t);      // periodic position of offset t along each axis
+            w[TABCAP + t] = entry(i0[q] - sa * t);      // (|offset| <= N/2: one wrap suffices, raytracing.cu:270-272)
+            w[2 * TABCAP + t] = entry(j0[q] + sb * t);
+            w[3 * TABCAP + t] = entry(j0[q] - sb * t);
+            w[4 * TABCAP + t] = entry(k0[q] + sc * t);
+            w[5 * TABCAP + t] = entry(k0[q] - sc * t);
         }
     }
     if (threadIdx.x == 0) {
@@ -419,14 +439,21 @@ __global__ void __launch_bounds__(RT_THREADS, 1) raytrace_octant_kernel(const Rt
         const bool zt = ztr && (abc >> 30) == 2;
         // the [k][j][i] copies follow the [i][j][k] grids in memory: one 32-bit index covers both
         // (one formula with the outer and inner coordinate swapped, rather than two under a branch)
-        const unsigned outer = zt ? k : i, inner = zt ? i : k;
+        // OPEN: the marks of the three entries.  `outer` and `row` are 24-bit multiplicands below, so the mark of `outer` and
+        // the one `j` carries into `row` fall away by themselves; `inner` is the final 32-bit addend and is stripped here.
+        // The OR of the three rides on the top bit of `idx` (an index stays below 2^28 while one descriptor spans both
+        // layouts, N <= 512), so the step that rates the cell gets it at no register.
+        const unsigned outside = OPEN ? ((i | j | k) & WTAB_OUTSIDE) : 0u;
+        const unsigned outer = zt ? k : i, inner = (zt ? i : k) & (OPEN ? ~WTAB_OUTSIDE : ~0u);
         // (24-bit multiplies: N <= 1280 (device_init) so outer * N + j < 2^21; a 32-bit integer multiply runs at a quarter of their rate)
         // (spelled out: from __umul24 the compiler makes one 24-bit and one 64-bit multiply-add)
         unsigned row, cell;
         asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(row) : "v"(outer), "s"(N), "v"(j));
         asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(cell) : "v"(row), "s"(N), "v"(inner));
         idx = cell + (zt ? p.ncell : 0u);
-        return p.nhi + idx;
+        const double *addr = p.nhi + idx;
+        if (OPEN) idx |= outside;
+        return addr;
     };
 
     // One step of one lane, straight-line (whole-wave instruction count is what matters, so
@@ -557,7 +584,8 @@ __global__ void __launch_bounds__(RT_THREADS, 1) raytrace_octant_kernel(const Rt
                     p.dump[(di * N + dj) * N + dk] = cd_out[q];
                 }
             }
-            const bool ok = owner && cdi <= maxcd && (NSRC == 1 || have[q]);
+            // OPEN: a cell beyond a face of the box is neither rated nor counted; its pending offset below is ASORA_OOB_OFFSET
+            const bool ok = owner && cdi <= maxcd && (NSRC == 1 || have[q]) && !(OPEN && (cur_idx[q] & WTAB_OUTSIDE));
             rated[q] = ok;
             n_gamma += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(ok));
             vol_nhi[q] = volfac * nHI;
@@ -1005,6 +1033,44 @@ static int launch_variant(State &st, const RtParams &q, unsigned grid, size_t ld
     return 0;
 }
 
+// Open boundaries (ASORA_OPT_OPEN_BOUNDARIES, the kernel's OPEN): the forms of the variant table's last row.  Workgroups of 256 or
+// 512 threads, LDS tables of 256 or 1024 entries; two sources per workgroup with the 256-entry tables and the shells in LDS,
+// one source per workgroup with or without heating, shells in LDS or -- where they outgrow it -- in global memory, the rates
+// through buffer atomics either way (one descriptor: N <= 512).
+template <int T, int TABCAP>
+static int launch_variant_open(const RtParams &q, unsigned grid, size_t lds_bytes, bool use_lds, bool heat, bool pairs, hipStream_t stream)
+{
+#define ASORA_LAUNCH_OPEN(GS, HT, NS)                                                                                                       \
+    do {                                                                                                                                \
+        ASORA_HIP_TRY(hipFuncSetAttribute((const void *)raytrace_octant_kernel<T, GS, false, HT, TABCAP, false, false, true, NS, false, false, true, true>, \
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));                                 \
+        hipLaunchKernelGGL((raytrace_octant_kernel<T, GS, false, HT, TABCAP, false, false, true, NS, false, false, true, true>), dim3(grid), dim3(T), \
+                           lds_bytes, stream, q);                                                                                       \
+    } while (0)
+    if constexpr (TABCAP == 256) {
+        if (pairs) { ASORA_LAUNCH_OPEN(false, false, 2); ASORA_HIP_TRY(hipGetLastError()); return 0; }
+    }
+    if (pairs) return fail(11, "raytrace: no paired open-boundary form with these LDS tables (internal error)");
+    if (use_lds) { if (heat) ASORA_LAUNCH_OPEN(false, true, 1); else ASORA_LAUNCH_OPEN(false, false, 1); }
+    else         { if (heat) ASORA_LAUNCH_OPEN(true, true, 1);  else ASORA_LAUNCH_OPEN(true, false, 1); }
+#undef ASORA_LAUNCH_OPEN
+    ASORA_HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// What open boundaries are not built for: refused before anything is launched (every entry point asks through
+// require_raytrace_inputs; launch_raytrace asks again, so that no launch can slip past)
+int check_open_boundaries(const State &st, const char *who, bool open, bool dump)
+{
+    if (!open) return 0;
+    const std::string w = std::string(who) + ": open boundaries (ASORA_OPT_OPEN_BOUNDARIES) ";
+    if (16ull * st.ncell > 0x80000000ull) return fail(4, w + "are built for N <= 512 (mesh of " + std::to_string(st.N) + ")");
+    if (st.opt[ASORA_OPT_GREY_NOTABLES] && !st.coldens_only) return fail(4, w + "need table rates (grey opacity, ASORA_OPT_GREY_NOTABLES, is on)");
+    if (st.opt[ASORA_OPT_GLOBAL_ATOMICS]) return fail(4, w + "need the buffer-atomic kernels (ASORA_OPT_GLOBAL_ATOMICS is on)");
+    if (dump) return fail(4, w + "have no column-density dump");
+    return 0;
+}
+
 // Who shares a workgroup with whom when the tables are the aligned kind (build_unit_geometry, align_class): two sources
 // that agree modulo 8 in k (units of the x- and y-sector: list 0) or in i (units of the z-sector: list 1).  The list is walked
 // in its order -- position-sorted for a whole-list call -- and a source waits for the next one of its class, so partners are
@@ -1075,8 +1141,11 @@ int launch_raytrace(State &st, RtParams &p, bool dump, bool heat, hipStream_t si
 {
     // (per-source spectra: checked by the entry points already; here so that no launch can carry an unchecked index)
     if (p.src_spec) { if (int rc = check_source_spectra("raytrace")) return rc; }
+    const bool open = p.open_bc != 0;
+    if (int rc = check_open_boundaries(st, "raytrace", open, dump)) return rc;
     int units, threads;   // one workgroup per (source, octant) or per (source, octant, sector)
     pick_launch_shape(st, p.R, p.N, p.shape_src_count > 0 ? p.shape_src_count : p.src_count, dump, units, threads);
+    if (open) threads = threads <= 256 ? 256 : 512;         // the workgroup sizes the open forms are built for (launch_variant_open)
     {   // number of shells, known before the tables are built: the 1024-entry LDS tables exist for 256/512 threads
         const double R2hi = p.R * p.R * (1.0 + 1e-9) + 1e-9;
         const int Emax = p.N / 2;
@@ -1121,7 +1190,7 @@ int launch_raytrace(State &st, RtParams &p, bool dump, bool heat, hipStream_t si
     const size_t slots = ((size_t)p.max_cells + 2) & ~(size_t)1;   // max_cells + zero slot, rounded to even (16-B alignment)
     // small tables (log table, 1/s, three wrapped-coordinate tables) at fixed capacity, then the shell buffers
     const bool big_tables = p.S + 1 > 256;
-    const bool small_tables = p.S + 1 <= 64 && threads <= 128;
+    const bool small_tables = !open && p.S + 1 <= 64 && threads <= 128;
     if (p.S + 1 > 1024) return fail(4, "raytrace: more than 1023 shells (mesh too large for this build)");
     size_t fixed_bytes = lds_table_bytes(big_tables ? 1024 : small_tables ? 64 : 256);
     size_t shell_bytes = 2 * slots * sizeof(double);
@@ -1138,13 +1207,13 @@ int launch_raytrace(State &st, RtParams &p, bool dump, bool heat, hipStream_t si
         const int want = st.opt[ASORA_OPT_PAIR_SOURCES];
         const bool possible = use_lds && !dump && !heat && !p.grey && !big_tables && threads <= 512 &&
                               bufatom_fits && p.src_count >= 2 &&
-                              2 * shell_bytes + lds_table_bytes((p.S + 1 <= 32 && threads == 256) ? 32 : (p.S + 1 <= 64 && threads <= 256) ? 64 : 256, 2) <= LDS_LIMIT_BYTES;
+                              2 * shell_bytes + lds_table_bytes(open ? 256 : (p.S + 1 <= 32 && threads == 256) ? 32 : (p.S + 1 <= 64 && threads <= 256) ? 64 : 256, 2) <= LDS_LIMIT_BYTES;
         pairs = possible && (want == 2 || (want == 0 && pair_sources_pays(st, p.R, p.N, p.shape_src_count > 0 ? p.shape_src_count : p.src_count, units, threads)));
     }
-    const bool pairs_small = p.S + 1 <= 64 && threads <= 256;      // the paired variant has the 64-entry tables for 256 threads too
+    const bool pairs_small = !open && p.S + 1 <= 64 && threads <= 256;      // the paired variant has the 64-entry tables for 256 threads too
     // ... and 32-entry ones for 256 threads: at r_RT = 30 the 1.75 KB they save are what separates two workgroups per CU from
     // three (four shell buffers of 11.6 KB + tables: 53.9 KB against 52.2 KB; three per CU fit up to 53.3 KB; worth ~4 %)
-    const bool pairs_tiny = p.S + 1 <= 32 && threads == 256;
+    const bool pairs_tiny = !open && p.S + 1 <= 32 && threads == 256;
     if (pairs) {
         fixed_bytes = lds_table_bytes(pairs_tiny ? 32 : pairs_small ? 64 : 256, 2);
         shell_bytes *= 2;
@@ -1164,7 +1233,8 @@ int launch_raytrace(State &st, RtParams &p, bool dump, bool heat, hipStream_t si
     // waiting, by a later call: the first launch, every 64th after it, every launch while the dark variant runs anyway.
     bool skip_zero = false, probe = false;
     {
-        const bool exists = use_lds && !dump && !heat && !p.grey && std::isfinite(p.tau_zero) && bufatom_fits;
+        // (open boundaries: the forms that add exact zeros only)
+        const bool exists = use_lds && !dump && !heat && !p.grey && std::isfinite(p.tau_zero) && bufatom_fits && !open;
         if (exists && skip_zero_opt == 1) skip_zero = true;
         else if (exists && skip_zero_opt == 0) {
             if (!st.zero_probe_dev) {
@@ -1223,12 +1293,19 @@ int launch_raytrace(State &st, RtParams &p, bool dump, bool heat, hipStream_t si
         q.spread = (long)groups * units <= 2L * st.cu_count ? 1 : 0;     // few workgroups: spread a source's units over the XCDs
         const unsigned grid = q.spread ? (unsigned)units * (unsigned)groups : 8u * (unsigned)units * (unsigned)((groups + 7) / 8);
         st.last_variant = (pairs ? ASORA_VARIANT_PAIRED : 0) | (aligned ? ASORA_VARIANT_ALIGNED : 0) |
-                          ((bufatom_fits && use_lds && !dump) ? ASORA_VARIANT_BUFFER_ATOMICS : 0) | (split ? ASORA_VARIANT_SPLIT_DESCRIPTORS : 0) |
+                          ((bufatom_fits && (use_lds || open) && !dump) ? ASORA_VARIANT_BUFFER_ATOMICS : 0) | (split ? ASORA_VARIANT_SPLIT_DESCRIPTORS : 0) |
+                          (open ? ASORA_VARIANT_OPEN_BOUNDARIES : 0) |
                           (skip_zero ? ASORA_VARIANT_SKIP_ZERO : 0) | (use_lds ? 0 : ASORA_VARIANT_GLOBAL_SHELLS) | (units << 8) | (threads << 16);
         {
             KernelTimer kt(ASORA_KERNEL_RAYTRACE, stream);
             int rc = 0;
-            if (pairs && split) {         // 512 < N <= 645: sectors x 256 / 512 threads
+            if (open) {
+                if (!bufatom_fits || split) return fail(11, "raytrace: open boundaries without one buffer descriptor (internal error)");
+                if (big_tables) rc = threads == 512 ? launch_variant_open<512, 1024>(q, grid, lds_bytes, use_lds, heat, pairs, stream)
+                                                    : launch_variant_open<256, 1024>(q, grid, lds_bytes, use_lds, heat, pairs, stream);
+                else            rc = threads == 512 ? launch_variant_open<512, 256>(q, grid, lds_bytes, use_lds, heat, pairs, stream)
+                                                    : launch_variant_open<256, 256>(q, grid, lds_bytes, use_lds, heat, pairs, stream);
+            } else if (pairs && split) {         // 512 < N <= 645: sectors x 256 / 512 threads
                 if (pairs_tiny)          rc = launch_variant_pairs<256, 32, true>(st, q, grid, lds_bytes, stream, skip_zero);
                 else if (pairs_small)    rc = launch_variant_pairs<256, 64, true>(st, q, grid, lds_bytes, stream, skip_zero);
                 else if (threads == 512) rc = launch_variant_pairs<512, 256, true>(st, q, grid, lds_bytes, stream, skip_zero);

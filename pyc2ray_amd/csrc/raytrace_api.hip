@@ -17,6 +17,8 @@ int require_raytrace_inputs(const char *who, double R, int NumTau, bool density,
 {
     State &st = state();
     const std::string w = std::string(who) + ": ";
+    // (a matter of the library's settings alone: said before anything about the data)
+    if (int rc = check_open_boundaries(st, who, st.opt[ASORA_OPT_OPEN_BOUNDARIES] != 0, false)) return rc;
     if (density && !st.grid_valid[ASORA_GRID_NDENS]) return fail(4, w + "density not on device (density_to_device)");
     if (xh_av && !st.grid_valid[ASORA_GRID_XH_AV]) return fail(4, w + "xh_av not on device");
     if (!st.opt[ASORA_OPT_GREY_NOTABLES] && !st.tables) return fail(4, w + "radiation tables not on device (photo_table_to_device)");
@@ -56,6 +58,7 @@ void fill_rt_params(RtParams &p, double R, double sig, double dr, double minlogt
     use_source_list(p, st, false);
     p.counters = st.counters;
     p.radius_stays = note_call_radius(st, R, radius_path) ? 1 : 0;
+    p.open_bc = st.opt[ASORA_OPT_OPEN_BOUNDARIES] != 0 ? 1 : 0;
 }
 
 // A raytrace call in three parts, so that a caller can overlap the multi-GPU sum of finished slabs of the
@@ -439,6 +442,7 @@ int asora_debug_coldens(double R, double sig, double dr, int source_index, doubl
     if (int rc = check_N("debug_coldens", N)) return rc;
     if (!coldens_out) return fail(3, "debug_coldens: null output");
     State &st = state();
+    if (int rc = check_open_boundaries(st, "debug_coldens", st.opt[ASORA_OPT_OPEN_BOUNDARIES] != 0, true)) return rc;
     const size_t bytes = st.ncell * sizeof(double);
     ASORA_HIP_TRY(hipMemsetAsync(st.staging, 0, bytes, st.stream));
     // the column density does not depend on the tables: trace with whatever is loaded

@@ -18,6 +18,7 @@ import numpy as np
 
 from . import _capi, _residency
 from .asora_core import cuda_is_init
+from .boundaries import open_boundaries, periodic_spec
 from .lls import lls_reset, lls_spec
 from .load_extensions import load_asora, load_c2ray
 from .spectra import source_spectrum_spec
@@ -459,7 +460,7 @@ def _scalars(dt, dr, R_max_LLS, convergence_fraction, sig, minlogtau, dlogtau, c
 
 def evolve3D_resident(dt, dr, src_flux, src_pos, uploads, N, photo_thin_table, minlogtau, dlogtau, R_max_LLS,
                       convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile="pyC2Ray.log", quiet=False,
-                      thermal=None, clumping=None, src_spectrum=None, lls=None):
+                      thermal=None, clumping=None, src_spectrum=None, lls=None, periodic=True):
     """evolve3D for a caller that keeps the grids on the device between time steps (the C2Ray class with
     ``device_resident = True``): same loop, log lines and results as :func:`evolve3D` with ``use_gpu=True``, but only the
     grids in ``uploads`` ({grid selector: host array}, those the caller changed on the host) cross PCIe, and nothing
@@ -469,7 +470,8 @@ def evolve3D_resident(dt, dr, src_flux, src_pos, uploads, N, photo_thin_table, m
     end-of-step temperature afterwards, PHI_HEAT the heating rates.
     ``clumping`` as in :func:`evolve3D`; like the other grids, an (N, N, N) grid crosses PCIe only when ``uploads`` holds it
     (under ``_capi.GRID_CLUMP``, checked then): otherwise GRID_CLUMP must still hold it from an earlier step.
-    ``src_spectrum`` and ``lls`` as in :func:`evolve3D`."""
+    ``src_spectrum``, ``lls`` and ``periodic`` as in :func:`evolve3D`."""
+    periodic = periodic_spec(periodic, "evolve3D_resident")
     lls = lls_spec(lls, "evolve3D_resident")
     spec = source_spectrum_spec(src_spectrum, src_flux.shape[0], True, lambda: load_asora().num_spectra(), "evolve3D_resident")
     clump = _clumping_spec(clumping, N, check_values=_capi.GRID_CLUMP in uploads)
@@ -479,7 +481,7 @@ def evolve3D_resident(dt, dr, src_flux, src_pos, uploads, N, photo_thin_table, m
         raise RuntimeError("GPU not initialized. Please initialize it by calling device_init(N)")
     scalars = _scalars(dt, dr, R_max_LLS, convergence_fraction, sig, minlogtau, dlogtau, (bh00, albpow, colh0, temph0, abu_c),
                        logfile, quiet)
-    with _clumping_reset(clump), lls_reset(lls, load_asora):
+    with _clumping_reset(clump), lls_reset(lls, load_asora), open_boundaries(periodic, load_asora):
         return _evolve_resident(scalars, src_flux, src_pos, uploads, N, photo_thin_table, thermal, clump, spec, lls)
 
 
@@ -609,7 +611,7 @@ def evolve3D(dt, dr,
              minlogtau, dlogtau,
              R_max_LLS, convergence_fraction,
              sig, bh00, albpow, colh0, temph0, abu_c,
-             logfile="pyC2Ray.log", quiet=False, *, thermal=None, clumping=None, src_spectrum=None, lls=None):
+             logfile="pyC2Ray.log", quiet=False, *, thermal=None, clumping=None, src_spectrum=None, lls=None, periodic=True):
     """Evolve the ionised fraction of the whole grid over one time step.
 
     Parameters have the reference's meaning (pyc2ray/evolve.py:49-109): dt [s], dr [cm],
@@ -642,7 +644,15 @@ def evolve3D(dt, dr,
     raytrace (DESIGN.md section 4.1b).  The absorber density of the raytrace becomes ndens ((1 - xh_av) + per_density) + n_const;
     the chemistry is unchanged.  Anything else, a negative or a non-finite value raises ValueError before any GPU work.  Works with
     use_gpu=False, `thermal`, `clumping` and `src_spectrum`.
+
+    periodic : True (default, the reference's ``-D PERIODIC`` build: every trace wraps around the box) or False: open boundaries
+     -- a cell whose unwrapped position lies beyond a face of the box receives nothing from that source.
+    The reach stays the periodic window's, N/2 cells per axis.  Set in the library for this call only (True leaves the
+    library's own option alone).  Anything but a bool, or False with use_gpu=False (the sub-box sweep has no such mode), raises
+    ValueError before any GPU work; the library refuses meshes beyond 512.  Works with `thermal`, `clumping`, `src_spectrum` and
+    `lls`.
     """
+    periodic = periodic_spec(periodic, "evolve3D", use_gpu)
     lls = lls_spec(lls, "evolve3D")
     spec = source_spectrum_spec(src_spectrum, src_flux.shape[0], use_gpu, lambda: load_asora().num_spectra(), "evolve3D")
     clump = _clumping_spec(clumping, np.shape(temp)[0])
@@ -650,7 +660,7 @@ def evolve3D(dt, dr,
         raise ValueError("evolve3D: the thermal mode needs use_gpu=True (the use_gpu=False raytracer has no thermal form)")
     scalars = _scalars(dt, dr, R_max_LLS, convergence_fraction, sig, minlogtau, dlogtau, (bh00, albpow, colh0, temph0, abu_c),
                        logfile, quiet)
-    with _clumping_reset(clump), lls_reset(lls, load_asora):
+    with _clumping_reset(clump), lls_reset(lls, load_asora), open_boundaries(periodic, load_asora):
         if use_gpu:
             return _evolve(scalars, src_flux, src_pos, (temp, ndens, xh), photo_thin_table, thermal=thermal, clump=clump, spec=spec,
                            lls=lls)
@@ -667,7 +677,7 @@ def evolve3D_MPI(dt, dr,
                  minlogtau, dlogtau,
                  R_max_LLS, convergence_fraction,
                  sig, bh00, albpow, colh0, temph0, abu_c,
-                 logfile="pyC2Ray.log", quiet=False, *, thermal=None, clumping=None, src_spectrum=None, lls=None):
+                 logfile="pyC2Ray.log", quiet=False, *, thermal=None, clumping=None, src_spectrum=None, lls=None, periodic=True):
     """Source-sharded variant (pyc2ray/evolve.py:249-498): rank r traces the contiguous block
     [r*(Ns//nprocs), (r+1)*(Ns//nprocs)) of the source list, the last rank to the end
     (evolve.py:362-367); the per-rank rate grids are summed across ranks each iteration.
@@ -687,7 +697,10 @@ def evolve3D_MPI(dt, dr,
     ``clumping`` as in :func:`evolve3D`; every rank passes (and uploads) the whole grid, as it does ``ndens``.
     ``src_spectrum`` as in :func:`evolve3D`, for the whole source list; a rank's shard of the sources takes its shard of it.
     ``lls`` as in :func:`evolve3D`; every rank passes the same one and sets the same state, on every loop.
+    ``periodic`` as in :func:`evolve3D`, the same on every rank and on every loop; the planes the ranks exchange stay those of the
+    periodic trace (the wrapped ones then carry zeros).
     """
+    periodic = periodic_spec(periodic, "evolve3D_MPI", use_gpu)
     lls = lls_spec(lls, "evolve3D_MPI")
     spec = source_spectrum_spec(src_spectrum, src_flux.shape[0], use_gpu, lambda: load_asora().num_spectra(), "evolve3D_MPI")
     if thermal is not None:
@@ -701,7 +714,7 @@ def evolve3D_MPI(dt, dr,
     scalars = _scalars(dt, dr, R_max_LLS, convergence_fraction, sig, minlogtau, dlogtau, (bh00, albpow, colh0, temph0, abu_c),
                        logfile, quiet)
     ranks = (use_mpi, comm, rank, nprocs)
-    with _clumping_reset(clump), lls_reset(lls, load_asora):
+    with _clumping_reset(clump), lls_reset(lls, load_asora), open_boundaries(periodic, load_asora):
         if use_gpu:
             return _evolve(scalars, src_flux, src_pos, (temp, ndens, xh), photo_thin_table, ranks, thermal=thermal, clump=clump,
                            spec=spec, lls=lls)

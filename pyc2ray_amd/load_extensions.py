@@ -456,11 +456,11 @@ class _LibAsora:
         return z.value
 
     def last_raytrace_variant(self):
-        """{"paired", "aligned", "buffer_atomics", "split_descriptors", "skip_zero", "global_shells": bool, "units", "threads"} of the
+        """{"paired", "aligned", "buffer_atomics", "split_descriptors", "skip_zero", "global_shells", "open": bool, "units", "threads"} of the
         last raytrace launch (asora_last_raytrace_variant)."""
         v = self._lib.asora_last_raytrace_variant()
         return {"paired": bool(v & 1), "aligned": bool(v & 2), "buffer_atomics": bool(v & 4), "split_descriptors": bool(v & 8),
-                "skip_zero": bool(v & 16), "global_shells": bool(v & 32), "units": (v >> 8) & 255, "threads": v >> 16}
+                "skip_zero": bool(v & 16), "global_shells": bool(v & 32), "open": bool(v & _capi.VARIANT_OPEN_BOUNDARIES), "units": (v >> 8) & 255, "threads": v >> 16}
 
     def debug_geometry_bytes(self):
         """Device memory of the current geometry tables (shared parts once)."""

@@ -5,6 +5,7 @@ import numpy as np
 
 from . import _capi, _residency
 from .asora_core import cuda_is_init
+from .boundaries import open_boundaries, periodic_spec
 from .lls import lls_reset, lls_spec
 from .load_extensions import load_asora, load_c2ray
 from .spectra import source_spectrum_spec
@@ -23,7 +24,7 @@ def do_raytracing(dr,
                   minlogtau, dlogtau,
                   R_max_LLS,
                   sig,
-                  logfile="pyC2Ray.log", quiet=False, stats=False, src_spectrum=None, lls=None):
+                  logfile="pyC2Ray.log", quiet=False, stats=False, src_spectrum=None, lls=None, periodic=True):
     """Raytrace all sources once and return the photo-ionisation rate grid.
 
     Same 17 positional arguments as the reference (pyc2ray/raytracing.py:34-43).  Returns
@@ -43,14 +44,17 @@ def do_raytracing(dr,
 
     ``lls``: as in :func:`pyc2ray_amd.evolve3D` -- None or a :class:`pyc2ray_amd.lls.LLSOpacity`, the unresolved Lyman-limit
     systems among the absorbers the rays cross.
+
+    ``periodic``: as in :func:`pyc2ray_amd.evolve3D` -- False: open boundaries, no rate beyond a face of the box (use_gpu=True only).
     """
+    periodic = periodic_spec(periodic, "do_raytracing", use_gpu)
     lls = lls_spec(lls, "do_raytracing")
     spec = source_spectrum_spec(src_spectrum, src_flux.shape[0], use_gpu, lambda: load_asora().num_spectra(), "do_raytracing")
     if use_gpu and not cuda_is_init():
         raise RuntimeError("GPU not initialized. Please initialize it by calling device_init(N)")
     _residency.reclaim()              # this call overwrites device grids a resident C2Ray object may be relying on
 
-    with lls_reset(lls, load_asora):
+    with lls_reset(lls, load_asora), open_boundaries(periodic, load_asora):
         return _do_raytracing(dr, src_flux, src_pos, use_gpu, max_subbox, subboxsize, loss_fraction, ndens, xh_av, photo_thin_table,
                               photo_thick_table, heat_thin_table, heat_thick_table, minlogtau, dlogtau, R_max_LLS, sig, logfile,
                               quiet, stats, spec, lls)
