@@ -384,6 +384,32 @@ int asora_clumping(int mode, double constant);
 int asora_lls_opacity(double n_const, double per_density);
 int asora_get_lls_opacity(double *n_const, double *per_density);
 
+/* Plane-parallel ionising flux through faces of the box: radiation that enters from outside.
+ *   face[q]      0 ... 5 = -x +x -y +y -z +z, the face the radiation ENTERS through (-x: the plane i = 0, travelling towards
+ *                increasing i; x is the first index of the (N, N, N) C-ordered grids); at most one entry per face
+ *   flux[q]      in the units of the source strengths per cm^2: 1e48 photons s^-1 cm^-2; finite and >= 0
+ *   spectrum[q]  the table set the face shines with (asora_spectra_to_device), or spectrum = NULL: set 0 for every face
+ * count = 0 switches it off.  Each of the N^2 rays of a face is marched over its N cells in travel order, never wrapping
+ * (whatever ASORA_OPT_OPEN_BOUNDARIES says) and without a cut at R: cd_out = cd_in + n_abs dr with the absorber density of
+ * the point-source trace (asora_lls_opacity included), the rate of photoion_rates with prefact = flux / dr, divided by
+ * n_abs and added where cd_in <= the column-density cap.  The sweep runs once per trace, behind the zeroing of the rate
+ * accumulators and the forming of nHI and ahead of every point-source launch: asora_raytrace_device, asora_raytrace_begin /
+ * _begin_planes (so the three-part call), asora_do_all_sources (which then takes its plain path), asora_evolve_begin /
+ * _enqueue (every iteration) and the asora_evolve_slab_* loop (ahead of an iteration's first asora_evolve_slab_trace, which
+ * must then be called every iteration, with an empty source range if need be).  A trace or a step with faces and no point
+ * source is valid.  With ASORA_OPT_HEATING / the thermal mode the faces deposit heating rates as well.  A trace or step keeps the
+ * setting it began with.
+ * Fails with code 3 for a count outside 0 ... 6, a face outside 0 ... 5 or given twice, a flux that is negative or not
+ * finite, a spectrum index outside 0 ... ASORA_MAX_SPECTRA - 1.  While faces are set, code 4 and nothing launched from: any
+ * trace under grey opacity (ASORA_OPT_GREY_NOTABLES), asora_debug_coldens, both sub-box entries (c2ray_do_all_sources,
+ * asora_subbox_raytrace_device), asora_evolve_begin_slab(_thermal) with fewer than all planes owned (the slab exchange does not
+ * deliver a whole-box sweep; own every plane and use asora_evolve_slab_fold_all), heating without heating tables, a spectrum index the device holds no set for, and a z
+ * face without the [k][j][i] twins (ASORA_OPT_Z_TRANSPOSED = 0).  The setting holds until it is set again or the device is
+ * re-initialised. */
+int asora_plane_flux(int count, const int32_t *face, const double *flux, const int32_t *spectrum);
+/* Reads the setting back: *count, and the first *count entries of face / flux / spectrum (room for 6 each; any may be NULL). */
+int asora_get_plane_flux(int *count, int32_t *face, double *flux, int32_t *spectrum);
+
 /* ------------------------------------------------------------------------------------------ */
 /* C. Options, measurement and diagnostics                                                     */
 /* ------------------------------------------------------------------------------------------ */
@@ -502,7 +528,8 @@ int asora_synchronize(void);
 
 /* Work accounting of the last raytrace: (source,cell) pairs that received a rate
  * (|d|<=R inside the periodic window: the Gamma-contributing set of raytracing.cu:315), and
- * (source,cell) column-density evaluations actually performed (incl. octant-boundary planes). */
+ * (source,cell) column-density evaluations actually performed (incl. octant-boundary planes).
+ * Point sources only: the cells a plane-parallel flux (asora_plane_flux) rates are not counted. */
 int asora_last_raytrace_counts(long long *gamma_cells, long long *evaluated_cells);
 /* The same, and how many of the rate-receiving pairs got a rate of exactly +0 that was therefore not added to the grid
  * (ASORA_OPT_SKIP_ZERO_RATES; they are part of gamma_cells). */

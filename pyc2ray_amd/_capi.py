@@ -103,6 +103,8 @@ SIGNATURES = {
     "asora_clumping": (C.c_int, [C.c_int, C.c_double]),
     "asora_lls_opacity": (C.c_int, [C.c_double, C.c_double]),
     "asora_get_lls_opacity": (C.c_int, [_dp, _dp]),
+    "asora_plane_flux": (C.c_int, [C.c_int, _ip, _dp, _ip]),
+    "asora_get_plane_flux": (C.c_int, [C.POINTER(C.c_int), _ip, _dp, _ip]),
     "asora_set_option": (C.c_int, [C.c_int, C.c_int]),
     "asora_get_option": (C.c_int, [C.c_int]),
     "asora_kernel_time_ms": (C.c_int, [C.c_int, _dp, C.POINTER(C.c_long)]),

@@ -24,6 +24,9 @@ Differences from the reference:
     add the opacity of unresolved Lyman-limit systems to the raytrace (pyc2ray_amd/lls.py; evolve3D's ``lls=``).
   * ``Raytracing: periodic: 0|1`` (optional key, default 1) and the attribute ``periodic`` (a bool, assignable between steps)
     choose between traces that wrap around the box and open boundaries (evolve3D's ``periodic=``; use_gpu only).
+  * ``Photo: plane_flux_face`` / ``plane_flux`` / ``plane_flux_spectrum`` (optional keys, scalars or lists of equal length) and the
+    attribute ``plane_flux`` add a plane-parallel photon flux that enters through faces of the box (pyc2ray_amd/planeflux.py;
+    evolve3D's ``plane_flux=``; use_gpu only).  ``plane_flux`` of the file is in photons s^-1 cm^-2.
 """
 import atexit
 import re
@@ -41,6 +44,7 @@ from . import _capi, _residency
 from .evolve import evolve3D, evolve3D_MPI, evolve3D_resident
 from .boundaries import periodic_spec
 from .lls import LLSOpacity, LLSSchedule, lls_spec
+from .planeflux import PlaneFlux, plane_flux_spec
 from .load_extensions import load_asora
 from .radiation import BlackBodySource, make_tau_table
 from .raytracing import do_raytracing
@@ -223,6 +227,7 @@ class C2Ray:
         self._radiation_init()
         self._lls_init()
         self._boundaries_init()
+        self._plane_flux_init()
         if self.rank == 0:
             if self.gpu:
                 q_max = np.ceil(1.73205080757 * min(self.R_max_LLS, 1.73205080757 * self.N / 2))
@@ -340,6 +345,42 @@ class C2Ray:
     def periodic(self, value):
         self.__dict__["_periodic"] = periodic_spec(value, "C2Ray.periodic", self.gpu)      # ValueError for what evolve3D would refuse, now
 
+    def _plane_flux_init(self):
+        """The optional keys ``Photo: plane_flux_face`` (names of :data:`pyc2ray_amd.planeflux.FACES`, or 0 ... 5), ``plane_flux``
+        (photons s^-1 cm^-2; divided by 1e48 here, like the source strengths) and ``plane_flux_spectrum`` (default 0): each a
+        scalar or a list, of one length.  None present: no faces, until ``plane_flux`` is assigned."""
+        photo = self._ld.get('Photo', {})
+        self.__dict__["_plane_flux"] = ()
+        present = [k for k in ("plane_flux_face", "plane_flux", "plane_flux_spectrum") if k in photo]
+        if not present:
+            return
+        if "plane_flux_face" not in photo or "plane_flux" not in photo:
+            raise ValueError("Photo: plane_flux_face and plane_flux come together")
+        as_list = lambda v: list(v) if isinstance(v, (list, tuple)) else [v]
+        faces, fluxes = as_list(photo["plane_flux_face"]), as_list(photo["plane_flux"])
+        spectra = as_list(photo.get("plane_flux_spectrum", [0] * len(faces)))
+        if not (len(faces) == len(fluxes) == len(spectra)):
+            raise ValueError(f"Photo: plane_flux_face, plane_flux and plane_flux_spectrum must have one length, not "
+                             f"{len(faces)}, {len(fluxes)}, {len(spectra)}")
+        for x in fluxes:
+            if isinstance(x, bool) or not isinstance(x, (int, float)):
+                raise ValueError(f"Photo: plane_flux must be a number or a list of numbers, not {x!r}")
+        value = [PlaneFlux(f, x / 1e48, s) for f, x, s in zip(faces, fluxes, spectra)]
+        self.__dict__["_plane_flux"] = plane_flux_spec(value, "Photo: plane_flux", self.gpu)      # (faces need use_gpu: said now)
+        if self.rank == 0:
+            for f in self.__dict__["_plane_flux"]:
+                self.printlog(f"Plane-parallel flux through the {f.name} face: {f.flux * 1e48:.3e} photons/s/cm^2")
+
+    @property
+    def plane_flux(self):
+        """The plane-parallel fluxes of the next steps: a tuple of :class:`pyc2ray_amd.planeflux.PlaneFlux` (empty: none).  A
+        driver may assign None, one PlaneFlux or a sequence of them between steps (use_gpu=True only)."""
+        return self.__dict__.get("_plane_flux", ())
+
+    @plane_flux.setter
+    def plane_flux(self, value):
+        self.__dict__["_plane_flux"] = plane_flux_spec(value, "C2Ray.plane_flux", self.gpu)    # ValueError for what evolve3D would refuse, now
+
     def evolve3D(self, dt, src_flux, src_pos, src_spectrum=None):
         """Evolve the grid over one time step (c2ray_base.py:170-226).  src_spectrum: with ``BlackBodySource: Teff`` a list, the
         index into it of each source's temperature (None: every source the first one); see pyc2ray_amd.evolve3D."""
@@ -350,13 +391,13 @@ class C2Ray:
                 self.R_max_LLS, self.convergence_fraction, self.sig, self.bh00, self.albpow, self.colh0, self.temph0, self.abu_c,
                 self.logfile)
         thermal = self._thermal_params()
-        if self.mpi and src_flux.shape[0] >= self.nprocs:
+        if self.mpi and np.size(src_flux) >= self.nprocs:
             result = evolve3D_MPI(*head, self.mpi, self.comm, self.rank, self.nprocs, *tail, thermal=thermal,
                                   clumping=self.__dict__["_clumping"], src_spectrum=src_spectrum, lls=self.lls,
-                                  periodic=self.periodic)
+                                  periodic=self.periodic, plane_flux=self.plane_flux)
         else:
             result = evolve3D(*head, *tail, thermal=thermal, clumping=self.__dict__["_clumping"], src_spectrum=src_spectrum,
-                              lls=self.lls, periodic=self.periodic)
+                              lls=self.lls, periodic=self.periodic, plane_flux=self.plane_flux)
         self.xh, self.phi_ion = result[:2]
         if thermal is not None:
             self.temp = result[2]
@@ -419,7 +460,7 @@ class C2Ray:
         evolve3D_resident(dt, self.dr, src_flux, src_pos, uploads, self.N, self.photo_thin_table, self.minlogtau, self.dlogtau,
                           self.R_max_LLS, self.convergence_fraction, self.sig, self.bh00, self.albpow, self.colh0, self.temph0,
                           self.abu_c, self.logfile, thermal=self._thermal_params(), clumping=clumping, src_spectrum=src_spectrum,
-                          lls=self.lls, periodic=self.periodic)
+                          lls=self.lls, periodic=self.periodic, plane_flux=self.plane_flux)
         self._host_newer -= {"ndens", "temp", "xh", "phi_ion", "clumping"}
         self._device_newer |= {"xh", "phi_ion"} if self.isothermal else {"xh", "phi_ion", "temp"}
 
@@ -492,7 +533,8 @@ class C2Ray:
         gamma = do_raytracing(self.dr, src_flux, src_pos, self.gpu, self.max_subbox, self.subboxsize,
                               self.loss_fraction, self.ndens, self.xh, self.photo_thin_table,
                               self.photo_thick_table, self.heat_thin_table, self.heat_thick_table, self.minlogtau,
-                              self.dlogtau, self.R_max_LLS, self.sig, self.logfile, lls=self.lls, periodic=self.periodic)
+                              self.dlogtau, self.R_max_LLS, self.sig, self.logfile, lls=self.lls, periodic=self.periodic,
+                              plane_flux=self.plane_flux)
         self.phi_ion = gamma[0]
         if gamma[1] is not None:
             self.phi_heat = gamma[1]

@@ -49,6 +49,14 @@ inline double lut_index_limit(int NumTau, int table_len)
     return by_reference < by_table ? by_reference : by_table;
 }
 
+// Plane-parallel flux through faces of the box (asora_plane_flux; plane_flux.hip)
+struct PlaneFluxSet {
+    int count;                         // 0: off
+    int face[6];                       // 0 ... 5 = -x +x -y +y -z +z, the face the radiation enters through
+    int spec[6];                       // table set of the face
+    double flux[6];
+};                                     // (a plain aggregate: RtParams stays trivial; PlaneFluxSet{} is "off")
+
 struct RtParams {
     int N;
     int S;                 // last Chebyshev shell over all octants
@@ -98,6 +106,8 @@ struct RtParams {
     unsigned spec_stride;       // double2 entries from one set's [thick | thin | heat thick | heat thin] block to the next
     // ---- open boundaries (ASORA_OPT_OPEN_BOUNDARIES as it stood when the call began; read by the launcher, not by the kernels) ----
     int open_bc;
+    // ---- plane-parallel flux (asora_plane_flux as it stood when the call began; read by launch_plane_flux, not by the kernels above) ----
+    PlaneFluxSet plane;
 };
 
 // Constants of the thermal form of the chemistry pass (asora_thermal_params; chemistry.hip: thermal_integrate)
@@ -318,6 +328,11 @@ struct State {
     double lls_a = 0.0, lls_b = 0.0;
     bool coldens_only = false;
 
+    // plane-parallel flux through faces of the box (asora_plane_flux).  ev_plane_swept: the current
+    // iteration of a sharded step has had its sweep (ahead of its first asora_evolve_slab_trace)
+    PlaneFluxSet plane{};
+    bool ev_plane_swept = false;
+
     hipStream_t stream = nullptr;
     struct PendingTimer { int which; hipEvent_t e0, e1; };
     std::vector<PendingTimer> pending_timers;     // recorded, not yet resolved
@@ -385,6 +400,11 @@ int launch_prepare_nhi(State &st, bool need_transposed);
 int launch_finish_phi(State &st);
 // open boundaries: what they are not built for (N > 512, grey opacity, global atomics, the column-density dump), code 4
 int check_open_boundaries(const State &st, const char *who, bool open, bool dump);
+// plane_flux.hip: what a trace with faces set is not built for (grey opacity, the dump, heating without its tables, a table set
+// the device does not hold, a z face without the twins), code 4; the sweeps of p.plane into phi (+ heat_acc), [i][j][k] then
+// [k][j][i] each, on the library's stream (nothing without faces)
+int check_plane_flux(const State &st, const PlaneFluxSet &pf, const char *who, bool dump, bool heat);
+int launch_plane_flux(State &st, const RtParams &p, double *phi, double *heat_acc, bool heat, const int *done);
 int launch_raytrace(State &st, RtParams &p, bool dump, bool heat, hipStream_t side = nullptr);   // side: stream to launch on when no shared scratch is needed
 // The sub-box sweep on tabulated geometry (raytrace.hip): prepare -> tables for (N, R, range, box size), then one launch per
 // sub-box.  `shells` = (s_begin, s_end] of the box; returns without launching when the tables hold nothing there.

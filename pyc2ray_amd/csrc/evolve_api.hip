@@ -60,12 +60,14 @@ static int zero_pairs_unless_clean(bool heating = false)
 // passes zero changes, BOTH pairs are zeroed once: the dirty pair of the previous step may hold rates where the new
 // sources do not reach.  Not for traces that cover (nearly) the whole box, nor with ASORA_REACH_MASK=0 (2: whenever built).
 // Leaves State::reach.in_use set for the step (one GPU; a sharded step uses no mask).
-static int decide_reach_mask(int src_begin, int src_count, double R)
+// faces: the step has plane-parallel fluxes (asora_plane_flux), which reach every line -- no mask; going from a mask to none
+// zeroes both pairs like any other change of the set of lines.
+static int decide_reach_mask(int src_begin, int src_count, double R, bool faces)
 {
     State &st = state();
     State::ReachMask &rm = st.reach;
     static const int mode = []() { const char *v = getenv("ASORA_REACH_MASK"); return v ? atoi(v) : 1; }();
-    const bool possible = mode != 0 && std::isfinite(R) && 2.0 * R + 2.0 < (double)st.N && st.opt[ASORA_OPT_Z_TRANSPOSED] != 0;
+    const bool possible = !faces && mode != 0 && std::isfinite(R) && 2.0 * R + 2.0 < (double)st.N && st.opt[ASORA_OPT_Z_TRANSPOSED] != 0;
     const State::ReachMask::Key now{true, st.src_generation, src_begin, src_count, R};
     const bool same = rm.key == now;
     // where the spheres together hold more cells than the box, (nearly) every line is reached: the mask can not pay and is
@@ -166,6 +168,12 @@ static int evolve_begin_impl(double dt, double bh00, double albpow, double colh0
         if (int rc = ensure_heat_acc()) return rc;
         if (slab) { if (int rc = ensure_heat_outbox()) return rc; }
     }
+    if (int rc = check_plane_flux(st, st.plane, "evolve_begin", false, st.th_on)) return rc;
+    // a face's sweep rates every plane, and a step that owns only some of them folds out, sends and zeroes only the planes its
+    // sources reach: the rates on the other foreign planes would never arrive and would pile up from iteration to iteration
+    if (slab && st.plane.count > 0 && !(own_begin == 0 && own_count == st.N))
+        return fail(4, "evolve_begin_slab: a plane-parallel flux (asora_plane_flux) needs a step that owns every plane (the full-grid "
+                       "exchange, asora_evolve_slab_fold_all): the slab exchange does not deliver a whole-box sweep");
     if (int rc = ensure_temp_probe(bh00, albpow, colh0, temph0)) return rc;
 
     // 2. which lines of the accumulators the passes sweep.  The first trace needs a zeroed pair; every fused pass zeroes the
@@ -176,7 +184,7 @@ static int evolve_begin_impl(double dt, double bh00, double albpow, double colh0
     if (!st.ev_sets_known || slab)
         if (int rc = zero_pairs_unless_clean()) return rc;
     if (slab) st.reach.in_use = false;
-    else if (int rc = decide_reach_mask(src_begin, src_count, R)) return rc;
+    else if (int rc = decide_reach_mask(src_begin, src_count, R, st.plane.count > 0)) return rc;
 
     // 3. the accumulators and the status block of the step
     if (!st.ev_clean[0] && !st.ev_clean[1]) return fail(11, "evolve_begin: no clean accumulator pair (internal error)");
@@ -218,6 +226,7 @@ static int evolve_begin_impl(double dt, double bh00, double albpow, double colh0
     st.ev_slab = slab; st.ev_own_begin = own_begin; st.ev_own_count = own_count; st.ev_slab_passed = false;
     st.ev_slab_thermal = slab && st.th_on;
     st.ev_rates_in_outbox = false; st.ev_folded_all = false;
+    st.ev_plane_swept = false;
     st.ev_open = true;
     return 0;
 }
@@ -292,6 +301,13 @@ int asora_evolve_slab_trace(int src_begin, int src_count)
     if (st.ev_slab_passed) return fail(4, "evolve_slab_trace: the iteration's pass has been enqueued already (close it first)");
     if (src_begin < st.ev_src_begin || src_count < 0 || src_begin + src_count > st.ev_src_begin + st.ev_src_count)
         return fail(4, "evolve_slab_trace: source range outside the step's sources");
+    if (st.ev_rt.plane.count > 0 && !st.ev_plane_swept) {      // the faces' sweeps: once per iteration, ahead of its first trace
+        st.ev_sets_known = false;
+        if (st.ev_slab_thermal) st.heat_clean[0] = st.heat_clean[1] = false;
+        if (int rc = launch_plane_flux(st, st.ev_rt, slab_pair(0), st.ev_slab_thermal ? slab_heat_pair(0) : nullptr, st.ev_slab_thermal,
+                                       &st.ev_status->done)) return rc;
+        st.ev_plane_swept = true;
+    }
     if (src_count == 0) return 0;
     st.ev_sets_known = false;
     RtParams p = st.ev_rt;
@@ -495,6 +511,7 @@ int asora_evolve_slab_close(const double *host_sums)
     if (int rc = launch_convergence_test(st, st.red_final, st.ev_status)) return rc;
     st.ev_first = false;
     st.ev_slab_passed = false; st.ev_folded_all = false;
+    st.ev_plane_swept = false;
     st.ev_enqueued += 1;
     return 0;
 }
@@ -516,6 +533,9 @@ int asora_evolve_enqueue(int iterations)
     for (int it = 0; it < iterations; ++it) {
         // iteration k = ev_enqueued + it + 1 of the step (as long as the step has not converged: then nothing runs anyway)
         const int set = (st.ev_base + st.ev_enqueued + it) & 1;
+        // the faces' sweeps (asora_plane_flux) into the iteration's pairs, ahead of the point sources; a step may have only faces
+        if (int rc = launch_plane_flux(st, st.ev_rt, acc_pair(set), st.th_on ? heat_pair(set) : nullptr, st.th_on, &st.ev_status->done))
+            return rc;
         if (st.ev_src_count > 0) {
             RtParams p = st.ev_rt;
             p.phi = acc_pair(set);

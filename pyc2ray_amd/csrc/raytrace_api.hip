@@ -59,6 +59,7 @@ void fill_rt_params(RtParams &p, double R, double sig, double dr, double minlogt
     p.counters = st.counters;
     p.radius_stays = note_call_radius(st, R, radius_path) ? 1 : 0;
     p.open_bc = st.opt[ASORA_OPT_OPEN_BOUNDARIES] != 0 ? 1 : 0;
+    p.plane = st.plane;
 }
 
 // A raytrace call in three parts, so that a caller can overlap the multi-GPU sum of finished slabs of the
@@ -77,6 +78,7 @@ static int rt_begin(double R, double sig, double dr, double minlogtau, double dl
     const bool heat = st.opt[ASORA_OPT_HEATING] != 0 && dump == nullptr;
     if (heat && (!st.have_heat_tables || st.opt[ASORA_OPT_GREY_NOTABLES]))
         return fail(4, "raytrace: heating requested but no heating tables on device (heat_table_to_device)");
+    if (int rc = check_plane_flux(st, st.plane, "raytrace", dump != nullptr, heat)) return rc;
     const size_t bytes = st.ncell * sizeof(double);
     ASORA_HIP_TRY(hipMemsetAsync(st.grid[ASORA_GRID_PHI_ION], 0, bytes, st.stream));      // raytracing.cu:113
     if (zt) ASORA_HIP_TRY(hipMemsetAsync(st.phi_t, 0, bytes, st.stream));
@@ -90,6 +92,9 @@ static int rt_begin(double R, double sig, double dr, double minlogtau, double dl
     RtParams &p = st.rt_params;
     fill_rt_params(p, R, sig, dr, minlogtau, dlogtau, NumTau);
     p.dump = dump;
+    // the faces' sweeps (asora_plane_flux): behind the zeroed accumulators and nHI, ahead of every point-source launch (and of
+    // main_ready below, so the side streams of the pipelined form start behind them)
+    if (int rc = launch_plane_flux(st, p, st.grid[ASORA_GRID_PHI_ION], st.grid[ASORA_GRID_PHI_HEAT], heat, nullptr)) return rc;
     st.rt_heat = heat;
     st.rt_pipelined = pipelined;
     st.rt_by_planes = false;
@@ -182,6 +187,7 @@ static int do_all_sources_pipelined(double R, double sig, double dr, const doubl
     const char *kenv = getenv("ASORA_PIPELINE_SLABS");
     const int K = kenv ? std::max(2, std::min(KMAX, atoi(kenv))) : 8;
     if (!st.opt[ASORA_OPT_PIPELINED_COPIES] || !st.opt[ASORA_OPT_Z_TRANSPOSED] || st.opt[ASORA_OPT_HEATING]) return 0;
+    if (st.plane.count > 0) return 0;                       // a face's sweep needs nHI of the whole box before anything is traced
     if (NumSrc != st.num_src || NumSrc < 1 || !st.src_pos_sorted || N < 8 * K) return 0;
     if (!std::isfinite(R) || !(R >= 0.0)) return 0;
     const int m = (int)std::floor(R);                       // a source rates the planes i0 - floor(R) ... i0 + floor(R)
@@ -358,10 +364,15 @@ int asora_raytrace_begin_planes(double R, double sig, double dr, double minlogta
     if (nruns < 0 || (nruns > 0 && !runs)) return fail(3, "raytrace_begin_planes: bad plane runs");
     for (int q = 0; q < nruns; ++q)
         if (int rc = check_planes("raytrace_begin_planes", 3, "plane run outside the mesh", runs[2 * q], runs[2 * q + 1])) return rc;
+    if (int rc = check_plane_flux(st, st.plane, "raytrace_begin_planes", false, false)) return rc;
     if (int rc = reset_counters()) return rc;
-    for (int q = 0; q < nruns; ++q)
-        if (int rc = launch_prepare_range(st, runs[2 * q], runs[2 * q + 1], true, st.grid[ASORA_GRID_PHI_ION])) return rc;
+    if (st.plane.count > 0) {      // a face's sweep reads nHI of, and rates, every plane: the runs become the whole box
+        if (int rc = launch_prepare_range(st, 0, st.N, true, st.grid[ASORA_GRID_PHI_ION])) return rc;
+    } else
+        for (int q = 0; q < nruns; ++q)
+            if (int rc = launch_prepare_range(st, runs[2 * q], runs[2 * q + 1], true, st.grid[ASORA_GRID_PHI_ION])) return rc;
     fill_rt_params(st.rt_params, R, sig, dr, minlogtau, dlogtau, NumTau);
+    if (int rc = launch_plane_flux(st, st.rt_params, st.grid[ASORA_GRID_PHI_ION], nullptr, false, nullptr)) return rc;
     st.rt_heat = false;
     st.rt_pipelined = false;
     st.rt_by_planes = true;

@@ -227,6 +227,8 @@ int c2ray_do_all_sources(const double *normflux, const int32_t *srcpos, int max_
     clear_error();
     State &st = state();
     const char *who = "c2ray_do_all_sources";
+    if (st.plane.count > 0)
+        return fail(4, std::string(who) + ": a plane-parallel flux (asora_plane_flux) has no sub-box sweep");
     if (st.opt[ASORA_OPT_OPEN_BOUNDARIES])
         return fail(4, std::string(who) + ": open boundaries (ASORA_OPT_OPEN_BOUNDARIES) have no sub-box sweep (the reference's Fortran has no such mode)");
     if (m1 != m2 || m1 != m3) return fail(3, std::string(who) + ": the mesh must be cubic (raytracing.f90:174-175 use m1 for every axis)");
@@ -328,6 +330,8 @@ int asora_subbox_raytrace_device(int max_subbox, int subboxsize, float loss_frac
     if (int rc = require_init("subbox_raytrace_device")) return rc;
     State &st = state();
     const char *who = "subbox_raytrace_device";
+    if (st.plane.count > 0)
+        return fail(4, std::string(who) + ": a plane-parallel flux (asora_plane_flux) has no sub-box sweep");
     if (st.opt[ASORA_OPT_OPEN_BOUNDARIES])
         return fail(4, std::string(who) + ": open boundaries (ASORA_OPT_OPEN_BOUNDARIES) have no sub-box sweep (the reference's Fortran has no such mode)");
     if (!st.grid_valid[ASORA_GRID_NDENS]) return fail(4, std::string(who) + ": density not on device");

@@ -20,6 +20,7 @@ from . import _capi, _residency
 from .asora_core import cuda_is_init
 from .boundaries import open_boundaries, periodic_spec
 from .lls import lls_reset, lls_spec
+from .planeflux import log_plane_flux, plane_flux_reset, plane_flux_spec, source_arrays
 from .load_extensions import load_asora, load_c2ray
 from .spectra import source_spectrum_spec
 from .utils import printlog
@@ -145,7 +146,7 @@ def _spectra_along(reorder, *args, spec):
 
 def _prologue(libasora, scalars, N, NumTau, src_flux, my_pos, my_flux, uploads, clump, *, ranks=_ONE_RANK,
               calling="Calling evolve3D...", xh_copies=False, say_copied=False, clump_upload=True, tables=None, spec=None,
-              lls=None):
+              lls=None, faces=()):
     """What every form of the step does before its loop: the convergence criterion, this rank's sources (`my_pos`, `my_flux`)
     and the grids of `uploads` ({grid selector: host array}) to the device, the clumping mode, and the header lines of
     evolve.py:156-162 on rank 0.  Returns the :class:`_Step`.  The forms differ in: `calling`, the first header line;
@@ -153,11 +154,13 @@ def _prologue(libasora, scalars, N, NumTau, src_flux, my_pos, my_flux, uploads, 
     reference's one-process GPU branch; `clump_upload=False`, a clumping grid is among `uploads` or on the device already;
     `tables` = (thin, thick), use_gpu=False: that branch has no device_init of its own in the reference, so the library sets itself
     up for the mesh here; `spec`, the spectra of `my_pos` (None: all 0, nothing more is uploaded); `lls`, the LLS opacity of the
-    raytrace (None: off), set like the clumping mode: after the uploads, the same on every rank."""
+    raytrace (None: off), set like the clumping mode: after the uploads, the same on every rank; `faces`, the step's plane-parallel
+    fluxes (the library's state is the caller's, plane_flux_reset): each counts as one source in the convergence criterion, so that
+    a step with faces alone can still converge by the cell count."""
     NumSrc, n_local, NumCells = src_flux.shape[0], my_flux.shape[0], N * N * N
     logfile, quiet, rank = scalars["logfile"], scalars["quiet"], ranks[2]
     # evolve.py:127 (computed from the TOTAL source count, evolve.py:346)
-    conv_criterion = min(int(scalars["convergence_fraction"] * NumCells), (NumSrc - 1) / 3)
+    conv_criterion = min(int(scalars["convergence_fraction"] * NumCells), (NumSrc + len(faces) - 1) / 3)
     step = _Step(NumTau=NumTau, conv_criterion=conv_criterion, N=N, NumCells=NumCells, n_local=n_local, rank=rank, **scalars)
     if _is_distributed(ranks):
         printlog(f"...rank={rank:n} has {n_local:n} sources.", logfile, quiet)
@@ -195,19 +198,28 @@ def _prologue(libasora, scalars, N, NumTau, src_flux, my_pos, my_flux, uploads, 
             clump.log(libasora, NumCells, logfile, quiet)
         if lls is not None:
             lls.log(logfile, quiet)
+        log_plane_flux(faces, logfile, quiet)
         printlog(f"Convergence Criterion (Number of points): {conv_criterion : n}", logfile, quiet, end='\n\n')
     return step
 
 
-def _loop_strategy(libasora, comm, distributed):
+def _loop_strategy(libasora, comm, distributed, faces=(), log=None):
     """Which loop runs the outer iterations of a use_gpu=True step: "one GPU", or across ranks "slab", "pipelined", "all-reduce"
     or "three calls" (what an mpi4py communicator gets).  The two device loops across ranks need the [k][j][i] twins of the
-    grids (asora_evolve_begin_slab fails without: ASORA_OPT_Z_TRANSPOSED = 0 is a diagnostic setting)."""
+    grids (asora_evolve_begin_slab fails without: ASORA_OPT_Z_TRANSPOSED = 0 is a diagnostic setting).  With `faces` (plane-parallel
+    fluxes) a communicator set up for the slab exchange runs the all-reduce loop, and `log(line)` is told: rank 0 sweeps the whole
+    box, which the slab schedule's per-rank plane reach does not cover."""
     if not distributed:
         return "one GPU"
     overlap = getattr(comm, "overlap", False)
     if hasattr(comm, "slab_enqueue") and getattr(comm, "exchange", "") == "slab" and not overlap and _has_transposed_twins(libasora):
-        return "slab"
+        if not faces:
+            return "slab"
+        if hasattr(comm, "reduce_begin") and hasattr(libasora, "evolve_slab_fold_all"):
+            if log is not None:
+                log("plane_flux: a face's sweep spans the whole box; this step takes the all-reduce loop instead of the slab exchange")
+            return "all-reduce"
+        return "three calls"
     if overlap and hasattr(comm, "raytrace_and_allreduce"):
         return "pipelined"
     if (getattr(comm, "device_loop", False) and hasattr(comm, "reduce_begin") and hasattr(libasora, "evolve_slab_fold_all")
@@ -460,7 +472,7 @@ def _scalars(dt, dr, R_max_LLS, convergence_fraction, sig, minlogtau, dlogtau, c
 
 def evolve3D_resident(dt, dr, src_flux, src_pos, uploads, N, photo_thin_table, minlogtau, dlogtau, R_max_LLS,
                       convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile="pyC2Ray.log", quiet=False,
-                      thermal=None, clumping=None, src_spectrum=None, lls=None, periodic=True):
+                      thermal=None, clumping=None, src_spectrum=None, lls=None, periodic=True, plane_flux=None):
     """evolve3D for a caller that keeps the grids on the device between time steps (the C2Ray class with
     ``device_resident = True``): same loop, log lines and results as :func:`evolve3D` with ``use_gpu=True``, but only the
     grids in ``uploads`` ({grid selector: host array}, those the caller changed on the host) cross PCIe, and nothing
@@ -470,9 +482,11 @@ def evolve3D_resident(dt, dr, src_flux, src_pos, uploads, N, photo_thin_table, m
     end-of-step temperature afterwards, PHI_HEAT the heating rates.
     ``clumping`` as in :func:`evolve3D`; like the other grids, an (N, N, N) grid crosses PCIe only when ``uploads`` holds it
     (under ``_capi.GRID_CLUMP``, checked then): otherwise GRID_CLUMP must still hold it from an earlier step.
-    ``src_spectrum``, ``lls`` and ``periodic`` as in :func:`evolve3D`."""
+    ``src_spectrum``, ``lls``, ``periodic`` and ``plane_flux`` as in :func:`evolve3D`."""
     periodic = periodic_spec(periodic, "evolve3D_resident")
     lls = lls_spec(lls, "evolve3D_resident")
+    faces = plane_flux_spec(plane_flux, "evolve3D_resident", True, lambda: load_asora().num_spectra())
+    src_flux, src_pos = source_arrays(src_flux, src_pos, faces)
     spec = source_spectrum_spec(src_spectrum, src_flux.shape[0], True, lambda: load_asora().num_spectra(), "evolve3D_resident")
     clump = _clumping_spec(clumping, N, check_values=_capi.GRID_CLUMP in uploads)
     if clump is not None and clump.grid is not None and _capi.GRID_CLUMP in uploads and uploads[_capi.GRID_CLUMP] is not clumping:
@@ -481,14 +495,14 @@ def evolve3D_resident(dt, dr, src_flux, src_pos, uploads, N, photo_thin_table, m
         raise RuntimeError("GPU not initialized. Please initialize it by calling device_init(N)")
     scalars = _scalars(dt, dr, R_max_LLS, convergence_fraction, sig, minlogtau, dlogtau, (bh00, albpow, colh0, temph0, abu_c),
                        logfile, quiet)
-    with _clumping_reset(clump), lls_reset(lls, load_asora), open_boundaries(periodic, load_asora):
-        return _evolve_resident(scalars, src_flux, src_pos, uploads, N, photo_thin_table, thermal, clump, spec, lls)
+    with _clumping_reset(clump), lls_reset(lls, load_asora), open_boundaries(periodic, load_asora), plane_flux_reset(faces, load_asora):
+        return _evolve_resident(scalars, src_flux, src_pos, uploads, N, photo_thin_table, thermal, clump, spec, lls, faces)
 
 
-def _evolve_resident(scalars, src_flux, src_pos, uploads, N, photo_thin_table, thermal, clump, spec=None, lls=None):
+def _evolve_resident(scalars, src_flux, src_pos, uploads, N, photo_thin_table, thermal, clump, spec=None, lls=None, faces=()):
     libasora = load_asora()
     step = _prologue(libasora, scalars, N, photo_thin_table.shape[0], src_flux, np.asarray(src_pos), src_flux, uploads, clump,
-                     say_copied=True, clump_upload=False, spec=spec, lls=lls)
+                     say_copied=True, clump_upload=False, spec=spec, lls=lls, faces=faces)
     niter = _one_gpu_loop(libasora, step, thermal)
     printlog("Multiple source convergence reached.", step.logfile, step.quiet)
     libasora.grid_copy(_capi.GRID_XH, _capi.GRID_XH_INTERMED)       # the next step starts from the new ionised fraction
@@ -511,7 +525,8 @@ def _thermal_ranks_refusal(comm):
     return None
 
 
-def _evolve(scalars, src_flux, src_pos, grids, photo_thin_table, ranks=_ONE_RANK, thermal=None, clump=None, spec=None, lls=None):
+def _evolve(scalars, src_flux, src_pos, grids, photo_thin_table, ranks=_ONE_RANK, thermal=None, clump=None, spec=None, lls=None,
+            faces=()):
     """A use_gpu=True step on host arrays, grids = (temp, ndens, xh), on one GPU or across `ranks`; `thermal` on one GPU, or
     across ranks on the "slab" and "all-reduce" device loops; `spec`, the spectrum of each source of the whole list (None: all 0),
     which follows its source through every re-ordering and sharding below."""
@@ -523,7 +538,8 @@ def _evolve(scalars, src_flux, src_pos, grids, photo_thin_table, ranks=_ONE_RANK
     libasora = load_asora()
     temp, ndens, xh = grids
     N = temp.shape[0]                   # mesh size
-    strategy = _loop_strategy(libasora, comm, distributed)
+    strategy = _loop_strategy(libasora, comm, distributed, faces,
+                              (lambda line: printlog(line, scalars["logfile"], scalars["quiet"])) if rank == 0 else None)
     if thermal is not None and strategy not in ("one GPU", "slab", "all-reduce"):
         raise ValueError(f"evolve3D_MPI: the thermal mode across ranks runs on the slab and all-reduce device loops; this step would "
                          f"take the {strategy} loop (the [k][j][i] twins are off?), where it is single-GPU only")
@@ -547,7 +563,7 @@ def _evolve(scalars, src_flux, src_pos, grids, photo_thin_table, ranks=_ONE_RANK
     step = _prologue(libasora, scalars, N, photo_thin_table.shape[0], src_flux, my_pos, my_flux,
                      {_capi.GRID_NDENS: ndens, _capi.GRID_TEMP: temp, _capi.GRID_XH: xh}, clump, ranks=ranks,
                      calling=f"Calling evolve3D with {nprocs:n} MPI-processors..." if distributed else "Calling evolve3D...",
-                     xh_copies=distributed, say_copied=not distributed, spec=my_spec, lls=lls)
+                     xh_copies=distributed, say_copied=not distributed, spec=my_spec, lls=lls, faces=faces)
     if strategy == "one GPU":
         niter = _one_gpu_loop(libasora, step, thermal)
     elif strategy == "slab":
@@ -611,7 +627,8 @@ def evolve3D(dt, dr,
              minlogtau, dlogtau,
              R_max_LLS, convergence_fraction,
              sig, bh00, albpow, colh0, temph0, abu_c,
-             logfile="pyC2Ray.log", quiet=False, *, thermal=None, clumping=None, src_spectrum=None, lls=None, periodic=True):
+             logfile="pyC2Ray.log", quiet=False, *, thermal=None, clumping=None, src_spectrum=None, lls=None, periodic=True,
+             plane_flux=None):
     """Evolve the ionised fraction of the whole grid over one time step.
 
     Parameters have the reference's meaning (pyc2ray/evolve.py:49-109): dt [s], dr [cm],
@@ -651,19 +668,28 @@ def evolve3D(dt, dr,
     library's own option alone).  Anything but a bool, or False with use_gpu=False (the sub-box sweep has no such mode), raises
     ValueError before any GPU work; the library refuses meshes beyond 512.  Works with `thermal`, `clumping`, `src_spectrum` and
     `lls`.
+
+    plane_flux : None or an empty sequence (off), a :class:`pyc2ray_amd.planeflux.PlaneFlux` or a sequence of them, one per face at
+    most: a plane-parallel photon flux that enters the box through that face, swept along the axis over
+    all N cells -- never wrapping, whatever `periodic` says, and not cut at R_max_LLS.  The flux is in the units of src_flux per
+    cm^2 (1e48 photons s^-1 cm^-2).  With faces, src_flux / src_pos may be empty, and each face counts as one source in the
+    convergence criterion.  Anything else, a face given twice, or faces with use_gpu=False raises ValueError before any GPU work.
+    Works with `thermal`, `clumping`, `src_spectrum`, `lls` and `periodic`.
     """
     periodic = periodic_spec(periodic, "evolve3D", use_gpu)
     lls = lls_spec(lls, "evolve3D")
+    faces = plane_flux_spec(plane_flux, "evolve3D", use_gpu, lambda: load_asora().num_spectra())
+    src_flux, src_pos = source_arrays(src_flux, src_pos, faces)
     spec = source_spectrum_spec(src_spectrum, src_flux.shape[0], use_gpu, lambda: load_asora().num_spectra(), "evolve3D")
     clump = _clumping_spec(clumping, np.shape(temp)[0])
     if not use_gpu and thermal is not None:
         raise ValueError("evolve3D: the thermal mode needs use_gpu=True (the use_gpu=False raytracer has no thermal form)")
     scalars = _scalars(dt, dr, R_max_LLS, convergence_fraction, sig, minlogtau, dlogtau, (bh00, albpow, colh0, temph0, abu_c),
                        logfile, quiet)
-    with _clumping_reset(clump), lls_reset(lls, load_asora), open_boundaries(periodic, load_asora):
+    with _clumping_reset(clump), lls_reset(lls, load_asora), open_boundaries(periodic, load_asora), plane_flux_reset(faces, load_asora):
         if use_gpu:
             return _evolve(scalars, src_flux, src_pos, (temp, ndens, xh), photo_thin_table, thermal=thermal, clump=clump, spec=spec,
-                           lls=lls)
+                           lls=lls, faces=faces)
         return _evolve_cpu_semantics(scalars, src_flux, src_pos, (temp, ndens, xh), (photo_thin_table, photo_thick_table),
                                      (max_subbox, subboxsize, loss_fraction), clump=clump, lls=lls)
 
@@ -677,7 +703,8 @@ def evolve3D_MPI(dt, dr,
                  minlogtau, dlogtau,
                  R_max_LLS, convergence_fraction,
                  sig, bh00, albpow, colh0, temph0, abu_c,
-                 logfile="pyC2Ray.log", quiet=False, *, thermal=None, clumping=None, src_spectrum=None, lls=None, periodic=True):
+                 logfile="pyC2Ray.log", quiet=False, *, thermal=None, clumping=None, src_spectrum=None, lls=None, periodic=True,
+                 plane_flux=None):
     """Source-sharded variant (pyc2ray/evolve.py:249-498): rank r traces the contiguous block
     [r*(Ns//nprocs), (r+1)*(Ns//nprocs)) of the source list, the last rank to the end
     (evolve.py:362-367); the per-rank rate grids are summed across ranks each iteration.
@@ -699,9 +726,14 @@ def evolve3D_MPI(dt, dr,
     ``lls`` as in :func:`evolve3D`; every rank passes the same one and sets the same state, on every loop.
     ``periodic`` as in :func:`evolve3D`, the same on every rank and on every loop; the planes the ranks exchange stay those of the
     periodic trace (the wrapped ones then carry zeros).
+    ``plane_flux`` as in :func:`evolve3D`, the same on every rank.  The faces belong to rank 0: only its library holds them, and
+    its sweep needs nHI of the whole box -- which the all-reduce device loop, the pipelined loop and the three-call loop have on
+    every rank.  A ``TorchComm`` set up for the slab exchange runs the all-reduce loop for such a step (one log line says so).
     """
     periodic = periodic_spec(periodic, "evolve3D_MPI", use_gpu)
     lls = lls_spec(lls, "evolve3D_MPI")
+    faces = plane_flux_spec(plane_flux, "evolve3D_MPI", use_gpu, lambda: load_asora().num_spectra())
+    src_flux, src_pos = source_arrays(src_flux, src_pos, faces)
     spec = source_spectrum_spec(src_spectrum, src_flux.shape[0], use_gpu, lambda: load_asora().num_spectra(), "evolve3D_MPI")
     if thermal is not None:
         if not use_gpu:
@@ -714,9 +746,10 @@ def evolve3D_MPI(dt, dr,
     scalars = _scalars(dt, dr, R_max_LLS, convergence_fraction, sig, minlogtau, dlogtau, (bh00, albpow, colh0, temph0, abu_c),
                        logfile, quiet)
     ranks = (use_mpi, comm, rank, nprocs)
-    with _clumping_reset(clump), lls_reset(lls, load_asora), open_boundaries(periodic, load_asora):
+    with _clumping_reset(clump), lls_reset(lls, load_asora), open_boundaries(periodic, load_asora), \
+            plane_flux_reset(faces if rank == 0 else (), load_asora):
         if use_gpu:
             return _evolve(scalars, src_flux, src_pos, (temp, ndens, xh), photo_thin_table, ranks, thermal=thermal, clump=clump,
-                           spec=spec, lls=lls)
+                           spec=spec, lls=lls, faces=faces)
         return _evolve_cpu_semantics(scalars, src_flux, src_pos, (temp, ndens, xh), (photo_thin_table, photo_thick_table),
                                      (max_subbox, subboxsize, loss_fraction), ranks, clump=clump, lls=lls)

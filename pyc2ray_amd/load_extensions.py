@@ -418,6 +418,23 @@ class _LibAsora:
         _capi.check(self._lib.asora_get_lls_opacity(C.byref(a), C.byref(b)), "get_lls_opacity")
         return a.value, b.value
 
+    def plane_flux(self, face, flux, spectrum=None):
+        """Plane-parallel flux through faces of the box (include/asora_hip.h, asora_plane_flux): sequences of equal length, face
+        0 ... 5 = -x +x -y +y -z +z, flux in 1e48 photons s^-1 cm^-2, spectrum the table set (None: 0); empty sequences: off."""
+        f = np.ascontiguousarray(face, dtype=np.int32).ravel()
+        x = np.ascontiguousarray(flux, dtype=np.float64).ravel()
+        s = np.zeros(f.size, dtype=np.int32) if spectrum is None else np.ascontiguousarray(spectrum, dtype=np.int32).ravel()
+        if not (f.size == x.size == s.size):
+            raise ValueError("plane_flux: face, flux and spectrum must have the same length")
+        _capi.check(self._lib.asora_plane_flux(int(f.size), _capi.iptr(f), _capi.dptr(x), _capi.iptr(s)), "plane_flux")
+
+    def get_plane_flux(self):
+        """The setting as a list of (face, flux, spectrum)."""
+        n = C.c_int(0)
+        f, x, s = np.zeros(6, dtype=np.int32), np.zeros(6), np.zeros(6, dtype=np.int32)
+        _capi.check(self._lib.asora_get_plane_flux(C.byref(n), _capi.iptr(f), _capi.dptr(x), _capi.iptr(s)), "get_plane_flux")
+        return [(int(f[q]), float(x[q]), int(s[q])) for q in range(n.value)]
+
     def thermal_stats(self):
         """(cells that hit max_substeps, cells clamped to t_floor, most substeps of one integration) since the last
         chemistry_device / evolve_begin."""

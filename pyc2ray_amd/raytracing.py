@@ -7,6 +7,7 @@ from . import _capi, _residency
 from .asora_core import cuda_is_init
 from .boundaries import open_boundaries, periodic_spec
 from .lls import lls_reset, lls_spec
+from .planeflux import log_plane_flux, plane_flux_reset, plane_flux_spec, source_arrays
 from .load_extensions import load_asora, load_c2ray
 from .spectra import source_spectrum_spec
 from .utils import printlog
@@ -24,7 +25,8 @@ def do_raytracing(dr,
                   minlogtau, dlogtau,
                   R_max_LLS,
                   sig,
-                  logfile="pyC2Ray.log", quiet=False, stats=False, src_spectrum=None, lls=None, periodic=True):
+                  logfile="pyC2Ray.log", quiet=False, stats=False, src_spectrum=None, lls=None, periodic=True,
+                  plane_flux=None):
     """Raytrace all sources once and return the photo-ionisation rate grid.
 
     Same 17 positional arguments as the reference (pyc2ray/raytracing.py:34-43).  Returns
@@ -46,23 +48,28 @@ def do_raytracing(dr,
     systems among the absorbers the rays cross.
 
     ``periodic``: as in :func:`pyc2ray_amd.evolve3D` -- False: open boundaries, no rate beyond a face of the box (use_gpu=True only).
+
+    ``plane_flux``: as in :func:`pyc2ray_amd.evolve3D` -- plane-parallel fluxes through faces of the box (use_gpu=True only); the
+    source list may then be empty.
     """
     periodic = periodic_spec(periodic, "do_raytracing", use_gpu)
     lls = lls_spec(lls, "do_raytracing")
+    faces = plane_flux_spec(plane_flux, "do_raytracing", use_gpu, lambda: load_asora().num_spectra())
+    src_flux, src_pos = source_arrays(src_flux, src_pos, faces)
     spec = source_spectrum_spec(src_spectrum, src_flux.shape[0], use_gpu, lambda: load_asora().num_spectra(), "do_raytracing")
     if use_gpu and not cuda_is_init():
         raise RuntimeError("GPU not initialized. Please initialize it by calling device_init(N)")
     _residency.reclaim()              # this call overwrites device grids a resident C2Ray object may be relying on
 
-    with lls_reset(lls, load_asora), open_boundaries(periodic, load_asora):
+    with lls_reset(lls, load_asora), open_boundaries(periodic, load_asora), plane_flux_reset(faces, load_asora):
         return _do_raytracing(dr, src_flux, src_pos, use_gpu, max_subbox, subboxsize, loss_fraction, ndens, xh_av, photo_thin_table,
                               photo_thick_table, heat_thin_table, heat_thick_table, minlogtau, dlogtau, R_max_LLS, sig, logfile,
-                              quiet, stats, spec, lls)
+                              quiet, stats, spec, lls, faces)
 
 
 def _do_raytracing(dr, src_flux, src_pos, use_gpu, max_subbox, subboxsize, loss_fraction, ndens, xh_av, photo_thin_table,
                    photo_thick_table, heat_thin_table, heat_thick_table, minlogtau, dlogtau, R_max_LLS, sig, logfile, quiet, stats,
-                   spec, lls):
+                   spec, lls, faces=()):
     NumSrc = src_flux.shape[0]
     N = ndens.shape[0]
     NumTau = photo_thin_table.shape[0]
@@ -105,6 +112,7 @@ def _do_raytracing(dr, src_flux, src_pos, use_gpu, max_subbox, subboxsize, loss_
     if lls is not None:
         lls.apply(libasora)
         lls.log(logfile, quiet)
+    log_plane_flux(faces, logfile, quiet)
 
     # photo-heating: only when real heating tables are passed (the reference's callers pass zeros when
     # compute_heating_rates is off, c2ray_base.py:430-431)
