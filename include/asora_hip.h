@@ -410,6 +410,27 @@ int asora_plane_flux(int count, const int32_t *face, const double *flux, const i
 /* Reads the setting back: *count, and the first *count entries of face / flux / spectrum (room for 6 each; any may be NULL). */
 int asora_get_plane_flux(int *count, int32_t *face, double *flux, int32_t *spectrum);
 
+/* Photon budget and mean ionised fractions of a time step: twelve sums over the cells of the planes
+ * [i_begin, i_begin + i_count) of the device grids, formed by ONE read-only streaming pass (no grid is written) and returned on
+ * the host.  With n = NDENS, x0 = XH, x1 = XH_INTERMED, xav = XH_AV, Gamma = PHI_ION; c the clumping factor of the cell
+ * (asora_clumping: 1, the constant, or CLUMP); (a, b) the pair of asora_get_lls_opacity; T = TEMP, or (TEMP + TEMP_END) / 2 with
+ * use_temp_end != 0; ne = n (xav + abu_c), nHI = n (1 - xav):
+ *   CELLS 1            N   n              X   x1                 NX   n x1
+ *   NX0   n x0         DNX n (x1 - x0)    PHOTO Gamma nHI        LLS  Gamma (n b + a)
+ *   REC   c bh00 (T/1e4)^albpow ne n xav  COL colh0 sqrt(T) exp(-temph0/T) ne nHI        T  T        NT  n T
+ * A thermal step's chemistry uses a time-averaged temperature of its own that is not stored; use_temp_end evaluates REC and COL at
+ * the mean of the step's first and last temperature instead.  Call it after the step's loop has ended (after asora_evolve_poll
+ * reported convergence, or after the last chemistry pass) and before XH is overwritten with XH_INTERMED.
+ * The sums are order-fixed (no floating-point atomics): two calls on the same grids return the same bits.  Ordered on
+ * asora_stream(); returns once the twelve doubles are on the host (one synchronisation).  With ASORA_OPT_TIMING the pass counts
+ * under ASORA_KERNEL_FINISH.  i_count = 0: twelve zeros.  Fails with code 3 for sums = NULL or a plane range outside the mesh,
+ * with code 4 when a grid it reads holds no data: NDENS, XH, XH_INTERMED, XH_AV, PHI_ION, TEMP; TEMP_END with use_temp_end;
+ * CLUMP in clumping mode 2. */
+enum { ASORA_BUDGET_CELLS = 0, ASORA_BUDGET_N = 1, ASORA_BUDGET_X = 2, ASORA_BUDGET_NX = 3, ASORA_BUDGET_NX0 = 4,
+       ASORA_BUDGET_DNX = 5, ASORA_BUDGET_PHOTO = 6, ASORA_BUDGET_LLS = 7, ASORA_BUDGET_REC = 8, ASORA_BUDGET_COL = 9,
+       ASORA_BUDGET_T = 10, ASORA_BUDGET_NT = 11, ASORA_BUDGET_COUNT = 12 };
+int asora_step_budget(double bh00, double albpow, double colh0, double temph0, double abu_c, int use_temp_end, int i_begin, int i_count, double *sums);
+
 /* ------------------------------------------------------------------------------------------ */
 /* C. Options, measurement and diagnostics                                                     */
 /* ------------------------------------------------------------------------------------------ */

@@ -23,6 +23,9 @@ MAX_SPECTRA = 16
 KERNEL_RAYTRACE, KERNEL_CHEMISTRY, KERNEL_PREP, KERNEL_FINISH = range(4)
 VARIANT_PAIRED, VARIANT_ALIGNED, VARIANT_BUFFER_ATOMICS, VARIANT_SPLIT_DESCRIPTORS, VARIANT_SKIP_ZERO, VARIANT_GLOBAL_SHELLS = 1, 2, 4, 8, 16, 32
 VARIANT_OPEN_BOUNDARIES = 64
+(BUDGET_CELLS, BUDGET_N, BUDGET_X, BUDGET_NX, BUDGET_NX0, BUDGET_DNX, BUDGET_PHOTO, BUDGET_LLS, BUDGET_REC, BUDGET_COL,
+ BUDGET_T, BUDGET_NT) = range(12)
+BUDGET_COUNT = 12
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -105,6 +108,7 @@ SIGNATURES = {
     "asora_get_lls_opacity": (C.c_int, [_dp, _dp]),
     "asora_plane_flux": (C.c_int, [C.c_int, _ip, _dp, _ip]),
     "asora_get_plane_flux": (C.c_int, [C.POINTER(C.c_int), _ip, _dp, _ip]),
+    "asora_step_budget": (C.c_int, [C.c_double] * 5 + [C.c_int, C.c_int, C.c_int, _dp]),
     "asora_set_option": (C.c_int, [C.c_int, C.c_int]),
     "asora_get_option": (C.c_int, [C.c_int]),
     "asora_kernel_time_ms": (C.c_int, [C.c_int, _dp, C.POINTER(C.c_long)]),

@@ -27,6 +27,9 @@ Differences from the reference:
   * ``Photo: plane_flux_face`` / ``plane_flux`` / ``plane_flux_spectrum`` (optional keys, scalars or lists of equal length) and the
     attribute ``plane_flux`` add a plane-parallel photon flux that enters through faces of the box (pyc2ray_amd/planeflux.py;
     evolve3D's ``plane_flux=``; use_gpu only).  ``plane_flux`` of the file is in photons s^-1 cm^-2.
+  * ``Output: photon_budget: 0|1`` (optional key, default 0) and the attribute ``photon_budget`` (a bool, assignable between steps)
+    close every time step with its photon statistics (pyc2ray_amd/budget.py; evolve3D's ``budget=``; use_gpu only): ``last_budget``,
+    the cumulative ``total_budget``, and one line in the log.
 """
 import atexit
 import re
@@ -43,6 +46,7 @@ from .asora_core import cuda_is_init, device_close, device_init, photo_table_to_
 from . import _capi, _residency
 from .evolve import evolve3D, evolve3D_MPI, evolve3D_resident
 from .boundaries import periodic_spec
+from .budget import StepBudget
 from .lls import LLSOpacity, LLSSchedule, lls_spec
 from .planeflux import PlaneFlux, plane_flux_spec
 from .load_extensions import load_asora
@@ -228,6 +232,7 @@ class C2Ray:
         self._lls_init()
         self._boundaries_init()
         self._plane_flux_init()
+        self._photon_budget_init()
         if self.rank == 0:
             if self.gpu:
                 q_max = np.ceil(1.73205080757 * min(self.R_max_LLS, 1.73205080757 * self.N / 2))
@@ -381,11 +386,51 @@ class C2Ray:
     def plane_flux(self, value):
         self.__dict__["_plane_flux"] = plane_flux_spec(value, "C2Ray.plane_flux", self.gpu)    # ValueError for what evolve3D would refuse, now
 
+    def _photon_budget_init(self):
+        """The optional key ``Output: photon_budget`` (0 | 1; absent: 0): whether every step is closed with its photon budget,
+        until ``photon_budget`` is assigned."""
+        v = (self._ld.get('Output') or {}).get('photon_budget', 0)
+        if isinstance(v, (bool, np.bool_)):
+            v = int(v)
+        if not isinstance(v, (int, np.integer)) or v not in (0, 1):
+            raise ValueError(f"Output: photon_budget must be 0 or 1, not {v!r}")
+        self.last_budget, self.total_budget = None, StepBudget()
+        self._set_photon_budget(bool(v), "Output: photon_budget: 1")
+
+    def _set_photon_budget(self, value, who):
+        if not isinstance(value, (bool, np.bool_)):
+            raise ValueError(f"{who}: photon_budget must be a bool, not {type(value).__name__}")
+        if value and not self.gpu:
+            raise ValueError(f"{who}: photon_budget needs use_gpu=True (the use_gpu=False loop takes no photon budget)")
+        self.__dict__["_photon_budget"] = bool(value)
+
+    @property
+    def photon_budget(self):
+        """Is every time step closed with its photon budget (pyc2ray_amd.budget.StepBudget; use_gpu=True only: on an object
+        without, True is refused at the assignment)?  A driver may assign a bool between steps.  After a step ``last_budget``
+        holds the step's budget and ``total_budget`` the sum since the object was made; rank 0 writes one line to the log.  The
+        sums are reduced on the device: no grid crosses PCIe for them, on the device-resident path either."""
+        return self.__dict__.get("_photon_budget", False)
+
+    @photon_budget.setter
+    def photon_budget(self, value):
+        self._set_photon_budget(value, "C2Ray.photon_budget")
+
+    def _close_budget(self, budget):
+        """A filled budget of the step just run (None: off) becomes last_budget, joins total_budget and the log."""
+        if budget is None:
+            return
+        self.last_budget = budget
+        self.total_budget = self.__dict__.get("total_budget", StepBudget()) + budget
+        if self.rank == 0:
+            self.printlog(budget.log_line())
+
     def evolve3D(self, dt, src_flux, src_pos, src_spectrum=None):
         """Evolve the grid over one time step (c2ray_base.py:170-226).  src_spectrum: with ``BlackBodySource: Teff`` a list, the
         index into it of each source's temperature (None: every source the first one); see pyc2ray_amd.evolve3D."""
         if self.device_resident and self.gpu and not self.mpi:
             return self._evolve3D_resident(dt, src_flux, src_pos, src_spectrum)
+        budget = {"budget": StepBudget()} if self.photon_budget else {}      # (off: the entry never hears of it)
         head = (dt, self.dr, src_flux, src_pos, self.gpu, self.max_subbox, self.subboxsize, self.loss_fraction)
         tail = (self.temp, self.ndens, self.xh, self.photo_thin_table, self.photo_thick_table, self.minlogtau, self.dlogtau,
                 self.R_max_LLS, self.convergence_fraction, self.sig, self.bh00, self.albpow, self.colh0, self.temph0, self.abu_c,
@@ -394,13 +439,14 @@ class C2Ray:
         if self.mpi and np.size(src_flux) >= self.nprocs:
             result = evolve3D_MPI(*head, self.mpi, self.comm, self.rank, self.nprocs, *tail, thermal=thermal,
                                   clumping=self.__dict__["_clumping"], src_spectrum=src_spectrum, lls=self.lls,
-                                  periodic=self.periodic, plane_flux=self.plane_flux)
+                                  periodic=self.periodic, plane_flux=self.plane_flux, **budget)
         else:
             result = evolve3D(*head, *tail, thermal=thermal, clumping=self.__dict__["_clumping"], src_spectrum=src_spectrum,
-                              lls=self.lls, periodic=self.periodic, plane_flux=self.plane_flux)
+                              lls=self.lls, periodic=self.periodic, plane_flux=self.plane_flux, **budget)
         self.xh, self.phi_ion = result[:2]
         if thermal is not None:
             self.temp = result[2]
+        self._close_budget(budget.get("budget"))
 
     @classmethod
     def _fingerprint(cls, arr):
@@ -457,12 +503,14 @@ class C2Ray:
         phi_host = d.get("_grid_phi_ion")                       # (a subclass may never have assigned phi_ion)
         if phi_host is None or (phi_host.flags.f_contiguous and not phi_host.flags.c_contiguous):
             d["_grid_phi_ion"] = np.zeros(self.shape)           # the GPU path returns C-ordered rates (evolve.py:200)
+        budget = {"budget": StepBudget()} if self.photon_budget else {}      # (off: the entry never hears of it)
         evolve3D_resident(dt, self.dr, src_flux, src_pos, uploads, self.N, self.photo_thin_table, self.minlogtau, self.dlogtau,
                           self.R_max_LLS, self.convergence_fraction, self.sig, self.bh00, self.albpow, self.colh0, self.temph0,
                           self.abu_c, self.logfile, thermal=self._thermal_params(), clumping=clumping, src_spectrum=src_spectrum,
-                          lls=self.lls, periodic=self.periodic, plane_flux=self.plane_flux)
+                          lls=self.lls, periodic=self.periodic, plane_flux=self.plane_flux, **budget)
         self._host_newer -= {"ndens", "temp", "xh", "phi_ion", "clumping"}
         self._device_newer |= {"xh", "phi_ion"} if self.isothermal else {"xh", "phi_ion", "temp"}
+        self._close_budget(budget.get("budget"))
 
     def cosmo_evolve(self, dt):
         """Advance time and redshift by dt, diluting density and rescaling the cell size when the run is

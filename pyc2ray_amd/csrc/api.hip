@@ -100,6 +100,8 @@ static int release_all()
     st.clump_mode = 0; st.clump_c = 1.0;
     st.lls_a = st.lls_b = 0.0;
     st.plane = PlaneFluxSet{};
+    drop(st.budget_partial);
+    if (st.budget_host) { (void)hipHostFree(st.budget_host); st.budget_host = nullptr; }
     for (int g = 0; g < ASORA_GRID_COUNT; ++g) { st.grid[g] = nullptr; st.grid_valid[g] = false; }
     st.nhi = st.staging = st.acc = nullptr;
     drop(st.arena); st.arena_bytes = 0;

@@ -245,6 +245,10 @@ struct State {
     double *red_final = nullptr;   // [3]
     double *red_host = nullptr;    // pinned [3]
     int red_blocks = 0;
+    // the step budget's own buffers (asora_step_budget, step_budget.hip), allocated by the first call: per-workgroup partials
+    // [ASORA_BUDGET_COUNT][red_blocks] with the twelve results behind them, and where those arrive on the host (pinned)
+    double *budget_partial = nullptr;
+    double *budget_host = nullptr;
 
     unsigned long long *counters = nullptr; // [COUNTER_FIELDS * COUNTER_SLOTS] device: gamma cells, evaluated cells, exact zeros left out, spread over the slots
     long long last_gamma_cells = 0, last_eval_cells = 0;

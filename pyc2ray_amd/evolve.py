@@ -19,6 +19,7 @@ import numpy as np
 from . import _capi, _residency
 from .asora_core import cuda_is_init
 from .boundaries import open_boundaries, periodic_spec
+from .budget import budget_spec
 from .lls import lls_reset, lls_spec
 from .planeflux import log_plane_flux, plane_flux_reset, plane_flux_spec, source_arrays
 from .load_extensions import load_asora, load_c2ray
@@ -406,6 +407,19 @@ def _allreduce_phi(libasora, N, use_mpi, comm, rank):
     libasora.grid_to_device(_capi.GRID_PHI_ION, phi)
 
 
+def _take_budget(libasora, budget, step, src_flux, faces, thermal, planes=None, comm=None):
+    """Fill `budget` (a pyc2ray_amd.budget.StepBudget) from the device grids of the step whose loop has just ended: XH still holds
+    the step's starting state, XH_INTERMED / XH_AV / PHI_ION its results.  One call of the library over `planes` = (i_begin,
+    i_count), None: every plane.  `comm`: the planes are this rank's share of the grid (the slab loop), and the twelve sums are
+    added over the ranks on the host -- one small collective that every rank must reach."""
+    sums = libasora.step_budget(step.chem, use_temp_end=thermal is not None, planes=planes)
+    if comm is not None:
+        total = np.zeros_like(sums)
+        comm.Allreduce(sums, total)
+        sums = total
+    budget.fill(sums, step.dt, step.dr, step.N, src_flux, faces)
+
+
 class _Clumping:
     """A validated ``clumping=`` argument: ``constant`` (a float != 1) or ``grid`` (an (N, N, N)
     float64 array), the sub-grid clumping factor C = <n^2>/<n>^2 of the case-B recombination rate."""
@@ -472,7 +486,7 @@ def _scalars(dt, dr, R_max_LLS, convergence_fraction, sig, minlogtau, dlogtau, c
 
 def evolve3D_resident(dt, dr, src_flux, src_pos, uploads, N, photo_thin_table, minlogtau, dlogtau, R_max_LLS,
                       convergence_fraction, sig, bh00, albpow, colh0, temph0, abu_c, logfile="pyC2Ray.log", quiet=False,
-                      thermal=None, clumping=None, src_spectrum=None, lls=None, periodic=True, plane_flux=None):
+                      thermal=None, clumping=None, src_spectrum=None, lls=None, periodic=True, plane_flux=None, budget=None):
     """evolve3D for a caller that keeps the grids on the device between time steps (the C2Ray class with
     ``device_resident = True``): same loop, log lines and results as :func:`evolve3D` with ``use_gpu=True``, but only the
     grids in ``uploads`` ({grid selector: host array}, those the caller changed on the host) cross PCIe, and nothing
@@ -482,7 +496,8 @@ def evolve3D_resident(dt, dr, src_flux, src_pos, uploads, N, photo_thin_table, m
     end-of-step temperature afterwards, PHI_HEAT the heating rates.
     ``clumping`` as in :func:`evolve3D`; like the other grids, an (N, N, N) grid crosses PCIe only when ``uploads`` holds it
     (under ``_capi.GRID_CLUMP``, checked then): otherwise GRID_CLUMP must still hold it from an earlier step.
-    ``src_spectrum``, ``lls``, ``periodic`` and ``plane_flux`` as in :func:`evolve3D`."""
+    ``src_spectrum``, ``lls``, ``periodic``, ``plane_flux`` and ``budget`` as in :func:`evolve3D`."""
+    budget = budget_spec(budget, "evolve3D_resident")
     periodic = periodic_spec(periodic, "evolve3D_resident")
     lls = lls_spec(lls, "evolve3D_resident")
     faces = plane_flux_spec(plane_flux, "evolve3D_resident", True, lambda: load_asora().num_spectra())
@@ -496,15 +511,18 @@ def evolve3D_resident(dt, dr, src_flux, src_pos, uploads, N, photo_thin_table, m
     scalars = _scalars(dt, dr, R_max_LLS, convergence_fraction, sig, minlogtau, dlogtau, (bh00, albpow, colh0, temph0, abu_c),
                        logfile, quiet)
     with _clumping_reset(clump), lls_reset(lls, load_asora), open_boundaries(periodic, load_asora), plane_flux_reset(faces, load_asora):
-        return _evolve_resident(scalars, src_flux, src_pos, uploads, N, photo_thin_table, thermal, clump, spec, lls, faces)
+        return _evolve_resident(scalars, src_flux, src_pos, uploads, N, photo_thin_table, thermal, clump, spec, lls, faces, budget)
 
 
-def _evolve_resident(scalars, src_flux, src_pos, uploads, N, photo_thin_table, thermal, clump, spec=None, lls=None, faces=()):
+def _evolve_resident(scalars, src_flux, src_pos, uploads, N, photo_thin_table, thermal, clump, spec=None, lls=None, faces=(),
+                     budget=None):
     libasora = load_asora()
     step = _prologue(libasora, scalars, N, photo_thin_table.shape[0], src_flux, np.asarray(src_pos), src_flux, uploads, clump,
                      say_copied=True, clump_upload=False, spec=spec, lls=lls, faces=faces)
     niter = _one_gpu_loop(libasora, step, thermal)
     printlog("Multiple source convergence reached.", step.logfile, step.quiet)
+    if budget is not None:
+        _take_budget(libasora, budget, step, src_flux, faces, thermal)
     libasora.grid_copy(_capi.GRID_XH, _capi.GRID_XH_INTERMED)       # the next step starts from the new ionised fraction
     if thermal is not None:
         libasora.grid_copy(_capi.GRID_TEMP, _capi.GRID_TEMP_END)    # ... and from the new temperature
@@ -526,7 +544,7 @@ def _thermal_ranks_refusal(comm):
 
 
 def _evolve(scalars, src_flux, src_pos, grids, photo_thin_table, ranks=_ONE_RANK, thermal=None, clump=None, spec=None, lls=None,
-            faces=()):
+            faces=(), budget=None):
     """A use_gpu=True step on host arrays, grids = (temp, ndens, xh), on one GPU or across `ranks`; `thermal` on one GPU, or
     across ranks on the "slab" and "all-reduce" device loops; `spec`, the spectrum of each source of the whole list (None: all 0),
     which follows its source through every re-ordering and sharding below."""
@@ -579,6 +597,14 @@ def _evolve(scalars, src_flux, src_pos, grids, photo_thin_table, ranks=_ONE_RANK
 
     if rank == 0:
         printlog("Multiple source convergence reached.", step.logfile, step.quiet)
+    if budget is not None:
+        # the slab loop: a rank's results are complete on the planes whose chemistry it ran, and the ranks add their sums up; on
+        # every other loop each rank holds the whole grids and reduces them itself
+        if strategy == "slab":
+            a, b = plan.own[rank]
+            _take_budget(libasora, budget, step, src_flux, faces, thermal, (a, b - a), comm)
+        else:
+            _take_budget(libasora, budget, step, src_flux, faces, thermal)
     if strategy == "slab":       # every rank returns the whole fields (evolve.py:480-481,497): collect the owners' slabs
         comm.slab_gather(libasora, plan, _capi.GRID_XH_INTERMED, N)
         comm.slab_gather(libasora, plan, _capi.GRID_PHI_ION, N)
@@ -628,7 +654,7 @@ def evolve3D(dt, dr,
              R_max_LLS, convergence_fraction,
              sig, bh00, albpow, colh0, temph0, abu_c,
              logfile="pyC2Ray.log", quiet=False, *, thermal=None, clumping=None, src_spectrum=None, lls=None, periodic=True,
-             plane_flux=None):
+             plane_flux=None, budget=None):
     """Evolve the ionised fraction of the whole grid over one time step.
 
     Parameters have the reference's meaning (pyc2ray/evolve.py:49-109): dt [s], dr [cm],
@@ -675,7 +701,13 @@ def evolve3D(dt, dr,
     cm^2 (1e48 photons s^-1 cm^-2).  With faces, src_flux / src_pos may be empty, and each face counts as one source in the
     convergence criterion.  Anything else, a face given twice, or faces with use_gpu=False raises ValueError before any GPU work.
     Works with `thermal`, `clumping`, `src_spectrum`, `lls` and `periodic`.
+
+    budget : None, or a :class:`pyc2ray_amd.budget.StepBudget` that is filled in place with the photon budget and the mean ionised
+    fractions of the step: twelve sums reduced on the device once the loop has ended, one call and one
+    synchronisation per time step; the return values are what they are without it.  Anything else, or a budget with
+    use_gpu=False, raises ValueError before any GPU work.  Works with every keyword above.
     """
+    budget = budget_spec(budget, "evolve3D", use_gpu)
     periodic = periodic_spec(periodic, "evolve3D", use_gpu)
     lls = lls_spec(lls, "evolve3D")
     faces = plane_flux_spec(plane_flux, "evolve3D", use_gpu, lambda: load_asora().num_spectra())
@@ -689,7 +721,7 @@ def evolve3D(dt, dr,
     with _clumping_reset(clump), lls_reset(lls, load_asora), open_boundaries(periodic, load_asora), plane_flux_reset(faces, load_asora):
         if use_gpu:
             return _evolve(scalars, src_flux, src_pos, (temp, ndens, xh), photo_thin_table, thermal=thermal, clump=clump, spec=spec,
-                           lls=lls, faces=faces)
+                           lls=lls, faces=faces, budget=budget)
         return _evolve_cpu_semantics(scalars, src_flux, src_pos, (temp, ndens, xh), (photo_thin_table, photo_thick_table),
                                      (max_subbox, subboxsize, loss_fraction), clump=clump, lls=lls)
 
@@ -704,7 +736,7 @@ def evolve3D_MPI(dt, dr,
                  R_max_LLS, convergence_fraction,
                  sig, bh00, albpow, colh0, temph0, abu_c,
                  logfile="pyC2Ray.log", quiet=False, *, thermal=None, clumping=None, src_spectrum=None, lls=None, periodic=True,
-                 plane_flux=None):
+                 plane_flux=None, budget=None):
     """Source-sharded variant (pyc2ray/evolve.py:249-498): rank r traces the contiguous block
     [r*(Ns//nprocs), (r+1)*(Ns//nprocs)) of the source list, the last rank to the end
     (evolve.py:362-367); the per-rank rate grids are summed across ranks each iteration.
@@ -729,7 +761,11 @@ def evolve3D_MPI(dt, dr,
     ``plane_flux`` as in :func:`evolve3D`, the same on every rank.  The faces belong to rank 0: only its library holds them, and
     its sweep needs nHI of the whole box -- which the all-reduce device loop, the pipelined loop and the three-call loop have on
     every rank.  A ``TorchComm`` set up for the slab exchange runs the all-reduce loop for such a step (one log line says so).
+    ``budget`` as in :func:`evolve3D`, on every rank or on none: every rank's is filled with the budget of the whole grid.  On the
+    slab loop a rank reduces the planes whose chemistry it ran and the twelve sums are added over the ranks (one small collective
+    after the loop); on every other loop each rank holds whole grids and reduces them itself.
     """
+    budget = budget_spec(budget, "evolve3D_MPI", use_gpu)
     periodic = periodic_spec(periodic, "evolve3D_MPI", use_gpu)
     lls = lls_spec(lls, "evolve3D_MPI")
     faces = plane_flux_spec(plane_flux, "evolve3D_MPI", use_gpu, lambda: load_asora().num_spectra())
@@ -750,6 +786,6 @@ def evolve3D_MPI(dt, dr,
             plane_flux_reset(faces if rank == 0 else (), load_asora):
         if use_gpu:
             return _evolve(scalars, src_flux, src_pos, (temp, ndens, xh), photo_thin_table, ranks, thermal=thermal, clump=clump,
-                           spec=spec, lls=lls, faces=faces)
+                           spec=spec, lls=lls, faces=faces, budget=budget)
         return _evolve_cpu_semantics(scalars, src_flux, src_pos, (temp, ndens, xh), (photo_thin_table, photo_thick_table),
                                      (max_subbox, subboxsize, loss_fraction), ranks, clump=clump, lls=lls)

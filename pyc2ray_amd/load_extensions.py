@@ -435,6 +435,21 @@ class _LibAsora:
         _capi.check(self._lib.asora_get_plane_flux(C.byref(n), _capi.iptr(f), _capi.dptr(x), _capi.iptr(s)), "get_plane_flux")
         return [(int(f[q]), float(x[q]), int(s[q])) for q in range(n.value)]
 
+    def step_budget(self, chem, use_temp_end=False, planes=None):
+        """The twelve sums of the photon budget of the step just run (include/asora_hip.h, asora_step_budget; the slots are
+        ``_capi.BUDGET_*``), reduced on the device: an array of 12 float64.  `chem` = (dt, bh00, albpow, colh0, temph0, abu_c) as
+        the chemistry calls take it (dt plays no part in the sums); `use_temp_end`: a thermal step, rates at the mean of TEMP and
+        TEMP_END; `planes` = (i_begin, i_count), None: every plane."""
+        _dt, bh00, albpow, colh0, temph0, abu_c = chem
+        i_begin, i_count = (0, self._N) if planes is None else planes
+        if i_count is None:
+            raise RuntimeError("step_budget: planes=None needs a device initialised through device_init (the mesh size)")
+        sums = np.zeros(_capi.BUDGET_COUNT, dtype=np.float64)
+        _capi.check(self._lib.asora_step_budget(float(bh00), float(albpow), float(colh0), float(temph0), float(abu_c),
+                                                1 if use_temp_end else 0, int(i_begin), int(i_count), _capi.dptr(sums)),
+                    "step_budget")
+        return sums
+
     def thermal_stats(self):
         """(cells that hit max_substeps, cells clamped to t_floor, most substeps of one integration) since the last
         chemistry_device / evolve_begin."""
