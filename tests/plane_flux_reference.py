@@ -111,7 +111,17 @@ def evolve3D_plane_oracle(faces, dt, dr, src_flux, src_pos, temp, ndens, xh, thi
     """evolve3D(..., plane_flux=faces) on the CPU: per iteration the oracle's point-source trace (skipped without point sources)
     plus the plane trace, then O.global_pass -- or, with `thermal_params` (a thermal_reference.Params) and the heating tables,
     thermal_reference.chemistry_thermal.  faces: (face, flux) pairs, all on the one table set.  The convergence criterion counts
-    the faces as sources.  Returns (xh_intermed, phi_ion, niter, history[, T_end, phi_heat])."""
+    the faces as sources.  With `clumping` (a factor or a grid) the step is step_reference.reference_step's, which has the clumped
+    passes; without, this loop stays as it is: it is one of the restatements that anchor that function.
+    Returns (xh_intermed, phi_ion, niter, history[, T_end, phi_heat])."""
+    if clumping is not None:
+        from step_reference import reference_step
+        case = dict(dt=dt, dr=dr, flux=np.asarray(src_flux, dtype=np.float64).ravel(), pos=np.asarray(src_pos).reshape(3, -1), temp=temp,
+                    ndens=ndens, xh=xh, thin=thin, thick=thick, heat_thin=heat_thin, heat_thick=heat_thick, minlogtau=minlogtau,
+                    dlogtau=dlogtau, R=R_max_LLS, conv=convergence_fraction, sig=sig, chem=(bh00, albpow, colh0, temph0, abu_c))
+        r = reference_step(case, thermal=thermal_params, clump=clumping, faces=[(f, x, 0) for f, x in faces], max_iter=max_iter)
+        out = (r["xh_intermed"], r["phi_ion"], r["niter"], r["history"])
+        return out + (r["T_end"], r["phi_heat"]) if thermal_params is not None else out
     NumSrc = int(np.size(src_flux))
     NumCells = ndens.size
     NumTau = thin.shape[0]
