@@ -431,6 +431,40 @@ enum { ASORA_BUDGET_CELLS = 0, ASORA_BUDGET_N = 1, ASORA_BUDGET_X = 2, ASORA_BUD
        ASORA_BUDGET_T = 10, ASORA_BUDGET_NT = 11, ASORA_BUDGET_COUNT = 12 };
 int asora_step_budget(double bh00, double albpow, double colh0, double temph0, double abu_c, int use_temp_end, int i_begin, int i_count, double *sums);
 
+/* Size distribution of the ionised regions by the mean-free-path method (Mesinger & Furlanetto 2007), on
+ * the device grid `which_grid` where it lies: n_rays rays start in random in-phase cells, fly in random directions and end at the
+ * first cell that is not in phase; their lengths, in cells, are binned.  A cell x is in phase when x >= threshold (phase 0: ionised
+ * regions of XH) or x < threshold (phase 1: neutral islands); a NaN is in neither.  No grid is written.  Three stages on
+ * asora_stream(): a threshold pass that turns the grid into a bit mask -- bit k & 63 of word (i N + j) W + (k >> 6), W = ceil(N / 64),
+ * pad bits 0 -- and one count per row (i, j); an exclusive scan of the counts, whose total is n_phase; the rays.
+ * Ray r is a pure function of (seed, r, mask), all hashes in uint64 with wrap-around:
+ *   mix(seed, c): z = seed + (c + 1) 0x9E3779B97F4A7C15; z = (z ^ z >> 30) 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) 0x94D049BB133111EB;
+ *                 z ^ z >> 31 (splitmix64);  u01(h) = (h >> 11) 2^-53;
+ *   start: the u-th in-phase cell in C order, u = mix(seed, 4 r) % n_phase;
+ *   direction: mu = 2 u01(mix(seed, 4 r + 1)) - 1, phi = 2 pi u01(mix(seed, 4 r + 2)), s = sqrt(1 - mu mu), d = (s cos phi, s sin phi, mu);
+ *   march: exact cell traversal from the cell centre.  Per axis a: step = sign(d_a), tDelta = 1 / |d_a| (infinite for d_a = 0),
+ *          m_a = 0 crossings.  Loop: tMax_a = (m_a + 0.5) tDelta_a; the axis of the smallest tMax (ties: the lowest), t = that tMax;
+ *          t > l_max: CAPPED, length l_max; else one cell along the axis, ++m_a; periodic != 0: wrap; else outside [0, N): LEFT_BOX,
+ *          length t; the new cell not in phase: ENDED, length t.
+ * An ENDED ray of length L with edges[b] <= L < edges[b + 1] counts in counts[b]; L < edges[0] is underflow, L >= edges[n_bins]
+ * overflow.  tallies = {ENDED rays (under- and overflow included), CAPPED, LEFT_BOX, underflow, overflow, n_phase}; moments =
+ * {sum L, sum L^2} over the ENDED rays.  Counts are integers and the two sums are order-fixed: two calls return the same bits.
+ * ray_start [n_rays][3], ray_dir [n_rays][3], ray_len [n_rays], ray_status [n_rays] (ASORA_BUBBLE_*): the per-ray record, for
+ * tests; all four NULL in production.  n_rays = 0 or n_phase = 0: no ray is marched, every output is zero except n_phase (n_phase
+ * is known on the device only, so the ray kernel of a call with n_rays > 0 is enqueued and returns at once when it reads 0).
+ * One synchronisation per call; the buffers are allocated by the first call and kept until the device is closed.  With
+ * ASORA_OPT_TIMING the stages count under ASORA_KERNEL_BUBBLE_MASK / _SCAN / _RAYS.  Fails with code 2 before device_init, 4 for a
+ * grid that holds no data, 3 for: a bad selector, a non-finite threshold, phase not 0 or 1, n_rays < 0, l_max not finite or not > 0,
+ * n_bins outside [1, ASORA_BUBBLE_MAX_BINS], edges not finite or not ascending, a null pointer among edges / counts / tallies /
+ * moments, some but not all of the four record pointers. */
+enum { ASORA_BUBBLE_ENDED = 0, ASORA_BUBBLE_CAPPED = 1, ASORA_BUBBLE_LEFT_BOX = 2 };
+enum { ASORA_BUBBLE_MAX_BINS = 256 };
+int asora_bubble_mfp(int which_grid, double threshold, int phase, int periodic, unsigned long long seed, long long n_rays, double l_max,
+                     int n_bins, const double *edges, unsigned long long *counts, unsigned long long *tallies, double *moments,
+                     int32_t *ray_start, double *ray_dir, double *ray_len, int32_t *ray_status);
+/* The products of the threshold pass alone, downloaded (tests): mask_words [N^2 W], row_counts [N^2]. */
+int asora_bubble_mask(int which_grid, double threshold, int phase, uint64_t *mask_words, uint32_t *row_counts);
+
 /* ------------------------------------------------------------------------------------------ */
 /* C. Options, measurement and diagnostics                                                     */
 /* ------------------------------------------------------------------------------------------ */
@@ -540,6 +574,9 @@ int asora_get_option(int option);
 /* Kernel selectors for asora_kernel_time_ms */
 enum { ASORA_KERNEL_RAYTRACE = 0, ASORA_KERNEL_CHEMISTRY = 1, ASORA_KERNEL_PREP = 2,
        ASORA_KERNEL_FINISH = 3, ASORA_KERNEL_COUNT = 4 };
+/* Selectors appended later: the stages of asora_bubble_mfp.  ASORA_KERNEL_COUNT stays the count of the first four; every selector
+ * below ASORA_KERNEL_SLOTS is valid. */
+enum { ASORA_KERNEL_BUBBLE_MASK = 4, ASORA_KERNEL_BUBBLE_SCAN = 5, ASORA_KERNEL_BUBBLE_RAYS = 6, ASORA_KERNEL_SLOTS = 7 };
 /* Sum of HIP-event durations (ms) and number of launches of a kernel since the last reset,
  * measured on the library's stream (ASORA_OPT_TIMING must be 1). */
 int asora_kernel_time_ms(int kernel, double *total_ms, long *launches);

@@ -11,6 +11,7 @@ from .raytracing import *      # noqa: F401,F403
 from .chemistry import *       # noqa: F401,F403
 from .utils import *           # noqa: F401,F403
 from .radiation import *       # noqa: F401,F403
+from .bubbles import *         # noqa: F401,F403  BubbleSizes, mfp_distribution
 from .c2ray_base import *      # noqa: F401,F403
 from .c2ray_test import *      # noqa: F401,F403
-from . import evolve, raytracing, chemistry, asora_core, utils, dist   # noqa: F401
+from . import evolve, raytracing, chemistry, asora_core, utils, dist, bubbles   # noqa: F401

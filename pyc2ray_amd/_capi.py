@@ -21,14 +21,18 @@ GRID_CLUMP = 8
  OPT_PLACEMENT_CANDIDATES, OPT_OPEN_BOUNDARIES) = range(19)
 MAX_SPECTRA = 16
 KERNEL_RAYTRACE, KERNEL_CHEMISTRY, KERNEL_PREP, KERNEL_FINISH = range(4)
+KERNEL_BUBBLE_MASK, KERNEL_BUBBLE_SCAN, KERNEL_BUBBLE_RAYS = 4, 5, 6
 VARIANT_PAIRED, VARIANT_ALIGNED, VARIANT_BUFFER_ATOMICS, VARIANT_SPLIT_DESCRIPTORS, VARIANT_SKIP_ZERO, VARIANT_GLOBAL_SHELLS = 1, 2, 4, 8, 16, 32
 VARIANT_OPEN_BOUNDARIES = 64
 (BUDGET_CELLS, BUDGET_N, BUDGET_X, BUDGET_NX, BUDGET_NX0, BUDGET_DNX, BUDGET_PHOTO, BUDGET_LLS, BUDGET_REC, BUDGET_COL,
  BUDGET_T, BUDGET_NT) = range(12)
 BUDGET_COUNT = 12
+BUBBLE_ENDED, BUBBLE_CAPPED, BUBBLE_LEFT_BOX = range(3)
+BUBBLE_MAX_BINS = 256
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
+_u64p = C.POINTER(C.c_uint64)
 
 #: every symbol include/asora_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -109,6 +113,9 @@ SIGNATURES = {
     "asora_plane_flux": (C.c_int, [C.c_int, _ip, _dp, _ip]),
     "asora_get_plane_flux": (C.c_int, [C.POINTER(C.c_int), _ip, _dp, _ip]),
     "asora_step_budget": (C.c_int, [C.c_double] * 5 + [C.c_int, C.c_int, C.c_int, _dp]),
+    "asora_bubble_mfp": (C.c_int, [C.c_int, C.c_double, C.c_int, C.c_int, C.c_ulonglong, C.c_longlong, C.c_double, C.c_int, _dp,
+                                   _u64p, _u64p, _dp, _ip, _dp, _dp, _ip]),
+    "asora_bubble_mask": (C.c_int, [C.c_int, C.c_double, C.c_int, _u64p, C.POINTER(C.c_uint32)]),
     "asora_set_option": (C.c_int, [C.c_int, C.c_int]),
     "asora_get_option": (C.c_int, [C.c_int]),
     "asora_kernel_time_ms": (C.c_int, [C.c_int, _dp, C.POINTER(C.c_long)]),

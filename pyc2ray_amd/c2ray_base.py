@@ -30,6 +30,10 @@ Differences from the reference:
   * ``Output: photon_budget: 0|1`` (optional key, default 0) and the attribute ``photon_budget`` (a bool, assignable between steps)
     close every time step with its photon statistics (pyc2ray_amd/budget.py; evolve3D's ``budget=``; use_gpu only): ``last_budget``,
     the cumulative ``total_budget``, and one line in the log.
+  * ``bubble_sizes()`` returns the mean-free-path size distribution of the ionised regions of the current state
+    (pyc2ray_amd/bubbles.py; on the device-resident path from the ionised fraction where it lies).  ``Output: bubble_sizes: 0|1``
+    (optional key, default 0; with ``bubble_rays``, ``bubble_threshold``, ``bubble_seed``) and the attribute ``bubble_stats`` (a bool,
+    assignable between steps) do that after every time step (use_gpu only): ``last_bubble_sizes`` and one line in the log.
 """
 import atexit
 import re
@@ -46,6 +50,7 @@ from .asora_core import cuda_is_init, device_close, device_init, photo_table_to_
 from . import _capi, _residency
 from .evolve import evolve3D, evolve3D_MPI, evolve3D_resident
 from .boundaries import periodic_spec
+from .bubbles import bubble_spec, mfp_distribution, distribution_on_device
 from .budget import StepBudget
 from .lls import LLSOpacity, LLSSchedule, lls_spec
 from .planeflux import PlaneFlux, plane_flux_spec
@@ -233,6 +238,7 @@ class C2Ray:
         self._boundaries_init()
         self._plane_flux_init()
         self._photon_budget_init()
+        self._bubble_init()
         if self.rank == 0:
             if self.gpu:
                 q_max = np.ceil(1.73205080757 * min(self.R_max_LLS, 1.73205080757 * self.N / 2))
@@ -425,6 +431,66 @@ class C2Ray:
         if self.rank == 0:
             self.printlog(budget.log_line())
 
+    def _bubble_init(self):
+        """The optional keys ``Output: bubble_sizes`` (0 | 1; absent: 0): whether every step ends with the size distribution of
+        its ionised regions, until ``bubble_stats`` is assigned; ``bubble_rays`` (an integer >= 0, default 100000),
+        ``bubble_threshold`` (a finite number, default 0.5) and ``bubble_seed`` (an integer in [0, 2^64), default 0): the ``n_rays``,
+        ``threshold`` and ``seed`` of those calls, and the defaults of :meth:`bubble_sizes`."""
+        out = self._ld.get('Output') or {}
+        v = out.get('bubble_sizes', 0)
+        if isinstance(v, (bool, np.bool_)):
+            v = int(v)
+        if not isinstance(v, (int, np.integer)) or v not in (0, 1):
+            raise ValueError(f"Output: bubble_sizes must be 0 or 1, not {v!r}")
+        kw = {name: out[key] for key, name in (("bubble_rays", "n_rays"), ("bubble_threshold", "threshold"), ("bubble_seed", "seed"))
+              if key in out}
+        bubble_spec("Output: bubble_rays / bubble_threshold / bubble_seed", self.N, **kw)     # ValueError for what a call would refuse, now
+        self.__dict__["_bubble_defaults"] = kw
+        self.last_bubble_sizes = None
+        self._set_bubble_stats(bool(v), "Output: bubble_sizes: 1")
+
+    def _set_bubble_stats(self, value, who):
+        if not isinstance(value, (bool, np.bool_)):
+            raise ValueError(f"{who}: bubble_stats must be a bool, not {type(value).__name__}")
+        if value and not self.gpu:
+            raise ValueError(f"{who}: bubble_stats needs use_gpu=True (the rays are marched on the device)")
+        self.__dict__["_bubble_stats"] = bool(value)
+
+    @property
+    def bubble_stats(self):
+        """Does every time step end with the size distribution of its ionised regions (:meth:`bubble_sizes` with the ``Output:
+        bubble_*`` keys; use_gpu=True only: on an object without, True is refused at the assignment)?  A driver may assign a bool
+        between steps.  After a step ``last_bubble_sizes`` holds the result and rank 0 writes one line to the log."""
+        return self.__dict__.get("_bubble_stats", False)
+
+    @bubble_stats.setter
+    def bubble_stats(self, value):
+        self._set_bubble_stats(value, "C2Ray.bubble_stats")
+
+    def bubble_sizes(self, **kw):
+        """The mean-free-path size distribution of the ionised regions of the current state, a
+        :class:`pyc2ray_amd.bubbles.BubbleSizes`; the keywords of :func:`pyc2ray_amd.bubbles.mfp_distribution` but ``field`` and
+        ``grid``, with ``periodic`` = ``self.periodic`` and ``dr`` = ``self.dr`` unless given, and the ``Output: bubble_*`` keys of
+        the parameter file for ``n_rays``, ``threshold`` and ``seed``.  While the ionised fraction of the last step lives on the
+        device only (``device_resident``), it is analysed there: nothing is downloaded, and ``xh`` stays where it is.  Otherwise --
+        with ``use_mpi`` too -- the host array is uploaded and analysed; every rank computes the same result from its own copy."""
+        for name in ("field", "grid"):
+            if name in kw:
+                raise ValueError(f"C2Ray.bubble_sizes: {name} is not for the class (it analyses its own ionised fraction)")
+        kw = {**self.__dict__.get("_bubble_defaults", {}), "periodic": self.periodic, "dr": self.dr, **kw}
+        if self.device_resident and self.gpu and not self.mpi and "xh" in self._device_newer and cuda_is_init():
+            spec = bubble_spec("C2Ray.bubble_sizes", self.N, **kw)
+            return distribution_on_device(load_asora(), _capi.GRID_XH, spec)
+        return mfp_distribution(self.xh, **kw)
+
+    def _close_bubbles(self):
+        """With ``bubble_stats``: the distribution of the step just run becomes last_bubble_sizes and joins the log."""
+        if not self.bubble_stats:
+            return
+        self.last_bubble_sizes = self.bubble_sizes()
+        if self.rank == 0:
+            self.printlog(self.last_bubble_sizes.log_line())
+
     def evolve3D(self, dt, src_flux, src_pos, src_spectrum=None):
         """Evolve the grid over one time step (c2ray_base.py:170-226).  src_spectrum: with ``BlackBodySource: Teff`` a list, the
         index into it of each source's temperature (None: every source the first one); see pyc2ray_amd.evolve3D."""
@@ -447,6 +513,7 @@ class C2Ray:
         if thermal is not None:
             self.temp = result[2]
         self._close_budget(budget.get("budget"))
+        self._close_bubbles()
 
     @classmethod
     def _fingerprint(cls, arr):
@@ -511,6 +578,7 @@ class C2Ray:
         self._host_newer -= {"ndens", "temp", "xh", "phi_ion", "clumping"}
         self._device_newer |= {"xh", "phi_ion"} if self.isothermal else {"xh", "phi_ion", "temp"}
         self._close_budget(budget.get("budget"))
+        self._close_bubbles()
 
     def cosmo_evolve(self, dt):
         """Advance time and redshift by dt, diluting density and rescaling the cell size when the run is

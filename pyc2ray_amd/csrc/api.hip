@@ -102,6 +102,8 @@ static int release_all()
     st.plane = PlaneFluxSet{};
     drop(st.budget_partial);
     if (st.budget_host) { (void)hipHostFree(st.budget_host); st.budget_host = nullptr; }
+    drop(st.bubble_mask); drop(st.bubble_rows); drop(st.bubble_scan); drop(st.bubble_partial); drop(st.bubble_result); drop(st.bubble_edges);
+    if (st.bubble_host) { (void)hipHostFree(st.bubble_host); st.bubble_host = nullptr; }
     for (int g = 0; g < ASORA_GRID_COUNT; ++g) { st.grid[g] = nullptr; st.grid_valid[g] = false; }
     st.nhi = st.staging = st.acc = nullptr;
     drop(st.arena); st.arena_bytes = 0;
@@ -362,7 +364,7 @@ int asora_get_option(int option)
 int asora_kernel_time_ms(int kernel, double *total_ms, long *launches)
 {
     clear_error();
-    if (kernel < 0 || kernel >= ASORA_KERNEL_COUNT) return fail(3, "kernel_time_ms: unknown kernel");
+    if (kernel < 0 || kernel >= ASORA_KERNEL_SLOTS) return fail(3, "kernel_time_ms: unknown kernel");
     if (int rc = flush_timers()) return rc;
     if (total_ms) *total_ms = g_state.k_ms[kernel];
     if (launches) *launches = g_state.k_n[kernel];
@@ -372,7 +374,7 @@ int asora_kernel_time_ms(int kernel, double *total_ms, long *launches)
 int asora_kernel_time_reset(void)
 {
     (void)flush_timers();
-    for (int k = 0; k < ASORA_KERNEL_COUNT; ++k) { g_state.k_ms[k] = 0.0; g_state.k_n[k] = 0; }
+    for (int k = 0; k < ASORA_KERNEL_SLOTS; ++k) { g_state.k_ms[k] = 0.0; g_state.k_n[k] = 0; }
     return 0;
 }
 

@@ -249,6 +249,12 @@ struct State {
     // [ASORA_BUDGET_COUNT][red_blocks] with the twelve results behind them, and where those arrive on the host (pinned)
     double *budget_partial = nullptr;
     double *budget_host = nullptr;
+    // the bubble-size distribution's own buffers (asora_bubble_mfp, bubble_mfp.hip), allocated by the first call for the mesh of
+    // device_init: the bit mask [N^2 W], the row counts [N^2], their exclusive scan [N^2 + 1], the ray workgroups' partial moments,
+    // the result words and the bin edges on the device; result words and edges on the host (pinned)
+    unsigned long long *bubble_mask = nullptr, *bubble_scan = nullptr, *bubble_result = nullptr, *bubble_host = nullptr;
+    unsigned *bubble_rows = nullptr;
+    double *bubble_partial = nullptr, *bubble_edges = nullptr;
 
     unsigned long long *counters = nullptr; // [COUNTER_FIELDS * COUNTER_SLOTS] device: gamma cells, evaluated cells, exact zeros left out, spread over the slots
     long long last_gamma_cells = 0, last_eval_cells = 0;
@@ -342,8 +348,8 @@ struct State {
     std::vector<PendingTimer> pending_timers;     // recorded, not yet resolved
     std::vector<hipEvent_t> free_events;
     int opt[ASORA_OPT_COUNT] = {0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0};
-    double k_ms[ASORA_KERNEL_COUNT] = {0, 0, 0, 0};
-    long k_n[ASORA_KERNEL_COUNT] = {0, 0, 0, 0};
+    double k_ms[ASORA_KERNEL_SLOTS] = {0, 0, 0, 0, 0, 0, 0};
+    long k_n[ASORA_KERNEL_SLOTS] = {0, 0, 0, 0, 0, 0, 0};
 };
 
 State &state();

@@ -450,6 +450,35 @@ class _LibAsora:
                     "step_budget")
         return sums
 
+    def bubble_mfp(self, which, threshold, phase, periodic, seed, n_rays, l_max, edges, record=False):
+        """The mean-free-path size distribution of the in-phase regions of device grid `which` (include/asora_hip.h,
+        asora_bubble_mfp): ``(counts, tallies, moments)`` -- uint64 counts of the ``len(edges) - 1`` bins, the uint64 tallies
+        (ended, capped, left_box, underflow, overflow, n_phase) and (sum L, sum L^2) over the ended rays, lengths in cells.
+        `record`: a fourth value, the per-ray record ``(start (n, 3) int32, direction (n, 3), length (n,), status (n,) int32)``."""
+        e = np.ascontiguousarray(edges, dtype=np.float64).ravel()
+        n = int(n_rays)
+        counts, tallies, moments = np.zeros(max(e.size - 1, 1), dtype=np.uint64), np.zeros(6, dtype=np.uint64), np.zeros(2)
+        rec = (np.zeros((max(n, 0), 3), dtype=np.int32), np.zeros((max(n, 0), 3)), np.zeros(max(n, 0)),
+               np.zeros(max(n, 0), dtype=np.int32)) if record else None
+        u64 = lambda a: a.ctypes.data_as(_capi._u64p)
+        _capi.check(self._lib.asora_bubble_mfp(int(which), float(threshold), int(phase), 1 if periodic else 0, int(seed), n, float(l_max),
+                                               int(e.size) - 1, _capi.dptr(e), u64(counts), u64(tallies), _capi.dptr(moments),
+                                               _capi.iptr(rec[0]) if record else None, _capi.dptr(rec[1]) if record else None,
+                                               _capi.dptr(rec[2]) if record else None, _capi.iptr(rec[3]) if record else None),
+                    "bubble_mfp")
+        return (counts, tallies, moments, rec) if record else (counts, tallies, moments)
+
+    def bubble_mask(self, which, threshold, phase):
+        """The products of the threshold pass of bubble_mfp alone: ``(words (N, N, W) uint64, row counts (N, N) uint32)``, bit
+        k & 63 of ``words[i, j, k >> 6]`` set where cell (i, j, k) is in phase."""
+        if self._N is None:
+            raise RuntimeError("bubble_mask needs a device initialised through device_init (the mesh size)")
+        N = self._N
+        words, rows = np.zeros((N, N, (N + 63) // 64), dtype=np.uint64), np.zeros((N, N), dtype=np.uint32)
+        _capi.check(self._lib.asora_bubble_mask(int(which), float(threshold), int(phase), words.ctypes.data_as(_capi._u64p),
+                                                rows.ctypes.data_as(C.POINTER(C.c_uint32))), "bubble_mask")
+        return words, rows
+
     def thermal_stats(self):
         """(cells that hit max_substeps, cells clamped to t_floor, most substeps of one integration) since the last
         chemistry_device / evolve_begin."""
