@@ -465,6 +465,40 @@ int asora_bubble_mfp(int which_grid, double threshold, int phase, int periodic, 
 /* The products of the threshold pass alone, downloaded (tests): mask_words [N^2 W], row_counts [N^2]. */
 int asora_bubble_mask(int which_grid, double threshold, int phase, uint64_t *mask_words, uint32_t *row_counts);
 
+/* The connected in-phase regions of device grid `which_grid` (the friends-of-friends view of the ionised bubbles; DESIGN.md section
+ * 4.2e): the distribution of their volumes and the numbers that describe percolation.  No grid is written.  The specification,
+ * which no implementation detail enters:
+ *   in phase  : as for asora_bubble_mfp -- phase 0: x >= threshold, phase 1: x < threshold; a NaN is in neither;
+ *   neighbours: connectivity 6: the cells across the faces; 26: across faces, edges and corners.  periodic != 0: the relation wraps
+ *               on every axis, else it stops at the faces of the box.  (For N = 1, 2 a cell is its own neighbour, or meets the same
+ *               neighbour twice, through the wrap: harmless);
+ *   region    : an equivalence class of in-phase cells under the transitive closure of the neighbour relation.  Its label is the
+ *               smallest C-order index (i N + j) N + k of its cells, a uint32 (N <= ASORA_REGION_MAX_N = 645, the mesh at which the
+ *               labelling's 8 bytes per cell reach 2 GiB: N^3 < 2^32); cells out of phase carry 0xFFFFFFFF.  Its volume V is its number of cells;
+ *   histogram : counts[b] = the number of regions with edges[b] <= (double)V < edges[b + 1], cells[b] = the sum of V over them, for
+ *               the n_bins bins (1 ... ASORA_BUBBLE_MAX_BINS) of the ascending, finite edges[n_bins + 1]; regions with V < edges[0] or
+ *               V >= edges[n_bins] are in no bin and counted, in regions and in cells, as underflow and overflow;
+ *   tallies   : uint64 [ASORA_REGION_TALLIES], indexed by the enum below: n_phase (cells in phase), n_regions, sum_v2 = sum V^2
+ *               (< 2^63 at 645^3), v_largest and label_largest, extent_i / _j / _k (how many of the N planes along the axis hold a cell
+ *               of the largest region), v_second and label_second, underflow and overflow in regions and in cells;
+ *   largest   : the greatest V, ties to the smaller label; second: the same rule among the other regions, 0 and 0xFFFFFFFF when
+ *               there is none.  No cell in phase: every output is 0, the two labels 0xFFFFFFFF.
+ * Every output is an integer formed by order-independent operations: two calls return the same bits.
+ * labels [N^3] or NULL: the label of every cell, downloaded (tests, visualisation); NULL in production, where some hundred integers
+ * cross to the host.  One synchronisation per call.  The labelling keeps 8 bytes per cell on the device (a uint32 label and a uint32
+ * volume: 128 MiB at 256^3, 2.0 GiB at N = 645), allocated by the first call and kept until the device is closed.  With
+ * ASORA_OPT_TIMING the threshold pass counts under ASORA_KERNEL_BUBBLE_MASK (it is that launch); the other stages are not timed.
+ * Fails with code 2 before device_init, 4 for a grid that holds no data or a mesh with N > ASORA_REGION_MAX_N, 3 for: a bad selector,
+ * a non-finite threshold, phase not 0 or 1, connectivity not 6 or 26, n_bins outside [1, ASORA_BUBBLE_MAX_BINS], edges not finite or
+ * not ascending, a null pointer among edges / counts / cells / tallies.  A refused call writes nothing. */
+enum { ASORA_REGION_MAX_N = 645 };
+enum { ASORA_REGION_N_PHASE = 0, ASORA_REGION_N_REGIONS = 1, ASORA_REGION_SUM_V2 = 2, ASORA_REGION_V_LARGEST = 3,
+       ASORA_REGION_LABEL_LARGEST = 4, ASORA_REGION_EXTENT_I = 5, ASORA_REGION_EXTENT_J = 6, ASORA_REGION_EXTENT_K = 7,
+       ASORA_REGION_V_SECOND = 8, ASORA_REGION_LABEL_SECOND = 9, ASORA_REGION_UNDERFLOW = 10, ASORA_REGION_UNDERFLOW_CELLS = 11,
+       ASORA_REGION_OVERFLOW = 12, ASORA_REGION_OVERFLOW_CELLS = 13, ASORA_REGION_TALLIES = 14 };
+int asora_region_sizes(int which_grid, double threshold, int phase, int periodic, int connectivity, int n_bins, const double *edges,
+                       unsigned long long *counts, unsigned long long *cells, unsigned long long *tallies, uint32_t *labels);
+
 /* ------------------------------------------------------------------------------------------ */
 /* C. Options, measurement and diagnostics                                                     */
 /* ------------------------------------------------------------------------------------------ */

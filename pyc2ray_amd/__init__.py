@@ -12,6 +12,7 @@ from .chemistry import *       # noqa: F401,F403
 from .utils import *           # noqa: F401,F403
 from .radiation import *       # noqa: F401,F403
 from .bubbles import *         # noqa: F401,F403  BubbleSizes, mfp_distribution
+from .regions import *         # noqa: F401,F403  RegionSizes, region_sizes
 from .c2ray_base import *      # noqa: F401,F403
 from .c2ray_test import *      # noqa: F401,F403
-from . import evolve, raytracing, chemistry, asora_core, utils, dist, bubbles   # noqa: F401
+from . import evolve, raytracing, chemistry, asora_core, utils, dist, bubbles, regions   # noqa: F401

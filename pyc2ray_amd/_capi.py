@@ -29,6 +29,12 @@ VARIANT_OPEN_BOUNDARIES = 64
 BUDGET_COUNT = 12
 BUBBLE_ENDED, BUBBLE_CAPPED, BUBBLE_LEFT_BOX = range(3)
 BUBBLE_MAX_BINS = 256
+(REGION_N_PHASE, REGION_N_REGIONS, REGION_SUM_V2, REGION_V_LARGEST, REGION_LABEL_LARGEST, REGION_EXTENT_I, REGION_EXTENT_J,
+ REGION_EXTENT_K, REGION_V_SECOND, REGION_LABEL_SECOND, REGION_UNDERFLOW, REGION_UNDERFLOW_CELLS, REGION_OVERFLOW,
+ REGION_OVERFLOW_CELLS) = range(14)
+REGION_TALLIES = 14
+REGION_MAX_N = 645
+REGION_NO_LABEL = 0xFFFFFFFF
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -116,6 +122,8 @@ SIGNATURES = {
     "asora_bubble_mfp": (C.c_int, [C.c_int, C.c_double, C.c_int, C.c_int, C.c_ulonglong, C.c_longlong, C.c_double, C.c_int, _dp,
                                    _u64p, _u64p, _dp, _ip, _dp, _dp, _ip]),
     "asora_bubble_mask": (C.c_int, [C.c_int, C.c_double, C.c_int, _u64p, C.POINTER(C.c_uint32)]),
+    "asora_region_sizes": (C.c_int, [C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _u64p, _u64p, _u64p,
+                                     C.POINTER(C.c_uint32)]),
     "asora_set_option": (C.c_int, [C.c_int, C.c_int]),
     "asora_get_option": (C.c_int, [C.c_int]),
     "asora_kernel_time_ms": (C.c_int, [C.c_int, _dp, C.POINTER(C.c_long)]),

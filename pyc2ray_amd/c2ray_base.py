@@ -34,6 +34,10 @@ Differences from the reference:
     (pyc2ray_amd/bubbles.py; on the device-resident path from the ionised fraction where it lies).  ``Output: bubble_sizes: 0|1``
     (optional key, default 0; with ``bubble_rays``, ``bubble_threshold``, ``bubble_seed``) and the attribute ``bubble_stats`` (a bool,
     assignable between steps) do that after every time step (use_gpu only): ``last_bubble_sizes`` and one line in the log.
+  * ``regions()`` returns the connected ionised regions of the current state, their volumes and whether the largest spans the box
+    (pyc2ray_amd/regions.py; on the device-resident path from the ionised fraction where it lies).  ``Output: region_sizes: 0|1``
+    (optional key, default 0; with ``region_threshold``, ``region_connectivity``) and the attribute ``region_stats`` (a bool,
+    assignable between steps) do that after every time step (use_gpu only): ``last_regions`` and one line in the log.
 """
 import atexit
 import re
@@ -51,6 +55,7 @@ from . import _capi, _residency
 from .evolve import evolve3D, evolve3D_MPI, evolve3D_resident
 from .boundaries import periodic_spec
 from .bubbles import bubble_spec, mfp_distribution, distribution_on_device
+from .regions import region_spec, region_sizes, regions_on_device
 from .budget import StepBudget
 from .lls import LLSOpacity, LLSSchedule, lls_spec
 from .planeflux import PlaneFlux, plane_flux_spec
@@ -239,6 +244,7 @@ class C2Ray:
         self._plane_flux_init()
         self._photon_budget_init()
         self._bubble_init()
+        self._region_init()
         if self.rank == 0:
             if self.gpu:
                 q_max = np.ceil(1.73205080757 * min(self.R_max_LLS, 1.73205080757 * self.N / 2))
@@ -491,6 +497,66 @@ class C2Ray:
         if self.rank == 0:
             self.printlog(self.last_bubble_sizes.log_line())
 
+    def _region_init(self):
+        """The optional keys ``Output: region_sizes`` (0 | 1; absent: 0): whether every step ends with the connected regions of its
+        ionised fraction, until ``region_stats`` is assigned; ``region_threshold`` (a finite number, default 0.5) and
+        ``region_connectivity`` (6 or 26, default 6): the ``threshold`` and ``connectivity`` of those calls, and the defaults of
+        :meth:`regions`."""
+        out = self._ld.get('Output') or {}
+        v = out.get('region_sizes', 0)
+        if isinstance(v, (bool, np.bool_)):
+            v = int(v)
+        if not isinstance(v, (int, np.integer)) or v not in (0, 1):
+            raise ValueError(f"Output: region_sizes must be 0 or 1, not {v!r}")
+        kw = {name: out[key] for key, name in (("region_threshold", "threshold"), ("region_connectivity", "connectivity")) if key in out}
+        region_spec("Output: region_threshold / region_connectivity", None, **kw)     # ValueError for what a call would refuse, now
+                                                                                       # (the keys only: a mesh beyond the entry's limit is refused by a call)
+        self.__dict__["_region_defaults"] = kw
+        self.last_regions = None
+        self._set_region_stats(bool(v), "Output: region_sizes: 1")
+
+    def _set_region_stats(self, value, who):
+        if not isinstance(value, (bool, np.bool_)):
+            raise ValueError(f"{who}: region_stats must be a bool, not {type(value).__name__}")
+        if value and not self.gpu:
+            raise ValueError(f"{who}: region_stats needs use_gpu=True (the regions are labelled on the device)")
+        self.__dict__["_region_stats"] = bool(value)
+
+    @property
+    def region_stats(self):
+        """Does every time step end with the connected regions of its ionised fraction (:meth:`regions` with the ``Output:
+        region_*`` keys; use_gpu=True only: on an object without, True is refused at the assignment)?  A driver may assign a bool
+        between steps.  After a step ``last_regions`` holds the result and rank 0 writes one line to the log."""
+        return self.__dict__.get("_region_stats", False)
+
+    @region_stats.setter
+    def region_stats(self, value):
+        self._set_region_stats(value, "C2Ray.region_stats")
+
+    def regions(self, **kw):
+        """The connected ionised regions of the current state, a :class:`pyc2ray_amd.regions.RegionSizes`; the keywords of
+        :func:`pyc2ray_amd.regions.region_sizes` but ``field`` and ``grid``, with ``periodic`` = ``self.periodic`` and ``dr`` =
+        ``self.dr`` unless given, and the ``Output: region_*`` keys of the parameter file for ``threshold`` and ``connectivity``.
+        While the ionised fraction of the last step lives on the device only (``device_resident``), it is analysed there: nothing
+        is downloaded, and ``xh`` stays where it is.  Otherwise -- with ``use_mpi`` too -- the host array is uploaded and analysed;
+        every rank computes the same result from its own copy."""
+        for name in ("field", "grid"):
+            if name in kw:
+                raise ValueError(f"C2Ray.regions: {name} is not for the class (it analyses its own ionised fraction)")
+        kw = {**self.__dict__.get("_region_defaults", {}), "periodic": self.periodic, "dr": self.dr, **kw}
+        if self.device_resident and self.gpu and not self.mpi and "xh" in self._device_newer and cuda_is_init():
+            spec = region_spec("C2Ray.regions", self.N, **kw)
+            return regions_on_device(load_asora(), _capi.GRID_XH, spec)
+        return region_sizes(self.xh, **kw)
+
+    def _close_regions(self):
+        """With ``region_stats``: the regions of the step just run become last_regions and join the log."""
+        if not self.region_stats:
+            return
+        self.last_regions = self.regions()
+        if self.rank == 0:
+            self.printlog(self.last_regions.log_line())
+
     def evolve3D(self, dt, src_flux, src_pos, src_spectrum=None):
         """Evolve the grid over one time step (c2ray_base.py:170-226).  src_spectrum: with ``BlackBodySource: Teff`` a list, the
         index into it of each source's temperature (None: every source the first one); see pyc2ray_amd.evolve3D."""
@@ -514,6 +580,7 @@ class C2Ray:
             self.temp = result[2]
         self._close_budget(budget.get("budget"))
         self._close_bubbles()
+        self._close_regions()
 
     @classmethod
     def _fingerprint(cls, arr):
@@ -579,6 +646,7 @@ class C2Ray:
         self._device_newer |= {"xh", "phi_ion"} if self.isothermal else {"xh", "phi_ion", "temp"}
         self._close_budget(budget.get("budget"))
         self._close_bubbles()
+        self._close_regions()
 
     def cosmo_evolve(self, dt):
         """Advance time and redshift by dt, diluting density and rescaling the cell size when the run is

@@ -255,6 +255,11 @@ struct State {
     unsigned long long *bubble_mask = nullptr, *bubble_scan = nullptr, *bubble_result = nullptr, *bubble_host = nullptr;
     unsigned *bubble_rows = nullptr;
     double *bubble_partial = nullptr, *bubble_edges = nullptr;
+    // the connected regions' own buffers (asora_region_sizes, region_label.hip), allocated by the first call: one uint32 label and
+    // one uint32 volume per cell, the result words, the 3 N plane flags of the largest region; mask, edges and the pinned area are
+    // the bubble buffers above
+    unsigned *region_label = nullptr, *region_volume = nullptr, *region_flags = nullptr;
+    unsigned long long *region_result = nullptr;
 
     unsigned long long *counters = nullptr; // [COUNTER_FIELDS * COUNTER_SLOTS] device: gamma cells, evaluated cells, exact zeros left out, spread over the slots
     long long last_gamma_cells = 0, last_eval_cells = 0;
@@ -578,5 +583,11 @@ void sort_sources_by_position(const int32_t *pos, int NumSrc, std::vector<int> &
 int ensure_red_capacity(size_t entries);
 int ensure_temp_probe(double bh00, double albpow, double colh0, double temph0);
 ChemTileParams chem_tile_common(int i_begin, int i_count, const double chem[6]);
+// bubble_mfp.hip: what asora_region_sizes (region_label.hip) shares with asora_bubble_mfp -- the argument checks of a thresholded
+// grid (codes 3 and 4), the feature's buffers, the threshold pass (and, with `scan`, the scan of the row counts)
+constexpr int BUBBLE_HOST_WORDS = 1024;         // uint64 words of State::bubble_host (pinned): a call's result words, its edges behind them
+int check_bubble_grid(const char *who, int which, double threshold, int phase);
+int ensure_bubble_buffers(State &st);
+int launch_bubble_mask(State &st, int which, double threshold, int phase, bool scan);
 
 } // namespace asora

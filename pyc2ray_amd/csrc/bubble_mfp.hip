@@ -26,6 +26,7 @@ constexpr int BM_UNDER = ASORA_BUBBLE_MAX_BINS, BM_OVER = BM_UNDER + 1, BM_ENDED
               BM_LEFT = BM_UNDER + 4;
 constexpr int BM_RESULT = BM_SLOTS + 3;                  // ... then n_phase and the bits of sum L, sum L^2: what crosses PCIe
 constexpr int BM_BLOCKS_PER_CU = 8;
+static_assert(BM_RESULT + ASORA_BUBBLE_MAX_BINS + 1 <= BUBBLE_HOST_WORDS, "the pinned area holds the result words and the edges");
 
 // ---- a. threshold ------------------------------------------------------------------------------------------------------------
 // One wave per row (i, j), one __ballot per word of it: lane l of the ballot of word w holds cell k = 64 w + l; lanes beyond N vote
@@ -265,7 +266,7 @@ __global__ void __launch_bounds__(BM_THREADS) bubble_final_kernel(const double *
 // the row counts, their scan, the workgroups' partials, the result words and the edges on the device; the last two pinned on the host.
 static int bubble_ray_blocks(const State &st) { return st.cu_count * BM_BLOCKS_PER_CU; }
 
-static int ensure_bubble_buffers(State &st)
+int ensure_bubble_buffers(State &st)
 {
     if (st.bubble_mask && st.bubble_rows && st.bubble_scan && st.bubble_partial && st.bubble_result && st.bubble_edges && st.bubble_host)
         return 0;
@@ -277,12 +278,12 @@ static int ensure_bubble_buffers(State &st)
     if (!st.bubble_result) ASORA_HIP_TRY(hipMalloc(&st.bubble_result, sizeof(unsigned long long) * BM_RESULT));
     if (!st.bubble_edges) ASORA_HIP_TRY(hipMalloc(&st.bubble_edges, sizeof(double) * (ASORA_BUBBLE_MAX_BINS + 1)));
     if (!st.bubble_host)
-        ASORA_HIP_TRY(hipHostMalloc(&st.bubble_host, sizeof(unsigned long long) * (BM_RESULT + ASORA_BUBBLE_MAX_BINS + 1), hipHostMallocDefault));
+        ASORA_HIP_TRY(hipHostMalloc(&st.bubble_host, sizeof(unsigned long long) * BUBBLE_HOST_WORDS, hipHostMallocDefault));
     return 0;
 }
 
 // stages a and b
-static int launch_bubble_mask(State &st, int which, double threshold, int phase, bool scan)
+int launch_bubble_mask(State &st, int which, double threshold, int phase, bool scan)
 {
     const size_t nrows = (size_t)st.N * st.N;
     const int W = (st.N + 63) / 64;
@@ -302,7 +303,7 @@ static int launch_bubble_mask(State &st, int which, double threshold, int phase,
     return 0;
 }
 
-static int check_bubble_grid(const char *who, int which, double threshold, int phase)
+int check_bubble_grid(const char *who, int which, double threshold, int phase)
 {
     const State &st = state();
     if (which < 0 || which >= ASORA_GRID_COUNT) return fail(3, std::string(who) + ": bad grid selector");

@@ -479,6 +479,25 @@ class _LibAsora:
                                                 rows.ctypes.data_as(C.POINTER(C.c_uint32))), "bubble_mask")
         return words, rows
 
+    def region_sizes(self, which, threshold, phase, periodic, connectivity, edges, labels=False):
+        """The connected in-phase regions of device grid `which` (include/asora_hip.h, asora_region_sizes): ``(counts, cells,
+        tallies)`` -- per bin of ``edges`` (volumes in cells) the uint64 number of regions and the cells they hold, and the uint64
+        tallies indexed by ``_capi.REGION_*``.  `labels`: a fourth value, the label of every cell, (N, N, N) uint32."""
+        e = np.ascontiguousarray(edges, dtype=np.float64).ravel()
+        nb = max(e.size - 1, 1)
+        counts, cells = np.zeros(nb, dtype=np.uint64), np.zeros(nb, dtype=np.uint64)
+        tallies = np.zeros(_capi.REGION_TALLIES, dtype=np.uint64)
+        grid = None
+        if labels:
+            if self._N is None:
+                raise RuntimeError("region_sizes with labels needs a device initialised through device_init (the mesh size)")
+            grid = np.zeros((self._N,) * 3, dtype=np.uint32)
+        u64 = lambda a: a.ctypes.data_as(_capi._u64p)
+        _capi.check(self._lib.asora_region_sizes(int(which), float(threshold), int(phase), 1 if periodic else 0, int(connectivity),
+                                                 int(e.size) - 1, _capi.dptr(e), u64(counts), u64(cells), u64(tallies),
+                                                 grid.ctypes.data_as(C.POINTER(C.c_uint32)) if labels else None), "region_sizes")
+        return (counts, cells, tallies, grid) if labels else (counts, cells, tallies)
+
     def thermal_stats(self):
         """(cells that hit max_substeps, cells clamped to t_floor, most substeps of one integration) since the last
         chemistry_device / evolve_begin."""
