@@ -122,6 +122,38 @@ def partition(labels):
     return first[inverse.ravel()].reshape(np.shape(labels))
 
 
+def crowded(N, seed):
+    """The checkerboard (i + j + k even) plus a seeded random half of the odd cells with i % 4 == 1, j % 4 == 0, k % 4 == 0.  Under 6
+    neighbours every even cell is a region of its own, except where a filled odd cell joins its six neighbours (five or four
+    where j = 0 or k = 0 lies on an open face) into one region of 7 (6, 5): nearly as many regions as a mask can hold, of unequal
+    volumes, and the runs of a region of 7 lie in five rows of three planes.  Under 26 neighbours it is one region.  Boolean
+    (N, N, N); N a multiple of 4, so that the pattern is the same through the wrap."""
+    if N % 4:
+        raise ValueError("N is a multiple of 4")
+    i, j, k = np.indices((N, N, N))
+    sites = (i % 4 == 1) & (j % 4 == 0) & (k % 4 == 0)
+    filled = np.zeros((N, N, N), dtype=bool)
+    filled[sites] = np.random.default_rng(seed).random(int(sites.sum())) < 0.5
+    return ((i + j + k) % 2 == 0) | filled
+
+
+def run_firsts(mask):
+    """True at the first cell of every run of in-phase cells along k inside its row (no wrap)."""
+    first = mask.copy()
+    first[:, :, 1:] &= ~mask[:, :, :-1]
+    return first
+
+
+def roots_per_workgroup(labels, mask, threads, blocks):
+    """(blocks,) int64: how many distinct roots the run-first cells of workgroup (c // threads) % blocks carry, c the C-order
+    index -- what a grid-stride launch of `blocks` workgroups of `threads` threads, one thread per cell, puts into one workgroup's
+    table of roots."""
+    cells = np.flatnonzero(run_firsts(np.asarray(mask, dtype=bool)))
+    group = (cells // threads) % blocks
+    pairs = np.unique((group.astype(np.int64) << 32) | labels.ravel()[cells].astype(np.int64))
+    return np.bincount(pairs >> 32, minlength=blocks)
+
+
 def serpentine(N):
     """A one-cell-wide path through every second row (i, j even) of the box, rows joined by single cells at alternating ends and
     planes by a single cell: one region under 6 neighbours, open or periodic for odd N, whose union-find chain is the longest a

@@ -6,8 +6,17 @@ import pytest
 
 import bubble_reference as BR
 
-GPU_FIELDS = [(17, 3), (64, 5), (70, 9)]          # (N, seed) of the fields tests/test_gpu_bubbles.py uses
+# (N, seed) of the fields tests/test_gpu_bubbles.py and tests/test_gpu_regions.py use.  The seed of N = 136 is the first of 20 000 at
+# which the field has runs along k through all three words of a row (tests/test_regions_reference.py) AND the largest region at
+# threshold 0.69 holds 0.3 ... 0.41 of the phase with open boundaries too, as test_gpu_regions.py asserts of every mesh (at this mesh
+# the open fraction is 0.21 ... 0.28 for most seeds).
+GPU_FIELDS = [(17, 3), (64, 5), (70, 9), (136, 2755)]
 L_MAX = lambda N: (3.0, 4.0 * N)                  # ... and its two l_max: one that caps many rays, one beyond every ray
+# Its many-ray test, on the first field's ionised phase: two full trips of a ray launch of 256 CUs (8 workgroups of 256 threads
+# each: 524 288 threads), 4096 more and an odd tail; the ray seed; (periodic, l_max) of its runs.
+MANY_RAYS = 2 * 524_288 + 4096 + 37
+MANY_RAYS_SEED = 7
+MANY_RAY_CASES = [(True, 3.0), (False, 3.0), (False, 4.0 * GPU_FIELDS[0][0])]
 
 
 def _mix_int(seed, c):
@@ -89,6 +98,22 @@ def _shift(d, ulps):
     return out
 
 
+def _unmoved_by_four_ulp(mask, start, d, l_max, periodic, name):
+    """Asserts that three patterns of 4-ulp shifts of every direction component leave the statuses and the bins (32 geometric ones
+    up to l_max, as the GPU tests have them) of the rays as they are; the largest relative change of a length."""
+    edges = np.geomspace(0.5, l_max, 33)
+    L0, s0 = BR.march(mask, start, d, l_max, periodic)
+    b0 = np.searchsorted(edges, L0, "right")
+    rng = np.random.default_rng(1)
+    worst = 0.0
+    for ulps in (np.ones_like(d), -np.ones_like(d), rng.choice([-1.0, 1.0], size=d.shape)):
+        L1, s1 = BR.march(mask, start, _shift(d, ulps), l_max, periodic)
+        assert np.array_equal(s0, s1), name
+        assert np.array_equal(b0, np.searchsorted(edges, L1, "right")), name
+        worst = max(worst, float(np.max(np.abs(L1 - L0) / L0)))
+    return worst
+
+
 def _fields():
     rng = np.random.default_rng(24)
     plain = rng.random((24, 24, 24))
@@ -114,17 +139,22 @@ def test_four_ulp_of_the_directions_change_no_status_and_no_bin(periodic):
         for seed in (0, 7):
             start, d = BR.rays(mask, seed, n)
             for l_max in L_MAX(N):
-                edges = np.geomspace(0.5, l_max, 33)
-                L0, s0 = BR.march(mask, start, d, l_max, periodic)
-                b0 = np.searchsorted(edges, L0, "right")
-                rng = np.random.default_rng(1)
-                for ulps in (np.ones_like(d), -np.ones_like(d), rng.choice([-1.0, 1.0], size=d.shape)):
-                    L1, s1 = BR.march(mask, start, _shift(d, ulps), l_max, periodic)
-                    assert np.array_equal(s0, s1), name
-                    assert np.array_equal(b0, np.searchsorted(edges, L1, "right")), name
-                    worst = max(worst, float(np.max(np.abs(L1 - L0) / L0)))
+                worst = max(worst, _unmoved_by_four_ulp(mask, start, d, l_max, periodic, name))
     print(f"largest relative change of a length: {worst:.3e}")
     # 4 ulp of d are at most 8.9e-16 of it, and 1 / |d| and the product round once each, in both marches
+    assert worst <= 4 * 2.0 ** -52 + 4 * 2.0 ** -53
+
+
+@pytest.mark.parametrize("periodic,l_max", MANY_RAY_CASES, ids=lambda v: str(v))
+def test_four_ulp_change_no_status_and_no_bin_of_the_many_rays(periodic, l_max):
+    """The same for exactly the ray set of test_gpu_bubbles.py's many-ray test -- MANY_RAYS rays of seed MANY_RAYS_SEED in the ionised
+    phase of the smallest field, at the boundaries and l_max that test runs --, which is what lets it compare the counts of a
+    million rays with the all-CPU reference without slack."""
+    N, seed = GPU_FIELDS[0]
+    mask = BR.in_phase(BR.blob_field(N, seed), 0.5, 0)
+    start, d = BR.rays(mask, MANY_RAYS_SEED, MANY_RAYS)
+    worst = _unmoved_by_four_ulp(mask, start, d, l_max, periodic, f"{MANY_RAYS} rays")
+    print(f"periodic {periodic}, l_max {l_max}: largest relative change of a length {worst:.3e}")
     assert worst <= 4 * 2.0 ** -52 + 4 * 2.0 ** -53
 
 

@@ -1,9 +1,12 @@
 """GPU: the mean-free-path bubble sizes (asora_bubble_mfp, asora_bubble_mask, mfp_distribution, C2Ray.bubble_sizes; DESIGN.md
 section 4.2d) against their numpy statement, tests/bubble_reference.py.
 
-* Meshes: N = 17 (odd, one word per row, fewer cells than a launch has threads), 64 (rows of exactly one full word) and 70 (two
-  words per row, the second with a 6-bit tail).  The field is uniform-random with a smooth blob laid over it
-  (bubble_reference.blob_field): short rays in the noise, long ones in the blob.
+* Meshes: N = 17 (odd, one word per row, fewer cells than a launch has threads), 64 (rows of exactly one full word), 70 (two
+  words per row, the second with a 6-bit tail) and 136 (three words per row, the third with an 8-bit tail: the popcount walk to a
+  start cell passes two words, lane 2 keeps a mask word; 18 496 row counts are five tiles of the scan).  The field is
+  uniform-random with a smooth blob laid over it (bubble_reference.blob_field): short rays in the noise, long ones in the blob.
+* 4096 rays per call, which is one trip of the ray kernel's grid-stride loop and 16 partial sums; test_many_rays shoots 1 052 709 at
+  N = 17: two and three trips per thread, 2048 partials on 256 CUs.
 * The mask and the row counts are compared bit for bit; so are the start cells of the rays, and the lengths and statuses of the
   reference march fed the DEVICE's directions (one correctly rounded division and one multiplication per crossing: nothing may
   differ).  The directions themselves agree with numpy's to 4 ulp per component (sqrt, cos, sin and one product).
@@ -17,7 +20,7 @@ import numpy as np
 import pytest
 
 import bubble_reference as BR
-from test_bubble_reference import GPU_FIELDS, L_MAX
+from test_bubble_reference import GPU_FIELDS, L_MAX, MANY_RAY_CASES, MANY_RAYS, MANY_RAYS_SEED
 
 pytestmark = pytest.mark.gpu
 
@@ -229,6 +232,55 @@ def test_module_entry_and_kernel_timers(asora, box):
     assert np.array_equal(same.counts, b.counts) and same.sum_length == b.sum_length and same.dr is None
     neutral = mfp_distribution(None, grid=capi.GRID_XH, phase="neutral", n_rays=500, periodic=False)
     assert neutral.n_phase == N ** 3 - b.n_phase and neutral.l_max == N and neutral.edges.size == 65
+
+
+def test_many_rays(asora):
+    """MANY_RAYS = 1 052 709 rays of the N = 17 field's ionised phase: more than twice the threads of the launch (asserted from the
+    device's CU count), so every thread of bubble_rays_kernel carries its two sums and its workgroup's histogram over two rays and
+    some over three; and more than 256 workgroups, so bubble_final_kernel's strided loop over the partials takes further turns.
+    The structure of test_rays_and_the_production_call; tests/test_bubble_reference.py shows for exactly these rays that 4 ulp of
+    the directions move no status and no bin.  Moments: a sum of n positive terms in another order differs by (n - 1) 2^-53 of it
+    at most, 1.17e-10."""
+    import torch
+    p, lib, capi = asora
+    N, seed = GPU_FIELDS[0]
+    n = MANY_RAYS
+    blocks = torch.cuda.get_device_properties(0).multi_processor_count * 8       # bubble_mfp.hip: BM_BLOCKS_PER_CU workgroups of 256
+    assert n > 2 * blocks * 256 and (n + 255) // 256 >= blocks > 256, (n, blocks)
+    field = BR.blob_field(N, seed)
+    if p.cuda_is_init():
+        p.device_close()
+    p.device_init(N, 8)
+    lib.grid_to_device(capi.GRID_XH, field)
+    mask = BR.in_phase(field, 0.5, 0)
+    start, d = BR.rays(mask, MANY_RAYS_SEED, n)
+    bound = (n - 1) * 2.0 ** -53
+    for periodic, l_max in MANY_RAY_CASES:
+        edges = np.geomspace(0.5, l_max, 33)
+        counts, tallies, moments, rec = lib.bubble_mfp(capi.GRID_XH, 0.5, 0, periodic, MANY_RAYS_SEED, n, l_max, edges, record=True)
+        r_start, r_dir, r_len, r_status = rec
+        # ---- the per-ray record
+        assert r_start.shape == (n, 3) and np.array_equal(r_start, start)
+        worst = float(_ulps(r_dir, d).max())
+        print(f"{n} rays, periodic {periodic}, l_max {l_max}: directions within {worst:.2f} ulp")
+        assert worst <= 4.0
+        L, status = BR.march(mask, start, r_dir, l_max, periodic)
+        assert np.array_equal(r_status, status)
+        assert np.array_equal(r_len, L)                      # bit for bit
+        # ---- the binning of the record, and the production call without it
+        b_counts, b_tallies, b_moments = BR.bin_lengths(edges, r_len, r_status)
+        assert np.array_equal(counts, b_counts) and np.array_equal(tallies[:5], b_tallies) and tallies[5] == mask.sum()
+        assert int(tallies[0] + tallies[1] + tallies[2]) == n and tallies[0] > 0
+        p_counts, p_tallies, p_moments = lib.bubble_mfp(capi.GRID_XH, 0.5, 0, periodic, MANY_RAYS_SEED, n, l_max, edges)
+        assert np.array_equal(p_counts, counts) and np.array_equal(p_tallies, tallies)
+        assert p_moments.tobytes() == moments.tobytes()      # two calls, the same bits
+        # ---- the all-CPU reference, numpy's own directions (BR.distribution, its rays computed once for the three runs)
+        c_counts, c_tallies, c_moments = BR.bin_lengths(edges, *BR.march(mask, start, d, l_max, periodic))
+        assert np.array_equal(p_counts, c_counts) and np.array_equal(p_tallies[:5], c_tallies)
+        rel = np.abs(p_moments - c_moments) / np.abs(c_moments)
+        rel_record = np.abs(p_moments - b_moments) / np.abs(b_moments)
+        print(f"    moments within {rel.max():.2e} of the reference's and {rel_record.max():.2e} of the record's (relative); bound {bound:.2e}")
+        assert np.all(rel <= bound) and np.all(rel_record <= bound)
 
 
 def test_class(asora, tmp_path):

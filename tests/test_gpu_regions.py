@@ -2,8 +2,12 @@
 statement, tests/regions_reference.py.  Everything is integers: every comparison is for equality.
 
 * Meshes: those of the mean-free-path tests with their seeds -- N = 17 (odd, one word per row, fewer cells than a workgroup has
-  threads), 64 (rows of exactly one full word: a run ends on the word boundary, next to the wrap) and 70 (two words per row, the second
-  with a 6-bit tail: runs straddle the word boundary).
+  threads), 64 (rows of exactly one full word: a run ends on the word boundary, next to the wrap), 70 (two words per row, the second
+  with a 6-bit tail: runs straddle the word boundary) and 136 (three words per row, the third with an 8-bit tail, and runs that begin
+  in the first and end in the third: both word walks take two steps; 4.8 trips of every grid-stride loop on 256 CUs).
+* N = 216, regions_reference.crowded: 4.6 million regions of 1, 5, 6 and 7 cells under 6 neighbours, one under 26; 19 trips, and
+  every workgroup meets more roots than its LDS table holds, so run lengths go straight to global memory (asserted from the device's
+  CU count); the threshold pass takes a second trip.
 * Fields: bubble_reference.blob_field at (threshold, phase, connectivity) = (0.5, both, 6) -- one dominant region and thousands of
   specks --, (0.69, ionised, 6) near the site-percolation threshold of 6 neighbours, (0.9, ionised, 26) the same for 26; each
   periodic and open, which differ in every one of them (asserted), so a missing or a spurious wrap cannot pass.
@@ -17,7 +21,7 @@ import pytest
 import bubble_reference as BR
 import regions_reference as RR
 from test_bubble_reference import GPU_FIELDS
-from test_regions_reference import BLOB_CASES, hand_cases, two_cubes
+from test_regions_reference import BLOB_CASES, CROWDED, crowded_condition, hand_cases, two_cubes
 
 pytestmark = pytest.mark.gpu
 
@@ -91,11 +95,13 @@ def test_blob_fields(asora, box, case, periodic):
     assert other[3][T["n_regions"]] != tallies[T["n_regions"]] and not np.array_equal(other[0], labels)
     assert counts.sum() == tallies[T["n_regions"]] and cells.sum() == tallies[T["n_phase"]] == BR.in_phase(field, threshold, phase).sum()
     if case == (0.69, 0, 6) and N > 17:                      # near percolation: a third of the phase in the largest, twelve bins occupied
-        assert tallies[T["n_regions"]] == {(64, False): 13_823, (70, False): 18_146, (64, True): 12_968, (70, True): 17_062}[N, periodic]
-        assert 0.3 < tallies[T["v_largest"]] / tallies[T["n_phase"]] < 0.41 and tallies[T["v_second"]] > 1000 and (counts > 0).sum() == 12
+        assert tallies[T["n_regions"]] == {(64, False): 13_823, (70, False): 18_146, (136, False): 129_629,
+                                           (64, True): 12_968, (70, True): 17_062, (136, True): 125_629}[N, periodic]
+        assert 0.3 < tallies[T["v_largest"]] / tallies[T["n_phase"]] < 0.41 and tallies[T["v_second"]] > 1000
+        assert (counts > 0).sum() == {64: 12, 70: 12, 136: 14}[N]      # (eight times the cells: fourteen)
         assert tallies[T["v_largest"]] > tallies[T["v_second"]] and tallies[T["extent_i"]] == tallies[T["extent_k"]] == N
     if case == (0.9, 0, 26) and N > 17 and not periodic:
-        assert tallies[T["n_regions"]] == {64: 3616, 70: 4708}[N] and (counts > 0).sum() == {64: 11, 70: 12}[N]
+        assert tallies[T["n_regions"]] == {64: 3616, 70: 4708, 136: 32_679}[N] and (counts > 0).sum() == {64: 11, 70: 12, 136: 13}[N]
 
 
 def test_26_neighbours_at_one_half(asora, box):
@@ -256,6 +262,69 @@ def test_crafted_masks(asora, N):
                     first, second = (1 * N + 1) * N + 1, (8 * N + 6) * N + 7
                     assert (t[T["v_largest"]], t[T["label_largest"]], t[T["v_second"]], t[T["label_second"]]) == (27, first, 27, second)
                     assert (t[T["extent_i"]], t[T["extent_j"]], t[T["extent_k"]]) == (3, 3, 3)
+
+
+def _cu_count():
+    import torch
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def test_crowded_mask_overflows_every_root_table(asora):
+    """N = 216, regions_reference.crowded.  With 6 neighbours every workgroup of region_flatten_kernel meets more distinct roots
+    than its LDS table has slots -- asserted for this device's launch by crowded_condition, which tests/test_regions_reference.py
+    asserts for 256 CUs without a GPU --, so every workgroup adds run lengths straight onto volume[], beside the sums it empties out
+    of the table at its end; every grid-stride loop of the six region kernels takes 19 trips; the regions of 7 have their runs in
+    three planes, hence in several workgroups.  With 26 neighbours the same mask is ONE region, whose 4.7 million cells go through
+    every workgroup's table: the reference is analytic."""
+    p, lib, capi = asora
+    N, seed = CROWDED
+    _mesh(asora, N)
+    cus = _cu_count()
+    mask = RR.crowded(N, seed)
+    edges = RR.default_edges(N)
+    lib.grid_to_device(capi.GRID_XH_AV, mask.astype(np.float64))
+    call = lambda connectivity, periodic, **kw: lib.region_sizes(capi.GRID_XH_AV, 0.5, 0, periodic, connectivity, edges, **kw)
+    wanted = {}
+    for periodic in (True, False):
+        want = wanted[periodic] = RR.sizes(mask, 6, periodic, edges)
+        fewest, most, trips = crowded_condition(want[0], mask, cus)
+        print(f"{cus} CUs, periodic {periodic}: {fewest} ... {most} roots per workgroup for a table of 2048, {trips:.1f} trips")
+        got = call(6, periodic, labels=True)
+        print(f"    tallies {got[2].tolist()}, reference {want[3].tolist()}")
+        assert got[3].dtype == np.uint32 and np.array_equal(got[3], want[0])
+        _same(got[:3], want[1:], ("with labels", periodic))
+        production = call(6, periodic)
+        _same(production, want[1:], ("production", periodic))
+        assert all(a.tobytes() == b.tobytes() for a, b in zip(production, call(6, periodic)))
+    assert wanted[True][3][T["n_regions"]] != wanted[False][3][T["n_regions"]] and not np.array_equal(wanted[True][0], wanted[False][0])
+    assert not np.array_equal(wanted[True][1], wanted[False][1])             # (the open faces make regions of 6 and 5)
+    # 26 neighbours: one region, label 0, all of the mask
+    V = int(mask.sum())
+    b = V.bit_length() - 1
+    one = np.where(mask, 0, RR.NO_LABEL).astype(np.uint32)
+    for periodic in (True, False):
+        got = call(26, periodic, labels=True)
+        assert np.array_equal(got[3], one)
+        for out in (got[:3], call(26, periodic)):
+            counts, cells, t = out
+            assert t.tolist() == [V, 1, V * V, V, 0, N, N, N, 0, RR.NO_LABEL, 0, 0, 0, 0], (periodic, t.tolist())
+            assert counts[b] == 1 and counts.sum() == 1 and cells[b] == V and cells.sum() == V
+
+
+def test_threshold_pass_with_more_rows_than_waves(asora):
+    """N = 216: the 46 656 rows are more than the waves bubble_mask_kernel is launched with (32 workgroups of 4 per CU), so waves take
+    a second row; four words per row, the last with a 24-bit tail."""
+    p, lib, capi = asora
+    N, seed = CROWDED
+    _mesh(asora, N)
+    assert N * N > _cu_count() * 32 * 4
+    field = BR.blob_field(N, seed)
+    lib.grid_to_device(capi.GRID_XH, field)
+    for phase in (0, 1):
+        words, rows = lib.bubble_mask(capi.GRID_XH, 0.5, phase)
+        ref_words, ref_rows = BR.mask_words(BR.in_phase(field, 0.5, phase))
+        assert words.shape == (N, N, 4) and np.array_equal(words, ref_words), phase
+        assert np.array_equal(rows, ref_rows) and rows.sum() == BR.in_phase(field, 0.5, phase).sum(), phase
 
 
 def test_class(asora, tmp_path):

@@ -10,6 +10,11 @@ import regions_reference as RR
 #: (threshold, phase, connectivity) of the blob fields the GPU tests label (bubble_reference.blob_field on GPU_FIELDS' meshes)
 BLOB_CASES = [(0.5, 0, 6), (0.5, 1, 6), (0.69, 0, 6), (0.9, 0, 26)]
 
+#: (N, seed) of regions_reference.crowded in the GPU test of the table overflow, and of the blob field whose mask it takes beside it
+CROWDED = (216, 2)
+#: the launch of the region kernels (csrc/region_label.hip): threads per workgroup, workgroups per CU, slots of the LDS root table
+RG_THREADS, RG_BLOCKS_PER_CU, RG_HASH = 256, 8, 2048
+
 T = {name: n for n, name in enumerate(RR.TALLIES)}
 
 
@@ -156,3 +161,62 @@ def test_periodic_volumes_do_not_depend_on_the_origin(N, seed):
         assert np.array_equal(np.sort(RR.volumes(RR.label(rolled, connectivity, True))[1]), vols)
         open_vols = np.sort(RR.volumes(RR.label(mask, connectivity, False))[1])
         assert open_vols.size > vols.size                       # (the wrap joins regions: open and periodic differ on these fields)
+
+
+def launch_blocks(N, cus):
+    """Workgroups of a region kernel at mesh N on a chip of `cus` compute units."""
+    return min((N ** 3 + RG_THREADS - 1) // RG_THREADS, cus * RG_BLOCKS_PER_CU)
+
+
+def crowded_condition(labels, mask, cus):
+    """What makes the crowded mask a test of region_flatten_kernel's overflow on a chip of `cus` compute units (shared with
+    tests/test_gpu_regions.py, which asserts it for the device it runs on): every workgroup meets more distinct roots than its
+    table has slots, so by pigeonhole every workgroup adds some run straight to global memory, and every thread of the
+    grid-stride loops takes more than 16 trips.  Returns (fewest, most) roots of a workgroup and the trips."""
+    N = mask.shape[0]
+    blocks = launch_blocks(N, cus)
+    per = RR.roots_per_workgroup(labels, mask, RG_THREADS, blocks)
+    trips = N ** 3 / (blocks * RG_THREADS)
+    assert per.size == blocks and per.min() > RG_HASH, (cus, blocks, int(per.min()), int(per.max()))
+    assert N ** 3 > 16 * blocks * RG_THREADS, (cus, blocks, trips)
+    return int(per.min()), int(per.max()), trips
+
+
+@pytest.mark.parametrize("periodic", [True, False], ids=["periodic", "open"])
+def test_crowded_mask_overflows_every_root_table_of_256_cus(periodic):
+    N, seed = CROWDED
+    mask = RR.crowded(N, seed)
+    i, j, k = np.indices((N, N, N))
+    odd = mask & ((i + j + k) % 2 == 1)
+    filled = int(odd.sum())
+    assert np.all(mask[(i + j + k) % 2 == 0]) and 0.45 * (N // 4) ** 3 < filled < 0.55 * (N // 4) ** 3
+    assert np.all(i[odd] % 4 == 1) and np.all(j[odd] % 4 == 0) and np.all(k[odd] % 4 == 0)
+    labels = RR.label(mask, 6, periodic)
+    roots, vols = RR.volumes(labels)
+    # a filled odd cell and its six neighbours (five or four of them where j = 0 or k = 0 lies on an open face); every other cell alone
+    at_face = (j[odd] == 0).astype(int) + (k[odd] == 0).astype(int)
+    joined = np.full(filled, 7) if periodic else 7 - at_face
+    want = {int(v): int(c) for v, c in zip(*np.unique(joined, return_counts=True))}
+    want[1] = N ** 3 // 2 - int((joined - 1).sum())
+    assert {int(v): int(c) for v, c in zip(*np.unique(vols, return_counts=True))} == want
+    assert len(want) == (2 if periodic else 4)                       # (the volumes are not all equal)
+    # the runs of one region lie in several workgroups: the seven cells of the first filled site
+    c = np.flatnonzero(odd)[0]
+    members = np.flatnonzero(labels.ravel() == labels.ravel()[c - N * N])
+    assert c in members and np.unique((members // RG_THREADS) % launch_blocks(N, 256)).size >= 3
+    fewest, most, trips = crowded_condition(labels, mask, 256)
+    print(f"crowded({N}, {seed}), periodic {periodic}: {roots.size} regions, {fewest} ... {most} roots per workgroup, {trips:.1f} trips")
+
+
+def test_the_136_field_has_runs_through_three_mask_words():
+    """At threshold 0.5 the ionised phase of the N = 136 field of the GPU tests holds runs along k that begin in word 0 and end in
+    word 2: region_init_kernel walks back two words from their last cells, region_flatten_kernel forward two words from their first."""
+    from test_bubble_reference import GPU_FIELDS
+    (N, seed), = [f for f in GPU_FIELDS if f[0] > 128]
+    assert (N + 63) // 64 == 3 and N % 64 == 8
+    mask = BR.in_phase(BR.blob_field(N, seed), 0.5, 0)
+    through = mask[:, :, 63:129].all(axis=2)                 # cells 63 ... 128 in phase: the run begins at k < 64 and ends at k >= 128
+    print(f"blob_field({N}, {seed}) >= 0.5: {int(through.sum())} runs begin in word 0 and end in word 2")
+    assert through.sum() >= 1
+    # ... and one of them ends short of the row's end, one begins after its start: both walks stop on a bit, not on the row's edge
+    assert np.any(through & ~mask[:, :, N - 1]) and np.any(through & ~mask[:, :, 0])
