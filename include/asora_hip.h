@@ -645,6 +645,19 @@ enum {
 };
 int asora_last_raytrace_variant(void);
 
+/* What a raytrace launch would be, from the launcher's own planning functions (pyc2ray_amd/csrc/raytrace_plan.hpp): host only, no
+ * device needed.  The options are read as asora_set_option left them (grey opacity, open boundaries and the [k][j][i] twins among
+ * them); cu_count <= 0: the device's, 256 before asora_device_init.  flags: ASORA_PLAN_*.  shells < 0: stage 1 only -- out[0 ... 2]
+ * = workgroups per source, threads per workgroup, line-aligned tables.  Else, for geometry tables of `shells` shells whose largest
+ * holds max_cells cells: out[3 ... 15] the template arguments of raytrace_octant_kernel in their order, out[16] shells in LDS,
+ * out[17] dynamic LDS bytes, out[18] the word asora_last_raytrace_variant would report (with ASORA_OPT_SKIP_ZERO_RATES = 0 the
+ * probes of a run decide about the exact zeros: planned as kept), out[19] whether that form is built, out[20] whether a form that
+ * drops exact zeros exists, out[21] = 1.  A combination the launcher refuses returns its code and message. */
+enum { ASORA_PLAN_HEAT = 1, ASORA_PLAN_DUMP = 2, ASORA_PLAN_TABLE_SETS = 4, ASORA_PLAN_HOST_POSITIONS = 8, ASORA_PLAN_RADIUS_STAYS = 16,
+       ASORA_PLAN_RATE_TABLES = 32 /* rate tables with a positive step are loaded */, ASORA_PLAN_WORDS = 24 };
+int asora_debug_launch_plan(int N, double R, int src_count, int shape_src_count, int cu_count, int flags, int shells, int max_cells,
+                            int32_t *out);
+
 /* The geometry tables the last raytrace launch used (tests: device-built against host-built tables).  *ntables = tables of the
  * launch shape (units x 8 when line-aligned); for 0 <= table < *ntables: `words` receives 8 uint32 per entry (the 16-byte
  * cell-A and cell-B records, raytrace.hip) for up to capacity_entries entries, *entries the table's entry count, *nsteps its

@@ -24,6 +24,8 @@ KERNEL_RAYTRACE, KERNEL_CHEMISTRY, KERNEL_PREP, KERNEL_FINISH = range(4)
 KERNEL_BUBBLE_MASK, KERNEL_BUBBLE_SCAN, KERNEL_BUBBLE_RAYS = 4, 5, 6
 VARIANT_PAIRED, VARIANT_ALIGNED, VARIANT_BUFFER_ATOMICS, VARIANT_SPLIT_DESCRIPTORS, VARIANT_SKIP_ZERO, VARIANT_GLOBAL_SHELLS = 1, 2, 4, 8, 16, 32
 VARIANT_OPEN_BOUNDARIES = 64
+PLAN_HEAT, PLAN_DUMP, PLAN_TABLE_SETS, PLAN_HOST_POSITIONS, PLAN_RADIUS_STAYS, PLAN_RATE_TABLES = 1, 2, 4, 8, 16, 32
+PLAN_WORDS = 24
 (BUDGET_CELLS, BUDGET_N, BUDGET_X, BUDGET_NX, BUDGET_NX0, BUDGET_DNX, BUDGET_PHOTO, BUDGET_LLS, BUDGET_REC, BUDGET_COL,
  BUDGET_T, BUDGET_NT) = range(12)
 BUDGET_COUNT = 12
@@ -133,6 +135,7 @@ SIGNATURES = {
     "asora_last_raytrace_counts_ex": (C.c_int, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "asora_debug_coldens": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_int, _dp, C.c_int]),
     "asora_last_raytrace_variant": (C.c_int, []),
+    "asora_debug_launch_plan": (C.c_int, [C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip]),
     "asora_debug_geometry_bytes": (C.c_size_t, []),
     "asora_debug_geometry_table": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int),
                                              C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),

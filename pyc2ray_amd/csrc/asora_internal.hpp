@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/asora_hip.h"
+#include "raytrace_plan.hpp"
 
 namespace asora {
 
@@ -88,7 +89,7 @@ struct RtParams {
     unsigned long long *counters;
     const int *done_flag;       // evolve loop: device flag "the step has converged" -> the launch does nothing; or nullptr
     unsigned long long *zero_probe;   // SKIP_ZERO kernels: where a probe launch sums what it rated and what it left out, or nullptr
-    // ---- rows cut at 64-byte lines (ASORA_OPT_ALIGNED_ROWS; launch_raytrace) ----
+    // ---- rows cut at 64-byte lines (ASORA_OPT_ALIGNED_ROWS; plan_shape) ----
     int aligned;                // 1: geom[] holds 8 x units tables, [class * units + unit], class = source position & 7 along the
                                 //    memory-contiguous axis of the unit's face (k for the x- and y-sectors, i for the z-sector)
     const int2 *pairs[2];       // NSRC = 2 && aligned: the workgroup's two sources (indices into src_pos; .y < 0: only one) for
@@ -181,8 +182,8 @@ struct State {
     size_t geom_bytes = 0;                  // device memory the current tables occupy (shells shared by several tables count once)
     OctGeomDev geom_host[MAX_UNITS];        // device pointers of the unit tables ([class * units + unit] when geom_aligned)
     bool geom_aligned = false;
-    // how the radius has behaved across raytrace launches (launch_raytrace: the eight-fold tables only pay when they are reused)
-    // exact-zero rates (ASORA_OPT_SKIP_ZERO_RATES = 0): launch_raytrace takes the kernels that leave them out while its probes
+    // how the radius has behaved across raytrace launches (plan_shape: the eight-fold tables only pay when they are reused)
+    // exact-zero rates (ASORA_OPT_SKIP_ZERO_RATES = 0): decide_skip_zero takes the kernels that leave them out while its probes
     // find enough of them
     unsigned long long *zero_probe_dev = nullptr;    // [2 * ZERO_PROBE_SLOTS]
     unsigned long long *zero_probe_host = nullptr;   // pinned: {rated, left out} of the last probe
@@ -421,6 +422,7 @@ int check_open_boundaries(const State &st, const char *who, bool open, bool dump
 int check_plane_flux(const State &st, const PlaneFluxSet &pf, const char *who, bool dump, bool heat);
 int launch_plane_flux(State &st, const RtParams &p, double *phi, double *heat_acc, bool heat, const int *done);
 int launch_raytrace(State &st, RtParams &p, bool dump, bool heat, hipStream_t side = nullptr);   // side: stream to launch on when no shared scratch is needed
+void plan_options(const State &st, RtPlanInput &in);    // cu_count and the options a launch plan reads (raytrace_plan.hpp)
 // The sub-box sweep on tabulated geometry (raytrace.hip): prepare -> tables for (N, R, range, box size), then one launch per
 // sub-box.  `shells` = (s_begin, s_end] of the box; returns without launching when the tables hold nothing there.
 struct SubboxTables { int units = 0, threads = 0, S = 0, max_batch = 0, nsrc = 1; bool ok = false, aligned = false; const int32_t *host_pos = nullptr; };   // max_batch: sources per launch the trailing-shell scratch holds; nsrc: sources per workgroup (2: paired sweep); host_pos: the source positions on the host (0-based, xyz-interleaved; pairing for the aligned tables) or nullptr

@@ -39,7 +39,7 @@ int asora_grid_to_device(int which, const double *host, int N, char order)
     if (!host) return fail(3, "grid_to_device: null host pointer");
     State &st = state();
     if (int rc = ensure_optional_grid(which)) return rc;
-    st.zero_since_probe = std::max(st.zero_since_probe, 48);   // new medium: look again for cells beyond the table soon (launch_raytrace: at 64)
+    st.zero_since_probe = std::max(st.zero_since_probe, 48);   // new medium: look again for cells beyond the table soon (decide_skip_zero: at 64)
     const size_t bytes = st.ncell * sizeof(double);
     if (order == 'C' || order == 'c') {
         ASORA_HIP_TRY(hipMemcpyAsync(st.grid[which], host, bytes, hipMemcpyHostToDevice, st.stream));

@@ -44,6 +44,7 @@
 #include <cstring>
 #include <chrono>
 #include <thread>
+#include <utility>
 #include <vector>
 
 namespace asora {
@@ -202,16 +203,17 @@ extern "C" __device__ double asora_buffer_atomic_fadd_f64(double, __amdgpu_buffe
 // its own there; cells on the faces of the box add what passes through them (phi_out, photorates.f90:120-125) to the
 // source's photon loss; every source is rated with the flux of `flux_src` (f90:500,503).  Fortran-flavoured constants.
 //
-// Which combinations exist (the two static_asserts below admit exactly these; DESIGN.md 4.1 has the same table with the launch
-// shapes that select them):
-//   family                         THREADS x TABCAP                               GS   DUMP HEAT SKIP_ZERO GREY BUFATOM NSRC SUBBOX   launcher
-//   paired production              {64,128,256,512}x256 {64,128,256}x64 256x32     f    f    f    f/t       f    t       2    f        launch_variant_pairs
-//   single source, buffer atomics  {64..1024}x256 {64,128}x64 {256,512,1024}x1024  f    f    f/t  f/t       f/t  t       1    f        launch_variant
-//   single source, global atomics  same (N > 512, option, shells in global memory) f/t  f    f/t  f (t: GS=f) f/t f       1    f        launch_variant
-//   column-density dump            256 x {256,1024}                                f/t  t    f    f         f/t  f       1    f        launch_variant
-//   sub-box sweep                  {256,512} x 256                                 f    f    f/t  f         f    t       1|2  t        launch_subbox_tables_variant
-//   descriptors per layout (SPLIT) paired {256x32, 256x64, 256x256, 512x256}; single {256,512}x256            f    f    f/t  f/t       f/t  t       1|2  f        launch_variant_pairs / _split
-//   open boundaries (OPEN)         paired {256,512}x256; single {256,512}x{256,1024} f/t(1) f    f/t(1) f       f    t       1|2  f        launch_variant_open
+// Which combinations exist: the rows of RT_FORMS (raytrace_plan.hpp, make_form_table), which is the source -- launch_form_row below
+// instantiates exactly its rows, 182 of the 13 template parameters, and the static_asserts below check every one.  In summary
+// (SPLIT, SPEC and OPEN are f, t, f unless the family says otherwise; DESIGN.md 4.1 has the launch shapes that select them):
+//   family                         THREADS x TABCAP                               GS   DUMP HEAT SKIP_ZERO GREY BUFATOM NSRC SUBBOX   forms
+//   paired production              {64,128,256,512}x256 {64,128,256}x64 256x32     f    f    f    f/t       f    t       2    f        16
+//   single source, buffer atomics  {64..1024}x256 {64,128}x64 {256,512,1024}x1024  f    f    f/t  f/t       f/t  t       1    f        40
+//   single source, global atomics  same (N > 512, option, shells in global memory) f/t  f    f/t  f (t: GS=f) f/t f       1    f        70
+//   column-density dump            256 x {256,1024}                                f/t  t    f    f         f/t  f       1    f        8
+//   sub-box sweep                  {256,512} x 256                                 f    f    f/t  f         f    t       1|2  t        6
+//   descriptors per layout (SPLIT) paired {256x32, 256x64, 256x256, 512x256}, SPEC f/t; single {256,512}x256   f    f    f/t  f/t       f/t  t       1|2  f        16 + 8
+//   open boundaries (OPEN)         paired {256,512}x256; single {256,512}x{256,1024} f/t(1) f    f/t(1) f       f    t       1|2  f        18
 //   (SKIP_ZERO with HEAT or GREY, NSRC = 2 with HEAT, DUMP, GREY or global atomics, SUBBOX with NSRC = 2 and HEAT: not built)
 // OPEN (ASORA_OPT_OPEN_BOUNDARIES): a cell whose unwrapped position i0 +- a, j0 +- b, k0 +- c lies outside [0, N)
 // on any axis is swept like every other -- its upstream neighbours and whatever reads it lie outside as well, since every
@@ -220,13 +222,13 @@ extern "C" __device__ double asora_buffer_atomic_fadd_f64(double, __amdgpu_buffe
 // tables carry the verdict per axis and offset in their top bit, nhi_address hands the OR of the three on in the top bit of the
 // cell index, and the lane's pending atomic gets the out-of-range offset of a lane without a rate.  A compile-time variant: with
 // OPEN = false every instantiation is what it was (register counts line for line); the last row of the table is all that is
-// built with it -- 18 forms -- and launch_raytrace maps every launch shape onto them (64 ... 256 threads -> 256, 512 and 1024
+// built with it -- 18 forms -- and plan_shape maps every launch shape onto them (64 ... 256 threads -> 256, 512 and 1024
 // -> 512; 256-entry LDS tables unless there are more than 256 shells; no exact-zero skipping); N > 512, grey opacity, global
 // atomics, the column-density dump and the sub-box sweep are refused (check_open_boundaries).  138 VGPRs paired (three waves
 // per SIMD against four), 100 single (four against five), 108 with heating.
 // SPEC: the kernel reads the table set of its source(s) (RtParams::src_spec; a scalar load and a scalar multiply-add per source).
 // Every form is built with it, at no VGPR; only the paired SPLIT family tips from 128 to 129 VGPRs (four waves per SIMD to three),
-// so that family alone is ALSO built without (SPEC = false) and launches without table sets take that form: launch_variant_pairs.
+// so that family alone is ALSO built without (SPEC = false) and launches without table sets take that form: plan_launch.
 // split descriptors: does this unit's face write the [k][j][i] twin?  (the z-sector with the twins in use)
 __device__ __forceinline__ bool ztr_desc(const RtParams &p, int uinfo) { return p.z_transposed != 0 && ((uinfo >> 8) & 3) == 3; }
 
@@ -841,234 +843,40 @@ __global__ void __launch_bounds__(RT_THREADS, 1) raytrace_octant_kernel(const Rt
 
 // ---------------------------------------------------------------------------------------------
 // Host driver of the octant kernel (the role of do_all_sources_gpu's batch loop,
-// raytracing.cu:101-143)
+// raytracing.cu:101-143).  What a launch is going to be is decided in raytrace_plan.hpp; here is what touches the device.
 // ---------------------------------------------------------------------------------------------
-static const size_t LDS_LIMIT_BYTES = 160 * 1024;
+static_assert(LDS_LOG_TABLE_BYTES == LOG_TABLE_SIZE * sizeof(double2), "raytrace_plan.hpp counts the log table as the kernel lays it out");
 
-// Decomposition and workgroup size.  Shells of a small trace do not fill 256 lanes (R=16: <= 310 cells per
-// octant shell); a large one needs so much LDS per octant that few workgroups fit a CU.  Three things pull:
-//   * padding: every shell of every unit is padded to whole waves, so FEWER, LARGER units waste fewer lanes (R = 16:
-//     1.41 lane-steps per rated cell with 8 octants, 1.04 with the whole sphere in one workgroup; R = 32: 1.17 with 12
-//     sector pairs, 1.10 with 6 sectors whose transverse axes are both mirrored), and units that cover both signs of an
-//     axis do not evaluate the plane between them twice;
-//   * the rate atomics want long contiguous rows: units that mirror the memory-contiguous axis of a face sweep full
-//     chords of the sphere (~15 % fewer 64-B atomic requests per rated cell than octants);
-//   * LDS: a unit's two shell buffers must leave room for enough workgroups per CU, which is what stops the merging --
-//     the whole sphere needs 39 KB at R = 16 and 157 KB at R = 32.
-// Thresholds from sweeps on MI355X (1000 sources, 256^3; tools/sweep_units.sh, profiles/r03_sweep_units_run*.txt):
-//   R < 11.5: whole sphere x 128 threads | < 15.5: x 256 | < 21.5: x 512 | < 23.5: half spheres x 256 | < 25.5: x 512 |
-//   < 36.5: 6 sectors by sign of the dominant offset x 256 | < 52.5: 12 mirrored sector pairs x 256 | else x 512
-// (round 2, without the merged kinds: R <= 12 octant pairs x 64 | 13..14 x 128 | 15..19 octants x 64 | 20..22 sector pairs
-//  x 64 | 23..28 octant pairs x 256 | 29..35 sector pairs x 128 | 36..54 x 256 | >= 55 x 512 -- still what is used when the
-//  merged kinds would leave CUs without a workgroup)
-static void pick_launch_shape(const State &st, double R, int N, int src_count, bool dump, int &units, int &threads)
+// Row I of RT_FORMS: the one place where the kernel's template arguments are written, so the rows of the table are the
+// instantiations of the build
+template <size_t I>
+static int launch_form_row(const RtParams &q, unsigned grid, size_t lds_bytes, hipStream_t stream)
 {
-    const double r = std::min(R, 0.87 * N);                 // the window cuts the trace at ~sqrt(3)/2 N
-    const double est_cells = 1.2 * r * r;                   // largest shell of an octant
-    if (r <= 12.5) { units = 4; threads = 64; }             // pairs of whole octants mirrored in x
-    else if (r <= 14.5) { units = 4; threads = 128; }
-    else if (est_cells <= 450.0) { units = 8; threads = 64; }        // r <= 19.4
-    else if (r <= 22.5) { units = 12; threads = 64; }
-    else if (r <= 28.5) { units = 4; threads = 256; }
-    else if (est_cells <= 1500.0) { units = 12; threads = 128; }     // r <= 35.3
-    else if (est_cells <= 3500.0) { units = 12; threads = 256; }     // r <= 54
-    else { units = 12; threads = 512; }
-    {   // the merged kinds, when they still give every CU a couple of workgroups
-        int mu = 0, mt = 0;
-        if (r < 11.5) { mu = 1; mt = 128; }
-        else if (r < 15.5) { mu = 1; mt = 256; }
-        else if (r < 21.5) { mu = 1; mt = 512; }
-        else if (r < 23.5) { mu = 2; mt = 256; }
-        else if (r < 25.5) { mu = 2; mt = 512; }
-        else if (r < 36.5) { mu = 6; mt = 256; }
-        else if (r < 52.5) { mu = 12; mt = 256; }
-        if (mu && (long)src_count * mu >= 2L * st.cu_count && !dump) { units = mu; threads = mt; }
-        // Beyond N = 512 a buffer descriptor spans ONE layout of the rate grid (launch_raytrace, `split`), so the production forms --
-        // two sources per workgroup, buffer atomics -- need units whose rated cells all lie on one kind of face.  Where the radius
-        // would take the whole sphere or the half spheres (cells of every face in one workgroup: the global-atomic family, one
-        // source per workgroup), the three all-sign sectors take their place (round 6; the reference's meshes end at 645,
-        // ref: src/asora/raytracing.cu:95).  Measured at N = 576, 1000 sources (profiles/r06_ab_576_small_radii.txt): r_RT = 16
-        // 0.286 -> 0.241 ms, r_RT = 24 0.605 -> 0.589 ms; below the radius from which two sources share a workgroup (15.5) the
-        // whole sphere stays (r_RT = 12: 0.137 against 0.140 ms).
-        if ((units == 1 || units == 2) && units == mu && r >= 15.5 && N > 512 && N <= 645 && (long)src_count * 3 >= 2L * st.cu_count &&
-            !st.opt[ASORA_OPT_GLOBAL_ATOMICS] && st.opt[ASORA_OPT_Z_TRANSPOSED]) {
-            units = 3;
-            threads = r < 21.5 ? 256 : 512;
-        }
-    }
-    // Few sources (fewer workgroups than CUs): the time of the call is the time of ONE workgroup, so cut a source
-    // into more (24 sectors) and wider pieces.  One source, 128^3, R = 64: 0.235 -> 0.146 ms (tools/sweep_single_source.sh)
-    // A few dozen sources (workgroups for half the CUs' slots at most): still one round, wider workgroups finish it sooner
-    // (64 sources, R = 32: pairs x 256 threads 0.183 ms against 0.202 with 128; tools/sweep_mid_counts.sh)
-    if ((long)src_count * 12 <= (long)st.cu_count * 4 && units == 12 && threads == 128) threads = 256;
-    if ((long)src_count * 12 < (long)st.cu_count) {
-        units = 24;
-        if (est_cells > 900.0) threads = std::max(threads, 512);
-        if (est_cells > 2500.0) threads = 1024;
-    }
-    // A handful of sources: 24 workgroups each still leave most CUs idle -- quarter the sectors (96 per source; each wedge
-    // re-derives the inner part of its sector, so evaluations double, time about halves)
-    // (measured, one source: 128^3 whole box 0.205 -> 0.157 ms, R = 32 0.051 -> 0.043 ms; the floor is the chain of shells,
-    //  ~2 us each, not the work: tools/sweep_single_source.sh)
-    if ((long)src_count * 48 <= (long)st.cu_count) {
-        units = 96;
-        threads = est_cells > 6000.0 ? 1024 : est_cells > 2500.0 ? 512 : 256;
-    }
-    const int want_sectors = st.opt[ASORA_OPT_SECTORS];
-    if (want_sectors == 1) units = 8;
-    if (want_sectors == 2) units = 24;
-    if (want_sectors == 3) units = 12;
-    if (want_sectors == 4) units = 96;
-    if (want_sectors == 5) units = 4;
-    if (want_sectors == 6) units = 1;
-    if (want_sectors == 7) units = 2;
-    if (want_sectors == 8) units = 3;
-    if (want_sectors == 9) units = 6;
-    const int forced = st.opt[ASORA_OPT_BLOCK_THREADS];
-    if (forced == 64 || forced == 128 || forced == 256 || forced == 512 || forced == 1024) threads = forced;
-    if (dump) threads = 256;                                // the column-density dump variant is built for 256 only
-}
-
-// Does sweeping two sources per workgroup pay?  (auto mode of ASORA_OPT_PAIR_SOURCES; from A/B runs on MI355X, 1000 sources,
-// 256^3: profiles/r03_ab_two_sources.txt -- R = 16 -4 %, 20 -2 %, 26 -10 %, 28 -12 %, 32 -7 %, 40 -8 %, 48 -5 %, 56 and 64 0 %;
-// nothing below R ~ 15, where the whole sphere is swept by few waves)
-static bool pair_sources_pays(const State &st, double R, int N, int src_count, int units, int threads)
-{
-    const double r = std::min(R, 0.87 * N);
-    if (!(r >= 15.5 && r < 52.5)) return false;
-    // enough waves must be left to fill the chip (two per SIMD)
-    return (long)(src_count / 2) * units * (threads / 64) >= 8L * st.cu_count;
-}
-
-// Can the rate atomics go through buffer descriptors (the kernel's BUFATOM)?  One descriptor over both layouts of the rate
-// grid while the pair fits 2 GiB (N <= 512); one per layout (split) up to 2 GiB per layout (N <= 645) for units whose rated
-// cells all lie on one face -- the sector kinds.
-// The split form is built for the shapes such meshes take at ordinary radii: 256 or 512 threads, up to 256 shells; two sources
-// per workgroup for table rates without heating, one source per workgroup also with heating or grey opacity (everything else
-// beyond N = 512 -- column-density dump, more than 256 shells, whole spheres below r = 15.5 -- keeps the global-atomic family).
-static bool buffer_atomics_fit(const State &st, const RtParams &p, int units, int threads, bool plain_tables, bool &split)
-{
-    split = false;
-    if (st.opt[ASORA_OPT_GLOBAL_ATOMICS]) return false;
-    if (16ull * p.ncell <= 0x80000000ull) return true;
-    const bool one_face = units == 3 || units == 6 || units == 12 || units == 24 || units == 96;
-    if (8ull * p.ncell <= 0x80000000ull && one_face && p.z_transposed && (threads == 256 || threads == 512) && plain_tables) { split = true; return true; }
-    return false;
-}
-
-constexpr size_t lds_table_bytes(int tabcap, int nsrc = 1) { return LOG_TABLE_SIZE * sizeof(double2) + (size_t)tabcap * (sizeof(double) + (size_t)nsrc * 6 * sizeof(int)); }
-
-// the paired-sources variant (NSRC = 2) exists for the production path only: table rates, no heating, no dump, shell
-// buffers in LDS, buffer atomics
-template <int T, int TABCAP, bool SPLIT = false>
-static int launch_variant_pairs(State &st, const RtParams &q, unsigned grid, size_t lds_bytes, hipStream_t stream, bool skip_zero)
-{
-#define ASORA_LAUNCH_PAIRS(SZ, SP)                                                                                                          \
-    do {                                                                                                                                \
-        ASORA_HIP_TRY(hipFuncSetAttribute((const void *)raytrace_octant_kernel<T, false, false, false, TABCAP, SZ, false, true, 2, false, SPLIT, SP>, \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));                                 \
-        hipLaunchKernelGGL((raytrace_octant_kernel<T, false, false, false, TABCAP, SZ, false, true, 2, false, SPLIT, SP>), dim3(grid), dim3(T), \
-                           lds_bytes, stream, q);                                                                                       \
-    } while (0)
-    // (SPLIT without table sets per source: the form that does not read them -- see the kernel's SPEC)
-    if constexpr (SPLIT) {
-        if (!q.src_spec) {
-            if (skip_zero) ASORA_LAUNCH_PAIRS(true, false); else ASORA_LAUNCH_PAIRS(false, false);
-            ASORA_HIP_TRY(hipGetLastError());
-            return 0;
-        }
-    }
-    if (skip_zero) ASORA_LAUNCH_PAIRS(true, true); else ASORA_LAUNCH_PAIRS(false, true);
-#undef ASORA_LAUNCH_PAIRS
+    constexpr RtForm f = RT_FORMS.row[I];
+    constexpr auto kernel = raytrace_octant_kernel<f.threads, f.global_scratch, f.dump, f.heat, f.tabcap, f.skip_zero, f.grey, f.bufatom, f.nsrc, f.subbox, f.split, f.spec, f.open>;
+    ASORA_HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(f.threads), lds_bytes, stream, q);
     ASORA_HIP_TRY(hipGetLastError());
     return 0;
 }
-
-// single source, buffer descriptors per layout (512 < N <= 645): table rates (plain and zero-skipping form), with heating, grey opacity
-template <int T>
-static int launch_variant_split(State &st, const RtParams &q, unsigned grid, size_t lds_bytes, hipStream_t stream, bool skip_zero, bool heat)
+// The row equal to the planned form; a form that is not built is an error, never a neighbouring kernel
+template <size_t... I>
+static int launch_form(const RtForm &f, const RtParams &q, unsigned grid, size_t lds_bytes, hipStream_t stream, std::index_sequence<I...>)
 {
-#define ASORA_LAUNCH_SPLIT(HT, SZ, GR)                                                                                                 \
-    do {                                                                                                                           \
-        ASORA_HIP_TRY(hipFuncSetAttribute((const void *)raytrace_octant_kernel<T, false, false, HT, 256, SZ, GR, true, 1, false, true>, \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));                            \
-        hipLaunchKernelGGL((raytrace_octant_kernel<T, false, false, HT, 256, SZ, GR, true, 1, false, true>), dim3(grid), dim3(T), lds_bytes, stream, q); \
-    } while (0)
-    if (q.grey)         ASORA_LAUNCH_SPLIT(false, false, true);
-    else if (heat)      ASORA_LAUNCH_SPLIT(true, false, false);
-    else if (skip_zero) ASORA_LAUNCH_SPLIT(false, true, false);
-    else                ASORA_LAUNCH_SPLIT(false, false, false);
-#undef ASORA_LAUNCH_SPLIT
-    ASORA_HIP_TRY(hipGetLastError());
-    return 0;
+    int rc = -1;
+    (void)((RT_FORMS.row[I] == f && ((rc = launch_form_row<I>(q, grid, lds_bytes, stream)), true)) || ...);
+    if (rc < 0) return fail(11, "raytrace: no kernel is built for the form " + form_text(f) + " (internal error)");
+    return rc;
 }
-
-template <int T, int TABCAP>
-static int launch_variant(State &st, const RtParams &q, unsigned grid, size_t lds_bytes, bool use_lds, bool dump, bool heat,
-                          hipStream_t stream, bool skip_zero)
-{
-#define ASORA_LAUNCH(GS, DP, HT, SZ, GR, BA)                                                                           \
-    do {                                                                                                           \
-        ASORA_HIP_TRY(hipFuncSetAttribute((const void *)raytrace_octant_kernel<T, GS, DP, HT, TABCAP, SZ, GR, BA>, \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));            \
-        hipLaunchKernelGGL((raytrace_octant_kernel<T, GS, DP, HT, TABCAP, SZ, GR, BA>), dim3(grid), dim3(T),       \
-                           lds_bytes, stream, q);                                                                  \
-    } while (0)
-    const bool grey = q.grey != 0;
-    // rate atomics through buffer descriptors (see the kernel's BUFATOM): [phi | phi_t] must not exceed 2 GiB
-    // (q.split_desc: launch_raytrace has decided that the descriptors go per layout; those forms are launched from there)
-    const bool ba = use_lds && !q.split_desc && 16ull * q.ncell <= 0x80000000ull && !st.opt[ASORA_OPT_GLOBAL_ATOMICS];
-    if (T == 256 && dump) {
-        if (grey)         { if (use_lds) ASORA_LAUNCH(false, true, false, false, true, false); else ASORA_LAUNCH(true, true, false, false, true, false); }
-        else              { if (use_lds) ASORA_LAUNCH(false, true, false, false, false, false); else ASORA_LAUNCH(true, true, false, false, false, false); }
-    }
-    else if (grey)        { if (ba) ASORA_LAUNCH(false, false, false, false, true, true); else if (use_lds) ASORA_LAUNCH(false, false, false, false, true, false); else ASORA_LAUNCH(true, false, false, false, true, false); }
-    else if (heat)        { if (ba) ASORA_LAUNCH(false, false, true, false, false, true); else if (use_lds) ASORA_LAUNCH(false, false, true, false, false, false); else ASORA_LAUNCH(true, false, true, false, false, false); }
-    // ASORA_OPT_SKIP_ZERO_RATES = 1 where the buffer-atomic kernel (which drops exact zeros by itself) is not available: the
-    // branching variant that leaves them out
-    else if (use_lds && !ba && std::isfinite(q.tau_zero) && st.opt[ASORA_OPT_SKIP_ZERO_RATES] == 1) ASORA_LAUNCH(false, false, false, true, false, false);
-    else                  { if (ba && skip_zero) ASORA_LAUNCH(false, false, false, true, false, true); else if (ba) ASORA_LAUNCH(false, false, false, false, false, true); else if (use_lds) ASORA_LAUNCH(false, false, false, false, false, false); else ASORA_LAUNCH(true, false, false, false, false, false); }
-#undef ASORA_LAUNCH
-    ASORA_HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// Open boundaries (ASORA_OPT_OPEN_BOUNDARIES, the kernel's OPEN): the forms of the variant table's last row.  Workgroups of 256 or
-// 512 threads, LDS tables of 256 or 1024 entries; two sources per workgroup with the 256-entry tables and the shells in LDS,
-// one source per workgroup with or without heating, shells in LDS or -- where they outgrow it -- in global memory, the rates
-// through buffer atomics either way (one descriptor: N <= 512).
-template <int T, int TABCAP>
-static int launch_variant_open(const RtParams &q, unsigned grid, size_t lds_bytes, bool use_lds, bool heat, bool pairs, hipStream_t stream)
-{
-#define ASORA_LAUNCH_OPEN(GS, HT, NS)                                                                                                       \
-    do {                                                                                                                                \
-        ASORA_HIP_TRY(hipFuncSetAttribute((const void *)raytrace_octant_kernel<T, GS, false, HT, TABCAP, false, false, true, NS, false, false, true, true>, \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));                                 \
-        hipLaunchKernelGGL((raytrace_octant_kernel<T, GS, false, HT, TABCAP, false, false, true, NS, false, false, true, true>), dim3(grid), dim3(T), \
-                           lds_bytes, stream, q);                                                                                       \
-    } while (0)
-    if constexpr (TABCAP == 256) {
-        if (pairs) { ASORA_LAUNCH_OPEN(false, false, 2); ASORA_HIP_TRY(hipGetLastError()); return 0; }
-    }
-    if (pairs) return fail(11, "raytrace: no paired open-boundary form with these LDS tables (internal error)");
-    if (use_lds) { if (heat) ASORA_LAUNCH_OPEN(false, true, 1); else ASORA_LAUNCH_OPEN(false, false, 1); }
-    else         { if (heat) ASORA_LAUNCH_OPEN(true, true, 1);  else ASORA_LAUNCH_OPEN(true, false, 1); }
-#undef ASORA_LAUNCH_OPEN
-    ASORA_HIP_TRY(hipGetLastError());
-    return 0;
-}
+constexpr std::make_index_sequence<RT_FORM_COUNT> ALL_FORMS{};
 
 // What open boundaries are not built for: refused before anything is launched (every entry point asks through
 // require_raytrace_inputs; launch_raytrace asks again, so that no launch can slip past)
 int check_open_boundaries(const State &st, const char *who, bool open, bool dump)
 {
     if (!open) return 0;
-    const std::string w = std::string(who) + ": open boundaries (ASORA_OPT_OPEN_BOUNDARIES) ";
-    if (16ull * st.ncell > 0x80000000ull) return fail(4, w + "are built for N <= 512 (mesh of " + std::to_string(st.N) + ")");
-    if (st.opt[ASORA_OPT_GREY_NOTABLES] && !st.coldens_only) return fail(4, w + "need table rates (grey opacity, ASORA_OPT_GREY_NOTABLES, is on)");
-    if (st.opt[ASORA_OPT_GLOBAL_ATOMICS]) return fail(4, w + "need the buffer-atomic kernels (ASORA_OPT_GLOBAL_ATOMICS is on)");
-    if (dump) return fail(4, w + "have no column-density dump");
-    return 0;
+    const std::string why = open_boundaries_refusal(st.N, st.opt[ASORA_OPT_GREY_NOTABLES] && !st.coldens_only, st.opt[ASORA_OPT_GLOBAL_ATOMICS] != 0, dump);
+    return why.empty() ? 0 : fail(4, std::string(who) + ": open boundaries (ASORA_OPT_OPEN_BOUNDARIES) " + why);
 }
 
 // Who shares a workgroup with whom when the tables are the aligned kind (build_unit_geometry, align_class): two sources
@@ -1107,6 +915,21 @@ static int source_pairs_by_class(State &st, const int32_t *host_pos, const void 
     return 0;
 }
 
+// The workgroups of a launch of q.src_count sources from q.src_begin: per unit one for every source or every two, by the
+// class lists where the tables are aligned; q.spread and the grid from their number
+static int set_launch_grid(State &st, RtParams &q, int units, bool pairs, bool aligned, const int32_t *host_pos, unsigned &grid)
+{
+    int groups = pairs ? (q.src_count + 1) / 2 : q.src_count;              // workgroups per unit
+    if (pairs && aligned) {        // partners agree modulo 8 along the memory-contiguous axis of the unit's face
+        const State::PairList *pl = nullptr;
+        if (int rc = source_pairs_by_class(st, host_pos, q.src_pos, q.src_begin, q.src_count, pl)) return rc;
+        for (int ft = 0; ft < 2; ++ft) { q.pairs[ft] = pl->dev[ft]; q.npairs[ft] = pl->n[ft]; }
+        groups = std::max(pl->n[0], pl->n[1]);
+    }
+    grid = launch_grid(groups, units, st.cu_count, q.spread);
+    return 0;
+}
+
 // {rated pairs, exact zeros left out} of a probe launch, summed over its slots into pinned host memory
 __global__ void __launch_bounds__(ZERO_PROBE_SLOTS) zero_probe_sum_kernel(const unsigned long long *__restrict__ slots, unsigned long long *out)
 {
@@ -1120,8 +943,69 @@ __global__ void __launch_bounds__(ZERO_PROBE_SLOTS) zero_probe_sum_kernel(const 
     if (threadIdx.x == 0) { out[0] = r[0][0]; out[1] = r[1][0]; }
 }
 
+// Exact-zero rates (ASORA_OPT_SKIP_ZERO_RATES, see the kernel's SKIP_ZERO).  The kernels that leave them out cost 5 % where
+// there are none, and save up to a quarter of the launch where most cells lie beyond the table (the neutral medium of an
+// early-reionisation run).  Left to the library (0) a launch takes them while the last PROBE found more than 15 % of the
+// rated pairs dark; a probe is such a launch whose two sums go to pinned host memory behind it and are looked at, without
+// waiting, by a later call: the first launch, every 64th after it, every launch while the dark variant runs anyway.
+// exists: such a form exists for this launch (RtPlan::zero_form_exists)
+static int decide_skip_zero(State &st, bool exists, bool &skip_zero, bool &probe)
+{
+    skip_zero = false; probe = false;
+    const int skip_zero_opt = st.opt[ASORA_OPT_SKIP_ZERO_RATES];
+    if (exists && skip_zero_opt == 1) skip_zero = true;
+    else if (exists && skip_zero_opt == 0) {
+        if (!st.zero_probe_dev) {
+            ASORA_HIP_TRY(hipMalloc(&st.zero_probe_dev, 2 * ZERO_PROBE_SLOTS * sizeof(unsigned long long)));
+            ASORA_HIP_TRY(hipHostMalloc(&st.zero_probe_host, 2 * sizeof(unsigned long long), hipHostMallocDefault));
+            ASORA_HIP_TRY(hipEventCreateWithFlags(&st.zero_probe_done, hipEventDisableTiming));
+        }
+        if (st.zero_probe_pending && hipEventQuery(st.zero_probe_done) == hipSuccess) {
+            const double rated = (double)st.zero_probe_host[0], dark = (double)st.zero_probe_host[1];
+            st.zero_dark = rated > 0.0 && dark > 0.15 * rated;
+            st.zero_known = true;
+            st.zero_probe_pending = false;
+        }
+        (void)hipGetLastError();      // (hipErrorNotReady from the query is not an error)
+        st.zero_since_probe += 1;
+        probe = !st.zero_probe_pending && (!st.zero_known || st.zero_since_probe >= 64 || st.zero_dark);
+        skip_zero = probe || st.zero_dark;
+    }
+    return 0;
+}
+// behind a probe launch: its sums to the host
+static int launch_zero_probe_sum(State &st, hipStream_t stream)
+{
+    hipLaunchKernelGGL(zero_probe_sum_kernel, dim3(1), dim3(ZERO_PROBE_SLOTS), 0, stream,
+                       (const unsigned long long *)st.zero_probe_dev, st.zero_probe_host);
+    ASORA_HIP_TRY(hipGetLastError());
+    ASORA_HIP_TRY(hipEventRecord(st.zero_probe_done, stream));
+    st.zero_probe_pending = true;
+    st.zero_since_probe = 0;
+    return 0;
+}
+
+// Shells that outgrow LDS live in global memory: bound that scratch to ~2 GiB per launch (the reference's source batching,
+// raytracing.cu:126, reappears only for such traces).  batch: in, the sources left; out, those of this launch
+static int ensure_shell_scratch(State &st, int units, size_t shell_bytes, int &batch)
+{
+    const size_t per_src = (size_t)units * shell_bytes;
+    const size_t budget = (size_t)2 << 30;
+    int max_batch = (int)std::max<size_t>(8, (budget / per_src) / 8 * 8);
+    batch = std::min(batch, max_batch);
+    const size_t need = (size_t)8 * units * ((batch + 7) / 8) * shell_bytes;
+    if (need > st.shell_scratch_bytes) {
+        if (st.shell_scratch) ASORA_HIP_TRY(hipFree(st.shell_scratch));
+        st.shell_scratch = nullptr;
+        st.shell_scratch_bytes = 0;
+        ASORA_HIP_TRY(hipMalloc(&st.shell_scratch, need));
+        st.shell_scratch_bytes = need;
+    }
+    return 0;
+}
+
 // How the radius behaves from call to call (a call = one raytrace of the library's API, one time step of the evolve loop):
-// the eight-fold line-aligned tables only pay when they are reused (see launch_raytrace)
+// the eight-fold line-aligned tables only pay when they are reused (see plan_shape)
 bool note_call_radius(State &st, double R, int path)
 {
     // (one history per path -- 0: the whole-box ASORA trace and the evolve loop, 1: the sub-box sweep, whose R is R_max_LLS and
@@ -1137,41 +1021,29 @@ bool note_call_radius(State &st, double R, int path)
     return !h.has_changed || h.same_R_calls > 32;
 }
 
+// the options a plan reads, as asora_set_option left them
+void plan_options(const State &st, RtPlanInput &in)
+{
+    in.cu_count = st.cu_count;
+    in.sectors = st.opt[ASORA_OPT_SECTORS]; in.block_threads = st.opt[ASORA_OPT_BLOCK_THREADS]; in.pair_sources = st.opt[ASORA_OPT_PAIR_SOURCES];
+    in.aligned_rows = st.opt[ASORA_OPT_ALIGNED_ROWS]; in.global_atomics = st.opt[ASORA_OPT_GLOBAL_ATOMICS];
+    in.skip_zero_rates = st.opt[ASORA_OPT_SKIP_ZERO_RATES]; in.z_transposed_opt = st.opt[ASORA_OPT_Z_TRANSPOSED] != 0;
+}
+
 int launch_raytrace(State &st, RtParams &p, bool dump, bool heat, hipStream_t side)
 {
     // (per-source spectra: checked by the entry points already; here so that no launch can carry an unchecked index)
     if (p.src_spec) { if (int rc = check_source_spectra("raytrace")) return rc; }
-    const bool open = p.open_bc != 0;
-    if (int rc = check_open_boundaries(st, "raytrace", open, dump)) return rc;
-    int units, threads;   // one workgroup per (source, octant) or per (source, octant, sector)
-    pick_launch_shape(st, p.R, p.N, p.shape_src_count > 0 ? p.shape_src_count : p.src_count, dump, units, threads);
-    if (open) threads = threads <= 256 ? 256 : 512;         // the workgroup sizes the open forms are built for (launch_variant_open)
-    {   // number of shells, known before the tables are built: the 1024-entry LDS tables exist for 256/512 threads
-        const double R2hi = p.R * p.R * (1.0 + 1e-9) + 1e-9;
-        const int Emax = p.N / 2;
-        const int S_est = std::isfinite(R2hi) ? (int)std::min((double)Emax, std::floor(std::sqrt(R2hi))) : Emax;
-        if (S_est + 1 > 256 && threads < 256) threads = 256;
-    }
-    // rows cut at 64-byte lines (ASORA_OPT_ALIGNED_ROWS): units of one face, a mesh whose rows start on lines, the [k][j][i]
-    // twin for the z-faces, a source list whose positions the host knows (pairing), and eight times the tables.  By default
-    // where two sources share a workgroup (r < 52.5: -1.5 ... -4.7 %; beyond, with one source per workgroup and 0.13-0.2 GB of
-    // tables, nothing: profiles/r03_ab_aligned_rows.txt); on request up to r ~ 110
+    if (int rc = check_open_boundaries(st, "raytrace", p.open_bc != 0, dump)) return rc;
     const int32_t *host_pos = p.src_pos == st.src_pos_sorted ? st.src_pos_sorted_host.data()
                             : p.src_pos == st.src_pos ? st.src_pos_host.data() : nullptr;
-    // ... and, left to the library, a radius that stays: building eight forms costs eight times as long (12 ms instead of
-    // 2.5 at r = 30), which a run whose r_RT changes with every time step (R_max_LLS in cells under cosmological expansion,
-    // ref: c2ray_base.py:460; a dozen launches per step) would pay every step for 0.3 ms saved.  So: aligned from the first
-    // call on until the radius changes for the first time, afterwards only once a radius has served 32 calls in a row.
-    // Decided ONCE PER CALL (note_call_radius, from fill_rt_params), never per launch: every range of a pipelined or chunked
-    // call and every iteration of an evolve batch sees the same tables.
-    bool aligned = false;
-    {
-        const int want = st.opt[ASORA_OPT_ALIGNED_ROWS];
-        const double r = std::min(p.R, 0.87 * p.N);
-        const bool possible = (units == 6 || units == 12) && !dump && p.N % 8 == 0 && p.z_transposed && host_pos != nullptr && r <= 110.0;
-        aligned = possible && (want == 2 || (want == 0 && r < 52.5 && p.radius_stays));
-    }
-    if (int rc = ensure_geometry(st, p, threads, units, nullptr, aligned)) return rc;
+    RtPlanInput in{};
+    plan_options(st, in);
+    in.N = p.N; in.R = p.R; in.src_count = p.src_count; in.shape_src_count = p.shape_src_count;
+    in.grey = p.grey != 0; in.heat = heat; in.dump = dump; in.open = p.open_bc != 0; in.z_transposed = p.z_transposed != 0;
+    in.table_sets = p.src_spec != nullptr; in.host_positions = host_pos != nullptr; in.radius_stays = p.radius_stays != 0;
+    const RtShape sh = plan_shape(in);
+    if (int rc = ensure_geometry(st, p, sh.threads, sh.units, nullptr, sh.aligned)) return rc;
     st.last_variant = 0;
     p.lut_k1 = 0.30102999566398119521 / p.dlogtau;      // log10(2)/dlogtau
     p.lut_k0 = 1.0 - p.minlogtau / p.dlogtau;
@@ -1181,174 +1053,47 @@ int launch_raytrace(State &st, RtParams &p, bool dump, bool heat, hipStream_t si
     // ASORA_OPT_SKIP_ZERO_RATES: 0 = where it costs nothing (the buffer-atomic kernels drop such lanes' atomics), 1 = everywhere
     // (kernels without buffer atomics take the branching SKIP_ZERO variant), 2 = nowhere
     p.tau_zero = INFINITY;
-    const int skip_zero_opt = st.opt[ASORA_OPT_SKIP_ZERO_RATES];
-    if (skip_zero_opt != 2 && !p.grey && p.lut_k1 > 0.0) {
+    if (in.skip_zero_rates != 2 && !p.grey && p.lut_k1 > 0.0) {
         const double last = std::min(p.numtau_f, (double)(p.table_len - 1));
         p.tau_zero = std::exp2((last + 0.01 - p.lut_k0) / p.lut_k1);
     }
-
-    const size_t slots = ((size_t)p.max_cells + 2) & ~(size_t)1;   // max_cells + zero slot, rounded to even (16-B alignment)
-    // small tables (log table, 1/s, three wrapped-coordinate tables) at fixed capacity, then the shell buffers
-    const bool big_tables = p.S + 1 > 256;
-    const bool small_tables = !open && p.S + 1 <= 64 && threads <= 128;
-    if (p.S + 1 > 1024) return fail(4, "raytrace: more than 1023 shells (mesh too large for this build)");
-    size_t fixed_bytes = lds_table_bytes(big_tables ? 1024 : small_tables ? 64 : 256);
-    size_t shell_bytes = 2 * slots * sizeof(double);
-    const bool use_lds = shell_bytes + fixed_bytes <= LDS_LIMIT_BYTES;
-    bool split = false;
-    // (beyond N = 512: per-layout descriptors also for the single-source form with heating or grey opacity, round 6)
-    const bool bufatom_fits = buffer_atomics_fit(st, p, units, threads, use_lds && !dump && !big_tables, split);
-    p.split_desc = split ? 1 : 0;
-    // Two sources per workgroup (see the kernel's NSRC): the variant exists for table rates without heating, column-density
-    // dump or exact-zero skipping, with the shell buffers in LDS and the rates through buffer atomics, for 64..512 threads
-    // and the two smaller LDS table capacities
-    bool pairs = false;
-    {
-        const int want = st.opt[ASORA_OPT_PAIR_SOURCES];
-        const bool possible = use_lds && !dump && !heat && !p.grey && !big_tables && threads <= 512 &&
-                              bufatom_fits && p.src_count >= 2 &&
-                              2 * shell_bytes + lds_table_bytes(open ? 256 : (p.S + 1 <= 32 && threads == 256) ? 32 : (p.S + 1 <= 64 && threads <= 256) ? 64 : 256, 2) <= LDS_LIMIT_BYTES;
-        pairs = possible && (want == 2 || (want == 0 && pair_sources_pays(st, p.R, p.N, p.shape_src_count > 0 ? p.shape_src_count : p.src_count, units, threads)));
-    }
-    const bool pairs_small = !open && p.S + 1 <= 64 && threads <= 256;      // the paired variant has the 64-entry tables for 256 threads too
-    // ... and 32-entry ones for 256 threads: at r_RT = 30 the 1.75 KB they save are what separates two workgroups per CU from
-    // three (four shell buffers of 11.6 KB + tables: 53.9 KB against 52.2 KB; three per CU fit up to 53.3 KB; worth ~4 %)
-    const bool pairs_tiny = !open && p.S + 1 <= 32 && threads == 256;
-    if (pairs) {
-        fixed_bytes = lds_table_bytes(pairs_tiny ? 32 : pairs_small ? 64 : 256, 2);
-        shell_bytes *= 2;
-    }
-    const size_t lds_bytes = (use_lds ? shell_bytes : 0) + fixed_bytes;
+    in.tau_zero_finite = std::isfinite(p.tau_zero);
+    RtPlan plan{};
+    std::string why;
+    if (int rc = plan_launch(in, sh, p.S, p.max_cells, plan, why)) return fail(rc, why);
+    p.split_desc = plan.form.split ? 1 : 0;
     // launches that share the global shell scratch stay on the main stream (one at a time)
-    hipStream_t stream = (side && use_lds) ? side : st.stream;
-    if (side && !use_lds) {       // ... behind whatever the side streams still run, and the side streams behind it
+    hipStream_t stream = (side && plan.use_lds) ? side : st.stream;
+    if (side && !plan.use_lds) {       // ... behind whatever the side streams still run, and the side streams behind it
         for (int q = 0; q < 2; ++q)
             if (st.side_pending[q]) ASORA_HIP_TRY(hipStreamWaitEvent(st.stream, st.side_done[q], 0));
     }
-
-    // Exact-zero rates (ASORA_OPT_SKIP_ZERO_RATES, see the kernel's SKIP_ZERO).  The kernels that leave them out cost 5 % where
-    // there are none, and save up to a quarter of the launch where most cells lie beyond the table (the neutral medium of an
-    // early-reionisation run).  Left to the library (0) a launch takes them while the last PROBE found more than 15 % of the
-    // rated pairs dark; a probe is such a launch whose two sums go to pinned host memory behind it and are looked at, without
-    // waiting, by a later call: the first launch, every 64th after it, every launch while the dark variant runs anyway.
     bool skip_zero = false, probe = false;
-    {
-        // (open boundaries: the forms that add exact zeros only)
-        const bool exists = use_lds && !dump && !heat && !p.grey && std::isfinite(p.tau_zero) && bufatom_fits && !open;
-        if (exists && skip_zero_opt == 1) skip_zero = true;
-        else if (exists && skip_zero_opt == 0) {
-            if (!st.zero_probe_dev) {
-                ASORA_HIP_TRY(hipMalloc(&st.zero_probe_dev, 2 * ZERO_PROBE_SLOTS * sizeof(unsigned long long)));
-                ASORA_HIP_TRY(hipHostMalloc(&st.zero_probe_host, 2 * sizeof(unsigned long long), hipHostMallocDefault));
-                ASORA_HIP_TRY(hipEventCreateWithFlags(&st.zero_probe_done, hipEventDisableTiming));
-            }
-            if (st.zero_probe_pending && hipEventQuery(st.zero_probe_done) == hipSuccess) {
-                const double rated = (double)st.zero_probe_host[0], dark = (double)st.zero_probe_host[1];
-                st.zero_dark = rated > 0.0 && dark > 0.15 * rated;
-                st.zero_known = true;
-                st.zero_probe_pending = false;
-            }
-            (void)hipGetLastError();      // (hipErrorNotReady from the query is not an error)
-            st.zero_since_probe += 1;
-            probe = !st.zero_probe_pending && (!st.zero_known || st.zero_since_probe >= 64 || st.zero_dark);
-            skip_zero = probe || st.zero_dark;
-        }
-    }
+    if (int rc = decide_skip_zero(st, plan.zero_form_exists, skip_zero, probe)) return rc;
+    plan_skip_zero(plan, skip_zero);
+    const RtForm &form = plan.form;
 
     int done = 0;
     while (done < p.src_count) {
         int batch = p.src_count - done;
-        if (!use_lds) {
-            // bound the global shell scratch to ~2 GiB per launch (the reference's source batching,
-            // raytracing.cu:126, reappears only for traces whose shells outgrow LDS)
-            const size_t per_src = (size_t)units * shell_bytes;
-            const size_t budget = (size_t)2 << 30;
-            int max_batch = (int)std::max<size_t>(8, (budget / per_src) / 8 * 8);
-            batch = std::min(batch, max_batch);
-            const size_t need = (size_t)8 * units * ((batch + 7) / 8) * shell_bytes;
-            if (need > st.shell_scratch_bytes) {
-                if (st.shell_scratch) ASORA_HIP_TRY(hipFree(st.shell_scratch));
-                st.shell_scratch = nullptr;
-                st.shell_scratch_bytes = 0;
-                ASORA_HIP_TRY(hipMalloc(&st.shell_scratch, need));
-                st.shell_scratch_bytes = need;
-            }
-        }
+        if (!plan.use_lds) { if (int rc = ensure_shell_scratch(st, sh.units, plan.shell_bytes, batch)) return rc; }
         RtParams q = p;
         q.src_begin = p.src_begin + done;
         q.src_count = batch;
-        q.shell_scratch = use_lds ? nullptr : st.shell_scratch;
+        q.shell_scratch = plan.use_lds ? nullptr : st.shell_scratch;
         q.zero_probe = nullptr;
         if (probe && done == 0) {
             ASORA_HIP_TRY(hipMemsetAsync(st.zero_probe_dev, 0, 2 * ZERO_PROBE_SLOTS * sizeof(unsigned long long), stream));
             q.zero_probe = st.zero_probe_dev;
         }
-        int groups = pairs ? (batch + 1) / 2 : batch;              // workgroups per unit
-        if (pairs && aligned) {
-            const State::PairList *pl = nullptr;
-            if (int rc = source_pairs_by_class(st, host_pos, p.src_pos, q.src_begin, batch, pl)) return rc;
-            for (int ft = 0; ft < 2; ++ft) { q.pairs[ft] = pl->dev[ft]; q.npairs[ft] = pl->n[ft]; }
-            groups = std::max(pl->n[0], pl->n[1]);
-        }
-        q.spread = (long)groups * units <= 2L * st.cu_count ? 1 : 0;     // few workgroups: spread a source's units over the XCDs
-        const unsigned grid = q.spread ? (unsigned)units * (unsigned)groups : 8u * (unsigned)units * (unsigned)((groups + 7) / 8);
-        st.last_variant = (pairs ? ASORA_VARIANT_PAIRED : 0) | (aligned ? ASORA_VARIANT_ALIGNED : 0) |
-                          ((bufatom_fits && (use_lds || open) && !dump) ? ASORA_VARIANT_BUFFER_ATOMICS : 0) | (split ? ASORA_VARIANT_SPLIT_DESCRIPTORS : 0) |
-                          (open ? ASORA_VARIANT_OPEN_BOUNDARIES : 0) |
-                          (skip_zero ? ASORA_VARIANT_SKIP_ZERO : 0) | (use_lds ? 0 : ASORA_VARIANT_GLOBAL_SHELLS) | (units << 8) | (threads << 16);
+        unsigned grid = 0;
+        if (int rc = set_launch_grid(st, q, sh.units, form.nsrc == 2, sh.aligned, host_pos, grid)) return rc;
+        st.last_variant = variant_word(form, sh.units, sh.aligned);
         {
             KernelTimer kt(ASORA_KERNEL_RAYTRACE, stream);
-            int rc = 0;
-            if (open) {
-                if (!bufatom_fits || split) return fail(11, "raytrace: open boundaries without one buffer descriptor (internal error)");
-                if (big_tables) rc = threads == 512 ? launch_variant_open<512, 1024>(q, grid, lds_bytes, use_lds, heat, pairs, stream)
-                                                    : launch_variant_open<256, 1024>(q, grid, lds_bytes, use_lds, heat, pairs, stream);
-                else            rc = threads == 512 ? launch_variant_open<512, 256>(q, grid, lds_bytes, use_lds, heat, pairs, stream)
-                                                    : launch_variant_open<256, 256>(q, grid, lds_bytes, use_lds, heat, pairs, stream);
-            } else if (pairs && split) {         // 512 < N <= 645: sectors x 256 / 512 threads
-                if (pairs_tiny)          rc = launch_variant_pairs<256, 32, true>(st, q, grid, lds_bytes, stream, skip_zero);
-                else if (pairs_small)    rc = launch_variant_pairs<256, 64, true>(st, q, grid, lds_bytes, stream, skip_zero);
-                else if (threads == 512) rc = launch_variant_pairs<512, 256, true>(st, q, grid, lds_bytes, stream, skip_zero);
-                else                     rc = launch_variant_pairs<256, 256, true>(st, q, grid, lds_bytes, stream, skip_zero);
-            } else if (split) {
-                rc = threads == 512 ? launch_variant_split<512>(st, q, grid, lds_bytes, stream, skip_zero, heat)
-                                    : launch_variant_split<256>(st, q, grid, lds_bytes, stream, skip_zero, heat);
-            } else if (pairs) {
-                if (pairs_tiny) rc = launch_variant_pairs<256, 32>(st, q, grid, lds_bytes, stream, skip_zero);
-                else if (pairs_small) {
-                    if (threads == 64)       rc = launch_variant_pairs<64, 64>(st, q, grid, lds_bytes, stream, skip_zero);
-                    else if (threads == 128) rc = launch_variant_pairs<128, 64>(st, q, grid, lds_bytes, stream, skip_zero);
-                    else                     rc = launch_variant_pairs<256, 64>(st, q, grid, lds_bytes, stream, skip_zero);
-                } else switch (threads) {
-                    case 64:  rc = launch_variant_pairs<64, 256>(st, q, grid, lds_bytes, stream, skip_zero); break;
-                    case 128: rc = launch_variant_pairs<128, 256>(st, q, grid, lds_bytes, stream, skip_zero); break;
-                    case 512: rc = launch_variant_pairs<512, 256>(st, q, grid, lds_bytes, stream, skip_zero); break;
-                    default:  rc = launch_variant_pairs<256, 256>(st, q, grid, lds_bytes, stream, skip_zero); break;
-                }
-            } else if (big_tables) {
-                if (threads == 1024)     rc = launch_variant<1024, 1024>(st, q, grid, lds_bytes, use_lds, dump, heat, stream, skip_zero);
-                else if (threads == 512) rc = launch_variant<512, 1024>(st, q, grid, lds_bytes, use_lds, dump, heat, stream, skip_zero);
-                else                rc = launch_variant<256, 1024>(st, q, grid, lds_bytes, use_lds, dump, heat, stream, skip_zero);
-            } else if (small_tables) {
-                if (threads == 64) rc = launch_variant<64, 64>(st, q, grid, lds_bytes, use_lds, dump, heat, stream, skip_zero);
-                else               rc = launch_variant<128, 64>(st, q, grid, lds_bytes, use_lds, dump, heat, stream, skip_zero);
-            } else switch (threads) {
-                case 64:  rc = launch_variant<64, 256>(st, q, grid, lds_bytes, use_lds, dump, heat, stream, skip_zero); break;
-                case 128: rc = launch_variant<128, 256>(st, q, grid, lds_bytes, use_lds, dump, heat, stream, skip_zero); break;
-                case 512: rc = launch_variant<512, 256>(st, q, grid, lds_bytes, use_lds, dump, heat, stream, skip_zero); break;
-                case 1024: rc = launch_variant<1024, 256>(st, q, grid, lds_bytes, use_lds, dump, heat, stream, skip_zero); break;
-                default:  rc = launch_variant<256, 256>(st, q, grid, lds_bytes, use_lds, dump, heat, stream, skip_zero); break;
-            }
-            if (rc) return rc;
+            if (int rc = launch_form(form, q, grid, plan.lds_bytes, stream, ALL_FORMS)) return rc;
         }
-        if (q.zero_probe) {
-            hipLaunchKernelGGL(zero_probe_sum_kernel, dim3(1), dim3(ZERO_PROBE_SLOTS), 0, stream,
-                               (const unsigned long long *)st.zero_probe_dev, st.zero_probe_host);
-            ASORA_HIP_TRY(hipGetLastError());
-            ASORA_HIP_TRY(hipEventRecord(st.zero_probe_done, stream));
-            st.zero_probe_pending = true;
-            st.zero_since_probe = 0;
-        }
+        if (q.zero_probe) { if (int rc = launch_zero_probe_sum(st, stream)) return rc; }
         done += batch;
     }
     return 0;
@@ -1360,21 +1105,9 @@ int launch_raytrace(State &st, RtParams &p, bool dump, bool heat, hipStream_t si
 // that are rated or add to the photon loss; a source whose column densities go back to the caller needs the whole cube and
 // stays with the on-the-fly kernel of subbox.hip.
 // ---------------------------------------------------------------------------------------------
-template <int T, bool HT, int NS = 1>
-static int launch_subbox_tables_variant(const RtParams &q, unsigned grid, size_t lds_bytes, hipStream_t stream)
-{
-    ASORA_HIP_TRY(hipFuncSetAttribute((const void *)raytrace_octant_kernel<T, false, false, HT, 256, false, false, true, NS, true>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    hipLaunchKernelGGL((raytrace_octant_kernel<T, false, false, HT, 256, false, false, true, NS, true>), dim3(grid), dim3(T), lds_bytes,
-                       stream, q);
-    ASORA_HIP_TRY(hipGetLastError());
-    return 0;
-}
-
 int subbox_tables_prepare(State &st, RtParams &p, int ext_r, int ext_l, int subboxsize, int src_count, bool heat, SubboxTables &out,
                           const int32_t *host_pos)
 {
-    (void)heat;
     out = SubboxTables();
     out.host_pos = host_pos;
     const int want = st.opt[ASORA_OPT_SUBBOX_TABLES];
@@ -1387,18 +1120,16 @@ int subbox_tables_prepare(State &st, RtParams &p, int ext_r, int ext_l, int subb
     // auto: when the radius, not the range, bounds the work (else the tables would hold the whole cube), and not beyond
     // what a table of a few tens of MB covers
     if (want == 0 && !(S_tab < std::min(ext_r, ext_l) && S_tab <= 96)) return 0;
+    // the merged kinds of the ASORA sweep, in the workgroup sizes the sub-box forms are built for (256 and 512: the whole sphere
+    // below 11.5 takes 256), and the sector pairs x 512 beyond them
     int units, threads;
     const double r = (double)S_tab;
-    if (r < 15.5) { units = 1; threads = 256; }
-    else if (r < 21.5) { units = 1; threads = 512; }
-    else if (r < 23.5) { units = 2; threads = 256; }
-    else if (r < 25.5) { units = 2; threads = 512; }
-    else if (r < 36.5) { units = 6; threads = 256; }
-    else if (r < 52.5) { units = 12; threads = 256; }
-    else { units = 12; threads = 512; }
+    merged_kind(r, units, threads);
+    if (!units) { units = 12; threads = 512; }
+    threads = std::max(threads, 256);
     if (want == 0 && (long)src_count * units < 2L * st.cu_count) return 0;     // a handful of sources: subbox.hip's wide workgroups
     const SubboxGeometry sbg{ext_r, ext_l, subboxsize};
-    // Rows cut at 64-byte lines, as for the ASORA sweep (launch_raytrace): sectors of one face, a mesh whose rows start on
+    // Rows cut at 64-byte lines, as for the ASORA sweep (plan_shape): sectors of one face, a mesh whose rows start on
     // lines, positions the host knows.  ON REQUEST ONLY (ASORA_OPT_ALIGNED_ROWS = 2): measured on MI355X, 1000 sources, 256^3,
     // r_RT = 32 (profiles/r05_ab_subbox_aligned.jsonl), the aligned tables give this sweep nothing -- 1.136 / 1.151 ms aligned
     // against 1.139 / 1.143 ms packed with two sources per workgroup, 1.235 against 1.18 ms with one -- where they gave the
@@ -1412,10 +1143,9 @@ int subbox_tables_prepare(State &st, RtParams &p, int ext_r, int ext_l, int subb
     }
     if (int rc = ensure_geometry(st, p, threads, units, &sbg, aligned)) return rc;
     out.aligned = aligned;
-    const size_t slots = ((size_t)p.max_cells + 2) & ~(size_t)1;
-    if (2 * slots * sizeof(double) + lds_table_bytes(256) > LDS_LIMIT_BYTES) return 0;
+    if (form_lds_bytes(subbox_form(threads, heat, 1), p.max_cells) > LDS_LIMIT_BYTES) return 0;
     // one trailing shell per source and unit, within 2 GiB (82 KB per source at r_RT = 32: 26 000 sources per launch)
-    const size_t per_source = (size_t)units * slots * sizeof(double);
+    const size_t per_source = (size_t)units * shell_slots(p.max_cells) * sizeof(double);
     size_t trail_budget = (size_t)2 << 30;
     if (const char *e = getenv("ASORA_SUBBOX_TRAIL_BUDGET")) trail_budget = std::max<size_t>(per_source, (size_t)atoll(e));   // tests: force several batches
     const int max_batch = (int)std::max<size_t>(1, std::min<size_t>((size_t)src_count, trail_budget / per_source));
@@ -1433,8 +1163,8 @@ int subbox_tables_prepare(State &st, RtParams &p, int ext_r, int ext_l, int subb
     // heating (two more lookups per source in flight)
     {
         const int want = st.opt[ASORA_OPT_PAIR_SOURCES];
-        const bool possible = !heat && src_count >= 2 && 4 * slots * sizeof(double) + lds_table_bytes(256, 2) <= LDS_LIMIT_BYTES;
-        const bool pays = r >= 15.5 && (long)(src_count / 2) * units * (threads / 64) >= 8L * st.cu_count;
+        const bool possible = !heat && src_count >= 2 && form_lds_bytes(subbox_form(threads, false, 2), p.max_cells) <= LDS_LIMIT_BYTES;
+        const bool pays = r >= 15.5 && pairs_fill_chip(src_count, units, threads, st.cu_count);
         out.nsrc = (possible && (want == 2 || (want == 0 && pays))) ? 2 : 1;
     }
     return 0;
@@ -1454,27 +1184,14 @@ int subbox_tables_sweep(State &st, const RtParams &p, const SubboxTables &tab, i
     }
     if (!any) return 0;                       // the box lies beyond the radius: nothing is rated, nothing is lost
     q.sb_first = s_begin == 0 ? 1 : 0;
-    const size_t slots = ((size_t)p.max_cells + 2) & ~(size_t)1;
     const bool pairs = tab.nsrc == 2 && !heat;
-    const size_t lds_bytes = (pairs ? 4 : 2) * slots * sizeof(double) + lds_table_bytes(256, pairs ? 2 : 1);
-    int groups = pairs ? (q.src_count + 1) / 2 : q.src_count;
-    if (pairs && tab.aligned) {        // partners agree modulo 8 along the memory-contiguous axis of the unit's face
-        const State::PairList *pl = nullptr;
-        if (int rc = source_pairs_by_class(st, tab.host_pos, p.src_pos, q.src_begin, q.src_count, pl)) return rc;
-        for (int ft = 0; ft < 2; ++ft) { q.pairs[ft] = pl->dev[ft]; q.npairs[ft] = pl->n[ft]; }
-        groups = std::max(pl->n[0], pl->n[1]);
-    }
-    q.spread = (long)groups * tab.units <= 2L * st.cu_count ? 1 : 0;
-    const unsigned grid = q.spread ? (unsigned)tab.units * (unsigned)groups : 8u * (unsigned)tab.units * (unsigned)((groups + 7) / 8);
-    st.last_variant = (pairs ? ASORA_VARIANT_PAIRED : 0) | (tab.aligned ? ASORA_VARIANT_ALIGNED : 0) | ASORA_VARIANT_BUFFER_ATOMICS |
-                      (tab.units << 8) | (tab.threads << 16);
+    const RtForm form = subbox_form(tab.threads, heat, pairs ? 2 : 1);
+    unsigned grid = 0;
+    if (int rc = set_launch_grid(st, q, tab.units, pairs, tab.aligned, tab.host_pos, grid)) return rc;
+    st.last_variant = variant_word(form, tab.units, tab.aligned);
     KernelTimer kt(ASORA_KERNEL_RAYTRACE);
-    if (pairs) return tab.threads == 512 ? launch_subbox_tables_variant<512, false, 2>(q, grid, lds_bytes, st.stream)
-                                         : launch_subbox_tables_variant<256, false, 2>(q, grid, lds_bytes, st.stream);
-    if (tab.threads == 512) return heat ? launch_subbox_tables_variant<512, true>(q, grid, lds_bytes, st.stream)
-                                        : launch_subbox_tables_variant<512, false>(q, grid, lds_bytes, st.stream);
-    return heat ? launch_subbox_tables_variant<256, true>(q, grid, lds_bytes, st.stream)
-                : launch_subbox_tables_variant<256, false>(q, grid, lds_bytes, st.stream);
+    return launch_form(form, q, grid, form_lds_bytes(form, p.max_cells), st.stream, ALL_FORMS);
 }
 
 } // namespace asora
+

@@ -446,6 +446,40 @@ int asora_last_raytrace_counts_ex(long long *gamma_cells, long long *evaluated_c
 
 int asora_last_raytrace_variant(void) { return state().last_variant; }
 
+int asora_debug_launch_plan(int N, double R, int src_count, int shape_src_count, int cu_count, int flags, int shells, int max_cells,
+                            int32_t *out)
+{
+    clear_error();
+    if (N < 1 || src_count < 1 || !out || (shells >= 0 && max_cells < 0)) return fail(3, "debug_launch_plan: bad arguments");
+    const State &st = state();
+    RtPlanInput in{};
+    plan_options(st, in);
+    if (cu_count > 0) in.cu_count = cu_count;
+    in.N = N; in.R = R; in.src_count = src_count; in.shape_src_count = shape_src_count;
+    // as fill_rt_params reads them when a call begins
+    in.grey = st.opt[ASORA_OPT_GREY_NOTABLES] != 0; in.open = st.opt[ASORA_OPT_OPEN_BOUNDARIES] != 0; in.z_transposed = in.z_transposed_opt;
+    in.heat = flags & ASORA_PLAN_HEAT; in.dump = flags & ASORA_PLAN_DUMP; in.table_sets = flags & ASORA_PLAN_TABLE_SETS;
+    in.host_positions = flags & ASORA_PLAN_HOST_POSITIONS; in.radius_stays = flags & ASORA_PLAN_RADIUS_STAYS;
+    in.tau_zero_finite = (flags & ASORA_PLAN_RATE_TABLES) && in.skip_zero_rates != 2 && !in.grey;      // launch_raytrace: p.tau_zero
+    for (int k = 0; k < ASORA_PLAN_WORDS; ++k) out[k] = 0;
+    if (in.open) {
+        const std::string why = open_boundaries_refusal(N, in.grey, in.global_atomics != 0, in.dump);
+        if (!why.empty()) return fail(4, "raytrace: open boundaries (ASORA_OPT_OPEN_BOUNDARIES) " + why);
+    }
+    const RtShape sh = plan_shape(in);
+    out[0] = sh.units; out[1] = sh.threads; out[2] = sh.aligned;
+    if (shells < 0) return 0;
+    RtPlan plan{};
+    std::string why;
+    if (int rc = plan_launch(in, sh, shells, max_cells, plan, why)) return fail(rc, why);
+    plan_skip_zero(plan, plan.zero_form_exists && in.skip_zero_rates == 1);     // (left to the library, 0, the probes decide: not planned)
+    const RtForm &f = plan.form;
+    form_values(f, out + 3);
+    out[16] = plan.use_lds; out[17] = (int32_t)plan.lds_bytes; out[18] = variant_word(f, sh.units, sh.aligned);
+    out[19] = form_is_built(f); out[20] = plan.zero_form_exists; out[21] = 1;
+    return 0;
+}
+
 int asora_debug_coldens(double R, double sig, double dr, int source_index, double *coldens_out, int N)
 {
     clear_error();

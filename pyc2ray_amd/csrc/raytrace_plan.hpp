@@ -1,0 +1,358 @@
+// raytrace_plan.hpp -- what a raytrace launch is going to be, decided by pure host functions: no HIP, no State.
+//   stage 1 (plan_shape), before the geometry tables exist: workgroups per source, threads per workgroup, aligned rows;
+//   stage 2 (plan_launch), from stage 1 and the tables' shell count and largest shell: the kernel form (RtForm, one field per
+//   template parameter of raytrace_octant_kernel), LDS, and the ASORA_VARIANT_* word;
+//   RT_FORMS: the forms that are built.  raytrace.hip instantiates exactly these rows and launches the row equal to the plan.
+// raytrace.hip feeds them from State and RtParams, asora_debug_launch_plan from its arguments (tests/test_launch_forms_host.py).
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <string>
+
+#include "../../include/asora_hip.h"
+
+namespace asora {
+
+// One field per template parameter of raytrace_octant_kernel, in its order
+struct RtForm {
+    int threads; bool global_scratch, dump, heat; int tabcap; bool skip_zero, grey, bufatom; int nsrc; bool subbox, split, spec, open;
+};
+constexpr bool operator==(const RtForm &a, const RtForm &b)
+{
+    return a.threads == b.threads && a.global_scratch == b.global_scratch && a.dump == b.dump && a.heat == b.heat && a.tabcap == b.tabcap &&
+           a.skip_zero == b.skip_zero && a.grey == b.grey && a.bufatom == b.bufatom && a.nsrc == b.nsrc && a.subbox == b.subbox &&
+           a.split == b.split && a.spec == b.spec && a.open == b.open;
+}
+inline void form_values(const RtForm &f, int v[13])
+{
+    const int a[13] = {f.threads, f.global_scratch, f.dump, f.heat, f.tabcap, f.skip_zero, f.grey, f.bufatom, f.nsrc, f.subbox, f.split, f.spec, f.open};
+    std::copy(a, a + 13, v);
+}
+inline std::string form_text(const RtForm &f)      // the template arguments, as DESIGN.md writes them
+{
+    int v[13];
+    form_values(f, v);
+    std::string s = "<";
+    for (int k = 0; k < 13; ++k) s += (k ? "," : "") + std::to_string(v[k]);
+    return s + ">";
+}
+
+// The forms that are built, family by family (kind: 0 table rates, 1 the same without the exact zeros, 2 with heating, 3 grey
+// opacity); the kernel's static_asserts check every row.
+constexpr int RT_FORM_COUNT = 182;
+struct RtFormTable { RtForm row[RT_FORM_COUNT]; int n; };
+constexpr RtFormTable make_form_table()
+{
+    RtFormTable t{};
+    constexpr bool f = false, y = true;
+    // single source, THREADS x TABCAP: 256-entry tables at every size, 64-entry ones for small workgroups, 1024-entry ones for large.
+    // Buffer atomics; global atomics (N > 512, option; the exact zeros left out by a branch) with the shells in LDS or, without a
+    // zero-skipping form, in global memory
+    constexpr int single[10][2] = {{64, 256}, {128, 256}, {256, 256}, {512, 256}, {1024, 256}, {64, 64}, {128, 64}, {256, 1024}, {512, 1024}, {1024, 1024}};
+    for (const auto &s : single)
+        for (int gs = 0; gs < 2; ++gs)
+            for (int ba = 0; ba < 2; ++ba)
+                for (int kind = 0; kind < 4; ++kind)
+                    if (!(gs && (ba || kind == 1))) t.row[t.n++] = RtForm{s[0], gs != 0, f, kind == 2, s[1], kind == 1, kind == 3, ba != 0, 1, f, f, y, f};
+    // column-density dump: 256 threads (pick_launch_shape), shells in LDS or global memory, table or grey opacity
+    for (int cap : {256, 1024})
+        for (int gs = 0; gs < 2; ++gs)
+            for (int gr = 0; gr < 2; ++gr) t.row[t.n++] = RtForm{256, gs != 0, y, f, cap, f, gr != 0, f, 1, f, f, y, f};
+    // two sources per workgroup (production): with and without the exact zeros
+    constexpr int paired[8][2] = {{64, 256}, {128, 256}, {256, 256}, {512, 256}, {64, 64}, {128, 64}, {256, 64}, {256, 32}};
+    for (const auto &s : paired)
+        for (int sz = 0; sz < 2; ++sz) t.row[t.n++] = RtForm{s[0], f, f, f, s[1], sz != 0, f, y, 2, f, f, y, f};
+    // descriptors per layout (512 < N <= 645), paired: also without per-source table sets (see the kernel's SPEC)
+    constexpr int paired_split[4][2] = {{256, 32}, {256, 64}, {256, 256}, {512, 256}};
+    for (const auto &s : paired_split)
+        for (int sz = 0; sz < 2; ++sz)
+            for (int sp = 0; sp < 2; ++sp) t.row[t.n++] = RtForm{s[0], f, f, f, s[1], sz != 0, f, y, 2, f, y, sp != 0, f};
+    for (int th : {256, 512}) {
+        // ... and single, every kind
+        for (int kind = 0; kind < 4; ++kind) t.row[t.n++] = RtForm{th, f, f, kind == 2, 256, kind == 1, kind == 3, y, 1, f, y, y, f};
+        // open boundaries: paired with the 256-entry tables; single with or without heating, shells in LDS or global memory
+        t.row[t.n++] = RtForm{th, f, f, f, 256, f, f, y, 2, f, f, y, y};
+        for (int cap : {256, 1024})
+            for (int gs = 0; gs < 2; ++gs)
+                for (int ht = 0; ht < 2; ++ht) t.row[t.n++] = RtForm{th, gs != 0, f, ht != 0, cap, f, f, y, 1, f, f, y, y};
+        // sub-box sweep: one source with or without heating, two without
+        for (int k = 0; k < 3; ++k) t.row[t.n++] = RtForm{th, f, f, k == 1, 256, f, f, y, k == 2 ? 2 : 1, y, f, y, f};
+    }
+    return t;
+}
+constexpr RtFormTable RT_FORMS = make_form_table();
+static_assert(RT_FORMS.n == RT_FORM_COUNT, "RT_FORM_COUNT is the number of rows make_form_table writes");
+inline bool form_is_built(const RtForm &f) { return std::find(RT_FORMS.row, RT_FORMS.row + RT_FORM_COUNT, f) != RT_FORMS.row + RT_FORM_COUNT; }
+
+// What the decisions read
+struct RtPlanInput {
+    int N;
+    double R;
+    int src_count, shape_src_count;   // sources of this launch; sources the launch shape is chosen for (the whole call's, not a pipelined range's)
+    int cu_count;
+    int sectors, block_threads, pair_sources, aligned_rows, global_atomics, skip_zero_rates;   // options as they stood when the call began
+    bool z_transposed_opt;            // ASORA_OPT_Z_TRANSPOSED itself; z_transposed: what the launch's grids have
+    bool grey, heat, dump, open, z_transposed;
+    bool table_sets;                  // per-source table sets are attached (RtParams::src_spec)
+    bool host_positions;              // the host knows the positions of the source list (pairing by alignment class)
+    bool radius_stays;                // note_call_radius
+    bool tau_zero_finite;             // an optical depth exists beyond which rates are exactly 0 (RtParams::tau_zero)
+};
+
+constexpr size_t LDS_LIMIT_BYTES = 160 * 1024;
+constexpr size_t LDS_LOG_TABLE_BYTES = 256 * 2 * sizeof(double);     // LOG_TABLE_SIZE x double2 (rates_device.hpp)
+constexpr size_t lds_table_bytes(int tabcap, int nsrc = 1) { return LDS_LOG_TABLE_BYTES + (size_t)tabcap * (sizeof(double) + (size_t)nsrc * 6 * sizeof(int)); }
+constexpr size_t shell_slots(int max_cells) { return ((size_t)max_cells + 2) & ~(size_t)1; }   // a shell buffer: max_cells + zero slot, rounded to even (16-B alignment)
+constexpr size_t shell_pair_bytes(int max_cells) { return 2 * shell_slots(max_cells) * sizeof(double); }   // the two shell buffers of one source
+
+// Decomposition and workgroup size.  Shells of a small trace do not fill 256 lanes (R=16: <= 310 cells per
+// octant shell); a large one needs so much LDS per octant that few workgroups fit a CU.  Three things pull:
+//   * padding: every shell of every unit is padded to whole waves, so FEWER, LARGER units waste fewer lanes (R = 16:
+//     1.41 lane-steps per rated cell with 8 octants, 1.04 with the whole sphere in one workgroup; R = 32: 1.17 with 12
+//     sector pairs, 1.10 with 6 sectors whose transverse axes are both mirrored), and units that cover both signs of an
+//     axis do not evaluate the plane between them twice;
+//   * the rate atomics want long contiguous rows: units that mirror the memory-contiguous axis of a face sweep full
+//     chords of the sphere (~15 % fewer 64-B atomic requests per rated cell than octants);
+//   * LDS: a unit's two shell buffers must leave room for enough workgroups per CU, which is what stops the merging --
+//     the whole sphere needs 39 KB at R = 16 and 157 KB at R = 32.
+// Thresholds from sweeps on MI355X (1000 sources, 256^3; tools/sweep_units.sh, profiles/r03_sweep_units_run*.txt):
+//   R < 11.5: whole sphere x 128 threads | < 15.5: x 256 | < 21.5: x 512 | < 23.5: half spheres x 256 | < 25.5: x 512 |
+//   < 36.5: 6 sectors by sign of the dominant offset x 256 | < 52.5: 12 mirrored sector pairs x 256 | else x 512
+// (round 2, without the merged kinds: R <= 12 octant pairs x 64 | 13..14 x 128 | 15..19 octants x 64 | 20..22 sector pairs
+//  x 64 | 23..28 octant pairs x 256 | 29..35 sector pairs x 128 | 36..54 x 256 | >= 55 x 512 -- still what is used when the
+//  merged kinds would leave CUs without a workgroup)
+// the merged kinds by radius (mu = 0 beyond them); the sub-box sweep takes its shape from the same table
+inline void merged_kind(double r, int &mu, int &mt)
+{
+    mu = 0; mt = 0;
+    if (r < 11.5) { mu = 1; mt = 128; }
+    else if (r < 15.5) { mu = 1; mt = 256; }
+    else if (r < 21.5) { mu = 1; mt = 512; }
+    else if (r < 23.5) { mu = 2; mt = 256; }
+    else if (r < 25.5) { mu = 2; mt = 512; }
+    else if (r < 36.5) { mu = 6; mt = 256; }
+    else if (r < 52.5) { mu = 12; mt = 256; }
+}
+inline void pick_launch_shape(const RtPlanInput &in, int &units, int &threads)
+{
+    const double R = in.R;
+    const int N = in.N, src_count = in.shape_src_count > 0 ? in.shape_src_count : in.src_count;
+    const bool dump = in.dump;
+    const double r = std::min(R, 0.87 * N);                 // the window cuts the trace at ~sqrt(3)/2 N
+    const double est_cells = 1.2 * r * r;                   // largest shell of an octant
+    if (r <= 12.5) { units = 4; threads = 64; }             // pairs of whole octants mirrored in x
+    else if (r <= 14.5) { units = 4; threads = 128; }
+    else if (est_cells <= 450.0) { units = 8; threads = 64; }        // r <= 19.4
+    else if (r <= 22.5) { units = 12; threads = 64; }
+    else if (r <= 28.5) { units = 4; threads = 256; }
+    else if (est_cells <= 1500.0) { units = 12; threads = 128; }     // r <= 35.3
+    else if (est_cells <= 3500.0) { units = 12; threads = 256; }     // r <= 54
+    else { units = 12; threads = 512; }
+    {   // the merged kinds, when they still give every CU a couple of workgroups
+        int mu = 0, mt = 0;
+        merged_kind(r, mu, mt);
+        if (mu && (long)src_count * mu >= 2L * in.cu_count && !dump) { units = mu; threads = mt; }
+        // Beyond N = 512 a buffer descriptor spans ONE layout of the rate grid (buffer_atomics_fit, `split`), so the production forms --
+        // two sources per workgroup, buffer atomics -- need units whose rated cells all lie on one kind of face.  Where the radius
+        // would take the whole sphere or the half spheres (cells of every face in one workgroup: the global-atomic family, one
+        // source per workgroup), the three all-sign sectors take their place (round 6; the reference's meshes end at 645,
+        // ref: src/asora/raytracing.cu:95).  Measured at N = 576, 1000 sources (profiles/r06_ab_576_small_radii.txt): r_RT = 16
+        // 0.286 -> 0.241 ms, r_RT = 24 0.605 -> 0.589 ms; below the radius from which two sources share a workgroup (15.5) the
+        // whole sphere stays (r_RT = 12: 0.137 against 0.140 ms).
+        if ((units == 1 || units == 2) && units == mu && r >= 15.5 && N > 512 && N <= 645 && (long)src_count * 3 >= 2L * in.cu_count &&
+            !in.global_atomics && in.z_transposed_opt) {
+            units = 3;
+            threads = r < 21.5 ? 256 : 512;
+        }
+    }
+    // Few sources (fewer workgroups than CUs): the time of the call is the time of ONE workgroup, so cut a source
+    // into more (24 sectors) and wider pieces.  One source, 128^3, R = 64: 0.235 -> 0.146 ms (tools/sweep_single_source.sh)
+    // A few dozen sources (workgroups for half the CUs' slots at most): still one round, wider workgroups finish it sooner
+    // (64 sources, R = 32: pairs x 256 threads 0.183 ms against 0.202 with 128; tools/sweep_mid_counts.sh)
+    if ((long)src_count * 12 <= (long)in.cu_count * 4 && units == 12 && threads == 128) threads = 256;
+    if ((long)src_count * 12 < (long)in.cu_count) {
+        units = 24;
+        if (est_cells > 900.0) threads = std::max(threads, 512);
+        if (est_cells > 2500.0) threads = 1024;
+    }
+    // A handful of sources: 24 workgroups each still leave most CUs idle -- quarter the sectors (96 per source; each wedge
+    // re-derives the inner part of its sector, so evaluations double, time about halves)
+    // (measured, one source: 128^3 whole box 0.205 -> 0.157 ms, R = 32 0.051 -> 0.043 ms; the floor is the chain of shells,
+    //  ~2 us each, not the work: tools/sweep_single_source.sh)
+    if ((long)src_count * 48 <= (long)in.cu_count) {
+        units = 96;
+        threads = est_cells > 6000.0 ? 1024 : est_cells > 2500.0 ? 512 : 256;
+    }
+    const int want_sectors = in.sectors;
+    if (want_sectors == 1) units = 8;
+    if (want_sectors == 2) units = 24;
+    if (want_sectors == 3) units = 12;
+    if (want_sectors == 4) units = 96;
+    if (want_sectors == 5) units = 4;
+    if (want_sectors == 6) units = 1;
+    if (want_sectors == 7) units = 2;
+    if (want_sectors == 8) units = 3;
+    if (want_sectors == 9) units = 6;
+    const int forced = in.block_threads;
+    if (forced == 64 || forced == 128 || forced == 256 || forced == 512 || forced == 1024) threads = forced;
+    if (dump) threads = 256;                                // the column-density dump variant is built for 256 only
+}
+
+// Enough waves must be left to fill the chip (two per SIMD) when two sources share a workgroup
+inline bool pairs_fill_chip(int src_count, int units, int threads, int cu_count)
+{
+    return (long)(src_count / 2) * units * (threads / 64) >= 8L * cu_count;
+}
+// Does sweeping two sources per workgroup pay?  (auto mode of ASORA_OPT_PAIR_SOURCES; from A/B runs on MI355X, 1000 sources,
+// 256^3: profiles/r03_ab_two_sources.txt -- R = 16 -4 %, 20 -2 %, 26 -10 %, 28 -12 %, 32 -7 %, 40 -8 %, 48 -5 %, 56 and 64 0 %;
+// nothing below R ~ 15, where the whole sphere is swept by few waves)
+inline bool pair_sources_pays(const RtPlanInput &in, int units, int threads)
+{
+    const double r = std::min(in.R, 0.87 * in.N);
+    if (!(r >= 15.5 && r < 52.5)) return false;
+    return pairs_fill_chip(in.shape_src_count > 0 ? in.shape_src_count : in.src_count, units, threads, in.cu_count);
+}
+
+// Can the rate atomics go through buffer descriptors (the kernel's BUFATOM)?  One descriptor over both layouts of the rate
+// grid while the pair fits 2 GiB (N <= 512); one per layout (split) up to 2 GiB per layout (N <= 645) for units whose rated
+// cells all lie on one face -- the sector kinds.
+// The split form is built for the shapes such meshes take at ordinary radii: 256 or 512 threads, up to 256 shells; two sources
+// per workgroup for table rates without heating, one source per workgroup also with heating or grey opacity (everything else
+// beyond N = 512 -- column-density dump, more than 256 shells, whole spheres below r = 15.5 -- keeps the global-atomic family).
+inline bool buffer_atomics_fit(const RtPlanInput &in, int units, int threads, bool plain_tables, bool &split)
+{
+    const unsigned long long ncell = (unsigned long long)in.N * in.N * in.N;
+    split = false;
+    if (in.global_atomics) return false;
+    if (16ull * ncell <= 0x80000000ull) return true;
+    const bool one_face = units == 3 || units == 6 || units == 12 || units == 24 || units == 96;
+    if (8ull * ncell <= 0x80000000ull && one_face && in.z_transposed && (threads == 256 || threads == 512) && plain_tables) { split = true; return true; }
+    return false;
+}
+
+// What open boundaries are not built for (check_open_boundaries, code 4): the reason, or "" when the launch may go on
+inline std::string open_boundaries_refusal(int N, bool grey_rates, bool global_atomics, bool dump)
+{
+    if (16ull * N * N * N > 0x80000000ull) return "are built for N <= 512 (mesh of " + std::to_string(N) + ")";
+    if (grey_rates) return "need table rates (grey opacity, ASORA_OPT_GREY_NOTABLES, is on)";
+    if (global_atomics) return "need the buffer-atomic kernels (ASORA_OPT_GLOBAL_ATOMICS is on)";
+    if (dump) return "have no column-density dump";
+    return "";
+}
+
+// Stage 1: before the geometry tables are built
+struct RtShape { int units, threads; bool aligned; };   // one workgroup per (source, octant) or per (source, octant, sector)
+inline RtShape plan_shape(const RtPlanInput &in)
+{
+    RtShape sh{0, 0, false};
+    int &units = sh.units, &threads = sh.threads;
+    pick_launch_shape(in, units, threads);
+    if (in.open) threads = threads <= 256 ? 256 : 512;      // the workgroup sizes the open forms are built for (RT_FORMS)
+    {   // number of shells, known before the tables are built: the 1024-entry LDS tables exist for 256/512 threads
+        const double R2hi = in.R * in.R * (1.0 + 1e-9) + 1e-9;
+        const int Emax = in.N / 2;
+        const int S_est = std::isfinite(R2hi) ? (int)std::min((double)Emax, std::floor(std::sqrt(R2hi))) : Emax;
+        if (S_est + 1 > 256 && threads < 256) threads = 256;
+    }
+    // rows cut at 64-byte lines (ASORA_OPT_ALIGNED_ROWS): units of one face, a mesh whose rows start on lines, the [k][j][i]
+    // twin for the z-faces, a source list whose positions the host knows (pairing), and eight times the tables.  By default
+    // where two sources share a workgroup (r < 52.5: -1.5 ... -4.7 %; beyond, with one source per workgroup and 0.13-0.2 GB of
+    // tables, nothing: profiles/r03_ab_aligned_rows.txt); on request up to r ~ 110
+    // ... and, left to the library, a radius that stays: building eight forms costs eight times as long (12 ms instead of
+    // 2.5 at r = 30), which a run whose r_RT changes with every time step (R_max_LLS in cells under cosmological expansion,
+    // ref: c2ray_base.py:460; a dozen launches per step) would pay every step for 0.3 ms saved.  So: aligned from the first
+    // call on until the radius changes for the first time, afterwards only once a radius has served 32 calls in a row.
+    // Decided ONCE PER CALL (note_call_radius, from fill_rt_params), never per launch: every range of a pipelined or chunked
+    // call and every iteration of an evolve batch sees the same tables.
+    {
+        const int want = in.aligned_rows;
+        const double r = std::min(in.R, 0.87 * in.N);
+        const bool possible = (units == 6 || units == 12) && !in.dump && in.N % 8 == 0 && in.z_transposed && in.host_positions && r <= 110.0;
+        sh.aligned = possible && (want == 2 || (want == 0 && r < 52.5 && in.radius_stays));
+    }
+    return sh;
+}
+
+// Stage 2: from stage 1 and the tables' S (last shell) and max_cells (largest shell)
+struct RtPlan {
+    RtForm form;               // skip_zero: the branching form only; what decide_skip_zero decides goes in through plan_skip_zero
+    bool use_lds;              // the shell buffers fit LDS (else global memory, one launch at a time)
+    bool zero_form_exists;     // a form that drops exact zeros at no cost exists for this launch
+    size_t lds_bytes;
+    size_t shell_bytes;        // per source: its two shell buffers
+};
+
+// The ASORA_VARIANT_* word of a launch.  (SKIP_ZERO reports the forms that drop the zeros' atomics; the branching form under
+// global atomics has never been reported.)
+inline int variant_word(const RtForm &f, int units, bool aligned)
+{
+    return (f.nsrc == 2 ? ASORA_VARIANT_PAIRED : 0) | (aligned ? ASORA_VARIANT_ALIGNED : 0) |
+           (f.bufatom ? ASORA_VARIANT_BUFFER_ATOMICS : 0) | (f.split ? ASORA_VARIANT_SPLIT_DESCRIPTORS : 0) |
+           (f.open ? ASORA_VARIANT_OPEN_BOUNDARIES : 0) |
+           ((f.skip_zero && f.bufatom) ? ASORA_VARIANT_SKIP_ZERO : 0) | (f.global_scratch ? ASORA_VARIANT_GLOBAL_SHELLS : 0) | (units << 8) | (f.threads << 16);
+}
+// the sub-box sweep's form: table rates through buffer atomics, 256-entry tables, shells in LDS
+constexpr RtForm subbox_form(int threads, bool heat, int nsrc) { return RtForm{threads, false, false, heat, 256, false, false, true, nsrc, true, false, true, false}; }
+inline size_t form_lds_bytes(const RtForm &f, int max_cells)
+{
+    return (f.global_scratch ? 0 : (size_t)f.nsrc * shell_pair_bytes(max_cells)) + lds_table_bytes(f.tabcap, f.nsrc);
+}
+// workgroups of a launch: `groups` per unit; few of them are spread, a source's units over the XCDs (RtParams::spread)
+inline unsigned launch_grid(int groups, int units, int cu_count, int &spread)
+{
+    spread = (long)groups * units <= 2L * cu_count ? 1 : 0;
+    return spread ? (unsigned)units * (unsigned)groups : 8u * (unsigned)units * (unsigned)((groups + 7) / 8);
+}
+
+// returns 0, or the launcher's error code with its message in `why`
+inline int plan_launch(const RtPlanInput &in, const RtShape &sh, int S, int max_cells, RtPlan &out, std::string &why)
+{
+    const int units = sh.units, threads = sh.threads;
+    const bool open = in.open, dump = in.dump, heat = in.heat, grey = in.grey;
+    // small tables (log table, 1/s, three wrapped-coordinate tables) at fixed capacity, then the shell buffers
+    const bool big_tables = S + 1 > 256;
+    const bool small_tables = !open && S + 1 <= 64 && threads <= 128;
+    if (S + 1 > 1024) { why = "raytrace: more than 1023 shells (mesh too large for this build)"; return 4; }
+    const size_t fixed_bytes = lds_table_bytes(big_tables ? 1024 : small_tables ? 64 : 256);
+    const size_t shell_bytes = shell_pair_bytes(max_cells);
+    const bool use_lds = shell_bytes + fixed_bytes <= LDS_LIMIT_BYTES;
+    bool split = false;
+    // (beyond N = 512: per-layout descriptors also for the single-source form with heating or grey opacity, round 6)
+    const bool bufatom_fits = buffer_atomics_fit(in, units, threads, use_lds && !dump && !big_tables, split);
+    // Two sources per workgroup (see the kernel's NSRC): the variant exists for table rates without heating, column-density
+    // dump or exact-zero skipping, with the shell buffers in LDS and the rates through buffer atomics, for 64..512 threads
+    // and the two smaller LDS table capacities
+    bool pairs = false;
+    {
+        const int want = in.pair_sources;
+        const bool possible = use_lds && !dump && !heat && !grey && !big_tables && threads <= 512 &&
+                              bufatom_fits && in.src_count >= 2 &&
+                              2 * shell_bytes + lds_table_bytes(open ? 256 : (S + 1 <= 32 && threads == 256) ? 32 : (S + 1 <= 64 && threads <= 256) ? 64 : 256, 2) <= LDS_LIMIT_BYTES;
+        pairs = possible && (want == 2 || (want == 0 && pair_sources_pays(in, units, threads)));
+    }
+    const bool pairs_small = !open && S + 1 <= 64 && threads <= 256;      // the paired variant has the 64-entry tables for 256 threads too
+    // ... and 32-entry ones for 256 threads: at r_RT = 30 the 1.75 KB they save are what separates two workgroups per CU from
+    // three (four shell buffers of 11.6 KB + tables: 53.9 KB against 52.2 KB; three per CU fit up to 53.3 KB; worth ~4 %)
+    const bool pairs_tiny = !open && S + 1 <= 32 && threads == 256;
+
+    const int tabcap = pairs ? (pairs_tiny ? 32 : pairs_small ? 64 : 256) : big_tables ? 1024 : small_tables ? 64 : 256;
+    // rate atomics through buffer descriptors (see the kernel's BUFATOM): decided here, once
+    const bool bufatom = bufatom_fits && (use_lds || open) && !dump;
+    // ASORA_OPT_SKIP_ZERO_RATES = 1 where the buffer-atomic kernel (which drops exact zeros by itself) is not available: the
+    // branching variant that leaves them out
+    const bool branching = use_lds && !bufatom && !dump && !grey && !heat && in.tau_zero_finite && in.skip_zero_rates == 1;
+    // (the grey and the dump forms have no heating; SPLIT without table sets per source: the form that does not read them -- see the kernel's SPEC)
+    const RtForm &f = out.form = RtForm{threads, !use_lds, dump, heat && !grey && !dump, tabcap, branching, grey, bufatom, pairs ? 2 : 1, false, split,
+                                        !(pairs && split && !in.table_sets), open};
+    out.use_lds = use_lds;
+    // (open boundaries: the forms that add exact zeros only)
+    out.zero_form_exists = use_lds && !dump && !heat && !grey && in.tau_zero_finite && bufatom_fits && !open;
+    out.shell_bytes = shell_bytes;
+    out.lds_bytes = form_lds_bytes(f, max_cells);
+    return 0;
+}
+// what decide_skip_zero decided for a launch whose zero_form_exists
+inline void plan_skip_zero(RtPlan &plan, bool skip_zero) { if (skip_zero) plan.form.skip_zero = true; }
+
+} // namespace asora

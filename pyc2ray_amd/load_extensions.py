@@ -538,21 +538,48 @@ class _LibAsora:
     def last_raytrace_variant(self):
         """{"paired", "aligned", "buffer_atomics", "split_descriptors", "skip_zero", "global_shells", "open": bool, "units", "threads"} of the
         last raytrace launch (asora_last_raytrace_variant)."""
-        v = self._lib.asora_last_raytrace_variant()
+        return self.variant_fields(self._lib.asora_last_raytrace_variant())
+
+    @staticmethod
+    def variant_fields(v):
+        """The fields of an ASORA_VARIANT_* word (last_raytrace_variant, launch_plan)."""
         return {"paired": bool(v & 1), "aligned": bool(v & 2), "buffer_atomics": bool(v & 4), "split_descriptors": bool(v & 8),
                 "skip_zero": bool(v & 16), "global_shells": bool(v & 32), "open": bool(v & _capi.VARIANT_OPEN_BOUNDARIES), "units": (v >> 8) & 255, "threads": v >> 16}
+
+    FORM_FIELDS = ("threads", "global_scratch", "dump", "heat", "tabcap", "skip_zero", "grey", "bufatom", "nsrc", "subbox", "split",
+                   "spec", "open")
+
+    def launch_plan(self, N, R, src_count, shape_src_count=0, cu_count=0, shells=-1, max_cells=0, heat=False, dump=False,
+                    table_sets=False, host_positions=True, radius_stays=True, rate_tables=True):
+        """What a raytrace launch would be under the options as they stand (asora_debug_launch_plan; host only, no device needed):
+        {"units", "threads", "aligned"}, and with `shells` >= 0 also "form" (the kernel's template arguments by name), "use_lds",
+        "lds_bytes", "variant" (the word of asora_last_raytrace_variant), "built", "zero_form_exists".  A combination the launcher
+        refuses raises RuntimeError with its code and message."""
+        flags = ((_capi.PLAN_HEAT if heat else 0) | (_capi.PLAN_DUMP if dump else 0) | (_capi.PLAN_TABLE_SETS if table_sets else 0) |
+                 (_capi.PLAN_HOST_POSITIONS if host_positions else 0) | (_capi.PLAN_RADIUS_STAYS if radius_stays else 0) |
+                 (_capi.PLAN_RATE_TABLES if rate_tables else 0))
+        out = np.zeros(_capi.PLAN_WORDS, dtype=np.int32)
+        _capi.check(self._lib.asora_debug_launch_plan(int(N), float(R), int(src_count), int(shape_src_count), int(cu_count), flags,
+                                                      int(shells), int(max_cells), _capi.iptr(out)), "launch_plan")
+        plan = {"units": int(out[0]), "threads": int(out[1]), "aligned": bool(out[2])}
+        if out[21]:
+            form = {k: int(v) if k in ("threads", "tabcap", "nsrc") else bool(v) for k, v in zip(self.FORM_FIELDS, out[3:16])}
+            plan.update(form=form, use_lds=bool(out[16]), lds_bytes=int(out[17]), variant=int(out[18]), built=bool(out[19]),
+                        zero_form_exists=bool(out[20]))
+        return plan
 
     def debug_geometry_bytes(self):
         """Device memory of the current geometry tables (shared parts once)."""
         return int(self._lib.asora_debug_geometry_bytes())
 
-    def debug_geometry_tables(self):
-        """The geometry tables of the last raytrace launch: (list of (entries x 8) uint32 arrays, dict(nsteps, shells, max_cells, threads))."""
+    def debug_geometry_tables(self, counts_only=False):
+        """The geometry tables of the last raytrace launch: (list of (entries x 8) uint32 arrays, dict(nsteps, shells, max_cells, threads));
+        counts_only: no table is copied, the list and nsteps stay empty."""
         n, ns, nt, sh, mc, th = C.c_size_t(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
         _capi.check(self._lib.asora_debug_geometry_table(-1, None, 0, C.byref(n), C.byref(ns), C.byref(nt), C.byref(sh), C.byref(mc),
                                                          C.byref(th)), "debug_geometry_table")
         tables, steps = [], []
-        for t in range(nt.value):
+        for t in range(0 if counts_only else nt.value):
             _capi.check(self._lib.asora_debug_geometry_table(t, None, 0, C.byref(n), C.byref(ns), C.byref(nt), C.byref(sh), C.byref(mc),
                                                              C.byref(th)), "debug_geometry_table")
             a = np.zeros((n.value, 8), dtype=np.uint32)

@@ -3,7 +3,7 @@ zero-flux-filler check").
 
 The forms a real run takes -- the whole sphere x 128 / 256 / 512 threads, half spheres, six sectors, twelve sector pairs, two
 sources per workgroup, line-aligned tables -- are chosen by `pick_launch_shape`, `pair_sources_pays` and the aligned-rows rule of
-`launch_raytrace` (csrc/raytrace.hip) from the radius and from the NUMBER of uploaded sources, about 1000 of them, which the oracle
+`plan_shape` (csrc/raytrace_plan.hpp) from the radius and from the NUMBER of uploaded sources, about 1000 of them, which the oracle
 cannot trace in seconds.  So a case uploads NS sources of which K are bright and NS - K have flux exactly 0.0: the library culls
 nothing on upload, the launch shape is that of NS sources, every rate of a filler is flux / (vol nHI) x (...) = +0 wherever
 nHI > 0, and the reference is the oracle over the K bright sources alone.

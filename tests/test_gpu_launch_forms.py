@@ -111,6 +111,18 @@ def test_production_form_against_the_oracle(asora, name, mode):
     tag = f"{name} {mode}"
     print(f"{tag}: variant {v}")
     assert v == want, f"{tag}: the library took {v}, the table expects {want}"
+    # the host-only window on the launcher's plan (asora_debug_launch_plan), fed this launch's own shell count and largest shell
+    # under the options it ran with: the word of the launch that ran, every bit of it, and a form that is built
+    ran, geo = lib.last_raytrace_variant(), lib.debug_geometry_tables(counts_only=True)[1]
+    try:
+        for k, x in opts.items():
+            lib.set_option(getattr(capi, k), x)
+        plan = lib.launch_plan(N, case.R, case.NS, shells=geo["shells"], max_cells=geo["max_cells"], heat=mode == "heat",
+                               table_sets=mode == "spectra")
+    finally:
+        for k in opts:
+            lib.set_option(getattr(capi, k), 0)
+    assert lib.variant_fields(plan["variant"]) == ran and plan["built"] and plan["form"]["threads"] == geo["threads"], f"{tag}: {plan}, ran {ran}"
     _against_oracle(phi, ref["phi_ion"], tag + " phi_ion")
     if mode == "heat":
         _against_oracle(heat, ref["phi_heat"], tag + " phi_heat")

@@ -1,6 +1,8 @@
 """CPU: what tests/test_gpu_launch_forms.py rests on (tests/launch_forms.py) -- the case table against a restatement of the
 dispatcher's rules, the six properties of every upload list against a numpy restatement of the library's sort and against the
-library's own, the oracle's indifference to zero-flux sources, and the media."""
+library's own, the oracle's indifference to zero-flux sources, and the media.  Then the launcher's own plan, which
+asora_debug_launch_plan returns without a device: against that restatement, at the edges of its second stage, and enumerated over
+the options against the table of built forms."""
 import numpy as np
 import pytest
 
@@ -206,3 +208,193 @@ def test_open_trace_by_source_equals_open_trace_where_both_apply():
                                  NumTau=thin.shape[0] - 1, flags=O.ASORA_MODE)["phi_ion"]
     w = far != 0
     np.testing.assert_allclose(far[w], per[w], rtol=1e-13, atol=0)
+
+
+# ---- the launcher's own plan (asora_debug_launch_plan: csrc/raytrace_plan.hpp without a device) -----------------------------------
+PLAN_OPTIONS = ("OPT_SECTORS", "OPT_BLOCK_THREADS", "OPT_PAIR_SOURCES", "OPT_ALIGNED_ROWS", "OPT_GLOBAL_ATOMICS", "OPT_SKIP_ZERO_RATES",
+                "OPT_GREY_NOTABLES", "OPT_OPEN_BOUNDARIES")
+LDS_LIMIT = 160 * 1024
+
+
+@pytest.fixture
+def plan(lib):
+    """plan(N, R, NS, ..., **options): lib.launch_plan on 256 compute units under the named options, which go back to 0 afterwards."""
+    from pyc2ray_amd import _capi
+
+    def call(N, R, NS, shells=-1, max_cells=0, **kw):
+        opts = {k: kw.pop(k) for k in list(kw) if k.startswith("OPT_")}
+        assert set(opts) <= set(PLAN_OPTIONS)
+        for k in PLAN_OPTIONS:
+            lib.set_option(getattr(_capi, k), opts.get(k, 0))
+        return lib.launch_plan(N, R, NS, cu_count=LF.CU_COUNT, shells=shells, max_cells=max_cells, **kw)
+
+    yield call
+    for k in PLAN_OPTIONS:
+        lib.set_option(getattr(_capi, k), 0)
+
+
+def _refused(plan, code, *a, **kw):
+    with pytest.raises(RuntimeError, match=rf"\(code {code}\)") as e:
+        plan(*a, **kw)
+    return str(e.value)
+
+
+def _shells(N, R):
+    return min(int(np.floor(R)), N // 2)
+
+
+def _lds(max_cells, tabcap, nsrc):
+    """Dynamic LDS of a form with its shells in LDS (the kernel's layout: log table, 1/s, 6 wrapped-coordinate tables and two shell
+    buffers per source)."""
+    return nsrc * 2 * ((max_cells + 2) & ~1) * 8 + 256 * 16 + tabcap * (8 + nsrc * 6 * 4)
+
+
+def _largest_that_fits(tabcap, nsrc):
+    mc = (LDS_LIMIT - 256 * 16 - tabcap * (8 + nsrc * 24)) // (16 * nsrc)
+    while _lds(mc + 1, tabcap, nsrc) <= LDS_LIMIT:
+        mc += 1
+    while _lds(mc, tabcap, nsrc) > LDS_LIMIT:
+        mc -= 1
+    return mc
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_plan_of_the_sixteen_cases_is_the_table(lib, plan, name):
+    """Stage 1 against expected_shape, the variant word against expected_variant, in every mode; the planned form is built."""
+    c = LF.CASES[name]
+    units, threads, paired, aligned = LF.expected_shape(c.N, c.NS, c.R)
+    for mode in ("tables", "heat", "spectra", "open"):
+        kw = {"heat": mode == "heat", "table_sets": mode == "spectra", "OPT_OPEN_BOUNDARIES": int(mode == "open"),
+              "OPT_SKIP_ZERO_RATES": 0 if mode in ("heat", "open") else 2}
+        want_threads = threads if mode != "open" else 256 if threads <= 256 else 512      # the sizes the open forms are built for
+        s1 = plan(c.N, c.R, c.NS, **kw)
+        assert (s1["units"], s1["threads"], s1["aligned"]) == (units, want_threads, aligned), (name, mode)
+        s2 = plan(c.N, c.R, c.NS, shells=_shells(c.N, c.R), max_cells=1000, **kw)
+        got = {k: v for k, v in lib.variant_fields(s2["variant"]).items() if k != "skip_zero"}
+        assert got == LF.expected_variant(c, mode), (name, mode)
+        assert s2["built"] and s2["use_lds"] and s2["form"]["threads"] == want_threads, (name, mode)
+        assert s2["form"]["nsrc"] == (2 if got["paired"] else 1) and s2["form"]["heat"] == (mode == "heat") and s2["form"]["open"] == (mode == "open")
+        if mode == "tables":
+            assert paired == got["paired"], name
+
+
+def test_plan_shape_sweep_against_expected_shape(plan):
+    """No forced option, N <= 512, first radius: every threshold of pick_launch_shape and pair_sources_pays from either side."""
+    radii = (11.5, 12.5, 14.5, 15.5, np.sqrt(450 / 1.2), 21.5, 22.5, 23.5, 25.5, 28.5, 35.3, 36.5, 52.5, np.sqrt(3500 / 1.2))
+    radii = sorted({x for r in radii for x in (np.nextafter(r, 0), r, np.nextafter(r, 1e9), r - 0.25, r + 0.25)} | {1000.0})
+    n = 0
+    for N in (33, 48, 64, 96, 128, 256, 512):
+        for NS in (1, 3, 5, 20, 21, 64, 85, 100, 1000, 1001):
+            for R in radii:
+                units, threads, paired, aligned = LF.expected_shape(N, NS, R)
+                if _shells(N, R) + 1 > 256:
+                    threads = max(threads, 256)           # more than 256 shells: the 1024-entry LDS tables, 256 threads at least
+                s2 = plan(N, R, NS, shells=_shells(N, R), max_cells=1000)
+                assert (s2["units"], s2["threads"], s2["aligned"]) == (units, threads, aligned), (N, NS, R)
+                # stage 2 on top: expected_shape's pairing rule, where a paired form exists (up to 512 threads and 256 shells)
+                assert (s2["form"]["nsrc"] == 2) == (paired and threads <= 512 and _shells(N, R) + 1 <= 256), (N, NS, R)
+                assert s2["built"], (N, NS, R, s2["form"])
+                n += 1
+    assert n == 7 * 10 * len(radii)
+
+
+def test_plan_stage_two_edges(lib, plan):
+    from pyc2ray_amd import _capi
+    N, R, NS = 256, 30.0, 1000                                          # six sectors x 256 threads
+    # LDS table capacities by the number of shells: paired, single x 256, single x 128
+    for shells1, paired_cap, single_cap, small_cap in ((32, 32, 256, 64), (33, 64, 256, 64), (64, 64, 256, 64), (65, 256, 256, 256), (256, 256, 256, 256),
+                                                       (257, None, 1024, None), (1024, None, 1024, None)):
+        a = plan(N, R, NS, shells=shells1 - 1, max_cells=1000, OPT_PAIR_SOURCES=2)
+        b = plan(N, R, NS, shells=shells1 - 1, max_cells=1000, OPT_PAIR_SOURCES=1)
+        assert a["built"] and b["built"]
+        assert (a["form"]["nsrc"], a["form"]["tabcap"]) == ((2, paired_cap) if paired_cap else (1, 1024)), shells1
+        assert (b["form"]["nsrc"], b["form"]["tabcap"], b["form"]["threads"]) == (1, single_cap, 256), shells1
+        assert a["lds_bytes"] == _lds(1000, a["form"]["tabcap"], a["form"]["nsrc"]) and b["lds_bytes"] == _lds(1000, single_cap, 1)
+        if small_cap:
+            s = plan(N, R, NS, shells=shells1 - 1, max_cells=1000, OPT_BLOCK_THREADS=128, OPT_PAIR_SOURCES=1)
+            assert s["built"] and (s["form"]["threads"], s["form"]["tabcap"]) == (128, small_cap), shells1
+    assert "more than 1023 shells" in _refused(plan, 4, N, R, NS, shells=1024, max_cells=1000)
+    # the LDS limit: the shells of a single source leave LDS, the four shell buffers of a pair leave it first
+    mc = _largest_that_fits(256, 1)
+    assert _lds(mc, 256, 1) <= LDS_LIMIT < _lds(mc + 1, 256, 1)
+    fits, over = (plan(N, R, NS, shells=40, max_cells=m, OPT_PAIR_SOURCES=1) for m in (mc, mc + 1))
+    assert fits["use_lds"] and not fits["form"]["global_scratch"] and fits["form"]["bufatom"] and fits["lds_bytes"] == _lds(mc, 256, 1)
+    assert not over["use_lds"] and over["form"]["global_scratch"] and not over["form"]["bufatom"] and over["built"]
+    assert over["lds_bytes"] == 256 * 16 + 256 * 32 and lib.variant_fields(over["variant"])["global_shells"]
+    mc2 = _largest_that_fits(256, 2)
+    assert mc2 < mc
+    two, one = (plan(N, R, NS, shells=80, max_cells=m, OPT_PAIR_SOURCES=2) for m in (mc2, mc2 + 1))
+    assert two["form"]["nsrc"] == 2 and two["lds_bytes"] == _lds(mc2, 256, 2) <= LDS_LIMIT
+    assert one["form"]["nsrc"] == 1 and one["use_lds"] and one["built"] and not lib.variant_fields(one["variant"])["paired"]
+    # one descriptor, one per layout, global atomics
+    for n, split, bufatom in ((512, False, True), (520, True, True), (645, True, True), (648, False, False)):
+        q = plan(n, R, NS, shells=30, max_cells=1000)
+        assert (q["form"]["split"], q["form"]["bufatom"], q["built"]) == (split, bufatom, True), n
+        v = lib.variant_fields(q["variant"])
+        assert (v["split_descriptors"], v["buffer_atomics"], v["paired"]) == (split, bufatom, bufatom), n
+    # per-source table sets: the paired split family alone has a form without them
+    for n in (512, 520):
+        for sets in (False, True):
+            q = plan(n, R, NS, shells=30, max_cells=1000, table_sets=sets)
+            assert q["form"]["nsrc"] == 2 and q["form"]["spec"] == (sets or n == 512) and q["built"], (n, sets)
+    assert plan(520, R, NS, shells=30, max_cells=1000, heat=True)["form"]["spec"]
+    # what open boundaries are not built for
+    assert "N <= 512" in _refused(plan, 4, 520, R, NS, OPT_OPEN_BOUNDARIES=1)
+    assert "table rates" in _refused(plan, 4, N, R, NS, OPT_OPEN_BOUNDARIES=1, OPT_GREY_NOTABLES=1)
+    assert "buffer-atomic" in _refused(plan, 4, N, R, NS, OPT_OPEN_BOUNDARIES=1, OPT_GLOBAL_ATOMICS=1)
+    assert "dump" in _refused(plan, 4, N, R, NS, OPT_OPEN_BOUNDARIES=1, dump=True)
+    # heating, grey opacity and the dump each end pairing and zero-skipping
+    base = plan(N, R, NS, shells=30, max_cells=1000, OPT_PAIR_SOURCES=2, OPT_SKIP_ZERO_RATES=1)
+    assert base["form"]["nsrc"] == 2 and base["form"]["skip_zero"] and base["zero_form_exists"] and base["variant"] & _capi.VARIANT_SKIP_ZERO
+    for kw in ({"heat": True}, {"OPT_GREY_NOTABLES": 1}, {"dump": True}):
+        q = plan(N, R, NS, shells=30, max_cells=1000, OPT_PAIR_SOURCES=2, OPT_SKIP_ZERO_RATES=1, **kw)
+        assert q["form"]["nsrc"] == 1 and not q["form"]["skip_zero"] and not q["zero_form_exists"] and q["built"], kw
+        assert not q["variant"] & (_capi.VARIANT_SKIP_ZERO | _capi.VARIANT_PAIRED), kw
+        assert (q["form"]["heat"], q["form"]["grey"], q["form"]["dump"]) == ("heat" in kw, "OPT_GREY_NOTABLES" in kw, "dump" in kw)
+    assert plan(N, R, NS, shells=30, max_cells=1000, dump=True)["threads"] == 256
+    assert not plan(N, R, NS, shells=30, max_cells=1000, OPT_SKIP_ZERO_RATES=2)["zero_form_exists"]
+    # ASORA_OPT_SKIP_ZERO_RATES = 1 without buffer atomics: the branching form, which the variant word does not report
+    q = plan(N, R, NS, shells=30, max_cells=1000, OPT_GLOBAL_ATOMICS=1, OPT_SKIP_ZERO_RATES=1)
+    assert q["form"]["skip_zero"] and not q["form"]["bufatom"] and q["form"]["nsrc"] == 1 and q["built"] and not q["zero_form_exists"]
+    assert not q["variant"] & (_capi.VARIANT_SKIP_ZERO | _capi.VARIANT_BUFFER_ATOMICS)
+    assert not plan(N, R, NS, shells=30, max_cells=1000, OPT_GLOBAL_ATOMICS=1)["form"]["skip_zero"]
+
+
+def test_every_plan_is_refused_or_built(plan):
+    """The dispatcher's soundness: over the options that shape a launch, the modes and meshes on every side of the descriptor rules,
+    radii of every launch shape and shells inside and outside LDS, a call is refused with a message or plans a form of the table.
+    The product of the options, the modes and the meshes is complete; what is thinned is what each combination is run with: four of
+    the eight radii (one per launch-shape regime of pick_launch_shape, one beyond the box), each with shells inside LDS and outside,
+    one of three source counts and of three ASORA_OPT_SKIP_ZERO_RATES, going round with a running count."""
+    modes = ({}, {"heat": True}, {"OPT_GREY_NOTABLES": 1}, {"dump": True}, {"OPT_OPEN_BOUNDARIES": 1}, {"OPT_OPEN_BOUNDARIES": 1, "heat": True})
+    radii = (8.0, 13.0, 18.0, 24.5, 30.0, 41.0, 56.0, 1000.0)
+    planned = refused = k = 0
+    seen, ran = set(), set()
+    for sectors in range(10):
+        for threads in (0, 64, 128, 256, 512, 1024):
+            for pair in (0, 1, 2):
+                for rows in (0, 1, 2):
+                    for ga in (0, 1):
+                        k += 1
+                        for m, mode in enumerate(modes):
+                            for N in (64, 512, 576):
+                                for j in range(8):
+                                    R, max_cells, NS = radii[(k + 2 * (j // 2)) % 8], (500, 12000)[j % 2], (1000, 3, 64)[(k // 16) % 3]
+                                    ran.add((m, N, R, max_cells))
+                                    try:
+                                        q = plan(N, R, NS, shells=_shells(N, R), max_cells=max_cells, table_sets=bool((k // 2) % 2),
+                                                 OPT_SECTORS=sectors, OPT_BLOCK_THREADS=threads, OPT_PAIR_SOURCES=pair, OPT_ALIGNED_ROWS=rows,
+                                                 OPT_GLOBAL_ATOMICS=ga, OPT_SKIP_ZERO_RATES=(k // 48) % 3, **mode)
+                                    except RuntimeError as e:
+                                        assert "open boundaries" in str(e) and "(code 4)" in str(e) and m >= 4 and (N == 576 or ga), str(e)
+                                        refused += 1
+                                        continue
+                                    assert not (m >= 4 and (N == 576 or ga))
+                                    assert q["built"], (sectors, threads, pair, rows, ga, N, R, NS, max_cells, mode, q["form"])
+                                    assert q["use_lds"] == (max_cells == 500)
+                                    planned += 1
+                                    seen.add(tuple(q["form"].values()))
+    print(f"{planned} planned, {refused} refused, {len(seen)} distinct forms, {len(ran)} of {6 * 3 * 8 * 2} (mode, N, R, shells) run")
+    total = 8 * 10 * 6 * 3 * 3 * 2 * 6 * 3
+    assert planned + refused == total and refused == total // 3 * 4 // 6          # the two open modes, on N = 576 or under global atomics
+    assert len(ran) == 6 * 3 * 8 * 2
