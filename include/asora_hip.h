@@ -658,6 +658,16 @@ enum { ASORA_PLAN_HEAT = 1, ASORA_PLAN_DUMP = 2, ASORA_PLAN_TABLE_SETS = 4, ASOR
 int asora_debug_launch_plan(int N, double R, int src_count, int shape_src_count, int cu_count, int flags, int shells, int max_cells,
                             int32_t *out);
 
+/* Which workgroup sweeps what in a raytrace launch that is not spread, from the launcher's own functions (block_order,
+ * pyc2ray_amd/csrc/raytrace_plan.hpp): host only, no device needed.  pos0: 0-based xyz-interleaved positions of a source list; the
+ * launch is of `count` sources from `begin`, `units` workgroups per source, nsrc = 1 or 2 sources per workgroup, line-aligned tables
+ * or not.  Block b sweeps out[4 b ... 4 b + 3] = {group, unit, first source, second source or -1}, all -1 for a block that does
+ * nothing; blocks b & 7 = x run on XCD x in the order of b.  *grid = the blocks of the launch; where capacity (in blocks) is less,
+ * nothing is written.  cu_count <= 0: the device's, 256 before asora_device_init; a launch so small that it is spread instead
+ * (<= 2 cu_count workgroups) has no order: *grid = 0. */
+int asora_debug_block_order(const int32_t *pos0, int begin, int count, int units, int nsrc, int aligned, int cu_count, int32_t *out,
+                            size_t capacity, int *grid);
+
 /* The geometry tables the last raytrace launch used (tests: device-built against host-built tables).  *ntables = tables of the
  * launch shape (units x 8 when line-aligned); for 0 <= table < *ntables: `words` receives 8 uint32 per entry (the 16-byte
  * cell-A and cell-B records, raytrace.hip) for up to capacity_entries entries, *entries the table's entry count, *nsteps its

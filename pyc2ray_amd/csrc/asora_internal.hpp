@@ -105,6 +105,8 @@ struct RtParams {
     // ---- per-source spectra (asora_spectra_to_device; appended, so the fields above keep their offsets) ----
     const int32_t *src_spec;    // table set of each source, indexed like src_pos / src_flux; nullptr: every source set 0
     unsigned spec_stride;       // double2 entries from one set's [thick | thin | heat thick | heat thin] block to the next
+    // ---- dispatch order (block_order, raytrace_plan.hpp) ----
+    const int2 *order;          // block b sweeps {group, unit} = order[b], {-1, -1}: nothing; nullptr: the arithmetic map of the prologue
     // ---- open boundaries (ASORA_OPT_OPEN_BOUNDARIES as it stood when the call began; read by the launcher, not by the kernels) ----
     int open_bc;
     // ---- plane-parallel flux (asora_plane_flux as it stood when the call began; read by launch_plane_flux, not by the kernels above) ----
@@ -196,8 +198,12 @@ struct State {
     // host copies of the two source lists (as uploaded, and in lexicographic order of the position) and, for the paired-sources
     // variant on aligned tables, who shares a workgroup with whom: built once per (list, range), see source_pairs_by_class
     std::vector<int32_t> src_pos_host, src_pos_sorted_host;
-    struct PairList { const void *list; int begin, count; int2 *dev[2]; int n[2]; };
+    struct PairList { const void *list; int begin, count; int2 *dev[2]; int n[2]; std::vector<int> cls[2]; };   // cls: the class of each pair
     std::vector<PairList> pair_lists;      // (a sharded or chunked trace asks for the same few ranges every iteration)
+    // ... and which (group, unit) every block of such a launch sweeps (block_order, raytrace_plan.hpp): built once per (list, range,
+    // launch shape), released with the pair lists
+    struct OrderList { const void *list; int begin, count, units, aligned, nsrc; int2 *dev; unsigned grid; };
+    std::vector<OrderList> order_lists;
     int geom_units = 0;
     double2 *logtab_dev = nullptr;          // log2 table (ensure_logtab), lives until the runtime is torn down
     bool geom_valid = false;

@@ -253,14 +253,24 @@ __global__ void __launch_bounds__(RT_THREADS, 1) raytrace_octant_kernel(const Rt
     // p.spread (a handful of sources): consecutive blocks are the units of ONE source, i.e. they go to different XCDs --
     // with the grouping above a single source would keep all its workgroups on one XCD's 32 CUs.
     int src_local, unit;      // src_local: index of the group of NSRC sources this workgroup sweeps
-    if (p.spread) {
-        src_local = blk / p.units;
-        unit = blk % p.units;
+    // p.order (whole-list and sub-range traces that are not spread): the host has dealt the workgroups table-major per XCD
+    // (block_order, raytrace_plan.hpp) -- the workgroups resident on an XCD then stream one or two geometry tables, which stay in
+    // its L2, instead of one table each.  One scalar load; padding at the lanes' ends does nothing.
+    if (p.order) {
+        const int2 e = p.order[blk];
+        if (e.x < 0) return;
+        src_local = e.x;
+        unit = e.y;
     } else {
-        src_local = (blk & 7) + 8 * (blk / (8 * p.units));
-        unit = (blk >> 3) % p.units;
+        if (p.spread) {
+            src_local = blk / p.units;
+            unit = blk % p.units;
+        } else {
+            src_local = (blk & 7) + 8 * (blk / (8 * p.units));
+            unit = (blk >> 3) % p.units;
+        }
+        unit = p.units - 1 - unit;   // sector units: z (most cells) first, x (fewest) last in dispatch order
     }
-    unit = p.units - 1 - unit;   // sector units: z (most cells) first, x (fewest) last in dispatch order
     const int uinfo = p.geom[unit].info;           // sign bits of the unit | merged axes << 3 | rates-source << 6 | (face + 1) << 8
     // p.aligned: the unit's tables come in eight forms, by the source's position modulo 8 along the memory-contiguous axis of
     // the unit's face; the two sources of a workgroup agree in it (the host paired them so: p.pairs)
@@ -879,14 +889,14 @@ int check_open_boundaries(const State &st, const char *who, bool open, bool dump
     return why.empty() ? 0 : fail(4, std::string(who) + ": open boundaries (ASORA_OPT_OPEN_BOUNDARIES) " + why);
 }
 
-// Who shares a workgroup with whom when the tables are the aligned kind (build_unit_geometry, align_class): two sources
-// that agree modulo 8 in k (units of the x- and y-sector: list 0) or in i (units of the z-sector: list 1).  The list is walked
-// in its order -- position-sorted for a whole-list call -- and a source waits for the next one of its class, so partners are
-// neighbours in the list, hence in space; what is left over at the end sweeps alone.
+// Who shares a workgroup with whom when the tables are the aligned kind (pairs_by_class, raytrace_plan.hpp), and the dispatch
+// orders: cached on the device per (list, range), dropped with every change of the source lists
 void release_pair_lists(State &st)
 {
     for (auto &e : st.pair_lists) for (int ft = 0; ft < 2; ++ft) if (e.dev[ft]) (void)hipFree(e.dev[ft]);
     st.pair_lists.clear();
+    for (auto &e : st.order_lists) if (e.dev) (void)hipFree(e.dev);
+    st.order_lists.clear();
 }
 
 static int source_pairs_by_class(State &st, const int32_t *host_pos, const void *list, int begin, int count, const State::PairList *&out)
@@ -895,17 +905,10 @@ static int source_pairs_by_class(State &st, const int32_t *host_pos, const void 
         if (e.list == list && e.begin == begin && e.count == count) { out = &e; return 0; }
     if (st.pair_lists.size() >= 64) release_pair_lists(st);
     State::PairList e{list, begin, count, {nullptr, nullptr}, {0, 0}};
+    static_assert(sizeof(SrcPair) == sizeof(int2), "the kernel reads a pair as int2");
     for (int ft = 0; ft < 2; ++ft) {
-        const int axis = ft ? 0 : 2;
-        std::vector<int2> pairs;
-        pairs.reserve((size_t)count / 2 + 8);
-        int open[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
-        for (int s = begin; s < begin + count; ++s) {
-            const int c = host_pos[3 * (size_t)s + axis] & 7;
-            if (open[c] < 0) open[c] = s;
-            else { pairs.push_back(int2{open[c], s}); open[c] = -1; }
-        }
-        for (int c = 0; c < 8; ++c) if (open[c] >= 0) pairs.push_back(int2{open[c], -1});
+        std::vector<SrcPair> pairs;
+        pairs_by_class(host_pos, begin, count, ft, pairs, e.cls[ft]);
         e.n[ft] = (int)pairs.size();
         ASORA_HIP_TRY(hipMalloc(&e.dev[ft], std::max<size_t>(1, pairs.size()) * sizeof(int2)));
         ASORA_HIP_TRY(hipMemcpy(e.dev[ft], pairs.data(), pairs.size() * sizeof(int2), hipMemcpyHostToDevice));
@@ -917,16 +920,49 @@ static int source_pairs_by_class(State &st, const int32_t *host_pos, const void 
 
 // The workgroups of a launch of q.src_count sources from q.src_begin: per unit one for every source or every two, by the
 // class lists where the tables are aligned; q.spread and the grid from their number
-static int set_launch_grid(State &st, RtParams &q, int units, bool pairs, bool aligned, const int32_t *host_pos, unsigned &grid)
+// `ordered`: a launch that is not spread takes its blocks from a dispatch order (block_order, raytrace_plan.hpp; the kernel's
+// p.order), built once per (list, range, shape) like the pair lists; else, and for the few workgroups of a spread launch, the
+// arithmetic map of the kernel's prologue
+static int set_launch_grid(State &st, RtParams &q, int units, bool pairs, bool aligned, const int32_t *host_pos, bool ordered, unsigned &grid)
 {
     int groups = pairs ? (q.src_count + 1) / 2 : q.src_count;              // workgroups per unit
+    const State::PairList *pl = nullptr;
     if (pairs && aligned) {        // partners agree modulo 8 along the memory-contiguous axis of the unit's face
-        const State::PairList *pl = nullptr;
         if (int rc = source_pairs_by_class(st, host_pos, q.src_pos, q.src_begin, q.src_count, pl)) return rc;
         for (int ft = 0; ft < 2; ++ft) { q.pairs[ft] = pl->dev[ft]; q.npairs[ft] = pl->n[ft]; }
         groups = std::max(pl->n[0], pl->n[1]);
     }
     grid = launch_grid(groups, units, st.cu_count, q.spread);
+    q.order = nullptr;
+    if (!ordered || q.spread) return 0;
+    if (aligned && !host_pos) return fail(11, "raytrace: aligned tables without the positions of the source list (internal error)");
+    const int nsrc = pairs ? 2 : 1;
+    for (const auto &e : st.order_lists)
+        if (e.list == q.src_pos && e.begin == q.src_begin && e.count == q.src_count && e.units == units && e.aligned == (int)aligned && e.nsrc == nsrc) {
+            q.order = e.dev; grid = e.grid;
+            return 0;
+        }
+    if (st.order_lists.size() >= 64) {
+        for (auto &e : st.order_lists) if (e.dev) (void)hipFree(e.dev);
+        st.order_lists.clear();
+    }
+    std::vector<int> face_type((size_t)units);
+    for (int u = 0; u < units; ++u) {
+        face_type[(size_t)u] = ((st.geom_host[u].info >> 8) & 3) == 3 ? 1 : 0;
+        if (face_type[(size_t)u] != (unit_face(units, u) == 2 ? 1 : 0)) return fail(11, "raytrace: unit_face disagrees with the geometry tables (internal error)");
+    }
+    const int none[2] = {0, 0};
+    const int *const no_cls[2] = {nullptr, nullptr};
+    const int *const pair_cls[2] = {pl ? pl->cls[0].data() : nullptr, pl ? pl->cls[1].data() : nullptr};
+    std::vector<int32_t> order;
+    State::OrderList e{q.src_pos, q.src_begin, q.src_count, units, (int)aligned, nsrc, nullptr, 0};
+    e.grid = launch_block_order(host_pos, q.src_begin, q.src_count, units, face_type.data(), pairs, aligned, pl ? pl->n : none, pl ? pair_cls : no_cls, order);
+    if (e.grid == 0 || e.grid > grid) return fail(11, "raytrace: dispatch order of " + std::to_string(e.grid) + " blocks (internal error)");
+    static_assert(sizeof(int2) == 2 * sizeof(int32_t), "an entry of the dispatch order is {group, unit}");
+    ASORA_HIP_TRY(hipMalloc(&e.dev, order.size() * sizeof(int32_t)));
+    ASORA_HIP_TRY(hipMemcpy(e.dev, order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    st.order_lists.push_back(e);
+    q.order = e.dev; grid = e.grid;
     return 0;
 }
 
@@ -1087,7 +1123,7 @@ int launch_raytrace(State &st, RtParams &p, bool dump, bool heat, hipStream_t si
             q.zero_probe = st.zero_probe_dev;
         }
         unsigned grid = 0;
-        if (int rc = set_launch_grid(st, q, sh.units, form.nsrc == 2, sh.aligned, host_pos, grid)) return rc;
+        if (int rc = set_launch_grid(st, q, sh.units, form.nsrc == 2, sh.aligned, host_pos, !dump, grid)) return rc;
         st.last_variant = variant_word(form, sh.units, sh.aligned);
         {
             KernelTimer kt(ASORA_KERNEL_RAYTRACE, stream);
@@ -1187,7 +1223,7 @@ int subbox_tables_sweep(State &st, const RtParams &p, const SubboxTables &tab, i
     const bool pairs = tab.nsrc == 2 && !heat;
     const RtForm form = subbox_form(tab.threads, heat, pairs ? 2 : 1);
     unsigned grid = 0;
-    if (int rc = set_launch_grid(st, q, tab.units, pairs, tab.aligned, tab.host_pos, grid)) return rc;
+    if (int rc = set_launch_grid(st, q, tab.units, pairs, tab.aligned, tab.host_pos, false, grid)) return rc;
     st.last_variant = variant_word(form, tab.units, tab.aligned);
     KernelTimer kt(ASORA_KERNEL_RAYTRACE);
     return launch_form(form, q, grid, form_lds_bytes(form, p.max_cells), st.stream, ALL_FORMS);

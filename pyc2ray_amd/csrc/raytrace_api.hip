@@ -480,6 +480,46 @@ int asora_debug_launch_plan(int N, double R, int src_count, int shape_src_count,
     return 0;
 }
 
+int asora_debug_block_order(const int32_t *pos0, int begin, int count, int units, int nsrc, int aligned, int cu_count, int32_t *out,
+                            size_t capacity, int *grid)
+{
+    clear_error();
+    if (!pos0 || begin < 0 || count < 1 || units < 1 || units > MAX_UNITS || (nsrc != 1 && nsrc != 2) || !grid || (aligned && units != 6 && units != 12))
+        return fail(3, "debug_block_order: bad arguments");
+    const bool pairs = nsrc == 2;
+    // as set_launch_grid (raytrace.hip) feeds the same functions
+    std::vector<SrcPair> pl[2];
+    std::vector<int> cls[2];
+    int npairs[2] = {0, 0};
+    int groups = pairs ? (count + 1) / 2 : count;
+    if (pairs && aligned) {
+        for (int ft = 0; ft < 2; ++ft) { pairs_by_class(pos0, begin, count, ft, pl[ft], cls[ft]); npairs[ft] = (int)pl[ft].size(); }
+        groups = std::max(npairs[0], npairs[1]);
+    }
+    int spread = 0;
+    if (cu_count <= 0) cu_count = state().cu_count;
+    (void)launch_grid(groups, units, cu_count, spread);
+    *grid = 0;
+    if (spread) return 0;
+    std::vector<int> face_type((size_t)units);
+    for (int u = 0; u < units; ++u) face_type[(size_t)u] = unit_face(units, u) == 2 ? 1 : 0;
+    const int *const pair_cls[2] = {cls[0].data(), cls[1].data()};
+    std::vector<int32_t> order;
+    const unsigned n = launch_block_order(pos0, begin, count, units, face_type.data(), pairs, aligned != 0, npairs, pair_cls, order);
+    *grid = (int)n;
+    if (!out || capacity < n) return 0;
+    for (unsigned b = 0; b < n; ++b) {
+        const int g = order[2 * (size_t)b], u = order[2 * (size_t)b + 1];
+        int32_t *o = out + 4 * (size_t)b;
+        o[0] = g; o[1] = u; o[2] = o[3] = -1;
+        if (g < 0) continue;
+        if (pairs && aligned) { const SrcPair &s = pl[face_type[(size_t)u]][(size_t)g]; o[2] = s.x; o[3] = s.y; }
+        else if (pairs) { o[2] = begin + 2 * g; o[3] = 2 * g + 1 < count ? begin + 2 * g + 1 : -1; }
+        else o[2] = begin + g;
+    }
+    return 0;
+}
+
 int asora_debug_coldens(double R, double sig, double dr, int source_index, double *coldens_out, int N)
 {
     clear_error();

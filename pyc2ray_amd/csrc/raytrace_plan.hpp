@@ -8,7 +8,9 @@
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
+#include <cstdint>
 #include <string>
+#include <vector>
 
 #include "../../include/asora_hip.h"
 
@@ -303,6 +305,92 @@ inline unsigned launch_grid(int groups, int units, int cu_count, int &spread)
 {
     spread = (long)groups * units <= 2L * cu_count ? 1 : 0;
     return spread ? (unsigned)units * (unsigned)groups : 8u * (unsigned)units * (unsigned)((groups + 7) / 8);
+}
+
+// Who shares a workgroup with whom when the tables are the aligned kind (build_unit_geometry, align_class): two sources
+// that agree modulo 8 in k (units of the x- and y-sector: face type 0) or in i (units of the z-sector: face type 1).  The list is
+// walked in its order -- position-sorted for a whole-list call -- and a source waits for the next one of its class, so partners are
+// neighbours in the list, hence in space; what is left over at the end sweeps alone (y = -1).  cls: the class of each pair.
+struct SrcPair { int x, y; };
+inline void pairs_by_class(const int32_t *host_pos, int begin, int count, int face_type, std::vector<SrcPair> &pairs, std::vector<int> &cls)
+{
+    const int axis = face_type ? 0 : 2;
+    pairs.clear(); cls.clear();
+    pairs.reserve((size_t)count / 2 + 8);
+    int open[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+    for (int s = begin; s < begin + count; ++s) {
+        const int c = host_pos[3 * (size_t)s + axis] & 7;
+        if (open[c] < 0) open[c] = s;
+        else { pairs.push_back(SrcPair{open[c], s}); cls.push_back(c); open[c] = -1; }
+    }
+    for (int c = 0; c < 8; ++c) if (open[c] >= 0) { pairs.push_back(SrcPair{open[c], -1}); cls.push_back(c); }
+}
+
+// The face of unit u of a source cut into `units` (ensure_geometry): 0 x, 1 y, 2 z, -1 for units that hold cells of every face
+inline int unit_face(int units, int u)
+{
+    return units == 6 ? u >> 1 : units == 12 ? u >> 2 : units == 3 ? u : units == 24 ? u >> 3 : units == 96 ? (u % 24) >> 3 : -1;
+}
+// Which (group, unit) a block index stands for, where the arithmetic map of the kernel's prologue is not used: block b sweeps entry b
+// of `order`, {group, unit} or {-1, -1} for padding.  A group is what one workgroup sweeps per unit (a pair of the class lists, two
+// consecutive sources, or one source).  Blocks b and b + 8 share an XCD, so blocks b & 7 = x form the "lane" of XCD x, and a lane is
+// dealt TABLE-MAJOR: per unit (in dispatch order) the groups of the unit's face type are ordered stably by their table class and cut
+// into 8 contiguous slices whose sizes differ by at most 1; lane x sweeps its slice of the first unit, then of the second, ...  A
+// slice spans one or two classes (more only where a class holds fewer groups than a slice), so the workgroups resident on an XCD read
+// one or two tables, four across a unit boundary, and those stay in its L2.
+//   dispatch[d]: the unit dispatched d-th (largest first); face_type[u]: 1 for a z-sector unit, else 0;
+//   ngroups[ft], cls[ft][g]: the groups of face type ft and the table class of each (cls[ft] == nullptr: all one class).
+// Returns the grid: 8 x the longest lane.
+inline unsigned block_order(int units, const int *dispatch, const int *face_type, const int ngroups[2], const int *const cls[2],
+                            std::vector<int32_t> &order)
+{
+    std::vector<int> sorted[2];
+    for (int ft = 0; ft < 2; ++ft) {
+        sorted[ft].resize((size_t)std::max(ngroups[ft], 0));
+        for (int g = 0; g < ngroups[ft]; ++g) sorted[ft][(size_t)g] = g;
+        if (cls[ft]) std::stable_sort(sorted[ft].begin(), sorted[ft].end(), [&](int a, int b) { return cls[ft][a] < cls[ft][b]; });
+    }
+    auto cut = [](int n, int x) { return (int)((long long)n * x / 8); };       // slice x of n groups: [cut(n, x), cut(n, x + 1))
+    size_t len = 0;
+    for (int x = 0; x < 8; ++x) {
+        size_t l = 0;
+        for (int d = 0; d < units; ++d) { const int n = ngroups[face_type[dispatch[d]]]; l += (size_t)(cut(n, x + 1) - cut(n, x)); }
+        len = std::max(len, l);
+    }
+    order.assign(16 * len, -1);
+    for (int x = 0; x < 8; ++x) {
+        size_t t = 0;
+        for (int d = 0; d < units; ++d) {
+            const int u = dispatch[d], ft = face_type[u], n = ngroups[ft];
+            for (int k = cut(n, x); k < cut(n, x + 1); ++k, ++t) {
+                order[2 * (8 * t + (size_t)x)] = sorted[ft][(size_t)k];
+                order[2 * (8 * t + (size_t)x) + 1] = u;
+            }
+        }
+    }
+    return (unsigned)(8 * len);
+}
+
+// ... of a launch of `count` sources from `begin`: units dispatched largest first (the z-sector units hold the most cells: unit
+// units - 1 first); groups = the pairs of the class lists (pairs && aligned: npairs, pair_cls from pairs_by_class), two consecutive
+// sources (pairs), or single sources, whose class is their own where the tables are aligned
+inline unsigned launch_block_order(const int32_t *host_pos, int begin, int count, int units, const int *face_type, bool pairs, bool aligned,
+                                   const int npairs[2], const int *const pair_cls[2], std::vector<int32_t> &order)
+{
+    std::vector<int> dispatch((size_t)units), own[2];
+    for (int d = 0; d < units; ++d) dispatch[(size_t)d] = units - 1 - d;
+    int n[2] = {pairs ? (count + 1) / 2 : count, pairs ? (count + 1) / 2 : count};
+    const int *cls[2] = {nullptr, nullptr};
+    if (pairs && aligned) {
+        for (int ft = 0; ft < 2; ++ft) { n[ft] = npairs[ft]; cls[ft] = pair_cls[ft]; }
+    } else if (aligned) {
+        for (int ft = 0; ft < 2; ++ft) {
+            own[ft].resize((size_t)count);
+            for (int g = 0; g < count; ++g) own[ft][(size_t)g] = host_pos[3 * (size_t)(begin + g) + (ft ? 0 : 2)] & 7;
+            cls[ft] = own[ft].data();
+        }
+    }
+    return block_order(units, dispatch.data(), face_type, n, cls, order);
 }
 
 // returns 0, or the launcher's error code with its message in `why`

@@ -568,6 +568,21 @@ class _LibAsora:
                         zero_form_exists=bool(out[20]))
         return plan
 
+    def block_order(self, pos0, units, nsrc, aligned, begin=0, count=None, cu_count=0):
+        """Which workgroup sweeps what in a raytrace launch that is not spread (asora_debug_block_order; host only, no device needed):
+        an (blocks, 4) int32 array of {group, unit, first source, second source or -1}, all -1 for a block that does nothing; blocks
+        b % 8 == x run on XCD x in the order of b.  None for a launch so small that it is spread."""
+        pos0 = np.ascontiguousarray(pos0, dtype=np.int32).ravel()
+        count = pos0.size // 3 - begin if count is None else count
+        grid = C.c_int(0)
+        args = (_capi.iptr(pos0), int(begin), int(count), int(units), int(nsrc), int(bool(aligned)), int(cu_count))
+        _capi.check(self._lib.asora_debug_block_order(*args, None, 0, C.byref(grid)), "block_order")
+        if grid.value == 0:
+            return None
+        out = np.zeros((grid.value, 4), dtype=np.int32)
+        _capi.check(self._lib.asora_debug_block_order(*args, _capi.iptr(out), grid.value, C.byref(grid)), "block_order")
+        return out
+
     def debug_geometry_bytes(self):
         """Device memory of the current geometry tables (shared parts once)."""
         return int(self._lib.asora_debug_geometry_bytes())
