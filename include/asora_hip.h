@@ -499,6 +499,39 @@ enum { ASORA_REGION_N_PHASE = 0, ASORA_REGION_N_REGIONS = 1, ASORA_REGION_SUM_V2
 int asora_region_sizes(int which_grid, double threshold, int phase, int periodic, int connectivity, int n_bins, const double *edges,
                        unsigned long long *counts, unsigned long long *cells, unsigned long long *tallies, uint32_t *labels);
 
+/* The topology of the in-phase cells of device grid `which_grid`: the numbers of lattice elements from which
+ * the Euler characteristic and the Minkowski functionals follow, and the numbers of components from which the Betti numbers follow.
+ * No grid is written.  The specification, which no implementation detail enters:
+ *   in phase   : as for asora_bubble_mfp -- phase 0: x >= threshold, phase 1: x < threshold; a NaN is in neither.  The complement is
+ *                every cell that is not in phase, NaN cells included;
+ *   element    : an anchor (i, j, k) and a set E of the axes along which the element extends: |E| = 0 a vertex, 1 an edge, 2 a face,
+ *                3 a cell.  Its incident cells are (i - a, j - b, k - c), where the offset on an axis in E is 0 and the offset on an
+ *                axis not in E takes both 0 and 1: a vertex has 8 incident cells, an edge 4, a face 2, a cell 1;
+ *   anchors    : periodic != 0: 0 ... N - 1 on every axis, and indices wrap.  periodic == 0: 0 ... N - 1 on the axes in E and 0 ... N
+ *                on the others; cells outside the box are out of phase;
+ *   counts     : the closed count of a dimension is the number of its elements with AT LEAST ONE incident cell in phase (the complex
+ *                of closed cubes: it goes with 26 neighbours), the open count the number with ALL incident cells in phase (it goes
+ *                with 6 neighbours).  Both sets are returned whatever `connectivity` is;
+ *   tallies    : uint64 [ASORA_TOPO_TALLIES], indexed by the enum below: CELLS (in-phase cells), CLOSED_FACES, CLOSED_EDGES,
+ *                CLOSED_VERTICES, OPEN_FACES, OPEN_EDGES, OPEN_VERTICES, COMPONENTS (the regions of the phase under `connectivity`
+ *                and `periodic`: n_regions of asora_region_sizes), COMPLEMENT_COMPONENTS (the regions of the complement under the
+ *                DUAL connectivity, 6 <-> 26, and the same `periodic`), CAVITIES (periodic == 0: the complement's regions that hold no
+ *                cell on a face of the box; periodic != 0: 0).
+ * The Euler characteristics (V - E + F - C of the closed counts, C - F + E - V of the open ones), the Minkowski functionals and the
+ * Betti numbers are formed by the caller (pyc2ray_amd/topology.py).  N = 1 and 2 with periodic != 0 follow the formula through the
+ * wrap (an element then meets a cell more than once) and mean nothing topologically.
+ * Every output is an integer formed by order-independent sums: two calls return the same bits.  One synchronisation per call.
+ * Device memory: the labelling's 8 bytes per cell (shared with asora_region_sizes) and a second bit mask (2 MiB at 256^3), allocated
+ * by the first call and kept until the device is closed.  With ASORA_OPT_TIMING the threshold pass counts under
+ * ASORA_KERNEL_BUBBLE_MASK; the other stages are not timed.
+ * Fails with code 2 before device_init, 4 for a grid that holds no data or a mesh with N > ASORA_REGION_MAX_N, 3 for: a bad selector,
+ * a non-finite threshold, phase not 0 or 1, connectivity not 6 or 26, tallies = NULL.  A refused call writes nothing. */
+enum { ASORA_TOPO_CELLS = 0, ASORA_TOPO_CLOSED_FACES = 1, ASORA_TOPO_CLOSED_EDGES = 2, ASORA_TOPO_CLOSED_VERTICES = 3,
+       ASORA_TOPO_OPEN_FACES = 4, ASORA_TOPO_OPEN_EDGES = 5, ASORA_TOPO_OPEN_VERTICES = 6, ASORA_TOPO_COMPONENTS = 7,
+       ASORA_TOPO_COMPLEMENT_COMPONENTS = 8, ASORA_TOPO_CAVITIES = 9, ASORA_TOPO_TALLIES = 10 };
+int asora_topology(int which_grid, double threshold, int phase, int periodic, int connectivity,
+                   unsigned long long *tallies /* [ASORA_TOPO_TALLIES] */);
+
 /* ------------------------------------------------------------------------------------------ */
 /* C. Options, measurement and diagnostics                                                     */
 /* ------------------------------------------------------------------------------------------ */

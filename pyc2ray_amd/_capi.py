@@ -37,6 +37,9 @@ BUBBLE_MAX_BINS = 256
 REGION_TALLIES = 14
 REGION_MAX_N = 645
 REGION_NO_LABEL = 0xFFFFFFFF
+(TOPO_CELLS, TOPO_CLOSED_FACES, TOPO_CLOSED_EDGES, TOPO_CLOSED_VERTICES, TOPO_OPEN_FACES, TOPO_OPEN_EDGES, TOPO_OPEN_VERTICES,
+ TOPO_COMPONENTS, TOPO_COMPLEMENT_COMPONENTS, TOPO_CAVITIES) = range(10)
+TOPO_TALLIES = 10
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -126,6 +129,7 @@ SIGNATURES = {
     "asora_bubble_mask": (C.c_int, [C.c_int, C.c_double, C.c_int, _u64p, C.POINTER(C.c_uint32)]),
     "asora_region_sizes": (C.c_int, [C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _u64p, _u64p, _u64p,
                                      C.POINTER(C.c_uint32)]),
+    "asora_topology": (C.c_int, [C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _u64p]),
     "asora_set_option": (C.c_int, [C.c_int, C.c_int]),
     "asora_get_option": (C.c_int, [C.c_int]),
     "asora_kernel_time_ms": (C.c_int, [C.c_int, _dp, C.POINTER(C.c_long)]),

@@ -38,6 +38,11 @@ Differences from the reference:
     (pyc2ray_amd/regions.py; on the device-resident path from the ionised fraction where it lies).  ``Output: region_sizes: 0|1``
     (optional key, default 0; with ``region_threshold``, ``region_connectivity``) and the attribute ``region_stats`` (a bool,
     assignable between steps) do that after every time step (use_gpu only): ``last_regions`` and one line in the log.
+  * ``topology()`` returns the Euler characteristic, the Minkowski functionals and the Betti numbers of the ionised cells of the
+    current state (pyc2ray_amd/topology.py; on the device-resident path from the ionised fraction where it lies).  ``Output:
+    topology: 0|1`` (optional key, default 0; with ``topology_threshold``, ``topology_connectivity``) and the attribute
+    ``topology_stats`` (a bool, assignable between steps) do that after every time step (use_gpu only): ``last_topology`` and one
+    line in the log.
 """
 import atexit
 import re
@@ -56,6 +61,7 @@ from .evolve import evolve3D, evolve3D_MPI, evolve3D_resident
 from .boundaries import periodic_spec
 from .bubbles import bubble_spec, mfp_distribution, distribution_on_device
 from .regions import region_spec, region_sizes, regions_on_device
+from .topology import topology_spec, topology as field_topology, topology_on_device
 from .budget import StepBudget
 from .lls import LLSOpacity, LLSSchedule, lls_spec
 from .planeflux import PlaneFlux, plane_flux_spec
@@ -245,6 +251,7 @@ class C2Ray:
         self._photon_budget_init()
         self._bubble_init()
         self._region_init()
+        self._topology_init()
         if self.rank == 0:
             if self.gpu:
                 q_max = np.ceil(1.73205080757 * min(self.R_max_LLS, 1.73205080757 * self.N / 2))
@@ -557,6 +564,65 @@ class C2Ray:
         if self.rank == 0:
             self.printlog(self.last_regions.log_line())
 
+    def _topology_init(self):
+        """The optional keys ``Output: topology`` (0 | 1; absent: 0): whether every step ends with the topology of its ionised
+        fraction, until ``topology_stats`` is assigned; ``topology_threshold`` (a finite number, default 0.5) and
+        ``topology_connectivity`` (6 or 26, default 6): the ``threshold`` and ``connectivity`` of those calls, and the defaults of
+        :meth:`topology`."""
+        out = self._ld.get('Output') or {}
+        v = out.get('topology', 0)
+        if isinstance(v, (bool, np.bool_)):
+            v = int(v)
+        if not isinstance(v, (int, np.integer)) or v not in (0, 1):
+            raise ValueError(f"Output: topology must be 0 or 1, not {v!r}")
+        kw = {name: out[key] for key, name in (("topology_threshold", "threshold"), ("topology_connectivity", "connectivity")) if key in out}
+        topology_spec("Output: topology_threshold / topology_connectivity", None, **kw)    # ValueError for what a call would refuse, now
+        self.__dict__["_topology_defaults"] = kw
+        self.last_topology = None
+        self._set_topology_stats(bool(v), "Output: topology: 1")
+
+    def _set_topology_stats(self, value, who):
+        if not isinstance(value, (bool, np.bool_)):
+            raise ValueError(f"{who}: topology_stats must be a bool, not {type(value).__name__}")
+        if value and not self.gpu:
+            raise ValueError(f"{who}: topology_stats needs use_gpu=True (the elements are counted and the phases labelled on the device)")
+        self.__dict__["_topology_stats"] = bool(value)
+
+    @property
+    def topology_stats(self):
+        """Does every time step end with the topology of its ionised fraction (:meth:`topology` with the ``Output: topology_*``
+        keys; use_gpu=True only: on an object without, True is refused at the assignment)?  A driver may assign a bool between
+        steps.  After a step ``last_topology`` holds the result and rank 0 writes one line to the log."""
+        return self.__dict__.get("_topology_stats", False)
+
+    @topology_stats.setter
+    def topology_stats(self, value):
+        self._set_topology_stats(value, "C2Ray.topology_stats")
+
+    def topology(self, **kw):
+        """The topology of the ionised cells of the current state, a :class:`pyc2ray_amd.topology.Topology`; the keywords of
+        :func:`pyc2ray_amd.topology.topology` but ``field`` and ``grid``, with ``periodic`` = ``self.periodic`` and ``dr`` =
+        ``self.dr`` unless given, and the ``Output: topology_*`` keys of the parameter file for ``threshold`` and ``connectivity``.
+        While the ionised fraction of the last step lives on the device only (``device_resident``), it is analysed there: nothing
+        is downloaded, and ``xh`` stays where it is.  Otherwise -- with ``use_mpi`` too -- the host array is uploaded and analysed;
+        every rank computes the same result from its own copy."""
+        for name in ("field", "grid"):
+            if name in kw:
+                raise ValueError(f"C2Ray.topology: {name} is not for the class (it analyses its own ionised fraction)")
+        kw = {**self.__dict__.get("_topology_defaults", {}), "periodic": self.periodic, "dr": self.dr, **kw}
+        if self.device_resident and self.gpu and not self.mpi and "xh" in self._device_newer and cuda_is_init():
+            spec = topology_spec("C2Ray.topology", self.N, **kw)
+            return topology_on_device(load_asora(), _capi.GRID_XH, spec)
+        return field_topology(self.xh, **kw)
+
+    def _close_topology(self):
+        """With ``topology_stats``: the topology of the step just run becomes last_topology and joins the log."""
+        if not self.topology_stats:
+            return
+        self.last_topology = self.topology()
+        if self.rank == 0:
+            self.printlog(self.last_topology.log_line())
+
     def evolve3D(self, dt, src_flux, src_pos, src_spectrum=None):
         """Evolve the grid over one time step (c2ray_base.py:170-226).  src_spectrum: with ``BlackBodySource: Teff`` a list, the
         index into it of each source's temperature (None: every source the first one); see pyc2ray_amd.evolve3D."""
@@ -581,6 +647,7 @@ class C2Ray:
         self._close_budget(budget.get("budget"))
         self._close_bubbles()
         self._close_regions()
+        self._close_topology()
 
     @classmethod
     def _fingerprint(cls, arr):
@@ -647,6 +714,7 @@ class C2Ray:
         self._close_budget(budget.get("budget"))
         self._close_bubbles()
         self._close_regions()
+        self._close_topology()
 
     def cosmo_evolve(self, dt):
         """Advance time and redshift by dt, diluting density and rescaling the cell size when the run is

@@ -105,6 +105,7 @@ static int release_all()
     drop(st.bubble_mask); drop(st.bubble_rows); drop(st.bubble_scan); drop(st.bubble_partial); drop(st.bubble_result); drop(st.bubble_edges);
     if (st.bubble_host) { (void)hipHostFree(st.bubble_host); st.bubble_host = nullptr; }
     drop(st.region_label); drop(st.region_volume); drop(st.region_flags); drop(st.region_result);
+    drop(st.topo_complement);
     for (int g = 0; g < ASORA_GRID_COUNT; ++g) { st.grid[g] = nullptr; st.grid_valid[g] = false; }
     st.nhi = st.staging = st.acc = nullptr;
     drop(st.arena); st.arena_bytes = 0;

@@ -267,6 +267,9 @@ struct State {
     // the bubble buffers above
     unsigned *region_label = nullptr, *region_volume = nullptr, *region_flags = nullptr;
     unsigned long long *region_result = nullptr;
+    // the topology's own buffer (asora_topology, topology.hip), allocated by the first call: the bit mask of the complement [N^2 W];
+    // everything else it uses is the bubble and region buffers above
+    unsigned long long *topo_complement = nullptr;
 
     unsigned long long *counters = nullptr; // [COUNTER_FIELDS * COUNTER_SLOTS] device: gamma cells, evaluated cells, exact zeros left out, spread over the slots
     long long last_gamma_cells = 0, last_eval_cells = 0;
@@ -597,5 +600,11 @@ constexpr int BUBBLE_HOST_WORDS = 1024;         // uint64 words of State::bubble
 int check_bubble_grid(const char *who, int which, double threshold, int phase);
 int ensure_bubble_buffers(State &st);
 int launch_bubble_mask(State &st, int which, double threshold, int phase, bool scan);
+// region_label.hip: what asora_topology (topology.hip) shares with asora_region_sizes -- the labelling's buffers, and the launches
+// that label the in-phase cells of a bit mask of the mesh (`mask`: the layout of State::bubble_mask, pad bits 0): afterwards
+// region_label holds every in-phase cell's root (the smallest index of its region; 0xFFFFFFFF out of phase) and region_volume every
+// root's volume (0 elsewhere)
+int ensure_region_buffers(State &st);
+int launch_region_label(State &st, const unsigned long long *mask, int periodic, int connectivity);
 
 } // namespace asora

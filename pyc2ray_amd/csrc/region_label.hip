@@ -279,13 +279,39 @@ __global__ void __launch_bounds__(RG_THREADS) region_final_kernel(const unsigned
     if (threadIdx.x < 3) res[RG_EXTENT + threadIdx.x] = count[threadIdx.x];
 }
 
-static int ensure_region_buffers(State &st)
+int ensure_region_buffers(State &st)
 {
     if (st.region_label && st.region_volume && st.region_result && st.region_flags) return 0;
     if (!st.region_label) ASORA_HIP_TRY(hipMalloc(&st.region_label, sizeof(unsigned) * st.ncell));
     if (!st.region_volume) ASORA_HIP_TRY(hipMalloc(&st.region_volume, sizeof(unsigned) * st.ncell));
     if (!st.region_result) ASORA_HIP_TRY(hipMalloc(&st.region_result, sizeof(unsigned long long) * RG_WORDS));
     if (!st.region_flags) ASORA_HIP_TRY(hipMalloc(&st.region_flags, sizeof(unsigned) * 3 * (size_t)st.N));
+    return 0;
+}
+
+static unsigned region_blocks(const State &st)
+{
+    return (unsigned)std::min<size_t>((st.ncell + RG_THREADS - 1) / RG_THREADS, (size_t)st.cu_count * RG_BLOCKS_PER_CU);
+}
+
+// stage b, and the volumes of c.1 with it: the launches that leave every in-phase cell of `mask` with its root in region_label and
+// every root with its volume in region_volume
+int launch_region_label(State &st, const unsigned long long *mask, int periodic, int connectivity)
+{
+    const int N = st.N, W = (N + 63) / 64;
+    const size_t ncell = st.ncell;
+    const dim3 grid(region_blocks(st)), block(RG_THREADS);
+    hipLaunchKernelGGL(region_init_kernel, grid, block, 0, st.stream, mask, N, W, ncell, st.region_label, st.region_volume);
+    ASORA_HIP_TRY(hipGetLastError());
+    RegionMergeParams mp;
+    mp.mask = mask; mp.label = st.region_label; mp.N = N; mp.W = W; mp.periodic = periodic != 0; mp.ncell = ncell;
+    mp.nrows_fwd = connectivity == 6 ? 2 : 4;
+    const int di[4] = {0, 1, 1, 1}, dj[4] = {1, 0, -1, 1};
+    for (int q = 0; q < 4; ++q) { mp.di[q] = di[q]; mp.dj[q] = dj[q]; }
+    hipLaunchKernelGGL(region_merge_kernel, grid, block, 0, st.stream, mp);
+    ASORA_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(region_flatten_kernel, grid, block, 0, st.stream, mask, N, W, ncell, st.region_label, st.region_volume);
+    ASORA_HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -315,7 +341,7 @@ int asora_region_sizes(int which_grid, double threshold, int phase, int periodic
     if (int rc = ensure_bubble_buffers(st)) return rc;
     if (int rc = ensure_region_buffers(st)) return rc;
 
-    const int N = st.N, W = (N + 63) / 64;
+    const int N = st.N;
     const size_t ncell = st.ncell;
     double *edges_host = reinterpret_cast<double *>(st.bubble_host + RG_WORDS);
     for (int b = 0; b <= n_bins; ++b) edges_host[b] = edges[b];
@@ -324,20 +350,8 @@ int asora_region_sizes(int which_grid, double threshold, int phase, int periodic
     ASORA_HIP_TRY(hipMemsetAsync(st.region_flags, 0, sizeof(unsigned) * 3 * (size_t)N, st.stream));
     if (int rc = launch_bubble_mask(st, which_grid, threshold, phase, false)) return rc;
 
-    const unsigned blocks = (unsigned)std::min<size_t>((ncell + RG_THREADS - 1) / RG_THREADS, (size_t)st.cu_count * RG_BLOCKS_PER_CU);
-    const dim3 grid(blocks), block(RG_THREADS);
-    const unsigned long long *mask = st.bubble_mask;
-    hipLaunchKernelGGL(region_init_kernel, grid, block, 0, st.stream, mask, N, W, ncell, st.region_label, st.region_volume);
-    ASORA_HIP_TRY(hipGetLastError());
-    RegionMergeParams mp;
-    mp.mask = mask; mp.label = st.region_label; mp.N = N; mp.W = W; mp.periodic = periodic != 0; mp.ncell = ncell;
-    mp.nrows_fwd = connectivity == 6 ? 2 : 4;
-    const int di[4] = {0, 1, 1, 1}, dj[4] = {1, 0, -1, 1};
-    for (int q = 0; q < 4; ++q) { mp.di[q] = di[q]; mp.dj[q] = dj[q]; }
-    hipLaunchKernelGGL(region_merge_kernel, grid, block, 0, st.stream, mp);
-    ASORA_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(region_flatten_kernel, grid, block, 0, st.stream, mask, N, W, ncell, st.region_label, st.region_volume);
-    ASORA_HIP_TRY(hipGetLastError());
+    const dim3 grid(region_blocks(st)), block(RG_THREADS);
+    if (int rc = launch_region_label(st, st.bubble_mask, periodic, connectivity)) return rc;
     hipLaunchKernelGGL(region_roots_kernel, grid, block, 0, st.stream, (const unsigned *)st.region_label, (const unsigned *)st.region_volume,
                        ncell, n_bins, (const double *)st.bubble_edges, st.region_result);
     ASORA_HIP_TRY(hipGetLastError());

@@ -498,6 +498,14 @@ class _LibAsora:
                                                  grid.ctypes.data_as(C.POINTER(C.c_uint32)) if labels else None), "region_sizes")
         return (counts, cells, tallies, grid) if labels else (counts, cells, tallies)
 
+    def topology(self, which, threshold, phase, periodic, connectivity):
+        """The element and component counts of the in-phase cells of device grid `which` (include/asora_hip.h, asora_topology): the
+        uint64 tallies indexed by ``_capi.TOPO_*``."""
+        tallies = np.zeros(_capi.TOPO_TALLIES, dtype=np.uint64)
+        _capi.check(self._lib.asora_topology(int(which), float(threshold), int(phase), 1 if periodic else 0, int(connectivity),
+                                             tallies.ctypes.data_as(_capi._u64p)), "topology")
+        return tallies
+
     def thermal_stats(self):
         """(cells that hit max_substeps, cells clamped to t_floor, most substeps of one integration) since the last
         chemistry_device / evolve_begin."""
