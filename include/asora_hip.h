@@ -532,6 +532,40 @@ enum { ASORA_TOPO_CELLS = 0, ASORA_TOPO_CLOSED_FACES = 1, ASORA_TOPO_CLOSED_EDGE
 int asora_topology(int which_grid, double threshold, int phase, int periodic, int connectivity,
                    unsigned long long *tallies /* [ASORA_TOPO_TALLIES] */);
 
+/* The granulometry of the in-phase cells of device grid `which_grid`: the exact squared Euclidean distance
+ * transform of the phase, and from it the numbers of cells that survive an erosion and an opening by digital balls of the given
+ * radii (Kakiichi et al. 2017).  No grid is written.  The specification, which no implementation detail enters; all integers:
+ *   in phase   : as for asora_bubble_mfp -- phase 0: x >= threshold, phase 1: x < threshold; a NaN is in neither;
+ *   metric     : d(c, q)^2 = the sum over the axes of the squared index difference; periodic != 0: of the minimum image,
+ *                min(d, N - d) per axis; periodic == 0: the plain difference, and the cells of the exterior (index -1 or N on any
+ *                axis) are out of phase;
+ *   D2(c)      : a uint32 per cell: the minimum of d(c, q)^2 over the out-of-phase cells q (periodic == 0: those of the exterior
+ *                included, so D2(c) <= min(x + 1, N - x)^2 on every axis).  Out-of-phase cells have D2 = 0.  Without any out-of-phase
+ *                cell -- a periodic box that is all in phase -- every cell holds ASORA_GRAN_UNBOUNDED = 0xFFFFFFFF.  Every finite
+ *                value is < 2^20 (N <= ASORA_REGION_MAX_N);
+ *   radii      : radii[n_radii], finite, >= 0, strictly ascending, 1 <= n_radii <= ASORA_BUBBLE_MAX_BINS; r2_n = floor(R_n^2) formed
+ *                in double, R_n^2 < 2^31.  The digital ball is B_n = {o in Z^3: |o|^2 <= r2_n};
+ *   eroded[n]  : the size of E_n = {c: D2(c) > r2_n}, the centres at which the ball lies wholly in the phase;
+ *   opened[n]  : the size of O_n = the union of c + B_n over c in E_n = {x: D2'_n(x) <= r2_n}, D2'_n the squared distance to the
+ *                nearest cell of E_n in the same metric -- but the exterior of an open box holds no centre and is no source here.
+ *                An empty E_n gives 0; the unbounded case gives E_n = all cells and opened[n] = N^3.  Digital balls are no
+ *                granulometry in the strict sense: opened[] is NOT always monotone in n, and is returned as counted;
+ *   tallies    : uint64 [ASORA_GRAN_TALLIES], indexed by the enum below: N_PHASE (cells in phase), D2_MAX (the largest finite D2, 0
+ *                if there is none), N_UNBOUNDED (the cells that hold ASORA_GRAN_UNBOUNDED: 0 or N^3), SUM_D2 (the sum of the finite D2).
+ * dist2 [N^3] or NULL: D2 of every cell in C order, downloaded (tests, distance maps); NULL in production, where 2 n_radii + 4
+ * integers cross to the host.  Every output is an integer formed by order-independent operations: two calls return the same bits.
+ * One synchronisation per call.  Device memory: the labelling's 8 bytes per cell (shared with asora_region_sizes and asora_topology,
+ * used one call after the other), a third uint32 per cell and a second bit mask, allocated by the first call and kept until the
+ * device is closed.  With ASORA_OPT_TIMING the threshold pass counts under ASORA_KERNEL_BUBBLE_MASK; the other stages are not timed.
+ * Fails with code 2 before device_init, 4 for a grid that holds no data or a mesh with N > ASORA_REGION_MAX_N, 3 for: a bad selector,
+ * a non-finite threshold, phase not 0 or 1, n_radii outside [1, ASORA_BUBBLE_MAX_BINS], radii not finite, negative, not strictly
+ * ascending or with R^2 >= 2^31, a null pointer among radii / eroded / opened / tallies.  A refused call writes nothing. */
+enum { ASORA_GRAN_N_PHASE = 0, ASORA_GRAN_D2_MAX = 1, ASORA_GRAN_N_UNBOUNDED = 2, ASORA_GRAN_SUM_D2 = 3, ASORA_GRAN_TALLIES = 4 };
+#define ASORA_GRAN_UNBOUNDED 0xFFFFFFFFu
+int asora_granulometry(int which_grid, double threshold, int phase, int periodic, int n_radii, const double *radii,
+                       unsigned long long *eroded, unsigned long long *opened, unsigned long long *tallies,
+                       unsigned *dist2 /* NULL, or host [N^3] */);
+
 /* ------------------------------------------------------------------------------------------ */
 /* C. Options, measurement and diagnostics                                                     */
 /* ------------------------------------------------------------------------------------------ */

@@ -16,5 +16,7 @@ from .regions import *         # noqa: F401,F403  RegionSizes, region_sizes
 from .c2ray_base import *      # noqa: F401,F403
 from .c2ray_test import *      # noqa: F401,F403
 from . import evolve, raytracing, chemistry, asora_core, utils, dist, bubbles, regions   # noqa: F401
-# (last, so that the package's `topology` is the function, not the module of that name: importlib.import_module finds the module)
+# (last, so that the package's `topology` and `granulometry` are the functions, not the modules of those names:
+# importlib.import_module finds the modules)
 from .topology import *        # noqa: F401,F403,E402  Topology, topology
+from .granulometry import *    # noqa: F401,F403,E402  Granulometry, granulometry

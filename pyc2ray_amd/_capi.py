@@ -40,6 +40,9 @@ REGION_NO_LABEL = 0xFFFFFFFF
 (TOPO_CELLS, TOPO_CLOSED_FACES, TOPO_CLOSED_EDGES, TOPO_CLOSED_VERTICES, TOPO_OPEN_FACES, TOPO_OPEN_EDGES, TOPO_OPEN_VERTICES,
  TOPO_COMPONENTS, TOPO_COMPLEMENT_COMPONENTS, TOPO_CAVITIES) = range(10)
 TOPO_TALLIES = 10
+GRAN_N_PHASE, GRAN_D2_MAX, GRAN_N_UNBOUNDED, GRAN_SUM_D2 = range(4)
+GRAN_TALLIES = 4
+GRAN_UNBOUNDED = 0xFFFFFFFF
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -130,6 +133,7 @@ SIGNATURES = {
     "asora_region_sizes": (C.c_int, [C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _u64p, _u64p, _u64p,
                                      C.POINTER(C.c_uint32)]),
     "asora_topology": (C.c_int, [C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _u64p]),
+    "asora_granulometry": (C.c_int, [C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _dp, _u64p, _u64p, _u64p, C.POINTER(C.c_uint32)]),
     "asora_set_option": (C.c_int, [C.c_int, C.c_int]),
     "asora_get_option": (C.c_int, [C.c_int]),
     "asora_kernel_time_ms": (C.c_int, [C.c_int, _dp, C.POINTER(C.c_long)]),

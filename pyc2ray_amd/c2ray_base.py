@@ -43,6 +43,11 @@ Differences from the reference:
     topology: 0|1`` (optional key, default 0; with ``topology_threshold``, ``topology_connectivity``) and the attribute
     ``topology_stats`` (a bool, assignable between steps) do that after every time step (use_gpu only): ``last_topology`` and one
     line in the log.
+  * ``granulometry()`` returns the size distribution of the ionised cells of the current state by morphological opening, with the
+    exact distance transform behind it (pyc2ray_amd/granulometry.py; on the device-resident path from the ionised fraction where it
+    lies).  ``Output: granulometry: 0|1`` (optional key, default 0; with ``granulometry_threshold``, ``granulometry_radii``) and
+    the attribute ``granulometry_stats`` (a bool, assignable between steps) do that after every time step (use_gpu only):
+    ``last_granulometry`` and one line in the log.
 """
 import atexit
 import re
@@ -62,6 +67,7 @@ from .boundaries import periodic_spec
 from .bubbles import bubble_spec, mfp_distribution, distribution_on_device
 from .regions import region_spec, region_sizes, regions_on_device
 from .topology import topology_spec, topology as field_topology, topology_on_device
+from .granulometry import granulometry_spec, granulometry as field_granulometry, granulometry_on_device
 from .budget import StepBudget
 from .lls import LLSOpacity, LLSSchedule, lls_spec
 from .planeflux import PlaneFlux, plane_flux_spec
@@ -252,6 +258,7 @@ class C2Ray:
         self._bubble_init()
         self._region_init()
         self._topology_init()
+        self._granulometry_init()
         if self.rank == 0:
             if self.gpu:
                 q_max = np.ceil(1.73205080757 * min(self.R_max_LLS, 1.73205080757 * self.N / 2))
@@ -623,6 +630,65 @@ class C2Ray:
         if self.rank == 0:
             self.printlog(self.last_topology.log_line())
 
+    def _granulometry_init(self):
+        """The optional keys ``Output: granulometry`` (0 | 1; absent: 0): whether every step ends with the granulometry of its ionised
+        fraction, until ``granulometry_stats`` is assigned; ``granulometry_threshold`` (a finite number, default 0.5) and
+        ``granulometry_radii`` (an int n for the radii 1 ... n, or a list of ascending radii; default 1 ... max(1, min(N // 4, 32))):
+        the ``threshold`` and ``radii`` of those calls, and the defaults of :meth:`granulometry`."""
+        out = self._ld.get('Output') or {}
+        v = out.get('granulometry', 0)
+        if isinstance(v, (bool, np.bool_)):
+            v = int(v)
+        if not isinstance(v, (int, np.integer)) or v not in (0, 1):
+            raise ValueError(f"Output: granulometry must be 0 or 1, not {v!r}")
+        kw = {name: out[key] for key, name in (("granulometry_threshold", "threshold"), ("granulometry_radii", "radii")) if key in out}
+        granulometry_spec("Output: granulometry_threshold / granulometry_radii", None, **kw)    # ValueError for what a call would refuse, now
+        self.__dict__["_granulometry_defaults"] = kw
+        self.last_granulometry = None
+        self._set_granulometry_stats(bool(v), "Output: granulometry: 1")
+
+    def _set_granulometry_stats(self, value, who):
+        if not isinstance(value, (bool, np.bool_)):
+            raise ValueError(f"{who}: granulometry_stats must be a bool, not {type(value).__name__}")
+        if value and not self.gpu:
+            raise ValueError(f"{who}: granulometry_stats needs use_gpu=True (the distance transform and the openings run on the device)")
+        self.__dict__["_granulometry_stats"] = bool(value)
+
+    @property
+    def granulometry_stats(self):
+        """Does every time step end with the granulometry of its ionised fraction (:meth:`granulometry` with the ``Output:
+        granulometry_*`` keys; use_gpu=True only: on an object without, True is refused at the assignment)?  A driver may assign a
+        bool between steps.  After a step ``last_granulometry`` holds the result and rank 0 writes one line to the log."""
+        return self.__dict__.get("_granulometry_stats", False)
+
+    @granulometry_stats.setter
+    def granulometry_stats(self, value):
+        self._set_granulometry_stats(value, "C2Ray.granulometry_stats")
+
+    def granulometry(self, **kw):
+        """The granulometry of the ionised cells of the current state, a :class:`pyc2ray_amd.granulometry.Granulometry`; the keywords
+        of :func:`pyc2ray_amd.granulometry.granulometry` but ``field`` and ``grid``, with ``periodic`` = ``self.periodic`` and ``dr``
+        = ``self.dr`` unless given, and the ``Output: granulometry_*`` keys of the parameter file for ``threshold`` and ``radii``.
+        While the ionised fraction of the last step lives on the device only (``device_resident``), it is analysed there: nothing
+        is downloaded, and ``xh`` stays where it is.  Otherwise -- with ``use_mpi`` too -- the host array is uploaded and analysed;
+        every rank computes the same result from its own copy."""
+        for name in ("field", "grid"):
+            if name in kw:
+                raise ValueError(f"C2Ray.granulometry: {name} is not for the class (it analyses its own ionised fraction)")
+        kw = {**self.__dict__.get("_granulometry_defaults", {}), "periodic": self.periodic, "dr": self.dr, **kw}
+        if self.device_resident and self.gpu and not self.mpi and "xh" in self._device_newer and cuda_is_init():
+            spec = granulometry_spec("C2Ray.granulometry", self.N, **kw)
+            return granulometry_on_device(load_asora(), _capi.GRID_XH, spec)
+        return field_granulometry(self.xh, **kw)
+
+    def _close_granulometry(self):
+        """With ``granulometry_stats``: the granulometry of the step just run becomes last_granulometry and joins the log."""
+        if not self.granulometry_stats:
+            return
+        self.last_granulometry = self.granulometry()
+        if self.rank == 0:
+            self.printlog(self.last_granulometry.log_line())
+
     def evolve3D(self, dt, src_flux, src_pos, src_spectrum=None):
         """Evolve the grid over one time step (c2ray_base.py:170-226).  src_spectrum: with ``BlackBodySource: Teff`` a list, the
         index into it of each source's temperature (None: every source the first one); see pyc2ray_amd.evolve3D."""
@@ -648,6 +714,7 @@ class C2Ray:
         self._close_bubbles()
         self._close_regions()
         self._close_topology()
+        self._close_granulometry()
 
     @classmethod
     def _fingerprint(cls, arr):
@@ -715,6 +782,7 @@ class C2Ray:
         self._close_bubbles()
         self._close_regions()
         self._close_topology()
+        self._close_granulometry()
 
     def cosmo_evolve(self, dt):
         """Advance time and redshift by dt, diluting density and rescaling the cell size when the run is

@@ -106,6 +106,7 @@ static int release_all()
     if (st.bubble_host) { (void)hipHostFree(st.bubble_host); st.bubble_host = nullptr; }
     drop(st.region_label); drop(st.region_volume); drop(st.region_flags); drop(st.region_result);
     drop(st.topo_complement);
+    drop(st.gran_work); drop(st.gran_mask); drop(st.gran_result);
     for (int g = 0; g < ASORA_GRID_COUNT; ++g) { st.grid[g] = nullptr; st.grid_valid[g] = false; }
     st.nhi = st.staging = st.acc = nullptr;
     drop(st.arena); st.arena_bytes = 0;

@@ -270,6 +270,10 @@ struct State {
     // the topology's own buffer (asora_topology, topology.hip), allocated by the first call: the bit mask of the complement [N^2 W];
     // everything else it uses is the bubble and region buffers above
     unsigned long long *topo_complement = nullptr;
+    // the granulometry's own buffers (asora_granulometry, granulometry.hip), allocated by the first call: a third uint32 grid [N^3]
+    // next to region_label / region_volume, the bit mask of an eroded set [N^2 W] and the result words
+    unsigned *gran_work = nullptr;
+    unsigned long long *gran_mask = nullptr, *gran_result = nullptr;
 
     unsigned long long *counters = nullptr; // [COUNTER_FIELDS * COUNTER_SLOTS] device: gamma cells, evaluated cells, exact zeros left out, spread over the slots
     long long last_gamma_cells = 0, last_eval_cells = 0;

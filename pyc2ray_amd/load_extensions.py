@@ -506,6 +506,26 @@ class _LibAsora:
                                              tallies.ctypes.data_as(_capi._u64p)), "topology")
         return tallies
 
+    def granulometry(self, which, threshold, phase, periodic, radii, distances=False):
+        """The erosion and opening counts of the in-phase cells of device grid `which` for the ascending `radii` (include/asora_hip.h,
+        asora_granulometry): (eroded, opened, tallies), uint64 arrays, the tallies indexed by ``_capi.GRAN_*``; with `distances`
+        also the squared distance transform, an (N, N, N) uint32 array."""
+        radii = np.ascontiguousarray(radii, dtype=np.float64)
+        if radii.ndim != 1:
+            raise ValueError("granulometry: radii must be one-dimensional")
+        eroded, opened = np.zeros(radii.size, dtype=np.uint64), np.zeros(radii.size, dtype=np.uint64)
+        tallies = np.zeros(_capi.GRAN_TALLIES, dtype=np.uint64)
+        grid = None
+        if distances:
+            if self._N is None:
+                raise RuntimeError("granulometry with distances needs a device initialised through device_init (the mesh size)")
+            grid = np.zeros((self._N,) * 3, dtype=np.uint32)
+        _capi.check(self._lib.asora_granulometry(int(which), float(threshold), int(phase), 1 if periodic else 0, int(radii.size),
+                                                 radii.ctypes.data_as(_capi._dp), eroded.ctypes.data_as(_capi._u64p),
+                                                 opened.ctypes.data_as(_capi._u64p), tallies.ctypes.data_as(_capi._u64p),
+                                                 grid.ctypes.data_as(C.POINTER(C.c_uint32)) if distances else None), "granulometry")
+        return (eroded, opened, tallies, grid) if distances else (eroded, opened, tallies)
+
     def thermal_stats(self):
         """(cells that hit max_substeps, cells clamped to t_floor, most substeps of one integration) since the last
         chemistry_device / evolve_begin."""
