@@ -725,6 +725,40 @@ enum { ASORA_PLAN_HEAT = 1, ASORA_PLAN_DUMP = 2, ASORA_PLAN_TABLE_SETS = 4, ASOR
 int asora_debug_launch_plan(int N, double R, int src_count, int shape_src_count, int cu_count, int flags, int shells, int max_cells,
                             int32_t *out);
 
+/* What the last sub-box call (c2ray_do_all_sources, asora_subbox_raytrace_device) launched, written where its launches are made
+ * (tests; no reference counterpart).  out[ASORA_SBL_*], ASORA_SUBBOX_LAUNCH_WORDS ints; all 0 before the first call.  Sources are
+ * summed over the batches of the call; units ... heat describe the last launch of their kind (one call launches one form of each
+ * kind); launches count the sweep launches, one per sub-box round and batch in which anything was swept. */
+enum {
+    ASORA_SBL_VALID = 0,             /* 1 once a sub-box call has run */
+    ASORA_SBL_TABLE_SOURCES = 1,     /* sources swept on tabulated geometry (raytrace.hip, SUBBOX) */
+    ASORA_SBL_UNITS = 2,             /* ... workgroups per source (or per two) */
+    ASORA_SBL_THREADS = 3,           /* ... threads per workgroup */
+    ASORA_SBL_NSRC = 4,              /* ... sources per workgroup, 1 or 2 */
+    ASORA_SBL_ALIGNED = 5,           /* ... on line-aligned tables */
+    ASORA_SBL_HEAT = 6,              /* ... the form with heating */
+    ASORA_SBL_TABLE_LAUNCHES = 7,    /* launches of the tabulated sweep */
+    ASORA_SBL_FLY_SOURCES = 8,       /* sources swept by the on-the-fly kernel (subbox.hip) */
+    ASORA_SBL_FLY_THREADS = 9,       /* ... threads per workgroup: 128, 256 or 1024 */
+    ASORA_SBL_FLY_LDS_SHELLS = 10,   /* ... 1: both shell buffers in LDS, 0: in global memory */
+    ASORA_SBL_FLY_HEAT = 11,         /* ... the form with heating */
+    ASORA_SBL_FLY_LAUNCHES = 12,     /* launches of the on-the-fly kernel */
+    ASORA_SBL_BATCHES = 13,          /* batches the call's sources were swept in */
+    ASORA_SUBBOX_LAUNCH_WORDS = 16
+};
+int asora_debug_last_subbox_launch(int32_t *out);
+
+/* What a sub-box call would launch when nothing about the built geometry intervenes, from the driver's own planning function
+ * (plan_subbox, pyc2ray_amd/csrc/raytrace_plan.hpp): host only, no device needed.  A call on a mesh of N cells with `src_count`
+ * sources, the last of which returns its column densities when has_dump (c2ray_do_all_sources: 1, asora_subbox_raytrace_device: 0).
+ * ASORA_OPT_SUBBOX_TABLES, _PAIR_SOURCES, _ALIGNED_ROWS, _GREY_NOTABLES and _GLOBAL_ATOMICS are read as asora_set_option left
+ * them; cu_count <= 0: the device's, 256 before asora_device_init.  out[0] sources on tables, out[1 ... 4] their units, threads,
+ * sources per workgroup and line-aligned tables (before the mesh and the host's positions are asked), out[5] sources on the fly,
+ * out[6] that kernel's threads, out[7] the last tabulated shell; ASORA_SUBBOX_PLAN_WORDS ints.  Not planned: the fall-backs that
+ * need the built tables (shells of one or two sources exceeding LDS) and batching; asora_debug_last_subbox_launch reports what ran. */
+enum { ASORA_SUBBOX_PLAN_WORDS = 8 };
+int asora_debug_subbox_plan(int N, double R, int max_subbox, int src_count, int has_dump, int heat, int cu_count, int32_t *out);
+
 /* Which workgroup sweeps what in a raytrace launch that is not spread, from the launcher's own functions (block_order,
  * pyc2ray_amd/csrc/raytrace_plan.hpp): host only, no device needed.  pos0: 0-based xyz-interleaved positions of a source list; the
  * launch is of `count` sources from `begin`, `units` workgroups per source, nsrc = 1 or 2 sources per workgroup, line-aligned tables

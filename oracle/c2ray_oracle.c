@@ -34,6 +34,15 @@
 #define ORACLE_GREY             4  /* analytic grey rates (GREY_NOTABLES builds) */
 #define ORACLE_PER_SOURCE_FLUX  8  /* flux[ns] (raytracing.cu:247) instead of the Fortran's
                                       normflux(NumSrc) for every source (raytracing.f90:500,503) */
+#define ORACLE_STOPPED_CELLS_LOSE_NOTHING 16
+                                   /* Fortran path only: a cell that deposits nothing (beyond R_max_LLS or above
+                                      the column-density cap, raytracing.f90:474-478) adds 0 to the photon loss of
+                                      its sub-box instead of the stale phi_out (see fctx.stale_phi_out).  This is
+                                      the convention of pyc2ray_amd/csrc/subbox.hip and of the tabulated sweep.
+                                      The reference leaves the value undefined, so the flag CANNOT be validated
+                                      against oracle/_ref wherever it changes a result: it states this library's
+                                      convention, nothing more.  Where no stopped cell lies on a box face it
+                                      changes nothing, and there the flagged oracle still equals oracle/_ref. */
 
 static const double PI_F90   = 3.14159265358979323846264338;   /* raytracing.f90:47 */
 static const double S_STAR   = 1.0e48;                         /* photorates.f90:7  */
@@ -208,7 +217,8 @@ typedef struct {
                              (raytracing.f90:408,495-519,543); we carry the last
                              defined value, which is what a reused stack slot
                              does.  Tests only compare photon_loss where no
-                             stopped cell lies on a sub-box boundary.          */
+                             stopped cell lies on a sub-box boundary, or under
+                             ORACLE_STOPPED_CELLS_LOSE_NOTHING (0 instead).    */
 } fctx;
 
 /* evolve0D, src/c2ray/raytracing.f90:347-567 */
@@ -244,7 +254,8 @@ static void f_cell(fctx *c, const int rt[3], const int src[3], int ns,
     double cd_out = cd_in + nHI * path;                               /* f90:488 */
     c->coldens[idx] = cd_out;
 
-    double phi = 0.0, heat = 0.0, phi_out = c->stale_phi_out;
+    double phi = 0.0, heat = 0.0;
+    double phi_out = (c->flags & ORACLE_STOPPED_CELLS_LOSE_NOTHING) ? 0.0 : c->stale_phi_out;
     if (!stop) {
         double flux = (c->flags & ORACLE_PER_SOURCE_FLUX) ? c->normflux[ns]
                                                           : c->normflux[c->NumSrc - 1];  /* f90:500,503 */
@@ -310,14 +321,15 @@ static void f_source(fctx *c, int ns, int max_subbox, int subboxsize, float loss
     *photon_loss += c->loss;
 }
 
-/* do_all_sources, raytracing.f90:52-119 */
-void oracle_do_all_sources(const double *normflux, const int32_t *srcpos, int max_subbox, int subboxsize,
+/* do_all_sources, raytracing.f90:52-119.  nbox_per_source (optional, NumSrc ints): the sub-boxes each source was traced
+ * in (tests state conditions on their inputs with it: which sources stop before the range ends). */
+void oracle_do_all_sources_boxes(const double *normflux, const int32_t *srcpos, int max_subbox, int subboxsize,
                            double *coldensh_out, double sig, double dr, const double *ndens,
                            const double *xh_av, double *phi_ion, double *phi_heat, float loss_fraction,
                            const double *thin, const double *thick, const double *hthin, const double *hthick,
                            double minlogtau, double dlogtau, double R_max_LLS,
                            int NumTau, int table_len, int NumSrc, int m1, int m2, int m3, int flags,
-                           int *sum_nbox, double *photon_loss)
+                           int *sum_nbox, double *photon_loss, int *nbox_per_source)
 {
     fctx c;
     memset(&c, 0, sizeof c);
@@ -331,8 +343,25 @@ void oracle_do_all_sources(const double *normflux, const int32_t *srcpos, int ma
     size_t n = (size_t)m1 * m2 * m3;
     memset(phi_ion, 0, n * sizeof(double));                            /* f90:95 */
     *sum_nbox = 0; *photon_loss = 0.0;
-    for (int ns = 0; ns < NumSrc; ++ns)
+    for (int ns = 0; ns < NumSrc; ++ns) {
+        int before = *sum_nbox;
         f_source(&c, ns, max_subbox, subboxsize, loss_fraction, sum_nbox, photon_loss);
+        if (nbox_per_source) nbox_per_source[ns] = *sum_nbox - before;
+    }
+}
+
+/* (a function of its own above, so that the ABI of oracle_do_all_sources stays) */
+void oracle_do_all_sources(const double *normflux, const int32_t *srcpos, int max_subbox, int subboxsize,
+                           double *coldensh_out, double sig, double dr, const double *ndens,
+                           const double *xh_av, double *phi_ion, double *phi_heat, float loss_fraction,
+                           const double *thin, const double *thick, const double *hthin, const double *hthick,
+                           double minlogtau, double dlogtau, double R_max_LLS,
+                           int NumTau, int table_len, int NumSrc, int m1, int m2, int m3, int flags,
+                           int *sum_nbox, double *photon_loss)
+{
+    oracle_do_all_sources_boxes(normflux, srcpos, max_subbox, subboxsize, coldensh_out, sig, dr, ndens, xh_av, phi_ion,
+                                phi_heat, loss_fraction, thin, thick, hthin, hthick, minlogtau, dlogtau, R_max_LLS,
+                                NumTau, table_len, NumSrc, m1, m2, m3, flags, sum_nbox, photon_loss, NULL);
 }
 
 /* ------------------------------------------------------------------------- */

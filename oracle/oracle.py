@@ -19,6 +19,9 @@ ASORA_CONSTS = 1
 THIN_TAU_OUT = 2
 GREY = 4
 PER_SOURCE_FLUX = 8
+#: do_all_sources only: a cell that deposits nothing adds 0 to the sub-box photon loss (this library's convention; the
+#: reference leaves the value undefined, so where the flag matters it has no counterpart in oracle/_ref)
+STOPPED_CELLS_LOSE_NOTHING = 16
 #: flags that make the oracle follow the CUDA (libasora) semantics instead of the Fortran
 ASORA_MODE = ASORA_CONSTS | THIN_TAU_OUT | PER_SOURCE_FLUX
 
@@ -58,7 +61,7 @@ def do_all_sources(normflux, srcpos, max_subbox, subboxsize, sig, dr, ndens, xh_
                    loss_fraction, thin, thick, minlogtau, dlogtau, R_max_LLS,
                    heat_thin=None, heat_thick=None, NumTau=None, flags=0):
     """Fortran-path raytrace. ndens/xh_av: (N,N,N) any order (logical [i,j,k]);
-    srcpos: (3,Ns) 1-based.  Returns dict(phi_ion, phi_heat, coldens, nsubbox, photon_loss),
+    srcpos: (3,Ns) 1-based.  Returns dict(phi_ion, phi_heat, coldens, nsubbox, photon_loss, nbox_per_source),
     arrays Fortran-ordered, coldens = scratch of the LAST source."""
     N = ndens.shape[0]
     nd = np.asfortranarray(ndens, dtype=np.float64)
@@ -77,13 +80,16 @@ def do_all_sources(normflux, srcpos, max_subbox, subboxsize, sig, dr, ndens, xh_
     cd = np.zeros((N, N, N), order="F")
     nbox = C.c_int(0)
     loss = C.c_double(0.0)
-    lib().oracle_do_all_sources(
+    per_source = np.zeros(flux.shape[0], dtype=np.int32)
+    lib().oracle_do_all_sources_boxes(
         _d(flux), pos.ctypes.data_as(_ip), C.c_int(max_subbox), C.c_int(subboxsize), _d(cd),
         C.c_double(sig), C.c_double(dr), _d(nd), _d(xh), _d(phi), _d(heat), C.c_float(loss_fraction),
         _d(thin), _d(thick), _opt(ht), _opt(hk), C.c_double(minlogtau), C.c_double(dlogtau),
         C.c_double(R_max_LLS), C.c_int(NumTau), C.c_int(thin.shape[0]), C.c_int(flux.shape[0]),
-        C.c_int(N), C.c_int(N), C.c_int(N), C.c_int(flags), C.byref(nbox), C.byref(loss))
-    return dict(phi_ion=phi, phi_heat=heat, coldens=cd, nsubbox=nbox.value, photon_loss=loss.value)
+        C.c_int(N), C.c_int(N), C.c_int(N), C.c_int(flags), C.byref(nbox), C.byref(loss),
+        per_source.ctypes.data_as(_ip))
+    return dict(phi_ion=phi, phi_heat=heat, coldens=cd, nsubbox=nbox.value, photon_loss=loss.value,
+                nbox_per_source=per_source)
 
 
 def asora_do_all_sources(R, sig, dr, ndens, xh_av, src_pos0, src_flux, thin, thick,

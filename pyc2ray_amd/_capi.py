@@ -26,6 +26,10 @@ VARIANT_PAIRED, VARIANT_ALIGNED, VARIANT_BUFFER_ATOMICS, VARIANT_SPLIT_DESCRIPTO
 VARIANT_OPEN_BOUNDARIES = 64
 PLAN_HEAT, PLAN_DUMP, PLAN_TABLE_SETS, PLAN_HOST_POSITIONS, PLAN_RADIUS_STAYS, PLAN_RATE_TABLES = 1, 2, 4, 8, 16, 32
 PLAN_WORDS = 24
+(SBL_VALID, SBL_TABLE_SOURCES, SBL_UNITS, SBL_THREADS, SBL_NSRC, SBL_ALIGNED, SBL_HEAT, SBL_TABLE_LAUNCHES, SBL_FLY_SOURCES,
+ SBL_FLY_THREADS, SBL_FLY_LDS_SHELLS, SBL_FLY_HEAT, SBL_FLY_LAUNCHES, SBL_BATCHES) = range(14)
+SUBBOX_LAUNCH_WORDS = 16
+SUBBOX_PLAN_WORDS = 8
 (BUDGET_CELLS, BUDGET_N, BUDGET_X, BUDGET_NX, BUDGET_NX0, BUDGET_DNX, BUDGET_PHOTO, BUDGET_LLS, BUDGET_REC, BUDGET_COL,
  BUDGET_T, BUDGET_NT) = range(12)
 BUDGET_COUNT = 12
@@ -144,6 +148,8 @@ SIGNATURES = {
     "asora_debug_coldens": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_int, _dp, C.c_int]),
     "asora_last_raytrace_variant": (C.c_int, []),
     "asora_debug_launch_plan": (C.c_int, [C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip]),
+    "asora_debug_last_subbox_launch": (C.c_int, [_ip]),
+    "asora_debug_subbox_plan": (C.c_int, [C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip]),
     "asora_debug_block_order": (C.c_int, [_ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.c_size_t, C.POINTER(C.c_int)]),
     "asora_debug_geometry_bytes": (C.c_size_t, []),
     "asora_debug_geometry_table": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int),

@@ -193,6 +193,7 @@ struct State {
     bool zero_probe_pending = false, zero_known = false, zero_dark = false;
     int zero_since_probe = 0;
     int last_variant = 0;                   // ASORA_VARIANT_* bits | units << 8 | threads << 16 of the last raytrace launch
+    int sb_launch[ASORA_SUBBOX_LAUNCH_WORDS] = {};   // what the last sub-box call launched (asora_debug_last_subbox_launch), written where the launches are made
     struct RadiusHistory { double last_R = -1.0; long same_R_calls = 0; bool has_changed = false; };
     RadiusHistory rt_radius[2];             // [0]: whole-box traces and the evolve loop, [1]: the sub-box sweep (note_call_radius)
     // host copies of the two source lists (as uploaded, and in lexicographic order of the position) and, for the paired-sources

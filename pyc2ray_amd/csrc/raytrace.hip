@@ -1146,37 +1146,18 @@ int subbox_tables_prepare(State &st, RtParams &p, int ext_r, int ext_l, int subb
 {
     out = SubboxTables();
     out.host_pos = host_pos;
-    const int want = st.opt[ASORA_OPT_SUBBOX_TABLES];
-    if (want == 1 || p.grey || ext_r <= 0 || ext_l <= 0 || src_count < 1) return 0;
-    if (!p.z_transposed || st.opt[ASORA_OPT_GLOBAL_ATOMICS] || 16ull * p.ncell > 0x80000000ull) return 0;   // the rates go through buffer atomics (one descriptor: N <= 512)
-    const double R2hi = p.R * p.R * (1.0 + 1e-9) + 1e-9;
-    const int range = std::max(ext_r, ext_l);
-    const int S_tab = std::isfinite(R2hi) ? (int)std::min((double)range, std::floor(std::sqrt(R2hi))) : range;
-    if (S_tab + 1 > 256) return 0;                                    // the variant is built with the 256-entry LDS tables
-    // auto: when the radius, not the range, bounds the work (else the tables would hold the whole cube), and not beyond
-    // what a table of a few tens of MB covers
-    if (want == 0 && !(S_tab < std::min(ext_r, ext_l) && S_tab <= 96)) return 0;
-    // the merged kinds of the ASORA sweep, in the workgroup sizes the sub-box forms are built for (256 and 512: the whole sphere
-    // below 11.5 takes 256), and the sector pairs x 512 beyond them
-    int units, threads;
-    const double r = (double)S_tab;
-    merged_kind(r, units, threads);
-    if (!units) { units = 12; threads = 512; }
-    threads = std::max(threads, 256);
-    if (want == 0 && (long)src_count * units < 2L * st.cu_count) return 0;     // a handful of sources: subbox.hip's wide workgroups
+    SubboxPlanInput in{};
+    in.ext_r = ext_r; in.ext_l = ext_l; in.S_tab = subbox_table_extent(p.R, ext_r, ext_l);
+    in.table_sources = src_count; in.has_dump = false; in.heat = heat;
+    in.buffer_atomics = !p.grey && p.z_transposed && !st.opt[ASORA_OPT_GLOBAL_ATOMICS] && 16ull * p.ncell <= 0x80000000ull;   // the rates go through buffer atomics (one descriptor: N <= 512)
+    in.cu_count = st.cu_count;
+    in.opt_tables = st.opt[ASORA_OPT_SUBBOX_TABLES]; in.opt_pairs = st.opt[ASORA_OPT_PAIR_SOURCES]; in.opt_aligned = st.opt[ASORA_OPT_ALIGNED_ROWS];
+    const SubboxPlan plan = plan_subbox(in);
+    if (!plan.tables) return 0;
+    const int units = plan.units, threads = plan.threads;
     const SubboxGeometry sbg{ext_r, ext_l, subboxsize};
-    // Rows cut at 64-byte lines, as for the ASORA sweep (plan_shape): sectors of one face, a mesh whose rows start on
-    // lines, positions the host knows.  ON REQUEST ONLY (ASORA_OPT_ALIGNED_ROWS = 2): measured on MI355X, 1000 sources, 256^3,
-    // r_RT = 32 (profiles/r05_ab_subbox_aligned.jsonl), the aligned tables give this sweep nothing -- 1.136 / 1.151 ms aligned
-    // against 1.139 / 1.143 ms packed with two sources per workgroup, 1.235 against 1.18 ms with one -- where they gave the
-    // ASORA sweep -1.5 ... -4.7 %: here the photon-loss arithmetic and 141 VGPRs (three waves per SIMD), not the atomic
-    // requests, set the pace.
-    bool aligned = false;
-    {
-        const int want_a = st.opt[ASORA_OPT_ALIGNED_ROWS];
-        const bool possible = (units == 6 || units == 12) && p.N % 8 == 0 && host_pos != nullptr && r <= 110.0;
-        aligned = possible && want_a == 2;
-    }
+    // (line-aligned tables: also a mesh whose rows start on lines, positions the host knows)
+    const bool aligned = plan.aligned && p.N % 8 == 0 && host_pos != nullptr;
     if (int rc = ensure_geometry(st, p, threads, units, &sbg, aligned)) return rc;
     out.aligned = aligned;
     if (form_lds_bytes(subbox_form(threads, heat, 1), p.max_cells) > LDS_LIMIT_BYTES) return 0;
@@ -1194,15 +1175,8 @@ int subbox_tables_prepare(State &st, RtParams &p, int ext_r, int ext_l, int subb
     }
     p.sb_trail = st.sb_trail;
     out.units = units; out.threads = threads; out.S = p.S; out.max_batch = max_batch; out.ok = true;
-    // two sources per workgroup (the kernel's NSRC = 2, round 4): as for the ASORA sweep -- table entry decoded once, tables
-    // streamed once, two dependency chains per wave -- where four shell buffers fit and enough workgroups remain; not with
-    // heating (two more lookups per source in flight)
-    {
-        const int want = st.opt[ASORA_OPT_PAIR_SOURCES];
-        const bool possible = !heat && src_count >= 2 && form_lds_bytes(subbox_form(threads, false, 2), p.max_cells) <= LDS_LIMIT_BYTES;
-        const bool pays = r >= 15.5 && pairs_fill_chip(src_count, units, threads, st.cu_count);
-        out.nsrc = (possible && (want == 2 || (want == 0 && pays))) ? 2 : 1;
-    }
+    // two sources per workgroup where the plan wants them and four shell buffers fit
+    out.nsrc = (plan.nsrc == 2 && form_lds_bytes(subbox_form(threads, false, 2), p.max_cells) <= LDS_LIMIT_BYTES) ? 2 : 1;
     return 0;
 }
 
@@ -1225,6 +1199,13 @@ int subbox_tables_sweep(State &st, const RtParams &p, const SubboxTables &tab, i
     unsigned grid = 0;
     if (int rc = set_launch_grid(st, q, tab.units, pairs, tab.aligned, tab.host_pos, false, grid)) return rc;
     st.last_variant = variant_word(form, tab.units, tab.aligned);
+    {   // asora_debug_last_subbox_launch: the form and grid shape of this very launch
+        int *r = st.sb_launch;
+        if (q.sb_first) r[ASORA_SBL_TABLE_SOURCES] += p.src_count;
+        r[ASORA_SBL_UNITS] = tab.units; r[ASORA_SBL_THREADS] = form.threads; r[ASORA_SBL_NSRC] = form.nsrc;
+        r[ASORA_SBL_ALIGNED] = tab.aligned ? 1 : 0; r[ASORA_SBL_HEAT] = form.heat ? 1 : 0;
+        r[ASORA_SBL_TABLE_LAUNCHES] += 1;
+    }
     KernelTimer kt(ASORA_KERNEL_RAYTRACE);
     return launch_form(form, q, grid, form_lds_bytes(form, p.max_cells), st.stream, ALL_FORMS);
 }

@@ -216,6 +216,86 @@ inline bool pair_sources_pays(const RtPlanInput &in, int units, int threads)
     return pairs_fill_chip(in.shape_src_count > 0 ? in.shape_src_count : in.src_count, units, threads, in.cu_count);
 }
 
+// ---- the sub-box sweep (subbox_api.hip): what it launches when left to itself --------------------------------------------------
+// traversal range per axis side (raytracing.f90:174-175) and the last shell a table of the cells within R_max_LLS would hold
+inline void subbox_range(int N, int max_subbox, int &ext_r, int &ext_l)
+{
+    ext_r = std::min(max_subbox, N / 2 - 1 + N % 2);
+    ext_l = std::min(max_subbox, N / 2);
+}
+inline int subbox_table_extent(double R, int ext_r, int ext_l)
+{
+    const double R2hi = R * R * (1.0 + 1e-9) + 1e-9;
+    const int range = std::max(ext_r, ext_l);
+    return std::isfinite(R2hi) ? (int)std::min((double)range, std::floor(std::sqrt(R2hi))) : range;
+}
+// workgroup size of the on-the-fly kernel (subbox.hip) for a launch of `sources` sources whose shells have pitch W:
+// fewer workgroups than CUs (a handful of sources): the launch lasts as long as one workgroup, so wider workgroups shorten it;
+// enough sources to fill the chip: 256 threads per workgroup; small boxes: shells of a few hundred cells fill 128 threads
+// better (+-16: 0.65 -> 0.59 ms per 1000 sources; +-32: 256)
+inline int subbox_fly_threads(int sources, int W, int cu_count)
+{
+    if ((long)sources * 8 < (long)cu_count) return 1024;
+    return W <= 20 ? 128 : 256;
+}
+struct SubboxPlanInput {
+    int S_tab, ext_r, ext_l;          // subbox_table_extent, subbox_range
+    int table_sources;                // the call's sources without the one whose column densities go back to the caller
+    bool has_dump, heat;
+    bool buffer_atomics;              // table rates through one buffer descriptor: not grey, [k][j][i] twins, N <= 512, no ASORA_OPT_GLOBAL_ATOMICS
+    int cu_count;
+    int opt_tables, opt_pairs, opt_aligned;     // ASORA_OPT_SUBBOX_TABLES, _PAIR_SOURCES, _ALIGNED_ROWS
+};
+// Decided before the geometry exists.  What needs the built tables stays with subbox_tables_prepare: the sweep falls back to the
+// on-the-fly kernel when one source's shells exceed LDS, to one source per workgroup when two sources' do, and `aligned` further
+// needs a mesh that is a multiple of 8 and positions the host knows.
+struct SubboxPlan {
+    bool tables;                      // the sources that are not dumped sweep on tabulated geometry
+    int units, threads, nsrc;         // ... in this shape, nsrc sources per workgroup
+    bool aligned;                     // ... on line-aligned tables
+    int fly_sources, fly_threads;     // sources of a one-batch call swept by the on-the-fly kernel, and its workgroup size
+};
+inline SubboxPlan plan_subbox(const SubboxPlanInput &in)
+{
+    SubboxPlan out{false, 0, 0, 1, false, 0, 0};
+    const int want = in.opt_tables, src_count = in.table_sources;
+    const double r = (double)in.S_tab;
+    auto decide = [&]() {
+        if (want == 1 || !in.buffer_atomics || in.ext_r <= 0 || in.ext_l <= 0 || src_count < 1) return false;
+        if (in.S_tab + 1 > 256) return false;                             // the variant is built with the 256-entry LDS tables
+        // auto: when the radius, not the range, bounds the work (else the tables would hold the whole cube), and not beyond
+        // what a table of a few tens of MB covers
+        if (want == 0 && !(in.S_tab < std::min(in.ext_r, in.ext_l) && in.S_tab <= 96)) return false;
+        // the merged kinds of the ASORA sweep, in the workgroup sizes the sub-box forms are built for (256 and 512: the whole sphere
+        // below 11.5 takes 256), and the sector pairs x 512 beyond them
+        merged_kind(r, out.units, out.threads);
+        if (!out.units) { out.units = 12; out.threads = 512; }
+        out.threads = std::max(out.threads, 256);
+        if (want == 0 && (long)src_count * out.units < 2L * in.cu_count) return false;     // a handful of sources: subbox.hip's wide workgroups
+        return true;
+    };
+    out.tables = decide();
+    if (out.tables) {
+        // Rows cut at 64-byte lines, as for the ASORA sweep (plan_shape): sectors of one face.  ON REQUEST ONLY
+        // (ASORA_OPT_ALIGNED_ROWS = 2): measured on MI355X, 1000 sources, 256^3, r_RT = 32 (profiles/r05_ab_subbox_aligned.jsonl), the
+        // aligned tables give this sweep nothing -- 1.136 / 1.151 ms aligned against 1.139 / 1.143 ms packed with two sources per
+        // workgroup, 1.235 against 1.18 ms with one -- where they gave the ASORA sweep -1.5 ... -4.7 %: here the photon-loss
+        // arithmetic and 141 VGPRs (three waves per SIMD), not the atomic requests, set the pace.
+        out.aligned = (out.units == 6 || out.units == 12) && r <= 110.0 && in.opt_aligned == 2;
+        // two sources per workgroup (the kernel's NSRC = 2, round 4): as for the ASORA sweep -- table entry decoded once, tables
+        // streamed once, two dependency chains per wave -- where enough workgroups remain; not with heating (two more lookups per
+        // source in flight)
+        const bool pays = r >= 15.5 && pairs_fill_chip(src_count, out.units, out.threads, in.cu_count);
+        out.nsrc = (!in.heat && src_count >= 2 && (in.opt_pairs == 2 || (in.opt_pairs == 0 && pays))) ? 2 : 1;
+    } else {
+        out.units = out.threads = 0;
+    }
+    // with the tables, the on-the-fly kernel only sweeps the dumped source
+    out.fly_sources = out.tables ? (in.has_dump ? 1 : 0) : std::max(src_count, 0) + (in.has_dump ? 1 : 0);
+    out.fly_threads = out.fly_sources > 0 ? subbox_fly_threads(out.fly_sources, std::max(std::max(in.ext_r, in.ext_l), 0) + 1, in.cu_count) : 0;
+    return out;
+}
+
 // Can the rate atomics go through buffer descriptors (the kernel's BUFATOM)?  One descriptor over both layouts of the rate
 // grid while the pair fits 2 GiB (N <= 512); one per layout (split) up to 2 GiB per layout (N <= 645) for units whose rated
 // cells all lie on one face -- the sector kinds.

@@ -313,10 +313,15 @@ int launch_subbox_sweep(State &st, const SubboxParams &p, hipStream_t side)
     // both shell buffers in LDS up to 56 KB per workgroup (W <= 34: a +-32 box, the benchmark's)
     const size_t lds_bytes = (size_t)6 * p.W * p.W * sizeof(double);
     const bool lds = lds_bytes <= 56 * 1024 && !st.opt[ASORA_OPT_SUBBOX_GLOBAL_SHELLS];
-    if ((long)p.src_count * 8 < (long)st.cu_count) return launch_subbox_variant<1024>(st, p, grid, lds, lds_bytes, stream);
-    // enough sources to fill the chip: 256 threads per workgroup; small boxes: shells of a few hundred cells fill 128 threads
-    // better (+-16: 0.65 -> 0.59 ms per 1000 sources; +-32: 256)
-    if (p.W <= 20) return launch_subbox_variant<128>(st, p, grid, lds, lds_bytes, stream);
+    const int threads = subbox_fly_threads(p.src_count, p.W, st.cu_count);
+    {   // asora_debug_last_subbox_launch: the form of this very launch
+        int *r = st.sb_launch;
+        if (p.s_begin == 0) r[ASORA_SBL_FLY_SOURCES] += p.src_count;
+        r[ASORA_SBL_FLY_THREADS] = threads; r[ASORA_SBL_FLY_LDS_SHELLS] = lds ? 1 : 0; r[ASORA_SBL_FLY_HEAT] = p.heat ? 1 : 0;
+        r[ASORA_SBL_FLY_LAUNCHES] += 1;
+    }
+    if (threads == 1024) return launch_subbox_variant<1024>(st, p, grid, lds, lds_bytes, stream);
+    if (threads == 128) return launch_subbox_variant<128>(st, p, grid, lds, lds_bytes, stream);
     return launch_subbox_variant<256>(st, p, grid, lds, lds_bytes, stream);
 }
 

@@ -49,8 +49,8 @@ static int subbox_core(const SubboxCall &c, long long &total_nbox, double &total
     if (int rc = ensure_logtab(st)) return rc;
 
     // traversal range per axis side, f90:174-175
-    const int ext_r = std::min(c.max_subbox, N / 2 - 1 + N % 2);
-    const int ext_l = std::min(c.max_subbox, N / 2);
+    int ext_r, ext_l;
+    subbox_range(N, c.max_subbox, ext_r, ext_l);
     const int S_all = std::max(ext_r, ext_l);
     const bool range_open = ext_r > 0 && ext_l > 0;      // else the while loop of do_source never runs (f90:193-195)
 
@@ -76,6 +76,8 @@ static int subbox_core(const SubboxCall &c, long long &total_nbox, double &total
 
     total_nbox = 0;
     total_loss = 0.0;
+    std::fill(st.sb_launch, st.sb_launch + ASORA_SUBBOX_LAUNCH_WORDS, 0);
+    st.sb_launch[ASORA_SBL_VALID] = 1;
     // (pair lists are cached by the address of the source list: a caller's temporary list must not meet an older one's entries)
     struct DropPairs { State &s; bool on; ~DropPairs() { if (on) release_pair_lists(s); } } drop_pairs{st, c.src_pos != st.src_pos};
     if (drop_pairs.on) release_pair_lists(st);
@@ -173,6 +175,7 @@ static int subbox_core(const SubboxCall &c, long long &total_nbox, double &total
             ASORA_HIP_TRY(hipMemcpyAsync(&n_active, st.sb_nactive, sizeof(int), hipMemcpyDeviceToHost, st.stream));
             ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
         }
+        st.sb_launch[ASORA_SBL_BATCHES] += 1;
         ASORA_HIP_TRY(hipMemcpy(h_nbox.data(), st.sb_nbox, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost));
         ASORA_HIP_TRY(hipMemcpy(h_loss.data(), st.sb_loss_final, (size_t)batch * sizeof(double), hipMemcpyDeviceToHost));
         for (int s = 0; s < batch; ++s) { total_nbox += h_nbox[s]; total_loss += h_loss[s]; }   // f90:246-247, in source order
@@ -355,6 +358,35 @@ int asora_subbox_raytrace_device(int max_subbox, int subboxsize, float loss_frac
     if (int rc = subbox_core(c, total_nbox, total_loss)) return rc;
     if (sum_nbox) *sum_nbox = (int)total_nbox;
     if (photon_loss) *photon_loss = total_loss;
+    return 0;
+}
+
+int asora_debug_last_subbox_launch(int32_t *out)
+{
+    clear_error();
+    if (!out) return fail(3, "debug_last_subbox_launch: null output");
+    const State &st = state();
+    for (int k = 0; k < ASORA_SUBBOX_LAUNCH_WORDS; ++k) out[k] = st.sb_launch[k];
+    return 0;
+}
+
+int asora_debug_subbox_plan(int N, double R, int max_subbox, int src_count, int has_dump, int heat, int cu_count, int32_t *out)
+{
+    clear_error();
+    if (N < 1 || src_count < 1 || !out) return fail(3, "debug_subbox_plan: bad arguments");
+    const State &st = state();
+    SubboxPlanInput in{};
+    subbox_range(N, max_subbox, in.ext_r, in.ext_l);
+    in.S_tab = subbox_table_extent(R, in.ext_r, in.ext_l);
+    in.table_sources = src_count - (has_dump ? 1 : 0); in.has_dump = has_dump != 0; in.heat = heat != 0;
+    // as subbox_core and subbox_tables_prepare read them (the sweep's grids always have their [k][j][i] twins)
+    in.buffer_atomics = !st.opt[ASORA_OPT_GREY_NOTABLES] && !st.opt[ASORA_OPT_GLOBAL_ATOMICS] && 16ull * N * N * N <= 0x80000000ull;
+    in.cu_count = cu_count > 0 ? cu_count : st.cu_count;
+    in.opt_tables = st.opt[ASORA_OPT_SUBBOX_TABLES]; in.opt_pairs = st.opt[ASORA_OPT_PAIR_SOURCES]; in.opt_aligned = st.opt[ASORA_OPT_ALIGNED_ROWS];
+    const SubboxPlan plan = plan_subbox(in);
+    out[0] = plan.tables ? in.table_sources : 0;
+    out[1] = plan.units; out[2] = plan.threads; out[3] = plan.tables ? plan.nsrc : 0; out[4] = plan.aligned ? 1 : 0;
+    out[5] = plan.fly_sources; out[6] = plan.fly_threads; out[7] = in.S_tab;
     return 0;
 }
 

@@ -596,6 +596,27 @@ class _LibAsora:
                         zero_form_exists=bool(out[20]))
         return plan
 
+    SUBBOX_LAUNCH_FIELDS = ("valid", "table_sources", "units", "threads", "nsrc", "aligned", "heat", "table_launches", "fly_sources",
+                            "fly_threads", "fly_lds_shells", "fly_heat", "fly_launches", "batches")
+
+    def last_subbox_launch(self):
+        """What the last sub-box call launched (asora_debug_last_subbox_launch), recorded where its launches are made: sources swept on
+        tables, their "units", "threads", "nsrc" (sources per workgroup), "aligned" and "heat"; sources swept on the fly, that kernel's
+        "fly_threads", "fly_lds_shells" (else global shells) and "fly_heat"; sweep launches of either kind; "batches"."""
+        out = np.zeros(_capi.SUBBOX_LAUNCH_WORDS, dtype=np.int32)
+        _capi.check(self._lib.asora_debug_last_subbox_launch(_capi.iptr(out)), "last_subbox_launch")
+        return {k: int(v) for k, v in zip(self.SUBBOX_LAUNCH_FIELDS, out)}
+
+    def subbox_plan(self, N, R, max_subbox, src_count, has_dump=True, heat=False, cu_count=0):
+        """What a sub-box call would launch under the options as they stand, before the built geometry has its say
+        (asora_debug_subbox_plan; host only, no device needed): {"table_sources", "units", "threads", "nsrc", "aligned", "fly_sources",
+        "fly_threads", "S_tab"}."""
+        out = np.zeros(_capi.SUBBOX_PLAN_WORDS, dtype=np.int32)
+        _capi.check(self._lib.asora_debug_subbox_plan(int(N), float(R), int(max_subbox), int(src_count), int(bool(has_dump)), int(bool(heat)),
+                                                      int(cu_count), _capi.iptr(out)), "subbox_plan")
+        keys = ("table_sources", "units", "threads", "nsrc", "aligned", "fly_sources", "fly_threads", "S_tab")
+        return {k: int(v) for k, v in zip(keys, out)}
+
     def block_order(self, pos0, units, nsrc, aligned, begin=0, count=None, cu_count=0):
         """Which workgroup sweeps what in a raytrace launch that is not spread (asora_debug_block_order; host only, no device needed):
         an (blocks, 4) int32 array of {group, unit, first source, second source or -1}, all -1 for a block that does nothing; blocks

@@ -214,13 +214,15 @@ def test_many_sources_larger_mesh_against_oracle(libs):
     _fresh(p, N)
     phi, heat, cd, nbox, loss = _call(c2ray, c, 1000, 6, 2e-2, 20.0)
     n = thin.shape[0] - 1
+    # R_max_LLS = 20 < box: the reference's loss on the faces beyond the radius is undefined; the library adds 0 there, and so
+    # does the oracle under STOPPED_CELLS_LOSE_NOTHING (tests/test_oracle_subbox_loss.py)
     ref = O.do_all_sources(flux, pos, 1000, 6, cases.SIG, dr, nd, xh, 2e-2, thin[:n], thick[:n], cases.MINLOGTAU, dlog,
-                           20.0, heat_thin=c["heat_thin"][:n], heat_thick=c["heat_thick"][:n])
+                           20.0, heat_thin=c["heat_thin"][:n], heat_thick=c["heat_thick"][:n], flags=O.STOPPED_CELLS_LOSE_NOTHING)
+    assert nbox == ref["nsubbox"]
+    np.testing.assert_allclose(loss, ref["photon_loss"], rtol=RATE_RTOL)
     _close(phi, ref["phi_ion"], RATE_RTOL)
     _close(heat, ref["phi_heat"], RATE_RTOL)
     np.testing.assert_allclose(cd, ref["coldens"], rtol=1e-11)
-    # R_max_LLS = 20 < box: the reference's loss on the faces beyond the radius is undefined; the oracle carries
-    # the last defined phi_out there, the GPU adds 0 -- so only compare when both agree on the box counts
     assert 12 <= nbox <= 12 * 6
 
 
@@ -365,9 +367,9 @@ def test_tabulated_sweep_matches_the_reference(libs, name):
 
 def test_tabulated_sweep_randomised_against_oracle_and_on_the_fly_kernel(libs):
     """Seeded sweep: mesh sizes, source counts (corners included), ranges, box sizes, loss fractions, opacities, and radii
-    both beyond the range (loss defined everywhere: against the oracle) and INSIDE it (the tables then hold the sphere
-    only; cells on box faces beyond the radius add nothing on either GPU path: the two paths against each other, rates
-    against the oracle)."""
+    both beyond the range (loss defined everywhere) and INSIDE it (the tables then hold the sphere only; cells on box faces
+    beyond the radius add nothing on either GPU path, nor in the oracle under STOPPED_CELLS_LOSE_NOTHING): the two paths
+    against each other and against the oracle -- box counts, loss, rates, heating."""
     p, c2ray, asora, capi = libs
     rng = np.random.default_rng(2031)
     thin, thick, dlog = cases.soft_tables(400)
@@ -423,14 +425,13 @@ def test_tabulated_sweep_randomised_against_oracle_and_on_the_fly_kernel(libs):
         _close(heat2, heat1, RATE_RTOL)
         ref = O.do_all_sources(flux, pos, max_subbox, subboxsize, cases.SIG, dr, nd, xh, lf, thin, thick, cases.MINLOGTAU,
                                dlog, R, heat_thin=ht if use_heat else None, heat_thick=hk if use_heat else None,
-                               **({"flags": O.PER_SOURCE_FLUX} if own_flux else {}))
-        if R >= 1000.0:
-            assert nbox2 == ref["nsubbox"], tag
-            np.testing.assert_allclose(loss2, ref["photon_loss"], rtol=RATE_RTOL, err_msg=tag)
-            _close(phi2, ref["phi_ion"], RATE_RTOL)
-            _close(heat2, ref["phi_heat"], RATE_RTOL)
-        elif nbox2 == ref["nsubbox"]:       # same boxes swept: same rates (the oracle's loss beyond the radius is the reference's undefined one)
-            _close(phi2, ref["phi_ion"], RATE_RTOL)
+                               flags=O.STOPPED_CELLS_LOSE_NOTHING | (O.PER_SOURCE_FLUX if own_flux else 0))
+        # (with the radius inside the range the faces hold cells that deposit nothing: 0 to the loss on the device and, under the
+        #  flag, in the oracle; beyond the range the flag changes nothing)
+        assert nbox2 == ref["nsubbox"], tag
+        np.testing.assert_allclose(loss2, ref["photon_loss"], rtol=RATE_RTOL, err_msg=tag)
+        _close(phi2, ref["phi_ion"], RATE_RTOL)
+        _close(heat2, ref["phi_heat"], RATE_RTOL)
         seen_multi_box += nbox2 > ns
     assert seen_multi_box >= 8
 
@@ -477,11 +478,12 @@ def test_tabulated_sweep_on_line_aligned_tables(libs, heat):
         _close(a[0], other[0], 1e-12)
         _close(a[1], other[1], 1e-12)
     ref = O.do_all_sources(flux, pos, 1000, 7, cases.SIG, dr, nd, xh, 1e-3, thin, thick, cases.MINLOGTAU, dlog, R,
-                           heat_thin=ht if heat else None, heat_thick=hk if heat else None)
-    if a[3] == ref["nsubbox"]:
-        _close(a[0], ref["phi_ion"], RATE_RTOL)
-        if heat:
-            _close(a[1], ref["phi_heat"], RATE_RTOL)
+                           heat_thin=ht if heat else None, heat_thick=hk if heat else None, flags=O.STOPPED_CELLS_LOSE_NOTHING)
+    assert a[3] == ref["nsubbox"]
+    np.testing.assert_allclose(a[4], ref["photon_loss"], rtol=RATE_RTOL)
+    _close(a[0], ref["phi_ion"], RATE_RTOL)
+    if heat:
+        _close(a[1], ref["phi_heat"], RATE_RTOL)
     assert a[3] >= ns and np.isfinite(a[0]).all() and a[0].max() > 0
 
 
@@ -534,6 +536,8 @@ def test_tabulated_sweep_in_several_batches(libs, monkeypatch):
     _close(heat1, heat0, 1e-12)
     n = thin.shape[0] - 1
     ref = O.do_all_sources(flux, pos, 1000, 3, cases.SIG, dr, nd, xh, 2e-2, thin[:n], thick[:n], cases.MINLOGTAU, dlog, 7.0,
-                           heat_thin=c["heat_thin"][:n], heat_thick=c["heat_thick"][:n])
-    if nbox1 == ref["nsubbox"]:
-        _close(phi1, ref["phi_ion"], RATE_RTOL)
+                           heat_thin=c["heat_thin"][:n], heat_thick=c["heat_thick"][:n], flags=O.STOPPED_CELLS_LOSE_NOTHING)
+    assert nbox1 == ref["nsubbox"]
+    np.testing.assert_allclose(loss1, ref["photon_loss"], rtol=RATE_RTOL)
+    _close(phi1, ref["phi_ion"], RATE_RTOL)
+    _close(heat1, ref["phi_heat"], RATE_RTOL)
