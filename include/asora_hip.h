@@ -566,6 +566,58 @@ int asora_granulometry(int which_grid, double threshold, int phase, int periodic
                        unsigned long long *eroded, unsigned long long *opened, unsigned long long *tallies,
                        unsigned *dist2 /* NULL, or host [N^3] */);
 
+/* The spherically averaged power spectrum of one field formed from the device grids, or of two with their cross-spectrum (DESIGN.md
+ * section 4.2h): the 21-cm brightness temperature, the neutral fraction, the density.  No grid is written.  The specification, which
+ * no implementation detail enters:
+ *   field      : selected by a kind (the enum below) and formed per cell c from ASORA_GRID_XH (x), ASORA_GRID_NDENS (n) and
+ *                ASORA_GRID_TEMP (T), in double, in the order of operations written here:
+ *                  ASORA_PS_XH      g = x
+ *                  ASORA_PS_XHI     g = 1 - x
+ *                  ASORA_PS_DENSITY g = n / nbar
+ *                  ASORA_PS_HI      g = ((scale (1 - x)) (n / nbar)) s,  s = 1 if t_gamma == 0, s = 1 - t_gamma / T if t_gamma > 0
+ *                                   (the spin temperature coupled to the kinetic one);
+ *                nbar is the mean of ASORA_GRID_NDENS over all cells, formed on the device by a fixed-order sum (correct to an ulp
+ *                or two).  scale and t_gamma apply to ASORA_PS_HI only; the differential brightness temperature is ASORA_PS_HI with
+ *                the cosmological prefactor as scale;
+ *   call       : kind_a, and kind_b = -1 for the auto-spectrum of a alone, or a second kind for b;
+ *   transform  : ghat(n) = sum over the N^3 cells c of g(c) exp(-2 pi i n.c / N): unnormalised, numpy's sign and layout
+ *                (np.fft.rfftn).  Only the half-space n_z = 0 ... floor(N/2) is stored and binned;
+ *   modes      : every index is folded, m = min(n, N - n) per axis; n2 = m_x^2 + m_y^2 + m_z^2, an integer.  The weight w of a
+ *                stored mode is 1 if n_z = 0, or if N is even and n_z = N/2; else 2 (the mode and its conjugate partner).  The mode
+ *                n = 0 is never binned;
+ *   bins       : n_bins in [1, ASORA_BUBBLE_MAX_BINS] and thresholds[n_bins + 1], unsigned integers, non-decreasing, with
+ *                thresholds[0] >= 1.  A mode belongs to bin b if thresholds[b] <= n2 < thresholds[b + 1]; anything outside is
+ *                dropped.  (A caller with real edges e_b in units of the fundamental mode passes thresholds[b] = ceil(e_b^2); only
+ *                integers are compared here);
+ *   per bin    : count (uint64) = sum of w, exact; sum_k = sum of w sqrt(n2); sum_aa = sum of w |ahat|^2; with a second field also
+ *                sum_bb = sum of w |bhat|^2 and sum_ab = sum of w Re(ahat conj(bhat)).  With kind_b = -1 sum_bb, sum_ab and
+ *                moments_b may be NULL and are not written;
+ *   per field  : moments[2] = (sum of g, sum of g^2) over the cells.
+ * field_out [N^3] or NULL: the formed real field a in C order; modes_out [N N (floor(N/2) + 1)] complex doubles (re, im interleaved,
+ * C order) or NULL: ahat.  Both are for tests and for callers who want the brightness-temperature cube; NULL in production, where
+ * 5 n_bins + 4 numbers cross to the host.
+ * Every floating-point sum (nbar, the moments, the bin sums) is formed in an order that depends on (N, thresholds) only, and no
+ * floating-point atomic enters any of them: two calls return the same bits.  One synchronisation per call.
+ * Device memory: one complex buffer of N N (floor(N/2) + 1) entries (138 MB at 256^3, 2.15 GB at 645^3), a second one from the first
+ * call with kind_b >= 0, the planes' partial bin sums (40 bytes x ASORA_BUBBLE_MAX_BINS x N) and the table of the N roots of unity;
+ * allocated by the first call that needs them and kept until the device is closed.  The stages are not timed under
+ * ASORA_OPT_TIMING (no ASORA_KERNEL_* slot is free); asora_debug_power_spectrum_ms reports them.
+ * Fails with code 2 before device_init; 3 for: a bad kind, a non-finite scale, a non-finite or negative t_gamma, n_bins outside
+ * [1, ASORA_BUBBLE_MAX_BINS], thresholds not non-decreasing or thresholds[0] = 0, a null pointer among thresholds / count / sum_k /
+ * sum_aa / moments_a or, with kind_b >= 0, sum_bb / sum_ab / moments_b; 4 for a grid the kinds need that holds no data (ASORA_GRID_TEMP
+ * is needed by ASORA_PS_HI with t_gamma > 0) and for a mesh with N > ASORA_REGION_MAX_N; 10 for a failed allocation.  A refused call
+ * writes nothing. */
+enum { ASORA_PS_XH = 0, ASORA_PS_XHI = 1, ASORA_PS_DENSITY = 2, ASORA_PS_HI = 3, ASORA_PS_KINDS = 4 };
+int asora_power_spectrum(int kind_a, int kind_b, double scale, double t_gamma, int n_bins, const unsigned *thresholds,
+                         unsigned long long *count, double *sum_k, double *sum_aa, double *sum_bb, double *sum_ab,
+                         double *moments_a /* [2] */, double *moments_b /* [2] or NULL */,
+                         double *field_out /* NULL, or host [N^3] */, double *modes_out /* NULL, or host [2 N N (N/2 + 1)] */);
+/* The durations (ms, HIP events on the library's stream) of the stages of the last asora_power_spectrum call that ran with
+ * ASORA_OPT_TIMING = 1: ms[0] the mean density, [1] the pass along k with the forming of the field(s), [2] the pass along j, [3] the
+ * pass along i, [4] the binning; zeros if no such call has run.  Code 3 for ms = NULL. */
+enum { ASORA_PS_STAGES = 5 };
+int asora_debug_power_spectrum_ms(double *ms /* [ASORA_PS_STAGES] */);
+
 /* ------------------------------------------------------------------------------------------ */
 /* C. Options, measurement and diagnostics                                                     */
 /* ------------------------------------------------------------------------------------------ */

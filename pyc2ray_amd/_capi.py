@@ -47,6 +47,9 @@ TOPO_TALLIES = 10
 GRAN_N_PHASE, GRAN_D2_MAX, GRAN_N_UNBOUNDED, GRAN_SUM_D2 = range(4)
 GRAN_TALLIES = 4
 GRAN_UNBOUNDED = 0xFFFFFFFF
+PS_XH, PS_XHI, PS_DENSITY, PS_HI = range(4)
+PS_KINDS = 4
+PS_STAGES = 5
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -138,6 +141,9 @@ SIGNATURES = {
                                      C.POINTER(C.c_uint32)]),
     "asora_topology": (C.c_int, [C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _u64p]),
     "asora_granulometry": (C.c_int, [C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, _dp, _u64p, _u64p, _u64p, C.POINTER(C.c_uint32)]),
+    "asora_power_spectrum": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_uint32), _u64p, _dp, _dp, _dp, _dp,
+                                       _dp, _dp, _dp, _dp]),
+    "asora_debug_power_spectrum_ms": (C.c_int, [_dp]),
     "asora_set_option": (C.c_int, [C.c_int, C.c_int]),
     "asora_get_option": (C.c_int, [C.c_int]),
     "asora_kernel_time_ms": (C.c_int, [C.c_int, _dp, C.POINTER(C.c_long)]),

@@ -48,8 +48,15 @@ Differences from the reference:
     lies).  ``Output: granulometry: 0|1`` (optional key, default 0; with ``granulometry_threshold``, ``granulometry_radii``) and
     the attribute ``granulometry_stats`` (a bool, assignable between steps) do that after every time step (use_gpu only):
     ``last_granulometry`` and one line in the log.
+  * ``power_spectrum()`` returns the spherically averaged power spectrum of the 21-cm brightness temperature of the current state
+    -- or of the ionised or neutral fraction, the density, and cross-spectra of two of them -- with the prefactor from the object's
+    cosmology and redshift (pyc2ray_amd/powerspec.py; on the device-resident path from the grids where they lie).  ``Output:
+    power_spectrum: 0|1`` (optional key, default 0; with ``power_spectrum_kind``, ``power_spectrum_bins``) and the attribute
+    ``power_spectrum_stats`` (a bool, assignable between steps) do that after every time step (use_gpu only):
+    ``last_power_spectrum`` and one line in the log.
 """
 import atexit
+import math
 import re
 
 import numpy as np
@@ -68,6 +75,7 @@ from .bubbles import bubble_spec, mfp_distribution, distribution_on_device
 from .regions import region_spec, region_sizes, regions_on_device
 from .topology import topology_spec, topology as field_topology, topology_on_device
 from .granulometry import granulometry_spec, granulometry as field_granulometry, granulometry_on_device
+from .powerspec import powerspec_spec, powerspec_on_device
 from .budget import StepBudget
 from .lls import LLSOpacity, LLSSchedule, lls_spec
 from .planeflux import PlaneFlux, plane_flux_spec
@@ -259,6 +267,7 @@ class C2Ray:
         self._region_init()
         self._topology_init()
         self._granulometry_init()
+        self._power_spectrum_init()
         if self.rank == 0:
             if self.gpu:
                 q_max = np.ceil(1.73205080757 * min(self.R_max_LLS, 1.73205080757 * self.N / 2))
@@ -689,6 +698,89 @@ class C2Ray:
         if self.rank == 0:
             self.printlog(self.last_granulometry.log_line())
 
+    def _power_spectrum_init(self):
+        """The optional keys ``Output: power_spectrum`` (0 | 1; absent: 0): whether every step ends with the power spectrum of its
+        state, until ``power_spectrum_stats`` is assigned; ``power_spectrum_kind`` ('xh', 'xhi', 'density', 'hi' or 'dtb', default
+        'dtb') and ``power_spectrum_bins`` (an int n for n equal bins, or a list of ascending edges in units of the fundamental mode;
+        default unit-width bins): the ``kind`` and ``bins`` of those calls, and the defaults of :meth:`power_spectrum`."""
+        out = self._ld.get('Output') or {}
+        v = out.get('power_spectrum', 0)
+        if isinstance(v, (bool, np.bool_)):
+            v = int(v)
+        if not isinstance(v, (int, np.integer)) or v not in (0, 1):
+            raise ValueError(f"Output: power_spectrum must be 0 or 1, not {v!r}")
+        kw = {name: out[key] for key, name in (("power_spectrum_kind", "kind"), ("power_spectrum_bins", "bins")) if key in out}
+        powerspec_spec("Output: power_spectrum_kind / power_spectrum_bins", None, **kw)    # ValueError for what a call would refuse, now
+        self.__dict__["_power_spectrum_defaults"] = kw
+        self.last_power_spectrum = None
+        self._set_power_spectrum_stats(bool(v), "Output: power_spectrum: 1")
+
+    def _set_power_spectrum_stats(self, value, who):
+        if not isinstance(value, (bool, np.bool_)):
+            raise ValueError(f"{who}: power_spectrum_stats must be a bool, not {type(value).__name__}")
+        if value and not self.gpu:
+            raise ValueError(f"{who}: power_spectrum_stats needs use_gpu=True (the transform and the binning run on the device)")
+        self.__dict__["_power_spectrum_stats"] = bool(value)
+
+    @property
+    def power_spectrum_stats(self):
+        """Does every time step end with the power spectrum of its state (:meth:`power_spectrum` with the ``Output:
+        power_spectrum_*`` keys; use_gpu=True only: on an object without, True is refused at the assignment)?  A driver may assign a
+        bool between steps.  After a step ``last_power_spectrum`` holds the result and rank 0 writes one line to the log."""
+        return self.__dict__.get("_power_spectrum_stats", False)
+
+    @power_spectrum_stats.setter
+    def power_spectrum_stats(self, value):
+        self._set_power_spectrum_stats(value, "C2Ray.power_spectrum_stats")
+
+    def brightness_temperature_scale(self):
+        """The prefactor of the 21-cm differential brightness temperature at ``self.zred`` in mK, from the object's own cosmology:
+        27 sqrt((1 + z) / 10  0.15 / (Omega_m h^2)) (Omega_b h^2 / 0.023)."""
+        cs = self._ld['Cosmology']
+        h2 = float(cs['h']) ** 2
+        return 27.0 * math.sqrt((1.0 + float(self.zred)) / 10.0 * 0.15 / (float(cs['Omega0']) * h2)) * (float(cs['Omega_B']) * h2 / 0.023)
+
+    def power_spectrum(self, **kw):
+        """The spherically averaged power spectrum of the current state, a :class:`pyc2ray_amd.powerspec.PowerSpectrum`; the keywords
+        of :func:`pyc2ray_amd.powerspec.power_spectrum` but ``field`` and ``field_b``, and ``spin``.  ``kind`` is 'dtb' unless given
+        (or set by ``Output: power_spectrum_kind``): the brightness temperature in mK, with ``scale`` =
+        :meth:`brightness_temperature_scale` and ``box_len`` = the comoving side of the box in Mpc unless given.  ``spin``: None
+        (default) for a spin temperature far above the CMB's (``t_gamma`` = 0 unless given), 'kinetic' for the spin temperature
+        coupled to the object's temperature grid (``t_gamma`` = the CMB temperature at ``self.zred``).
+        While the ionised fraction of the last step lives on the device only (``device_resident``) and density and temperature
+        there are the host's, the grids are analysed there: nothing is downloaded.  Otherwise -- with ``use_mpi`` too -- the host
+        arrays are uploaded and analysed; every rank computes the same result from its own copy."""
+        for name in ("field", "field_b"):
+            if name in kw:
+                raise ValueError(f"C2Ray.power_spectrum: {name} is not for the class (it analyses its own grids)")
+        kw = {**self.__dict__.get("_power_spectrum_defaults", {}), **kw}
+        spin = kw.pop("spin", None)
+        if spin not in (None, "kinetic"):
+            raise ValueError(f"C2Ray.power_spectrum: spin must be None or 'kinetic', not {spin!r}")
+        if spin == "kinetic":
+            if "t_gamma" in kw:
+                raise ValueError("C2Ray.power_spectrum: spin='kinetic' sets t_gamma itself")
+            kw["t_gamma"] = float(self._ld['Cosmology']['cmbtemp']) * (1.0 + float(self.zred))
+        kw = {"scale": self.brightness_temperature_scale(), "box_len": self.boxsize_c / Mpc, **kw}
+        spec = powerspec_spec("C2Ray.power_spectrum", self.N, **kw)
+        if not cuda_is_init():
+            raise RuntimeError("GPU not initialized. Please initialize it by calling device_init(N)")
+        lib = load_asora()
+        stale = {"ndens", "temp"} & self._host_newer
+        if not (self.device_resident and self.gpu and not self.mpi and "xh" in self._device_newer and not stale):
+            _residency.reclaim()          # (this object's device copies among them: they come down first)
+            for which, grid in ((_capi.GRID_XH, self.xh), (_capi.GRID_NDENS, self.ndens), (_capi.GRID_TEMP, self.temp)):
+                lib.grid_to_device(which, np.asarray(grid, dtype=np.float64))
+        return powerspec_on_device(lib, spec)
+
+    def _close_power_spectrum(self):
+        """With ``power_spectrum_stats``: the power spectrum of the step just run becomes last_power_spectrum and joins the log."""
+        if not self.power_spectrum_stats:
+            return
+        self.last_power_spectrum = self.power_spectrum()
+        if self.rank == 0:
+            self.printlog(self.last_power_spectrum.log_line())
+
     def evolve3D(self, dt, src_flux, src_pos, src_spectrum=None):
         """Evolve the grid over one time step (c2ray_base.py:170-226).  src_spectrum: with ``BlackBodySource: Teff`` a list, the
         index into it of each source's temperature (None: every source the first one); see pyc2ray_amd.evolve3D."""
@@ -715,6 +807,7 @@ class C2Ray:
         self._close_regions()
         self._close_topology()
         self._close_granulometry()
+        self._close_power_spectrum()
 
     @classmethod
     def _fingerprint(cls, arr):
@@ -783,6 +876,7 @@ class C2Ray:
         self._close_regions()
         self._close_topology()
         self._close_granulometry()
+        self._close_power_spectrum()
 
     def cosmo_evolve(self, dt):
         """Advance time and redshift by dt, diluting density and rescaling the cell size when the run is

@@ -275,6 +275,15 @@ struct State {
     // next to region_label / region_volume, the bit mask of an eroded set [N^2 W] and the result words
     unsigned *gran_work = nullptr;
     unsigned long long *gran_mask = nullptr, *gran_result = nullptr;
+    // the power spectrum's own buffers (asora_power_spectrum, power_spectrum.hip), allocated by the first call that needs them: the
+    // complex half-space of field a [N N (N/2 + 1)] and, from the first cross call, of field b; the N roots of unity; the partial
+    // sums (mean density, moments, the planes' bin sums) with the result words behind them, and where those arrive on the host
+    // (pinned).  ps_ms: the stage times of the last call under ASORA_OPT_TIMING (asora_debug_power_spectrum_ms)
+    double2 *ps_modes[2] = {nullptr, nullptr};
+    double2 *ps_twiddle = nullptr;
+    double *ps_partial = nullptr, *ps_host = nullptr;
+    unsigned *ps_thresholds = nullptr;
+    double ps_ms[ASORA_PS_STAGES] = {0, 0, 0, 0, 0};
 
     unsigned long long *counters = nullptr; // [COUNTER_FIELDS * COUNTER_SLOTS] device: gamma cells, evaluated cells, exact zeros left out, spread over the slots
     long long last_gamma_cells = 0, last_eval_cells = 0;

@@ -526,6 +526,42 @@ class _LibAsora:
                                                  grid.ctypes.data_as(C.POINTER(C.c_uint32)) if distances else None), "granulometry")
         return (eroded, opened, tallies, grid) if distances else (eroded, opened, tallies)
 
+    def power_spectrum(self, kind_a, kind_b, scale, t_gamma, thresholds, field=False, modes=False):
+        """The binned power sums of the field of kind `kind_a` (``_capi.PS_*``) formed from the device grids, and with `kind_b` (None:
+        none) those of a second field and of their cross-spectrum (include/asora_hip.h, asora_power_spectrum), for the bins of the
+        integer `thresholds` on n^2: a dict of ``count`` (uint64), ``sum_k``, ``sum_aa``, ``moments_a`` = (sum g, sum g^2), with
+        `kind_b` also ``sum_bb``, ``sum_ab``, ``moments_b`` (else None); with `field` the formed field a, (N, N, N) float64, under
+        ``field``, with `modes` its transform, (N, N, N // 2 + 1) complex128, under ``modes`` (else None)."""
+        thr = np.ascontiguousarray(thresholds, dtype=np.uint32)
+        if thr.ndim != 1:
+            raise ValueError("power_spectrum: thresholds must be one-dimensional")
+        nb = max(thr.size - 1, 1)
+        cross = kind_b is not None
+        out = dict(count=np.zeros(nb, dtype=np.uint64), sum_k=np.zeros(nb), sum_aa=np.zeros(nb), moments_a=np.zeros(2),
+                   sum_bb=np.zeros(nb) if cross else None, sum_ab=np.zeros(nb) if cross else None,
+                   moments_b=np.zeros(2) if cross else None, field=None, modes=None)
+        if field or modes:
+            if self._N is None:
+                raise RuntimeError("power_spectrum with field or modes needs a device initialised through device_init (the mesh size)")
+            if field:
+                out["field"] = np.zeros((self._N,) * 3)
+            if modes:
+                out["modes"] = np.zeros((self._N, self._N, self._N // 2 + 1), dtype=np.complex128)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(_capi._dp)
+        _capi.check(self._lib.asora_power_spectrum(int(kind_a), int(kind_b) if cross else -1, float(scale), float(t_gamma), int(thr.size) - 1,
+                                                   thr.ctypes.data_as(C.POINTER(C.c_uint32)), out["count"].ctypes.data_as(_capi._u64p),
+                                                   ptr(out["sum_k"]), ptr(out["sum_aa"]), ptr(out["sum_bb"]), ptr(out["sum_ab"]),
+                                                   ptr(out["moments_a"]), ptr(out["moments_b"]), ptr(out["field"]), ptr(out["modes"])),
+                    "power_spectrum")
+        return out
+
+    def power_spectrum_ms(self):
+        """The stage times (ms) of the last power_spectrum call that ran with OPT_TIMING: mean density, the pass along k, along j,
+        along i, the binning (include/asora_hip.h, asora_debug_power_spectrum_ms)."""
+        ms = np.zeros(_capi.PS_STAGES)
+        _capi.check(self._lib.asora_debug_power_spectrum_ms(_capi.dptr(ms)), "debug_power_spectrum_ms")
+        return ms
+
     def thermal_stats(self):
         """(cells that hit max_substeps, cells clamped to t_floor, most substeps of one integration) since the last
         chemistry_device / evolve_begin."""
