@@ -618,6 +618,56 @@ int asora_power_spectrum(int kind_a, int kind_b, double scale, double t_gamma, i
 enum { ASORA_PS_STAGES = 5 };
 int asora_debug_power_spectrum_ms(double *ms /* [ASORA_PS_STAGES] */);
 
+/* A field formed from the device grids, multiplied by a filter in Fourier space and transformed back, with the one-point statistics
+ * of the result: what a telescope of finite resolution would see of the brightness temperature -- a Gaussian
+ * beam across the sky, a top-hat along frequency, the mean removed -- or any other filter that is a product of three per-axis tables
+ * and a radial one.  The specification, which no implementation detail enters:
+ *   field      : g is formed exactly as asora_power_spectrum forms it: the kinds ASORA_PS_*, the same order of operations, the same
+ *                mean density; ghat(n) is its unnormalised transform, as there;
+ *   filter     : W(n) = ((w_i[n_x] w_j[n_y]) w_k[n_z]) w_r[m2], multiplied in this order, no product contracted into a fused
+ *                multiply-add; m = min(n, N - n) per axis is the folded index and m2 = m_x^2 + m_y^2 + m_z^2, an integer.  w_i, w_j,
+ *                w_k: [N] each; w_r: [n_r], n_r = 3 floor(N/2)^2 + 1; a NULL table counts as all ones (n_r is not looked at without w_r).  With
+ *                subtract_mean != 0 the mode n = 0 is multiplied by 0 instead.  The library indexes tables and multiplies; what a
+ *                filter is, is the caller's business.  w_i and w_j must be symmetric as bits, w[n] = w[N - n], 1 <= n < N: the
+ *                output would not be real otherwise.  (w_k is read at n_z = 0 ... floor(N/2) only: the stored half-space);
+ *   output     : h(c) = N^-3 sum over n of W(n) ghat(n) exp(+2 pi i n.c / N), a real field in the layout of the grids, kept in a
+ *                buffer of the library's own; with dst_grid >= 0 it is written into that grid instead, which is allocated as
+ *                asora_grid_to_device would allocate it and marked as holding data.  dst_grid may be a grid the kind reads: the whole
+ *                forward transform is stream-ordered before the first write.  field_out [N^3] or NULL: h in C order;
+ *   stats      : [ASORA_SMOOTH_STATS]: [0] the number of finite cells of h, [1] of non-finite ones (as doubles; exact, N^3 < 2^53);
+ *                [2] min and [3] max over the finite cells (+inf and -inf without one); [4] sum g and [5] sum g^2 of the INPUT field,
+ *                the moments asora_power_spectrum returns; [6] sum h; [7], [8], [9] the central sums S_p = sum (h - mu)^p, p = 2, 3,
+ *                4, with mu = fl([6] / N^3), (h - mu)^3 formed as ((h - mu)(h - mu))(h - mu) and ^4 as the square of the square.
+ *                The sums run over every cell (one non-finite cell makes them non-finite) in double-double, in the fixed order of
+ *                the power spectrum's moments;
+ *   hist       : n_hist in [0, ASORA_SMOOTH_MAX_BINS] bins with edges[n_hist + 1], finite and strictly ascending.  hist[n_hist + 2]:
+ *                hist[b] the finite cells with edges[b] <= h < edges[b + 1], hist[n_hist] those below edges[0], hist[n_hist + 1] those
+ *                at or above edges[n_hist].  Integers: any order of counting gives the same bits.  With n_hist = 0 edges and hist may
+ *                be NULL and are not touched.
+ * (One non-finite cell of g makes every cell of h non-finite: the transform mixes all cells.)
+ * No floating-point atomic anywhere: the same call returns the same bits.  One synchronisation per call; 10 + n_hist + 2 numbers
+ * cross to the host unless field_out is given.  Device memory beside the power spectrum's complex buffer, which is transformed in
+ * place and overwritten on the way back: N^3 doubles for h when a call without dst_grid is made, and the tables.
+ * Fails with code 2 before device_init; 3 for: a bad kind, a non-finite scale, a non-finite or negative t_gamma, a table with a
+ * non-finite entry, w_i or w_j that is not symmetric as bits, w_r with n_r != 3 floor(N/2)^2 + 1, n_hist
+ * outside [0, ASORA_SMOOTH_MAX_BINS], edges that are non-finite or do not strictly ascend, NULL edges or hist with n_hist > 0,
+ * dst_grid outside -1 ... ASORA_GRID_COUNT - 1, a NULL stats; 4 for a grid the kind needs that holds no data and for a mesh with
+ * N > ASORA_REGION_MAX_N; 10 for a failed allocation.  A refused call writes nothing, on the host or on the device. */
+enum { ASORA_SMOOTH_STATS = 10, ASORA_SMOOTH_MAX_BINS = 4096 };
+int asora_smooth_field(int kind, double scale, double t_gamma,
+                       const double *w_i, const double *w_j, const double *w_k,   /* [N] each, or NULL = all ones */
+                       const double *w_r, unsigned n_r,                           /* [n_r] or NULL */
+                       int subtract_mean,
+                       int n_hist, const double *edges,                           /* [n_hist + 1], or n_hist = 0 and NULL */
+                       int dst_grid,                                              /* -1, or a grid selector */
+                       double *stats, uint64_t *hist, double *field_out);
+/* The durations (ms) of the stages of the last asora_smooth_field call that ran with ASORA_OPT_TIMING = 1: ms[0] the mean density,
+ * [1] the forward pass along k with the forming of the field, [2] forward along j, [3] forward along i, [4] back along i with the
+ * filter, [5] back along j, [6] back along k to the real field with its first statistics, [7] the central moments and the
+ * histogram; zeros if no such call has run.  Code 3 for ms = NULL. */
+enum { ASORA_SMOOTH_STAGES = 8 };
+int asora_debug_smooth_field_ms(double *ms /* [ASORA_SMOOTH_STAGES] */);      /* stage times of the last call made under ASORA_OPT_TIMING */
+
 /* ------------------------------------------------------------------------------------------ */
 /* C. Options, measurement and diagnostics                                                     */
 /* ------------------------------------------------------------------------------------------ */

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("PYC2RAY_AMD_LIBASORA") or os.path.join(_HERE, "lib", 
 GRID_NDENS, GRID_XH_AV, GRID_PHI_ION, GRID_TEMP, GRID_XH, GRID_XH_INTERMED, GRID_PHI_HEAT = range(7)
 GRID_TEMP_END = 7
 GRID_CLUMP = 8
+GRID_COUNT = 9
 (OPT_FORTRAN_CONSTANTS, OPT_GREY_NOTABLES, OPT_TIMING, OPT_Z_TRANSPOSED, OPT_BLOCK_THREADS, OPT_SECTORS,
  OPT_HEATING, OPT_C2RAY_OWN_FLUX, OPT_NO_UNIFORM_T, OPT_SUBBOX_GLOBAL_SHELLS, OPT_PIPELINED_COPIES,
  OPT_SKIP_ZERO_RATES, OPT_GLOBAL_ATOMICS, OPT_PAIR_SOURCES, OPT_SUBBOX_TABLES, OPT_ALIGNED_ROWS, OPT_GEOMETRY_ON_HOST,
@@ -50,6 +51,11 @@ GRAN_UNBOUNDED = 0xFFFFFFFF
 PS_XH, PS_XHI, PS_DENSITY, PS_HI = range(4)
 PS_KINDS = 4
 PS_STAGES = 5
+(SMOOTH_N_FINITE, SMOOTH_N_NONFINITE, SMOOTH_MIN, SMOOTH_MAX, SMOOTH_INPUT_SUM, SMOOTH_INPUT_SUM2, SMOOTH_SUM, SMOOTH_S2, SMOOTH_S3,
+ SMOOTH_S4) = range(10)
+SMOOTH_STATS = 10
+SMOOTH_MAX_BINS = 4096
+SMOOTH_STAGES = 8
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -144,6 +150,9 @@ SIGNATURES = {
     "asora_power_spectrum": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_uint32), _u64p, _dp, _dp, _dp, _dp,
                                        _dp, _dp, _dp, _dp]),
     "asora_debug_power_spectrum_ms": (C.c_int, [_dp]),
+    "asora_smooth_field": (C.c_int, [C.c_int, C.c_double, C.c_double, _dp, _dp, _dp, _dp, C.c_uint, C.c_int, C.c_int, _dp, C.c_int, _dp, _u64p,
+                                     _dp]),
+    "asora_debug_smooth_field_ms": (C.c_int, [_dp]),
     "asora_set_option": (C.c_int, [C.c_int, C.c_int]),
     "asora_get_option": (C.c_int, [C.c_int]),
     "asora_kernel_time_ms": (C.c_int, [C.c_int, _dp, C.POINTER(C.c_long)]),

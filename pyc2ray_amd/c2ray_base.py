@@ -54,6 +54,13 @@ Differences from the reference:
     power_spectrum: 0|1`` (optional key, default 0; with ``power_spectrum_kind``, ``power_spectrum_bins``) and the attribute
     ``power_spectrum_stats`` (a bool, assignable between steps) do that after every time step (use_gpu only):
     ``last_power_spectrum`` and one line in the log.
+  * ``observed_map()`` returns the brightness temperature of the current state smoothed to a radio interferometer's resolution -- a
+    Gaussian beam across the sky and a top-hat of the same comoving width along the line of sight, from a maximum baseline, the
+    redshift and the cosmology, the mean removed -- with its one-point statistics (variance, skewness, kurtosis, PDF), and
+    ``smoothed_field()`` the same for any filter (pyc2ray_amd/smoothing.py; on the device-resident path from the grids where they
+    lie).  ``Output: observed_map: 0|1`` (optional key, default 0; with ``observed_baseline_km``, ``observed_los_axis``,
+    ``observed_bins``) and the attribute ``observed_stats`` (a bool, assignable between steps) do that after every time step
+    (use_gpu only): ``last_observed`` and one line in the log.
 """
 import atexit
 import math
@@ -76,6 +83,7 @@ from .regions import region_spec, region_sizes, regions_on_device
 from .topology import topology_spec, topology as field_topology, topology_on_device
 from .granulometry import granulometry_spec, granulometry as field_granulometry, granulometry_on_device
 from .powerspec import powerspec_spec, powerspec_on_device
+from .smoothing import smoothing_spec, smoothing_on_device, telescope
 from .budget import StepBudget
 from .lls import LLSOpacity, LLSSchedule, lls_spec
 from .planeflux import PlaneFlux, plane_flux_spec
@@ -136,6 +144,12 @@ class FlatLambdaCDMLite:
 
     def lookback_time(self, z):
         return self.age(0.0) - self.age(z)
+
+    def comoving_distance(self, z):
+        """The line-of-sight comoving distance to redshift z, in Mpc: c / H0 int_0^z dz' / E(z')."""
+        from scipy.integrate import quad
+        val, _ = quad(lambda x: 1.0 / float(self.efunc(x)), 0.0, float(z), epsabs=0.0, epsrel=1e-12, limit=200)
+        return self._c / 1e3 / self.H0 * val
 
     def z_at_age(self, t):
         from scipy.optimize import brentq
@@ -268,6 +282,7 @@ class C2Ray:
         self._topology_init()
         self._granulometry_init()
         self._power_spectrum_init()
+        self._observed_init()
         if self.rank == 0:
             if self.gpu:
                 q_max = np.ceil(1.73205080757 * min(self.R_max_LLS, 1.73205080757 * self.N / 2))
@@ -781,6 +796,121 @@ class C2Ray:
         if self.rank == 0:
             self.printlog(self.last_power_spectrum.log_line())
 
+    def _observed_init(self):
+        """The optional keys ``Output: observed_map`` (0 | 1; absent: 0): whether every step ends with the observed map of its state,
+        until ``observed_stats`` is assigned; ``observed_baseline_km`` (a number > 0, default 2), ``observed_los_axis`` (0, 1 or 2,
+        default 2) and ``observed_bins`` (an int n for n equal bins over the map's range, or a list of ascending edges in mK; default
+        no histogram): the ``baseline_km``, ``los_axis`` and ``bins`` of those calls, and the defaults of :meth:`observed_map`."""
+        out = self._ld.get('Output') or {}
+        v = out.get('observed_map', 0)
+        if isinstance(v, (bool, np.bool_)):
+            v = int(v)
+        if not isinstance(v, (int, np.integer)) or v not in (0, 1):
+            raise ValueError(f"Output: observed_map must be 0 or 1, not {v!r}")
+        kw = {name: out[key] for key, name in (("observed_baseline_km", "baseline_km"), ("observed_los_axis", "los_axis"),
+                                               ("observed_bins", "bins")) if key in out}
+        self._observed_filter_spec("Output: observed_baseline_km / observed_los_axis", kw.get("baseline_km", 2.0), kw.get("los_axis", 2))
+        smoothing_spec("Output: observed_bins", None, bins=kw.get("bins"))     # ValueError for what a call would refuse, now
+        self.__dict__["_observed_defaults"] = kw
+        self.last_observed = None
+        self._set_observed_stats(bool(v), "Output: observed_map: 1")
+
+    @staticmethod
+    def _observed_filter_spec(who, baseline_km, los_axis):
+        if isinstance(baseline_km, (bool, np.bool_)) or not isinstance(baseline_km, (int, float, np.integer, np.floating)) \
+                or not (math.isfinite(baseline_km) and baseline_km > 0):
+            raise ValueError(f"{who}: baseline_km must be a finite number > 0, not {baseline_km!r}")
+        if isinstance(los_axis, (bool, np.bool_)) or not isinstance(los_axis, (int, np.integer)) or los_axis not in (0, 1, 2):
+            raise ValueError(f"{who}: los_axis must be 0, 1 or 2, not {los_axis!r}")
+        return float(baseline_km), int(los_axis)
+
+    def _set_observed_stats(self, value, who):
+        if not isinstance(value, (bool, np.bool_)):
+            raise ValueError(f"{who}: observed_stats must be a bool, not {type(value).__name__}")
+        if value and not self.gpu:
+            raise ValueError(f"{who}: observed_stats needs use_gpu=True (the transforms and the statistics run on the device)")
+        self.__dict__["_observed_stats"] = bool(value)
+
+    @property
+    def observed_stats(self):
+        """Does every time step end with the observed map of its state (:meth:`observed_map` with the ``Output: observed_*`` keys;
+        use_gpu=True only: on an object without, True is refused at the assignment)?  A driver may assign a bool between steps.
+        After a step ``last_observed`` holds the result and rank 0 writes one line to the log."""
+        return self.__dict__.get("_observed_stats", False)
+
+    @observed_stats.setter
+    def observed_stats(self, value):
+        self._set_observed_stats(value, "C2Ray.observed_stats")
+
+    def comoving_distance(self, z):
+        """The line-of-sight comoving distance to redshift z in Mpc, from the object's cosmology."""
+        if self._astropy:
+            return float(self.cosmology.comoving_distance(z).to('Mpc').value)
+        return float(self.cosmology.comoving_distance(z))
+
+    def beam_fwhm_cells(self, baseline_km=2.0, z=None):
+        """The resolution of an interferometer with maximum baseline `baseline_km` at redshift `z` (None: ``self.zred``) in cells of
+        the mesh: lambda_21 (1 + z) / B radians times the comoving distance to z, over the comoving cell size (the convention of
+        ``tools21cm.smooth_coeval``)."""
+        z = float(self.zred) if z is None else float(z)
+        theta = 0.211 * (1.0 + z) / (float(baseline_km) * 1e3)                  # lambda_21 = 21.1 cm
+        return theta * self.comoving_distance(z) / (self.dr_c / Mpc)
+
+    def smoothed_field(self, **kw):
+        """The current state multiplied by a filter in Fourier space, with its one-point statistics: a
+        :class:`pyc2ray_amd.smoothing.SmoothedField`; the keywords of :func:`pyc2ray_amd.smoothing.smoothed_field` but ``field``, and
+        ``spin``.  ``kind`` is 'dtb' unless given: the brightness temperature in mK, with ``scale`` =
+        :meth:`brightness_temperature_scale` unless given; ``spin`` as in :meth:`power_spectrum`.
+        While the ionised fraction of the last step lives on the device only (``device_resident``) and density and temperature
+        there are the host's, the grids are analysed there: nothing is downloaded.  Otherwise -- with ``use_mpi`` too -- the host
+        arrays are uploaded and analysed.  ``into`` writes a device grid behind the object's back: the object's own device copies
+        come down first, and every grid goes up again at the next step."""
+        if "field" in kw:
+            raise ValueError("C2Ray.smoothed_field: field is not for the class (it analyses its own grids)")
+        spin = kw.pop("spin", None)
+        if spin not in (None, "kinetic"):
+            raise ValueError(f"C2Ray.smoothed_field: spin must be None or 'kinetic', not {spin!r}")
+        if spin == "kinetic":
+            if "t_gamma" in kw:
+                raise ValueError("C2Ray.smoothed_field: spin='kinetic' sets t_gamma itself")
+            kw["t_gamma"] = float(self._ld['Cosmology']['cmbtemp']) * (1.0 + float(self.zred))
+        kw = {"scale": self.brightness_temperature_scale(), **kw}
+        spec = smoothing_spec("C2Ray.smoothed_field", self.N, **kw)
+        if not cuda_is_init():
+            raise RuntimeError("GPU not initialized. Please initialize it by calling device_init(N)")
+        lib = load_asora()
+        stale = {"ndens", "temp"} & self._host_newer
+        resident = self.device_resident and self.gpu and not self.mpi and "xh" in self._device_newer and not stale
+        if not resident or spec["into"] is not None:
+            _residency.reclaim()          # (this object's device copies among them: they come down first)
+            for which, grid in ((_capi.GRID_XH, self.xh), (_capi.GRID_NDENS, self.ndens), (_capi.GRID_TEMP, self.temp)):
+                lib.grid_to_device(which, np.asarray(grid, dtype=np.float64))
+        return smoothing_on_device(lib, spec, "C2Ray.smoothed_field")
+
+    def observed_map(self, baseline_km=None, los_axis=None, subtract_mean=True, **kw):
+        """The brightness temperature of the current state as an interferometer with maximum baseline `baseline_km` (default 2, or
+        ``Output: observed_baseline_km``) would see it: smoothed by a Gaussian beam of FWHM :meth:`beam_fwhm_cells` on the two axes
+        across the sky and by a top-hat of the same comoving width along `los_axis` (default 2, or ``Output: observed_los_axis``),
+        the mean removed unless ``subtract_mean=False``: :meth:`smoothed_field` with that filter, and its other keywords."""
+        if "filter" in kw:
+            raise ValueError("C2Ray.observed_map: the filter is the telescope's (smoothed_field takes any)")
+        d = self.__dict__.get("_observed_defaults", {})
+        baseline_km = d.get("baseline_km", 2.0) if baseline_km is None else baseline_km
+        los_axis = d.get("los_axis", 2) if los_axis is None else los_axis
+        baseline_km, los_axis = self._observed_filter_spec("C2Ray.observed_map", baseline_km, los_axis)
+        if "bins" in d:
+            kw = {"bins": d["bins"], **kw}
+        width = self.beam_fwhm_cells(baseline_km)
+        return self.smoothed_field(filter=telescope(width, width, los_axis), subtract_mean=subtract_mean, **kw)
+
+    def _close_observed(self):
+        """With ``observed_stats``: the observed map of the step just run becomes last_observed and joins the log."""
+        if not self.observed_stats:
+            return
+        self.last_observed = self.observed_map()
+        if self.rank == 0:
+            self.printlog(self.last_observed.log_line())
+
     def evolve3D(self, dt, src_flux, src_pos, src_spectrum=None):
         """Evolve the grid over one time step (c2ray_base.py:170-226).  src_spectrum: with ``BlackBodySource: Teff`` a list, the
         index into it of each source's temperature (None: every source the first one); see pyc2ray_amd.evolve3D."""
@@ -808,6 +938,7 @@ class C2Ray:
         self._close_topology()
         self._close_granulometry()
         self._close_power_spectrum()
+        self._close_observed()
 
     @classmethod
     def _fingerprint(cls, arr):
@@ -877,6 +1008,7 @@ class C2Ray:
         self._close_topology()
         self._close_granulometry()
         self._close_power_spectrum()
+        self._close_observed()
 
     def cosmo_evolve(self, dt):
         """Advance time and redshift by dt, diluting density and rescaling the cell size when the run is

@@ -109,6 +109,8 @@ static int release_all()
     drop(st.gran_work); drop(st.gran_mask); drop(st.gran_result);
     drop(st.ps_modes[0]); drop(st.ps_modes[1]); drop(st.ps_twiddle); drop(st.ps_partial); drop(st.ps_thresholds);
     if (st.ps_host) { (void)hipHostFree(st.ps_host); st.ps_host = nullptr; }
+    drop(st.sm_field); drop(st.sm_tables); drop(st.sm_partial); drop(st.sm_result);
+    if (st.sm_host) { (void)hipHostFree(st.sm_host); st.sm_host = nullptr; }
     for (int g = 0; g < ASORA_GRID_COUNT; ++g) { st.grid[g] = nullptr; st.grid_valid[g] = false; }
     st.nhi = st.staging = st.acc = nullptr;
     drop(st.arena); st.arena_bytes = 0;

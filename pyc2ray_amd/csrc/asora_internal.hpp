@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <initializer_list>
 #include <string>
 #include <vector>
@@ -284,6 +285,13 @@ struct State {
     double *ps_partial = nullptr, *ps_host = nullptr;
     unsigned *ps_thresholds = nullptr;
     double ps_ms[ASORA_PS_STAGES] = {0, 0, 0, 0, 0};
+    // the smoothing's own buffers (asora_smooth_field, smooth_field.hip), allocated by the first call that needs them: the output
+    // field [N^3] of a call without dst_grid; the filter tables w_i, w_j, w_k [N each], w_r [3 floor(N/2)^2 + 1] and the histogram's
+    // edges behind them; the workgroups' partial statistics; the result words (stats, then the histogram); and the pinned area the
+    // tables and edges leave the host through and the results arrive in.  The complex buffer, the roots and the forward pass's
+    // partial sums are the power spectrum's.  sm_ms: the stage times of the last call under ASORA_OPT_TIMING
+    double *sm_field = nullptr, *sm_tables = nullptr, *sm_partial = nullptr, *sm_result = nullptr, *sm_host = nullptr;
+    double sm_ms[ASORA_SMOOTH_STAGES] = {0, 0, 0, 0, 0, 0, 0, 0};
 
     unsigned long long *counters = nullptr; // [COUNTER_FIELDS * COUNTER_SLOTS] device: gamma cells, evaluated cells, exact zeros left out, spread over the slots
     long long last_gamma_cells = 0, last_eval_cells = 0;
@@ -620,5 +628,9 @@ int launch_bubble_mask(State &st, int which, double threshold, int phase, bool s
 // root's volume (0 elsewhere)
 int ensure_region_buffers(State &st);
 int launch_region_label(State &st, const unsigned long long *mask, int periodic, int connectivity);
+// power_spectrum.hip: what asora_smooth_field (smooth_field.hip) shares with asora_power_spectrum -- which grids a kind reads, and
+// the forward transform of one field into State::ps_modes[0] (the mean density, the pass along k with the moments, along j, along i)
+bool ps_needs_grid(int kind, int grid, double t_gamma);
+int ps_forward(State &st, int kind, double scale, double t_gamma, const std::function<int()> &stage_done, const double **moments_dev);
 
 } // namespace asora

@@ -14,68 +14,21 @@
 //                     non-decreasing, reduces each run of equal bins by a segmented scan in lane order, and the last lane of a run
 //                     adds into the wave's own LDS histogram by plain read-modify-write; the waves' histograms are combined in wave
 //                     order into the plane's partial row, and ps_bin_final_kernel adds the planes in plane order.
-// The line transform (line_fft) is a mixed-radix Stockham autosort between two LDS buffers: a stage of radix p reads element
-// idx + j N/p, j = 0 ... p - 1 -- contiguous in the work-item index -- and writes r + p (idx - r) + s k with the twiddle
-// tw[(idx - r) k], r = idx mod s, s the product of the radices so far.  Radices 4, 2, 3, 5 and 7 have butterflies in registers, any
-// other prime factor p a generic one of p multiply-adds per output (one work item per OUTPUT, so a prime N still fills the
-// workgroup): N = 1 ... 645 all work, and the cost of a line grows with the sum of N's prime factors beyond 7 (N = 43 p, or prime,
-// is slow).  tw[r] = exp(-2 pi i r / N), r = 0 ... N - 1, is tabulated once per mesh on the host in extended precision; no index
-// beyond N - 1 is formed, no angle is multiplied, no recurrence is used.  Lines are stored with an odd pitch.
+// The line transform (line_fft), its plan, tile and LDS layout, the forming of the field and the double-double sums are shared with
+// the smoothing (smooth_field.hip): fft_device.hpp.
 // Every floating-point sum is formed in an order fixed by (N, thresholds): per thread in index order, per wave by a shuffle tree,
 // per workgroup in wave order, over workgroups in index order -- the mean density and the moments in double-double (two-sum), so
 // that they are correct to the last bit or two whatever the order.  No floating-point atomic anywhere.
 #include "asora_internal.hpp"
+#include "fft_device.hpp"
 
 namespace asora {
 
-constexpr int PS_THREADS = 256;
-constexpr int PS_WAVES = PS_THREADS / 64;
-constexpr int PS_RED_BLOCKS = 512;          // the workgroups of the mean-density sum: a constant, so that the order is the mesh's alone
-constexpr int PS_MAX_FACTORS = 12;          // (2^12 > 645)
 constexpr int PS_VALUES = 5;                // per bin: count, sum_k, sum_aa, sum_bb, sum_ab
 constexpr int PS_COUNT = 0, PS_SUM_K = 1, PS_SUM_AA = 2, PS_SUM_BB = 3, PS_SUM_AB = 4;
 // the result words (doubles; the counts are uint64 in the same 8 bytes): the bins, the moments of a and of b, the mean density
 constexpr int PS_RES_MOMENTS = PS_VALUES * ASORA_BUBBLE_MAX_BINS, PS_RES_NBAR = PS_RES_MOMENTS + 4, PS_RES_WORDS = PS_RES_NBAR + 1;
 constexpr int PS_HOST_WORDS = PS_RES_WORDS + (ASORA_BUBBLE_MAX_BINS + 2) / 2;     // the thresholds (uint32) behind the results
-
-struct PsPlan {
-    int nf;
-    int radix[PS_MAX_FACTORS];
-};
-
-// ---- double-double sums ------------------------------------------------------------------------------------------------------
-struct dd { double hi, lo; };
-__device__ __forceinline__ void dd_add(dd &a, double x)
-{
-    const double s = a.hi + x, b = s - a.hi;
-    a.lo += (a.hi - (s - b)) + (x - b);
-    a.hi = s;
-}
-__device__ __forceinline__ void dd_merge(dd &a, const dd &o)
-{
-    dd_add(a, o.hi);
-    a.lo += o.lo;
-}
-// the sum of v over the workgroup in lane, then wave order; every thread calls it and gets the result
-__device__ __forceinline__ dd ps_block_sum(dd v)
-{
-    __shared__ double sh[2 * PS_WAVES];
-    for (int o = 32; o > 0; o >>= 1) {
-        dd other;
-        other.hi = __shfl_down(v.hi, o);
-        other.lo = __shfl_down(v.lo, o);
-        dd_merge(v, other);
-    }
-    if ((threadIdx.x & 63) == 0) { sh[2 * (threadIdx.x >> 6)] = v.hi; sh[2 * (threadIdx.x >> 6) + 1] = v.lo; }
-    __syncthreads();
-    dd r = {sh[0], sh[1]};
-    for (int q = 1; q < PS_WAVES; ++q) {
-        dd o = {sh[2 * q], sh[2 * q + 1]};
-        dd_merge(r, o);
-    }
-    __syncthreads();
-    return r;
-}
 
 // partial[2 b], [2 b + 1] = the double-double sum of a[] over the cells of workgroup b (grid-stride; the grid is PS_RED_BLOCKS)
 __global__ void __launch_bounds__(PS_THREADS) ps_sum_kernel(const double *__restrict__ a, size_t n, double *__restrict__ partial)
@@ -100,150 +53,6 @@ __global__ void __launch_bounds__(PS_THREADS) ps_final_kernel(const double *__re
         }
         s = ps_block_sum(s);
         if (threadIdx.x == 0) out[q] = (s.hi + s.lo) / divisor;
-    }
-}
-
-// ---- the line transform --------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ double2 csub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ double2 cmul(double2 a, double2 w) { return make_double2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x); }
-
-// cos and sin of 2 pi m / P, m = 1 ... (P - 1) / 2, for P = 3, 5, 7
-template <int P> __device__ __forceinline__ constexpr double root_cos(int m)
-{
-    return P == 3 ? -0.5
-         : P == 5 ? (m == 1 ? 0.30901699437494742410 : -0.80901699437494742410)
-                  : (m == 1 ? 0.62348980185873353053 : m == 2 ? -0.22252093395631440429 : -0.90096886790241912624);
-}
-template <int P> __device__ __forceinline__ constexpr double root_sin(int m)
-{
-    return P == 3 ? 0.86602540378443864676
-         : P == 5 ? (m == 1 ? 0.95105651629515357212 : 0.58778525229247312917)
-                  : (m == 1 ? 0.78183148246802980871 : m == 2 ? 0.97492791218182360702 : 0.43388373911755812048);
-}
-
-template <int P> __device__ __forceinline__ void butterfly(double2 (&a)[P])
-{
-    if constexpr (P == 2) {
-        const double2 t = a[1];
-        a[1] = csub(a[0], t);
-        a[0] = cadd(a[0], t);
-    } else if constexpr (P == 4) {
-        const double2 t0 = cadd(a[0], a[2]), t1 = csub(a[0], a[2]), t2 = cadd(a[1], a[3]), t3 = csub(a[1], a[3]);
-        a[0] = cadd(t0, t2);
-        a[2] = csub(t0, t2);
-        a[1] = make_double2(t1.x + t3.y, t1.y - t3.x);      // t1 - i t3
-        a[3] = make_double2(t1.x - t3.y, t1.y + t3.x);      // t1 + i t3
-    } else {
-        // odd P: b_k, b_(P-k) = a_0 + sum_j cos(2 pi j k / P) (a_j + a_(P-j)) -/+ i sum_j sin(2 pi j k / P) (a_j - a_(P-j))
-        constexpr int H = (P - 1) / 2;
-        double2 u[H], v[H];
-#pragma unroll
-        for (int j = 1; j <= H; ++j) { u[j - 1] = cadd(a[j], a[P - j]); v[j - 1] = csub(a[j], a[P - j]); }
-        const double2 a0 = a[0];
-        double2 sum = a0;
-#pragma unroll
-        for (int j = 0; j < H; ++j) sum = cadd(sum, u[j]);
-        a[0] = sum;
-#pragma unroll
-        for (int k = 1; k <= H; ++k) {
-            double re = a0.x, im = a0.y, sr = 0.0, si = 0.0;
-#pragma unroll
-            for (int j = 1; j <= H; ++j) {
-                const int m = (j * k) % P;
-                const double c = m <= H ? root_cos<P>(m) : root_cos<P>(P - m);
-                const double s = m <= H ? root_sin<P>(m) : -root_sin<P>(P - m);
-                re += c * u[j - 1].x; im += c * u[j - 1].y;
-                sr += s * v[j - 1].x; si += s * v[j - 1].y;
-            }
-            a[k] = make_double2(re + si, im - sr);
-            a[P - k] = make_double2(re - si, im + sr);
-        }
-    }
-}
-
-// one Stockham stage of radix P over nl lines of length N (pitch apart) from x to y; s: the product of the radices before it
-template <int P> __device__ __forceinline__ void stage_fixed(const double2 *x, double2 *y, const double2 *tw, int N, int pitch, int nl, int s)
-{
-    const int L = N / P;
-    for (int w = threadIdx.x; w < nl * L; w += PS_THREADS) {
-        const int t = w / L, idx = w - t * L, base = idx - idx % s;
-        const double2 *xl = x + t * pitch;
-        double2 *yl = y + t * pitch + (idx - base) + P * base;
-        double2 a[P];
-#pragma unroll
-        for (int j = 0; j < P; ++j) a[j] = xl[idx + L * j];
-        butterfly<P>(a);
-        yl[0] = a[0];
-#pragma unroll
-        for (int k = 1; k < P; ++k) yl[s * k] = cmul(a[k], tw[base * k]);      // (base k < N)
-    }
-}
-
-// the same for any radix p: one work item per output k of a butterfly, p multiply-adds each; tw[m N/p] = exp(-2 pi i m / p)
-__device__ __forceinline__ void stage_generic(const double2 *x, double2 *y, const double2 *tw, int N, int pitch, int nl, int s, int p)
-{
-    const int L = N / p;
-    for (int w = threadIdx.x; w < nl * N; w += PS_THREADS) {
-        const int t = w / N, rem = w - t * N, k = rem / L, idx = rem - k * L, base = idx - idx % s;
-        const double2 *xl = x + t * pitch + idx;
-        double2 acc = xl[0];
-        int m = 0;
-        for (int j = 1; j < p; ++j) {
-            m += k;
-            m = m >= p ? m - p : m;                                           // (j k) mod p
-            acc = cadd(acc, cmul(xl[L * j], tw[m * L]));
-        }
-        y[t * pitch + (idx - base) + p * base + s * k] = cmul(acc, tw[base * k]);
-    }
-}
-
-// the transform of nl lines of length N, line t at a[t pitch ...]; b: a second buffer of the same size; tw: the N roots of unity.
-// Every thread of the workgroup calls it; returns the buffer that holds the result (a or b), synchronised
-__device__ __forceinline__ double2 *line_fft(double2 *a, double2 *b, const double2 *tw, const PsPlan &plan, int N, int pitch, int nl)
-{
-    int s = 1;
-    for (int f = 0; f < plan.nf; ++f) {
-        const int p = plan.radix[f];
-        __syncthreads();
-        switch (p) {
-        case 2: stage_fixed<2>(a, b, tw, N, pitch, nl, s); break;
-        case 3: stage_fixed<3>(a, b, tw, N, pitch, nl, s); break;
-        case 4: stage_fixed<4>(a, b, tw, N, pitch, nl, s); break;
-        case 5: stage_fixed<5>(a, b, tw, N, pitch, nl, s); break;
-        case 7: stage_fixed<7>(a, b, tw, N, pitch, nl, s); break;
-        default: stage_generic(a, b, tw, N, pitch, nl, s, p); break;
-        }
-        double2 *t = a; a = b; b = t;
-        s *= p;
-    }
-    __syncthreads();
-    return a;
-}
-
-// the dynamic LDS of the two transform kernels: the roots of unity [N], then the two line buffers [T pitch] each
-__device__ __forceinline__ void ps_lds_layout(double2 *lds, const double2 *__restrict__ twiddle, int N, int pitch, int T, double2 *&tw,
-                                              double2 *&a, double2 *&b)
-{
-    tw = lds;
-    a = lds + N;
-    b = a + (size_t)T * pitch;
-    for (int r = threadIdx.x; r < N; r += PS_THREADS) tw[r] = twiddle[r];
-}
-
-// g of a cell (the header's order of operations; nothing here may be contracted into a fused multiply-add)
-__device__ __forceinline__ double ps_form(int kind, size_t c, const double *__restrict__ x, const double *__restrict__ n,
-                                          const double *__restrict__ temp, double nbar, double scale, double t_gamma)
-{
-#pragma clang fp contract(off)
-    switch (kind) {
-    case ASORA_PS_XH: return x[c];
-    case ASORA_PS_XHI: return 1.0 - x[c];
-    case ASORA_PS_DENSITY: return n[c] / nbar;
-    default: {
-        const double g = (scale * (1.0 - x[c])) * (n[c] / nbar);
-        return t_gamma > 0.0 ? g * (1.0 - t_gamma / temp[c]) : g;
-    }
     }
 }
 
@@ -415,28 +224,6 @@ __global__ void __launch_bounds__(PS_THREADS) ps_bin_final_kernel(const double *
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
-// lines per workgroup: the most of 16, 8 whose two buffers and roots fit 72 KiB of LDS (two workgroups per CU), else 4 (N > 271;
-// 91 KiB at N = 645)
-static int ps_tile(int N)
-{
-    for (int T : {16, 8})
-        if (((size_t)2 * T * (N | 1) + N) * sizeof(double2) <= (size_t)72 * 1024) return T;
-    return 4;
-}
-
-static PsPlan ps_plan(int N)
-{
-    PsPlan plan{};
-    int n = N;
-    auto take = [&plan](int n, int p) {
-        while (n > 1 && n % p == 0) { plan.radix[plan.nf++] = p; n /= p; }
-        return n;
-    };
-    for (int p : {4, 2, 3, 5, 7}) n = take(n, p);
-    for (int p = 11; n > 1; p += 2) n = take(n, p);
-    return plan;
-}
-
 // the words of ps_partial: [bins: N PS_VALUES MAX_BINS | moments of a, of b: row workgroups x 4 each | mean density: 2 PS_RED_BLOCKS
 // | results: PS_RES_WORDS]
 struct PsLayout {
@@ -492,31 +279,7 @@ static int ensure_ps_buffers(State &st, const PsLayout &lay, bool cross)
     return 0;
 }
 
-// a host-side stopwatch of the stages: events on the library's stream, only with ASORA_OPT_TIMING
-struct PsStopwatch {
-    bool on;
-    hipStream_t stream;
-    hipEvent_t ev[ASORA_PS_STAGES + 1] = {};
-    int n = 0;
-    PsStopwatch(bool on_, hipStream_t s) : on(on_), stream(s) {}
-    ~PsStopwatch() { for (int q = 0; q <= ASORA_PS_STAGES; ++q) if (ev[q]) (void)hipEventDestroy(ev[q]); }
-    int mark()
-    {
-        if (!on || n > ASORA_PS_STAGES) return 0;
-        ASORA_HIP_TRY(hipEventCreate(&ev[n]));
-        ASORA_HIP_TRY(hipEventRecord(ev[n], stream));
-        ++n;
-        return 0;
-    }
-    void read(double *ms) const
-    {
-        if (!on || n != ASORA_PS_STAGES + 1) return;
-        for (int q = 0; q < ASORA_PS_STAGES; ++q) {
-            float t = 0.0f;
-            ms[q] = hipEventElapsedTime(&t, ev[q], ev[q + 1]) == hipSuccess ? (double)t : 0.0;
-        }
-    }
-};
+using PsStopwatch = StageStopwatch<ASORA_PS_STAGES>;
 
 struct PsFieldCopy {                     // the formed field on the device, for field_out: freed when the call ends, however it ends
     double *dev = nullptr;
@@ -530,6 +293,92 @@ static bool ps_kind_uses(int kind, int grid, double t_gamma)
     case ASORA_GRID_NDENS: return kind == ASORA_PS_DENSITY || kind == ASORA_PS_HI;
     default: return kind == ASORA_PS_HI && t_gamma > 0.0;       // ASORA_GRID_TEMP
     }
+}
+
+bool ps_needs_grid(int kind, int grid, double t_gamma) { return ps_kind_uses(kind, grid, t_gamma); }
+
+// The launches of stages a to c on the library's stream, for asora_power_spectrum and for ps_forward: field f of a kind goes into
+// st.ps_modes[f], its moments into the result words
+struct PsPasses {
+    State &st;
+    const int N, NZ, T, pitch;
+    const PsLayout lay;
+    const PsPlan plan;
+    const size_t fft_lds;
+    const dim3 block{PS_THREADS};
+    explicit PsPasses(State &s)
+        : st(s), N(s.N), NZ(s.N / 2 + 1), T(ps_tile(s.N)), pitch(s.N | 1), lay(s.N, ps_tile(s.N)), plan(ps_plan(s.N)),
+          fft_lds(((size_t)2 * ps_tile(s.N) * (s.N | 1) + s.N) * sizeof(double2)) {}
+    double *partial() const { return st.ps_partial; }
+    double *result() const { return st.ps_partial + lay.result; }
+    int prepare(bool cross)
+    {
+        if (int rc = ensure_ps_buffers(st, lay, cross)) return rc;
+        ASORA_HIP_TRY(hipFuncSetAttribute((const void *)ps_row_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fft_lds));
+        ASORA_HIP_TRY(hipFuncSetAttribute((const void *)ps_line_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fft_lds));
+        return 0;
+    }
+    int mean_density()
+    {
+        hipLaunchKernelGGL(ps_sum_kernel, dim3(PS_RED_BLOCKS), block, 0, st.stream, (const double *)st.grid[ASORA_GRID_NDENS], st.ncell,
+                           partial() + lay.nbar);
+        ASORA_HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(ps_final_kernel, dim3(1), block, 0, st.stream, (const double *)(partial() + lay.nbar), PS_RED_BLOCKS, 1,
+                           (double)st.ncell, result() + PS_RES_NBAR);
+        ASORA_HIP_TRY(hipGetLastError());
+        return 0;
+    }
+    int rows(int f, int kind, bool nbar, double scale, double t_gamma, double *field)     // along k, with the field and its moments
+    {
+        hipLaunchKernelGGL(ps_row_kernel, dim3((unsigned)lay.row_blocks), block, fft_lds, st.stream, kind,
+                           (const double *)st.grid[ASORA_GRID_XH], (const double *)st.grid[ASORA_GRID_NDENS],
+                           (const double *)st.grid[ASORA_GRID_TEMP], nbar ? (const double *)(result() + PS_RES_NBAR) : (const double *)nullptr,
+                           scale, t_gamma, N, pitch, T, plan, (const double2 *)st.ps_twiddle, st.ps_modes[f], partial() + lay.moments[f],
+                           field);
+        ASORA_HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(ps_final_kernel, dim3(1), block, 0, st.stream, (const double *)(partial() + lay.moments[f]), (int)lay.row_blocks,
+                           2, 1.0, result() + PS_RES_MOMENTS + 2 * f);
+        ASORA_HIP_TRY(hipGetLastError());
+        return 0;
+    }
+    int lines_j(int f)                  // N blocks (the planes i) of N lines, NZ columns wide
+    {
+        const unsigned tiles = (unsigned)((NZ + T - 1) / T);
+        hipLaunchKernelGGL(ps_line_kernel, dim3((unsigned)N * tiles), block, fft_lds, st.stream, st.ps_modes[f], N, pitch, T, plan,
+                           (const double2 *)st.ps_twiddle, (size_t)N * NZ, (size_t)NZ, (size_t)NZ, tiles);
+        ASORA_HIP_TRY(hipGetLastError());
+        return 0;
+    }
+    int lines_i(int f)                  // one block of N lines, N NZ columns wide
+    {
+        const unsigned tiles = (unsigned)(((size_t)N * NZ + T - 1) / T);
+        hipLaunchKernelGGL(ps_line_kernel, dim3(tiles), block, fft_lds, st.stream, st.ps_modes[f], N, pitch, T, plan,
+                           (const double2 *)st.ps_twiddle, (size_t)0, (size_t)N * NZ, (size_t)N * NZ, tiles);
+        ASORA_HIP_TRY(hipGetLastError());
+        return 0;
+    }
+};
+
+// The forward half of asora_smooth_field (smooth_field.hip): stages a to c above for the one field of `kind`, into st.ps_modes[0] --
+// the launches of an auto-spectrum, so the modes and the moments are its bits.  The caller has checked the kind and its grids.
+// stage_done is called behind each of the four stages (mean density, along k, j, i); *moments_dev: where (sum g, sum g^2) lie on the
+// device once the stream has got there
+int ps_forward(State &st, int kind, double scale, double t_gamma, const std::function<int()> &stage_done, const double **moments_dev)
+{
+    PsPasses pass(st);
+    if (int rc = pass.prepare(false)) return rc;
+    const bool nbar = ps_kind_uses(kind, ASORA_GRID_NDENS, t_gamma);
+    if (nbar)
+        if (int rc = pass.mean_density()) return rc;
+    if (int rc = stage_done()) return rc;
+    if (int rc = pass.rows(0, kind, nbar, scale, t_gamma, nullptr)) return rc;
+    if (int rc = stage_done()) return rc;
+    if (int rc = pass.lines_j(0)) return rc;
+    if (int rc = stage_done()) return rc;
+    if (int rc = pass.lines_i(0)) return rc;
+    if (int rc = stage_done()) return rc;
+    *moments_dev = pass.result() + PS_RES_MOMENTS;
+    return 0;
 }
 
 } // namespace asora
@@ -568,20 +417,16 @@ int asora_power_spectrum(int kind_a, int kind_b, double scale, double t_gamma, i
     if (st.N > ASORA_REGION_MAX_N)
         return fail(4, "power_spectrum: not built for N > " + std::to_string(ASORA_REGION_MAX_N) + " (a line and its roots must fit LDS)");
 
-    const int N = st.N, NZ = N / 2 + 1, T = ps_tile(N), pitch = N | 1;
-    const size_t ncell = st.ncell, nmodes = (size_t)N * N * NZ;
-    const PsLayout lay(N, T);
-    const PsPlan plan = ps_plan(N);
-    if (int rc = ensure_ps_buffers(st, lay, cross)) return rc;
+    PsPasses pass(st);
+    const int N = st.N, nf = cross ? 2 : 1;
+    const size_t ncell = st.ncell, nmodes = (size_t)N * N * pass.NZ;
+    const PsLayout &lay = pass.lay;
+    if (int rc = pass.prepare(cross)) return rc;
     PsFieldCopy field;
     if (field_out) ASORA_HIP_TRY(hipMalloc(&field.dev, sizeof(double) * ncell));
 
-    const size_t fft_lds = ((size_t)2 * T * pitch + N) * sizeof(double2);
     const size_t bin_lds = (size_t)PS_WAVES * PS_VALUES * n_bins * sizeof(double) + sizeof(unsigned) * (n_bins + 1);
-    ASORA_HIP_TRY(hipFuncSetAttribute((const void *)ps_row_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fft_lds));
-    ASORA_HIP_TRY(hipFuncSetAttribute((const void *)ps_line_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fft_lds));
-
-    double *part = st.ps_partial, *res = part + lay.result;
+    double *part = pass.partial(), *res = pass.result();
     unsigned *thr_host = (unsigned *)(st.ps_host + PS_RES_WORDS);
     std::memcpy(thr_host, thresholds, sizeof(unsigned) * (n_bins + 1));
     ASORA_HIP_TRY(hipMemcpyAsync(st.ps_thresholds, thr_host, sizeof(unsigned) * (n_bins + 1), hipMemcpyHostToDevice, st.stream));
@@ -590,38 +435,17 @@ int asora_power_spectrum(int kind_a, int kind_b, double scale, double t_gamma, i
     PsStopwatch watch(st.opt[ASORA_OPT_TIMING] != 0, st.stream);
 
     if (int rc = watch.mark()) return rc;
-    if (need[1]) {
-        hipLaunchKernelGGL(ps_sum_kernel, dim3(PS_RED_BLOCKS), block, 0, st.stream, (const double *)st.grid[ASORA_GRID_NDENS], ncell, part + lay.nbar);
-        ASORA_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(ps_final_kernel, dim3(1), block, 0, st.stream, (const double *)(part + lay.nbar), PS_RED_BLOCKS, 1, (double)ncell,
-                           res + PS_RES_NBAR);
-        ASORA_HIP_TRY(hipGetLastError());
-    }
+    if (need[1])
+        if (int rc = pass.mean_density()) return rc;
     if (int rc = watch.mark()) return rc;
-    for (int f = 0; f < (cross ? 2 : 1); ++f) {
-        hipLaunchKernelGGL(ps_row_kernel, dim3((unsigned)lay.row_blocks), block, fft_lds, st.stream, kinds[f],
-                           (const double *)st.grid[ASORA_GRID_XH], (const double *)st.grid[ASORA_GRID_NDENS],
-                           (const double *)st.grid[ASORA_GRID_TEMP], need[1] ? (const double *)(res + PS_RES_NBAR) : (const double *)nullptr,
-                           scale, t_gamma, N, pitch, T, plan, (const double2 *)st.ps_twiddle, st.ps_modes[f], part + lay.moments[f],
-                           f == 0 ? field.dev : (double *)nullptr);
-        ASORA_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(ps_final_kernel, dim3(1), block, 0, st.stream, (const double *)(part + lay.moments[f]), (int)lay.row_blocks, 2, 1.0,
-                           res + PS_RES_MOMENTS + 2 * f);
-        ASORA_HIP_TRY(hipGetLastError());
-    }
+    for (int f = 0; f < nf; ++f)
+        if (int rc = pass.rows(f, kinds[f], need[1], scale, t_gamma, f == 0 ? field.dev : (double *)nullptr)) return rc;
     if (int rc = watch.mark()) return rc;
-    const unsigned tiles_j = (unsigned)((NZ + T - 1) / T), tiles_i = (unsigned)(((size_t)N * NZ + T - 1) / T);
-    for (int f = 0; f < (cross ? 2 : 1); ++f) {        // along j: N blocks (the planes i) of N lines, NZ columns wide
-        hipLaunchKernelGGL(ps_line_kernel, dim3((unsigned)N * tiles_j), block, fft_lds, st.stream, st.ps_modes[f], N, pitch, T, plan,
-                           (const double2 *)st.ps_twiddle, (size_t)N * NZ, (size_t)NZ, (size_t)NZ, tiles_j);
-        ASORA_HIP_TRY(hipGetLastError());
-    }
+    for (int f = 0; f < nf; ++f)
+        if (int rc = pass.lines_j(f)) return rc;
     if (int rc = watch.mark()) return rc;
-    for (int f = 0; f < (cross ? 2 : 1); ++f) {        // along i: one block of N lines, N NZ columns wide
-        hipLaunchKernelGGL(ps_line_kernel, dim3(tiles_i), block, fft_lds, st.stream, st.ps_modes[f], N, pitch, T, plan,
-                           (const double2 *)st.ps_twiddle, (size_t)0, (size_t)N * NZ, (size_t)N * NZ, tiles_i);
-        ASORA_HIP_TRY(hipGetLastError());
-    }
+    for (int f = 0; f < nf; ++f)
+        if (int rc = pass.lines_i(f)) return rc;
     if (int rc = watch.mark()) return rc;
     const int nv = cross ? PS_VALUES : PS_SUM_AA + 1;
     if (cross)

@@ -562,6 +562,49 @@ class _LibAsora:
         _capi.check(self._lib.asora_debug_power_spectrum_ms(_capi.dptr(ms)), "debug_power_spectrum_ms")
         return ms
 
+    def smooth_field(self, kind, scale, t_gamma, w_i=None, w_j=None, w_k=None, w_r=None, subtract_mean=False, edges=None, dst_grid=None,
+                     field=False):
+        """The field of kind `kind` (``_capi.PS_*``) formed from the device grids, multiplied by the filter of the tables `w_i`, `w_j`,
+        `w_k` ((N,) each) and `w_r` ((3 (N // 2)^2 + 1,)) -- None: all ones -- in Fourier space and transformed back, with its
+        one-point statistics (include/asora_hip.h, asora_smooth_field): a dict of ``stats`` (``_capi.SMOOTH_STATS`` float64, indexed
+        by ``_capi.SMOOTH_*``), ``hist`` (with `edges`: uint64, the ``len(edges) - 1`` bins, then the cells below and the cells at or
+        above; else None) and ``field`` (with `field`: (N, N, N) float64; else None).  `dst_grid`: the grid the result is written
+        into (None: a buffer of the library's own)."""
+        tables = []
+        for name, w in (("w_i", w_i), ("w_j", w_j), ("w_k", w_k), ("w_r", w_r)):
+            if w is not None:
+                w = np.ascontiguousarray(w, dtype=np.float64)
+                if w.ndim != 1:
+                    raise ValueError(f"smooth_field: {name} must be one-dimensional")
+                if name != "w_r" and (self._N is None or w.size != self._N):       # (the library reads N entries; w_r carries its length)
+                    raise ValueError(f"smooth_field: {name} must have the N = {self._N} entries of the mesh of device_init, not {w.size}")
+            tables.append(w)
+        e = None
+        if edges is not None:
+            e = np.ascontiguousarray(edges, dtype=np.float64)
+            if e.ndim != 1 or e.size < 2:
+                raise ValueError("smooth_field: edges must be one-dimensional, two or more")
+        out = dict(stats=np.zeros(_capi.SMOOTH_STATS), hist=None if e is None else np.zeros(e.size + 1, dtype=np.uint64), field=None)
+        if field:
+            if self._N is None:
+                raise RuntimeError("smooth_field with field needs a device initialised through device_init (the mesh size)")
+            out["field"] = np.zeros((self._N,) * 3)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(_capi._dp)
+        _capi.check(self._lib.asora_smooth_field(int(kind), float(scale), float(t_gamma), ptr(tables[0]), ptr(tables[1]), ptr(tables[2]),
+                                                 ptr(tables[3]), 0 if tables[3] is None else int(tables[3].size), 1 if subtract_mean else 0,
+                                                 0 if e is None else int(e.size) - 1, ptr(e), -1 if dst_grid is None else int(dst_grid),
+                                                 ptr(out["stats"]), None if e is None else out["hist"].ctypes.data_as(_capi._u64p),
+                                                 ptr(out["field"])), "smooth_field")
+        return out
+
+    def smooth_field_ms(self):
+        """The stage times (ms) of the last smooth_field call that ran with OPT_TIMING: mean density, forward along k, j, i, back
+        along i with the filter, along j, along k with the first statistics, the central moments and the histogram
+        (include/asora_hip.h, asora_debug_smooth_field_ms)."""
+        ms = np.zeros(_capi.SMOOTH_STAGES)
+        _capi.check(self._lib.asora_debug_smooth_field_ms(_capi.dptr(ms)), "debug_smooth_field_ms")
+        return ms
+
     def thermal_stats(self):
         """(cells that hit max_substeps, cells clamped to t_floor, most substeps of one integration) since the last
         chemistry_device / evolve_begin."""
