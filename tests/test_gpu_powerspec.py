@@ -12,13 +12,21 @@ whole spectrum's norm, which the error of the transform is relative to: sqrt(S_b
 
 * Transform meshes: every specialised radix alone (2, 3, 4, 5, 7), the generic butterfly (17, 43, 129 = 3 x 43), repeated and
   mixed radices, odd and even N, tail tiles of the strided passes (N / 2 + 1 no multiple of the tile), several lines per workgroup
-  and several trips of the mean-density sum; N = 250 with the binned sums only."""
+  and several trips of the mean-density sum; N = 250 and 280 with the binned sums only.
+* The meshes of tests/fft_meshes.py (121, 139, 140, 169, 243, 256, 271, 272, 273; each row says what it is there for, and
+  tests/test_fft_meshes_host.py checks that it is so): the generic stage twice in one plan, five stages, primes up to 271, both
+  edges of the tile rule (139 | 140, 271 | 272), tail tiles and a tail row workgroup at 16, 8 and 4 lines per workgroup, and
+  256^3 -- the modes against numpy, the sums, Parseval, the moments.  At 169 (two trips of the binning's loop over n_z) the cross
+  form with two different fields and both forms with 256 bins; 121 and 273 form every kind of field (uneven trips of the
+  mean-density sum)."""
 import ctypes as C
+import functools
 import os
 
 import numpy as np
 import pytest
 
+import fft_meshes as FM
 import powerspec_reference as PR
 
 pytestmark = pytest.mark.gpu
@@ -80,13 +88,13 @@ def _check_sums(N, got, want, what):
 
 
 @pytest.mark.parametrize("N", MESHES)
-def test_transform_sums_and_parseval(asora, N):
+def test_transform_sums_and_parseval(asora, N, only=None):
     p, lib, capi = asora
     _mesh(asora, N)
     field = PR.noise_with_block(N, 1000 + N)
     lib.grid_to_device(capi.GRID_XH, field)
     c = PR.c_of_N(N)
-    sets = _bin_sets(N)
+    sets = {name: edges for name, edges in _bin_sets(N).items() if only is None or name in only}
     got = _twice(lib, capi.PS_XH, None, 1.0, 0.0, PR.thresholds_of(sets["default"]), field=True, modes=True)
     # 6. the formed field of kind xh is the grid, bit for bit; 1. its transform against numpy's of the downloaded field
     assert got["field"].tobytes() == field.tobytes() and got["modes"].shape == (N, N, N // 2 + 1)
@@ -117,6 +125,14 @@ def test_transform_sums_and_parseval(asora, N):
                 assert abs(power - spread) <= 4.0 * c * spread
     want_m = np.array([float(PR.exact_sum(field)), float(PR.exact_sum(field * field))])
     assert np.all(np.abs(got["moments_a"] - want_m) <= 1e-13 * np.abs(want_m)), (got["moments_a"].tolist(), want_m.tolist())
+
+
+@pytest.mark.parametrize("N", FM.MESHES)
+def test_transform_at_the_meshes_of_the_table(asora, N):
+    """The same assertions at the meshes of tests/fft_meshes.py: two generic stages, five stages, primes beyond a workgroup's work
+    items, both edges of the tile rule, tails at 8 and at 4 lines per workgroup, 256^3.  From N = 243 on the `default` and `all` bin
+    sets only (numpy's transform and the reference's binning take a second each there)."""
+    test_transform_sums_and_parseval(asora, N, only=("default", "all") if N >= FM.FEW_BIN_SETS_FROM else None)
 
 
 def test_a_single_cell_is_no_mesh_of_the_library(asora):
@@ -224,8 +240,111 @@ def test_cross_spectra(asora):
         assert np.all(np.abs(ab[key] - want[key]) <= 1e-13 * np.abs(want[key])), key
 
 
-@pytest.mark.parametrize("N", [17, 64])
+N_TRIPS = 169         # NZ = 85: the binning's loop over n_z makes two trips, 21 lanes in the second (tests/fft_meshes.py)
+
+
+@functools.lru_cache(maxsize=1)
+def _two_fields():
+    """x, n and numpy's transforms of x, 1 - x and n / nbar at N_TRIPS (computed once; treat as read-only)"""
+    N = N_TRIPS
+    rng = np.random.default_rng(78)
+    x = rng.random((N, N, N))
+    n = 1e-4 * np.exp(0.5 * rng.normal(size=(N, N, N)))
+    xi, dens = PR.form_field(PR.XHI, x), PR.form_field(PR.DENSITY, n=n)
+    moments = {name: np.array([float(PR.exact_sum(g)), float(PR.exact_sum(g * g))]) for name, g in (("x", x), ("xi", xi), ("dens", dens))}
+    return dict(x=x, n=n, xhat=np.fft.rfftn(x), xihat=np.fft.rfftn(xi), denshat=np.fft.rfftn(dens), moments=moments)
+
+
+def _upload_two_fields(asora):
+    p, lib, capi = asora
+    f = _two_fields()
+    _mesh(asora, N_TRIPS)
+    lib.grid_to_device(capi.GRID_XH, f["x"])
+    lib.grid_to_device(capi.GRID_NDENS, f["n"])
+    return f
+
+
+def _check_cross_sums(N, got, want, what):
+    """count and sum_k of _check_sums, and the three bounds of test_cross_spectra"""
+    c = PR.c_of_N(N)
+    _check_sums(N, got, want, what)
+    err = np.abs(got["sum_bb"] - want["sum_bb"])
+    assert np.all(err <= 4.0 * c * np.sqrt(want["sum_bb"] * want["total_bb"])), (what, "sum_bb")
+    bound = 4.0 * c * (np.sqrt(want["sum_aa"] * want["total_bb"]) + np.sqrt(want["sum_bb"] * want["total_aa"]))
+    err = np.abs(got["sum_ab"] - want["sum_ab"])
+    print(f"{what}: sum_ab uses {float(np.max(err / np.where(bound > 0, bound, 1.0))):.3e} of its bound")
+    assert np.all(err <= bound), (what, "sum_ab")
+
+
+def test_the_bin_limit(asora):
+    """n_bins = 256, all the ABI allows (the cross form then asks for 42 KB of LDS for its four histograms), at a mesh with two trips
+    of the loop over n_z.  The 257 thresholds are values of |n|^2 that occur on the mesh, so every bin holds modes, but for two pairs
+    of equal neighbours: two bins that are empty on purpose.  Modes below the first and at or above the last threshold are dropped."""
+    p, lib, capi = asora
+    N = N_TRIPS
+    n2 = PR.mode_n2(N)
+    q = np.unique(n2)
+    assert q[0] == 0 and q[1] == 1 and q[-1] == 3 * (N // 2) ** 2
+    pick = q[np.linspace(4, q.size - 40, 255).astype(int)]
+    thr = np.insert(pick, [40, 200], pick[[40, 200]]).astype(np.uint32)
+    f = _two_fields()
+    want = PR.binned(N, thr, f["xhat"], f["denshat"])
+    # the conditions, on the reference alone
+    assert thr.size == 257 and np.all(np.diff(thr.astype(np.int64)) >= 0) and 1 < thr[0] and thr[-1] < 3 * (N // 2) ** 2
+    assert int(np.sum(np.diff(thr.astype(np.int64)) == 0)) == 2
+    assert int(np.sum(want["count"] == 0)) == 2 and want["count"][40] == 0 and want["count"][201] == 0
+    w = np.broadcast_to(PR.mode_weights(N)[None, None, :], n2.shape)
+    below, above = int(w[(n2 >= 1) & (n2 < thr[0])].sum()), int(w[n2 >= thr[-1]].sum())
+    assert below > 0 and above > 0 and int(want["count"].sum()) + below + above == N ** 3 - 1
+    print(f"N {N}, 256 bins: {below} modes dropped below the first threshold, {above} at or above the last")
+    _upload_two_fields(asora)
+    auto = _twice(lib, capi.PS_XH, None, 1.0, 0.0, thr)
+    _check_sums(N, auto, want, f"N {N}, 256 bins")
+    assert auto["sum_aa"][40] == 0.0 and auto["sum_aa"][201] == 0.0 and auto["sum_k"][40] == 0.0
+    cross = _twice(lib, capi.PS_XH, capi.PS_DENSITY, 1.0, 0.0, thr)
+    _check_cross_sums(N, cross, want, f"N {N}, 256 bins, cross")
+    for key in ("count", "sum_k", "sum_aa", "moments_a"):
+        assert cross[key].tobytes() == auto[key].tobytes(), key
+    for key in ("sum_aa", "sum_bb", "sum_ab"):
+        assert cross[key][40] == 0.0 and cross[key][201] == 0.0, key
+
+
+def test_cross_spectra_across_trips(asora):
+    """test_cross_spectra's two different fields where a row of the second field, too, takes a second, partly filled trip of the loop
+    over n_z (NZ = 85); the density's mean is summed over 36.8 trips of the fixed grid."""
+    p, lib, capi = asora
+    N = N_TRIPS
+    f = _upload_two_fields(asora)
+    c = PR.c_of_N(N)
+    thr = PR.thresholds_of(_bin_sets(N)["default"])
+    ab = _twice(lib, capi.PS_XH, capi.PS_DENSITY, 1.0, 0.0, thr)
+    ba = _twice(lib, capi.PS_DENSITY, capi.PS_XH, 1.0, 0.0, thr)
+    assert ab["sum_aa"].tobytes() == ba["sum_bb"].tobytes() and ab["sum_bb"].tobytes() == ba["sum_aa"].tobytes()
+    assert ab["sum_ab"].tobytes() == ba["sum_ab"].tobytes() and ab["count"].tobytes() == ba["count"].tobytes()
+    assert ab["sum_k"].tobytes() == ba["sum_k"].tobytes()
+    assert ab["moments_a"].tobytes() == ba["moments_b"].tobytes() and ab["moments_b"].tobytes() == ba["moments_a"].tobytes()
+    want = PR.binned(N, thr, f["xhat"], f["denshat"])
+    _check_cross_sums(N, ab, want, f"N {N}, xh x density")
+    for key, name in (("moments_a", "x"), ("moments_b", "dens")):
+        assert np.all(np.abs(ab[key] - f["moments"][name]) <= 1e-13 * np.abs(f["moments"][name])), key
+    # a field against 1 - itself: every binned mode of the second is minus the first's
+    anti = _twice(lib, capi.PS_XH, capi.PS_XHI, 1.0, 0.0, thr)
+    want = PR.binned(N, thr, f["xhat"], f["xihat"])
+    bound = 4.0 * c * np.sqrt(want["sum_aa"] * want["total_aa"])
+    err = np.abs(anti["sum_ab"] + anti["sum_aa"])
+    print(f"N {N}, xh x xhi: sum_ab + sum_aa uses {float(np.max(err / (2.0 * bound))):.3e} of its bound")
+    assert np.all(err <= 2.0 * bound)
+    _check_cross_sums(N, anti, want, f"N {N}, xh x xhi")
+    assert anti["sum_aa"].tobytes() == ab["sum_aa"].tobytes()
+    assert np.all(np.abs(anti["moments_b"] - f["moments"]["xi"]) <= 1e-13 * np.abs(f["moments"]["xi"]))
+
+
+@pytest.mark.parametrize("N", [17, 64, 121, 273])
 def test_forming_the_field(asora, N):
+    """(121 and 273: uneven trips of the mean-density sum, 13.5 and 155.2, and a last row workgroup with one line at 16 and at 4
+    lines per workgroup.  At 273 three kinds, so that the case stays within seconds: 'xhi', 'density' and 'hi' with t_gamma, one
+    of each arithmetic form of the cell -- 'xh' is a copy, which the transform test asserts bit for bit at that mesh -- and the
+    binned sums of the two that divide by the mean density)"""
     p, lib, capi = asora
     _mesh(asora, N)
     rng = np.random.default_rng(300 + N)
@@ -235,8 +354,12 @@ def test_forming_the_field(asora, N):
     for which, grid in ((capi.GRID_XH, x), (capi.GRID_NDENS, n), (capi.GRID_TEMP, T)):
         lib.grid_to_device(which, grid)
     thr = PR.thresholds_of(_bin_sets(N)["default"])
-    for kind, scale, t_gamma in ((capi.PS_XH, 1.0, 0.0), (capi.PS_XHI, 1.0, 0.0), (capi.PS_DENSITY, 1.0, 0.0), (capi.PS_HI, 1.0, 0.0),
-                                 (capi.PS_HI, 27.3, 0.0), (capi.PS_HI, 27.3, 30.0), (capi.PS_XHI, 5.0, 30.0)):
+    kinds = ((capi.PS_XH, 1.0, 0.0), (capi.PS_XHI, 1.0, 0.0), (capi.PS_DENSITY, 1.0, 0.0), (capi.PS_HI, 1.0, 0.0),
+             (capi.PS_HI, 27.3, 0.0), (capi.PS_HI, 27.3, 30.0), (capi.PS_XHI, 5.0, 30.0))
+    binned_kinds = kinds
+    if N >= FM.FEW_BIN_SETS_FROM:
+        kinds, binned_kinds = (kinds[1], kinds[2], kinds[5]), (kinds[2], kinds[5])
+    for kind, scale, t_gamma in kinds:
         got = _twice(lib, kind, None, scale, t_gamma, thr, field=True)
         hi = kind == capi.PS_HI
         want = PR.form_field(kind, x, n, T, scale if hi else 1.0, t_gamma if hi else 0.0)     # (scale and t_gamma are for 'hi' alone)
@@ -247,7 +370,8 @@ def test_forming_the_field(asora, N):
             assert np.array_equal(got["field"], want)
         want_m = np.array([float(PR.exact_sum(got["field"])), float(PR.exact_sum(got["field"] ** 2))])
         assert np.all(np.abs(got["moments_a"] - want_m) <= 1e-13 * np.abs(want_m))
-        _check_sums(N, got, PR.binned(N, thr, np.fft.rfftn(got["field"])), f"N {N}, kind {kind}")
+        if (kind, scale, t_gamma) in binned_kinds:
+            _check_sums(N, got, PR.binned(N, thr, np.fft.rfftn(got["field"])), f"N {N}, kind {kind}")
     # no grid is written
     for which, grid in ((capi.GRID_XH, x), (capi.GRID_NDENS, n), (capi.GRID_TEMP, T)):
         assert np.array_equal(lib.grid_to_host(which, np.empty((N, N, N))), grid)

@@ -9,6 +9,11 @@ Parseval, ||h - h_ref||_2 <= 2.5 c(N) max|W| ||g||_2.  Every test prints the sha
 * Meshes: every specialised radix alone (2, 3, 4, 5, 7), the generic butterfly (17, 43, 129 = 3 x 43), repeated and mixed radices, odd
   and even N, tail tiles of the strided passes (N / 2 + 1 no multiple of the tile); 144 takes 8 lines per workgroup and 280 takes 4 (the
   round trip only, which needs no numpy transform).
+* The meshes of tests/fft_meshes.py (121, 139, 140, 169, 243, 256, 271, 272, 273; each row says what it is there for, and
+  tests/test_fft_meshes_host.py checks that it is so): the round trip at all nine -- both edges of the tile rule, tails in every pass
+  at 16, 8 and 4 lines per workgroup, two generic stages, five stages, primes up to 271, 256^3; the filter pass against numpy at 121,
+  169 and 273 (a tail tile at each tile size); the boxcar at 140 and 272; the statistics at 121 (four trips of the one-workgroup
+  fold, the last partial).
 * Statistics at N = 30 (a part of the second pass's fixed grid of 512 workgroups holds no cell) and at N = 72: 72^2 / 16 = 324 row
   workgroups, so the one-workgroup fold of their partials makes two trips, and 72^3 = 373 248 cells are 2.85 trips of the second
   pass's 131 072 threads, so some threads make three and some two."""
@@ -19,6 +24,7 @@ import numpy as np
 import pytest
 
 import bubble_reference as BR
+import fft_meshes as FM
 import powerspec_reference as PR
 import smoothing_reference as SR
 
@@ -28,6 +34,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 OBSERVED_PARAMS = os.path.join(HERE, "data", "parameters_observed_map.yml")
 ROUND_TRIP_MESHES = (2, 3, 4, 5, 7, 8, 9, 17, 30, 43, 64, 96, 129, 136, 144, 280)
 FILTER_MESHES = (8, 9, 17, 30, 43, 64, 96)
+FILTER_TAIL_MESHES = (121, 169, 273)        # 16, 8 and 4 lines per workgroup, each with a tail tile in the pass along i
 
 
 @pytest.fixture(scope="module")
@@ -95,6 +102,13 @@ def test_round_trip(asora, N):
     assert np.array_equal(lib.grid_to_host(capi.GRID_XH, np.empty((N, N, N))), g)             # no grid is written
 
 
+@pytest.mark.parametrize("N", FM.MESHES)
+def test_round_trip_at_the_meshes_of_the_table(asora, N):
+    """The same at the meshes of tests/fft_meshes.py: every pass of the inverse at both edges of the tile rule, with tails at 16, 8
+    and 4 lines per workgroup, two generic stages, five stages, primes up to 271, and 256^3."""
+    test_round_trip(asora, N)
+
+
 @pytest.mark.parametrize("N", FILTER_MESHES)
 def test_filters_against_the_numpy_statement(asora, N):
     """2. Five filters with the mean kept and removed on the ionised fraction; the brightness temperature with and without the
@@ -133,9 +147,45 @@ def test_filters_against_the_numpy_statement(asora, N):
     print(f"N {N}: the largest share of the bound used is {worst:.3e}")
 
 
-@pytest.mark.parametrize("N", [9, 16])
+@pytest.mark.parametrize("N", FILTER_TAIL_MESHES)
+def test_filters_beyond_sixteen_lines(asora, N):
+    """2. at 121, 169 and 273 (tests/fft_meshes.py): the filter pass with a tail tile at 16, 8 and 4 lines per workgroup -- its three
+    tables and its per-column indices behind line buffers of another size, w_r looked up at |m|^2 up to 3 x 136^2.  A product with
+    all four tables on the ionised fraction, mean kept and removed; the telescope's filter on the brightness temperature with the
+    spin-temperature factor, mean removed."""
+    p, lib, capi = asora
+    import pyc2ray_amd.smoothing as S
+    _mesh(asora, N)
+    rng = np.random.default_rng(500 + N)
+    x = np.clip(0.5 + 0.25 * PR.noise_with_block(N, 3000 + N), 0.0, 1.0)
+    n = 1e-4 * np.exp(0.7 * rng.normal(size=(N, N, N)))
+    T = 200.0 + 2e4 * rng.random((N, N, N))
+    for which, grid in ((capi.GRID_XH, x), (capi.GRID_NDENS, n), (capi.GRID_TEMP, T)):
+        lib.grid_to_device(which, grid)
+    filters = {"product": S.gaussian(2.0, axes=(0, 2)) * S.boxcar(3, 1) * S.spherical_tophat(1.5), "telescope": S.telescope(2.5, 3)}
+    assert all(w is not None for w in filters["product"].tables(N))
+    thr = PR.thresholds_of([0.5, N])
+    worst = 0.0
+    for kind, scale, t_gamma, name, subs in ((capi.PS_XH, 1.0, 0.0, "product", (False, True)), (capi.PS_HI, 27.3, 30.0, "telescope", (True,))):
+        ps = lib.power_spectrum(kind, None, scale, t_gamma, thr, field=True)
+        g, ghat = ps["field"], np.fft.rfftn(ps["field"])
+        tables = filters[name].tables(N)
+        for sub in subs:
+            got = _twice(lib, kind, scale, t_gamma, *tables, subtract_mean=sub, field=True)
+            W = SR.filter_on_mesh(N, tables, sub)
+            want = np.fft.irfftn(W * ghat, s=(N, N, N), axes=(0, 1, 2))
+            worst = max(worst, _check_field(f"N {N}, kind {kind}, t_gamma {t_gamma}, {name}, subtract_mean {sub}", N, got["field"], want,
+                                            float(np.abs(W).max()), g))
+            assert got["stats"][capi.SMOOTH_INPUT_SUM:capi.SMOOTH_INPUT_SUM2 + 1].tobytes() == ps["moments_a"].tobytes()
+            if sub:
+                assert abs(got["stats"][capi.SMOOTH_SUM]) <= 2.5 * PR.c_of_N(N) * N ** 1.5 * _norm(g)
+    print(f"N {N}: the largest share of the bound used is {worst:.3e}")
+
+
+@pytest.mark.parametrize("N", [9, 16, 140, 272])
 def test_boxcar_is_the_moving_average(asora, N):
-    """3. boxcar(3, axis) per axis against the periodic three-cell moving average: an answer that owes nothing to a transform."""
+    """3. boxcar(3, axis) per axis against the periodic three-cell moving average: an answer that owes nothing to a transform, at
+    16, 8 (N = 140) and 4 (N = 272) lines per workgroup."""
     p, lib, capi = asora
     import pyc2ray_amd.smoothing as S
     _mesh(asora, N)
@@ -156,7 +206,7 @@ def _edge_sets(h):
 
 
 @pytest.mark.parametrize("N", [30, 72])
-def test_statistics_against_the_downloaded_field(asora, N):
+def test_statistics_against_the_downloaded_field(asora, N, bins=(1, 7, 4096)):
     """4. Counts, min, max and the histogram equal numpy's on the field the device returns; the sums are within 1e-13 of exact
     summation of the same terms."""
     p, lib, capi = asora
@@ -167,7 +217,7 @@ def test_statistics_against_the_downloaded_field(asora, N):
     first = _twice(lib, capi.PS_XH, 1.0, 0.0, *tables, field=True)
     h = first["field"]
     want = SR.statistics(h)
-    for edges in [None] + list(_edge_sets(h).values()):
+    for edges in [None] + [e for count, e in _edge_sets(h).items() if count in bins]:
         got = _twice(lib, capi.PS_XH, 1.0, 0.0, *tables, edges=edges, field=True)
         assert got["field"].tobytes() == h.tobytes() and got["stats"].tobytes() == first["stats"].tobytes()
         if edges is not None:
@@ -180,6 +230,12 @@ def test_statistics_against_the_downloaded_field(asora, N):
     for key in (capi.SMOOTH_SUM, capi.SMOOTH_S2, capi.SMOOTH_S3, capi.SMOOTH_S4):
         print(f"N {N}, stats[{key}]: {s[key]!r} against {want[key]!r}: off by {abs(s[key] - want[key]) / abs(want[key]):.2e}")
         assert abs(s[key] - want[key]) <= 1e-13 * abs(want[key]), key
+
+
+def test_statistics_with_a_partial_fourth_trip_of_the_fold(asora):
+    """4. at N = 121: 121^2 / 16 = 916 row workgroups, so the one-workgroup fold of their partials makes four trips, the last of 148,
+    and the last row workgroup holds one line; 121^3 cells are 13.5 trips of the second pass.  The 7 and the 4096 bins only."""
+    test_statistics_against_the_downloaded_field(asora, 121, bins=(7, 4096))
 
 
 def test_non_finite_cells_are_counted_apart(asora):

@@ -3,6 +3,7 @@ the header says of weights, folding and edges."""
 import numpy as np
 import pytest
 
+import fft_meshes as FM
 import powerspec_reference as PR
 
 
@@ -33,6 +34,25 @@ def test_reference_against_a_brute_force_transform(N):
     sums = PR.power_sums(g, np.array([1, 3 * N * N], dtype=np.uint32))
     spread = sums["moments_a"][1] - sums["moments_a"][0] ** 2 / N ** 3
     assert abs(sums["sum_aa"][0] / N ** 3 - spread) <= 1e-12 * spread and sums["count"][0] == N ** 3 - 1
+
+
+@pytest.mark.parametrize("N", FM.MESHES)
+def test_numpy_serves_as_the_reference_at_the_meshes_of_the_table(N):
+    """The bounds of the GPU tests, c(N) = 8 eps (log2 N^3 + p), rest on numpy's own error being far inside them.  Along one axis:
+    np.fft.fft of 32 random real lines against the DFT matrix in extended precision ((r c) mod N reduced before the angle is formed,
+    as brute_force_dft does), in the relative 2-norm, within a tenth of the per-axis share c(N) / 3."""
+    lines = np.random.default_rng(7000 + N).normal(size=(32, N))
+    r = (np.arange(N)[:, None] * np.arange(N)[None, :]) % N
+    ang = -2.0 * np.pi * r.astype(np.longdouble) / N
+    W = np.cos(ang) + 1j * np.sin(ang)
+    want = lines.astype(np.clongdouble) @ W                           # (W is symmetric)
+    got = np.fft.fft(lines, axis=1)
+    diff = got.astype(np.clongdouble) - want
+    err = float(np.sqrt(np.sum(np.abs(diff) ** 2) / np.sum(np.abs(want) ** 2)))
+    share = PR.c_of_N(N) / 3.0
+    print(f"N {N}: np.fft.fft against the extended-precision DFT {err / PR.EPS:.2f} eps, c(N) / 3 = {share / PR.EPS:.0f} eps: "
+          f"{100.0 * err / share:.2f} % of it")
+    assert err <= 0.1 * share
 
 
 @pytest.mark.parametrize("N", [1, 2, 3, 4, 5, 6, 7, 8, 9, 16, 17])
@@ -73,4 +93,5 @@ def test_forming_the_field_and_the_bound():
     assert np.array_equal(PR.form_field(PR.HI, x, n, scale=3.0), (3.0 * (1.0 - x)) * (n / nbar))
     assert np.array_equal(PR.form_field(PR.HI, x, n, T, scale=3.0, t_gamma=30.0), ((3.0 * (1.0 - x)) * (n / nbar)) * (1.0 - 30.0 / T))
     assert [PR.largest_prime_factor(N) for N in (1, 2, 8, 30, 43, 49, 129, 136, 250, 645)] == [1, 2, 2, 5, 43, 7, 43, 17, 5, 43]
+    assert [PR.largest_prime_factor(N) for N in FM.MESHES] == [11, 139, 7, 13, 3, 2, 271, 17, 13]
     assert PR.c_of_N(64) == 8 * PR.EPS * 18 and PR.c_of_N(43) == 8 * PR.EPS * (3 * np.log2(43.0) + 43)
