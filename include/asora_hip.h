@@ -801,6 +801,25 @@ int asora_last_raytrace_counts_ex(long long *gamma_cells, long long *evaluated_c
  * (the reference keeps it in cdh_dev, src/asora/memory.cu:20, and never downloads it). */
 int asora_debug_coldens(double R, double sig, double dr, int source_index, double *coldens_out, int N);
 
+/* The device functions every rate goes through (pyc2ray_amd/csrc/rates_device.hpp), evaluated element-wise on host arrays of
+ * length n (tests; no reference counterpart): copy in, one kernel on the library's stream that calls the functions themselves,
+ * copy out.  op: ASORA_PRIM_*; inputs a ... d as the table says (the others may be null):
+ *   LOG2     a = x                                  out = log2_pos(x), no clamp added
+ *   LOOKUP   a = tau; which = 0 thick, 1 thin,      out = the interpolated value of table `which` of table set `spectrum`;
+ *            2 heat thick, 3 heat thin              out2 = the real table index as formed (integer part + residual)
+ *   DIV      a = x, b = y                           out = div_newton(x, y)
+ *   MUL ADD  a, b                                   out = mul_unfused(a, b), add_unfused(a, b)
+ *   ABSORBER a = n, b = x, c = a, d = b             out = absorber_density(n, x, a, b)
+ *   PHOTO HEAT GREY  a = flux, b = cd_in,           out = rate_value(rate_issue(...)), heat_rate_per_atom(...) of table set
+ *            c = cd_out, d = vol_nhi                      `spectrum`, grey_rate_per_atom(...)
+ * The parameter block is the one a trace gets (sig, minlogtau, dlogtau, NumTau as given; the table length, the index limit,
+ * ASORA_OPT_FORTRAN_CONSTANTS and the tables as they stand on the device).  Code 2 before asora_device_init, 3 for an unknown
+ * operation or a null array the operation needs, 4 where LOOKUP / PHOTO / HEAT find no (heating) tables or no such table set. */
+enum { ASORA_PRIM_LOG2 = 0, ASORA_PRIM_LOOKUP = 1, ASORA_PRIM_DIV = 2, ASORA_PRIM_MUL = 3, ASORA_PRIM_ADD = 4, ASORA_PRIM_ABSORBER = 5,
+       ASORA_PRIM_PHOTO = 6, ASORA_PRIM_HEAT = 7, ASORA_PRIM_GREY = 8, ASORA_PRIM_COUNT = 9 };
+int asora_debug_rate_primitives(int op, size_t n, const double *a, const double *b, const double *c, const double *d, int which,
+                                int spectrum, double sig, double minlogtau, double dlogtau, int NumTau, double *out, double *out2);
+
 /* Which form of the raytrace kernel the last launch took (measurement and tests; no reference counterpart): a bit set of
  * ASORA_VARIANT_* | workgroups per source << 8 | threads per workgroup << 16.  0 before the first launch. */
 enum {

@@ -56,6 +56,8 @@ PS_STAGES = 5
 SMOOTH_STATS = 10
 SMOOTH_MAX_BINS = 4096
 SMOOTH_STAGES = 8
+(PRIM_LOG2, PRIM_LOOKUP, PRIM_DIV, PRIM_MUL, PRIM_ADD, PRIM_ABSORBER, PRIM_PHOTO, PRIM_HEAT, PRIM_GREY) = range(9)
+PRIM_COUNT = 9
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -161,6 +163,8 @@ SIGNATURES = {
     "asora_last_raytrace_counts": (C.c_int, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "asora_last_raytrace_counts_ex": (C.c_int, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "asora_debug_coldens": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_int, _dp, C.c_int]),
+    "asora_debug_rate_primitives": (C.c_int, [C.c_int, C.c_size_t, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
+                                              C.c_int, _dp, _dp]),
     "asora_last_raytrace_variant": (C.c_int, []),
     "asora_debug_launch_plan": (C.c_int, [C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip]),
     "asora_debug_last_subbox_launch": (C.c_int, [_ip]),

@@ -51,6 +51,29 @@ inline double lut_index_limit(int NumTau, int table_len)
     return by_reference < by_table ? by_reference : by_table;
 }
 
+// The constants of the real table index k0 + k1 log2(tau) + kc (rates_device.hpp, lookup_issue) for every launcher:
+// k1 = log10(2)/dlogtau and k0 = 1 - minlogtau/dlogtau as the nearest doubles, and kc, what those two roundings leave out.  k0
+// cancels against k1 log2(tau) at small optical depths (k0 = 1668, index 1 at tau = 10^minlogtau), so its rounding -- half an
+// ulp of 1668, 1.1e-13 -- and k1's times log2(tau) weigh several ulp of a small index; (k0 - K0) + (k1 - K1) log2(tau) against
+// the exact K0, K1 is linear in log2(tau), and its value where the index is 1, L0 = minlogtau/log10(2), serves the whole
+// table: what remains, (k1 - K1)(log2 tau - L0) = 2e-17 (index - 1), is far below an ulp of the index everywhere.  Formed
+// in doubles from the exact remainders of the divisions (fma) and of the sum (two-sum).
+struct LutIndex { double k1, k0, kc; };
+inline LutIndex lut_index_constants(double minlogtau, double dlogtau)
+{
+    const double log10_2 = 0.30102999566398119521, log10_2_lo = -2.8037281277851703e-18;     // hi + lo = log10(2) to 2^-106
+    LutIndex c;
+    c.k1 = log10_2 / dlogtau;
+    const double q = minlogtau / dlogtau;
+    c.k0 = 1.0 - q;
+    const double k1_lo = (std::fma(-c.k1, dlogtau, log10_2) + log10_2_lo) / dlogtau;       // K1 = k1 + k1_lo
+    const double q_lo = std::fma(-q, dlogtau, minlogtau) / dlogtau;                         // minlogtau/dlogtau = q + q_lo
+    const double bb = c.k0 - 1.0, sum_lo = (1.0 - (c.k0 - bb)) + (-q - bb);                // 1 - q = k0 + sum_lo
+    c.kc = (sum_lo - q_lo) + k1_lo * (minlogtau / log10_2);                                 // -((k0 - K0) + (k1 - K1) L0)
+    if (!std::isfinite(c.kc)) c.kc = 0.0;
+    return c;
+}
+
 // Plane-parallel flux through faces of the box (asora_plane_flux; plane_flux.hip)
 struct PlaneFluxSet {
     int count;                         // 0: off
@@ -112,6 +135,8 @@ struct RtParams {
     int open_bc;
     // ---- plane-parallel flux (asora_plane_flux as it stood when the call began; read by launch_plane_flux, not by the kernels above) ----
     PlaneFluxSet plane;
+    // ---- the table index's correction term (lut_index_constants; appended) ----
+    double lut_kc;
 };
 
 // Constants of the thermal form of the chemistry pass (asora_thermal_params; chemistry.hip: thermal_integrate)
@@ -490,6 +515,7 @@ struct SubboxParams {
     size_t unit_stride;         // = 6 W^2
     const int *active;          // per source of the batch
     double *loss;               // per source of the batch: photons through the current box faces
+    double lut_kc;              // the table index's correction term (lut_index_constants)
 };
 int launch_subbox_sweep(State &st, const SubboxParams &p, hipStream_t side = nullptr);   // side: the stream to launch on (default: the library's)
 int launch_subbox_decide(State &st, int mode, int count, const double *src_flux, int src_begin, double loss_fraction,

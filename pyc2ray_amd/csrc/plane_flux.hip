@@ -18,7 +18,7 @@ struct PlaneFluxParams {
     double *phi, *heat;                // accumulators of the same layout (heat: HEAT form only)
     const double2 *tab;                // the face's table set: thick | thin | heat thick | heat thin
     const double2 *logtab;
-    double flux, sig, dr, numtau_f, lut_k1, lut_k0;
+    double flux, sig, dr, numtau_f, lut_k1, lut_k0, lut_kc;
     int table_len, fortran_consts;
     const int *done;                   // device loop: the step has converged -> nothing to do; or nullptr
 };
@@ -112,12 +112,12 @@ __global__ void __launch_bounds__(64 * PF_ROWS) plane_flux_kernel(const PlaneFlu
     }
 }
 
-// The tables of a lookup as launch_raytrace sets them (log10(2)/dlogtau, 1 - minlogtau/dlogtau)
+// The tables of a lookup as launch_raytrace sets them (lut_index_constants)
 static void fill_lookup(PlaneFluxParams &k, const RtParams &p)
 {
     k.numtau_f = p.numtau_f;
-    k.lut_k1 = 0.30102999566398119521 / p.dlogtau;
-    k.lut_k0 = 1.0 - p.minlogtau / p.dlogtau;
+    const LutIndex lut = lut_index_constants(p.minlogtau, p.dlogtau);
+    k.lut_k1 = lut.k1; k.lut_k0 = lut.k0; k.lut_kc = lut.kc;
     k.table_len = p.table_len;
     k.fortran_consts = p.fortran_consts;
 }

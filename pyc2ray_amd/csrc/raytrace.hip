@@ -49,79 +49,8 @@
 
 namespace asora {
 
-// photoion_rates_gpu rates.cu:16-41 divided by nHI (raytracing.cu:324), also in two halves.
-// pref = flux/(vol*nHI) replaces the reference's two divisions by one.  A cell is "thick" when
-// |tau_out - tau_in| > TAU_PHOTO_LIMIT: Gamma = pref*(T_thick(tau_in) - T_thick(tau_out)); else
-// Gamma = pref*(tau_out - tau_in)*T_thin(tau_out) [rates.cu:37; photorates.f90:121 uses tau_in].
-struct RateJob {
-    double pref, dtau;       // dtau = tau_out - tau_in for thin cells, unused (0) for thick ones
-    Lookup A, B;             // thick: T(tau_in), T(tau_out);  thin: T_thin(tau*), unused
-    bool thick;
-};
-// `tab`: the [thick | thin | heat thick | heat thin] block of the source's table set (RtParams::src_spec)
-__device__ __forceinline__ RateJob rate_issue(double flux, double cd_in, double cd_out, double vol_nhi,
-                                              const RtParams &p, const double2 *__restrict__ logtab, const double2 *__restrict__ tab)
-{
-    // (un-fused products: tau_out - tau_in must be the difference of the two ROUNDED optical depths, as in the
-    //  reference; fused into fma(cd_out, sig, -tau_in) it would carry the rounding error of one product -- a speck
-    //  instead of 0 where nHI = 0, and a 1e-8 relative change of dtau for thin cells)
-    const double tau_in = mul_unfused(cd_in, p.sig);
-    const double tau_out = mul_unfused(cd_out, p.sig);
-    // TAU_PHOTO_LIMIT: rates.cu:7 (double 1e-7) or photorates.f90:69 (single 1e-7 promoted)
-    const double limit = p.fortran_consts ? (double)1.0e-7f : 1.0e-7;
-    RateJob J;
-    J.pref = flux / vol_nhi;
-    J.thick = fabs(tau_out - tau_in) > limit;
-    J.dtau = tau_out - tau_in;
-    const double tau_thin = p.fortran_consts ? tau_in : tau_out;
-    // one code path for both kinds of cell: per-lane table and arguments
-    // thick table at [0, table_len), thin table at [table_len, 2*table_len) of one allocation
-    const int toff = J.thick ? 0 : table_stride(p.table_len);
-    J.A = lookup_issue(tab, J.thick ? tau_in : tau_thin, p, logtab, toff);
-    J.B = lookup_issue(tab, J.thick ? tau_out : tau_thin, p, logtab, toff);
-    return J;
-}
-__device__ __forceinline__ double rate_value(const RateJob &J)
-{
-    const double a = lookup_value(J.A), b = lookup_value(J.B);
-    // (pref*(a - b), not pref*a - pref*b: the compiler would fuse the latter into fma(pref, a, -(pref*b)), which
-    //  leaves the rounding error of pref*b -- a random-signed ~1e-16 relative speck -- where a == b, e.g. beyond the
-    //  last table entry, where the reference's un-fused arithmetic gives exactly 0)
-    return J.thick ? J.pref * (a - b) : J.pref * J.dtau * a;
-}
-
-// photoion_rates_test_gpu rates.cu:48-64 (analytic grey rates, GREY_NOTABLES builds), per atom
-__device__ __forceinline__ double grey_rate_per_atom(double flux, double cd_in, double cd_out, double vol_nhi,
-                                                     const RtParams &p)
-{
-    const double tau_in = mul_unfused(cd_in, p.sig), tau_out = mul_unfused(cd_out, p.sig);   // un-fused, see rate_issue
-    const double limit = p.fortran_consts ? (double)1.0e-7f : 1.0e-7;
-    const double pref = flux * 1e48 / vol_nhi;
-    if (fabs(tau_out - tau_in) > limit) return pref * (exp(-tau_in) - exp(-tau_out));
-    return pref * (tau_out - tau_in) * exp(-tau_in);
-}
-
-// heating rate of one cell per atom (photorates.f90:118,124), used for the source cell only
-__device__ __forceinline__ double heat_rate_per_atom(double flux, double cd_in, double cd_out, double vol_nhi,
-                                                     const RtParams &p, const double2 *__restrict__ logtab, const double2 *__restrict__ tab)
-{
-    const double tau_in = mul_unfused(cd_in, p.sig), tau_out = mul_unfused(cd_out, p.sig);   // un-fused, see rate_issue
-    const double limit = p.fortran_consts ? (double)1.0e-7f : 1.0e-7;
-    const double pref = flux / vol_nhi;
-    const bool thick = fabs(tau_out - tau_in) > limit;
-    const double tau_thin = p.fortran_consts ? tau_in : tau_out;
-    const int toff = thick ? 0 : table_stride(p.table_len);
-    const Lookup A = lookup_issue<true>(tab, thick ? tau_in : tau_thin, p, logtab, toff);
-    const Lookup B = lookup_issue<true>(tab, thick ? tau_out : tau_thin, p, logtab, toff);
-    return thick ? pref * (lookup_heat(A) - lookup_heat(B)) : pref * (tau_out - tau_in) * lookup_heat(A);
-}
-
-__device__ __forceinline__ double photo_rate_per_atom(double flux, double cd_in, double cd_out, double vol_nhi,
-                                                      const RtParams &p, const double2 *__restrict__ logtab, const double2 *__restrict__ tab)
-{
-    if (p.grey) return grey_rate_per_atom(flux, cd_in, cd_out, vol_nhi, p);
-    return rate_value(rate_issue(flux, cd_in, cd_out, vol_nhi, p, logtab, tab));
-}
+// (the rates of a cell -- rate_issue / rate_value, grey_rate_per_atom, heat_rate_per_atom, photo_rate_per_atom -- live in
+//  rates_device.hpp, where rate_primitives_debug.hip can call them too)
 
 // ---------------------------------------------------------------------------------------------
 // The octant kernel
@@ -1081,8 +1010,8 @@ int launch_raytrace(State &st, RtParams &p, bool dump, bool heat, hipStream_t si
     const RtShape sh = plan_shape(in);
     if (int rc = ensure_geometry(st, p, sh.threads, sh.units, nullptr, sh.aligned)) return rc;
     st.last_variant = 0;
-    p.lut_k1 = 0.30102999566398119521 / p.dlogtau;      // log10(2)/dlogtau
-    p.lut_k0 = 1.0 - p.minlogtau / p.dlogtau;
+    const LutIndex lut = lut_index_constants(p.minlogtau, p.dlogtau);      // log10(2)/dlogtau, 1 - minlogtau/dlogtau, their remainder
+    p.lut_k1 = lut.k1; p.lut_k0 = lut.k0; p.lut_kc = lut.kc;
     // optical depth from which BOTH lookups of a thick cell return the same table value (index clamped to NumTau, or on
     // the last pair of the device table, whose slope is 0): 0.01 index units beyond the exact point, far more than the
     // 1e-12 the device's log2 can be off by

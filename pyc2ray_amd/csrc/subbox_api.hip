@@ -60,8 +60,8 @@ static int subbox_core(const SubboxCall &c, long long &total_nbox, double &total
     p.ext_r = ext_r; p.ext_l = ext_l;
     p.sig = c.sig; p.dr = c.dr; p.R = c.R;
     p.numtau_f = lut_index_limit(c.NumTau, c.table_len);                   // photorates.f90:141 real(NumTau)
-    p.lut_k1 = 0.30102999566398119521 / c.dlogtau;
-    p.lut_k0 = 1.0 - c.minlogtau / c.dlogtau;
+    const LutIndex lut = lut_index_constants(c.minlogtau, c.dlogtau);
+    p.lut_k1 = lut.k1; p.lut_k0 = lut.k0; p.lut_kc = lut.kc;
     p.table_len = c.table_len;
     p.grey = grey ? 1 : 0; p.heat = c.heat ? 1 : 0; p.add_zero = st.opt[ASORA_OPT_SKIP_ZERO_RATES] == 1 ? 0 : 1;
     const int last = c.src_begin + c.src_count - 1;
@@ -86,7 +86,7 @@ static int subbox_core(const SubboxCall &c, long long &total_nbox, double &total
     // whole cube -- and everything else stay with the on-the-fly kernel of subbox.hip
     RtParams tp;
     fill_rt_params(tp, c.R, c.sig, c.dr, c.minlogtau, c.dlogtau, c.NumTau, 1);
-    tp.numtau_f = p.numtau_f; tp.lut_k1 = p.lut_k1; tp.lut_k0 = p.lut_k0; tp.tau_zero = INFINITY;
+    tp.numtau_f = p.numtau_f; tp.lut_k1 = p.lut_k1; tp.lut_k0 = p.lut_k0; tp.lut_kc = p.lut_kc; tp.tau_zero = INFINITY;
     tp.table_len = c.table_len; tp.tables = c.tables;
     tp.fortran_consts = 1; tp.grey = grey ? 1 : 0; tp.z_transposed = 1;
     tp.logtab = st.logtab_dev;

@@ -736,6 +736,27 @@ class _LibAsora:
         """Hash over the library's sources, headers and compiler flags (asora_build_id)."""
         return self._lib.asora_build_id().decode()
 
+    PRIMITIVES = ("log2", "lookup", "div", "mul", "add", "absorber", "photo", "heat", "grey")
+    TABLES = ("thick", "thin", "heat_thick", "heat_thin")
+
+    def debug_rate_primitives(self, op, a, b=None, c=None, d=None, which=0, spectrum=0, sig=1.0, minlogtau=-20.0, dlogtau=1.0, NumTau=1):
+        """One device function of the rates (csrc/rates_device.hpp) element-wise on float64 arrays (asora_debug_rate_primitives,
+        include/asora_hip.h): `op` a name of PRIMITIVES or its number, `which` a name of TABLES or its number.  Returns the
+        output array; for "lookup" the pair (value, real table index as formed)."""
+        op = self.PRIMITIVES.index(op) if isinstance(op, str) else int(op)
+        which = self.TABLES.index(which) if isinstance(which, str) else int(which)
+        arrays = [None if x is None else np.ascontiguousarray(x, dtype=np.float64).ravel() for x in (a, b, c, d)]
+        n = 0 if arrays[0] is None else arrays[0].size
+        for x in arrays[1:]:
+            if x is not None and x.size != n:
+                raise ValueError("debug_rate_primitives: the inputs must have one length")
+        out = np.empty(n)
+        out2 = np.empty(n) if op == _capi.PRIM_LOOKUP else None
+        _capi.check(self._lib.asora_debug_rate_primitives(op, n, *[None if x is None else _capi.dptr(x) for x in arrays], which, int(spectrum),
+                                                          float(sig), float(minlogtau), float(dlogtau), int(NumTau), _capi.dptr(out),
+                                                          None if out2 is None else _capi.dptr(out2)), "debug_rate_primitives")
+        return (out, out2) if out2 is not None else out
+
     def debug_coldens(self, R, sig, dr, source_index, N):
         out = np.zeros((N, N, N))
         _capi.check(self._lib.asora_debug_coldens(float(R), float(sig), float(dr), int(source_index),
