@@ -11,13 +11,12 @@ import math
 
 import numpy as np
 
-from . import _capi, _residency
+from . import _capi
 from .asora_core import cuda_is_init
 from .load_extensions import load_asora
+from ._fieldspec import PHASES, analyse, check_dr, check_edges, check_flag, check_phase, check_threshold, is_int, is_real
 
 __all__ = ['BubbleSizes', 'mfp_distribution']
-
-_PHASES = {"ionised": 0, "neutral": 1}
 
 
 class BubbleSizes:
@@ -96,34 +95,22 @@ class BubbleSizes:
         return f"<BubbleSizes: {self.log_line()}>"
 
 
-def _is_int(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-
-
-def _is_real(v):
-    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
-
-
 def bubble_spec(who, N, threshold=0.5, phase="ionised", n_rays=100_000, seed=0, l_max=None, bins=64, periodic=True, dr=None):
     """The keywords of :func:`mfp_distribution` checked and completed for a mesh of N cells a side: a dict with ``edges`` in place
     of ``bins`` and ``l_max`` filled in (N = None: checked only).  Raises ValueError -- before any device call -- for what the
     library would refuse."""
-    if not _is_real(threshold) or not math.isfinite(threshold):
-        raise ValueError(f"{who}: threshold must be a finite number, not {threshold!r}")
-    if phase not in _PHASES:
-        raise ValueError(f"{who}: phase must be 'ionised' or 'neutral', not {phase!r}")
-    if not _is_int(n_rays) or n_rays < 0:
+    check_threshold(who, threshold)
+    check_phase(who, phase)
+    if not is_int(n_rays) or n_rays < 0:
         raise ValueError(f"{who}: n_rays must be an integer >= 0, not {n_rays!r}")
-    if not _is_int(seed) or not 0 <= seed < 2 ** 64:
+    if not is_int(seed) or not 0 <= seed < 2 ** 64:
         raise ValueError(f"{who}: seed must be an integer in [0, 2^64), not {seed!r}")
-    if l_max is not None and (not _is_real(l_max) or not (math.isfinite(l_max) and l_max > 0)):
+    if l_max is not None and (not is_real(l_max) or not (math.isfinite(l_max) and l_max > 0)):
         raise ValueError(f"{who}: l_max must be None or a finite number > 0 (cells), not {l_max!r}")
-    if not isinstance(periodic, (bool, np.bool_)):
-        raise ValueError(f"{who}: periodic must be a bool, not {type(periodic).__name__}")
-    if dr is not None and (not _is_real(dr) or not (math.isfinite(dr) and dr > 0)):
-        raise ValueError(f"{who}: dr must be None or a finite number > 0, not {dr!r}")
+    check_flag(who, "periodic", periodic)
+    check_dr(who, dr)
     edges = None
-    if _is_int(bins):
+    if is_int(bins):
         if not 1 <= bins <= _capi.BUBBLE_MAX_BINS:
             raise ValueError(f"{who}: bins must be 1 ... {_capi.BUBBLE_MAX_BINS} or an array of edges, not {bins!r}")
         if l_max is not None and not l_max > 0.5:
@@ -133,10 +120,7 @@ def bubble_spec(who, N, threshold=0.5, phase="ionised", n_rays=100_000, seed=0, 
             edges = np.array(bins, dtype=np.float64)
         except (TypeError, ValueError):
             raise ValueError(f"{who}: bins must be a number of bins or an array of edges, not {type(bins).__name__}") from None
-        if edges.ndim != 1 or not 2 <= edges.size <= _capi.BUBBLE_MAX_BINS + 1:
-            raise ValueError(f"{who}: the bin edges must be a 1-D array of 2 ... {_capi.BUBBLE_MAX_BINS + 1} values")
-        if not np.all(np.isfinite(edges)) or not edges[0] > 0.0 or not np.all(np.diff(edges) > 0.0):
-            raise ValueError(f"{who}: the bin edges must be finite, > 0 and ascending")
+        check_edges(who, edges)
     if N is None:                          # (only the checks: the mesh size is the device's, asked for afterwards)
         return None
     if l_max is None:
@@ -160,38 +144,13 @@ def mfp_distribution(field=None, *, threshold=0.5, phase='ionised', n_rays=100_0
     for ``np.geomspace(0.5, l_max, bins + 1)``, or the edges themselves (cells, ascending, > 0; at most 256 bins).
     ``periodic``: rays wrap around the box (True) or leave it through its faces and are counted as ``left_box`` (False).
     ``dr``: the size of a cell, for the ``*_phys`` attributes of the result."""
-    who = "mfp_distribution"
-    if field is not None:
-        if grid is not None:
-            raise ValueError(f"{who}: grid selects a device grid and goes with field=None")
-        field = np.asarray(field)
-        if field.ndim != 3 or field.shape != (field.shape[0],) * 3 or field.dtype.kind not in "fiu":
-            raise ValueError(f"{who}: field must be a real (N, N, N) array")
-        N = field.shape[0]
-    else:
-        grid = _capi.GRID_XH if grid is None else grid
-        if not _is_int(grid) or not 0 <= grid <= _capi.GRID_CLUMP:
-            raise ValueError(f"{who}: grid must be one of the _capi.GRID_* selectors, not {grid!r}")
-        N = None
     kw = dict(threshold=threshold, phase=phase, n_rays=n_rays, seed=seed, l_max=l_max, bins=bins, periodic=periodic, dr=dr)
-    spec = bubble_spec(who, N, **kw)
-    if not cuda_is_init():
-        raise RuntimeError("GPU not initialized. Please initialize it by calling device_init(N)")
-    lib = load_asora()
-    if field is not None:
-        _residency.reclaim()              # this call overwrites a device grid a resident C2Ray object may be relying on
-        lib.grid_to_device(_capi.GRID_XH, np.asarray(field, dtype=np.float64))
-        grid = _capi.GRID_XH
-    else:
-        if getattr(lib, "_N", None) is None:
-            raise RuntimeError(f"{who}: field=None needs a device initialised through device_init (the mesh size)")
-        spec = bubble_spec(who, int(lib._N), **kw)
-    return distribution_on_device(lib, grid, spec)
+    return analyse("mfp_distribution", field, grid, bubble_spec, kw, distribution_on_device, cuda_is_init, load_asora)
 
 
 def distribution_on_device(lib, grid, spec):
     """The library call for a checked `spec` (bubble_spec) on device grid `grid`, as a :class:`BubbleSizes`."""
-    counts, tallies, moments = lib.bubble_mfp(grid, spec["threshold"], _PHASES[spec["phase"]], spec["periodic"], spec["seed"],
+    counts, tallies, moments = lib.bubble_mfp(grid, spec["threshold"], PHASES[spec["phase"]], spec["periodic"], spec["seed"],
                                               spec["n_rays"], spec["l_max"], spec["edges"])
     return BubbleSizes(spec["edges"], counts, tallies, moments, spec["n_rays"], spec["threshold"], spec["phase"], spec["seed"],
                        spec["l_max"], spec["periodic"], spec["dr"])

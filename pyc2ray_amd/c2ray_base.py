@@ -209,6 +209,41 @@ class _DeviceGrid:
         obj._host_newer.add(self.name)
 
 
+class _StepStatistic:
+    """A statistic that C2Ray can take after every time step, declared once: the attribute is its switch, a bool assignable
+    between steps.  `key`: its ``Output:`` key (0 | 1; absent: 0), the switch's value at construction.  `last`: the attribute a
+    step leaves the result in.  `method`: the method of C2Ray that computes it after the step (None: the step fills it itself).
+    `needs_gpu`: why True is refused on an object without use_gpu.  `doc`: the attribute's docstring.  `keys`: the further
+    ``Output:`` keys, each with the keyword of `method` whose default it sets.  ``validate(sim, kw)``: raises ValueError at
+    construction for what a call with those keywords would refuse.  C2Ray._statistic_init and C2Ray._close_step use all of it."""
+
+    def __init__(self, key, last, method, needs_gpu, doc, keys=(), validate=None):
+        self.key, self.last, self.method, self.needs_gpu, self.keys, self.validate = key, last, method, needs_gpu, keys, validate
+        self.__doc__ = doc
+
+    def __set_name__(self, owner, attr):
+        self.name, self.attr = attr, "_" + attr
+
+    def __get__(self, obj, objtype=None):
+        if obj is None:
+            return self
+        return obj.__dict__.get(self.attr, False)              # (an object that never read its keys: off)
+
+    def __set__(self, obj, value):
+        self.set(obj, value, f"C2Ray.{self.name}")
+
+    def set(self, obj, value, who):
+        if not isinstance(value, (bool, np.bool_)):
+            raise ValueError(f"{who}: {self.name} must be a bool, not {type(value).__name__}")
+        if value and not obj.gpu:
+            raise ValueError(f"{who}: {self.name} needs use_gpu=True ({self.needs_gpu})")
+        obj.__dict__[self.attr] = bool(value)
+
+    def defaults(self, obj):
+        """The keywords that the ``Output:`` keys of `obj` set for the method."""
+        return obj.__dict__.get(self.attr + "_defaults", {})
+
+
 class C2Ray:
     #: Default since round 6 (single GPU, use_gpu=True; set False on an instance for the reference's behaviour: every step uploads
     #: and downloads everything): ndens, temp, xh and phi_ion stay on the device between time steps.  evolve3D then uploads only
@@ -229,6 +264,70 @@ class C2Ray:
     temp = _DeviceGrid("temp", _capi.GRID_TEMP)
     xh = _DeviceGrid("xh", _capi.GRID_XH)
     phi_ion = _DeviceGrid("phi_ion", _capi.GRID_PHI_ION)
+
+    # The statistics of a time step.  A new one is one declaration here, its name in _STEP_STATISTICS and its method.
+    photon_budget = _StepStatistic(
+        "photon_budget", "last_budget", None, "the use_gpu=False loop takes no photon budget",
+        """Is every time step closed with its photon budget (pyc2ray_amd.budget.StepBudget; use_gpu=True only: on an object
+        without, True is refused at the assignment)?  A driver may assign a bool between steps.  After a step ``last_budget``
+        holds the step's budget and ``total_budget`` the sum since the object was made; rank 0 writes one line to the log.  The
+        sums are reduced on the device: no grid crosses PCIe for them, on the device-resident path either.""")
+    # bubble_rays: an integer >= 0, default 100000; bubble_threshold: a finite number, default 0.5; bubble_seed: an integer in
+    # [0, 2^64), default 0
+    bubble_stats = _StepStatistic(
+        "bubble_sizes", "last_bubble_sizes", "bubble_sizes", "the rays are marched on the device",
+        """Does every time step end with the size distribution of its ionised regions (:meth:`bubble_sizes` with the ``Output:
+        bubble_*`` keys; use_gpu=True only: on an object without, True is refused at the assignment)?  A driver may assign a bool
+        between steps.  After a step ``last_bubble_sizes`` holds the result and rank 0 writes one line to the log.""",
+        keys=(("bubble_rays", "n_rays"), ("bubble_threshold", "threshold"), ("bubble_seed", "seed")),
+        validate=lambda sim, kw: bubble_spec("Output: bubble_rays / bubble_threshold / bubble_seed", sim.N, **kw))
+    # region_threshold: a finite number, default 0.5; region_connectivity: 6 or 26, default 6  (the keys only are checked at
+    # construction, here and below: a mesh beyond the entry's limit is refused by a call)
+    region_stats = _StepStatistic(
+        "region_sizes", "last_regions", "regions", "the regions are labelled on the device",
+        """Does every time step end with the connected regions of its ionised fraction (:meth:`regions` with the ``Output:
+        region_*`` keys; use_gpu=True only: on an object without, True is refused at the assignment)?  A driver may assign a bool
+        between steps.  After a step ``last_regions`` holds the result and rank 0 writes one line to the log.""",
+        keys=(("region_threshold", "threshold"), ("region_connectivity", "connectivity")),
+        validate=lambda sim, kw: region_spec("Output: region_threshold / region_connectivity", None, **kw))
+    # topology_threshold: a finite number, default 0.5; topology_connectivity: 6 or 26, default 6
+    topology_stats = _StepStatistic(
+        "topology", "last_topology", "topology", "the elements are counted and the phases labelled on the device",
+        """Does every time step end with the topology of its ionised fraction (:meth:`topology` with the ``Output: topology_*``
+        keys; use_gpu=True only: on an object without, True is refused at the assignment)?  A driver may assign a bool between
+        steps.  After a step ``last_topology`` holds the result and rank 0 writes one line to the log.""",
+        keys=(("topology_threshold", "threshold"), ("topology_connectivity", "connectivity")),
+        validate=lambda sim, kw: topology_spec("Output: topology_threshold / topology_connectivity", None, **kw))
+    # granulometry_threshold: a finite number, default 0.5; granulometry_radii: an int n for the radii 1 ... n, or a list of
+    # ascending radii, default 1 ... max(1, min(N // 4, 32))
+    granulometry_stats = _StepStatistic(
+        "granulometry", "last_granulometry", "granulometry", "the distance transform and the openings run on the device",
+        """Does every time step end with the granulometry of its ionised fraction (:meth:`granulometry` with the ``Output:
+        granulometry_*`` keys; use_gpu=True only: on an object without, True is refused at the assignment)?  A driver may assign a
+        bool between steps.  After a step ``last_granulometry`` holds the result and rank 0 writes one line to the log.""",
+        keys=(("granulometry_threshold", "threshold"), ("granulometry_radii", "radii")),
+        validate=lambda sim, kw: granulometry_spec("Output: granulometry_threshold / granulometry_radii", None, **kw))
+    # power_spectrum_kind: 'xh', 'xhi', 'density', 'hi' or 'dtb', default 'dtb'; power_spectrum_bins: an int n for n equal bins, or
+    # a list of ascending edges in units of the fundamental mode, default unit-width bins
+    power_spectrum_stats = _StepStatistic(
+        "power_spectrum", "last_power_spectrum", "power_spectrum", "the transform and the binning run on the device",
+        """Does every time step end with the power spectrum of its state (:meth:`power_spectrum` with the ``Output:
+        power_spectrum_*`` keys; use_gpu=True only: on an object without, True is refused at the assignment)?  A driver may assign a
+        bool between steps.  After a step ``last_power_spectrum`` holds the result and rank 0 writes one line to the log.""",
+        keys=(("power_spectrum_kind", "kind"), ("power_spectrum_bins", "bins")),
+        validate=lambda sim, kw: powerspec_spec("Output: power_spectrum_kind / power_spectrum_bins", None, **kw))
+    # observed_baseline_km: a number > 0, default 2; observed_los_axis: 0, 1 or 2, default 2; observed_bins: an int n for n equal
+    # bins over the map's range, or a list of ascending edges in mK, default no histogram
+    observed_stats = _StepStatistic(
+        "observed_map", "last_observed", "observed_map", "the transforms and the statistics run on the device",
+        """Does every time step end with the observed map of its state (:meth:`observed_map` with the ``Output: observed_*`` keys;
+        use_gpu=True only: on an object without, True is refused at the assignment)?  A driver may assign a bool between steps.
+        After a step ``last_observed`` holds the result and rank 0 writes one line to the log.""",
+        keys=(("observed_baseline_km", "baseline_km"), ("observed_los_axis", "los_axis"), ("observed_bins", "bins")),
+        validate=lambda sim, kw: sim._observed_keys_spec(kw))
+    #: the order in which __init__ reads their keys and a step writes their lines to the log
+    _STEP_STATISTICS = ("photon_budget", "bubble_stats", "region_stats", "topology_stats", "granulometry_stats", "power_spectrum_stats",
+                        "observed_stats")
 
     def __init__(self, paramfile, Nmesh, use_gpu, use_mpi):
         """Basis class of a C2Ray simulation (pyc2ray/c2ray_base.py:82-145).
@@ -276,13 +375,8 @@ class C2Ray:
         self._lls_init()
         self._boundaries_init()
         self._plane_flux_init()
-        self._photon_budget_init()
-        self._bubble_init()
-        self._region_init()
-        self._topology_init()
-        self._granulometry_init()
-        self._power_spectrum_init()
-        self._observed_init()
+        for name in self._STEP_STATISTICS:
+            self._statistic_init(name)
         if self.rank == 0:
             if self.gpu:
                 q_max = np.ceil(1.73205080757 * min(self.R_max_LLS, 1.73205080757 * self.N / 2))
@@ -436,80 +530,54 @@ class C2Ray:
     def plane_flux(self, value):
         self.__dict__["_plane_flux"] = plane_flux_spec(value, "C2Ray.plane_flux", self.gpu)    # ValueError for what evolve3D would refuse, now
 
-    def _photon_budget_init(self):
-        """The optional key ``Output: photon_budget`` (0 | 1; absent: 0): whether every step is closed with its photon budget,
-        until ``photon_budget`` is assigned."""
-        v = (self._ld.get('Output') or {}).get('photon_budget', 0)
-        if isinstance(v, (bool, np.bool_)):
-            v = int(v)
-        if not isinstance(v, (int, np.integer)) or v not in (0, 1):
-            raise ValueError(f"Output: photon_budget must be 0 or 1, not {v!r}")
-        self.last_budget, self.total_budget = None, StepBudget()
-        self._set_photon_budget(bool(v), "Output: photon_budget: 1")
-
-    def _set_photon_budget(self, value, who):
-        if not isinstance(value, (bool, np.bool_)):
-            raise ValueError(f"{who}: photon_budget must be a bool, not {type(value).__name__}")
-        if value and not self.gpu:
-            raise ValueError(f"{who}: photon_budget needs use_gpu=True (the use_gpu=False loop takes no photon budget)")
-        self.__dict__["_photon_budget"] = bool(value)
-
-    @property
-    def photon_budget(self):
-        """Is every time step closed with its photon budget (pyc2ray_amd.budget.StepBudget; use_gpu=True only: on an object
-        without, True is refused at the assignment)?  A driver may assign a bool between steps.  After a step ``last_budget``
-        holds the step's budget and ``total_budget`` the sum since the object was made; rank 0 writes one line to the log.  The
-        sums are reduced on the device: no grid crosses PCIe for them, on the device-resident path either."""
-        return self.__dict__.get("_photon_budget", False)
-
-    @photon_budget.setter
-    def photon_budget(self, value):
-        self._set_photon_budget(value, "C2Ray.photon_budget")
-
-    def _close_budget(self, budget):
-        """A filled budget of the step just run (None: off) becomes last_budget, joins total_budget and the log."""
-        if budget is None:
-            return
-        self.last_budget = budget
-        self.total_budget = self.__dict__.get("total_budget", StepBudget()) + budget
-        if self.rank == 0:
-            self.printlog(budget.log_line())
-
-    def _bubble_init(self):
-        """The optional keys ``Output: bubble_sizes`` (0 | 1; absent: 0): whether every step ends with the size distribution of
-        its ionised regions, until ``bubble_stats`` is assigned; ``bubble_rays`` (an integer >= 0, default 100000),
-        ``bubble_threshold`` (a finite number, default 0.5) and ``bubble_seed`` (an integer in [0, 2^64), default 0): the ``n_rays``,
-        ``threshold`` and ``seed`` of those calls, and the defaults of :meth:`bubble_sizes`."""
+    # ---- statistics of a time step (the _StepStatistic declarations above) -------------------------
+    def _statistic_init(self, name):
+        """The ``Output:`` keys of the statistic declared as `name`: its own key (0 | 1; absent: 0) is the switch until that is
+        assigned; its further keys, checked now, are the defaults of its method; ``last_*`` starts empty."""
+        stat = getattr(type(self), name)
         out = self._ld.get('Output') or {}
-        v = out.get('bubble_sizes', 0)
+        v = out.get(stat.key, 0)
         if isinstance(v, (bool, np.bool_)):
             v = int(v)
         if not isinstance(v, (int, np.integer)) or v not in (0, 1):
-            raise ValueError(f"Output: bubble_sizes must be 0 or 1, not {v!r}")
-        kw = {name: out[key] for key, name in (("bubble_rays", "n_rays"), ("bubble_threshold", "threshold"), ("bubble_seed", "seed"))
-              if key in out}
-        bubble_spec("Output: bubble_rays / bubble_threshold / bubble_seed", self.N, **kw)     # ValueError for what a call would refuse, now
-        self.__dict__["_bubble_defaults"] = kw
-        self.last_bubble_sizes = None
-        self._set_bubble_stats(bool(v), "Output: bubble_sizes: 1")
+            raise ValueError(f"Output: {stat.key} must be 0 or 1, not {v!r}")
+        kw = {keyword: out[key] for key, keyword in stat.keys if key in out}
+        if stat.validate is not None:
+            stat.validate(self, kw)                             # ValueError for what a call would refuse, now
+        self.__dict__[stat.attr + "_defaults"] = kw
+        setattr(self, stat.last, None)
+        if name == "photon_budget":                             # (the one statistic that is also summed over the run)
+            self.total_budget = StepBudget()
+        stat.set(self, bool(v), f"Output: {stat.key}: 1")
 
-    def _set_bubble_stats(self, value, who):
-        if not isinstance(value, (bool, np.bool_)):
-            raise ValueError(f"{who}: bubble_stats must be a bool, not {type(value).__name__}")
-        if value and not self.gpu:
-            raise ValueError(f"{who}: bubble_stats needs use_gpu=True (the rays are marched on the device)")
-        self.__dict__["_bubble_stats"] = bool(value)
+    def _close_step(self, budget):
+        """The end of a time step.  The photon budget is filled by the step itself: `budget` (None: off) becomes last_budget, joins
+        total_budget and the log.  Every other statistic that is switched on is computed now, by its method, from the state the
+        step left: the result becomes its ``last_*`` and joins the log.  Off: no call, and ``last_*`` is left alone."""
+        if budget is not None:
+            self.last_budget = budget
+            self.total_budget = self.__dict__.get("total_budget", StepBudget()) + budget
+            if self.rank == 0:
+                self.printlog(budget.log_line())
+        for name in self._STEP_STATISTICS:
+            stat = getattr(type(self), name)
+            if stat.method is not None and getattr(self, name):
+                result = getattr(self, stat.method)()
+                setattr(self, stat.last, result)
+                if self.rank == 0:
+                    self.printlog(result.log_line())
 
-    @property
-    def bubble_stats(self):
-        """Does every time step end with the size distribution of its ionised regions (:meth:`bubble_sizes` with the ``Output:
-        bubble_*`` keys; use_gpu=True only: on an object without, True is refused at the assignment)?  A driver may assign a bool
-        between steps.  After a step ``last_bubble_sizes`` holds the result and rank 0 writes one line to the log."""
-        return self.__dict__.get("_bubble_stats", False)
-
-    @bubble_stats.setter
-    def bubble_stats(self, value):
-        self._set_bubble_stats(value, "C2Ray.bubble_stats")
+    def _analyse_xh(self, method, defaults, kw, spec, on_device, entry):
+        """The body of `method`, an analysis of the object's own ionised fraction with the keywords `kw` over `defaults`: on the
+        device grid where it lies while the last step's ``xh`` is there only, ``on_device(lib, grid, spec(who, N, **kw))``, else
+        through the module's ``entry(self.xh, **kw)``, which uploads the host array."""
+        for name in ("field", "grid"):
+            if name in kw:
+                raise ValueError(f"C2Ray.{method}: {name} is not for the class (it analyses its own ionised fraction)")
+        kw = {**defaults, "periodic": self.periodic, "dr": self.dr, **kw}
+        if self.device_resident and self.gpu and not self.mpi and "xh" in self._device_newer and cuda_is_init():
+            return on_device(load_asora(), _capi.GRID_XH, spec(f"C2Ray.{method}", self.N, **kw))
+        return entry(self.xh, **kw)
 
     def bubble_sizes(self, **kw):
         """The mean-free-path size distribution of the ionised regions of the current state, a
@@ -518,58 +586,7 @@ class C2Ray:
         the parameter file for ``n_rays``, ``threshold`` and ``seed``.  While the ionised fraction of the last step lives on the
         device only (``device_resident``), it is analysed there: nothing is downloaded, and ``xh`` stays where it is.  Otherwise --
         with ``use_mpi`` too -- the host array is uploaded and analysed; every rank computes the same result from its own copy."""
-        for name in ("field", "grid"):
-            if name in kw:
-                raise ValueError(f"C2Ray.bubble_sizes: {name} is not for the class (it analyses its own ionised fraction)")
-        kw = {**self.__dict__.get("_bubble_defaults", {}), "periodic": self.periodic, "dr": self.dr, **kw}
-        if self.device_resident and self.gpu and not self.mpi and "xh" in self._device_newer and cuda_is_init():
-            spec = bubble_spec("C2Ray.bubble_sizes", self.N, **kw)
-            return distribution_on_device(load_asora(), _capi.GRID_XH, spec)
-        return mfp_distribution(self.xh, **kw)
-
-    def _close_bubbles(self):
-        """With ``bubble_stats``: the distribution of the step just run becomes last_bubble_sizes and joins the log."""
-        if not self.bubble_stats:
-            return
-        self.last_bubble_sizes = self.bubble_sizes()
-        if self.rank == 0:
-            self.printlog(self.last_bubble_sizes.log_line())
-
-    def _region_init(self):
-        """The optional keys ``Output: region_sizes`` (0 | 1; absent: 0): whether every step ends with the connected regions of its
-        ionised fraction, until ``region_stats`` is assigned; ``region_threshold`` (a finite number, default 0.5) and
-        ``region_connectivity`` (6 or 26, default 6): the ``threshold`` and ``connectivity`` of those calls, and the defaults of
-        :meth:`regions`."""
-        out = self._ld.get('Output') or {}
-        v = out.get('region_sizes', 0)
-        if isinstance(v, (bool, np.bool_)):
-            v = int(v)
-        if not isinstance(v, (int, np.integer)) or v not in (0, 1):
-            raise ValueError(f"Output: region_sizes must be 0 or 1, not {v!r}")
-        kw = {name: out[key] for key, name in (("region_threshold", "threshold"), ("region_connectivity", "connectivity")) if key in out}
-        region_spec("Output: region_threshold / region_connectivity", None, **kw)     # ValueError for what a call would refuse, now
-                                                                                       # (the keys only: a mesh beyond the entry's limit is refused by a call)
-        self.__dict__["_region_defaults"] = kw
-        self.last_regions = None
-        self._set_region_stats(bool(v), "Output: region_sizes: 1")
-
-    def _set_region_stats(self, value, who):
-        if not isinstance(value, (bool, np.bool_)):
-            raise ValueError(f"{who}: region_stats must be a bool, not {type(value).__name__}")
-        if value and not self.gpu:
-            raise ValueError(f"{who}: region_stats needs use_gpu=True (the regions are labelled on the device)")
-        self.__dict__["_region_stats"] = bool(value)
-
-    @property
-    def region_stats(self):
-        """Does every time step end with the connected regions of its ionised fraction (:meth:`regions` with the ``Output:
-        region_*`` keys; use_gpu=True only: on an object without, True is refused at the assignment)?  A driver may assign a bool
-        between steps.  After a step ``last_regions`` holds the result and rank 0 writes one line to the log."""
-        return self.__dict__.get("_region_stats", False)
-
-    @region_stats.setter
-    def region_stats(self, value):
-        self._set_region_stats(value, "C2Ray.region_stats")
+        return self._analyse_xh("bubble_sizes", C2Ray.bubble_stats.defaults(self), kw, bubble_spec, distribution_on_device, mfp_distribution)
 
     def regions(self, **kw):
         """The connected ionised regions of the current state, a :class:`pyc2ray_amd.regions.RegionSizes`; the keywords of
@@ -578,57 +595,7 @@ class C2Ray:
         While the ionised fraction of the last step lives on the device only (``device_resident``), it is analysed there: nothing
         is downloaded, and ``xh`` stays where it is.  Otherwise -- with ``use_mpi`` too -- the host array is uploaded and analysed;
         every rank computes the same result from its own copy."""
-        for name in ("field", "grid"):
-            if name in kw:
-                raise ValueError(f"C2Ray.regions: {name} is not for the class (it analyses its own ionised fraction)")
-        kw = {**self.__dict__.get("_region_defaults", {}), "periodic": self.periodic, "dr": self.dr, **kw}
-        if self.device_resident and self.gpu and not self.mpi and "xh" in self._device_newer and cuda_is_init():
-            spec = region_spec("C2Ray.regions", self.N, **kw)
-            return regions_on_device(load_asora(), _capi.GRID_XH, spec)
-        return region_sizes(self.xh, **kw)
-
-    def _close_regions(self):
-        """With ``region_stats``: the regions of the step just run become last_regions and join the log."""
-        if not self.region_stats:
-            return
-        self.last_regions = self.regions()
-        if self.rank == 0:
-            self.printlog(self.last_regions.log_line())
-
-    def _topology_init(self):
-        """The optional keys ``Output: topology`` (0 | 1; absent: 0): whether every step ends with the topology of its ionised
-        fraction, until ``topology_stats`` is assigned; ``topology_threshold`` (a finite number, default 0.5) and
-        ``topology_connectivity`` (6 or 26, default 6): the ``threshold`` and ``connectivity`` of those calls, and the defaults of
-        :meth:`topology`."""
-        out = self._ld.get('Output') or {}
-        v = out.get('topology', 0)
-        if isinstance(v, (bool, np.bool_)):
-            v = int(v)
-        if not isinstance(v, (int, np.integer)) or v not in (0, 1):
-            raise ValueError(f"Output: topology must be 0 or 1, not {v!r}")
-        kw = {name: out[key] for key, name in (("topology_threshold", "threshold"), ("topology_connectivity", "connectivity")) if key in out}
-        topology_spec("Output: topology_threshold / topology_connectivity", None, **kw)    # ValueError for what a call would refuse, now
-        self.__dict__["_topology_defaults"] = kw
-        self.last_topology = None
-        self._set_topology_stats(bool(v), "Output: topology: 1")
-
-    def _set_topology_stats(self, value, who):
-        if not isinstance(value, (bool, np.bool_)):
-            raise ValueError(f"{who}: topology_stats must be a bool, not {type(value).__name__}")
-        if value and not self.gpu:
-            raise ValueError(f"{who}: topology_stats needs use_gpu=True (the elements are counted and the phases labelled on the device)")
-        self.__dict__["_topology_stats"] = bool(value)
-
-    @property
-    def topology_stats(self):
-        """Does every time step end with the topology of its ionised fraction (:meth:`topology` with the ``Output: topology_*``
-        keys; use_gpu=True only: on an object without, True is refused at the assignment)?  A driver may assign a bool between
-        steps.  After a step ``last_topology`` holds the result and rank 0 writes one line to the log."""
-        return self.__dict__.get("_topology_stats", False)
-
-    @topology_stats.setter
-    def topology_stats(self, value):
-        self._set_topology_stats(value, "C2Ray.topology_stats")
+        return self._analyse_xh("regions", C2Ray.region_stats.defaults(self), kw, region_spec, regions_on_device, region_sizes)
 
     def topology(self, **kw):
         """The topology of the ionised cells of the current state, a :class:`pyc2ray_amd.topology.Topology`; the keywords of
@@ -637,57 +604,7 @@ class C2Ray:
         While the ionised fraction of the last step lives on the device only (``device_resident``), it is analysed there: nothing
         is downloaded, and ``xh`` stays where it is.  Otherwise -- with ``use_mpi`` too -- the host array is uploaded and analysed;
         every rank computes the same result from its own copy."""
-        for name in ("field", "grid"):
-            if name in kw:
-                raise ValueError(f"C2Ray.topology: {name} is not for the class (it analyses its own ionised fraction)")
-        kw = {**self.__dict__.get("_topology_defaults", {}), "periodic": self.periodic, "dr": self.dr, **kw}
-        if self.device_resident and self.gpu and not self.mpi and "xh" in self._device_newer and cuda_is_init():
-            spec = topology_spec("C2Ray.topology", self.N, **kw)
-            return topology_on_device(load_asora(), _capi.GRID_XH, spec)
-        return field_topology(self.xh, **kw)
-
-    def _close_topology(self):
-        """With ``topology_stats``: the topology of the step just run becomes last_topology and joins the log."""
-        if not self.topology_stats:
-            return
-        self.last_topology = self.topology()
-        if self.rank == 0:
-            self.printlog(self.last_topology.log_line())
-
-    def _granulometry_init(self):
-        """The optional keys ``Output: granulometry`` (0 | 1; absent: 0): whether every step ends with the granulometry of its ionised
-        fraction, until ``granulometry_stats`` is assigned; ``granulometry_threshold`` (a finite number, default 0.5) and
-        ``granulometry_radii`` (an int n for the radii 1 ... n, or a list of ascending radii; default 1 ... max(1, min(N // 4, 32))):
-        the ``threshold`` and ``radii`` of those calls, and the defaults of :meth:`granulometry`."""
-        out = self._ld.get('Output') or {}
-        v = out.get('granulometry', 0)
-        if isinstance(v, (bool, np.bool_)):
-            v = int(v)
-        if not isinstance(v, (int, np.integer)) or v not in (0, 1):
-            raise ValueError(f"Output: granulometry must be 0 or 1, not {v!r}")
-        kw = {name: out[key] for key, name in (("granulometry_threshold", "threshold"), ("granulometry_radii", "radii")) if key in out}
-        granulometry_spec("Output: granulometry_threshold / granulometry_radii", None, **kw)    # ValueError for what a call would refuse, now
-        self.__dict__["_granulometry_defaults"] = kw
-        self.last_granulometry = None
-        self._set_granulometry_stats(bool(v), "Output: granulometry: 1")
-
-    def _set_granulometry_stats(self, value, who):
-        if not isinstance(value, (bool, np.bool_)):
-            raise ValueError(f"{who}: granulometry_stats must be a bool, not {type(value).__name__}")
-        if value and not self.gpu:
-            raise ValueError(f"{who}: granulometry_stats needs use_gpu=True (the distance transform and the openings run on the device)")
-        self.__dict__["_granulometry_stats"] = bool(value)
-
-    @property
-    def granulometry_stats(self):
-        """Does every time step end with the granulometry of its ionised fraction (:meth:`granulometry` with the ``Output:
-        granulometry_*`` keys; use_gpu=True only: on an object without, True is refused at the assignment)?  A driver may assign a
-        bool between steps.  After a step ``last_granulometry`` holds the result and rank 0 writes one line to the log."""
-        return self.__dict__.get("_granulometry_stats", False)
-
-    @granulometry_stats.setter
-    def granulometry_stats(self, value):
-        self._set_granulometry_stats(value, "C2Ray.granulometry_stats")
+        return self._analyse_xh("topology", C2Ray.topology_stats.defaults(self), kw, topology_spec, topology_on_device, field_topology)
 
     def granulometry(self, **kw):
         """The granulometry of the ionised cells of the current state, a :class:`pyc2ray_amd.granulometry.Granulometry`; the keywords
@@ -696,57 +613,8 @@ class C2Ray:
         While the ionised fraction of the last step lives on the device only (``device_resident``), it is analysed there: nothing
         is downloaded, and ``xh`` stays where it is.  Otherwise -- with ``use_mpi`` too -- the host array is uploaded and analysed;
         every rank computes the same result from its own copy."""
-        for name in ("field", "grid"):
-            if name in kw:
-                raise ValueError(f"C2Ray.granulometry: {name} is not for the class (it analyses its own ionised fraction)")
-        kw = {**self.__dict__.get("_granulometry_defaults", {}), "periodic": self.periodic, "dr": self.dr, **kw}
-        if self.device_resident and self.gpu and not self.mpi and "xh" in self._device_newer and cuda_is_init():
-            spec = granulometry_spec("C2Ray.granulometry", self.N, **kw)
-            return granulometry_on_device(load_asora(), _capi.GRID_XH, spec)
-        return field_granulometry(self.xh, **kw)
-
-    def _close_granulometry(self):
-        """With ``granulometry_stats``: the granulometry of the step just run becomes last_granulometry and joins the log."""
-        if not self.granulometry_stats:
-            return
-        self.last_granulometry = self.granulometry()
-        if self.rank == 0:
-            self.printlog(self.last_granulometry.log_line())
-
-    def _power_spectrum_init(self):
-        """The optional keys ``Output: power_spectrum`` (0 | 1; absent: 0): whether every step ends with the power spectrum of its
-        state, until ``power_spectrum_stats`` is assigned; ``power_spectrum_kind`` ('xh', 'xhi', 'density', 'hi' or 'dtb', default
-        'dtb') and ``power_spectrum_bins`` (an int n for n equal bins, or a list of ascending edges in units of the fundamental mode;
-        default unit-width bins): the ``kind`` and ``bins`` of those calls, and the defaults of :meth:`power_spectrum`."""
-        out = self._ld.get('Output') or {}
-        v = out.get('power_spectrum', 0)
-        if isinstance(v, (bool, np.bool_)):
-            v = int(v)
-        if not isinstance(v, (int, np.integer)) or v not in (0, 1):
-            raise ValueError(f"Output: power_spectrum must be 0 or 1, not {v!r}")
-        kw = {name: out[key] for key, name in (("power_spectrum_kind", "kind"), ("power_spectrum_bins", "bins")) if key in out}
-        powerspec_spec("Output: power_spectrum_kind / power_spectrum_bins", None, **kw)    # ValueError for what a call would refuse, now
-        self.__dict__["_power_spectrum_defaults"] = kw
-        self.last_power_spectrum = None
-        self._set_power_spectrum_stats(bool(v), "Output: power_spectrum: 1")
-
-    def _set_power_spectrum_stats(self, value, who):
-        if not isinstance(value, (bool, np.bool_)):
-            raise ValueError(f"{who}: power_spectrum_stats must be a bool, not {type(value).__name__}")
-        if value and not self.gpu:
-            raise ValueError(f"{who}: power_spectrum_stats needs use_gpu=True (the transform and the binning run on the device)")
-        self.__dict__["_power_spectrum_stats"] = bool(value)
-
-    @property
-    def power_spectrum_stats(self):
-        """Does every time step end with the power spectrum of its state (:meth:`power_spectrum` with the ``Output:
-        power_spectrum_*`` keys; use_gpu=True only: on an object without, True is refused at the assignment)?  A driver may assign a
-        bool between steps.  After a step ``last_power_spectrum`` holds the result and rank 0 writes one line to the log."""
-        return self.__dict__.get("_power_spectrum_stats", False)
-
-    @power_spectrum_stats.setter
-    def power_spectrum_stats(self, value):
-        self._set_power_spectrum_stats(value, "C2Ray.power_spectrum_stats")
+        return self._analyse_xh("granulometry", C2Ray.granulometry_stats.defaults(self), kw, granulometry_spec, granulometry_on_device,
+                                field_granulometry)
 
     def brightness_temperature_scale(self):
         """The prefactor of the 21-cm differential brightness temperature at ``self.zred`` in mK, from the object's own cosmology:
@@ -754,6 +622,32 @@ class C2Ray:
         cs = self._ld['Cosmology']
         h2 = float(cs['h']) ** 2
         return 27.0 * math.sqrt((1.0 + float(self.zred)) / 10.0 * 0.15 / (float(cs['Omega0']) * h2)) * (float(cs['Omega_B']) * h2 / 0.023)
+
+    def _spin_t_gamma(self, who, kw):
+        """``spin`` leaves the keywords `kw` of a transform analysis: 'kinetic' puts ``t_gamma``, the CMB temperature at
+        ``self.zred``, in its place."""
+        spin = kw.pop("spin", None)
+        if spin not in (None, "kinetic"):
+            raise ValueError(f"{who}: spin must be None or 'kinetic', not {spin!r}")
+        if spin == "kinetic":
+            if "t_gamma" in kw:
+                raise ValueError(f"{who}: spin='kinetic' sets t_gamma itself")
+            kw["t_gamma"] = float(self._ld['Cosmology']['cmbtemp']) * (1.0 + float(self.zred))
+
+    def _state_on_device(self, overwritten=False):
+        """The library, with the object's ionised fraction, density and temperature on the device: where they lie while the last
+        step's ``xh`` is there only and the host has touched neither of the other two, else -- or if the call to come will have
+        `overwritten` a grid -- uploaded from the host arrays."""
+        if not cuda_is_init():
+            raise RuntimeError("GPU not initialized. Please initialize it by calling device_init(N)")
+        lib = load_asora()
+        stale = {"ndens", "temp"} & self._host_newer
+        resident = self.device_resident and self.gpu and not self.mpi and "xh" in self._device_newer and not stale
+        if not resident or overwritten:
+            _residency.reclaim()          # (this object's device copies among them: they come down first)
+            for which, grid in ((_capi.GRID_XH, self.xh), (_capi.GRID_NDENS, self.ndens), (_capi.GRID_TEMP, self.temp)):
+                lib.grid_to_device(which, np.asarray(grid, dtype=np.float64))
+        return lib
 
     def power_spectrum(self, **kw):
         """The spherically averaged power spectrum of the current state, a :class:`pyc2ray_amd.powerspec.PowerSpectrum`; the keywords
@@ -768,52 +662,11 @@ class C2Ray:
         for name in ("field", "field_b"):
             if name in kw:
                 raise ValueError(f"C2Ray.power_spectrum: {name} is not for the class (it analyses its own grids)")
-        kw = {**self.__dict__.get("_power_spectrum_defaults", {}), **kw}
-        spin = kw.pop("spin", None)
-        if spin not in (None, "kinetic"):
-            raise ValueError(f"C2Ray.power_spectrum: spin must be None or 'kinetic', not {spin!r}")
-        if spin == "kinetic":
-            if "t_gamma" in kw:
-                raise ValueError("C2Ray.power_spectrum: spin='kinetic' sets t_gamma itself")
-            kw["t_gamma"] = float(self._ld['Cosmology']['cmbtemp']) * (1.0 + float(self.zred))
+        kw = {**C2Ray.power_spectrum_stats.defaults(self), **kw}
+        self._spin_t_gamma("C2Ray.power_spectrum", kw)
         kw = {"scale": self.brightness_temperature_scale(), "box_len": self.boxsize_c / Mpc, **kw}
         spec = powerspec_spec("C2Ray.power_spectrum", self.N, **kw)
-        if not cuda_is_init():
-            raise RuntimeError("GPU not initialized. Please initialize it by calling device_init(N)")
-        lib = load_asora()
-        stale = {"ndens", "temp"} & self._host_newer
-        if not (self.device_resident and self.gpu and not self.mpi and "xh" in self._device_newer and not stale):
-            _residency.reclaim()          # (this object's device copies among them: they come down first)
-            for which, grid in ((_capi.GRID_XH, self.xh), (_capi.GRID_NDENS, self.ndens), (_capi.GRID_TEMP, self.temp)):
-                lib.grid_to_device(which, np.asarray(grid, dtype=np.float64))
-        return powerspec_on_device(lib, spec)
-
-    def _close_power_spectrum(self):
-        """With ``power_spectrum_stats``: the power spectrum of the step just run becomes last_power_spectrum and joins the log."""
-        if not self.power_spectrum_stats:
-            return
-        self.last_power_spectrum = self.power_spectrum()
-        if self.rank == 0:
-            self.printlog(self.last_power_spectrum.log_line())
-
-    def _observed_init(self):
-        """The optional keys ``Output: observed_map`` (0 | 1; absent: 0): whether every step ends with the observed map of its state,
-        until ``observed_stats`` is assigned; ``observed_baseline_km`` (a number > 0, default 2), ``observed_los_axis`` (0, 1 or 2,
-        default 2) and ``observed_bins`` (an int n for n equal bins over the map's range, or a list of ascending edges in mK; default
-        no histogram): the ``baseline_km``, ``los_axis`` and ``bins`` of those calls, and the defaults of :meth:`observed_map`."""
-        out = self._ld.get('Output') or {}
-        v = out.get('observed_map', 0)
-        if isinstance(v, (bool, np.bool_)):
-            v = int(v)
-        if not isinstance(v, (int, np.integer)) or v not in (0, 1):
-            raise ValueError(f"Output: observed_map must be 0 or 1, not {v!r}")
-        kw = {name: out[key] for key, name in (("observed_baseline_km", "baseline_km"), ("observed_los_axis", "los_axis"),
-                                               ("observed_bins", "bins")) if key in out}
-        self._observed_filter_spec("Output: observed_baseline_km / observed_los_axis", kw.get("baseline_km", 2.0), kw.get("los_axis", 2))
-        smoothing_spec("Output: observed_bins", None, bins=kw.get("bins"))     # ValueError for what a call would refuse, now
-        self.__dict__["_observed_defaults"] = kw
-        self.last_observed = None
-        self._set_observed_stats(bool(v), "Output: observed_map: 1")
+        return powerspec_on_device(self._state_on_device(), spec)
 
     @staticmethod
     def _observed_filter_spec(who, baseline_km, los_axis):
@@ -824,23 +677,10 @@ class C2Ray:
             raise ValueError(f"{who}: los_axis must be 0, 1 or 2, not {los_axis!r}")
         return float(baseline_km), int(los_axis)
 
-    def _set_observed_stats(self, value, who):
-        if not isinstance(value, (bool, np.bool_)):
-            raise ValueError(f"{who}: observed_stats must be a bool, not {type(value).__name__}")
-        if value and not self.gpu:
-            raise ValueError(f"{who}: observed_stats needs use_gpu=True (the transforms and the statistics run on the device)")
-        self.__dict__["_observed_stats"] = bool(value)
-
-    @property
-    def observed_stats(self):
-        """Does every time step end with the observed map of its state (:meth:`observed_map` with the ``Output: observed_*`` keys;
-        use_gpu=True only: on an object without, True is refused at the assignment)?  A driver may assign a bool between steps.
-        After a step ``last_observed`` holds the result and rank 0 writes one line to the log."""
-        return self.__dict__.get("_observed_stats", False)
-
-    @observed_stats.setter
-    def observed_stats(self, value):
-        self._set_observed_stats(value, "C2Ray.observed_stats")
+    def _observed_keys_spec(self, kw):
+        """What the declaration of ``observed_stats`` checks of the ``Output: observed_*`` keys at construction."""
+        self._observed_filter_spec("Output: observed_baseline_km / observed_los_axis", kw.get("baseline_km", 2.0), kw.get("los_axis", 2))
+        smoothing_spec("Output: observed_bins", None, bins=kw.get("bins"))
 
     def comoving_distance(self, z):
         """The line-of-sight comoving distance to redshift z in Mpc, from the object's cosmology."""
@@ -867,25 +707,10 @@ class C2Ray:
         come down first, and every grid goes up again at the next step."""
         if "field" in kw:
             raise ValueError("C2Ray.smoothed_field: field is not for the class (it analyses its own grids)")
-        spin = kw.pop("spin", None)
-        if spin not in (None, "kinetic"):
-            raise ValueError(f"C2Ray.smoothed_field: spin must be None or 'kinetic', not {spin!r}")
-        if spin == "kinetic":
-            if "t_gamma" in kw:
-                raise ValueError("C2Ray.smoothed_field: spin='kinetic' sets t_gamma itself")
-            kw["t_gamma"] = float(self._ld['Cosmology']['cmbtemp']) * (1.0 + float(self.zred))
+        self._spin_t_gamma("C2Ray.smoothed_field", kw)
         kw = {"scale": self.brightness_temperature_scale(), **kw}
         spec = smoothing_spec("C2Ray.smoothed_field", self.N, **kw)
-        if not cuda_is_init():
-            raise RuntimeError("GPU not initialized. Please initialize it by calling device_init(N)")
-        lib = load_asora()
-        stale = {"ndens", "temp"} & self._host_newer
-        resident = self.device_resident and self.gpu and not self.mpi and "xh" in self._device_newer and not stale
-        if not resident or spec["into"] is not None:
-            _residency.reclaim()          # (this object's device copies among them: they come down first)
-            for which, grid in ((_capi.GRID_XH, self.xh), (_capi.GRID_NDENS, self.ndens), (_capi.GRID_TEMP, self.temp)):
-                lib.grid_to_device(which, np.asarray(grid, dtype=np.float64))
-        return smoothing_on_device(lib, spec, "C2Ray.smoothed_field")
+        return smoothing_on_device(self._state_on_device(overwritten=spec["into"] is not None), spec, "C2Ray.smoothed_field")
 
     def observed_map(self, baseline_km=None, los_axis=None, subtract_mean=True, **kw):
         """The brightness temperature of the current state as an interferometer with maximum baseline `baseline_km` (default 2, or
@@ -894,7 +719,7 @@ class C2Ray:
         the mean removed unless ``subtract_mean=False``: :meth:`smoothed_field` with that filter, and its other keywords."""
         if "filter" in kw:
             raise ValueError("C2Ray.observed_map: the filter is the telescope's (smoothed_field takes any)")
-        d = self.__dict__.get("_observed_defaults", {})
+        d = C2Ray.observed_stats.defaults(self)
         baseline_km = d.get("baseline_km", 2.0) if baseline_km is None else baseline_km
         los_axis = d.get("los_axis", 2) if los_axis is None else los_axis
         baseline_km, los_axis = self._observed_filter_spec("C2Ray.observed_map", baseline_km, los_axis)
@@ -902,14 +727,6 @@ class C2Ray:
             kw = {"bins": d["bins"], **kw}
         width = self.beam_fwhm_cells(baseline_km)
         return self.smoothed_field(filter=telescope(width, width, los_axis), subtract_mean=subtract_mean, **kw)
-
-    def _close_observed(self):
-        """With ``observed_stats``: the observed map of the step just run becomes last_observed and joins the log."""
-        if not self.observed_stats:
-            return
-        self.last_observed = self.observed_map()
-        if self.rank == 0:
-            self.printlog(self.last_observed.log_line())
 
     def evolve3D(self, dt, src_flux, src_pos, src_spectrum=None):
         """Evolve the grid over one time step (c2ray_base.py:170-226).  src_spectrum: with ``BlackBodySource: Teff`` a list, the
@@ -932,13 +749,7 @@ class C2Ray:
         self.xh, self.phi_ion = result[:2]
         if thermal is not None:
             self.temp = result[2]
-        self._close_budget(budget.get("budget"))
-        self._close_bubbles()
-        self._close_regions()
-        self._close_topology()
-        self._close_granulometry()
-        self._close_power_spectrum()
-        self._close_observed()
+        self._close_step(budget.get("budget"))
 
     @classmethod
     def _fingerprint(cls, arr):
@@ -1002,13 +813,7 @@ class C2Ray:
                           lls=self.lls, periodic=self.periodic, plane_flux=self.plane_flux, **budget)
         self._host_newer -= {"ndens", "temp", "xh", "phi_ion", "clumping"}
         self._device_newer |= {"xh", "phi_ion"} if self.isothermal else {"xh", "phi_ion", "temp"}
-        self._close_budget(budget.get("budget"))
-        self._close_bubbles()
-        self._close_regions()
-        self._close_topology()
-        self._close_granulometry()
-        self._close_power_spectrum()
-        self._close_observed()
+        self._close_step(budget.get("budget"))
 
     def cosmo_evolve(self, dt):
         """Advance time and redshift by dt, diluting density and rescaling the cell size when the run is

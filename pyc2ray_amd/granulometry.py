@@ -15,13 +15,13 @@ import math
 
 import numpy as np
 
-from . import _capi, _residency
+from . import _capi
 from .asora_core import cuda_is_init
 from .load_extensions import load_asora
+from ._fieldspec import MESH_LABELS, PHASES, analyse, check_dr, check_flag, check_mesh, check_phase, check_threshold, is_int
 
 __all__ = ['Granulometry', 'granulometry']
 
-_PHASES = {"ionised": 0, "neutral": 1}
 _TALLIES = ("n_phase", "d2_max", "n_unbounded", "sum_d2")
 _MAX_R2 = 2.0 ** 31
 
@@ -161,14 +161,6 @@ class Granulometry:
         return f"<Granulometry: {self.log_line()}>"
 
 
-def _is_int(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-
-
-def _is_real(v):
-    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
-
-
 def _radii(who, N, radii):
     """None: 1 ... max(1, min(N // 4, 32)) (needs N); an int n: 1 ... n; else an array of finite, >= 0, strictly ascending radii."""
     if radii is None:
@@ -177,7 +169,7 @@ def _radii(who, N, radii):
         return np.arange(1, max(1, min(N // 4, 32)) + 1, dtype=np.float64)
     if isinstance(radii, (bool, np.bool_)):
         raise ValueError(f"{who}: radii must be None, an int or an array of radii, not a bool")
-    if _is_int(radii):
+    if is_int(radii):
         if not 1 <= radii <= _capi.BUBBLE_MAX_BINS:
             raise ValueError(f"{who}: radii as an int must be in [1, {_capi.BUBBLE_MAX_BINS}], not {radii}")
         return np.arange(1, int(radii) + 1, dtype=np.float64)
@@ -201,21 +193,15 @@ def _radii(who, N, radii):
 def granulometry_spec(who, N, threshold=0.5, phase="ionised", periodic=True, radii=None, dr=None, distances=False):
     """The keywords of :func:`granulometry` checked and completed for a mesh of N cells a side, as a dict (N = None: checked only).
     Raises ValueError -- before any device call -- for what the library would refuse."""
-    if not _is_real(threshold) or not math.isfinite(threshold):
-        raise ValueError(f"{who}: threshold must be a finite number, not {threshold!r}")
-    if phase not in _PHASES:
-        raise ValueError(f"{who}: phase must be 'ionised' or 'neutral', not {phase!r}")
-    if not isinstance(periodic, (bool, np.bool_)):
-        raise ValueError(f"{who}: periodic must be a bool, not {type(periodic).__name__}")
+    check_threshold(who, threshold)
+    check_phase(who, phase)
+    check_flag(who, "periodic", periodic)
     r = _radii(who, N, radii)
-    if dr is not None and (not _is_real(dr) or not (math.isfinite(dr) and dr > 0)):
-        raise ValueError(f"{who}: dr must be None or a finite number > 0, not {dr!r}")
-    if not isinstance(distances, (bool, np.bool_)):
-        raise ValueError(f"{who}: distances must be a bool, not {type(distances).__name__}")
+    check_dr(who, dr)
+    check_flag(who, "distances", distances)
     if N is None:                          # (only the checks: the mesh size is the device's, asked for afterwards)
         return None
-    if not 1 <= N <= _capi.REGION_MAX_N:
-        raise ValueError(f"{who}: the mesh must have 1 ... {_capi.REGION_MAX_N} cells a side (8 bytes per cell on the device: 2 GiB there), not {N}")
+    check_mesh(who, N, MESH_LABELS)
     return dict(N=int(N), threshold=float(threshold), phase=phase, periodic=bool(periodic), radii=r, dr=None if dr is None else float(dr),
                 distances=bool(distances))
 
@@ -231,37 +217,12 @@ def granulometry(field=None, *, threshold=0.5, phase='ionised', periodic=True, r
     ``radii``: None for 1 ... max(1, min(N // 4, 32)), an int n for 1 ... n, or an array of finite, >= 0, strictly ascending radii
     (at most 256, R^2 < 2^31).  ``dr``: the size of a cell, for the ``*_phys`` attributes of the result.  ``distances``: download the
     squared distance transform as well (``dist2`` of the result)."""
-    who = "granulometry"
-    if field is not None:
-        if grid is not None:
-            raise ValueError(f"{who}: grid selects a device grid and goes with field=None")
-        field = np.asarray(field)
-        if field.ndim != 3 or field.shape != (field.shape[0],) * 3 or field.dtype.kind not in "fiu":
-            raise ValueError(f"{who}: field must be a real (N, N, N) array")
-        N = field.shape[0]
-    else:
-        grid = _capi.GRID_XH if grid is None else grid
-        if not _is_int(grid) or not 0 <= grid <= _capi.GRID_CLUMP:
-            raise ValueError(f"{who}: grid must be one of the _capi.GRID_* selectors, not {grid!r}")
-        N = None
     kw = dict(threshold=threshold, phase=phase, periodic=periodic, radii=radii, dr=dr, distances=distances)
-    spec = granulometry_spec(who, N, **kw)
-    if not cuda_is_init():
-        raise RuntimeError("GPU not initialized. Please initialize it by calling device_init(N)")
-    lib = load_asora()
-    if field is not None:
-        _residency.reclaim()              # this call overwrites a device grid a resident C2Ray object may be relying on
-        lib.grid_to_device(_capi.GRID_XH, np.asarray(field, dtype=np.float64))
-        grid = _capi.GRID_XH
-    else:
-        if getattr(lib, "_N", None) is None:
-            raise RuntimeError(f"{who}: field=None needs a device initialised through device_init (the mesh size)")
-        spec = granulometry_spec(who, int(lib._N), **kw)
-    return granulometry_on_device(lib, grid, spec)
+    return analyse("granulometry", field, grid, granulometry_spec, kw, granulometry_on_device, cuda_is_init, load_asora)
 
 
 def granulometry_on_device(lib, grid, spec):
     """The library call for a checked `spec` (granulometry_spec) on device grid `grid`, as a :class:`Granulometry`."""
-    got = lib.granulometry(grid, spec["threshold"], _PHASES[spec["phase"]], spec["periodic"], spec["radii"], distances=spec["distances"])
+    got = lib.granulometry(grid, spec["threshold"], PHASES[spec["phase"]], spec["periodic"], spec["radii"], distances=spec["distances"])
     return Granulometry(spec["radii"], got[0], got[1], got[2], spec["N"], spec["threshold"], spec["phase"], spec["periodic"], spec["dr"],
                         dist2=got[3] if spec["distances"] else None)

@@ -17,6 +17,7 @@ import numpy as np
 from . import _capi, _residency
 from .asora_core import cuda_is_init
 from .load_extensions import load_asora
+from ._fieldspec import MESH_TRANSFORM, check_flag, check_mesh, check_scale, check_t_gamma, host_field, is_int, is_real
 
 __all__ = ['PowerSpectrum', 'power_spectrum']
 
@@ -161,12 +162,9 @@ class PowerSpectrum:
         return f"<PowerSpectrum: {self.log_line()}>"
 
 
-def _is_int(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-
-
-def _is_real(v):
-    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+def _check_kind(who, kind):
+    if not isinstance(kind, str) or kind not in _KINDS:
+        raise ValueError(f"{who}: kind must be one of {', '.join(repr(k) for k in _KINDS)}, not {kind!r}")
 
 
 def _edges_to_thresholds(edges):
@@ -182,7 +180,7 @@ def _edges(who, N, bins):
         return None if N is None else np.arange(0, max(1, min(N // 2, _capi.BUBBLE_MAX_BINS)) + 1, dtype=np.float64) + 0.5
     if isinstance(bins, (bool, np.bool_)):
         raise ValueError(f"{who}: bins must be None, an int or an array of edges, not a bool")
-    if _is_int(bins):
+    if is_int(bins):
         if not 1 <= bins <= _capi.BUBBLE_MAX_BINS:
             raise ValueError(f"{who}: bins as an int must be in [1, {_capi.BUBBLE_MAX_BINS}], not {bins}")
         return None if N is None else np.linspace(0.5, max(1, N // 2) + 0.5, int(bins) + 1)
@@ -205,35 +203,22 @@ def powerspec_spec(who, N, kind='dtb', kind_b=None, bins=None, box_len=None, sca
                    return_modes=False):
     """The keywords of :func:`power_spectrum` checked and completed for a mesh of N cells a side, as a dict (N = None: checked only).
     Raises ValueError -- before any device call -- for what the library would refuse."""
-    if not isinstance(kind, str) or kind not in _KINDS:
-        raise ValueError(f"{who}: kind must be one of {', '.join(repr(k) for k in _KINDS)}, not {kind!r}")
+    _check_kind(who, kind)
     if kind_b is not None and (not isinstance(kind_b, str) or kind_b not in _KINDS):
         raise ValueError(f"{who}: kind_b must be None or one of {', '.join(repr(k) for k in _KINDS)}, not {kind_b!r}")
     e = _edges(who, N, bins)
-    if box_len is not None and (not _is_real(box_len) or not (math.isfinite(box_len) and box_len > 0)):
+    if box_len is not None and (not is_real(box_len) or not (math.isfinite(box_len) and box_len > 0)):
         raise ValueError(f"{who}: box_len must be None or a finite number > 0, not {box_len!r}")
-    if not _is_real(scale) or not math.isfinite(scale):
-        raise ValueError(f"{who}: scale must be a finite number, not {scale!r}")
-    if not _is_real(t_gamma) or not (math.isfinite(t_gamma) and t_gamma >= 0):
-        raise ValueError(f"{who}: t_gamma must be a finite number >= 0, not {t_gamma!r}")
-    for name, v in (("return_field", return_field), ("return_modes", return_modes)):
-        if not isinstance(v, (bool, np.bool_)):
-            raise ValueError(f"{who}: {name} must be a bool, not {type(v).__name__}")
+    check_scale(who, scale)
+    check_t_gamma(who, t_gamma)
+    check_flag(who, "return_field", return_field)
+    check_flag(who, "return_modes", return_modes)
     if N is None:                          # (only the checks: the mesh size is the device's, asked for afterwards)
         return None
-    if not 1 <= N <= _capi.REGION_MAX_N:
-        raise ValueError(f"{who}: the mesh must have 1 ... {_capi.REGION_MAX_N} cells a side (a line of the transform must fit the "
-                         f"device's local memory), not {N}")
+    check_mesh(who, N, MESH_TRANSFORM)
     return dict(N=int(N), kind=kind, kind_b=kind_b, edges=e, thresholds=_edges_to_thresholds(e),
                 box_len=None if box_len is None else float(box_len), scale=float(scale), t_gamma=float(t_gamma),
                 return_field=bool(return_field), return_modes=bool(return_modes))
-
-
-def _host_field(who, name, field):
-    field = np.asarray(field)
-    if field.ndim != 3 or field.shape != (field.shape[0],) * 3 or field.dtype.kind not in "fiu":
-        raise ValueError(f"{who}: {name} must be a real (N, N, N) array")
-    return field
 
 
 def power_spectrum(field=None, field_b=None, *, kind='dtb', kind_b=None, bins=None, box_len=None, scale=1.0, t_gamma=0.0,
@@ -254,13 +239,13 @@ def power_spectrum(field=None, field_b=None, *, kind='dtb', kind_b=None, bins=No
     the formed field a / its transform as well."""
     who = "power_spectrum"
     if field is not None:
-        field = _host_field(who, "field", field)
+        field = host_field(who, "field", field)
         N = field.shape[0]
         if kind not in ("dtb", "xh", "xhi"):
             raise ValueError(f"{who}: a host field is analysed as kind 'xh' or 'xhi', not {kind!r} (the other kinds go with field=None)")
         kind = "xh" if kind == "dtb" else kind
         if field_b is not None:
-            field_b = _host_field(who, "field_b", field_b)
+            field_b = host_field(who, "field_b", field_b)
             if field_b.shape != field.shape:
                 raise ValueError(f"{who}: field_b must have the shape of field")
             if kind_b not in (None, "density"):

@@ -12,13 +12,13 @@ import math
 
 import numpy as np
 
-from . import _capi, _residency
 from .asora_core import cuda_is_init
 from .load_extensions import load_asora
+from ._fieldspec import (MESH_LABELS, PHASES, analyse, check_connectivity, check_dr, check_edges, check_flag, check_mesh, check_phase,
+                         check_threshold, is_int)
 
 __all__ = ['RegionSizes', 'region_sizes']
 
-_PHASES = {"ionised": 0, "neutral": 1}
 _TALLIES = ("n_phase", "n_regions", "sum_v2", "v_largest", "label_largest", "extent_i", "extent_j", "extent_k", "v_second",
             "label_second", "underflow", "underflow_cells", "overflow", "overflow_cells")
 
@@ -114,46 +114,28 @@ class RegionSizes:
         return f"<RegionSizes: {self.log_line()}>"
 
 
-def _is_int(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-
-
-def _is_real(v):
-    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
-
-
 def region_spec(who, N, threshold=0.5, phase="ionised", connectivity=6, periodic=True, bins=None, dr=None, labels=False):
     """The keywords of :func:`region_sizes` checked and completed for a mesh of N cells a side: a dict with ``edges`` in place of
     ``bins`` (N = None: checked only).  Raises ValueError -- before any device call -- for what the library would refuse."""
-    if not _is_real(threshold) or not math.isfinite(threshold):
-        raise ValueError(f"{who}: threshold must be a finite number, not {threshold!r}")
-    if phase not in _PHASES:
-        raise ValueError(f"{who}: phase must be 'ionised' or 'neutral', not {phase!r}")
-    if not _is_int(connectivity) or connectivity not in (6, 26):
-        raise ValueError(f"{who}: connectivity must be 6 (faces) or 26 (faces, edges and corners), not {connectivity!r}")
-    if not isinstance(periodic, (bool, np.bool_)):
-        raise ValueError(f"{who}: periodic must be a bool, not {type(periodic).__name__}")
-    if dr is not None and (not _is_real(dr) or not (math.isfinite(dr) and dr > 0)):
-        raise ValueError(f"{who}: dr must be None or a finite number > 0, not {dr!r}")
-    if not isinstance(labels, (bool, np.bool_)):
-        raise ValueError(f"{who}: labels must be a bool, not {type(labels).__name__}")
+    check_threshold(who, threshold)
+    check_phase(who, phase)
+    check_connectivity(who, connectivity)
+    check_flag(who, "periodic", periodic)
+    check_dr(who, dr)
+    check_flag(who, "labels", labels)
     edges = None
     if bins is not None:
-        if _is_int(bins) or isinstance(bins, (bool, np.bool_)):
+        if is_int(bins) or isinstance(bins, (bool, np.bool_)):
             raise ValueError(f"{who}: bins must be None (powers of two) or an array of edges: a number of bins has no natural upper "
                              f"edge, not {bins!r}")
         try:
             edges = np.array(bins, dtype=np.float64)
         except (TypeError, ValueError):
             raise ValueError(f"{who}: bins must be None or an array of edges, not {type(bins).__name__}") from None
-        if edges.ndim != 1 or not 2 <= edges.size <= _capi.BUBBLE_MAX_BINS + 1:
-            raise ValueError(f"{who}: the bin edges must be a 1-D array of 2 ... {_capi.BUBBLE_MAX_BINS + 1} values")
-        if not np.all(np.isfinite(edges)) or not edges[0] > 0.0 or not np.all(np.diff(edges) > 0.0):
-            raise ValueError(f"{who}: the bin edges must be finite, > 0 and ascending")
+        check_edges(who, edges)
     if N is None:                          # (only the checks: the mesh size is the device's, asked for afterwards)
         return None
-    if not 1 <= N <= _capi.REGION_MAX_N:
-        raise ValueError(f"{who}: the mesh must have 1 ... {_capi.REGION_MAX_N} cells a side (8 bytes per cell on the device: 2 GiB there), not {N}")
+    check_mesh(who, N, MESH_LABELS)
     if edges is None:                      # bin b: 2^b <= V < 2^(b + 1); N^3 < 2^nb, so every possible volume is in a bin
         edges = 2.0 ** np.arange((int(N) ** 3).bit_length() + 1)
     return dict(N=int(N), threshold=float(threshold), phase=phase, connectivity=int(connectivity), periodic=bool(periodic), edges=edges,
@@ -173,38 +155,13 @@ def region_sizes(field=None, *, threshold=0.5, phase='ionised', connectivity=6, 
     2^b <= V < 2^(b + 1), floor(log2(N^3)) + 1 bins, every possible volume in one -- or the edges themselves (cells, ascending, > 0; at
     most 256 bins).  ``dr``: the size of a cell, for the ``*_phys`` attributes of the result.  ``labels``: also download the label of
     every cell ((N, N, N) uint32, 4 N^3 bytes across PCIe: tests and visualisation)."""
-    who = "region_sizes"
-    if field is not None:
-        if grid is not None:
-            raise ValueError(f"{who}: grid selects a device grid and goes with field=None")
-        field = np.asarray(field)
-        if field.ndim != 3 or field.shape != (field.shape[0],) * 3 or field.dtype.kind not in "fiu":
-            raise ValueError(f"{who}: field must be a real (N, N, N) array")
-        N = field.shape[0]
-    else:
-        grid = _capi.GRID_XH if grid is None else grid
-        if not _is_int(grid) or not 0 <= grid <= _capi.GRID_CLUMP:
-            raise ValueError(f"{who}: grid must be one of the _capi.GRID_* selectors, not {grid!r}")
-        N = None
     kw = dict(threshold=threshold, phase=phase, connectivity=connectivity, periodic=periodic, bins=bins, dr=dr, labels=labels)
-    spec = region_spec(who, N, **kw)
-    if not cuda_is_init():
-        raise RuntimeError("GPU not initialized. Please initialize it by calling device_init(N)")
-    lib = load_asora()
-    if field is not None:
-        _residency.reclaim()              # this call overwrites a device grid a resident C2Ray object may be relying on
-        lib.grid_to_device(_capi.GRID_XH, np.asarray(field, dtype=np.float64))
-        grid = _capi.GRID_XH
-    else:
-        if getattr(lib, "_N", None) is None:
-            raise RuntimeError(f"{who}: field=None needs a device initialised through device_init (the mesh size)")
-        spec = region_spec(who, int(lib._N), **kw)
-    return regions_on_device(lib, grid, spec)
+    return analyse("region_sizes", field, grid, region_spec, kw, regions_on_device, cuda_is_init, load_asora)
 
 
 def regions_on_device(lib, grid, spec):
     """The library call for a checked `spec` (region_spec) on device grid `grid`, as a :class:`RegionSizes`."""
-    out = lib.region_sizes(grid, spec["threshold"], _PHASES[spec["phase"]], spec["periodic"], spec["connectivity"], spec["edges"],
+    out = lib.region_sizes(grid, spec["threshold"], PHASES[spec["phase"]], spec["periodic"], spec["connectivity"], spec["edges"],
                            **({"labels": True} if spec["labels"] else {}))
     return RegionSizes(spec["edges"], out[0], out[1], out[2], spec["N"], spec["threshold"], spec["phase"], spec["connectivity"],
                        spec["periodic"], spec["dr"], out[3] if spec["labels"] else None)

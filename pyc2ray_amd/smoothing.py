@@ -21,7 +21,8 @@ import numpy as np
 from . import _capi, _residency
 from .asora_core import cuda_is_init
 from .load_extensions import load_asora
-from .powerspec import _KINDS, _host_field, _is_int, _is_real
+from ._fieldspec import MESH_TRANSFORM, check_flag, check_mesh, check_scale, check_t_gamma, host_field, is_int, is_real
+from .powerspec import _KINDS, _check_kind
 
 __all__ = ['Filter', 'SmoothedField', 'smoothed_field', 'gaussian', 'boxcar', 'spherical_tophat', 'sharp_k', 'telescope']
 
@@ -78,13 +79,13 @@ class Filter:
 
 
 def _positive(who, name, v):
-    if not _is_real(v) or not (math.isfinite(v) and v >= 0):
+    if not is_real(v) or not (math.isfinite(v) and v >= 0):
         raise ValueError(f"{who}: {name} must be a finite number >= 0, not {v!r}")
     return float(v)
 
 
 def _axis(who, axis):
-    if not _is_int(axis) or axis not in (0, 1, 2):
+    if not is_int(axis) or axis not in (0, 1, 2):
         raise ValueError(f"{who}: an axis must be 0, 1 or 2, not {axis!r}")
     return int(axis)
 
@@ -93,7 +94,7 @@ def gaussian(fwhm, axes=(0, 1, 2)):
     """A Gaussian of full width at half maximum `fwhm` cells along each of `axes`: exp(-(2 pi m / N)^2 sigma^2 / 2) per axis, sigma
     = fwhm / (2 sqrt(2 ln 2))."""
     fwhm = _positive("gaussian", "fwhm", fwhm)
-    axes = (axes,) if _is_int(axes) else tuple(axes)
+    axes = (axes,) if is_int(axes) else tuple(axes)
     axes = tuple(_axis("gaussian", a) for a in axes)
     if len(set(axes)) != len(axes):
         raise ValueError(f"gaussian: axes must not repeat, {axes!r}")
@@ -263,7 +264,7 @@ def _edges(who, bins):
         return None
     if isinstance(bins, (bool, np.bool_)):
         raise ValueError(f"{who}: bins must be None, an int or an array of edges, not a bool")
-    if _is_int(bins):
+    if is_int(bins):
         if not 1 <= bins <= _capi.SMOOTH_MAX_BINS:
             raise ValueError(f"{who}: bins as an int must be in [1, {_capi.SMOOTH_MAX_BINS}], not {bins}")
         return int(bins)
@@ -298,26 +299,20 @@ def smoothing_spec(who, N, kind='dtb', filter=None, subtract_mean=False, bins=No
                    return_field=False):
     """The keywords of :func:`smoothed_field` checked and completed for a mesh of N cells a side, as a dict (N = None: checked
     only).  Raises ValueError -- before any device call -- for what the library would refuse."""
-    if not isinstance(kind, str) or kind not in _KINDS:
-        raise ValueError(f"{who}: kind must be one of {', '.join(repr(k) for k in _KINDS)}, not {kind!r}")
+    _check_kind(who, kind)
     if filter is not None and not isinstance(filter, Filter):
         raise ValueError(f"{who}: filter must be None or a Filter (gaussian, boxcar, spherical_tophat, sharp_k, telescope and their "
                          f"products), not {type(filter).__name__}")
-    for name, v in (("subtract_mean", subtract_mean), ("return_field", return_field)):
-        if not isinstance(v, (bool, np.bool_)):
-            raise ValueError(f"{who}: {name} must be a bool, not {type(v).__name__}")
+    check_flag(who, "subtract_mean", subtract_mean)
+    check_flag(who, "return_field", return_field)
     e = _edges(who, bins)
-    if not _is_real(scale) or not math.isfinite(scale):
-        raise ValueError(f"{who}: scale must be a finite number, not {scale!r}")
-    if not _is_real(t_gamma) or not (math.isfinite(t_gamma) and t_gamma >= 0):
-        raise ValueError(f"{who}: t_gamma must be a finite number >= 0, not {t_gamma!r}")
-    if into is not None and (not _is_int(into) or not 0 <= into < _capi.GRID_COUNT):
+    check_scale(who, scale)
+    check_t_gamma(who, t_gamma)
+    if into is not None and (not is_int(into) or not 0 <= into < _capi.GRID_COUNT):
         raise ValueError(f"{who}: into must be None or a grid selector 0 ... {_capi.GRID_COUNT - 1} (_capi.GRID_*), not {into!r}")
     if N is None:
         return None
-    if not 1 <= N <= _capi.REGION_MAX_N:
-        raise ValueError(f"{who}: the mesh must have 1 ... {_capi.REGION_MAX_N} cells a side (a line of the transform must fit the "
-                         f"device's local memory), not {N}")
+    check_mesh(who, N, MESH_TRANSFORM)
     tables = (None, None, None, None) if filter is None else filter.tables(N)
     for w in tables:
         if w is not None and not np.all(np.isfinite(w)):
@@ -344,7 +339,7 @@ def smoothed_field(field=None, *, kind='dtb', filter=None, subtract_mean=False, 
     ``granulometry`` take it by the selector; it may be a grid the kind reads.  ``return_field``: download the result as well."""
     who = "smoothed_field"
     if field is not None:
-        field = _host_field(who, "field", field)
+        field = host_field(who, "field", field)
         N = field.shape[0]
         if kind not in ("dtb", "xh", "xhi"):
             raise ValueError(f"{who}: a host field is analysed as kind 'xh' or 'xhi', not {kind!r} (the other kinds go with field=None)")

@@ -8,17 +8,14 @@ the lattice elements of the mask -- cells, faces, edges, vertices -- are counted
 complement are labelled by the union-find of the regions, so an ionised-fraction grid that lives on the device is analysed where it
 lies.  ``C2Ray.topology()`` does that for the current state of a run.  Everything is integers: the same call returns the same bits.
 """
-import math
-
 import numpy as np
 
-from . import _capi, _residency
 from .asora_core import cuda_is_init
 from .load_extensions import load_asora
+from ._fieldspec import MESH_LABELS, PHASES, analyse, check_connectivity, check_dr, check_flag, check_mesh, check_phase, check_threshold
 
 __all__ = ['Topology', 'topology']
 
-_PHASES = {"ionised": 0, "neutral": 1}
 _TALLIES = ("cells", "closed_faces", "closed_edges", "closed_vertices", "open_faces", "open_edges", "open_vertices", "components",
             "complement_components", "cavities")
 
@@ -127,31 +124,17 @@ class Topology:
         return f"<Topology: {self.log_line()}>"
 
 
-def _is_int(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
-
-
-def _is_real(v):
-    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
-
-
 def topology_spec(who, N, threshold=0.5, phase="ionised", connectivity=6, periodic=True, dr=None):
     """The keywords of :func:`topology` checked and completed for a mesh of N cells a side, as a dict (N = None: checked only).
     Raises ValueError -- before any device call -- for what the library would refuse."""
-    if not _is_real(threshold) or not math.isfinite(threshold):
-        raise ValueError(f"{who}: threshold must be a finite number, not {threshold!r}")
-    if phase not in _PHASES:
-        raise ValueError(f"{who}: phase must be 'ionised' or 'neutral', not {phase!r}")
-    if not _is_int(connectivity) or connectivity not in (6, 26):
-        raise ValueError(f"{who}: connectivity must be 6 (faces) or 26 (faces, edges and corners), not {connectivity!r}")
-    if not isinstance(periodic, (bool, np.bool_)):
-        raise ValueError(f"{who}: periodic must be a bool, not {type(periodic).__name__}")
-    if dr is not None and (not _is_real(dr) or not (math.isfinite(dr) and dr > 0)):
-        raise ValueError(f"{who}: dr must be None or a finite number > 0, not {dr!r}")
+    check_threshold(who, threshold)
+    check_phase(who, phase)
+    check_connectivity(who, connectivity)
+    check_flag(who, "periodic", periodic)
+    check_dr(who, dr)
     if N is None:                          # (only the checks: the mesh size is the device's, asked for afterwards)
         return None
-    if not 1 <= N <= _capi.REGION_MAX_N:
-        raise ValueError(f"{who}: the mesh must have 1 ... {_capi.REGION_MAX_N} cells a side (8 bytes per cell on the device: 2 GiB there), not {N}")
+    check_mesh(who, N, MESH_LABELS)
     return dict(N=int(N), threshold=float(threshold), phase=phase, connectivity=int(connectivity), periodic=bool(periodic),
                 dr=None if dr is None else float(dr))
 
@@ -167,36 +150,11 @@ def topology(field=None, *, threshold=0.5, phase='ionised', connectivity=6, peri
     components and for which Euler characteristic is ``euler``; the complement is joined by the other.  ``periodic``: the lattice
     wraps around the box (True) or ends at its faces, beyond which nothing is in phase (False).  ``dr``: the size of a cell, for the
     ``*_phys`` attributes of the result."""
-    who = "topology"
-    if field is not None:
-        if grid is not None:
-            raise ValueError(f"{who}: grid selects a device grid and goes with field=None")
-        field = np.asarray(field)
-        if field.ndim != 3 or field.shape != (field.shape[0],) * 3 or field.dtype.kind not in "fiu":
-            raise ValueError(f"{who}: field must be a real (N, N, N) array")
-        N = field.shape[0]
-    else:
-        grid = _capi.GRID_XH if grid is None else grid
-        if not _is_int(grid) or not 0 <= grid <= _capi.GRID_CLUMP:
-            raise ValueError(f"{who}: grid must be one of the _capi.GRID_* selectors, not {grid!r}")
-        N = None
     kw = dict(threshold=threshold, phase=phase, connectivity=connectivity, periodic=periodic, dr=dr)
-    spec = topology_spec(who, N, **kw)
-    if not cuda_is_init():
-        raise RuntimeError("GPU not initialized. Please initialize it by calling device_init(N)")
-    lib = load_asora()
-    if field is not None:
-        _residency.reclaim()              # this call overwrites a device grid a resident C2Ray object may be relying on
-        lib.grid_to_device(_capi.GRID_XH, np.asarray(field, dtype=np.float64))
-        grid = _capi.GRID_XH
-    else:
-        if getattr(lib, "_N", None) is None:
-            raise RuntimeError(f"{who}: field=None needs a device initialised through device_init (the mesh size)")
-        spec = topology_spec(who, int(lib._N), **kw)
-    return topology_on_device(lib, grid, spec)
+    return analyse("topology", field, grid, topology_spec, kw, topology_on_device, cuda_is_init, load_asora)
 
 
 def topology_on_device(lib, grid, spec):
     """The library call for a checked `spec` (topology_spec) on device grid `grid`, as a :class:`Topology`."""
-    tallies = lib.topology(grid, spec["threshold"], _PHASES[spec["phase"]], spec["periodic"], spec["connectivity"])
+    tallies = lib.topology(grid, spec["threshold"], PHASES[spec["phase"]], spec["periodic"], spec["connectivity"])
     return Topology(tallies, spec["N"], spec["threshold"], spec["phase"], spec["connectivity"], spec["periodic"], spec["dr"])

@@ -162,7 +162,7 @@ def test_yaml_keys_the_attribute_and_the_forms_the_class_takes(tmp_path, monkeyp
         sim = pc2r.C2Ray_Test(PLAIN_PARAMS, N, False)
         sim.gpu = True
         sim._read_paramfile("p.yml")
-        sim._bubble_init()
+        sim._statistic_init("bubble_stats")
         assert sim.bubble_stats is True and sim.last_bubble_sizes is None
         lib = _install(monkeypatch, BB.Bubbling(N))
         steps = []

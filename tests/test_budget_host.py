@@ -183,7 +183,7 @@ def test_yaml_key_and_the_attribute(tmp_path, monkeypatch):
         sim = pc2r.C2Ray_Test(PLAIN_PARAMS, 8, False)
         sim.gpu = True
         sim._read_paramfile("p.yml")
-        sim._photon_budget_init()
+        sim._statistic_init("photon_budget")
         assert sim.photon_budget is True
         # the class hands a fresh StepBudget to the entry, keeps it, adds it up and logs one line per step; off: no keyword at all
         seen = []

@@ -216,7 +216,7 @@ def test_yaml_keys_the_attribute_and_the_forms_the_class_takes(tmp_path, monkeyp
         sim = pc2r.C2Ray_Test(PLAIN_PARAMS, N, False)
         sim.gpu = True
         sim._read_paramfile(GRANULOMETRY_PARAMS)
-        sim._granulometry_init()
+        sim._statistic_init("granulometry_stats")
         assert sim.granulometry_stats is True and sim.last_granulometry is None
         lib = _install(monkeypatch, GB.Counting(N))
         steps = []

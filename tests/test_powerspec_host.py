@@ -238,7 +238,7 @@ def test_yaml_keys_the_attribute_and_the_forms_the_class_takes(tmp_path, monkeyp
         sim = pc2r.C2Ray_Test(PLAIN_PARAMS, N, False)
         sim.gpu = True
         sim._read_paramfile(POWER_PARAMS)
-        sim._power_spectrum_init()
+        sim._statistic_init("power_spectrum_stats")
         assert sim.power_spectrum_stats is True and sim.last_power_spectrum is None
         cs = sim._ld["Cosmology"]
         scale = 27.0 * math.sqrt((1 + sim.zred) / 10 * 0.15 / (cs["Omega0"] * cs["h"] ** 2)) * (cs["Omega_B"] * cs["h"] ** 2 / 0.023)

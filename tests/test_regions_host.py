@@ -201,7 +201,7 @@ def test_yaml_keys_the_attribute_and_the_forms_the_class_takes(tmp_path, monkeyp
         sim = pc2r.C2Ray_Test(PLAIN_PARAMS, N, False)
         sim.gpu = True
         sim._read_paramfile(REGION_PARAMS)
-        sim._region_init()
+        sim._statistic_init("region_stats")
         assert sim.region_stats is True and sim.last_regions is None
         lib = _install(monkeypatch, RB.Labelling(N))
         steps = []

@@ -237,7 +237,7 @@ def test_yaml_keys_the_attribute_and_the_forms_the_class_takes(tmp_path, monkeyp
         sim = pc2r.C2Ray_Test(PLAIN_PARAMS, N, False)
         sim.gpu = True
         sim._read_paramfile(OBSERVED_PARAMS)
-        sim._observed_init()
+        sim._statistic_init("observed_stats")
         assert sim.observed_stats is True and sim.last_observed is None
         lib = _install(monkeypatch, MB.Counting(N))
         steps = []

@@ -189,7 +189,7 @@ def test_yaml_keys_the_attribute_and_the_forms_the_class_takes(tmp_path, monkeyp
         sim = pc2r.C2Ray_Test(PLAIN_PARAMS, N, False)
         sim.gpu = True
         sim._read_paramfile(TOPOLOGY_PARAMS)
-        sim._topology_init()
+        sim._statistic_init("topology_stats")
         assert sim.topology_stats is True and sim.last_topology is None
         lib = _install(monkeypatch, TB.Counting(N))
         steps = []
