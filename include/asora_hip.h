@@ -668,6 +668,91 @@ int asora_smooth_field(int kind, double scale, double t_gamma,
 enum { ASORA_SMOOTH_STAGES = 8 };
 int asora_debug_smooth_field_ms(double *ms /* [ASORA_SMOOTH_STAGES] */);      /* stage times of the last call made under ASORA_OPT_TIMING */
 
+/* The field of asora_power_spectrum in redshift space -- every cell moved along one axis, the line of sight, by its peculiar
+ * velocity -- and the power of that field resolved in direction: binned in (n_perp, n_par) or in (|n|, mu^2), with Legendre-weighted
+ * sums for the multipoles P_0, P_2, P_4.  The mapping is the mesh-to-mesh scheme of Mao et al. 2012
+ * (MNRAS 422, 926): a number-conserving regridding of every cell between its displaced edges.  The specification, which no
+ * implementation detail enters:
+ *   field      : g is formed exactly as asora_power_spectrum forms it: the kinds ASORA_PS_*, the same order of operations, the same
+ *                mean density;
+ *   velocity   : v, N^3 doubles in a buffer of the library's own (asora_los_velocity_to_device; not a grid), the velocity along the
+ *                line of sight in the caller's units; velocity_scale converts it to cells; los_axis is 0, 1 or 2.  With
+ *                use_velocity = 0 the field stays g, no velocity is needed and velocity_scale is not looked at;
+ *   mapping    : each of the N^2 lines along los_axis is handled alone and is periodic.  On a line with the cells q = 0 ... N - 1
+ *                every operation below is one IEEE double operation, in the order written; no product is contracted into a fused
+ *                multiply-add:
+ *                  u[q] = v[q] velocity_scale;  d[q] = 0.5 (u[q - 1] + u[q]), the displacement of the left edge of cell q;
+ *                  relative to q, cell q occupies [a, b], a = d[q], b = 1.0 + d[q + 1];  lo = min(a, b), hi = max(a, b),
+ *                  width = hi - lo (an inverted cell, a shell crossing, is spread over its absolute extent);
+ *                  the weight of cell q on the output cell p = q + o, o an integer:
+ *                    width >= 2^-10 : ov = min(hi, o + 1.0) - max(lo, (double)o);  w = ov / width if ov > 0, else 0;
+ *                    width <  2^-10 : (a degenerate cell) w = 1 for o == floor(0.5 (lo + hi)), else 0;
+ *                  h[p] = the sum over o = -W ... W, ascending, of w(q, o) g[q], q = (p - o) mod N, started from +0.0, each
+ *                  product rounded before it is added.
+ *                W is any integer >= ceil(max |d|): terms of weight 0 do not change the bits.  The library takes W = floor(max|v|
+ *                |velocity_scale|) + 1 and refuses a call with 2 W + 1 > N, in which the window would wrap onto itself.  The sign
+ *                convention is s = x + u: a cell with u > 0 moves towards larger indices;
+ *   output     : h, a real field in the layout of the grids.  asora_redshift_space_field keeps it in a buffer of the library's own
+ *                (the one asora_smooth_field keeps its result in: either call overwrites the other's), or with dst_grid >= 0
+ *                writes it into that grid, which is allocated as asora_grid_to_device would allocate it and marked as holding
+ *                data; dst_grid may be a grid the kind reads.  moments [2] or NULL: (sum g, sum g^2) of the real-space field;
+ *                field_out [N^3] or NULL: h in C order;
+ *   transform  : hhat(n), the unnormalised transform of h as in asora_power_spectrum; modes, folding (m = min(n, N - n) per axis),
+ *                the weight w of a stored mode and the exclusion of n = 0 are as there.  With los_axis = a: m_par = m[a], n2_perp
+ *                the sum of the other two squares, n2 their total;
+ *   bins       : two indices, from thr_a[n_a + 1] (unsigned, non-decreasing) and thr_b[n_b + 1] (doubles, finite, non-decreasing),
+ *                n_a, n_b >= 1 and n_a n_b <= ASORA_ANISO_MAX_BINS; a mode outside either range is dropped; the arrays are
+ *                [n_a][n_b] in C order.
+ *                  ASORA_ANISO_CYLINDRICAL : thr_a[ia] <= n2_perp < thr_a[ia + 1] (thr_a[0] = 0 is allowed);
+ *                                            thr_b[ib] <= (double)(m_par m_par) < thr_b[ib + 1];
+ *                                            sum_1 = sum of w sqrt(n2_perp), sum_2 = sum of w m_par;
+ *                  ASORA_ANISO_MU          : thr_a[ia] <= n2 < thr_a[ia + 1], thr_a[0] >= 1;
+ *                                            thr_b[ib] n2 <= m_par^2 < thr_b[ib + 1] n2, each product formed in double with one
+ *                                            rounding: thr_b holds edges of mu^2, and a last edge above 1 includes mu = 1;
+ *                                            sum_1 = sum of w sqrt(n2), sum_2 = sum of w sqrt(m_par^2 / n2).
+ *                (For every finite thr_b the index ib of the rounded comparison is monotone along a row of n_z, as the exact one is:
+ *                DESIGN.md section 4.2j; no edge is refused for being close to 1.)  Multipoles are ASORA_ANISO_MU with n_b = 1 and
+ *                thr_b = {0, 2};
+ *   per bin    : count (uint64) = sum of w, exact; sum_aa = sum of w |hhat|^2; sum_l2 = sum of (w |hhat|^2) L2 and sum_l4 = sum of
+ *                (w |hhat|^2) L4 with t = (double)m_par^2 / (double)n2, L2 = 0.5 (3.0 t - 1.0), L4 = 0.125 ((35.0 t - 30.0) t + 3.0),
+ *                no product contracted;
+ *   moments    : moments_real[2] = (sum g, sum g^2), moments_rs[2] = (sum h, sum h^2) over the cells (the same numbers with
+ *                use_velocity = 0).
+ * field_out [N^3] or NULL: h; modes_out [N N (floor(N/2) + 1)] complex doubles or NULL: hhat; with use_velocity = 0 both have the
+ * bytes asora_power_spectrum returns for the same kind.
+ * Every floating-point sum has an order fixed by (N, los_axis, mode, thresholds), and no floating-point atomic enters any of them:
+ * the same call returns the same bits.  One synchronisation per call.  Device memory beside the power spectrum's complex buffer:
+ * N^3 doubles for the velocity, N^3 for h (shared with asora_smooth_field), the planes' partial bin sums (48 bytes x
+ * ASORA_ANISO_MAX_BINS x N); kept until the device is closed (the velocity: or until asora_los_velocity_clear).
+ * Fail with code 2 before device_init; 3 for: a bad kind, a non-finite scale, a non-finite or negative t_gamma, los_axis outside
+ * 0 ... 2, with use_velocity a non-finite velocity_scale, no velocity on the device or 2 W + 1 > N, a bad mode, n_a or n_b < 1 or
+ * n_a n_b > ASORA_ANISO_MAX_BINS, thresholds that are not non-decreasing, a non-finite thr_b, thr_a[0] = 0 in mode ASORA_ANISO_MU, a
+ * null pointer among the thresholds and the outputs up to moments_rs, dst_grid outside -1 ... ASORA_GRID_COUNT - 1; 4 for a grid the
+ * kind needs that holds no data and for a mesh with N > ASORA_REGION_MAX_N; 10 for a failed allocation.  A refused call writes
+ * nothing, on the host or on the device. */
+enum { ASORA_ANISO_CYLINDRICAL = 0, ASORA_ANISO_MU = 1, ASORA_ANISO_MODES = 2, ASORA_ANISO_MAX_BINS = 1024 };
+int asora_power_spectrum_los(int kind, double scale, double t_gamma, int los_axis, int use_velocity, double velocity_scale, int mode,
+                             int n_a, const unsigned *thr_a, int n_b, const double *thr_b,
+                             unsigned long long *count, double *sum_1, double *sum_2, double *sum_aa, double *sum_l2, double *sum_l4,
+                             double *moments_real /* [2] */, double *moments_rs /* [2] */,
+                             double *field_out /* NULL, or host [N^3] */, double *modes_out /* NULL, or host [2 N N (N/2 + 1)] */);
+int asora_redshift_space_field(int kind, double scale, double t_gamma, int los_axis, int use_velocity, double velocity_scale,
+                               int dst_grid /* -1, or a grid selector */, double *moments /* NULL, or [2] */,
+                               double *field_out /* NULL, or host [N^3] */);
+/* The line-of-sight velocity of the two calls above: N^3 doubles in the layout `order` ('C' or 'F', as asora_grid_to_device) into a
+ * buffer of the library's own, which replaces the one of an earlier call.  max |v| is reduced on the device (a maximum does not
+ * depend on the order of its operands), kept with the buffer and returned in *max_abs (may be NULL).  Code 2 before device_init; 3
+ * for a wrong N, a null pointer, a bad order, and for a NaN or an infinity among the entries, which the same pass over the buffer
+ * finds: the velocity of the last good call then stays in place; 10 for a failed allocation.  asora_los_velocity_clear frees the
+ * buffer (nothing to do without one); asora_device_close does too. */
+int asora_los_velocity_to_device(const double *v, int N, char order, double *max_abs);
+int asora_los_velocity_clear(void);
+/* The durations (ms) of the stages of the last asora_power_spectrum_los call that ran with ASORA_OPT_TIMING = 1: ms[0] the mean
+ * density, [1] the mapping (0 without use_velocity), [2] the pass along k, [3] along j, [4] along i, [5] the binning; zeros if no such
+ * call has run.  Code 3 for ms = NULL. */
+enum { ASORA_PSLOS_STAGES = 6 };
+int asora_debug_power_spectrum_los_ms(double *ms /* [ASORA_PSLOS_STAGES] */);
+
 /* ------------------------------------------------------------------------------------------ */
 /* C. Options, measurement and diagnostics                                                     */
 /* ------------------------------------------------------------------------------------------ */

@@ -56,6 +56,10 @@ PS_STAGES = 5
 SMOOTH_STATS = 10
 SMOOTH_MAX_BINS = 4096
 SMOOTH_STAGES = 8
+ANISO_CYLINDRICAL, ANISO_MU = range(2)
+ANISO_MODES = 2
+ANISO_MAX_BINS = 1024
+PSLOS_STAGES = 6
 (PRIM_LOG2, PRIM_LOOKUP, PRIM_DIV, PRIM_MUL, PRIM_ADD, PRIM_ABSORBER, PRIM_PHOTO, PRIM_HEAT, PRIM_GREY) = range(9)
 PRIM_COUNT = 9
 
@@ -155,6 +159,12 @@ SIGNATURES = {
     "asora_smooth_field": (C.c_int, [C.c_int, C.c_double, C.c_double, _dp, _dp, _dp, _dp, C.c_uint, C.c_int, C.c_int, _dp, C.c_int, _dp, _u64p,
                                      _dp]),
     "asora_debug_smooth_field_ms": (C.c_int, [_dp]),
+    "asora_power_spectrum_los": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
+                                           C.POINTER(C.c_uint32), C.c_int, _dp, _u64p, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "asora_redshift_space_field": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _dp]),
+    "asora_los_velocity_to_device": (C.c_int, [_dp, C.c_int, C.c_char, _dp]),
+    "asora_los_velocity_clear": (C.c_int, []),
+    "asora_debug_power_spectrum_los_ms": (C.c_int, [_dp]),
     "asora_set_option": (C.c_int, [C.c_int, C.c_int]),
     "asora_get_option": (C.c_int, [C.c_int]),
     "asora_kernel_time_ms": (C.c_int, [C.c_int, _dp, C.POINTER(C.c_long)]),

@@ -61,6 +61,13 @@ Differences from the reference:
     lie).  ``Output: observed_map: 0|1`` (optional key, default 0; with ``observed_baseline_km``, ``observed_los_axis``,
     ``observed_bins``) and the attribute ``observed_stats`` (a bool, assignable between steps) do that after every time step
     (use_gpu only): ``last_observed`` and one line in the log.
+  * ``los_velocity`` (an (N, N, N) array in km/s, or None: the proper peculiar velocity along ``los_axis``), ``velocity_scale()``,
+    ``power_spectrum_los()`` and ``redshift_space_field()``: the brightness temperature of the current state moved into redshift
+    space and its power in (k_perp, k_par), in (k, mu) or as the multipoles P_0, P_2, P_4 (pyc2ray_amd/redshift_space.py; on the
+    device-resident path from the grids where they lie; the velocity is uploaded once per assignment).  ``Output: redshift_space:
+    0|1`` (optional key, default 0; with ``redshift_space_binning``, ``redshift_space_bins``, ``redshift_space_los_axis``) and the
+    attribute ``redshift_space_stats`` (a bool, assignable between steps) do that after every time step (use_gpu only):
+    ``last_redshift_space`` and one line in the log.  Without a velocity the spectrum is the real-space one, and the line says so.
 """
 import atexit
 import math
@@ -84,6 +91,7 @@ from .topology import topology_spec, topology as field_topology, topology_on_dev
 from .granulometry import granulometry_spec, granulometry as field_granulometry, granulometry_on_device
 from .powerspec import powerspec_spec, powerspec_on_device
 from .smoothing import smoothing_spec, smoothing_on_device, telescope
+from .redshift_space import redshift_space_spec, spectrum_on_device, field_on_device
 from .budget import StepBudget
 from .lls import LLSOpacity, LLSSchedule, lls_spec
 from .planeflux import PlaneFlux, plane_flux_spec
@@ -325,9 +333,22 @@ class C2Ray:
         After a step ``last_observed`` holds the result and rank 0 writes one line to the log.""",
         keys=(("observed_baseline_km", "baseline_km"), ("observed_los_axis", "los_axis"), ("observed_bins", "bins")),
         validate=lambda sim, kw: sim._observed_keys_spec(kw))
+    # redshift_space_binning: 'cylindrical', 'mu' or 'multipoles', default 'multipoles'; redshift_space_bins: an int n for n equal
+    # bins of k (of k_perp and of k_par with 'cylindrical'), or a list of ascending edges in units of the fundamental mode, default
+    # unit-width bins; redshift_space_los_axis: 0, 1 or 2, default 2, which is also the object's ``los_axis`` until that is assigned
+    redshift_space_stats = _StepStatistic(
+        "redshift_space", "last_redshift_space", "power_spectrum_los", "the mapping, the transform and the binning run on the device",
+        """Does every time step end with the redshift-space power spectrum of its state (:meth:`power_spectrum_los` with the
+        ``Output: redshift_space_*`` keys and ``los_velocity``; use_gpu=True only: on an object without, True is refused at the
+        assignment)?  A driver may assign a bool between steps.  After a step ``last_redshift_space`` holds the result and rank 0
+        writes one line to the log.""",
+        keys=(("redshift_space_binning", "binning"), ("redshift_space_bins", "bins"), ("redshift_space_los_axis", "los_axis")),
+        validate=lambda sim, kw: sim._redshift_space_keys_spec(kw))
     #: the order in which __init__ reads their keys and a step writes their lines to the log
     _STEP_STATISTICS = ("photon_budget", "bubble_stats", "region_stats", "topology_stats", "granulometry_stats", "power_spectrum_stats",
                         "observed_stats")
+    #: the statistics declared since, behind those: read, computed and logged after them
+    _STEP_STATISTICS_APPENDED = ("redshift_space_stats",)
 
     def __init__(self, paramfile, Nmesh, use_gpu, use_mpi):
         """Basis class of a C2Ray simulation (pyc2ray/c2ray_base.py:82-145).
@@ -375,7 +396,7 @@ class C2Ray:
         self._lls_init()
         self._boundaries_init()
         self._plane_flux_init()
-        for name in self._STEP_STATISTICS:
+        for name in self._STEP_STATISTICS + self._STEP_STATISTICS_APPENDED:
             self._statistic_init(name)
         if self.rank == 0:
             if self.gpu:
@@ -559,7 +580,7 @@ class C2Ray:
             self.total_budget = self.__dict__.get("total_budget", StepBudget()) + budget
             if self.rank == 0:
                 self.printlog(budget.log_line())
-        for name in self._STEP_STATISTICS:
+        for name in self._STEP_STATISTICS + self._STEP_STATISTICS_APPENDED:
             stat = getattr(type(self), name)
             if stat.method is not None and getattr(self, name):
                 result = getattr(self, stat.method)()
@@ -728,6 +749,104 @@ class C2Ray:
         width = self.beam_fwhm_cells(baseline_km)
         return self.smoothed_field(filter=telescope(width, width, los_axis), subtract_mean=subtract_mean, **kw)
 
+    # ---- redshift space (pyc2ray_amd/redshift_space.py) -----------------------------------------------
+    @property
+    def los_axis(self):
+        """The axis of the line of sight, 0, 1 or 2: what ``los_velocity`` is the velocity along.  2, or ``Output:
+        redshift_space_los_axis``, until it is assigned."""
+        return self.__dict__.get("_los_axis", C2Ray.redshift_space_stats.defaults(self).get("los_axis", 2))
+
+    @los_axis.setter
+    def los_axis(self, value):
+        if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or value not in (0, 1, 2):
+            raise ValueError(f"C2Ray.los_axis: los_axis must be 0, 1 or 2, not {value!r}")
+        self.__dict__["_los_axis"] = int(value)
+
+    @property
+    def los_velocity(self):
+        """The proper peculiar velocity along ``los_axis`` in km/s, an (N, N, N) array, or None (default): what
+        :meth:`power_spectrum_los` and :meth:`redshift_space_field` move the signal by.  An assignment is checked at once (shape,
+        finite entries) and uploaded to the device once, at the next call that needs it, not per step; assign again after writing
+        into the array."""
+        return self.__dict__.get("_los_velocity")
+
+    @los_velocity.setter
+    def los_velocity(self, value):
+        if value is not None:
+            value = np.asarray(value)
+            if value.shape != (self.N,) * 3 or value.dtype.kind not in "fiu":
+                raise ValueError(f"C2Ray.los_velocity: the velocity must be None or a real ({self.N}, {self.N}, {self.N}) array")
+            if not np.all(np.isfinite(value)):
+                raise ValueError("C2Ray.los_velocity: the velocity has a non-finite entry")
+        self.__dict__["_los_velocity"] = value
+        self.__dict__["_los_velocity_max"] = None               # (None: not on the device)
+
+    def velocity_scale(self):
+        """What converts a proper peculiar velocity in km/s to a displacement in cells of the mesh at ``self.zred``: (1 + z) / (H(z)
+        x the comoving cell size in Mpc), H(z) = 100 h E(z) km/s/Mpc from the object's cosmology."""
+        z = float(self.zred)
+        hubble = 100.0 * float(self._ld['Cosmology']['h']) * float(self.cosmology.efunc(z))
+        return (1.0 + z) / (hubble * (self.dr_c / Mpc))
+
+    def _redshift_space_keys_spec(self, kw):
+        """What the declaration of ``redshift_space_stats`` checks of the ``Output: redshift_space_*`` keys at construction."""
+        redshift_space_spec("Output: redshift_space_binning / redshift_space_bins / redshift_space_los_axis", None,
+                            **self._redshift_space_bins({"binning": "multipoles", **kw}))
+
+    @staticmethod
+    def _redshift_space_bins(kw):
+        """``bins`` of the class is the bins of k: with binning 'cylindrical' those of k_perp and of k_par, unless they are given."""
+        if kw.get("binning", "multipoles") == "cylindrical" and "bins" in kw:
+            kw = dict(kw)
+            b = kw.pop("bins")
+            kw = {"bins_perp": b, "bins_par": b, **kw}
+        return kw
+
+    def _redshift_space_call(self, who, kw):
+        """The keywords `kw` of a redshift-space analysis of the object's state completed and checked, and the library with the
+        state and the velocity on the device: (lib, spec)."""
+        for name in ("field", "velocity", "max_velocity"):
+            if name in kw:
+                raise ValueError(f"{who}: {name} is not for the class (it analyses its own grids with its los_velocity)")
+        self._spin_t_gamma(who, kw)
+        kw = {"scale": self.brightness_temperature_scale(), "los_axis": self.los_axis, "velocity_scale": self.velocity_scale(), **kw}
+        v = self.los_velocity
+        vmax = None if v is None else (self.__dict__.get("_los_velocity_max") or float(np.max(np.abs(v))))
+        spec = redshift_space_spec(who, self.N, max_velocity=vmax, **kw)
+        lib = self._state_on_device(overwritten=spec["into"] is not None)
+        if v is not None and self.__dict__.get("_los_velocity_max") is None:
+            _residency.register(self)                           # (whoever takes the device next says so: _leave_device)
+            self.__dict__["_los_velocity_max"] = lib.los_velocity_to_device(np.asarray(v, dtype=np.float64))
+        return lib, spec
+
+    def power_spectrum_los(self, **kw):
+        """The power spectrum of the current state in redshift space, resolved in direction: a
+        :class:`pyc2ray_amd.redshift_space.AnisotropicSpectrum`; the keywords of
+        :func:`pyc2ray_amd.redshift_space.power_spectrum_los` but ``field`` and ``velocity``, and ``spin`` as in
+        :meth:`power_spectrum`.  ``kind`` is 'dtb' unless given, with ``scale`` = :meth:`brightness_temperature_scale` and ``box_len``
+        = the comoving side of the box in Mpc; ``binning`` is 'multipoles' unless given (or set by ``Output:
+        redshift_space_binning``), ``bins`` the bins of k (with 'cylindrical': of k_perp and of k_par), ``los_axis`` =
+        ``self.los_axis`` and ``velocity_scale`` = :meth:`velocity_scale`.  The signal is moved by ``los_velocity``; while that is
+        None, the spectrum is the real-space one, resolved in direction all the same.  The grids are analysed where they lie, as
+        in :meth:`power_spectrum`; the velocity crosses to the device once per assignment."""
+        who = "C2Ray.power_spectrum_los"
+        defaults = {key: v for key, v in C2Ray.redshift_space_stats.defaults(self).items() if key != "los_axis"}     # (los_axis: the property)
+        kw = {"box_len": self.boxsize_c / Mpc, **self._redshift_space_bins({"binning": "multipoles", **defaults, **kw})}
+        if "into" in kw:
+            raise ValueError(f"{who}: into is for redshift_space_field")
+        lib, spec = self._redshift_space_call(who, kw)
+        return spectrum_on_device(lib, spec)
+
+    def redshift_space_field(self, **kw):
+        """The current state moved into redshift space by ``los_velocity``: the (N, N, N) cube, or with ``into`` (a grid selector)
+        None, the cube being left in that device grid for ``pyc2ray_amd.mfp_distribution(grid=...)`` and the other analyses of a
+        grid; the keywords of :func:`pyc2ray_amd.redshift_space.redshift_space_field` but ``field`` and ``velocity``, and ``spin``.
+        ``into`` writes a device grid behind the object's back: the object's own device copies come down first, and every grid
+        and the velocity go up again afterwards."""
+        who = "C2Ray.redshift_space_field"
+        lib, spec = self._redshift_space_call(who, dict(kw))
+        return field_on_device(lib, spec)
+
     def evolve3D(self, dt, src_flux, src_pos, src_spectrum=None):
         """Evolve the grid over one time step (c2ray_base.py:170-226).  src_spectrum: with ``BlackBodySource: Teff`` a list, the
         index into it of each source's temperature (None: every source the first one); see pyc2ray_amd.evolve3D."""
@@ -784,6 +903,7 @@ class C2Ray:
         self._device_newer.clear()
         self._host_newer |= {"ndens", "temp", "xh", "clumping"}
         self.__dict__.pop("_grid_fingerprints", None)
+        self.__dict__["_los_velocity_max"] = None               # (the velocity goes up again too)
 
     def _evolve3D_resident(self, dt, src_flux, src_pos, src_spectrum=None):
         """The same step with the grids left on the device (see `device_resident`)."""

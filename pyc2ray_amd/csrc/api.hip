@@ -111,6 +111,8 @@ static int release_all()
     if (st.ps_host) { (void)hipHostFree(st.ps_host); st.ps_host = nullptr; }
     drop(st.sm_field); drop(st.sm_tables); drop(st.sm_partial); drop(st.sm_result);
     if (st.sm_host) { (void)hipHostFree(st.sm_host); st.sm_host = nullptr; }
+    drop(st.rs_velocity); drop(st.rs_partial); drop(st.rs_thresholds); drop(st.rs_vmax_dev); st.rs_vmax = 0.0;
+    if (st.rs_host) { (void)hipHostFree(st.rs_host); st.rs_host = nullptr; }
     for (int g = 0; g < ASORA_GRID_COUNT; ++g) { st.grid[g] = nullptr; st.grid_valid[g] = false; }
     st.nhi = st.staging = st.acc = nullptr;
     drop(st.arena); st.arena_bytes = 0;

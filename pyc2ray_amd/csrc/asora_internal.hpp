@@ -317,6 +317,15 @@ struct State {
     // partial sums are the power spectrum's.  sm_ms: the stage times of the last call under ASORA_OPT_TIMING
     double *sm_field = nullptr, *sm_tables = nullptr, *sm_partial = nullptr, *sm_result = nullptr, *sm_host = nullptr;
     double sm_ms[ASORA_SMOOTH_STAGES] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // the redshift-space unit's own buffers (redshift_space.hip): the line-of-sight velocity [N^3] of asora_los_velocity_to_device
+    // with max |v| kept on the host; the planes' partial bin sums with the moments' partials and the result words behind them; the
+    // two threshold tables; the pinned area the thresholds leave through and the results arrive in.  The mapped field lies in
+    // sm_field (the smoothing's output buffer), the complex buffer, the roots and the mean density's partials are the power
+    // spectrum's.  rs_ms: the stage times of the last asora_power_spectrum_los call under ASORA_OPT_TIMING
+    double *rs_velocity = nullptr, *rs_partial = nullptr, *rs_thresholds = nullptr, *rs_host = nullptr;
+    unsigned long long *rs_vmax_dev = nullptr;
+    double rs_vmax = 0.0;
+    double rs_ms[ASORA_PSLOS_STAGES] = {0, 0, 0, 0, 0, 0};
 
     unsigned long long *counters = nullptr; // [COUNTER_FIELDS * COUNTER_SLOTS] device: gamma cells, evaluated cells, exact zeros left out, spread over the slots
     long long last_gamma_cells = 0, last_eval_cells = 0;
@@ -658,5 +667,9 @@ int launch_region_label(State &st, const unsigned long long *mask, int periodic,
 // the forward transform of one field into State::ps_modes[0] (the mean density, the pass along k with the moments, along j, along i)
 bool ps_needs_grid(int kind, int grid, double t_gamma);
 int ps_forward(State &st, int kind, double scale, double t_gamma, const std::function<int()> &stage_done, const double **moments_dev);
+// the same stage by stage, for redshift_space.hip: the mean density alone, and the three passes with `x` read as the ionised fraction
+int ps_mean_density(State &st, const double **nbar_dev);
+int ps_transform(State &st, int kind, const double *x, bool nbar, double scale, double t_gamma, double *field,
+                 const std::function<int()> &stage_done, const double **moments_dev);
 
 } // namespace asora

@@ -328,10 +328,11 @@ struct PsPasses {
         ASORA_HIP_TRY(hipGetLastError());
         return 0;
     }
-    int rows(int f, int kind, bool nbar, double scale, double t_gamma, double *field)     // along k, with the field and its moments
+    // along k, with the field and its moments; x: what the kinds read as the ionised fraction (the grid, or a caller's own buffer)
+    int rows(int f, int kind, bool nbar, double scale, double t_gamma, double *field, const double *x)
     {
         hipLaunchKernelGGL(ps_row_kernel, dim3((unsigned)lay.row_blocks), block, fft_lds, st.stream, kind,
-                           (const double *)st.grid[ASORA_GRID_XH], (const double *)st.grid[ASORA_GRID_NDENS],
+                           x, (const double *)st.grid[ASORA_GRID_NDENS],
                            (const double *)st.grid[ASORA_GRID_TEMP], nbar ? (const double *)(result() + PS_RES_NBAR) : (const double *)nullptr,
                            scale, t_gamma, N, pitch, T, plan, (const double2 *)st.ps_twiddle, st.ps_modes[f], partial() + lay.moments[f],
                            field);
@@ -365,13 +366,33 @@ struct PsPasses {
 // device once the stream has got there
 int ps_forward(State &st, int kind, double scale, double t_gamma, const std::function<int()> &stage_done, const double **moments_dev)
 {
+    const bool nbar = ps_kind_uses(kind, ASORA_GRID_NDENS, t_gamma);
+    const double *nbar_dev = nullptr;
+    if (nbar)
+        if (int rc = ps_mean_density(st, &nbar_dev)) return rc;
+    if (int rc = stage_done()) return rc;
+    return ps_transform(st, kind, st.grid[ASORA_GRID_XH], nbar, scale, t_gamma, nullptr, stage_done, moments_dev);
+}
+
+// The same stages one by one, for the redshift-space unit (redshift_space.hip), which puts a stage of its own between the mean
+// density and the pass along k.  ps_mean_density: stage a; *nbar_dev: where the mean lies on the device.  ps_transform: stages b and
+// c for the field of `kind`, read with `x` in the place of the ionised-fraction grid (a mapped field goes through ASORA_PS_XH), with
+// nbar as ps_mean_density left it if `nbar`; field: NULL, or where the formed field is stored; stage_done behind each of the three
+int ps_mean_density(State &st, const double **nbar_dev)
+{
     PsPasses pass(st);
     if (int rc = pass.prepare(false)) return rc;
-    const bool nbar = ps_kind_uses(kind, ASORA_GRID_NDENS, t_gamma);
-    if (nbar)
-        if (int rc = pass.mean_density()) return rc;
-    if (int rc = stage_done()) return rc;
-    if (int rc = pass.rows(0, kind, nbar, scale, t_gamma, nullptr)) return rc;
+    if (int rc = pass.mean_density()) return rc;
+    *nbar_dev = pass.result() + PS_RES_NBAR;
+    return 0;
+}
+
+int ps_transform(State &st, int kind, const double *x, bool nbar, double scale, double t_gamma, double *field,
+                 const std::function<int()> &stage_done, const double **moments_dev)
+{
+    PsPasses pass(st);
+    if (int rc = pass.prepare(false)) return rc;
+    if (int rc = pass.rows(0, kind, nbar, scale, t_gamma, field, x)) return rc;
     if (int rc = stage_done()) return rc;
     if (int rc = pass.lines_j(0)) return rc;
     if (int rc = stage_done()) return rc;
@@ -439,7 +460,7 @@ int asora_power_spectrum(int kind_a, int kind_b, double scale, double t_gamma, i
         if (int rc = pass.mean_density()) return rc;
     if (int rc = watch.mark()) return rc;
     for (int f = 0; f < nf; ++f)
-        if (int rc = pass.rows(f, kinds[f], need[1], scale, t_gamma, f == 0 ? field.dev : (double *)nullptr)) return rc;
+        if (int rc = pass.rows(f, kinds[f], need[1], scale, t_gamma, f == 0 ? field.dev : (double *)nullptr, st.grid[ASORA_GRID_XH])) return rc;
     if (int rc = watch.mark()) return rc;
     for (int f = 0; f < nf; ++f)
         if (int rc = pass.lines_j(f)) return rc;

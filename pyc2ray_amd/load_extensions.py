@@ -605,6 +605,80 @@ class _LibAsora:
         _capi.check(self._lib.asora_debug_smooth_field_ms(_capi.dptr(ms)), "debug_smooth_field_ms")
         return ms
 
+    def los_velocity_to_device(self, v):
+        """The line-of-sight velocity of power_spectrum_los and redshift_space_field, (N, N, N) float64, into the library's own
+        buffer (include/asora_hip.h, asora_los_velocity_to_device); returns max |v|, reduced on the device.  A non-finite entry is
+        refused."""
+        v = np.asarray(v, dtype=np.float64)
+        if self._N is None or v.shape != (self._N,) * 3:
+            raise ValueError(f"los_velocity_to_device: the velocity must have the shape ({self._N},) * 3 of the mesh of device_init, "
+                             f"not {v.shape}")
+        order = b"F" if (v.flags.f_contiguous and not v.flags.c_contiguous) else b"C"
+        if order == b"C":
+            v = np.ascontiguousarray(v)
+        vmax = C.c_double(0.0)
+        _capi.check(self._lib.asora_los_velocity_to_device(_capi.dptr(v), int(self._N), order, C.byref(vmax)), "los_velocity_to_device")
+        return vmax.value
+
+    def los_velocity_clear(self):
+        _capi.check(self._lib.asora_los_velocity_clear(), "los_velocity_clear")
+
+    def power_spectrum_los(self, kind, scale, t_gamma, los_axis, velocity_scale, mode, thr_a, thr_b, field=False, modes=False):
+        """The anisotropic power sums of the field of kind `kind` (``_capi.PS_*``) formed from the device grids and, with
+        `velocity_scale` not None, moved into redshift space along `los_axis` by the velocity of los_velocity_to_device
+        (include/asora_hip.h, asora_power_spectrum_los), in the bins of `mode` (``_capi.ANISO_*``), `thr_a` (integers) and `thr_b`
+        (doubles): a dict of ``count`` (uint64), ``sum_1``, ``sum_2``, ``sum_aa``, ``sum_l2``, ``sum_l4``, each (n_a, n_b),
+        ``moments_real`` and ``moments_rs`` = (sum, sum of squares) of the field before and after the mapping; with `field` the
+        mapped field, (N, N, N), under ``field``, with `modes` its transform, (N, N, N // 2 + 1) complex128, under ``modes``."""
+        ta = np.ascontiguousarray(thr_a, dtype=np.uint32)
+        tb = np.ascontiguousarray(thr_b, dtype=np.float64)
+        if ta.ndim != 1 or tb.ndim != 1 or ta.size < 2 or tb.size < 2:
+            raise ValueError("power_spectrum_los: thr_a and thr_b must be one-dimensional, two or more values each")
+        shape = (ta.size - 1, tb.size - 1)
+        out = dict(count=np.zeros(shape, dtype=np.uint64), moments_real=np.zeros(2), moments_rs=np.zeros(2), field=None, modes=None)
+        for name in ("sum_1", "sum_2", "sum_aa", "sum_l2", "sum_l4"):
+            out[name] = np.zeros(shape)
+        if field or modes:
+            if self._N is None:
+                raise RuntimeError("power_spectrum_los with field or modes needs a device initialised through device_init (the mesh size)")
+            if field:
+                out["field"] = np.zeros((self._N,) * 3)
+            if modes:
+                out["modes"] = np.zeros((self._N, self._N, self._N // 2 + 1), dtype=np.complex128)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(_capi._dp)
+        use = velocity_scale is not None
+        _capi.check(self._lib.asora_power_spectrum_los(int(kind), float(scale), float(t_gamma), int(los_axis), 1 if use else 0,
+                                                       float(velocity_scale) if use else 0.0, int(mode), shape[0],
+                                                       ta.ctypes.data_as(C.POINTER(C.c_uint32)), shape[1], ptr(tb),
+                                                       out["count"].ctypes.data_as(_capi._u64p), ptr(out["sum_1"]), ptr(out["sum_2"]),
+                                                       ptr(out["sum_aa"]), ptr(out["sum_l2"]), ptr(out["sum_l4"]), ptr(out["moments_real"]),
+                                                       ptr(out["moments_rs"]), ptr(out["field"]), ptr(out["modes"])), "power_spectrum_los")
+        return out
+
+    def power_spectrum_los_ms(self):
+        """The stage times (ms) of the last power_spectrum_los call that ran with OPT_TIMING: mean density, the mapping, the passes
+        along k, j and i, the binning (include/asora_hip.h, asora_debug_power_spectrum_los_ms)."""
+        ms = np.zeros(_capi.PSLOS_STAGES)
+        _capi.check(self._lib.asora_debug_power_spectrum_los_ms(_capi.dptr(ms)), "debug_power_spectrum_los_ms")
+        return ms
+
+    def redshift_space_field(self, kind, scale, t_gamma, los_axis, velocity_scale, dst_grid=None, field=False):
+        """The field of kind `kind` moved into redshift space along `los_axis` (`velocity_scale` None: left where it is), kept on
+        the device or written into the grid `dst_grid` (include/asora_hip.h, asora_redshift_space_field): a dict of ``moments`` =
+        (sum g, sum g^2) of the real-space field and ``field`` (with `field`: (N, N, N) float64; else None)."""
+        out = dict(moments=np.zeros(2), field=None)
+        if field:
+            if self._N is None:
+                raise RuntimeError("redshift_space_field with field needs a device initialised through device_init (the mesh size)")
+            out["field"] = np.zeros((self._N,) * 3)
+        use = velocity_scale is not None
+        _capi.check(self._lib.asora_redshift_space_field(int(kind), float(scale), float(t_gamma), int(los_axis), 1 if use else 0,
+                                                         float(velocity_scale) if use else 0.0, -1 if dst_grid is None else int(dst_grid),
+                                                         _capi.dptr(out["moments"]),
+                                                         None if out["field"] is None else _capi.dptr(out["field"])),
+                    "redshift_space_field")
+        return out
+
     def thermal_stats(self):
         """(cells that hit max_substeps, cells clamped to t_floor, most substeps of one integration) since the last
         chemistry_device / evolve_begin."""
