@@ -931,6 +931,21 @@ enum { ASORA_PLAN_HEAT = 1, ASORA_PLAN_DUMP = 2, ASORA_PLAN_TABLE_SETS = 4, ASOR
 int asora_debug_launch_plan(int N, double R, int src_count, int shape_src_count, int cu_count, int flags, int shells, int max_cells,
                             int32_t *out);
 
+/* Which built kernel forms have run (tests; no reference counterpart).  The raytrace kernel is built in the forms of one table
+ * (RT_FORMS, pyc2ray_amd/csrc/raytrace_plan.hpp); a row is the kernel's 13 template arguments in their order: THREADS,
+ * GLOBAL_SCRATCH, DUMP, HEAT, TABCAP, SKIP_ZERO, GREY, BUFATOM, NSRC, SUBBOX, SPLIT, SPEC, OPEN.
+ *   asora_debug_built_forms: the table, 13 ints per row for up to capacity_rows rows; *rows = the rows of the table.  Host only, no
+ *     device needed.
+ *   asora_debug_form_launches: per row, how many launches of it this process has made (counted once the launch has been accepted by
+ *     the runtime); the counters are the process's, not the device state's: they outlive asora_device_close.  Up to `capacity`
+ *     counters are written; *rows = the rows of the table.  asora_debug_form_launches_reset sets them to 0.
+ *   asora_debug_last_launch_form: the form and the row of the last raytrace launch, whole-box or sub-box sweep on tables, noted
+ *     where asora_last_raytrace_variant's word is; *row = -1 (form all 0) before the first launch. */
+int asora_debug_built_forms(int32_t *out, int capacity_rows, int *rows);
+int asora_debug_form_launches(unsigned long long *counts, int capacity, int *rows);
+int asora_debug_form_launches_reset(void);
+int asora_debug_last_launch_form(int32_t form[13], int *row);
+
 /* What the last sub-box call (c2ray_do_all_sources, asora_subbox_raytrace_device) launched, written where its launches are made
  * (tests; no reference counterpart).  out[ASORA_SBL_*], ASORA_SUBBOX_LAUNCH_WORDS ints; all 0 before the first call.  Sources are
  * summed over the batches of the call; units ... heat describe the last launch of their kind (one call launches one form of each

@@ -178,6 +178,10 @@ SIGNATURES = {
     "asora_last_raytrace_variant": (C.c_int, []),
     "asora_debug_launch_plan": (C.c_int, [C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip]),
     "asora_debug_last_subbox_launch": (C.c_int, [_ip]),
+    "asora_debug_built_forms": (C.c_int, [_ip, C.c_int, C.POINTER(C.c_int)]),
+    "asora_debug_form_launches": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int, C.POINTER(C.c_int)]),
+    "asora_debug_form_launches_reset": (C.c_int, []),
+    "asora_debug_last_launch_form": (C.c_int, [_ip, C.POINTER(C.c_int)]),
     "asora_debug_subbox_plan": (C.c_int, [C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip]),
     "asora_debug_block_order": (C.c_int, [_ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.c_size_t, C.POINTER(C.c_int)]),
     "asora_debug_geometry_bytes": (C.c_size_t, []),

@@ -488,6 +488,10 @@ int check_plane_flux(const State &st, const PlaneFluxSet &pf, const char *who, b
 int launch_plane_flux(State &st, const RtParams &p, double *phi, double *heat_acc, bool heat, const int *done);
 int launch_raytrace(State &st, RtParams &p, bool dump, bool heat, hipStream_t side = nullptr);   // side: stream to launch on when no shared scratch is needed
 void plan_options(const State &st, RtPlanInput &in);    // cu_count and the options a launch plan reads (raytrace_plan.hpp)
+// which rows of RT_FORMS have been launched, process-wide (raytrace.hip; asora_debug_form_launches, asora_debug_last_launch_form)
+const unsigned long long *form_launch_counts();         // RT_FORM_COUNT counters
+void reset_form_launch_counts();
+int last_launched_row();                                // -1 before the first launch
 // The sub-box sweep on tabulated geometry (raytrace.hip): prepare -> tables for (N, R, range, box size), then one launch per
 // sub-box.  `shells` = (s_begin, s_end] of the box; returns without launching when the tables hold nothing there.
 struct SubboxTables { int units = 0, threads = 0, S = 0, max_batch = 0, nsrc = 1; bool ok = false, aligned = false; const int32_t *host_pos = nullptr; };   // max_batch: sources per launch the trailing-shell scratch holds; nsrc: sources per workgroup (2: paired sweep); host_pos: the source positions on the host (0-based, xyz-interleaved; pairing for the aligned tables) or nullptr

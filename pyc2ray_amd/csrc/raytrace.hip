@@ -133,16 +133,17 @@ extern "C" __device__ double asora_buffer_atomic_fadd_f64(double, __amdgpu_buffe
 // source's photon loss; every source is rated with the flux of `flux_src` (f90:500,503).  Fortran-flavoured constants.
 //
 // Which combinations exist: the rows of RT_FORMS (raytrace_plan.hpp, make_form_table), which is the source -- launch_form_row below
-// instantiates exactly its rows, 182 of the 13 template parameters, and the static_asserts below check every one.  In summary
+// instantiates exactly its rows, 152 of the 13 template parameters, and the static_asserts below check every one.  In summary
 // (SPLIT, SPEC and OPEN are f, t, f unless the family says otherwise; DESIGN.md 4.1 has the launch shapes that select them):
 //   family                         THREADS x TABCAP                               GS   DUMP HEAT SKIP_ZERO GREY BUFATOM NSRC SUBBOX   forms
 //   paired production              {64,128,256,512}x256 {64,128,256}x64 256x32     f    f    f    f/t       f    t       2    f        16
-//   single source, buffer atomics  {64..1024}x256 {64,128}x64 {256,512,1024}x1024  f    f    f/t  f/t       f/t  t       1    f        40
-//   single source, global atomics  same (N > 512, option, shells in global memory) f/t  f    f/t  f (t: GS=f) f/t f       1    f        70
-//   column-density dump            256 x {256,1024}                                f/t  t    f    f         f/t  f       1    f        8
+//   single source, buffer atomics  {64..1024}x256 {64,128}x64                      f    f    f/t  f/t       f/t  t       1    f        28
+//   single source, global atomics  same, and {256,512,1024}x1024 with GS=t (N > 512, option, shells in global memory) f/t  f    f/t  f (t: GS=f) f/t f       1    f        58
+//   column-density dump            256 x {256, 1024 with GS=t}                     f/t  t    f    f         f/t  f       1    f        6
 //   sub-box sweep                  {256,512} x 256                                 f    f    f/t  f         f    t       1|2  t        6
 //   descriptors per layout (SPLIT) paired {256x32, 256x64, 256x256, 512x256}, SPEC f/t; single {256,512}x256   f    f    f/t  f/t       f/t  t       1|2  f        16 + 8
-//   open boundaries (OPEN)         paired {256,512}x256; single {256,512}x{256,1024} f/t(1) f    f/t(1) f       f    t       1|2  f        18
+//   open boundaries (OPEN)         paired {256,512}x256; single {256,512}x{256, 1024 with GS=t} f/t(1) f    f/t(1) f       f    t       1|2  f        14
+//   (the 1024-entry tables -- more than 256 shells -- only with the shells in global memory: raytrace_plan.hpp, at RT_FORM_COUNT)
 //   (SKIP_ZERO with HEAT or GREY, NSRC = 2 with HEAT, DUMP, GREY or global atomics, SUBBOX with NSRC = 2 and HEAT: not built)
 // OPEN (ASORA_OPT_OPEN_BOUNDARIES): a cell whose unwrapped position i0 +- a, j0 +- b, k0 +- c lies outside [0, N)
 // on any axis is swept like every other -- its upstream neighbours and whatever reads it lie outside as well, since every
@@ -151,7 +152,7 @@ extern "C" __device__ double asora_buffer_atomic_fadd_f64(double, __amdgpu_buffe
 // tables carry the verdict per axis and offset in their top bit, nhi_address hands the OR of the three on in the top bit of the
 // cell index, and the lane's pending atomic gets the out-of-range offset of a lane without a rate.  A compile-time variant: with
 // OPEN = false every instantiation is what it was (register counts line for line); the last row of the table is all that is
-// built with it -- 18 forms -- and plan_shape maps every launch shape onto them (64 ... 256 threads -> 256, 512 and 1024
+// built with it -- 14 forms -- and plan_shape maps every launch shape onto them (64 ... 256 threads -> 256, 512 and 1024
 // -> 512; 256-entry LDS tables unless there are more than 256 shells; no exact-zero skipping); N > 512, grey opacity, global
 // atomics, the column-density dump and the sub-box sweep are refused (check_open_boundaries).  138 VGPRs paired (three waves
 // per SIMD against four), 100 single (four against five), 108 with heating.
@@ -786,6 +787,20 @@ __global__ void __launch_bounds__(RT_THREADS, 1) raytrace_octant_kernel(const Rt
 // ---------------------------------------------------------------------------------------------
 static_assert(LDS_LOG_TABLE_BYTES == LOG_TABLE_SIZE * sizeof(double2), "raytrace_plan.hpp counts the log table as the kernel lays it out");
 
+// Which rows have been launched (asora_debug_form_launches, asora_debug_last_launch_form; tests): process-wide, not in State, so
+// that they outlive device_close.  A row counts once its launch's hipGetLastError is clean.
+static unsigned long long form_launches[RT_FORM_COUNT];
+static int last_launch_row = -1;
+const unsigned long long *form_launch_counts() { return form_launches; }
+void reset_form_launch_counts() { std::fill(form_launches, form_launches + RT_FORM_COUNT, 0ULL); }
+int last_launched_row() { return last_launch_row; }
+// the row of a form about to be launched, noted where st.last_variant is (-1: not built -- launch_form refuses it)
+static void note_launch_form(const RtForm &f)
+{
+    const RtForm *at = std::find(RT_FORMS.row, RT_FORMS.row + RT_FORM_COUNT, f);
+    last_launch_row = at != RT_FORMS.row + RT_FORM_COUNT ? (int)(at - RT_FORMS.row) : -1;
+}
+
 // Row I of RT_FORMS: the one place where the kernel's template arguments are written, so the rows of the table are the
 // instantiations of the build
 template <size_t I>
@@ -796,6 +811,7 @@ static int launch_form_row(const RtParams &q, unsigned grid, size_t lds_bytes, h
     ASORA_HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(f.threads), lds_bytes, stream, q);
     ASORA_HIP_TRY(hipGetLastError());
+    form_launches[I] += 1;
     return 0;
 }
 // The row equal to the planned form; a form that is not built is an error, never a neighbouring kernel
@@ -1054,6 +1070,7 @@ int launch_raytrace(State &st, RtParams &p, bool dump, bool heat, hipStream_t si
         unsigned grid = 0;
         if (int rc = set_launch_grid(st, q, sh.units, form.nsrc == 2, sh.aligned, host_pos, !dump, grid)) return rc;
         st.last_variant = variant_word(form, sh.units, sh.aligned);
+        note_launch_form(form);
         {
             KernelTimer kt(ASORA_KERNEL_RAYTRACE, stream);
             if (int rc = launch_form(form, q, grid, plan.lds_bytes, stream, ALL_FORMS)) return rc;
@@ -1128,6 +1145,7 @@ int subbox_tables_sweep(State &st, const RtParams &p, const SubboxTables &tab, i
     unsigned grid = 0;
     if (int rc = set_launch_grid(st, q, tab.units, pairs, tab.aligned, tab.host_pos, false, grid)) return rc;
     st.last_variant = variant_word(form, tab.units, tab.aligned);
+    note_launch_form(form);
     {   // asora_debug_last_subbox_launch: the form and grid shape of this very launch
         int *r = st.sb_launch;
         if (q.sb_first) r[ASORA_SBL_TABLE_SOURCES] += p.src_count;

@@ -480,6 +480,49 @@ int asora_debug_launch_plan(int N, double R, int src_count, int shape_src_count,
     return 0;
 }
 
+int asora_debug_built_forms(int32_t *out, int capacity_rows, int *rows)
+{
+    clear_error();
+    if (!rows || capacity_rows < 0 || (capacity_rows > 0 && !out)) return fail(3, "debug_built_forms: bad arguments");
+    *rows = RT_FORM_COUNT;
+    for (int r = 0; r < std::min(capacity_rows, RT_FORM_COUNT); ++r) {
+        int v[13];
+        form_values(RT_FORMS.row[r], v);
+        std::copy(v, v + 13, out + 13 * (size_t)r);
+    }
+    return 0;
+}
+
+int asora_debug_form_launches(unsigned long long *counts, int capacity, int *rows)
+{
+    clear_error();
+    if (!rows || capacity < 0 || (capacity > 0 && !counts)) return fail(3, "debug_form_launches: bad arguments");
+    *rows = RT_FORM_COUNT;
+    std::copy(form_launch_counts(), form_launch_counts() + std::min(capacity, RT_FORM_COUNT), counts);
+    return 0;
+}
+
+int asora_debug_form_launches_reset(void)
+{
+    clear_error();
+    reset_form_launch_counts();
+    return 0;
+}
+
+int asora_debug_last_launch_form(int32_t form[13], int *row)
+{
+    clear_error();
+    if (!form || !row) return fail(3, "debug_last_launch_form: null output");
+    *row = last_launched_row();
+    for (int k = 0; k < 13; ++k) form[k] = 0;
+    if (*row >= 0) {
+        int v[13];
+        form_values(RT_FORMS.row[*row], v);
+        std::copy(v, v + 13, form);
+    }
+    return 0;
+}
+
 int asora_debug_block_order(const int32_t *pos0, int begin, int count, int units, int nsrc, int aligned, int cu_count, int32_t *out,
                             size_t capacity, int *grid)
 {

@@ -42,24 +42,28 @@ inline std::string form_text(const RtForm &f)      // the template arguments, as
 
 // The forms that are built, family by family (kind: 0 table rates, 1 the same without the exact zeros, 2 with heating, 3 grey
 // opacity); the kernel's static_asserts check every row.
-constexpr int RT_FORM_COUNT = 182;
+// The 1024-entry LDS tables (more than 256 shells: N >= 512 with R >= 256) are built with the shells in global memory only: the
+// smallest largest shell such a trace has -- N = 512, R = 256, cut into the 96 quarter sectors -- holds 12 445 cells, 199 KB of shell
+// buffers against the 124 KB that LDS leaves beside those tables, so no launch of the library plans them with the shells in LDS
+// (plan_launch, asked about shells that no geometry has, still names such a form; it is reported as not built).
+constexpr int RT_FORM_COUNT = 152;
 struct RtFormTable { RtForm row[RT_FORM_COUNT]; int n; };
 constexpr RtFormTable make_form_table()
 {
     RtFormTable t{};
     constexpr bool f = false, y = true;
-    // single source, THREADS x TABCAP: 256-entry tables at every size, 64-entry ones for small workgroups, 1024-entry ones for large.
-    // Buffer atomics; global atomics (N > 512, option; the exact zeros left out by a branch) with the shells in LDS or, without a
-    // zero-skipping form, in global memory
+    // single source, THREADS x TABCAP: 256-entry tables at every size, 64-entry ones for small workgroups, 1024-entry ones for large
+    // (shells in global memory only).  Buffer atomics; global atomics (N > 512, option; the exact zeros left out by a branch) with
+    // the shells in LDS or, without a zero-skipping form, in global memory
     constexpr int single[10][2] = {{64, 256}, {128, 256}, {256, 256}, {512, 256}, {1024, 256}, {64, 64}, {128, 64}, {256, 1024}, {512, 1024}, {1024, 1024}};
     for (const auto &s : single)
         for (int gs = 0; gs < 2; ++gs)
             for (int ba = 0; ba < 2; ++ba)
                 for (int kind = 0; kind < 4; ++kind)
-                    if (!(gs && (ba || kind == 1))) t.row[t.n++] = RtForm{s[0], gs != 0, f, kind == 2, s[1], kind == 1, kind == 3, ba != 0, 1, f, f, y, f};
+                    if (!(gs && (ba || kind == 1)) && (gs || s[1] != 1024)) t.row[t.n++] = RtForm{s[0], gs != 0, f, kind == 2, s[1], kind == 1, kind == 3, ba != 0, 1, f, f, y, f};
     // column-density dump: 256 threads (pick_launch_shape), shells in LDS or global memory, table or grey opacity
     for (int cap : {256, 1024})
-        for (int gs = 0; gs < 2; ++gs)
+        for (int gs = cap == 1024 ? 1 : 0; gs < 2; ++gs)
             for (int gr = 0; gr < 2; ++gr) t.row[t.n++] = RtForm{256, gs != 0, y, f, cap, f, gr != 0, f, 1, f, f, y, f};
     // two sources per workgroup (production): with and without the exact zeros
     constexpr int paired[8][2] = {{64, 256}, {128, 256}, {256, 256}, {512, 256}, {64, 64}, {128, 64}, {256, 64}, {256, 32}};
@@ -76,7 +80,7 @@ constexpr RtFormTable make_form_table()
         // open boundaries: paired with the 256-entry tables; single with or without heating, shells in LDS or global memory
         t.row[t.n++] = RtForm{th, f, f, f, 256, f, f, y, 2, f, f, y, y};
         for (int cap : {256, 1024})
-            for (int gs = 0; gs < 2; ++gs)
+            for (int gs = cap == 1024 ? 1 : 0; gs < 2; ++gs)
                 for (int ht = 0; ht < 2; ++ht) t.row[t.n++] = RtForm{th, gs != 0, f, ht != 0, cap, f, f, y, 1, f, f, y, y};
         // sub-box sweep: one source with or without heating, two without
         for (int k = 0; k < 3; ++k) t.row[t.n++] = RtForm{th, f, f, k == 1, 256, f, f, y, k == 2 ? 2 : 1, y, f, y, f};

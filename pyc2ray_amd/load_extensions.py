@@ -749,6 +749,39 @@ class _LibAsora:
                         zero_form_exists=bool(out[20]))
         return plan
 
+    def built_forms(self):
+        """The forms raytrace_octant_kernel is built in (asora_debug_built_forms; host only, no device needed): a list of 13-tuples
+        of ints in the order of FORM_FIELDS, one per row of the launcher's table."""
+        rows = C.c_int(0)
+        _capi.check(self._lib.asora_debug_built_forms(None, 0, C.byref(rows)), "built_forms")
+        out = np.zeros((rows.value, 13), dtype=np.int32)
+        _capi.check(self._lib.asora_debug_built_forms(_capi.iptr(out), rows.value, C.byref(rows)), "built_forms")
+        return [tuple(int(v) for v in r) for r in out]
+
+    def form_launches(self):
+        """Launches of every row of built_forms() this process has made since reset_form_launches (asora_debug_form_launches): a
+        uint64 array.  The counters outlive device_close."""
+        rows = C.c_int(0)
+        _capi.check(self._lib.asora_debug_form_launches(None, 0, C.byref(rows)), "form_launches")
+        out = np.zeros(rows.value, dtype=np.uint64)
+        _capi.check(self._lib.asora_debug_form_launches(out.ctypes.data_as(C.POINTER(C.c_ulonglong)), rows.value, C.byref(rows)), "form_launches")
+        return out
+
+    def reset_form_launches(self):
+        _capi.check(self._lib.asora_debug_form_launches_reset(), "reset_form_launches")
+
+    def last_launch_form(self):
+        """(form, row) of the last raytrace launch (asora_debug_last_launch_form): the 13-tuple of built_forms() and its row index;
+        (None, -1) before the first launch."""
+        form, row = np.zeros(13, dtype=np.int32), C.c_int(0)
+        _capi.check(self._lib.asora_debug_last_launch_form(_capi.iptr(form), C.byref(row)), "last_launch_form")
+        return (tuple(int(v) for v in form) if row.value >= 0 else None), row.value
+
+    @staticmethod
+    def form_text(form):
+        """A form as DESIGN.md and the launcher's messages write it: <256,0,0,1,...>."""
+        return "<" + ",".join(str(int(v)) for v in form) + ">"
+
     SUBBOX_LAUNCH_FIELDS = ("valid", "table_sources", "units", "threads", "nsrc", "aligned", "heat", "table_launches", "fly_sources",
                             "fly_threads", "fly_lds_shells", "fly_heat", "fly_launches", "batches")
 

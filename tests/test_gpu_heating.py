@@ -55,25 +55,24 @@ def _reset(lib, capi, opts):
         lib.set_option(getattr(capi, k), 1 if k == "OPT_Z_TRANSPOSED" else 0)
 
 
-def _shells(N, R):
-    """Number of shells of a trace as the dispatcher estimates it (raytrace.hip, launch_raytrace)."""
-    r2 = R * R * (1.0 + 1e-9) + 1e-9
-    return int(min(N // 2, np.floor(np.sqrt(r2))))
-
-
-def _form(v, N, R):
-    """The heating form a launch took (variant table): family, workgroup size, table capacity."""
-    if v["split_descriptors"]:
+def _form(lib, v):
+    """The heating form the last launch took (variant table): family, workgroup size, table capacity -- read from the
+    row the library says it launched (asora_debug_last_launch_form), which must be a heating row and agree with the variant word."""
+    form, row = lib.last_launch_form()
+    assert form is not None and lib.built_forms()[row] == form, (form, row)
+    f = dict(zip(lib.FORM_FIELDS, form))
+    assert f["heat"] and not f["dump"] and not f["grey"] and not f["skip_zero"] and f["nsrc"] == 1 and not f["subbox"], f
+    assert (f["threads"], bool(f["bufatom"]), bool(f["split"]), bool(f["global_scratch"]), bool(f["open"])) == \
+           (v["threads"], v["buffer_atomics"], v["split_descriptors"], v["global_shells"], v["open"]), (f, v)
+    if f["split"]:
         family = "split"
-    elif v["buffer_atomics"]:
+    elif f["bufatom"]:
         family = "buffer"
-    elif v["global_shells"]:
+    elif f["global_scratch"]:
         family = "global_shells"
     else:
         family = "global"
-    S, t = _shells(N, R), v["threads"]
-    cap = 1024 if S + 1 > 256 else 64 if (S + 1 <= 64 and t <= 128) else 256
-    return family, t, cap
+    return family, f["threads"], f["tabcap"]
 
 
 def _lattice_sources(N, n, seed, spacing=12):
@@ -96,7 +95,7 @@ def _identity_launch(lib, capi, N, R, n, dr, numtau, dlog, opts, seen):
         heat = lib.grid_to_host(capi.GRID_PHI_HEAT, np.empty((N, N, N)))
     finally:
         _reset(lib, capi, dict(opts, OPT_HEATING=1))
-    seen.add(_form(v, N, R))
+    seen.add(_form(lib, v))
     assert not v["paired"] and not v["skip_zero"], (R, opts, v)     # neither form exists with heating
     tag = f"N={N} R={R} n={n} {opts} {v}"
     assert phi.max() > 0, tag
@@ -111,8 +110,8 @@ REQUIRED_FORMS = (
     # single source, global atomics (option), shells in LDS
     | {("global", t, 256) for t in (64, 128, 256, 512, 1024)} | {("global", t, 64) for t in (64, 128)})
 # ... and the shells in global memory (family "global_shells", at whatever workgroup size the library picks).  Not reachable
-# below N = 512 (tests/test_gpu_configs.py, test_mesh_576_*): the per-layout descriptor form (SPLIT) and the 1024-entry
-# tables (more than 255 shells).  The sub-box sweep with heating is asora_subbox_raytrace_device's (tests/test_gpu_subbox.py).
+# below N = 512: the per-layout descriptor form (SPLIT) and the 1024-entry tables (more than 256 shells), which
+# tests/test_gpu_form_recipes.py runs row by row, as it does the sub-box sweep with heating.
 
 
 def test_every_heating_form_by_identity_and_against_the_oracle(asora):
@@ -183,7 +182,7 @@ def test_every_heating_form_by_identity_and_against_the_oracle(asora):
             _set(lib, capi, opts)
             try:
                 lib.raytrace_device(R, cases.SIG, dr, 0, 80, cases.MINLOGTAU, bdlog, bthin.shape[0])
-                seen.add(_form(lib.last_raytrace_variant(), N, R))
+                seen.add(_form(lib, lib.last_raytrace_variant()))
                 phi = lib.grid_to_host(capi.GRID_PHI_ION, np.empty((N, N, N)))
                 heat = lib.grid_to_host(capi.GRID_PHI_HEAT, np.empty((N, N, N)))
             finally:

@@ -243,6 +243,16 @@ def _shells(N, R):
     return min(int(np.floor(R)), N // 2)
 
 
+#: the smallest largest shell a trace of more than 256 shells has (N = 512, R = 256, cut into the 96 quarter sectors): such shells
+#: never fit LDS beside the 1024-entry tables, and RT_FORMS holds those tables with the shells in global memory only
+MANY_SHELLS_MAX_CELLS = 12445
+
+
+def _max_cells(N, R, max_cells):
+    """A largest shell that a trace of this many shells can have: `max_cells`, or what more than 256 shells bring at least."""
+    return max(max_cells, MANY_SHELLS_MAX_CELLS) if _shells(N, R) + 1 > 256 else max_cells
+
+
 def _lds(max_cells, tabcap, nsrc):
     """Dynamic LDS of a form with its shells in LDS (the kernel's layout: log table, 1/s, 6 wrapped-coordinate tables and two shell
     buffers per source)."""
@@ -289,7 +299,7 @@ def test_plan_shape_sweep_against_expected_shape(plan):
                 units, threads, paired, aligned = LF.expected_shape(N, NS, R)
                 if _shells(N, R) + 1 > 256:
                     threads = max(threads, 256)           # more than 256 shells: the 1024-entry LDS tables, 256 threads at least
-                s2 = plan(N, R, NS, shells=_shells(N, R), max_cells=1000)
+                s2 = plan(N, R, NS, shells=_shells(N, R), max_cells=_max_cells(N, R, 1000))
                 assert (s2["units"], s2["threads"], s2["aligned"]) == (units, threads, aligned), (N, NS, R)
                 # stage 2 on top: expected_shape's pairing rule, where a paired form exists (up to 512 threads and 256 shells)
                 assert (s2["form"]["nsrc"] == 2) == (paired and threads <= 512 and _shells(N, R) + 1 <= 256), (N, NS, R)
@@ -306,13 +316,19 @@ def test_plan_stage_two_edges(lib, plan):
                                                        (257, None, 1024, None), (1024, None, 1024, None)):
         a = plan(N, R, NS, shells=shells1 - 1, max_cells=1000, OPT_PAIR_SOURCES=2)
         b = plan(N, R, NS, shells=shells1 - 1, max_cells=1000, OPT_PAIR_SOURCES=1)
-        assert a["built"] and b["built"]
+        # (more than 256 shells with a largest shell of 1000 cells: shells no geometry has -- planned, but not among the built forms)
+        assert a["built"] == b["built"] == (shells1 <= 256)
         assert (a["form"]["nsrc"], a["form"]["tabcap"]) == ((2, paired_cap) if paired_cap else (1, 1024)), shells1
         assert (b["form"]["nsrc"], b["form"]["tabcap"], b["form"]["threads"]) == (1, single_cap, 256), shells1
         assert a["lds_bytes"] == _lds(1000, a["form"]["tabcap"], a["form"]["nsrc"]) and b["lds_bytes"] == _lds(1000, single_cap, 1)
         if small_cap:
             s = plan(N, R, NS, shells=shells1 - 1, max_cells=1000, OPT_BLOCK_THREADS=128, OPT_PAIR_SOURCES=1)
             assert s["built"] and (s["form"]["threads"], s["form"]["tabcap"]) == (128, small_cap), shells1
+        else:       # ... and with the largest shell such a trace has at least: the 1024-entry tables, the shells in global memory, built
+            for q in (plan(512, 1000.0, 1, shells=shells1 - 1, max_cells=MANY_SHELLS_MAX_CELLS, OPT_PAIR_SOURCES=pair) for pair in (1, 2)):
+                assert q["built"] and not q["use_lds"] and (q["form"]["nsrc"], q["form"]["tabcap"], q["form"]["global_scratch"]) == (1, 1024, True)
+                assert q["lds_bytes"] == 256 * 16 + 1024 * 32
+    assert _lds(MANY_SHELLS_MAX_CELLS, 1024, 1) > LDS_LIMIT
     assert "more than 1023 shells" in _refused(plan, 4, N, R, NS, shells=1024, max_cells=1000)
     # the LDS limit: the shells of a single source leave LDS, the four shell buffers of a pair leave it first
     mc = _largest_that_fits(256, 1)
@@ -364,7 +380,8 @@ def test_every_plan_is_refused_or_built(plan):
     """The dispatcher's soundness: over the options that shape a launch, the modes and meshes on every side of the descriptor rules,
     radii of every launch shape and shells inside and outside LDS, a call is refused with a message or plans a form of the table.
     The product of the options, the modes and the meshes is complete; what is thinned is what each combination is run with: four of
-    the eight radii (one per launch-shape regime of pick_launch_shape, one beyond the box), each with shells inside LDS and outside,
+    the eight radii (one per launch-shape regime of pick_launch_shape, one beyond the box), each with shells inside LDS and outside
+    (more than 256 shells, N = 512 and 576 with the radius beyond the box: outside only, with the largest shell such a trace has at least),
     one of three source counts and of three ASORA_OPT_SKIP_ZERO_RATES, going round with a running count."""
     modes = ({}, {"heat": True}, {"OPT_GREY_NOTABLES": 1}, {"dump": True}, {"OPT_OPEN_BOUNDARIES": 1}, {"OPT_OPEN_BOUNDARIES": 1, "heat": True})
     radii = (8.0, 13.0, 18.0, 24.5, 30.0, 41.0, 56.0, 1000.0)
@@ -380,7 +397,9 @@ def test_every_plan_is_refused_or_built(plan):
                             for N in (64, 512, 576):
                                 for j in range(8):
                                     R, max_cells, NS = radii[(k + 2 * (j // 2)) % 8], (500, 12000)[j % 2], (1000, 3, 64)[(k // 16) % 3]
-                                    ran.add((m, N, R, max_cells))
+                                    in_lds = max_cells == 500 and _shells(N, R) + 1 <= 256       # (more than 256 shells never fit LDS)
+                                    max_cells = _max_cells(N, R, max_cells)
+                                    ran.add((m, N, R, in_lds))
                                     try:
                                         q = plan(N, R, NS, shells=_shells(N, R), max_cells=max_cells, table_sets=bool((k // 2) % 2),
                                                  OPT_SECTORS=sectors, OPT_BLOCK_THREADS=threads, OPT_PAIR_SOURCES=pair, OPT_ALIGNED_ROWS=rows,
@@ -391,10 +410,10 @@ def test_every_plan_is_refused_or_built(plan):
                                         continue
                                     assert not (m >= 4 and (N == 576 or ga))
                                     assert q["built"], (sectors, threads, pair, rows, ga, N, R, NS, max_cells, mode, q["form"])
-                                    assert q["use_lds"] == (max_cells == 500)
+                                    assert q["use_lds"] == in_lds
                                     planned += 1
                                     seen.add(tuple(q["form"].values()))
     print(f"{planned} planned, {refused} refused, {len(seen)} distinct forms, {len(ran)} of {6 * 3 * 8 * 2} (mode, N, R, shells) run")
     total = 8 * 10 * 6 * 3 * 3 * 2 * 6 * 3
     assert planned + refused == total and refused == total // 3 * 4 // 6          # the two open modes, on N = 576 or under global atomics
-    assert len(ran) == 6 * 3 * 8 * 2
+    assert len(ran) == 6 * 3 * 8 * 2 - 12                    # (N = 512 and 576 with the radius beyond the box: 257 and 289 shells, outside LDS both times)
