@@ -1000,6 +1000,11 @@ size_t asora_debug_geometry_bytes(void);
 void asora_debug_placement(int *candidates, double *chosen_probe_ms, double *slowest_probe_ms);
 /* Host wall clock (ms) of the last asora_device_init and, inside it, of the placement probe (0 when the first allocation was taken). */
 void asora_debug_init_cost(double *device_init_ms, double *placement_probe_ms);
+/* What the library holds in device and pinned host memory (pyc2ray_amd/csrc/device_memory.hpp).  Host only, no device needed.
+ * lifetime 0: the buffers of the mesh, which asora_device_close and a re-initialising asora_device_init release; 1: the buffers
+ * of the process, which are never released.  *buffers = the non-empty ones of that lifetime, *bytes = the sum of the sizes they
+ * were allocated with.  Code 3 for another lifetime. */
+int asora_debug_live_buffers(int lifetime, long long *buffers, unsigned long long *bytes);
 int asora_debug_geometry_table(int table, uint32_t *words, size_t capacity_entries, size_t *entries, int *nsteps, int *ntables,
                                int *shells, int *max_cells, int *threads);
 

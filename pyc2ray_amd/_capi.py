@@ -126,6 +126,7 @@ SIGNATURES = {
     "asora_evolve_slab_fold_all": (C.c_int, []),
     "asora_debug_placement": (None, [C.POINTER(C.c_int), _dp, _dp]),
     "asora_debug_init_cost": (None, [_dp, _dp]),
+    "asora_debug_live_buffers": (C.c_int, [C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_ulonglong)]),
     "asora_evolve_slab_add": (C.c_int, [C.c_int, C.c_int, C.c_void_p]),
     "asora_evolve_slab_add_host": (C.c_int, [C.c_int, C.c_int, _dp]),
     "asora_evolve_slab_heat_outbox": (C.c_void_p, []),

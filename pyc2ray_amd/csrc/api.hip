@@ -78,67 +78,29 @@ int ensure_runtime()
     }
     ASORA_HIP_TRY(hipEventCreateWithFlags(&st.main_ready, hipEventDisableTiming));
     st.red_blocks = chemistry_reduction_blocks(st);
-    st.red_cap = 3 * (size_t)st.red_blocks;
-    ASORA_HIP_TRY(hipMalloc(&st.red_partial, sizeof(double) * st.red_cap));
-    ASORA_HIP_TRY(hipMalloc(&st.red_final, sizeof(double) * 3));
-    ASORA_HIP_TRY(hipHostMalloc(&st.red_host, sizeof(double) * 3, hipHostMallocDefault));
-    ASORA_HIP_TRY(hipMalloc(&st.counters, sizeof(unsigned long long) * COUNTER_FIELDS * COUNTER_SLOTS));
+    if (int rc = st.red_partial.allocate(3 * (size_t)st.red_blocks)) return rc;
+    if (int rc = st.red_final.allocate(3)) return rc;
+    if (int rc = st.red_host.allocate(3)) return rc;
+    if (int rc = st.counters.allocate((size_t)COUNTER_FIELDS * COUNTER_SLOTS)) return rc;
     ASORA_HIP_TRY(hipMemset(st.counters, 0, sizeof(unsigned long long) * COUNTER_FIELDS * COUNTER_SLOTS));
     return 0;
 }
 
+// What dies with the mesh.  The buffers know it themselves (MeshBuffer / MeshPinned fields of State, device_memory.hpp); the
+// bookkeeping beside them goes back to what a fresh State holds.
 static int release_all()
 {
     State &st = g_state;
-    auto drop = [](auto *&ptr) { if (ptr) { (void)hipFree(ptr); ptr = nullptr; } };
-    // (the grids of the hot loop are parts of the arena; the heating grid is an allocation of its own)
-    drop(st.grid[ASORA_GRID_PHI_HEAT]);
-    drop(st.grid[ASORA_GRID_TEMP_END]); drop(st.heat_acc); drop(st.heat_outbox); drop(st.th_stats_dev);
-    st.heat_clean[0] = st.heat_clean[1] = false;
-    st.th_on = false; st.th = ThermalConsts();
-    drop(st.grid[ASORA_GRID_CLUMP]);
-    st.clump_mode = 0; st.clump_c = 1.0;
-    st.lls_a = st.lls_b = 0.0;
-    st.plane = PlaneFluxSet{};
-    drop(st.budget_partial);
-    if (st.budget_host) { (void)hipHostFree(st.budget_host); st.budget_host = nullptr; }
-    drop(st.bubble_mask); drop(st.bubble_rows); drop(st.bubble_scan); drop(st.bubble_partial); drop(st.bubble_result); drop(st.bubble_edges);
-    if (st.bubble_host) { (void)hipHostFree(st.bubble_host); st.bubble_host = nullptr; }
-    drop(st.region_label); drop(st.region_volume); drop(st.region_flags); drop(st.region_result);
-    drop(st.topo_complement);
-    drop(st.gran_work); drop(st.gran_mask); drop(st.gran_result);
-    drop(st.ps_modes[0]); drop(st.ps_modes[1]); drop(st.ps_twiddle); drop(st.ps_partial); drop(st.ps_thresholds);
-    if (st.ps_host) { (void)hipHostFree(st.ps_host); st.ps_host = nullptr; }
-    drop(st.sm_field); drop(st.sm_tables); drop(st.sm_partial); drop(st.sm_result);
-    if (st.sm_host) { (void)hipHostFree(st.sm_host); st.sm_host = nullptr; }
-    drop(st.rs_velocity); drop(st.rs_partial); drop(st.rs_thresholds); drop(st.rs_vmax_dev); st.rs_vmax = 0.0;
-    if (st.rs_host) { (void)hipHostFree(st.rs_host); st.rs_host = nullptr; }
-    for (int g = 0; g < ASORA_GRID_COUNT; ++g) { st.grid[g] = nullptr; st.grid_valid[g] = false; }
+    OwnedMemory::release_all_of(LIFETIME_MESH);
+    st.thermal.mode = {}; st.medium = {}; st.sources.loaded = {}; st.zero.verdict = {}; st.evolve.flags = {}; st.reach.d = {};
+    st.rt = {}; st.redshift.vmax = 0.0; st.temp_probe.valid = false;
+    for (int g = 0; g < ASORA_GRID_COUNT; ++g) { st.grid[g] = nullptr; st.grid_valid[g] = false; }     // (aliases of the arena and of the three grids beside it)
     st.nhi = st.staging = st.acc = nullptr;
-    drop(st.arena); st.arena_bytes = 0;
-    st.ev_clean[0] = st.ev_clean[1] = false; st.ev_sets_known = false;
-    drop(st.reach.mask); drop(st.reach.count_dev); st.reach = State::ReachMask();
-    st.ev_open = false;
-    st.temp_probe_valid = false;
     st.nhi_t = st.phi_t = st.heat_t = nullptr;    // second halves of nhi / phi_ion / phi_heat
-    st.have_heat_tables = false;
-    drop(st.tables); st.table_len = 0; st.num_spec = 1; st.spec_stride = 0;
-    drop(st.src_spec); drop(st.src_spec_sorted); st.src_spec_max = 0;
-    drop(st.src_pos); drop(st.src_flux); drop(st.src_pos_sorted); drop(st.src_flux_sorted); st.src_i0_sorted.clear(); st.num_src = 0;
-    st.src_pos_host.clear(); st.src_pos_sorted_host.clear();
     release_pair_lists(st);
-    drop(st.shell_scratch); st.shell_scratch_bytes = 0;
-    drop(st.sb_trail); st.sb_trail_bytes = 0;
-    if (st.geom_patch_dev) { (void)hipFree(st.geom_patch_dev); st.geom_patch_dev = nullptr; st.geom_patch_cap = 0; }
-    drop(st.sb_active); drop(st.sb_nbox); drop(st.sb_loss); drop(st.sb_loss_final); st.subbox_cap = 0;
     release_geometry(st);
+    if (st.zero.done) { (void)hipEventDestroy(st.zero.done); st.zero.done = nullptr; }
     st.init = false; st.N = 0; st.ncell = 0;
-    st.rt_radius[0] = State::RadiusHistory(); st.rt_radius[1] = State::RadiusHistory();
-    if (st.zero_probe_dev) { (void)hipFree(st.zero_probe_dev); st.zero_probe_dev = nullptr; }
-    if (st.zero_probe_host) { (void)hipHostFree(st.zero_probe_host); st.zero_probe_host = nullptr; }
-    if (st.zero_probe_done) { (void)hipEventDestroy(st.zero_probe_done); st.zero_probe_done = nullptr; }
-    st.zero_probe_pending = false; st.zero_known = false; st.zero_dark = false; st.zero_since_probe = 0;
-    st.rt_open = false;
     return 0;
 }
 
@@ -164,7 +126,7 @@ int check_planes(const char *who, int code, const char *tail, int i_begin, int i
 
 int check_sources(const char *who, int code, const std::string &tail, int src_begin, int src_count)
 {
-    if (src_begin < 0 || src_count < 0 || src_begin + src_count > g_state.num_src) return fail(code, std::string(who) + ": " + tail);
+    if (src_begin < 0 || src_count < 0 || src_begin + src_count > g_state.sources.loaded.num) return fail(code, std::string(who) + ": " + tail);
     return 0;
 }
 
@@ -232,8 +194,8 @@ static int choose_arena(State &st, size_t slot, int slots)
         want = (int)std::max<size_t>(1, std::min<size_t>((size_t)want, (size_t)(0.125 * (double)free_b) / total));     // (several ranks may share a GPU)
     st.arena_candidates = 0; st.arena_probe_ms = st.arena_probe_worst_ms = st.arena_probe_wall_ms = 0.0;
     if (want == 1) {
-        ASORA_HIP_TRY(hipMalloc(&st.arena, total));
-        st.arena_bytes = total; st.arena_candidates = 1;
+        if (int rc = st.arena.allocate(total)) return rc;
+        st.arena_candidates = 1;
         return 0;
     }
     hipEvent_t t0, t1;
@@ -265,8 +227,7 @@ static int choose_arena(State &st, size_t slot, int slots)
     (void)hipEventDestroy(t0); (void)hipEventDestroy(t1);
     if (best < 0) return fail(2, "device_init: out of device memory for the grids");
     for (size_t c = 0; c < cand.size(); ++c) if ((int)c != best) (void)hipFree(cand[c]);
-    st.arena = cand[(size_t)best];
-    st.arena_bytes = total;
+    st.arena.adopt(cand[(size_t)best], total);
     st.arena_candidates = (int)cand.size();
     st.arena_probe_ms = ms[(size_t)best]; st.arena_probe_worst_ms = worst;
     st.arena_probe_wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
@@ -284,6 +245,17 @@ void asora_debug_init_cost(double *device_init_ms, double *placement_probe_ms)
 {
     if (device_init_ms) *device_init_ms = g_state.device_init_wall_ms;
     if (placement_probe_ms) *placement_probe_ms = g_state.arena_probe_wall_ms;
+}
+
+int asora_debug_live_buffers(int lifetime, long long *buffers, unsigned long long *bytes)
+{
+    clear_error();
+    if (lifetime != LIFETIME_MESH && lifetime != LIFETIME_PROCESS) return fail(3, "debug_live_buffers: lifetime must be 0 (mesh) or 1 (process)");
+    long long n = 0; unsigned long long b = 0;
+    OwnedMemory::live((Lifetime)lifetime, n, b);
+    if (buffers) *buffers = n;
+    if (bytes) *bytes = b;
+    return 0;
 }
 
 const char *asora_last_error(void) { return g_error.c_str(); }
@@ -324,7 +296,7 @@ int asora_device_init_ex(int N, int num_src_par, int device_id)
     st.nhi_t = st.nhi + st.ncell;
     st.phi_t = st.grid[ASORA_GRID_PHI_ION] + st.ncell;
     st.heat_t = nullptr;
-    st.ev_sets_known = false;
+    st.evolve.flags.sets_known = false;
     {   // per-workgroup partials of the tiled chemistry pass: the j-chunk count is rounded up per (k tile x i tile), so a
         // RANGE of planes (asora_chemistry_range: a multi-GPU rank's slab) can need more workgroups than the whole grid
         size_t worst = 0;

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/asora_hip.h"
+#include "device_memory.hpp"
 #include "raytrace_plan.hpp"
 
 namespace asora {
@@ -164,7 +165,9 @@ struct EvolveStatus {
 };
 
 // ---------------------------------------------------------------------------------------------
-// Process-global device state (the role of src/asora/memory.cu:20-29)
+// Process-global device state (the role of src/asora/memory.cu:20-29).  Every buffer is an owning field (device_memory.hpp) of the
+// unit it belongs to: MeshBuffer / MeshPinned die with the mesh, ProcessBuffer / ProcessPinned never.  The scalar bookkeeping that
+// dies with the mesh stands in a plain aggregate beside its buffers, which release_all() (api.hip) resets by one assignment.
 // ---------------------------------------------------------------------------------------------
 struct State {
     bool init = false;
@@ -175,34 +178,52 @@ struct State {
     int num_src_par = 0;           // accepted, unused (no per-source N^3 scratch in this build)
     int cu_count = 256;
 
+    // every N^3 grid of the hot loop lives in ONE allocation (api.hip: choose_arena), picked among several candidates by a probe;
+    // PHI_HEAT (with its [k][j][i] twin), TEMP_END and CLUMP are allocations of their own, made on first use (ensure_optional_grid).
+    // grid[] aliases both kinds
+    MeshBuffer<char> arena;
+    MeshBuffer<double> phi_heat_grid, temp_end_grid, clump_grid;
     double *grid[ASORA_GRID_COUNT] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool grid_valid[ASORA_GRID_COUNT] = {false, false, false, false, false, false, false, false, false};
+    int arena_candidates = 0;               // how many were tried
+    double arena_probe_ms = 0.0, arena_probe_worst_ms = 0.0;     // the chosen one's probe time, the slowest candidate's
+    double arena_probe_wall_ms = 0.0, device_init_wall_ms = 0.0; // host wall clock of the whole probe / of the last device_init
 
-    // derived per raytrace call
+    // derived per raytrace call (aliases of the arena)
     // each of these is the second half of a 2 N^3 allocation whose first half is the [i][j][k] grid
-    double *nhi = nullptr;     // ndens*(1-xh_av), [i][j][k] (owns the allocation)
+    double *nhi = nullptr;     // ndens*(1-xh_av), [i][j][k]
     double *nhi_t = nullptr;   // = nhi + N^3: same, transposed [k][j][i]
     double *phi_t = nullptr;   // = grid[PHI_ION] + N^3: rate accumulator for z-faces, transposed [k][j][i]
     double *heat_t = nullptr;  // = grid[PHI_HEAT] + N^3: heating-rate accumulator for z-faces, transposed
-    bool have_heat_tables = false;
     double *staging = nullptr; // N^3 staging grid for 'F'-order transfers / debug dumps
+    // fused evolve loop (asora_evolve_*): raytrace accumulators of their own ([i][j][k] then [k][j][i]; the chemistry
+    // kernel folds them into PHI_ION and zeroes them), device-side convergence bookkeeping
+    // TWO sets of accumulators, each [i][j][k] then [k][j][i] (4 N^3 doubles).  Iteration k of a
+    // time step traces into set (evolve.base + k - 1) & 1; its fused pass reads that set WITHOUT destroying it and zeroes the
+    // other one for iteration k + 1.  The rates of the last iteration carried out therefore survive in their set until the
+    // host asks for them (asora_evolve_poll folds them into PHI_ION): the pass writes no rate grid (88 instead of 96 B per cell).
+    double *acc = nullptr;
 
-    double2 *tables = nullptr;     // num_spec blocks of [thick | thin | heat thick | heat thin] (pack_rate_table), spec_stride apart
-    int table_len = 0;
-    int num_spec = 1;              // table sets on the device (asora_spectra_to_device; the one-set uploads: 1)
-    size_t spec_stride = 0;        // double2 entries of one set's block (rate_block_entries)
-
-    int32_t *src_pos = nullptr;
-    double *src_flux = nullptr;
-    int num_src = 0;
-    // the same sources ordered by their first coordinate (pipelined asora_do_all_sources)
-    int32_t *src_pos_sorted = nullptr;
-    double *src_flux_sorted = nullptr;
-    std::vector<int> src_i0_sorted;
-    // table set of each source (asora_source_spectra_to_device), in the order of src_pos and of src_pos_sorted; nullptr while
-    // every source has set 0.  src_spec_max: the largest index uploaded, checked against num_spec before every trace
-    int32_t *src_spec = nullptr, *src_spec_sorted = nullptr;
-    int src_spec_max = 0;
+    // the sources and their spectra: the rate tables, num_spec blocks of [thick | thin | heat thick | heat thin] (pack_rate_table),
+    // spec_stride apart; the source list as uploaded and ordered by the first coordinate (pipelined asora_do_all_sources); the
+    // table set of each source (asora_source_spectra_to_device) in both orders, null while every source has set 0
+    struct Sources {
+        MeshBuffer<double2> tables;
+        MeshBuffer<int32_t> pos, pos_sorted, spec, spec_sorted;
+        MeshBuffer<double> flux, flux_sorted;
+        struct Loaded {
+            int table_len = 0, num = 0;    // entries of a table; sources
+            int num_spec = 1;              // table sets on the device (asora_spectra_to_device; the one-set uploads: 1)
+            size_t spec_stride = 0;        // double2 entries of one set's block (rate_block_entries)
+            bool heat_tables = false;
+            int spec_max = 0;              // the largest table set uploaded for a source, checked against num_spec before every trace
+            std::vector<int> i0_sorted;
+            // host copies of the two source lists (as uploaded, and in lexicographic order of the position): who shares a
+            // workgroup with whom on aligned tables is decided from them (source_pairs_by_class)
+            std::vector<int32_t> pos_host, pos_sorted_host;
+        } loaded;
+    } sources;
+    long src_generation = 0;                // counts asora_source_data_to_device calls
     std::vector<hipEvent_t> pipe_events;
 
     // raytracing geometry tables (built once per (N, R, dr), see raytrace.hip)
@@ -210,21 +231,21 @@ struct State {
     size_t geom_bytes = 0;                  // device memory the current tables occupy (shells shared by several tables count once)
     OctGeomDev geom_host[MAX_UNITS];        // device pointers of the unit tables ([class * units + unit] when geom_aligned)
     bool geom_aligned = false;
-    // how the radius has behaved across raytrace launches (plan_shape: the eight-fold tables only pay when they are reused)
     // exact-zero rates (ASORA_OPT_SKIP_ZERO_RATES = 0): decide_skip_zero takes the kernels that leave them out while its probes
     // find enough of them
-    unsigned long long *zero_probe_dev = nullptr;    // [2 * ZERO_PROBE_SLOTS]
-    unsigned long long *zero_probe_host = nullptr;   // pinned: {rated, left out} of the last probe
-    hipEvent_t zero_probe_done = nullptr;
-    bool zero_probe_pending = false, zero_known = false, zero_dark = false;
-    int zero_since_probe = 0;
+    struct ZeroProbe {
+        MeshBuffer<unsigned long long> dev;     // [2 * ZERO_PROBE_SLOTS]
+        MeshPinned<unsigned long long> host;    // {rated, left out} of the last probe
+        hipEvent_t done = nullptr;
+        struct Verdict { bool pending = false, known = false, dark = false; int since_probe = 0; } verdict;
+    } zero;
     int last_variant = 0;                   // ASORA_VARIANT_* bits | units << 8 | threads << 16 of the last raytrace launch
     int sb_launch[ASORA_SUBBOX_LAUNCH_WORDS] = {};   // what the last sub-box call launched (asora_debug_last_subbox_launch), written where the launches are made
+    // a raytrace call in progress (asora_raytrace_begin ... _range ... _fold); how the radius has behaved across launches (plan_shape)
     struct RadiusHistory { double last_R = -1.0; long same_R_calls = 0; bool has_changed = false; };
-    RadiusHistory rt_radius[2];             // [0]: whole-box traces and the evolve loop, [1]: the sub-box sweep (note_call_radius)
-    // host copies of the two source lists (as uploaded, and in lexicographic order of the position) and, for the paired-sources
-    // variant on aligned tables, who shares a workgroup with whom: built once per (list, range), see source_pairs_by_class
-    std::vector<int32_t> src_pos_host, src_pos_sorted_host;
+    struct Trace { bool open = false; RadiusHistory radius[2]; } rt;   // radius: [0] whole-box traces and the evolve loop, [1] the sub-box sweep (note_call_radius)
+    // for the paired-sources variant on aligned tables, who shares a workgroup with whom: built once per (list, range), see
+    // source_pairs_by_class
     struct PairList { const void *list; int begin, count; int2 *dev[2]; int n[2]; std::vector<int> cls[2]; };   // cls: the class of each pair
     std::vector<PairList> pair_lists;      // (a sharded or chunked trace asks for the same few ranges every iteration)
     // ... and which (group, unit) every block of such a launch sweeps (block_order, raytrace_plan.hpp): built once per (list, range,
@@ -232,7 +253,7 @@ struct State {
     struct OrderList { const void *list; int begin, count, units, aligned, nsrc; int2 *dev; unsigned grid; };
     std::vector<OrderList> order_lists;
     int geom_units = 0;
-    double2 *logtab_dev = nullptr;          // log2 table (ensure_logtab), lives until the runtime is torn down
+    ProcessBuffer<double2> logtab_dev;      // log2 table (ensure_logtab), lives until the runtime is torn down
     bool geom_valid = false;
     bool geom_on_host = false;              // the cached tables were built by the host builder (ASORA_OPT_GEOMETRY_ON_HOST)
     // table entries of cells that sit (to rounding) exactly ON the sphere: whether such a cell gets a rate is decided by
@@ -240,8 +261,7 @@ struct State {
     // their RATE bit is re-decided in place when dr changes (a cosmological run: every time step) -- no rebuild.
     struct SphereCell { uint32_t *dev_word; uint32_t word_without_rate; int a, b, c; };
     std::vector<SphereCell> geom_sphere;
-    void *geom_patch_dev = nullptr;         // staging for the patch kernel: {address, value} pairs
-    size_t geom_patch_cap = 0;
+    MeshBuffer<unsigned long long> geom_patch_dev;   // staging for the patch kernel: {address, value} pairs
     int geom_N = 0, geom_S = 0, geom_max_cells = 0, geom_threads = 0;
     // sub-box tables (subbox_tables_prepare): traversal range instead of the periodic window, no octahedron bound, every
     // sub-box boundary padded to whole triples of steps; step_after_shell[u][s] = first table step behind shell s of unit u
@@ -249,9 +269,8 @@ struct State {
     std::vector<int> geom_step_after_shell[12];
     double geom_R = 0.0, geom_dr = 0.0;
 
-    // a raytrace call in progress (asora_raytrace_begin ... _range ... _fold)
     RtParams rt_params;
-    bool rt_open = false, rt_heat = false;
+    bool rt_heat = false;
     // pipelined calls put consecutive source ranges on two side streams, so that the tail of one range and the
     // head of the next overlap; folds (main stream) wait for the ranges issued before them
     bool rt_pipelined = false;
@@ -261,158 +280,150 @@ struct State {
     bool side_pending[2] = {false, false};
     int side_next = 0;
 
-    // per-source bookkeeping of the sub-box raytracer (subbox.hip), sized for the largest batch so far
-    int *sb_active = nullptr, *sb_nbox = nullptr, *sb_nactive = nullptr;
-    double *sb_loss = nullptr, *sb_loss_final = nullptr;
-    size_t subbox_cap = 0;
-
-    double *sb_trail = nullptr;             // per (source, unit): the trailing shell between two sub-box launches (table path)
-    size_t sb_trail_bytes = 0;
+    // per-source bookkeeping of the sub-box raytracer (subbox.hip), sized for the largest batch so far, and, per (source, unit),
+    // the trailing shell between two sub-box launches (table path)
+    struct Subbox { MeshBuffer<int> active, nbox; MeshBuffer<double> loss, loss_final, trail; ProcessBuffer<int> nactive; } subbox;
 
     // shell scratch for traces whose shell buffers exceed LDS
-    double *shell_scratch = nullptr;
-    size_t shell_scratch_bytes = 0;
+    MeshBuffer<double> shell_scratch;
 
     // chemistry reductions
-    double *red_partial = nullptr; // [3][red_cap]: per-workgroup partial sums (red_cap >= red_blocks)
-    size_t red_cap = 0;
-    double *red_final = nullptr;   // [3]
-    double *red_host = nullptr;    // pinned [3]
+    ProcessBuffer<double> red_partial;      // per-workgroup partial sums: room for 3 red_blocks and for every tiled pass (ensure_red_capacity)
+    ProcessBuffer<double> red_final;        // [3]
+    ProcessPinned<double> red_host;         // [3]
     int red_blocks = 0;
     // the step budget's own buffers (asora_step_budget, step_budget.hip), allocated by the first call: per-workgroup partials
-    // [ASORA_BUDGET_COUNT][red_blocks] with the twelve results behind them, and where those arrive on the host (pinned)
-    double *budget_partial = nullptr;
-    double *budget_host = nullptr;
+    // [ASORA_BUDGET_COUNT][red_blocks] with the twelve results behind them, and where those arrive on the host
+    struct Budget { MeshBuffer<double> partial; MeshPinned<double> host; } budget;
     // the bubble-size distribution's own buffers (asora_bubble_mfp, bubble_mfp.hip), allocated by the first call for the mesh of
     // device_init: the bit mask [N^2 W], the row counts [N^2], their exclusive scan [N^2 + 1], the ray workgroups' partial moments,
-    // the result words and the bin edges on the device; result words and edges on the host (pinned)
-    unsigned long long *bubble_mask = nullptr, *bubble_scan = nullptr, *bubble_result = nullptr, *bubble_host = nullptr;
-    unsigned *bubble_rows = nullptr;
-    double *bubble_partial = nullptr, *bubble_edges = nullptr;
+    // the result words and the bin edges on the device; result words and edges on the host
+    struct Bubbles {
+        MeshBuffer<unsigned long long> mask, scan, result;
+        MeshPinned<unsigned long long> host;
+        MeshBuffer<unsigned> rows;
+        MeshBuffer<double> partial, edges;
+    } bubbles;
     // the connected regions' own buffers (asora_region_sizes, region_label.hip), allocated by the first call: one uint32 label and
     // one uint32 volume per cell, the result words, the 3 N plane flags of the largest region; mask, edges and the pinned area are
     // the bubble buffers above
-    unsigned *region_label = nullptr, *region_volume = nullptr, *region_flags = nullptr;
-    unsigned long long *region_result = nullptr;
+    struct Regions { MeshBuffer<unsigned> label, volume, flags; MeshBuffer<unsigned long long> result; } regions;
     // the topology's own buffer (asora_topology, topology.hip), allocated by the first call: the bit mask of the complement [N^2 W];
     // everything else it uses is the bubble and region buffers above
-    unsigned long long *topo_complement = nullptr;
+    struct Topology { MeshBuffer<unsigned long long> complement; } topology;
     // the granulometry's own buffers (asora_granulometry, granulometry.hip), allocated by the first call: a third uint32 grid [N^3]
-    // next to region_label / region_volume, the bit mask of an eroded set [N^2 W] and the result words
-    unsigned *gran_work = nullptr;
-    unsigned long long *gran_mask = nullptr, *gran_result = nullptr;
+    // next to regions.label / regions.volume, the bit mask of an eroded set [N^2 W] and the result words
+    struct Granulometry { MeshBuffer<unsigned> work; MeshBuffer<unsigned long long> mask, result; } granulometry;
     // the power spectrum's own buffers (asora_power_spectrum, power_spectrum.hip), allocated by the first call that needs them: the
     // complex half-space of field a [N N (N/2 + 1)] and, from the first cross call, of field b; the N roots of unity; the partial
-    // sums (mean density, moments, the planes' bin sums) with the result words behind them, and where those arrive on the host
-    // (pinned).  ps_ms: the stage times of the last call under ASORA_OPT_TIMING (asora_debug_power_spectrum_ms)
-    double2 *ps_modes[2] = {nullptr, nullptr};
-    double2 *ps_twiddle = nullptr;
-    double *ps_partial = nullptr, *ps_host = nullptr;
-    unsigned *ps_thresholds = nullptr;
-    double ps_ms[ASORA_PS_STAGES] = {0, 0, 0, 0, 0};
+    // sums (mean density, moments, the planes' bin sums) with the result words behind them, and where those arrive on the host.
+    // ms: the stage times of the last call under ASORA_OPT_TIMING (asora_debug_power_spectrum_ms)
+    struct Spectrum {
+        MeshBuffer<double2> modes[2], twiddle;
+        MeshBuffer<double> partial;
+        MeshPinned<double> host;
+        MeshBuffer<unsigned> thresholds;
+        double ms[ASORA_PS_STAGES] = {0, 0, 0, 0, 0};
+    } spectrum;
     // the smoothing's own buffers (asora_smooth_field, smooth_field.hip), allocated by the first call that needs them: the output
     // field [N^3] of a call without dst_grid; the filter tables w_i, w_j, w_k [N each], w_r [3 floor(N/2)^2 + 1] and the histogram's
     // edges behind them; the workgroups' partial statistics; the result words (stats, then the histogram); and the pinned area the
     // tables and edges leave the host through and the results arrive in.  The complex buffer, the roots and the forward pass's
-    // partial sums are the power spectrum's.  sm_ms: the stage times of the last call under ASORA_OPT_TIMING
-    double *sm_field = nullptr, *sm_tables = nullptr, *sm_partial = nullptr, *sm_result = nullptr, *sm_host = nullptr;
-    double sm_ms[ASORA_SMOOTH_STAGES] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // partial sums are the power spectrum's.  ms: the stage times of the last call under ASORA_OPT_TIMING
+    struct Smoothing {
+        MeshBuffer<double> field, tables, partial, result;
+        MeshPinned<double> host;
+        double ms[ASORA_SMOOTH_STAGES] = {0, 0, 0, 0, 0, 0, 0, 0};
+    } smoothing;
     // the redshift-space unit's own buffers (redshift_space.hip): the line-of-sight velocity [N^3] of asora_los_velocity_to_device
     // with max |v| kept on the host; the planes' partial bin sums with the moments' partials and the result words behind them; the
     // two threshold tables; the pinned area the thresholds leave through and the results arrive in.  The mapped field lies in
-    // sm_field (the smoothing's output buffer), the complex buffer, the roots and the mean density's partials are the power
-    // spectrum's.  rs_ms: the stage times of the last asora_power_spectrum_los call under ASORA_OPT_TIMING
-    double *rs_velocity = nullptr, *rs_partial = nullptr, *rs_thresholds = nullptr, *rs_host = nullptr;
-    unsigned long long *rs_vmax_dev = nullptr;
-    double rs_vmax = 0.0;
-    double rs_ms[ASORA_PSLOS_STAGES] = {0, 0, 0, 0, 0, 0};
+    // smoothing.field, the complex buffer, the roots and the mean density's partials are the power spectrum's.  ms: the stage times
+    // of the last asora_power_spectrum_los call under ASORA_OPT_TIMING
+    struct Redshift {
+        MeshBuffer<double> velocity, partial, thresholds;
+        MeshPinned<double> host;
+        MeshBuffer<unsigned long long> vmax_dev;
+        double vmax = 0.0;                  // dies with the velocity
+        double ms[ASORA_PSLOS_STAGES] = {0, 0, 0, 0, 0, 0};
+    } redshift;
 
-    unsigned long long *counters = nullptr; // [COUNTER_FIELDS * COUNTER_SLOTS] device: gamma cells, evaluated cells, exact zeros left out, spread over the slots
+    ProcessBuffer<unsigned long long> counters;   // [COUNTER_FIELDS * COUNTER_SLOTS]: gamma cells, evaluated cells, exact zeros left out, spread over the slots
     long long last_gamma_cells = 0, last_eval_cells = 0;
 
-    // fused evolve loop (asora_evolve_*): raytrace accumulators of their own ([i][j][k] then [k][j][i]; the chemistry
-    // kernel folds them into PHI_ION and zeroes them), device-side convergence bookkeeping
-    // TWO sets of accumulators, each [i][j][k] then [k][j][i] (4 N^3 doubles, allocated on first use).  Iteration k of a
-    // time step traces into set (ev_base + k - 1) & 1; its fused pass reads that set WITHOUT destroying it and zeroes the
-    // other one for iteration k + 1.  The rates of the last iteration carried out therefore survive in their set until the
-    // host asks for them (asora_evolve_poll folds them into PHI_ION): the pass writes no rate grid (88 instead of 96 B per cell).
-    double *acc = nullptr;
-    // every N^3 grid of the hot loop lives in ONE allocation (api.hip: choose_arena), picked among several candidates by a probe
-    char *arena = nullptr;
-    size_t arena_bytes = 0;
-    int arena_candidates = 0;               // how many were tried
-    double arena_probe_ms = 0.0, arena_probe_worst_ms = 0.0;     // the chosen one's probe time, the slowest candidate's
-    double arena_probe_wall_ms = 0.0, device_init_wall_ms = 0.0; // host wall clock of the whole probe / of the last device_init
-    int ev_base = 0;                        // set of the first iteration of the current time step
-    bool ev_clean[2] = {false, false};      // set known to be all zero (when nothing is enqueued)
-    bool ev_sets_known = false;             // the bookkeeping above is valid (a poll has happened since the last enqueue)
-    int ev_folded_iter = -1;                // PHI_ION holds the rates of this iteration of the current step (0: none yet)
-    EvolveStatus *ev_status = nullptr;      // device
-    EvolveStatus *ev_host = nullptr;        // pinned
-    bool ev_open = false, ev_first = true;
-    // temperature probe of the TEMP grid: valid for the upload `temp_generation` and the constants in temp_consts
-    double *temp_probe_dev = nullptr;       // [8] device: the probe's five results, [5] = asora_grid_sum's
-    double temp_probe[5] = {0, 0, 0, 0, 0}; // host copy: uniform?, T, brech0, acolh0, t_ok
-    bool temp_probe_valid = false;
-    double temp_consts[4] = {0, 0, 0, 0};
-    int ev_reported = 0;                    // iterations already handed to the caller by asora_evolve_poll
-    int ev_enqueued = 0;                    // upper bound of the iterations carried out (enqueued) in this step
-    double ev_chem[6] = {0, 0, 0, 0, 0, 0}; // dt, bh00, albpow, colh0, temph0, abu_c
-    int ev_src_begin = 0, ev_src_count = 0;
-    RtParams ev_rt;
-    // multi-GPU form of the loop (asora_evolve_begin_slab): this rank runs the fused pass on the planes it owns only
-    bool ev_slab = false;
-    int ev_own_begin = 0, ev_own_count = 0;
-    bool ev_slab_passed = false;            // the current iteration's pass has been enqueued (close comes next)
-    bool ev_folded_all = false;             // ... and this iteration's has been enqueued
-    bool ev_rates_in_outbox = false;        // asora_evolve_slab_fold_all: the passes of this step read the out-box and keep PHI_ION
-    bool ev_slab_thermal = false;           // begun with asora_evolve_begin_slab_thermal: every slab call carries the heating rates too
+    // the evolve step (asora_evolve_*): which accumulator set is which, the device-side convergence bookkeeping, what the step was
+    // begun with
+    struct Evolve {
+        struct Flags {
+            bool clean[2] = {false, false}; // set known to be all zero (when nothing is enqueued)
+            bool sets_known = false, open = false;   // sets_known: the line above is valid (a poll has happened since the last enqueue)
+        } flags;
+        int base = 0;                       // set of the first iteration of the current time step
+        int folded_iter = -1;               // PHI_ION holds the rates of this iteration of the current step (0: none yet)
+        ProcessBuffer<EvolveStatus> status;
+        ProcessPinned<EvolveStatus> host;
+        bool first = true;
+        int reported = 0;                   // iterations already handed to the caller by asora_evolve_poll
+        int enqueued = 0;                   // upper bound of the iterations carried out (enqueued) in this step
+        double chem[6] = {0, 0, 0, 0, 0, 0}; // dt, bh00, albpow, colh0, temph0, abu_c
+        int src_begin = 0, src_count = 0;
+        RtParams rt;
+        // multi-GPU form of the loop (asora_evolve_begin_slab): this rank runs the fused pass on the planes it owns only
+        bool slab = false;
+        int own_begin = 0, own_count = 0;
+        bool slab_passed = false;           // the current iteration's pass has been enqueued (close comes next)
+        bool folded_all = false;            // ... and this iteration's has been enqueued
+        bool rates_in_outbox = false;       // asora_evolve_slab_fold_all: the passes of this step read the out-box and keep PHI_ION
+        bool slab_thermal = false;          // begun with asora_evolve_begin_slab_thermal: every slab call carries the heating rates too
+        bool plane_swept = false;           // the current iteration of a sharded step has had its plane-flux sweep (ahead of its first asora_evolve_slab_trace)
+    } evolve;
+    // temperature probe of the TEMP grid: valid for the upload and the constants in consts; clump: the clumping factor the probe
+    // folded into its brech0 (the constant in mode 1, else 1)
+    struct TempProbe {
+        ProcessBuffer<double> dev;          // [8]: the probe's five results, [5] = asora_grid_sum's
+        double values[5] = {0, 0, 0, 0, 0}; // host copy: uniform?, T, brech0, acolh0, t_ok
+        bool valid = false;                 // dies with the mesh
+        double consts[4] = {0, 0, 0, 0};
+        double clump = 1.0;
+    } temp_probe;
     // Which 64-byte lines of the rate accumulators the sources of the current step can touch at all (round 4): one byte per
     // line of 8 cells, [i][j][k >> 3] for the plain layout and, behind it, [k][j][i >> 3] for the transposed one.  The fused
     // pass neither reads nor zeroes the lines no source reaches (they are zero and stay zero): 32 of its 88 bytes per cell.
     // Valid for (source upload, source range, R); nullptr in the pass = every line is reachable.
     struct ReachMask {
-        unsigned char *mask = nullptr;
-        size_t bytes = 0;                   // of ONE layout
-        unsigned long long *count_dev = nullptr;
-        bool in_use = false;
-        bool pays = false;                  // enough lines out of reach for the mask to pay (counted when the mask is built)
-        struct Key {                        // what `pays` (and the mask, where one was built) has been decided for
-            bool valid = false;
-            long src_generation = -1;
-            int src_begin = 0, src_count = 0;
-            double R = -1.0;
-            bool operator==(const Key &o) const { return valid == o.valid && src_generation == o.src_generation && src_begin == o.src_begin && src_count == o.src_count && R == o.R; }
-        } key;
+        MeshBuffer<unsigned char> mask;     // both layouts, half each
+        MeshBuffer<unsigned long long> count_dev;
+        struct Decision {                   // dies with the mesh
+            bool in_use = false;
+            bool pays = false;              // enough lines out of reach for the mask to pay (counted when the mask is built)
+            struct Key {                    // what `pays` (and the mask, where one was built) has been decided for
+                bool valid = false;
+                long src_generation = -1;
+                int src_begin = 0, src_count = 0;
+                double R = -1.0;
+                bool operator==(const Key &o) const { return valid == o.valid && src_generation == o.src_generation && src_begin == o.src_begin && src_count == o.src_count && R == o.R; }
+            } key;
+        } d;
     } reach;
-    long src_generation = 0;                // counts asora_source_data_to_device calls
 
     // thermal mode (asora_thermal_params): TEMP_END and the heating accumulators of the device loop are allocated on first use
-    bool th_on = false;
-    ThermalConsts th;
-    double *heat_acc = nullptr;             // two pairs like `acc`, [i][j][k] then [k][j][i] each (4 N^3 doubles)
-    bool heat_clean[2] = {false, false};    // pair known to be all zero
-    double *heat_outbox = nullptr;          // thermal step across ranks: the heating planes to send / the summed heating (N^3 doubles,
+    struct Thermal {
+        struct Mode { bool on = false; ThermalConsts consts; bool heat_clean[2] = {false, false}; } mode;   // heat_clean: pair known to be all zero
+        MeshBuffer<double> heat_acc;        // two pairs like `acc`, [i][j][k] then [k][j][i] each (4 N^3 doubles)
+        MeshBuffer<double> heat_outbox;     // thermal step across ranks: the heating planes to send / the summed heating (N^3 doubles,
                                             // the twin of `staging`'s role as rate out-box; allocated by the first such step)
-    unsigned long long *th_stats_dev = nullptr;   // [3]: cells at max_substeps, cells floored, most substeps
+        MeshBuffer<unsigned long long> stats_dev;   // [3]: cells at max_substeps, cells floored, most substeps
+    } thermal;
 
-    // sub-grid clumping of the recombination rate (asora_clumping): 0 off, 1 one constant, 2 per cell (ASORA_GRID_CLUMP, allocated
-    // on first upload).  The launchers of the chemistry passes apply it (chemistry.hip); temp_probe_clump is the factor the
-    // uniform-temperature probe folded into its brech0 (the constant in mode 1, else 1)
-    int clump_mode = 0;
-    double clump_c = 1.0;
-    double temp_probe_clump = 1.0;
-
-    // Lyman-limit-system opacity (asora_lls_opacity): the raytrace's absorber density is
-    // ndens ((1 - xh_av) + lls_b) + lls_a, formed wherever nHI is (launch_prepare_nhi*, launch_prepare_range, the emit forms of
-    // the fused pass through chem_tile_common).  Both 0: off.  coldens_only: asora_debug_coldens has borrowed the grey form
-    double lls_a = 0.0, lls_b = 0.0;
-    bool coldens_only = false;
-
-    // plane-parallel flux through faces of the box (asora_plane_flux).  ev_plane_swept: the current
-    // iteration of a sharded step has had its sweep (ahead of its first asora_evolve_slab_trace)
-    PlaneFluxSet plane{};
-    bool ev_plane_swept = false;
+    // what the raytrace and the chemistry are told about the medium, until the mesh goes:
+    //  * sub-grid clumping of the recombination rate (asora_clumping): 0 off, 1 one constant, 2 per cell (ASORA_GRID_CLUMP).  The
+    //    launchers of the chemistry passes apply it (chemistry.hip)
+    //  * Lyman-limit-system opacity (asora_lls_opacity): the raytrace's absorber density is
+    //    ndens ((1 - xh_av) + lls_b) + lls_a, formed wherever nHI is (launch_prepare_nhi*, launch_prepare_range, the emit forms of
+    //    the fused pass through chem_tile_common).  Both 0: off
+    //  * plane-parallel flux through faces of the box (asora_plane_flux)
+    struct Medium { int clump_mode = 0; double clump_c = 1.0, lls_a = 0.0, lls_b = 0.0; PlaneFluxSet plane{}; } medium;
+    bool coldens_only = false;              // asora_debug_coldens has borrowed the grey form
 
     hipStream_t stream = nullptr;
     struct PendingTimer { int which; hipEvent_t e0, e1; };
@@ -424,16 +435,7 @@ struct State {
 };
 
 State &state();
-int fail(int code, const std::string &msg);   // records the message, returns code
 void clear_error();
-
-#define ASORA_HIP_TRY(expr)                                                                     \
-    do {                                                                                        \
-        hipError_t e__ = (expr);                                                                \
-        if (e__ != hipSuccess)                                                                  \
-            return ::asora::fail(10, std::string(#expr) + ": " + hipGetErrorName(e__) + " - " + \
-                                         hipGetErrorString(e__));                               \
-    } while (0)
 
 // Scoped HIP-event timer around kernel launches on the library stream.
 struct KernelTimer {
@@ -551,12 +553,12 @@ struct ChemParams {
     double *temp_end = nullptr;
     unsigned long long *th_stats = nullptr;
     ThermalConsts th;
-    // clumping (set by launch_chemistry from State::clump_mode; appended, so the fields above keep their offsets): the per-cell
+    // clumping (set by launch_chemistry from State::medium.clump_mode; appended, so the fields above keep their offsets): the per-cell
     // factors, or nullptr with the one factor clump_c (thermal form only: the isothermal constant scales bh00 instead)
     const double *clump = nullptr;
     double clump_c = 1.0;
 };
-// clumped = false: State::clump_mode is not applied (c2ray_global_pass, the reference's f2py boundary, has no clumping argument)
+// clumped = false: State::medium.clump_mode is not applied (c2ray_global_pass, the reference's f2py boundary, has no clumping argument)
 int launch_chemistry(State &st, ChemParams &p, hipStream_t stream, bool clumped = true);
 int chemistry_reduction_blocks(const State &st);
 
@@ -593,13 +595,13 @@ struct ChemTileParams {
     double *temp_end = nullptr;
     unsigned long long *th_stats = nullptr;
     ThermalConsts th;
-    // clumping: set by launch_chemistry_tiles from State::clump_mode, as ChemParams::clump / clump_c
+    // clumping: set by launch_chemistry_tiles from State::medium.clump_mode, as ChemParams::clump / clump_c
     const double *clump = nullptr;
     double clump_c = 1.0;
     // thermal form without fold (heating already summed over both layouts and over the ranks: the all-reduce loop): where the pass
     // keeps it, as phi_out keeps the rates (appended, so the fields above keep their offsets)
     double *heat_out = nullptr;
-    // emit: the Lyman-limit absorbers in the next trace's nHI (State::lls_a / lls_b, set by chem_tile_common)
+    // emit: the Lyman-limit absorbers in the next trace's nHI (State::medium.lls_a / lls_b, set by chem_tile_common)
     double lls_a = 0.0, lls_b = 0.0;
 };
 int launch_grid_sum(State &st, const double *a, size_t n, double *out_dev);
@@ -643,9 +645,9 @@ void fill_rt_params(RtParams &p, double R, double sig, double dr, double minlogt
 // the source list a trace works from: as uploaded, or its position-ordered copy -- positions, fluxes and table sets together
 inline void use_source_list(RtParams &p, const State &st, bool sorted)
 {
-    p.src_pos = sorted ? st.src_pos_sorted : st.src_pos;
-    p.src_flux = sorted ? st.src_flux_sorted : st.src_flux;
-    p.src_spec = sorted ? st.src_spec_sorted : st.src_spec;
+    p.src_pos = sorted ? st.sources.pos_sorted : st.sources.pos;
+    p.src_flux = sorted ? st.sources.flux_sorted : st.sources.flux;
+    p.src_spec = sorted ? st.sources.spec_sorted : st.sources.spec;
 }
 // code 4 while a source has a table set the device does not hold, or a set other than 0 under grey opacity (no tables)
 int check_source_spectra(const char *who);
@@ -657,18 +659,18 @@ int ensure_temp_probe(double bh00, double albpow, double colh0, double temph0);
 ChemTileParams chem_tile_common(int i_begin, int i_count, const double chem[6]);
 // bubble_mfp.hip: what asora_region_sizes (region_label.hip) shares with asora_bubble_mfp -- the argument checks of a thresholded
 // grid (codes 3 and 4), the feature's buffers, the threshold pass (and, with `scan`, the scan of the row counts)
-constexpr int BUBBLE_HOST_WORDS = 1024;         // uint64 words of State::bubble_host (pinned): a call's result words, its edges behind them
+constexpr int BUBBLE_HOST_WORDS = 1024;         // uint64 words of State::bubbles.host (pinned): a call's result words, its edges behind them
 int check_bubble_grid(const char *who, int which, double threshold, int phase);
 int ensure_bubble_buffers(State &st);
 int launch_bubble_mask(State &st, int which, double threshold, int phase, bool scan);
 // region_label.hip: what asora_topology (topology.hip) shares with asora_region_sizes -- the labelling's buffers, and the launches
-// that label the in-phase cells of a bit mask of the mesh (`mask`: the layout of State::bubble_mask, pad bits 0): afterwards
+// that label the in-phase cells of a bit mask of the mesh (`mask`: the layout of State::bubbles.mask, pad bits 0): afterwards
 // region_label holds every in-phase cell's root (the smallest index of its region; 0xFFFFFFFF out of phase) and region_volume every
 // root's volume (0 elsewhere)
 int ensure_region_buffers(State &st);
 int launch_region_label(State &st, const unsigned long long *mask, int periodic, int connectivity);
 // power_spectrum.hip: what asora_smooth_field (smooth_field.hip) shares with asora_power_spectrum -- which grids a kind reads, and
-// the forward transform of one field into State::ps_modes[0] (the mean density, the pass along k with the moments, along j, along i)
+// the forward transform of one field into State::spectrum.modes[0] (the mean density, the pass along k with the moments, along j, along i)
 bool ps_needs_grid(int kind, int grid, double t_gamma);
 int ps_forward(State &st, int kind, double scale, double t_gamma, const std::function<int()> &stage_done, const double **moments_dev);
 // the same stage by stage, for redshift_space.hip: the mean density alone, and the three passes with `x` read as the ionised fraction

@@ -268,17 +268,16 @@ static int bubble_ray_blocks(const State &st) { return st.cu_count * BM_BLOCKS_P
 
 int ensure_bubble_buffers(State &st)
 {
-    if (st.bubble_mask && st.bubble_rows && st.bubble_scan && st.bubble_partial && st.bubble_result && st.bubble_edges && st.bubble_host)
+    if (st.bubbles.mask && st.bubbles.rows && st.bubbles.scan && st.bubbles.partial && st.bubbles.result && st.bubbles.edges && st.bubbles.host)
         return 0;
     const size_t nrows = (size_t)st.N * st.N, W = ((size_t)st.N + 63) / 64;
-    if (!st.bubble_mask) ASORA_HIP_TRY(hipMalloc(&st.bubble_mask, sizeof(unsigned long long) * nrows * W));
-    if (!st.bubble_rows) ASORA_HIP_TRY(hipMalloc(&st.bubble_rows, sizeof(unsigned) * nrows));
-    if (!st.bubble_scan) ASORA_HIP_TRY(hipMalloc(&st.bubble_scan, sizeof(unsigned long long) * (nrows + 1)));
-    if (!st.bubble_partial) ASORA_HIP_TRY(hipMalloc(&st.bubble_partial, sizeof(double) * 2 * (size_t)bubble_ray_blocks(st)));
-    if (!st.bubble_result) ASORA_HIP_TRY(hipMalloc(&st.bubble_result, sizeof(unsigned long long) * BM_RESULT));
-    if (!st.bubble_edges) ASORA_HIP_TRY(hipMalloc(&st.bubble_edges, sizeof(double) * (ASORA_BUBBLE_MAX_BINS + 1)));
-    if (!st.bubble_host)
-        ASORA_HIP_TRY(hipHostMalloc(&st.bubble_host, sizeof(unsigned long long) * BUBBLE_HOST_WORDS, hipHostMallocDefault));
+    if (int rc = st.bubbles.mask.allocate(nrows * W)) return rc;
+    if (int rc = st.bubbles.rows.allocate(nrows)) return rc;
+    if (int rc = st.bubbles.scan.allocate((nrows + 1))) return rc;
+    if (int rc = st.bubbles.partial.allocate(2 * (size_t)bubble_ray_blocks(st))) return rc;
+    if (int rc = st.bubbles.result.allocate(BM_RESULT)) return rc;
+    if (int rc = st.bubbles.edges.allocate((ASORA_BUBBLE_MAX_BINS + 1))) return rc;
+    if (int rc = st.bubbles.host.allocate(BUBBLE_HOST_WORDS)) return rc;
     return 0;
 }
 
@@ -292,13 +291,13 @@ int launch_bubble_mask(State &st, int which, double threshold, int phase, bool s
         const size_t want = (nrows + BM_WAVES - 1) / BM_WAVES;
         const unsigned blocks = (unsigned)std::min<size_t>(want, (size_t)st.cu_count * 32);
         hipLaunchKernelGGL(bubble_mask_kernel, dim3(blocks), dim3(BM_THREADS), 0, st.stream, (const double *)st.grid[which], st.N, W,
-                           threshold, phase, st.bubble_mask, st.bubble_rows);
+                           threshold, phase, st.bubbles.mask, st.bubbles.rows);
         ASORA_HIP_TRY(hipGetLastError());
     }
     if (!scan) return 0;
     KernelTimer kt(ASORA_KERNEL_BUBBLE_SCAN);
-    hipLaunchKernelGGL(bubble_scan_kernel, dim3(1), dim3(BM_SCAN_THREADS), 0, st.stream, (const unsigned *)st.bubble_rows, nrows,
-                       st.bubble_scan);
+    hipLaunchKernelGGL(bubble_scan_kernel, dim3(1), dim3(BM_SCAN_THREADS), 0, st.stream, (const unsigned *)st.bubbles.rows, nrows,
+                       st.bubbles.scan);
     ASORA_HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -315,9 +314,8 @@ int check_bubble_grid(const char *who, int which, double threshold, int phase)
 
 // the per-ray record of a call on the device: freed when the call ends, however it ends
 struct BubbleRecord {
-    int32_t *start = nullptr, *status = nullptr;
-    double *dir = nullptr, *len = nullptr;
-    ~BubbleRecord() { (void)hipFree(start); (void)hipFree(status); (void)hipFree(dir); (void)hipFree(len); }
+    Scoped<int32_t> start, status;
+    Scoped<double> dir, len;
 };
 
 } // namespace asora
@@ -336,8 +334,8 @@ int asora_bubble_mask(int which_grid, double threshold, int phase, uint64_t *mas
     if (int rc = ensure_bubble_buffers(st)) return rc;
     if (int rc = launch_bubble_mask(st, which_grid, threshold, phase, false)) return rc;
     const size_t nrows = (size_t)st.N * st.N, W = ((size_t)st.N + 63) / 64;
-    ASORA_HIP_TRY(hipMemcpyAsync(mask_words, st.bubble_mask, sizeof(unsigned long long) * nrows * W, hipMemcpyDeviceToHost, st.stream));
-    ASORA_HIP_TRY(hipMemcpyAsync(row_counts, st.bubble_rows, sizeof(unsigned) * nrows, hipMemcpyDeviceToHost, st.stream));
+    ASORA_HIP_TRY(hipMemcpyAsync(mask_words, st.bubbles.mask, sizeof(unsigned long long) * nrows * W, hipMemcpyDeviceToHost, st.stream));
+    ASORA_HIP_TRY(hipMemcpyAsync(row_counts, st.bubbles.rows, sizeof(unsigned) * nrows, hipMemcpyDeviceToHost, st.stream));
     ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
     return 0;
 }
@@ -366,20 +364,20 @@ int asora_bubble_mfp(int which_grid, double threshold, int phase, int periodic, 
     const size_t rays = (size_t)n_rays;
     BubbleRecord rec;
     if (given && n_rays > 0) {
-        ASORA_HIP_TRY(hipMalloc(&rec.start, sizeof(int32_t) * 3 * rays));
-        ASORA_HIP_TRY(hipMalloc(&rec.dir, sizeof(double) * 3 * rays));
-        ASORA_HIP_TRY(hipMalloc(&rec.len, sizeof(double) * rays));
-        ASORA_HIP_TRY(hipMalloc(&rec.status, sizeof(int32_t) * rays));
+        if (int rc = rec.start.allocate(3 * rays)) return rc;
+        if (int rc = rec.dir.allocate(3 * rays)) return rc;
+        if (int rc = rec.len.allocate(rays)) return rc;
+        if (int rc = rec.status.allocate(rays)) return rc;
         // (a grid without an in-phase cell shoots no ray: the record then comes back as zeros)
         ASORA_HIP_TRY(hipMemsetAsync(rec.start, 0, sizeof(int32_t) * 3 * rays, st.stream));
         ASORA_HIP_TRY(hipMemsetAsync(rec.dir, 0, sizeof(double) * 3 * rays, st.stream));
         ASORA_HIP_TRY(hipMemsetAsync(rec.len, 0, sizeof(double) * rays, st.stream));
         ASORA_HIP_TRY(hipMemsetAsync(rec.status, 0, sizeof(int32_t) * rays, st.stream));
     }
-    double *edges_host = reinterpret_cast<double *>(st.bubble_host + BM_RESULT);
+    double *edges_host = reinterpret_cast<double *>(st.bubbles.host + BM_RESULT);
     for (int b = 0; b <= n_bins; ++b) edges_host[b] = edges[b];
-    ASORA_HIP_TRY(hipMemcpyAsync(st.bubble_edges, edges_host, sizeof(double) * (n_bins + 1), hipMemcpyHostToDevice, st.stream));
-    ASORA_HIP_TRY(hipMemsetAsync(st.bubble_result, 0, sizeof(unsigned long long) * BM_RESULT, st.stream));
+    ASORA_HIP_TRY(hipMemcpyAsync(st.bubbles.edges, edges_host, sizeof(double) * (n_bins + 1), hipMemcpyHostToDevice, st.stream));
+    ASORA_HIP_TRY(hipMemsetAsync(st.bubbles.result, 0, sizeof(unsigned long long) * BM_RESULT, st.stream));
     if (int rc = launch_bubble_mask(st, which_grid, threshold, phase, true)) return rc;
 
     const size_t nrows = (size_t)st.N * st.N;
@@ -389,8 +387,8 @@ int asora_bubble_mfp(int which_grid, double threshold, int phase, int periodic, 
         BubbleParams p;
         p.N = st.N; p.W = (st.N + 63) / 64; p.periodic = periodic != 0; p.nb = n_bins;
         p.seed = seed; p.n_rays = n_rays; p.l_max = l_max;
-        p.mask = st.bubble_mask; p.scan = st.bubble_scan; p.nrows = nrows; p.edges = st.bubble_edges;
-        p.result = st.bubble_result; p.partial = st.bubble_partial;
+        p.mask = st.bubbles.mask; p.scan = st.bubbles.scan; p.nrows = nrows; p.edges = st.bubbles.edges;
+        p.result = st.bubbles.result; p.partial = st.bubbles.partial;
         nblocks = (int)std::min<size_t>((rays + BM_THREADS - 1) / BM_THREADS, (size_t)bubble_ray_blocks(st));
         p.nblocks = nblocks;
         p.ray_start = rec.start; p.ray_dir = rec.dir; p.ray_len = rec.len; p.ray_status = rec.status;
@@ -399,11 +397,11 @@ int asora_bubble_mfp(int which_grid, double threshold, int phase, int periodic, 
     }
     {
         KernelTimer kt(ASORA_KERNEL_BUBBLE_RAYS);
-        hipLaunchKernelGGL(bubble_final_kernel, dim3(1), dim3(BM_THREADS), 0, st.stream, (const double *)st.bubble_partial, nblocks,
-                           (const unsigned long long *)st.bubble_scan, nrows, st.bubble_result);
+        hipLaunchKernelGGL(bubble_final_kernel, dim3(1), dim3(BM_THREADS), 0, st.stream, (const double *)st.bubbles.partial, nblocks,
+                           (const unsigned long long *)st.bubbles.scan, nrows, st.bubbles.result);
         ASORA_HIP_TRY(hipGetLastError());
     }
-    ASORA_HIP_TRY(hipMemcpyAsync(st.bubble_host, st.bubble_result, sizeof(unsigned long long) * BM_RESULT, hipMemcpyDeviceToHost, st.stream));
+    ASORA_HIP_TRY(hipMemcpyAsync(st.bubbles.host, st.bubbles.result, sizeof(unsigned long long) * BM_RESULT, hipMemcpyDeviceToHost, st.stream));
     if (given && n_rays > 0) {
         ASORA_HIP_TRY(hipMemcpyAsync(ray_start, rec.start, sizeof(int32_t) * 3 * rays, hipMemcpyDeviceToHost, st.stream));
         ASORA_HIP_TRY(hipMemcpyAsync(ray_dir, rec.dir, sizeof(double) * 3 * rays, hipMemcpyDeviceToHost, st.stream));
@@ -411,7 +409,7 @@ int asora_bubble_mfp(int which_grid, double threshold, int phase, int periodic, 
         ASORA_HIP_TRY(hipMemcpyAsync(ray_status, rec.status, sizeof(int32_t) * rays, hipMemcpyDeviceToHost, st.stream));
     }
     ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
-    const unsigned long long *h = st.bubble_host;
+    const unsigned long long *h = st.bubbles.host;
     for (int b = 0; b < n_bins; ++b) counts[b] = h[b];
     tallies[0] = h[BM_ENDED]; tallies[1] = h[BM_CAPPED]; tallies[2] = h[BM_LEFT]; tallies[3] = h[BM_UNDER]; tallies[4] = h[BM_OVER];
     tallies[5] = h[BM_SLOTS];

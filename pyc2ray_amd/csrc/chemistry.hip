@@ -615,7 +615,7 @@ int launch_grid_sum(State &st, const double *a, size_t n, double *out_dev)
 
 int chemistry_reduction_blocks(const State &st) { return st.cu_count * 8; }
 
-// Clumping (State::clump_mode, asora_clumping) is applied here, for every pass that comes through a launcher:
+// Clumping (State::medium.clump_mode, asora_clumping) is applied here, for every pass that comes through a launcher:
 //   mode 1, isothermal : bh00 -> C bh00, the unclumped kernel -- doric's own order, (C bh00) (T/1e4)^albpow (chemistry.f90:257)
 //   mode 2, isothermal : the CLUMP form, brech0 of the cell = c x bh00 (T/1e4)^albpow (the cached / probed factor times c)
 //   thermal, mode 1 / 2: the CLUMP form with the constant / the grid (recombination rate and recombination cooling x c)
@@ -623,15 +623,15 @@ int chemistry_reduction_blocks(const State &st) { return st.cu_count * 8; }
 static int clumping_of(const State &st, bool thermal, size_t ncell, const double *&clump, double &clump_c, double &bh00_factor)
 {
     clump = nullptr; clump_c = 1.0; bh00_factor = 1.0;
-    if (st.clump_mode == 0) return 0;
-    if (st.clump_mode == 2) {
+    if (st.medium.clump_mode == 0) return 0;
+    if (st.medium.clump_mode == 2) {
         if (!st.grid[ASORA_GRID_CLUMP] || !st.grid_valid[ASORA_GRID_CLUMP] || ncell != st.ncell)
             return fail(4, "chemistry: clumping mode 2 needs ASORA_GRID_CLUMP on the device");
         clump = st.grid[ASORA_GRID_CLUMP];
         return 1;
     }
-    if (!thermal) { bh00_factor = st.clump_c; return 0; }
-    clump_c = st.clump_c;
+    if (!thermal) { bh00_factor = st.medium.clump_c; return 0; }
+    clump_c = st.medium.clump_c;
     return 1;
 }
 
@@ -707,7 +707,7 @@ int launch_chemistry_tiles(State &st, ChemTileParams &p, hipStream_t stream)
     if (planes <= 0) return 0;
     const dim3 grid = tile_pass_grid(st, p.N, planes);
     const size_t blocks = (size_t)grid.x * grid.y * grid.z;
-    if (3 * blocks > st.red_cap) return fail(11, "chemistry: reduction buffer too small (internal error)");
+    if (3 * blocks > st.red_partial.count()) return fail(11, "chemistry: reduction buffer too small (internal error)");
     ChemTileParams q = p;
     q.red_stride = (int)blocks;
     double f;
@@ -715,7 +715,7 @@ int launch_chemistry_tiles(State &st, ChemTileParams &p, hipStream_t stream)
     if (ck > 1) return ck;
     q.bh00 = f * p.bh00;
     // the uniform-temperature forms take brech0 from the probe (chemistry_api.hip: ensure_temp_probe), which folds in the mode-1 constant
-    if (p.uniform && !p.thermal && st.temp_probe_clump != f)
+    if (p.uniform && !p.thermal && st.temp_probe.clump != f)
         return fail(4, "chemistry: the temperature probe was made for another clumping mode (set asora_clumping before asora_evolve_begin)");
     {
         KernelTimer kt(ASORA_KERNEL_CHEMISTRY, stream);

@@ -5,28 +5,18 @@
 
 namespace asora {
 
-// The two accumulator pairs (State::acc; State::heat_acc in thermal mode): pair `set` is 2 N^3 doubles, [i][j][k] then [k][j][i].
-// Iteration k of a step traces into pair (ev_base + k - 1) & 1, and its pass zeroes the other one.
+// The two accumulator pairs (State::acc; State::thermal.heat_acc in thermal mode): pair `set` is 2 N^3 doubles, [i][j][k] then [k][j][i].
+// Iteration k of a step traces into pair (evolve.base + k - 1) & 1, and its pass zeroes the other one.
 static double *acc_pair(int set) { return state().acc + (size_t)set * 2 * state().ncell; }
-static double *heat_pair(int set) { return state().heat_acc + (size_t)set * 2 * state().ncell; }
+static double *heat_pair(int set) { return state().thermal.heat_acc + (size_t)set * 2 * state().ncell; }
 
 static int ensure_heat_acc()
 {
     State &st = state();
-    if (st.heat_acc) return 0;
-    ASORA_HIP_TRY(hipMalloc(&st.heat_acc, 4 * st.ncell * sizeof(double)));
-    ASORA_HIP_TRY(hipMemsetAsync(st.heat_acc, 0, 4 * st.ncell * sizeof(double), st.stream));
-    st.heat_clean[0] = st.heat_clean[1] = true;
-    return 0;
-}
-
-// The heating out-box of a thermal step across ranks (asora_evolve_begin_slab_thermal): N^3 doubles like the rate out-box
-// (State::staging), allocated with the first such step
-static int ensure_heat_outbox()
-{
-    State &st = state();
-    if (st.heat_outbox) return 0;
-    ASORA_HIP_TRY(hipMalloc(&st.heat_outbox, st.ncell * sizeof(double)));
+    if (st.thermal.heat_acc) return 0;
+    if (int rc = st.thermal.heat_acc.allocate(4 * st.ncell)) return rc;
+    ASORA_HIP_TRY(hipMemsetAsync(st.thermal.heat_acc, 0, 4 * st.ncell * sizeof(double), st.stream));
+    st.thermal.mode.heat_clean[0] = st.thermal.mode.heat_clean[1] = true;
     return 0;
 }
 
@@ -39,16 +29,16 @@ static int zero_pairs_unless_clean(bool heating = false)
     const size_t pair_bytes = 2 * st.ncell * sizeof(double);
     if (heating) {
         for (int q = 0; q < 2; ++q)
-            if (!st.heat_clean[q]) {
+            if (!st.thermal.mode.heat_clean[q]) {
                 ASORA_HIP_TRY(hipMemsetAsync(heat_pair(q), 0, pair_bytes, st.stream));
-                st.heat_clean[q] = true;
+                st.thermal.mode.heat_clean[q] = true;
             }
         return 0;
     }
-    if (!st.ev_sets_known) { st.ev_clean[0] = st.ev_clean[1] = false; st.ev_sets_known = true; }
-    if (st.ev_clean[0] && st.ev_clean[1]) return 0;
+    if (!st.evolve.flags.sets_known) { st.evolve.flags.clean[0] = st.evolve.flags.clean[1] = false; st.evolve.flags.sets_known = true; }
+    if (st.evolve.flags.clean[0] && st.evolve.flags.clean[1]) return 0;
     ASORA_HIP_TRY(hipMemsetAsync(acc_pair(0), 0, 2 * pair_bytes, st.stream));
-    st.ev_clean[0] = st.ev_clean[1] = true;
+    st.evolve.flags.clean[0] = st.evolve.flags.clean[1] = true;
     return 0;
 }
 
@@ -59,16 +49,16 @@ static int zero_pairs_unless_clean(bool heating = false)
 // BASELINE configurations gains, sparse runs (few sources, small radii) do.  Whenever the set of lines the
 // passes zero changes, BOTH pairs are zeroed once: the dirty pair of the previous step may hold rates where the new
 // sources do not reach.  Not for traces that cover (nearly) the whole box, nor with ASORA_REACH_MASK=0 (2: whenever built).
-// Leaves State::reach.in_use set for the step (one GPU; a sharded step uses no mask).
+// Leaves State::reach.d.in_use set for the step (one GPU; a sharded step uses no mask).
 // faces: the step has plane-parallel fluxes (asora_plane_flux), which reach every line -- no mask; going from a mask to none
 // zeroes both pairs like any other change of the set of lines.
 static int decide_reach_mask(int src_begin, int src_count, double R, bool faces)
 {
     State &st = state();
-    State::ReachMask &rm = st.reach;
+    State::ReachMask::Decision &rm = st.reach.d;
     static const int mode = []() { const char *v = getenv("ASORA_REACH_MASK"); return v ? atoi(v) : 1; }();
     const bool possible = !faces && mode != 0 && std::isfinite(R) && 2.0 * R + 2.0 < (double)st.N && st.opt[ASORA_OPT_Z_TRANSPOSED] != 0;
-    const State::ReachMask::Key now{true, st.src_generation, src_begin, src_count, R};
+    const State::ReachMask::Decision::Key now{true, st.src_generation, src_begin, src_count, R};
     const bool same = rm.key == now;
     // where the spheres together hold more cells than the box, (nearly) every line is reached: the mask can not pay and is
     // not built (in a cosmological run R changes every step, and every build ends with a blocking read-back)
@@ -78,12 +68,12 @@ static int decide_reach_mask(int src_begin, int src_count, double R, bool faces)
         if (covers) rm.pays = false;
         else {
             const size_t one = (size_t)st.N * st.N * ((st.N + 7) / 8);
-            if (!rm.mask) { ASORA_HIP_TRY(hipMalloc(&rm.mask, 2 * one)); rm.bytes = one; }
-            if (!rm.count_dev) ASORA_HIP_TRY(hipMalloc(&rm.count_dev, sizeof(unsigned long long)));
-            if (int rc = launch_reach_mask(st, st.src_pos, src_begin, src_count, R, rm.mask, one)) return rc;
-            if (int rc = launch_reach_count(st, rm.mask, 2 * one, rm.count_dev)) return rc;
+            if (int rc = st.reach.mask.allocate(2 * one)) return rc;
+            if (int rc = st.reach.count_dev.allocate(1)) return rc;
+            if (int rc = launch_reach_mask(st, st.sources.pos, src_begin, src_count, R, st.reach.mask, one)) return rc;
+            if (int rc = launch_reach_count(st, st.reach.mask, 2 * one, st.reach.count_dev)) return rc;
             unsigned long long marked = 0;
-            ASORA_HIP_TRY(hipMemcpyAsync(&marked, rm.count_dev, sizeof marked, hipMemcpyDeviceToHost, st.stream));
+            ASORA_HIP_TRY(hipMemcpyAsync(&marked, st.reach.count_dev, sizeof marked, hipMemcpyDeviceToHost, st.stream));
             ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
             rm.pays = (double)marked <= 0.55 * (double)(2 * one);
         }
@@ -103,12 +93,12 @@ static int decide_reach_mask(int src_begin, int src_count, double R, bool faces)
 static ChemTileParams evolve_pass_params(int i_begin, int i_count, int set)
 {
     State &st = state();
-    ChemTileParams c = chem_tile_common(i_begin, i_count, st.ev_chem);
-    c.xh_av_in = st.ev_first ? st.grid[ASORA_GRID_XH] : st.grid[ASORA_GRID_XH_AV];
+    ChemTileParams c = chem_tile_common(i_begin, i_count, st.evolve.chem);
+    c.xh_av_in = st.evolve.first ? st.grid[ASORA_GRID_XH] : st.grid[ASORA_GRID_XH_AV];
     c.gamma = acc_pair(set); c.gamma_t = c.gamma + st.ncell;
     c.zero_a = acc_pair(set ^ 1); c.zero_t = c.zero_a + st.ncell;
     c.nhi = st.nhi; c.nhi_t = st.nhi_t;
-    c.status = st.ev_status;
+    c.status = st.evolve.status;
     c.fold = true; c.emit = true;
     return c;
 }
@@ -118,10 +108,10 @@ static ChemTileParams evolve_pass_params(int i_begin, int i_count, int set)
 static void evolve_pass_thermal(ChemTileParams &c, int set)
 {
     State &st = state();
-    c.thermal = true; c.uniform = 0; c.th = st.th;
+    c.thermal = true; c.uniform = 0; c.th = st.thermal.mode.consts;
     c.heat = heat_pair(set); c.heat_t = c.heat + st.ncell;
     c.zero_ha = heat_pair(set ^ 1); c.zero_ht = c.zero_ha + st.ncell;
-    c.temp_end = st.grid[ASORA_GRID_TEMP_END]; c.th_stats = st.th_stats_dev;
+    c.temp_end = st.grid[ASORA_GRID_TEMP_END]; c.th_stats = st.thermal.stats_dev;
 }
 
 } // namespace asora
@@ -142,14 +132,14 @@ static int evolve_begin_impl(double dt, double bh00, double albpow, double colh0
     clear_error();
     if (int rc = require_init("evolve_begin")) return rc;
     State &st = state();
-    st.ev_open = false;
+    st.evolve.flags.open = false;
     // 1. what the step needs
-    if (slab && st.th_on && !slab_thermal)
+    if (slab && st.thermal.mode.on && !slab_thermal)
         return fail(4, "evolve_begin_slab: thermal mode is on, and this entry begins an isothermal step (single-GPU thermal loop: "
                        "asora_evolve_begin; across ranks, with the heating rates exchanged as well: asora_evolve_begin_slab_thermal)");
-    if (slab_thermal && (!st.have_heat_tables || st.opt[ASORA_OPT_GREY_NOTABLES]))
+    if (slab_thermal && (!st.sources.loaded.heat_tables || st.opt[ASORA_OPT_GREY_NOTABLES]))
         return fail(4, "evolve_begin_slab_thermal: needs heating tables on the device (heat_table_to_device)");
-    if (slab_thermal && !st.th_on)
+    if (slab_thermal && !st.thermal.mode.on)
         return fail(4, "evolve_begin_slab_thermal: needs the thermal mode (asora_thermal_params(1, ...) first)");
     if (slab) {
         if (int rc = check_planes("evolve_begin_slab", 4, "bad range of own planes", own_begin, own_count)) return rc;
@@ -157,21 +147,22 @@ static int evolve_begin_impl(double dt, double bh00, double albpow, double colh0
     }
     if (int rc = require_grids("evolve_begin", {ASORA_GRID_NDENS, ASORA_GRID_TEMP, ASORA_GRID_XH})) return rc;
     if (int rc = require_raytrace_inputs("evolve_begin", R, NumTau, false, false)) return rc;
-    if (int rc = check_sources("evolve_begin", 4, "source range outside the " + std::to_string(st.num_src) + " uploaded sources", src_begin, src_count)) return rc;
+    if (int rc = check_sources("evolve_begin", 4, "source range outside the " + std::to_string(st.sources.loaded.num) + " uploaded sources", src_begin, src_count)) return rc;
     if (st.opt[ASORA_OPT_HEATING]) return fail(4, "evolve_begin: the fused loop carries no heating rates (use raytrace_device)");
-    if (st.th_on) {
-        if (!st.have_heat_tables || st.opt[ASORA_OPT_GREY_NOTABLES])
+    if (st.thermal.mode.on) {
+        if (!st.sources.loaded.heat_tables || st.opt[ASORA_OPT_GREY_NOTABLES])
             return fail(4, "evolve_begin: thermal mode needs heating tables on the device (heat_table_to_device)");
         if (!st.opt[ASORA_OPT_Z_TRANSPOSED]) return fail(4, "evolve_begin: thermal mode needs the [k][j][i] twins (ASORA_OPT_Z_TRANSPOSED = 1)");
         if (int rc = ensure_optional_grid(ASORA_GRID_PHI_HEAT)) return rc;
         if (int rc = ensure_optional_grid(ASORA_GRID_TEMP_END)) return rc;
         if (int rc = ensure_heat_acc()) return rc;
-        if (slab) { if (int rc = ensure_heat_outbox()) return rc; }
+        // the heating out-box of a thermal step across ranks: N^3 doubles like the rate out-box (State::staging), with the first such step
+        if (slab) { if (int rc = st.thermal.heat_outbox.allocate(st.ncell)) return rc; }
     }
-    if (int rc = check_plane_flux(st, st.plane, "evolve_begin", false, st.th_on)) return rc;
+    if (int rc = check_plane_flux(st, st.medium.plane, "evolve_begin", false, st.thermal.mode.on)) return rc;
     // a face's sweep rates every plane, and a step that owns only some of them folds out, sends and zeroes only the planes its
     // sources reach: the rates on the other foreign planes would never arrive and would pile up from iteration to iteration
-    if (slab && st.plane.count > 0 && !(own_begin == 0 && own_count == st.N))
+    if (slab && st.medium.plane.count > 0 && !(own_begin == 0 && own_count == st.N))
         return fail(4, "evolve_begin_slab: a plane-parallel flux (asora_plane_flux) needs a step that owns every plane (the full-grid "
                        "exchange, asora_evolve_slab_fold_all): the slab exchange does not deliver a whole-box sweep");
     if (int rc = ensure_temp_probe(bh00, albpow, colh0, temph0)) return rc;
@@ -181,53 +172,51 @@ static int evolve_begin_impl(double dt, double bh00, double albpow, double colh0
     // multi-GPU: the pass sweeps the own planes only and the out-box folds zero the foreign ones (asora_evolve_slab_fold_out);
     // which planes those are changes with the plan, so a step simply starts from two zeroed pairs (256 MiB of stores at
     // 256^3, once per time step), and no reach mask
-    if (!st.ev_sets_known || slab)
+    if (!st.evolve.flags.sets_known || slab)
         if (int rc = zero_pairs_unless_clean()) return rc;
-    if (slab) st.reach.in_use = false;
-    else if (int rc = decide_reach_mask(src_begin, src_count, R, st.plane.count > 0)) return rc;
+    if (slab) st.reach.d.in_use = false;
+    else if (int rc = decide_reach_mask(src_begin, src_count, R, st.medium.plane.count > 0)) return rc;
 
     // 3. the accumulators and the status block of the step
-    if (!st.ev_clean[0] && !st.ev_clean[1]) return fail(11, "evolve_begin: no clean accumulator pair (internal error)");
-    st.ev_base = st.ev_clean[0] ? 0 : 1;
-    if (st.th_on) {
+    if (!st.evolve.flags.clean[0] && !st.evolve.flags.clean[1]) return fail(11, "evolve_begin: no clean accumulator pair (internal error)");
+    st.evolve.base = st.evolve.flags.clean[0] ? 0 : 1;
+    if (st.thermal.mode.on) {
         // the heating pairs start every thermal step all zero (the pass zeroes only the lines the step's sources reach)
         if (int rc = zero_pairs_unless_clean(true)) return rc;
-        ASORA_HIP_TRY(hipMemsetAsync(st.th_stats_dev, 0, 3 * sizeof(unsigned long long), st.stream));
+        ASORA_HIP_TRY(hipMemsetAsync(st.thermal.stats_dev, 0, 3 * sizeof(unsigned long long), st.stream));
     }
-    st.ev_folded_iter = 0;
-    if (!st.ev_status) {
-        ASORA_HIP_TRY(hipMalloc(&st.ev_status, sizeof(EvolveStatus)));
-        ASORA_HIP_TRY(hipHostMalloc(&st.ev_host, sizeof(EvolveStatus), hipHostMallocDefault));
-    }
-    ASORA_HIP_TRY(hipStreamSynchronize(st.stream));            // ev_host may still be the target of an earlier poll
-    std::memset(st.ev_host, 0, sizeof(EvolveStatus));
-    st.ev_host->prev1 = 2.0 * (double)st.ncell;                // evolve.py:130-131
-    st.ev_host->prev0 = 2.0 * (double)st.ncell;
-    st.ev_host->conv_criterion = conv_criterion;
-    st.ev_host->conv_fraction = convergence_fraction;
-    ASORA_HIP_TRY(hipMemcpyAsync(st.ev_status, st.ev_host, sizeof(EvolveStatus), hipMemcpyHostToDevice, st.stream));
+    st.evolve.folded_iter = 0;
+    if (int rc = st.evolve.status.allocate(1)) return rc;
+    if (int rc = st.evolve.host.allocate(1)) return rc;
+    ASORA_HIP_TRY(hipStreamSynchronize(st.stream));            // evolve.host may still be the target of an earlier poll
+    std::memset(st.evolve.host, 0, sizeof(EvolveStatus));
+    st.evolve.host->prev1 = 2.0 * (double)st.ncell;                // evolve.py:130-131
+    st.evolve.host->prev0 = 2.0 * (double)st.ncell;
+    st.evolve.host->conv_criterion = conv_criterion;
+    st.evolve.host->conv_fraction = convergence_fraction;
+    ASORA_HIP_TRY(hipMemcpyAsync(st.evolve.status, st.evolve.host, sizeof(EvolveStatus), hipMemcpyHostToDevice, st.stream));
     if (int rc = reset_counters()) return rc;
     // xh_av = copy(xh) (evolve.py:136) is not materialised: nHI of the first trace is formed from xh and the first
     // chemistry pass takes xh as its starting xh_av; xh_intermed (evolve.py:137) is only ever written
     if (int rc = launch_prepare_nhi_from(st, st.grid[ASORA_GRID_XH], st.opt[ASORA_OPT_Z_TRANSPOSED] != 0)) return rc;
 
     // 4. the step's parameters
-    fill_rt_params(st.ev_rt, R, sig, dr, minlogtau, dlogtau, NumTau);
-    st.ev_rt.phi = acc_pair(st.ev_base);       // (each iteration sets its own pair, asora_evolve_enqueue)
-    st.ev_rt.done_flag = &st.ev_status->done;
-    st.ev_rt.src_begin = src_begin; st.ev_rt.src_count = src_count; st.ev_rt.shape_src_count = src_count;
-    if (src_begin == 0 && src_count == st.num_src && st.src_pos_sorted) use_source_list(st.ev_rt, st, true);
-    st.ev_src_begin = src_begin; st.ev_src_count = src_count;
-    st.ev_chem[0] = dt; st.ev_chem[1] = bh00; st.ev_chem[2] = albpow; st.ev_chem[3] = colh0; st.ev_chem[4] = temph0;
-    st.ev_chem[5] = abu_c;
-    st.ev_first = true;
-    st.ev_reported = 0;
-    st.ev_enqueued = 0;
-    st.ev_slab = slab; st.ev_own_begin = own_begin; st.ev_own_count = own_count; st.ev_slab_passed = false;
-    st.ev_slab_thermal = slab && st.th_on;
-    st.ev_rates_in_outbox = false; st.ev_folded_all = false;
-    st.ev_plane_swept = false;
-    st.ev_open = true;
+    fill_rt_params(st.evolve.rt, R, sig, dr, minlogtau, dlogtau, NumTau);
+    st.evolve.rt.phi = acc_pair(st.evolve.base);       // (each iteration sets its own pair, asora_evolve_enqueue)
+    st.evolve.rt.done_flag = &st.evolve.status->done;
+    st.evolve.rt.src_begin = src_begin; st.evolve.rt.src_count = src_count; st.evolve.rt.shape_src_count = src_count;
+    if (src_begin == 0 && src_count == st.sources.loaded.num && st.sources.pos_sorted) use_source_list(st.evolve.rt, st, true);
+    st.evolve.src_begin = src_begin; st.evolve.src_count = src_count;
+    st.evolve.chem[0] = dt; st.evolve.chem[1] = bh00; st.evolve.chem[2] = albpow; st.evolve.chem[3] = colh0; st.evolve.chem[4] = temph0;
+    st.evolve.chem[5] = abu_c;
+    st.evolve.first = true;
+    st.evolve.reported = 0;
+    st.evolve.enqueued = 0;
+    st.evolve.slab = slab; st.evolve.own_begin = own_begin; st.evolve.own_count = own_count; st.evolve.slab_passed = false;
+    st.evolve.slab_thermal = slab && st.thermal.mode.on;
+    st.evolve.rates_in_outbox = false; st.evolve.folded_all = false;
+    st.evolve.plane_swept = false;
+    st.evolve.flags.open = true;
     return 0;
 }
 
@@ -276,19 +265,19 @@ int asora_evolve_begin_slab_thermal(double dt, double bh00, double albpow, doubl
 static int require_slab(const char *who)
 {
     if (int rc = require_init(who)) return rc;
-    if (!state().ev_open || !state().ev_slab)
+    if (!state().evolve.flags.open || !state().evolve.slab)
         return fail(4, std::string(who) + ": no multi-GPU evolve step in progress (call asora_evolve_begin_slab)");
-    if (state().ev_enqueued - state().ev_reported + 1 > EVOLVE_HIST)
+    if (state().evolve.enqueued - state().evolve.reported + 1 > EVOLVE_HIST)
         return fail(4, std::string(who) + ": " + std::to_string(EVOLVE_HIST) + " iterations enqueued since the last asora_evolve_poll (poll first)");
     return 0;
 }
-static int slab_set() { return (state().ev_base + state().ev_enqueued) & 1; }     // the pair the current iteration traces into
+static int slab_set() { return (state().evolve.base + state().evolve.enqueued) & 1; }     // the pair the current iteration traces into
 static double *slab_pair(int which) { return acc_pair(slab_set() ^ which); }     // 0: that pair, 1: the other one
 static double *slab_heat_pair(int which) { return heat_pair(slab_set() ^ which); }
 static int require_slab_thermal(const char *who)
 {
     if (int rc = require_slab(who)) return rc;
-    if (!state().ev_slab_thermal)
+    if (!state().evolve.slab_thermal)
         return fail(4, std::string(who) + ": the step carries no heating rates (begin it with asora_evolve_begin_slab_thermal)");
     return 0;
 }
@@ -298,27 +287,27 @@ int asora_evolve_slab_trace(int src_begin, int src_count)
     clear_error();
     if (int rc = require_slab("evolve_slab_trace")) return rc;
     State &st = state();
-    if (st.ev_slab_passed) return fail(4, "evolve_slab_trace: the iteration's pass has been enqueued already (close it first)");
-    if (src_begin < st.ev_src_begin || src_count < 0 || src_begin + src_count > st.ev_src_begin + st.ev_src_count)
+    if (st.evolve.slab_passed) return fail(4, "evolve_slab_trace: the iteration's pass has been enqueued already (close it first)");
+    if (src_begin < st.evolve.src_begin || src_count < 0 || src_begin + src_count > st.evolve.src_begin + st.evolve.src_count)
         return fail(4, "evolve_slab_trace: source range outside the step's sources");
-    if (st.ev_rt.plane.count > 0 && !st.ev_plane_swept) {      // the faces' sweeps: once per iteration, ahead of its first trace
-        st.ev_sets_known = false;
-        if (st.ev_slab_thermal) st.heat_clean[0] = st.heat_clean[1] = false;
-        if (int rc = launch_plane_flux(st, st.ev_rt, slab_pair(0), st.ev_slab_thermal ? slab_heat_pair(0) : nullptr, st.ev_slab_thermal,
-                                       &st.ev_status->done)) return rc;
-        st.ev_plane_swept = true;
+    if (st.evolve.rt.plane.count > 0 && !st.evolve.plane_swept) {      // the faces' sweeps: once per iteration, ahead of its first trace
+        st.evolve.flags.sets_known = false;
+        if (st.evolve.slab_thermal) st.thermal.mode.heat_clean[0] = st.thermal.mode.heat_clean[1] = false;
+        if (int rc = launch_plane_flux(st, st.evolve.rt, slab_pair(0), st.evolve.slab_thermal ? slab_heat_pair(0) : nullptr, st.evolve.slab_thermal,
+                                       &st.evolve.status->done)) return rc;
+        st.evolve.plane_swept = true;
     }
     if (src_count == 0) return 0;
-    st.ev_sets_known = false;
-    RtParams p = st.ev_rt;
+    st.evolve.flags.sets_known = false;
+    RtParams p = st.evolve.rt;
     p.phi = slab_pair(0);
     p.src_begin = src_begin; p.src_count = src_count;          // (shape_src_count stays the rank's whole share: one launch shape)
-    if (!(src_begin == 0 && src_count == st.num_src)) use_source_list(p, st, false);
-    if (st.ev_slab_thermal) {                 // the HEAT forms, into the iteration's heating pair
+    if (!(src_begin == 0 && src_count == st.sources.loaded.num)) use_source_list(p, st, false);
+    if (st.evolve.slab_thermal) {                 // the HEAT forms, into the iteration's heating pair
         p.heat = slab_heat_pair(0);
-        st.heat_clean[0] = st.heat_clean[1] = false;
+        st.thermal.mode.heat_clean[0] = st.thermal.mode.heat_clean[1] = false;
     }
-    return launch_raytrace(st, p, false, st.ev_slab_thermal);
+    return launch_raytrace(st, p, false, st.evolve.slab_thermal);
 }
 
 int asora_evolve_slab_fold_out(int i_begin, int i_count)
@@ -327,16 +316,16 @@ int asora_evolve_slab_fold_out(int i_begin, int i_count)
     if (int rc = require_slab("evolve_slab_fold_out")) return rc;
     State &st = state();
     if (int rc = check_planes("evolve_slab_fold_out", 4, "bad plane range", i_begin, i_count)) return rc;
-    if (i_count > 0 && i_begin < st.ev_own_begin + st.ev_own_count && st.ev_own_begin < i_begin + i_count)
+    if (i_count > 0 && i_begin < st.evolve.own_begin + st.evolve.own_count && st.evolve.own_begin < i_begin + i_count)
         return fail(4, "evolve_slab_fold_out: the range holds planes this rank owns (their rates stay: the pass folds them)");
-    st.ev_sets_known = false;
+    st.evolve.flags.sets_known = false;
     double *cur = slab_pair(0), *nxt = slab_pair(1);
-    if (st.ev_slab_thermal) {                 // both fields in one launch
+    if (st.evolve.slab_thermal) {                 // both fields in one launch
         double *hcur = slab_heat_pair(0), *hnxt = slab_heat_pair(1);
-        return launch_fold_out_pair(st, cur, cur + st.ncell, st.staging, nxt, nxt + st.ncell, hcur, hcur + st.ncell, st.heat_outbox,
-                                    hnxt, hnxt + st.ncell, i_begin, i_count, &st.ev_status->done);
+        return launch_fold_out_pair(st, cur, cur + st.ncell, st.staging, nxt, nxt + st.ncell, hcur, hcur + st.ncell, st.thermal.heat_outbox,
+                                    hnxt, hnxt + st.ncell, i_begin, i_count, &st.evolve.status->done);
     }
-    return launch_fold_out(st, cur, cur + st.ncell, st.staging, nxt, nxt + st.ncell, i_begin, i_count, &st.ev_status->done);
+    return launch_fold_out(st, cur, cur + st.ncell, st.staging, nxt, nxt + st.ncell, i_begin, i_count, &st.evolve.status->done);
 }
 
 // The full-grid exchange (pyc2ray/evolve.py:433-437: every rank all-reduces the rate grid) on the same loop: ALL planes folded
@@ -348,24 +337,24 @@ int asora_evolve_slab_fold_all(void)
     clear_error();
     if (int rc = require_slab("evolve_slab_fold_all")) return rc;
     State &st = state();
-    if (st.ev_slab_passed) return fail(4, "evolve_slab_fold_all: the iteration's pass has been enqueued already");
-    if (st.ev_own_begin != 0 || st.ev_own_count != st.N)
+    if (st.evolve.slab_passed) return fail(4, "evolve_slab_fold_all: the iteration's pass has been enqueued already");
+    if (st.evolve.own_begin != 0 || st.evolve.own_count != st.N)
         return fail(4, "evolve_slab_fold_all: the step must own every plane (asora_evolve_begin_slab(..., 0, N)): the chemistry is replicated");
-    st.ev_sets_known = false;
-    st.ev_rates_in_outbox = true; st.ev_folded_all = true;
+    st.evolve.flags.sets_known = false;
+    st.evolve.rates_in_outbox = true; st.evolve.folded_all = true;
     double *cur = slab_pair(0), *nxt = slab_pair(1);
     // (the pass zeroes the other pair's [i][j][k] layout as it goes; the transposed layout is zeroed here)
-    if (st.ev_slab_thermal) {
+    if (st.evolve.slab_thermal) {
         double *hcur = slab_heat_pair(0), *hnxt = slab_heat_pair(1);
-        return launch_fold_out_pair(st, cur, cur + st.ncell, st.staging, nullptr, nxt + st.ncell, hcur, hcur + st.ncell, st.heat_outbox,
-                                    nullptr, hnxt + st.ncell, 0, st.N, &st.ev_status->done);
+        return launch_fold_out_pair(st, cur, cur + st.ncell, st.staging, nullptr, nxt + st.ncell, hcur, hcur + st.ncell, st.thermal.heat_outbox,
+                                    nullptr, hnxt + st.ncell, 0, st.N, &st.evolve.status->done);
     }
-    return launch_fold_out(st, cur, cur + st.ncell, st.staging, nullptr, nxt + st.ncell, 0, st.N, &st.ev_status->done);
+    return launch_fold_out(st, cur, cur + st.ncell, st.staging, nullptr, nxt + st.ncell, 0, st.N, &st.evolve.status->done);
 }
 
 void *asora_evolve_slab_outbox(void) { return state().init ? (void *)state().staging : nullptr; }
 // (nullptr until a thermal step across ranks has been begun: the heating out-box is allocated then)
-void *asora_evolve_slab_heat_outbox(void) { return state().init ? (void *)state().heat_outbox : nullptr; }
+void *asora_evolve_slab_heat_outbox(void) { return state().init ? (void *)state().thermal.heat_outbox : nullptr; }
 
 // planes [i_begin, i_begin + i_count) of an out-box (`box`: the rate out-box, or the heating out-box) from / to the host
 static int outbox_copy(const char *who, double *box, int i_begin, int i_count, double *host, bool to_host)
@@ -396,12 +385,12 @@ int asora_evolve_slab_outbox_to_host(int i_begin, int i_count, double *host)
 
 int asora_evolve_slab_heat_outbox_from_host(int i_begin, int i_count, const double *host)
 {
-    return outbox_copy("evolve_slab_heat_outbox_from_host", state().heat_outbox, i_begin, i_count, const_cast<double *>(host), false);
+    return outbox_copy("evolve_slab_heat_outbox_from_host", state().thermal.heat_outbox, i_begin, i_count, const_cast<double *>(host), false);
 }
 
 int asora_evolve_slab_heat_outbox_to_host(int i_begin, int i_count, double *host)
 {
-    return outbox_copy("evolve_slab_heat_outbox_to_host", state().heat_outbox, i_begin, i_count, host, true);
+    return outbox_copy("evolve_slab_heat_outbox_to_host", state().thermal.heat_outbox, i_begin, i_count, host, true);
 }
 
 // planes received from another rank added on the own planes of the iteration's pair: heating = false the rates, true the heating
@@ -411,13 +400,13 @@ static int slab_add(const char *who, bool heating, int i_begin, int i_count, con
     if (int rc = heating ? require_slab_thermal(who) : require_slab(who)) return rc;
     State &st = state();
     if (i_begin < 0 || i_count < 0 || i_begin + i_count > st.N || (i_count > 0 && !dev_planes)) return fail(4, std::string(who) + ": bad arguments");
-    if (st.ev_slab_passed) return fail(4, std::string(who) + ": the iteration's pass has been enqueued already");
-    if (i_count > 0 && (i_begin < st.ev_own_begin || i_begin + i_count > st.ev_own_begin + st.ev_own_count))
+    if (st.evolve.slab_passed) return fail(4, std::string(who) + ": the iteration's pass has been enqueued already");
+    if (i_count > 0 && (i_begin < st.evolve.own_begin || i_begin + i_count > st.evolve.own_begin + st.evolve.own_count))
         return fail(4, std::string(who) + ": rates received for planes this rank does not own");
-    st.ev_sets_known = false;
+    st.evolve.flags.sets_known = false;
     const size_t plane = (size_t)st.N * st.N;
     double *pair = heating ? slab_heat_pair(0) : slab_pair(0);
-    return launch_add_planes(st, pair + (size_t)i_begin * plane, dev_planes, (size_t)i_count * plane, &st.ev_status->done);
+    return launch_add_planes(st, pair + (size_t)i_begin * plane, dev_planes, (size_t)i_count * plane, &st.evolve.status->done);
 }
 
 static int slab_add_host(const char *who, bool heating, int i_begin, int i_count, const double *host_planes)
@@ -429,7 +418,7 @@ static int slab_add_host(const char *who, bool heating, int i_begin, int i_count
     if (i_count == 0) return 0;
     // through the out-box: what is added belongs to planes this rank owns, what the out-box holds to planes it does not
     const size_t plane = (size_t)st.N * st.N;
-    double *tmp = (heating ? st.heat_outbox : st.staging) + (size_t)i_begin * plane;
+    double *tmp = (heating ? st.thermal.heat_outbox : st.staging) + (size_t)i_begin * plane;
     ASORA_HIP_TRY(hipMemcpyAsync(tmp, host_planes, (size_t)i_count * plane * sizeof(double), hipMemcpyHostToDevice, st.stream));
     ASORA_HIP_TRY(hipStreamSynchronize(st.stream));              // (the host buffer may be pageable)
     return slab_add(who, heating, i_begin, i_count, tmp);
@@ -460,30 +449,30 @@ int asora_evolve_slab_pass(void)
     clear_error();
     if (int rc = require_slab("evolve_slab_pass")) return rc;
     State &st = state();
-    if (st.ev_slab_passed) return fail(4, "evolve_slab_pass: already enqueued for this iteration");
-    if (st.ev_rates_in_outbox && !st.ev_folded_all)
+    if (st.evolve.slab_passed) return fail(4, "evolve_slab_pass: already enqueued for this iteration");
+    if (st.evolve.rates_in_outbox && !st.evolve.folded_all)
         return fail(4, "evolve_slab_pass: this step exchanges whole grids (asora_evolve_slab_fold_all), and this iteration's fold has not been enqueued");
-    st.ev_sets_known = false;
-    st.ev_slab_passed = true;
+    st.evolve.flags.sets_known = false;
+    st.evolve.slab_passed = true;
     st.grid_valid[ASORA_GRID_XH_AV] = st.grid_valid[ASORA_GRID_XH_INTERMED] = true;
     st.grid_valid[ASORA_GRID_PHI_ION] = false;
-    if (st.ev_slab_thermal) {
-        st.heat_clean[0] = st.heat_clean[1] = false;     // until the poll tells which pair the last iteration used
+    if (st.evolve.slab_thermal) {
+        st.thermal.mode.heat_clean[0] = st.thermal.mode.heat_clean[1] = false;     // until the poll tells which pair the last iteration used
         st.grid_valid[ASORA_GRID_TEMP_END] = true;
         st.grid_valid[ASORA_GRID_PHI_HEAT] = false;
     }
-    if (st.ev_own_count == 0) {           // nothing to own (more ranks than planes): this rank's share of the sums is zero
+    if (st.evolve.own_count == 0) {           // nothing to own (more ranks than planes): this rank's share of the sums is zero
         ASORA_HIP_TRY(hipMemsetAsync(st.red_final, 0, sizeof(double) * 3, st.stream));
         return 0;
     }
-    if (int rc = ensure_red_capacity(3 * chemistry_tile_blocks(st, st.N, st.ev_own_count))) return rc;    // (sized for every range at init)
-    ChemTileParams c = evolve_pass_params(st.ev_own_begin, st.ev_own_count, slab_set());
+    if (int rc = ensure_red_capacity(3 * chemistry_tile_blocks(st, st.N, st.evolve.own_count))) return rc;    // (sized for every range at init)
+    ChemTileParams c = evolve_pass_params(st.evolve.own_begin, st.evolve.own_count, slab_set());
     c.local_sums = true;
-    if (st.ev_slab_thermal) evolve_pass_thermal(c, slab_set());
-    if (st.ev_rates_in_outbox) {
+    if (st.evolve.slab_thermal) evolve_pass_thermal(c, slab_set());
+    if (st.evolve.rates_in_outbox) {
         c.gamma = st.staging; c.gamma_t = nullptr; c.phi_out = st.grid[ASORA_GRID_PHI_ION]; c.fold = false;
         // (thermal: the summed heating likewise from its out-box, kept in PHI_HEAT)
-        if (st.ev_slab_thermal) { c.heat = st.heat_outbox; c.heat_t = nullptr; c.heat_out = st.grid[ASORA_GRID_PHI_HEAT]; }
+        if (st.evolve.slab_thermal) { c.heat = st.thermal.heat_outbox; c.heat_t = nullptr; c.heat_out = st.grid[ASORA_GRID_PHI_HEAT]; }
     }
     return launch_chemistry_tiles(st, c, st.stream);
 }
@@ -494,7 +483,7 @@ int asora_evolve_slab_nhi(int i_begin, int i_count)
     if (int rc = require_slab("evolve_slab_nhi")) return rc;
     State &st = state();
     if (int rc = check_planes("evolve_slab_nhi", 4, "bad plane range", i_begin, i_count)) return rc;
-    return launch_prepare_range(st, i_begin, i_count, false, nullptr, &st.ev_status->done);
+    return launch_prepare_range(st, i_begin, i_count, false, nullptr, &st.evolve.status->done);
 }
 
 int asora_evolve_slab_close(const double *host_sums)
@@ -502,17 +491,17 @@ int asora_evolve_slab_close(const double *host_sums)
     clear_error();
     if (int rc = require_slab("evolve_slab_close")) return rc;
     State &st = state();
-    if (!st.ev_slab_passed) return fail(4, "evolve_slab_close: the iteration's pass has not been enqueued");
+    if (!st.evolve.slab_passed) return fail(4, "evolve_slab_close: the iteration's pass has not been enqueued");
     if (host_sums) {          // summed over the ranks on the host (gloo rehearsals, mpi4py): {sum x, sum 1-x, conv_flag}
         ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
         std::memcpy(st.red_host, host_sums, sizeof(double) * 3);
         ASORA_HIP_TRY(hipMemcpyAsync(st.red_final, st.red_host, sizeof(double) * 3, hipMemcpyHostToDevice, st.stream));
     }
-    if (int rc = launch_convergence_test(st, st.red_final, st.ev_status)) return rc;
-    st.ev_first = false;
-    st.ev_slab_passed = false; st.ev_folded_all = false;
-    st.ev_plane_swept = false;
-    st.ev_enqueued += 1;
+    if (int rc = launch_convergence_test(st, st.red_final, st.evolve.status)) return rc;
+    st.evolve.first = false;
+    st.evolve.slab_passed = false; st.evolve.folded_all = false;
+    st.evolve.plane_swept = false;
+    st.evolve.enqueued += 1;
     return 0;
 }
 
@@ -521,39 +510,39 @@ int asora_evolve_enqueue(int iterations)
     clear_error();
     if (int rc = require_init("evolve_enqueue")) return rc;
     State &st = state();
-    if (!st.ev_open) return fail(4, "evolve_enqueue: no evolve step in progress (call asora_evolve_begin)");
-    if (st.ev_slab) return fail(4, "evolve_enqueue: the step was begun with asora_evolve_begin_slab (use the asora_evolve_slab_* calls)");
+    if (!st.evolve.flags.open) return fail(4, "evolve_enqueue: no evolve step in progress (call asora_evolve_begin)");
+    if (st.evolve.slab) return fail(4, "evolve_enqueue: the step was begun with asora_evolve_begin_slab (use the asora_evolve_slab_* calls)");
     if (iterations < 1 || iterations > EVOLVE_HIST / 2) return fail(3, "evolve_enqueue: between 1 and 32 iterations per call");
     // the per-iteration history is a ring of EVOLVE_HIST rows on the device: rows not yet handed out by asora_evolve_poll
     // must not be overwritten
-    if (st.ev_enqueued - st.ev_reported + iterations > EVOLVE_HIST)
-        return fail(4, "evolve_enqueue: " + std::to_string(st.ev_enqueued - st.ev_reported) + " iterations enqueued since the last "
+    if (st.evolve.enqueued - st.evolve.reported + iterations > EVOLVE_HIST)
+        return fail(4, "evolve_enqueue: " + std::to_string(st.evolve.enqueued - st.evolve.reported) + " iterations enqueued since the last "
                            "asora_evolve_poll; the history ring holds " + std::to_string(EVOLVE_HIST) + " (poll first)");
-    st.ev_sets_known = false;                        // until the next poll tells how many of these were carried out
+    st.evolve.flags.sets_known = false;                        // until the next poll tells how many of these were carried out
     for (int it = 0; it < iterations; ++it) {
         // iteration k = ev_enqueued + it + 1 of the step (as long as the step has not converged: then nothing runs anyway)
-        const int set = (st.ev_base + st.ev_enqueued + it) & 1;
+        const int set = (st.evolve.base + st.evolve.enqueued + it) & 1;
         // the faces' sweeps (asora_plane_flux) into the iteration's pairs, ahead of the point sources; a step may have only faces
-        if (int rc = launch_plane_flux(st, st.ev_rt, acc_pair(set), st.th_on ? heat_pair(set) : nullptr, st.th_on, &st.ev_status->done))
+        if (int rc = launch_plane_flux(st, st.evolve.rt, acc_pair(set), st.thermal.mode.on ? heat_pair(set) : nullptr, st.thermal.mode.on, &st.evolve.status->done))
             return rc;
-        if (st.ev_src_count > 0) {
-            RtParams p = st.ev_rt;
+        if (st.evolve.src_count > 0) {
+            RtParams p = st.evolve.rt;
             p.phi = acc_pair(set);
-            if (st.th_on) p.heat = heat_pair(set);    // thermal mode: the HEAT forms, into the iteration's heating pair
-            if (int rc = launch_raytrace(st, p, false, st.th_on)) return rc;
+            if (st.thermal.mode.on) p.heat = heat_pair(set);    // thermal mode: the HEAT forms, into the iteration's heating pair
+            if (int rc = launch_raytrace(st, p, false, st.thermal.mode.on)) return rc;
         }
         ChemTileParams c = evolve_pass_params(0, st.N, set);
-        if (st.reach.in_use) { c.reach_a = st.reach.mask; c.reach_t = st.reach.mask + st.reach.bytes; }
-        if (st.th_on) evolve_pass_thermal(c, set);
+        if (st.reach.d.in_use) { c.reach_a = st.reach.mask; c.reach_t = st.reach.mask + st.reach.mask.bytes() / 2; }
+        if (st.thermal.mode.on) evolve_pass_thermal(c, set);
         if (int rc = launch_chemistry_tiles(st, c, st.stream)) return rc;
-        st.ev_first = false;
+        st.evolve.first = false;
     }
-    if (st.th_on) {
-        st.heat_clean[0] = st.heat_clean[1] = false;     // until the poll tells which pair the last iteration used
+    if (st.thermal.mode.on) {
+        st.thermal.mode.heat_clean[0] = st.thermal.mode.heat_clean[1] = false;     // until the poll tells which pair the last iteration used
         st.grid_valid[ASORA_GRID_TEMP_END] = true;
         st.grid_valid[ASORA_GRID_PHI_HEAT] = false;
     }
-    st.ev_enqueued += iterations;
+    st.evolve.enqueued += iterations;
     st.grid_valid[ASORA_GRID_XH_AV] = st.grid_valid[ASORA_GRID_XH_INTERMED] = true;
     st.grid_valid[ASORA_GRID_PHI_ION] = false;       // until asora_evolve_poll folds the last iteration's accumulators
     return 0;
@@ -564,40 +553,40 @@ int asora_evolve_poll(int *niter, int *converged, double *history, int history_r
     clear_error();
     if (int rc = require_init("evolve_poll")) return rc;
     State &st = state();
-    if (!st.ev_open) return fail(4, "evolve_poll: no evolve step in progress (call asora_evolve_begin)");
-    ASORA_HIP_TRY(hipMemcpyAsync(st.ev_host, st.ev_status, sizeof(EvolveStatus), hipMemcpyDeviceToHost, st.stream));
+    if (!st.evolve.flags.open) return fail(4, "evolve_poll: no evolve step in progress (call asora_evolve_begin)");
+    ASORA_HIP_TRY(hipMemcpyAsync(st.evolve.host, st.evolve.status, sizeof(EvolveStatus), hipMemcpyDeviceToHost, st.stream));
     ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
-    const EvolveStatus &h = *st.ev_host;
-    const bool thermal = st.ev_slab ? st.ev_slab_thermal : st.th_on;
+    const EvolveStatus &h = *st.evolve.host;
+    const bool thermal = st.evolve.slab ? st.evolve.slab_thermal : st.thermal.mode.on;
     // The rates of the last iteration carried out sit, unfolded, in its accumulator pair; the other pair is zero (the pass
     // of that iteration zeroed it; iterations enqueued beyond convergence did nothing).  Fold them into PHI_ION now.
     if (h.niter > 0) {
-        const int set = (st.ev_base + h.niter - 1) & 1;
-        if (st.ev_slab && st.ev_rates_in_outbox) st.ev_folded_iter = h.niter;      // (the pass has kept the summed rates in PHI_ION, and the heating in PHI_HEAT)
-        if (st.ev_folded_iter != h.niter) {
+        const int set = (st.evolve.base + h.niter - 1) & 1;
+        if (st.evolve.slab && st.evolve.rates_in_outbox) st.evolve.folded_iter = h.niter;      // (the pass has kept the summed rates in PHI_ION, and the heating in PHI_HEAT)
+        if (st.evolve.folded_iter != h.niter) {
             const double *a = acc_pair(set);
             if (int rc = launch_fold_sum(st, a, a + st.ncell, st.grid[ASORA_GRID_PHI_ION])) return rc;
             if (thermal) {       // thermal mode: the last iteration's heating as well (a sharded step: complete on the own planes)
                 const double *hsum = heat_pair(set);
                 if (int rc = launch_fold_sum(st, hsum, hsum + st.ncell, st.grid[ASORA_GRID_PHI_HEAT])) return rc;
             }
-            st.ev_folded_iter = h.niter;
+            st.evolve.folded_iter = h.niter;
         }
         st.grid_valid[ASORA_GRID_PHI_ION] = true;
-        st.ev_clean[set] = false; st.ev_clean[set ^ 1] = true;
+        st.evolve.flags.clean[set] = false; st.evolve.flags.clean[set ^ 1] = true;
         if (thermal) {
             st.grid_valid[ASORA_GRID_PHI_HEAT] = true;
-            st.heat_clean[set] = false; st.heat_clean[set ^ 1] = true;
+            st.thermal.mode.heat_clean[set] = false; st.thermal.mode.heat_clean[set ^ 1] = true;
         }
     }
-    st.ev_sets_known = true;
+    st.evolve.flags.sets_known = true;
     int rows = 0;
-    for (int it = st.ev_reported; it < h.niter && history && rows < history_rows; ++it, ++rows)
+    for (int it = st.evolve.reported; it < h.niter && history && rows < history_rows; ++it, ++rows)
         for (int q = 0; q < 5; ++q) history[5 * rows + q] = h.hist[it % EVOLVE_HIST][q];
     // everything enqueued has run by now (iterations enqueued beyond convergence did nothing and never will)
-    st.ev_enqueued = h.niter;
-    if (history) st.ev_reported += rows;
-    else st.ev_reported = h.niter;           // a caller that does not ask for the rows gives them up
+    st.evolve.enqueued = h.niter;
+    if (history) st.evolve.reported += rows;
+    else st.evolve.reported = h.niter;           // a caller that does not ask for the rows gives them up
     if (rows_written) *rows_written = rows;
     if (niter) *niter = h.niter;
     if (converged) *converged = h.done;

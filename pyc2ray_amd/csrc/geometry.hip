@@ -358,12 +358,11 @@ HostGeom restrict_to_wedge(const HostGeom &full, int wedge, int RT_THREADS, uint
 template <typename T>
 int upload(const std::vector<T> &v, const T *&dev_out, std::vector<void *> &owned)
 {
-    void *d = nullptr;
-    const size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(T);
-    ASORA_HIP_TRY(hipMalloc(&d, bytes));
+    T *d = nullptr;
+    if (int rc = device_allocate(d, std::max<size_t>(v.size(), 1))) return rc;
     owned.push_back(d);
     if (!v.empty()) ASORA_HIP_TRY(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    dev_out = static_cast<const T *>(d);
+    dev_out = d;
     return 0;
 }
 
@@ -380,10 +379,8 @@ int ensure_logtab(State &st)
         lt[i].x = (double)(2.0L / c);
         lt[i].y = (double)(std::log2(c) - 1.0L);
     }
-    double2 *d = nullptr;
-    ASORA_HIP_TRY(hipMalloc(&d, lt.size() * sizeof(double2)));
-    ASORA_HIP_TRY(hipMemcpy(d, lt.data(), lt.size() * sizeof(double2), hipMemcpyHostToDevice));
-    st.logtab_dev = d;
+    if (int rc = st.logtab_dev.allocate(lt.size())) return rc;
+    ASORA_HIP_TRY(hipMemcpy(st.logtab_dev, lt.data(), lt.size() * sizeof(double2), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -413,18 +410,13 @@ static int patch_sphere_cells(State &st, double R, double dr)
         pairs[2 * q] = (unsigned long long)reinterpret_cast<uintptr_t>(c.dev_word);
         pairs[2 * q + 1] = c.word_without_rate | (inside_radius_reference(c.a, c.b, c.c, dr, R * R) ? CELL_RATE : 0u);
     }
-    if (n > st.geom_patch_cap) {
-        if (st.geom_patch_dev) (void)hipFree(st.geom_patch_dev);
-        st.geom_patch_dev = nullptr; st.geom_patch_cap = 0;
-        ASORA_HIP_TRY(hipMalloc(&st.geom_patch_dev, 2 * n * sizeof(unsigned long long)));
-        st.geom_patch_cap = n;
-    }
+    if (int rc = st.geom_patch_dev.reserve(2 * n)) return rc;
     // (a blocking copy from pageable memory: `pairs` may go out of scope right after; the kernel is stream-ordered)
     ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
     for (int q = 0; q < 2; ++q) if (st.side[q]) ASORA_HIP_TRY(hipStreamSynchronize(st.side[q]));   // (traces of an earlier pipelined call)
     ASORA_HIP_TRY(hipMemcpy(st.geom_patch_dev, pairs.data(), 2 * n * sizeof(unsigned long long), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(patch_words_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st.stream,
-                       (const unsigned long long *)st.geom_patch_dev, (int)n);
+                       (const unsigned long long *)st.geom_patch_dev.get(), (int)n);
     ASORA_HIP_TRY(hipGetLastError());
     // a pipelined call (asora_raytrace_begin) traces on the side streams, which only wait for what the main stream had
     // done when the call began: they must not read the patched words before the patch has run

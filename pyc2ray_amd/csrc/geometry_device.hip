@@ -466,14 +466,11 @@ __global__ void __launch_bounds__(GB_THREADS) wedge_write_kernel(const WedgeJob 
 }
 
 template <typename T>
-struct DevArray {
-    T *p = nullptr;
-    ~DevArray() { if (p) (void)hipFree(p); }
-    int alloc(size_t n) { ASORA_HIP_TRY(hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T))); return 0; }
+struct DevArray : Scoped<T> {
     int upload(const std::vector<T> &v, hipStream_t s)
     {
-        if (int rc = alloc(v.size())) return rc;
-        if (!v.empty()) ASORA_HIP_TRY(hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
+        if (int rc = this->allocate(v.size())) return rc;
+        if (!v.empty()) ASORA_HIP_TRY(hipMemcpyAsync(this->get(), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
         return 0;
     }
 };
@@ -571,8 +568,10 @@ static int allocate_tables(State &st, const std::vector<GeomTableSpec> &specs, c
     for (size_t t = 0; t < nt; ++t) {
         const size_t own = L[t].entries - fill_from[t];
         uint4 *a = nullptr, *b = nullptr;
-        ASORA_HIP_TRY(hipMalloc(&a, own * sizeof(uint4))); st.geom_owned.push_back(a);
-        ASORA_HIP_TRY(hipMalloc(&b, own * sizeof(uint4))); st.geom_owned.push_back(b);
+        if (int rc = device_allocate(a, own)) return rc;
+        st.geom_owned.push_back(a);
+        if (int rc = device_allocate(b, own)) return rc;
+        st.geom_owned.push_back(b);
         st.geom_bytes += 2 * own * sizeof(uint4);
         // (entry e >= fill_from of the table is own[e - fill_from]; the shifted pointer is never dereferenced below fill_from)
         A[t] = reinterpret_cast<uint4 *>(reinterpret_cast<uintptr_t>(a) - fill_from[t] * sizeof(uint4));
@@ -627,8 +626,10 @@ int build_geometry_on_device(State &st, const std::vector<GeomTableSpec> &specs,
         for (int t = 0; t < nt; ++t) {
             uint4 *a = nullptr, *b = nullptr;
             const size_t n = 4 * (size_t)threads;
-            ASORA_HIP_TRY(hipMalloc(&a, n * sizeof(uint4))); st.geom_owned.push_back(a);
-            ASORA_HIP_TRY(hipMalloc(&b, n * sizeof(uint4))); st.geom_owned.push_back(b);
+            if (int rc = device_allocate(a, n)) return rc;
+            st.geom_owned.push_back(a);
+            if (int rc = device_allocate(b, n)) return rc;
+            st.geom_owned.push_back(b);
             st.geom_bytes += 2 * n * sizeof(uint4);
             ASORA_HIP_TRY(hipMemsetAsync(a, 0, n * sizeof(uint4), st.stream));
             hipLaunchKernelGGL(fill_pad_kernel, dim3(4), dim3(256), 0, st.stream, b, n, 1u);
@@ -668,16 +669,16 @@ int build_geometry_on_device(State &st, const std::vector<GeomTableSpec> &specs,
     DevArray<int> d_count, d_packed, d_len, d_flags;
     if (int rc = d_jobs.upload(jobs, st.stream)) return rc;
     if (int rc = d_shell_cand.upload(shell_cand, st.stream)) return rc;
-    if (int rc = d_rank.alloc(total_cand)) return rc;
-    if (int rc = d_pos.alloc(any_aligned ? total_cand : 1)) return rc;
-    if (int rc = d_count.alloc((size_t)nf * (S + 2))) return rc;
-    if (int rc = d_packed.alloc((size_t)nf * (S + 2))) return rc;
+    if (int rc = d_rank.allocate(total_cand)) return rc;
+    if (int rc = d_pos.allocate(any_aligned ? total_cand : 1)) return rc;
+    if (int rc = d_count.allocate((size_t)nf * (S + 2))) return rc;
+    if (int rc = d_packed.allocate((size_t)nf * (S + 2))) return rc;
     hipLaunchKernelGGL(geometry_count_kernel, dim3((unsigned)S, (unsigned)nf), dim3(GB_THREADS), 0, st.stream,
-                       (const TableJob *)d_jobs.p, (const size_t *)d_shell_cand.p, P, d_rank.p, d_pos.p, d_count.p, d_packed.p);
+                       (const TableJob *)d_jobs.get(), (const size_t *)d_shell_cand.get(), P, d_rank.get(), d_pos.get(), d_count.get(), d_packed.get());
     ASORA_HIP_TRY(hipGetLastError());
     std::vector<int> h_count((size_t)nf * (S + 2), 0), h_packed((size_t)nf * (S + 2), 0);
-    ASORA_HIP_TRY(hipMemcpyAsync(h_count.data(), d_count.p, h_count.size() * sizeof(int), hipMemcpyDeviceToHost, st.stream));
-    ASORA_HIP_TRY(hipMemcpyAsync(h_packed.data(), d_packed.p, h_packed.size() * sizeof(int), hipMemcpyDeviceToHost, st.stream));
+    ASORA_HIP_TRY(hipMemcpyAsync(h_count.data(), d_count.get(), h_count.size() * sizeof(int), hipMemcpyDeviceToHost, st.stream));
+    ASORA_HIP_TRY(hipMemcpyAsync(h_packed.data(), d_packed.get(), h_packed.size() * sizeof(int), hipMemcpyDeviceToHost, st.stream));
     ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
 
     // layout of the full tables
@@ -694,16 +695,17 @@ int build_geometry_on_device(State &st, const std::vector<GeomTableSpec> &specs,
     }
     // (the zero slot of the FINAL tables: the largest shell over all of them -- for quarter sectors that of the wedge tables,
     //  known only after their own count; the full sectors then keep MARK-free temporaries with their own zero slot)
-    std::vector<void *> temp_tables;
-    struct FreeTemps { std::vector<void *> &v; ~FreeTemps() { for (void *q : v) (void)hipFree(q); } } free_temps{temp_tables};
+    std::vector<Scoped<uint4>> temp_tables(wedges ? 2 * (size_t)nf : 0);
     std::vector<uint4 *> tabA, tabB;
     std::vector<int> first_shell((size_t)nf, 1), inner((size_t)nf, 0);
     std::vector<size_t> fill_from((size_t)nf, 0);
     if (wedges) {           // the full sectors are temporaries
         tabA.assign((size_t)nf, nullptr); tabB.assign((size_t)nf, nullptr);
         for (int t = 0; t < nf; ++t) {
-            ASORA_HIP_TRY(hipMalloc(&tabA[(size_t)t], L[(size_t)t].entries * sizeof(uint4))); temp_tables.push_back(tabA[(size_t)t]);
-            ASORA_HIP_TRY(hipMalloc(&tabB[(size_t)t], L[(size_t)t].entries * sizeof(uint4))); temp_tables.push_back(tabB[(size_t)t]);
+            Scoped<uint4> &a = temp_tables[2 * (size_t)t], &b = temp_tables[2 * (size_t)t + 1];
+            if (int rc = a.allocate(L[(size_t)t].entries)) return rc;
+            if (int rc = b.allocate(L[(size_t)t].entries)) return rc;
+            tabA[(size_t)t] = a; tabB[(size_t)t] = b;
         }
     } else if (int rc = allocate_tables(st, full, L, threads, tabA, tabB, first_shell, fill_from, inner)) return rc;
     for (int t = 0; t < nf; ++t) {
@@ -715,7 +717,7 @@ int build_geometry_on_device(State &st, const std::vector<GeomTableSpec> &specs,
         jobs[(size_t)t].cellA = tabA[(size_t)t]; jobs[(size_t)t].cellB = tabB[(size_t)t]; jobs[(size_t)t].S_built = L[(size_t)t].S_built;
         jobs[(size_t)t].first_shell = first_shell[(size_t)t];
     }
-    ASORA_HIP_TRY(hipMemcpyAsync(d_jobs.p, jobs.data(), jobs.size() * sizeof(TableJob), hipMemcpyHostToDevice, st.stream));
+    ASORA_HIP_TRY(hipMemcpyAsync(d_jobs.get(), jobs.data(), jobs.size() * sizeof(TableJob), hipMemcpyHostToDevice, st.stream));
     if (int rc = d_shell_entry.upload(shell_entry, st.stream)) return rc;
     if (int rc = d_len.upload(shell_len, st.stream)) return rc;
     std::vector<int> zero2(2, 0);
@@ -724,12 +726,12 @@ int build_geometry_on_device(State &st, const std::vector<GeomTableSpec> &specs,
     const unsigned sphere_cap = 1u << 20;
     DevArray<SphereRecord> d_sphere;
     DevArray<unsigned> d_nsphere;
-    if (int rc = d_sphere.alloc(sphere_cap)) return rc;
+    if (int rc = d_sphere.allocate(sphere_cap)) return rc;
     std::vector<unsigned> zero1(1, 0u);
     if (int rc = d_nsphere.upload(zero1, st.stream)) return rc;
-    hipLaunchKernelGGL(geometry_write_kernel, dim3((unsigned)S, (unsigned)nf), dim3(GB_THREADS), 0, st.stream, (const TableJob *)d_jobs.p,
-                       (const size_t *)d_shell_cand.p, (const size_t *)d_shell_entry.p, (const int *)d_len.p, P, (const uint32_t *)d_rank.p,
-                       (const uint32_t *)d_pos.p, max_cells_full, d_flags.p, d_sphere.p, d_nsphere.p, wedges ? 0u : sphere_cap);
+    hipLaunchKernelGGL(geometry_write_kernel, dim3((unsigned)S, (unsigned)nf), dim3(GB_THREADS), 0, st.stream, (const TableJob *)d_jobs.get(),
+                       (const size_t *)d_shell_cand.get(), (const size_t *)d_shell_entry.get(), (const int *)d_len.get(), P, (const uint32_t *)d_rank.get(),
+                       (const uint32_t *)d_pos.get(), max_cells_full, d_flags.get(), d_sphere.get(), d_nsphere.get(), wedges ? 0u : sphere_cap);
     ASORA_HIP_TRY(hipGetLastError());
 
     std::vector<uint4 *> final_A((size_t)nt, nullptr);
@@ -758,15 +760,15 @@ int build_geometry_on_device(State &st, const std::vector<GeomTableSpec> &specs,
         DevArray<int> d_wcount, d_wlen;
         DevArray<size_t> d_wentry;
         if (int rc = d_wj.upload(wj, st.stream)) return rc;
-        if (int rc = d_keep.alloc(keep_total)) return rc;
-        if (int rc = d_newslot.alloc(keep_total)) return rc;
-        if (int rc = d_wcount.alloc((size_t)nt * (S + 2))) return rc;
-        ASORA_HIP_TRY(hipMemsetAsync(d_keep.p, 0, keep_total, st.stream));
-        hipLaunchKernelGGL(wedge_seed_kernel, dim3((unsigned)S, (unsigned)nt), dim3(256), 0, st.stream, (const WedgeJob *)d_wj.p,
-                           (const size_t *)d_shell_entry.p, (const int *)d_count.p, d_keep.p);
+        if (int rc = d_keep.allocate(keep_total)) return rc;
+        if (int rc = d_newslot.allocate(keep_total)) return rc;
+        if (int rc = d_wcount.allocate((size_t)nt * (S + 2))) return rc;
+        ASORA_HIP_TRY(hipMemsetAsync(d_keep.get(), 0, keep_total, st.stream));
+        hipLaunchKernelGGL(wedge_seed_kernel, dim3((unsigned)S, (unsigned)nt), dim3(256), 0, st.stream, (const WedgeJob *)d_wj.get(),
+                           (const size_t *)d_shell_entry.get(), (const int *)d_count.get(), d_keep.get());
         for (int s = S; s >= 2; --s)
-            hipLaunchKernelGGL(wedge_mark_kernel, dim3(32, (unsigned)nt), dim3(256), 0, st.stream, (const WedgeJob *)d_wj.p,
-                               (const size_t *)d_shell_entry.p, (const int *)d_count.p, d_keep.p, s, max_cells_full);
+            hipLaunchKernelGGL(wedge_mark_kernel, dim3(32, (unsigned)nt), dim3(256), 0, st.stream, (const WedgeJob *)d_wj.get(),
+                               (const size_t *)d_shell_entry.get(), (const int *)d_count.get(), d_keep.get(), s, max_cells_full);
         {   // Families of wedge tables (the octant variants of one sector and wedge under a clipped window): their full sectors
             // hold the same entries up to shell m, but what a wedge KEEPS of them follows from its outer shells, which differ.  Keep
             // the union of the members' needs there: the inner shells of all members then come out identical (and are shared below).
@@ -777,16 +779,16 @@ int build_geometry_on_device(State &st, const std::vector<GeomTableSpec> &specs,
                     const unsigned blocks = (unsigned)std::min<size_t>(4096, (n + 255) / 256);
                     const size_t first = wj[(size_t)f.members[0]].keep_base;
                     for (size_t q = 1; q < f.members.size(); ++q)
-                        hipLaunchKernelGGL(keep_or_kernel, dim3(blocks), dim3(256), 0, st.stream, d_keep.p, first, wj[(size_t)f.members[q]].keep_base, n);
+                        hipLaunchKernelGGL(keep_or_kernel, dim3(blocks), dim3(256), 0, st.stream, d_keep.get(), first, wj[(size_t)f.members[q]].keep_base, n);
                     for (size_t q = 1; q < f.members.size(); ++q)
-                        ASORA_HIP_TRY(hipMemcpyAsync(d_keep.p + wj[(size_t)f.members[q]].keep_base, d_keep.p + first, n, hipMemcpyDeviceToDevice, st.stream));
+                        ASORA_HIP_TRY(hipMemcpyAsync(d_keep.get() + wj[(size_t)f.members[q]].keep_base, d_keep.get() + first, n, hipMemcpyDeviceToDevice, st.stream));
                 }
         }
-        hipLaunchKernelGGL(wedge_count_kernel, dim3((unsigned)S, (unsigned)nt), dim3(GB_THREADS), 0, st.stream, (const WedgeJob *)d_wj.p,
-                           (const size_t *)d_shell_entry.p, (const int *)d_count.p, (const unsigned char *)d_keep.p, d_newslot.p, d_wcount.p);
+        hipLaunchKernelGGL(wedge_count_kernel, dim3((unsigned)S, (unsigned)nt), dim3(GB_THREADS), 0, st.stream, (const WedgeJob *)d_wj.get(),
+                           (const size_t *)d_shell_entry.get(), (const int *)d_count.get(), (const unsigned char *)d_keep.get(), d_newslot.get(), d_wcount.get());
         ASORA_HIP_TRY(hipGetLastError());
         std::vector<int> h_wcount((size_t)nt * (S + 2), 0);
-        ASORA_HIP_TRY(hipMemcpyAsync(h_wcount.data(), d_wcount.p, h_wcount.size() * sizeof(int), hipMemcpyDeviceToHost, st.stream));
+        ASORA_HIP_TRY(hipMemcpyAsync(h_wcount.data(), d_wcount.get(), h_wcount.size() * sizeof(int), hipMemcpyDeviceToHost, st.stream));
         ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
         std::vector<Layout> WL((size_t)nt);
         std::vector<size_t> wentry((size_t)nt * (S + 2), 0);
@@ -813,13 +815,13 @@ int build_geometry_on_device(State &st, const std::vector<GeomTableSpec> &specs,
             step_after[(size_t)t] = WL[(size_t)t].step_after_shell;
             final_A[(size_t)t] = wA[(size_t)t];
         }
-        ASORA_HIP_TRY(hipMemcpyAsync(d_wj.p, wj.data(), wj.size() * sizeof(WedgeJob), hipMemcpyHostToDevice, st.stream));
-        ASORA_HIP_TRY(hipMemsetAsync(d_nsphere.p, 0, sizeof(unsigned), st.stream));       // (the full sectors' pass counted theirs)
+        ASORA_HIP_TRY(hipMemcpyAsync(d_wj.get(), wj.data(), wj.size() * sizeof(WedgeJob), hipMemcpyHostToDevice, st.stream));
+        ASORA_HIP_TRY(hipMemsetAsync(d_nsphere.get(), 0, sizeof(unsigned), st.stream));       // (the full sectors' pass counted theirs)
         if (int rc = d_wentry.upload(wentry, st.stream)) return rc;
         if (int rc = d_wlen.upload(wlen, st.stream)) return rc;
-        hipLaunchKernelGGL(wedge_write_kernel, dim3((unsigned)S, (unsigned)nt), dim3(GB_THREADS), 0, st.stream, (const WedgeJob *)d_wj.p,
-                           (const size_t *)d_shell_entry.p, (const int *)d_count.p, (const size_t *)d_wentry.p, (const int *)d_wlen.p,
-                           (const uint32_t *)d_newslot.p, max_cells_full, max_cells_all, threads, d_flags.p, d_sphere.p, d_nsphere.p,
+        hipLaunchKernelGGL(wedge_write_kernel, dim3((unsigned)S, (unsigned)nt), dim3(GB_THREADS), 0, st.stream, (const WedgeJob *)d_wj.get(),
+                           (const size_t *)d_shell_entry.get(), (const int *)d_count.get(), (const size_t *)d_wentry.get(), (const int *)d_wlen.get(),
+                           (const uint32_t *)d_newslot.get(), max_cells_full, max_cells_all, threads, d_flags.get(), d_sphere.get(), d_nsphere.get(),
                            sphere_cap, 0u);
         ASORA_HIP_TRY(hipGetLastError());
         ASORA_HIP_TRY(hipStreamSynchronize(st.stream));            // the temporaries (full sectors, keep bytes) go out of scope below
@@ -828,15 +830,15 @@ int build_geometry_on_device(State &st, const std::vector<GeomTableSpec> &specs,
     // flags and the on-sphere entries
     int h_flags[2] = {0, 0};
     unsigned n_sph = 0;
-    ASORA_HIP_TRY(hipMemcpyAsync(h_flags, d_flags.p, sizeof h_flags, hipMemcpyDeviceToHost, st.stream));
-    ASORA_HIP_TRY(hipMemcpyAsync(&n_sph, d_nsphere.p, sizeof n_sph, hipMemcpyDeviceToHost, st.stream));
+    ASORA_HIP_TRY(hipMemcpyAsync(h_flags, d_flags.get(), sizeof h_flags, hipMemcpyDeviceToHost, st.stream));
+    ASORA_HIP_TRY(hipMemcpyAsync(&n_sph, d_nsphere.get(), sizeof n_sph, hipMemcpyDeviceToHost, st.stream));
     ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
     if (h_flags[0] & 1) return fail(11, "raytrace geometry: a cell of a unit reads a corner outside the unit (internal error)");
     if (h_flags[0] & 2) return fail(11, "raytrace geometry: a cell of shell 1 lies beyond the first three steps (internal error)");
     if (n_sph > sphere_cap) return fail(11, "raytrace geometry: more on-sphere entries than the list holds (internal error)");
     if (n_sph) {
         std::vector<SphereRecord> rec(n_sph);
-        ASORA_HIP_TRY(hipMemcpy(rec.data(), d_sphere.p, n_sph * sizeof(SphereRecord), hipMemcpyDeviceToHost));
+        ASORA_HIP_TRY(hipMemcpy(rec.data(), d_sphere.get(), n_sph * sizeof(SphereRecord), hipMemcpyDeviceToHost));
         for (const auto &r : rec)
             st.geom_sphere.push_back({reinterpret_cast<uint32_t *>(final_A[r.table] + r.entry) + 1, r.word_without_rate, r.a, r.b, r.c});
     }

@@ -205,9 +205,9 @@ static unsigned gran_blocks(const State &st, size_t items)
 static int ensure_gran_buffers(State &st)
 {
     const size_t nwords = (size_t)st.N * st.N * (((size_t)st.N + 63) / 64);
-    if (!st.gran_work) ASORA_HIP_TRY(hipMalloc(&st.gran_work, sizeof(unsigned) * st.ncell));
-    if (!st.gran_mask) ASORA_HIP_TRY(hipMalloc(&st.gran_mask, sizeof(unsigned long long) * nwords));
-    if (!st.gran_result) ASORA_HIP_TRY(hipMalloc(&st.gran_result, sizeof(unsigned long long) * GR_WORDS));
+    if (int rc = st.granulometry.work.allocate(st.ncell)) return rc;
+    if (int rc = st.granulometry.mask.allocate(nwords)) return rc;
+    if (int rc = st.granulometry.result.allocate(GR_WORDS)) return rc;
     return 0;
 }
 
@@ -266,28 +266,28 @@ int asora_granulometry(int which_grid, double threshold, int phase, int periodic
     if (int rc = ensure_gran_buffers(st)) return rc;
     const int N = st.N, W = (N + 63) / 64, per = periodic != 0;
     const size_t ncell = st.ncell, nwords = (size_t)N * N * W;
-    unsigned *d2 = st.region_label, *ga = st.region_volume, *gb = st.gran_work;
-    unsigned long long *res = st.gran_result;
+    unsigned *d2 = st.regions.label, *ga = st.regions.volume, *gb = st.granulometry.work;
+    unsigned long long *res = st.granulometry.result;
 
     ASORA_HIP_TRY(hipMemsetAsync(res, 0, sizeof(unsigned long long) * GR_WORDS, st.stream));
     if (int rc = launch_bubble_mask(st, which_grid, threshold, phase, false)) return rc;
-    if (int rc = launch_gran_transform(st, st.bubble_mask, per, !per, 1, GR_INF, nullptr, ga, gb, d2, nullptr)) return rc;
+    if (int rc = launch_gran_transform(st, st.bubbles.mask, per, !per, 1, GR_INF, nullptr, ga, gb, d2, nullptr)) return rc;
     const dim3 block(GR_THREADS);
     hipLaunchKernelGGL(gran_tally_kernel, dim3(gran_blocks(st, ncell)), block, 0, st.stream, (const unsigned *)d2, ncell, res + GR_TALLY);
     ASORA_HIP_TRY(hipGetLastError());
     for (int n = 0; n < n_radii; ++n) {
         hipLaunchKernelGGL(gran_erode_kernel, dim3(gran_blocks(st, nwords * 64)), block, 0, st.stream, (const unsigned *)d2, N, W, r2[n], nwords,
-                           n > 0 ? (const unsigned long long *)(res + GR_ERODED + n - 1) : (const unsigned long long *)nullptr, st.gran_mask,
+                           n > 0 ? (const unsigned long long *)(res + GR_ERODED + n - 1) : (const unsigned long long *)nullptr, st.granulometry.mask,
                            res + GR_ERODED + n);
         ASORA_HIP_TRY(hipGetLastError());
-        if (int rc = launch_gran_transform(st, st.gran_mask, per, 0, 0, r2[n], res + GR_ERODED + n, ga, gb, nullptr, res + GR_OPENED + n))
+        if (int rc = launch_gran_transform(st, st.granulometry.mask, per, 0, 0, r2[n], res + GR_ERODED + n, ga, gb, nullptr, res + GR_OPENED + n))
             return rc;
     }
-    ASORA_HIP_TRY(hipMemcpyAsync(st.bubble_host, res, sizeof(unsigned long long) * GR_WORDS, hipMemcpyDeviceToHost, st.stream));
+    ASORA_HIP_TRY(hipMemcpyAsync(st.bubbles.host, res, sizeof(unsigned long long) * GR_WORDS, hipMemcpyDeviceToHost, st.stream));
     if (dist2) ASORA_HIP_TRY(hipMemcpyAsync(dist2, d2, sizeof(unsigned) * ncell, hipMemcpyDeviceToHost, st.stream));
     ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
 
-    const unsigned long long *h = st.bubble_host;
+    const unsigned long long *h = st.bubbles.host;
     for (int n = 0; n < n_radii; ++n) { eroded[n] = h[GR_ERODED + n]; opened[n] = h[GR_OPENED + n]; }
     for (int t = 0; t < ASORA_GRAN_TALLIES; ++t) tallies[t] = h[GR_TALLY + t];
     return 0;

@@ -75,7 +75,7 @@ static dim3 tile_grid(int N) { const unsigned t = (N + 31) / 32; return dim3(t, 
 // tested.  (asora_debug_coldens borrows the grey form when no tables are loaded and keeps its column densities alone.)
 static int check_lls_form(const State &st)
 {
-    if ((st.lls_a != 0.0 || st.lls_b != 0.0) && st.opt[ASORA_OPT_GREY_NOTABLES] && !st.coldens_only)
+    if ((st.medium.lls_a != 0.0 || st.medium.lls_b != 0.0) && st.opt[ASORA_OPT_GREY_NOTABLES] && !st.coldens_only)
         return fail(4, "raytrace: Lyman-limit-system opacity (asora_lls_opacity) needs table rates (ASORA_OPT_GREY_NOTABLES = 0)");
     return 0;
 }
@@ -87,11 +87,11 @@ int launch_prepare_nhi_from(State &st, const double *xh_av, bool need_transposed
     const int N = st.N;
     if (need_transposed)
         hipLaunchKernelGGL((prepare_nhi_kernel<true, false>), tile_grid(N), dim3(32, 8), 0, st.stream,
-                           st.grid[ASORA_GRID_NDENS], xh_av, st.nhi, st.nhi_t, N, 0, N, (double *)nullptr, st.ncell, st.lls_a, st.lls_b,
+                           st.grid[ASORA_GRID_NDENS], xh_av, st.nhi, st.nhi_t, N, 0, N, (double *)nullptr, st.ncell, st.medium.lls_a, st.medium.lls_b,
                            (const int *)nullptr);
     else
         hipLaunchKernelGGL((prepare_nhi_kernel<false, false>), tile_grid(N), dim3(32, 8), 0, st.stream,
-                           st.grid[ASORA_GRID_NDENS], xh_av, st.nhi, st.nhi_t, N, 0, N, (double *)nullptr, st.ncell, st.lls_a, st.lls_b,
+                           st.grid[ASORA_GRID_NDENS], xh_av, st.nhi, st.nhi_t, N, 0, N, (double *)nullptr, st.ncell, st.medium.lls_a, st.medium.lls_b,
                            (const int *)nullptr);
     ASORA_HIP_TRY(hipGetLastError());
     return 0;
@@ -114,11 +114,11 @@ int launch_prepare_range(State &st, int i_begin, int i_count, bool zero_acc, dou
     if (zero_acc)
         hipLaunchKernelGGL((prepare_nhi_kernel<true, true>), grid, dim3(32, 8), 0, st.stream, st.grid[ASORA_GRID_NDENS],
                            st.grid[ASORA_GRID_XH_AV], st.nhi, st.nhi_t, N, i_begin, i_begin + i_count, acc, st.ncell,
-                           st.lls_a, st.lls_b, done);
+                           st.medium.lls_a, st.medium.lls_b, done);
     else
         hipLaunchKernelGGL((prepare_nhi_kernel<true, false>), grid, dim3(32, 8), 0, st.stream, st.grid[ASORA_GRID_NDENS],
                            st.grid[ASORA_GRID_XH_AV], st.nhi, st.nhi_t, N, i_begin, i_begin + i_count, acc, st.ncell,
-                           st.lls_a, st.lls_b, done);
+                           st.medium.lls_a, st.medium.lls_b, done);
     ASORA_HIP_TRY(hipGetLastError());
     return 0;
 }

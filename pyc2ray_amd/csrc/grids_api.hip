@@ -18,7 +18,9 @@ int ensure_optional_grid(int which)
     State &st = state();
     if ((which != ASORA_GRID_PHI_HEAT && which != ASORA_GRID_TEMP_END && which != ASORA_GRID_CLUMP) || st.grid[which]) return 0;
     const bool twin = which == ASORA_GRID_PHI_HEAT;
-    ASORA_HIP_TRY(hipMalloc(&st.grid[which], (twin ? 2 : 1) * st.ncell * sizeof(double)));
+    MeshBuffer<double> &own = twin ? st.phi_heat_grid : which == ASORA_GRID_TEMP_END ? st.temp_end_grid : st.clump_grid;
+    if (int rc = own.allocate((twin ? 2 : 1) * st.ncell)) return rc;
+    st.grid[which] = own;
     if (twin) st.heat_t = st.grid[which] + st.ncell;
     st.grid_valid[which] = false;
     return 0;
@@ -39,7 +41,7 @@ int asora_grid_to_device(int which, const double *host, int N, char order)
     if (!host) return fail(3, "grid_to_device: null host pointer");
     State &st = state();
     if (int rc = ensure_optional_grid(which)) return rc;
-    st.zero_since_probe = std::max(st.zero_since_probe, 48);   // new medium: look again for cells beyond the table soon (decide_skip_zero: at 64)
+    st.zero.verdict.since_probe = std::max(st.zero.verdict.since_probe, 48);   // new medium: look again for cells beyond the table soon (decide_skip_zero: at 64)
     const size_t bytes = st.ncell * sizeof(double);
     if (order == 'C' || order == 'c') {
         ASORA_HIP_TRY(hipMemcpyAsync(st.grid[which], host, bytes, hipMemcpyHostToDevice, st.stream));
@@ -50,7 +52,7 @@ int asora_grid_to_device(int which, const double *host, int N, char order)
         return fail(3, "grid_to_device: order must be 'C' or 'F'");
     ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
     st.grid_valid[which] = true;
-    if (which == ASORA_GRID_TEMP) st.temp_probe_valid = false;
+    if (which == ASORA_GRID_TEMP) st.temp_probe.valid = false;
     return 0;
 }
 
@@ -87,7 +89,7 @@ int asora_grid_copy(int dst, int src)
     ASORA_HIP_TRY(hipMemcpyAsync(st.grid[dst], st.grid[src], st.ncell * sizeof(double), hipMemcpyDeviceToDevice,
                                  st.stream));
     st.grid_valid[dst] = true;
-    if (dst == ASORA_GRID_TEMP) st.temp_probe_valid = false;
+    if (dst == ASORA_GRID_TEMP) st.temp_probe.valid = false;
     return 0;
 }
 
@@ -99,7 +101,7 @@ int asora_grid_scale(int which, double factor)
     State &st = state();
     if (!st.grid_valid[which]) return fail(3, "grid_scale: grid " + std::to_string(which) + " holds no data");
     if (int rc = launch_scale(st, st.grid[which], st.ncell, factor)) return rc;
-    if (which == ASORA_GRID_TEMP) st.temp_probe_valid = false;
+    if (which == ASORA_GRID_TEMP) st.temp_probe.valid = false;
     return 0;
 }
 
@@ -111,9 +113,9 @@ int asora_grid_sum(int which, double *sum)
     if (!sum) return fail(3, "grid_sum: null output pointer");
     State &st = state();
     if (!st.grid_valid[which]) return fail(3, "grid_sum: grid " + std::to_string(which) + " holds no data");
-    if (!st.temp_probe_dev) ASORA_HIP_TRY(hipMalloc(&st.temp_probe_dev, sizeof(double) * 8));
-    if (int rc = launch_grid_sum(st, st.grid[which], st.ncell, st.temp_probe_dev + 5)) return rc;
-    ASORA_HIP_TRY(hipMemcpyAsync(sum, st.temp_probe_dev + 5, sizeof(double), hipMemcpyDeviceToHost, st.stream));
+    if (int rc = st.temp_probe.dev.allocate(8)) return rc;
+    if (int rc = launch_grid_sum(st, st.grid[which], st.ncell, st.temp_probe.dev + 5)) return rc;
+    ASORA_HIP_TRY(hipMemcpyAsync(sum, st.temp_probe.dev + 5, sizeof(double), hipMemcpyDeviceToHost, st.stream));
     ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
     return 0;
 }
@@ -158,9 +160,9 @@ static int upload_rate_tables(const char *who, int NumSpec, int NumTau, const do
     State &st = state();
     const bool heat = heat_thin && heat_thick;
     if (heat) { if (int rc = ensure_optional_grid(ASORA_GRID_PHI_HEAT)) return rc; }
-    st.zero_since_probe = std::max(st.zero_since_probe, 48);
-    if (st.tables) { (void)hipFree(st.tables); st.tables = nullptr; }
-    st.table_len = 0; st.num_spec = 1; st.spec_stride = 0; st.have_heat_tables = false;
+    st.zero.verdict.since_probe = std::max(st.zero.verdict.since_probe, 48);
+    (void)st.sources.tables.release();
+    st.sources.loaded.table_len = 0; st.sources.loaded.num_spec = 1; st.sources.loaded.spec_stride = 0; st.sources.loaded.heat_tables = false;
     const size_t block = rate_block_entries(NumTau);
     std::vector<double2> pairs(block * (size_t)NumSpec, double2{0.0, 0.0});
     for (int k = 0; k < NumSpec; ++k) {
@@ -173,12 +175,12 @@ static int upload_rate_tables(const char *who, int NumSpec, int NumTau, const do
         }
     }
     (void)who;
-    ASORA_HIP_TRY(hipMalloc(&st.tables, pairs.size() * sizeof(double2)));
-    ASORA_HIP_TRY(hipMemcpy(st.tables, pairs.data(), pairs.size() * sizeof(double2), hipMemcpyHostToDevice));
-    st.table_len = NumTau;
-    st.num_spec = NumSpec;
-    st.spec_stride = block;
-    st.have_heat_tables = heat;
+    if (int rc = st.sources.tables.allocate(pairs.size())) return rc;
+    ASORA_HIP_TRY(hipMemcpy(st.sources.tables, pairs.data(), pairs.size() * sizeof(double2), hipMemcpyHostToDevice));
+    st.sources.loaded.table_len = NumTau;
+    st.sources.loaded.num_spec = NumSpec;
+    st.sources.loaded.spec_stride = block;
+    st.sources.loaded.heat_tables = heat;
     return 0;
 }
 
@@ -195,21 +197,21 @@ int asora_heat_table_to_device(const double *heat_thin_table, const double *heat
     clear_error();
     if (int rc = require_init("heat_table_to_device")) return rc;
     State &st = state();
-    if (!st.tables) return fail(4, "heat_table_to_device: upload the photo tables first (photo_table_to_device)");
-    if (st.num_spec != 1)
-        return fail(4, "heat_table_to_device: " + std::to_string(st.num_spec) + " table sets are on the device; their heating tables go "
+    if (!st.sources.tables) return fail(4, "heat_table_to_device: upload the photo tables first (photo_table_to_device)");
+    if (st.sources.loaded.num_spec != 1)
+        return fail(4, "heat_table_to_device: " + std::to_string(st.sources.loaded.num_spec) + " table sets are on the device; their heating tables go "
                        "up with them (spectra_to_device)");
-    if (NumTau != st.table_len || !heat_thin_table || !heat_thick_table)
+    if (NumTau != st.sources.loaded.table_len || !heat_thin_table || !heat_thick_table)
         return fail(3, "heat_table_to_device: the heating tables must have the length of the photo tables (" +
-                           std::to_string(st.table_len) + ")");
+                           std::to_string(st.sources.loaded.table_len) + ")");
     if (int rc = ensure_optional_grid(ASORA_GRID_PHI_HEAT)) return rc;
     std::vector<double2> pairs(4 * (size_t)NumTau, double2{0.0, 0.0});
     pack_rate_table(pairs.data(), 2, heat_thick_table, NumTau);
     pack_rate_table(pairs.data(), 3, heat_thin_table, NumTau);
     const size_t lo = rate_table_byte_offset(2, NumTau), hi = rate_table_byte_offset(4, NumTau);
-    ASORA_HIP_TRY(hipMemcpy(reinterpret_cast<char *>(st.tables) + lo, reinterpret_cast<const char *>(pairs.data()) + lo, hi - lo,
+    ASORA_HIP_TRY(hipMemcpy(reinterpret_cast<char *>(st.sources.tables.get()) + lo, reinterpret_cast<const char *>(pairs.data()) + lo, hi - lo,
                             hipMemcpyHostToDevice));
-    st.have_heat_tables = true;
+    st.sources.loaded.heat_tables = true;
     return 0;
 }
 
@@ -225,7 +227,7 @@ int asora_spectra_to_device(int NumSpec, int NumTau, const double *photo_thin, c
     return upload_rate_tables("spectra_to_device", NumSpec, NumTau, photo_thin, photo_thick, heat_thin, heat_thick);
 }
 
-int asora_num_spectra(void) { return state().tables ? state().num_spec : 0; }
+int asora_num_spectra(void) { return state().sources.tables ? state().sources.loaded.num_spec : 0; }
 
 } // extern "C"
 
@@ -244,21 +246,20 @@ void sort_sources_by_position(const int32_t *pos, int NumSrc, std::vector<int> &
 
 static void drop_source_spectra(State &st)
 {
-    if (st.src_spec) { (void)hipFree(st.src_spec); st.src_spec = nullptr; }
-    if (st.src_spec_sorted) { (void)hipFree(st.src_spec_sorted); st.src_spec_sorted = nullptr; }
-    st.src_spec_max = 0;
+    (void)st.sources.spec.release(); (void)st.sources.spec_sorted.release();
+    st.sources.loaded.spec_max = 0;
 }
 
 int check_source_spectra(const char *who)
 {
     State &st = state();
-    if (!st.src_spec) return 0;
+    if (!st.sources.spec) return 0;
     if (st.opt[ASORA_OPT_GREY_NOTABLES])
         return fail(4, std::string(who) + ": grey opacity uses no tables, so sources cannot have table sets of their own "
                                           "(source_spectra_to_device with zeros, or ASORA_OPT_GREY_NOTABLES = 0)");
-    if (st.src_spec_max >= st.num_spec)
-        return fail(4, std::string(who) + ": a source has table set " + std::to_string(st.src_spec_max) + " but the device holds " +
-                           std::to_string(st.num_spec) + " (spectra_to_device)");
+    if (st.sources.loaded.spec_max >= st.sources.loaded.num_spec)
+        return fail(4, std::string(who) + ": a source has table set " + std::to_string(st.sources.loaded.spec_max) + " but the device holds " +
+                           std::to_string(st.sources.loaded.num_spec) + " (spectra_to_device)");
     return 0;
 }
 
@@ -272,27 +273,25 @@ int asora_source_data_to_device(const int32_t *pos, const double *flux, int NumS
     if (int rc = require_init("source_data_to_device")) return rc;
     if (NumSrc < 0 || (NumSrc > 0 && (!pos || !flux))) return fail(3, "source_data_to_device: bad arguments");
     State &st = state();
-    st.zero_since_probe = std::max(st.zero_since_probe, 48);
+    st.zero.verdict.since_probe = std::max(st.zero.verdict.since_probe, 48);
     // validate on the host before anything reaches a kernel: positions index the grid directly
     for (int s = 0; s < NumSrc; ++s)
         for (int ax = 0; ax < 3; ++ax)
             if (pos[3 * s + ax] < 0 || pos[3 * s + ax] >= st.N)
                 return fail(3, "source_data_to_device: source " + std::to_string(s) + " lies outside the mesh (0-based " +
                                    std::to_string(pos[3 * s + ax]) + " on axis " + std::to_string(ax) + ")");
-    if (st.src_pos) { (void)hipFree(st.src_pos); st.src_pos = nullptr; }          // memory.cu:102-103
-    if (st.src_flux) { (void)hipFree(st.src_flux); st.src_flux = nullptr; }
-    if (st.src_pos_sorted) { (void)hipFree(st.src_pos_sorted); st.src_pos_sorted = nullptr; }
-    if (st.src_flux_sorted) { (void)hipFree(st.src_flux_sorted); st.src_flux_sorted = nullptr; }
+    (void)st.sources.pos.release(); (void)st.sources.flux.release();          // memory.cu:102-103
+    (void)st.sources.pos_sorted.release(); (void)st.sources.flux_sorted.release();
     drop_source_spectra(st);              // every source back to table set 0
-    st.src_i0_sorted.clear();
-    st.src_pos_host.clear(); st.src_pos_sorted_host.clear();
+    st.sources.loaded.i0_sorted.clear();
+    st.sources.loaded.pos_host.clear(); st.sources.loaded.pos_sorted_host.clear();
     release_pair_lists(st);
-    st.num_src = 0;
+    st.sources.loaded.num = 0;
     if (NumSrc == 0) return 0;
-    ASORA_HIP_TRY(hipMalloc(&st.src_pos, sizeof(int32_t) * 3 * (size_t)NumSrc));
-    ASORA_HIP_TRY(hipMalloc(&st.src_flux, sizeof(double) * (size_t)NumSrc));
-    ASORA_HIP_TRY(hipMemcpy(st.src_pos, pos, sizeof(int32_t) * 3 * (size_t)NumSrc, hipMemcpyHostToDevice));
-    ASORA_HIP_TRY(hipMemcpy(st.src_flux, flux, sizeof(double) * (size_t)NumSrc, hipMemcpyHostToDevice));
+    if (int rc = st.sources.pos.allocate(3 * (size_t)NumSrc)) return rc;
+    if (int rc = st.sources.flux.allocate((size_t)NumSrc)) return rc;
+    ASORA_HIP_TRY(hipMemcpy(st.sources.pos, pos, sizeof(int32_t) * 3 * (size_t)NumSrc, hipMemcpyHostToDevice));
+    ASORA_HIP_TRY(hipMemcpy(st.sources.flux, flux, sizeof(double) * (size_t)NumSrc, hipMemcpyHostToDevice));
     {   // a second copy in lexicographic order of the position (the sum over sources does not depend on their order): what
         // a call that traces the WHOLE list works from -- sources that run side by side are then neighbours in space and
         // share nHI and rate lines (measured -2 % on the trace at r_RT = 16 and 32) -- and, ordered by the first
@@ -301,21 +300,21 @@ int asora_source_data_to_device(const int32_t *pos, const double *flux, int NumS
         sort_sources_by_position(pos, NumSrc, order);
         std::vector<int32_t> ps(3 * (size_t)NumSrc);
         std::vector<double> fs((size_t)NumSrc);
-        st.src_i0_sorted.resize((size_t)NumSrc);
+        st.sources.loaded.i0_sorted.resize((size_t)NumSrc);
         for (int s = 0; s < NumSrc; ++s) {
             const int o = order[s];
             ps[3 * s] = pos[3 * o]; ps[3 * s + 1] = pos[3 * o + 1]; ps[3 * s + 2] = pos[3 * o + 2];
             fs[s] = flux[o];
-            st.src_i0_sorted[s] = pos[3 * o];
+            st.sources.loaded.i0_sorted[s] = pos[3 * o];
         }
-        ASORA_HIP_TRY(hipMalloc(&st.src_pos_sorted, sizeof(int32_t) * 3 * (size_t)NumSrc));
-        ASORA_HIP_TRY(hipMalloc(&st.src_flux_sorted, sizeof(double) * (size_t)NumSrc));
-        ASORA_HIP_TRY(hipMemcpy(st.src_pos_sorted, ps.data(), sizeof(int32_t) * 3 * (size_t)NumSrc, hipMemcpyHostToDevice));
-        ASORA_HIP_TRY(hipMemcpy(st.src_flux_sorted, fs.data(), sizeof(double) * (size_t)NumSrc, hipMemcpyHostToDevice));
-        st.src_pos_sorted_host.swap(ps);
+        if (int rc = st.sources.pos_sorted.allocate(3 * (size_t)NumSrc)) return rc;
+        if (int rc = st.sources.flux_sorted.allocate((size_t)NumSrc)) return rc;
+        ASORA_HIP_TRY(hipMemcpy(st.sources.pos_sorted, ps.data(), sizeof(int32_t) * 3 * (size_t)NumSrc, hipMemcpyHostToDevice));
+        ASORA_HIP_TRY(hipMemcpy(st.sources.flux_sorted, fs.data(), sizeof(double) * (size_t)NumSrc, hipMemcpyHostToDevice));
+        st.sources.loaded.pos_sorted_host.swap(ps);
     }
-    st.src_pos_host.assign(pos, pos + 3 * (size_t)NumSrc);
-    st.num_src = NumSrc;
+    st.sources.loaded.pos_host.assign(pos, pos + 3 * (size_t)NumSrc);
+    st.sources.loaded.num = NumSrc;
     st.src_generation += 1;
     return 0;
 }
@@ -325,14 +324,14 @@ int asora_source_spectra_to_device(const int32_t *spec, int NumSrc)
     clear_error();
     if (int rc = require_init("source_spectra_to_device")) return rc;
     State &st = state();
-    if (NumSrc != st.num_src)
-        return fail(3, "source_spectra_to_device: " + std::to_string(NumSrc) + " table sets for the " + std::to_string(st.num_src) +
+    if (NumSrc != st.sources.loaded.num)
+        return fail(3, "source_spectra_to_device: " + std::to_string(NumSrc) + " table sets for the " + std::to_string(st.sources.loaded.num) +
                            " sources on the device (source_data_to_device first)");
     drop_source_spectra(st);
     if (!spec || NumSrc == 0) return 0;
     // validated on the host: the index becomes an offset on the table pointer.  Against the sets on the device now, if any; a
     // table upload that follows is met by check_source_spectra before the first trace
-    const int limit = st.tables ? st.num_spec : ASORA_MAX_SPECTRA;
+    const int limit = st.sources.tables ? st.sources.loaded.num_spec : ASORA_MAX_SPECTRA;
     int top = 0;
     for (int s = 0; s < NumSrc; ++s) {
         if (spec[s] < 0 || spec[s] >= limit)
@@ -342,14 +341,14 @@ int asora_source_spectra_to_device(const int32_t *spec, int NumSrc)
     }
     if (top == 0) return 0;               // all set 0: the launches carry no array at all
     std::vector<int> order;
-    sort_sources_by_position(st.src_pos_host.data(), NumSrc, order);
+    sort_sources_by_position(st.sources.loaded.pos_host.data(), NumSrc, order);
     std::vector<int32_t> sorted((size_t)NumSrc);
     for (int s = 0; s < NumSrc; ++s) sorted[s] = spec[order[s]];
-    ASORA_HIP_TRY(hipMalloc(&st.src_spec, sizeof(int32_t) * (size_t)NumSrc));
-    ASORA_HIP_TRY(hipMalloc(&st.src_spec_sorted, sizeof(int32_t) * (size_t)NumSrc));
-    ASORA_HIP_TRY(hipMemcpy(st.src_spec, spec, sizeof(int32_t) * (size_t)NumSrc, hipMemcpyHostToDevice));
-    ASORA_HIP_TRY(hipMemcpy(st.src_spec_sorted, sorted.data(), sizeof(int32_t) * (size_t)NumSrc, hipMemcpyHostToDevice));
-    st.src_spec_max = top;
+    if (int rc = st.sources.spec.allocate((size_t)NumSrc)) return rc;
+    if (int rc = st.sources.spec_sorted.allocate((size_t)NumSrc)) return rc;
+    ASORA_HIP_TRY(hipMemcpy(st.sources.spec, spec, sizeof(int32_t) * (size_t)NumSrc, hipMemcpyHostToDevice));
+    ASORA_HIP_TRY(hipMemcpy(st.sources.spec_sorted, sorted.data(), sizeof(int32_t) * (size_t)NumSrc, hipMemcpyHostToDevice));
+    st.sources.loaded.spec_max = top;
     return 0;
 }
 
@@ -403,7 +402,7 @@ int asora_planes_to_device(int which, int i_begin, int i_count, const double *ho
                                  hipMemcpyHostToDevice, st.stream));
     ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
     st.grid_valid[which] = true;             // (the caller vouches for the planes it did not write)
-    if (which == ASORA_GRID_TEMP) st.temp_probe_valid = false;
+    if (which == ASORA_GRID_TEMP) st.temp_probe.valid = false;
     return 0;
 }
 

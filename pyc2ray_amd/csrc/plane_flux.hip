@@ -128,12 +128,12 @@ int check_plane_flux(const State &st, const PlaneFluxSet &pf, const char *who, b
     const std::string w = std::string(who) + ": a plane-parallel flux (asora_plane_flux) ";
     if (st.opt[ASORA_OPT_GREY_NOTABLES]) return fail(4, w + "needs table rates (grey opacity, ASORA_OPT_GREY_NOTABLES, is on)");
     if (dump) return fail(4, w + "has no column-density dump (the dump is of one point source)");
-    if (!st.tables) return fail(4, w + "needs the radiation tables on the device (photo_table_to_device)");
-    if (heat && !st.have_heat_tables) return fail(4, w + "with heating needs heating tables on the device (heat_table_to_device)");
+    if (!st.sources.tables) return fail(4, w + "needs the radiation tables on the device (photo_table_to_device)");
+    if (heat && !st.sources.loaded.heat_tables) return fail(4, w + "with heating needs heating tables on the device (heat_table_to_device)");
     if (st.ncell >= ((size_t)1 << 32)) return fail(4, w + "is built for meshes below 2^32 cells");
     for (int q = 0; q < pf.count; ++q) {
-        if (pf.spec[q] >= st.num_spec)
-            return fail(4, w + "has table set " + std::to_string(pf.spec[q]) + " but the device holds " + std::to_string(st.num_spec) +
+        if (pf.spec[q] >= st.sources.loaded.num_spec)
+            return fail(4, w + "has table set " + std::to_string(pf.spec[q]) + " but the device holds " + std::to_string(st.sources.loaded.num_spec) +
                                " (asora_spectra_to_device)");
         if (pf.face[q] >= 4 && !st.opt[ASORA_OPT_Z_TRANSPOSED])
             return fail(4, w + "through a z face needs the [k][j][i] twins (ASORA_OPT_Z_TRANSPOSED = 1)");
@@ -182,7 +182,7 @@ int asora_plane_flux(int count, const int32_t *face, const double *flux, const i
     clear_error();
     State &st = state();
     if (count < 0 || count > 6) return fail(3, "plane_flux: count must be 0 ... 6 (one entry per face at most)");
-    if (count == 0) { st.plane = PlaneFluxSet{}; return 0; }          // (also without a device: nothing to switch off)
+    if (count == 0) { st.medium.plane = PlaneFluxSet{}; return 0; }          // (also without a device: nothing to switch off)
     if (!face || !flux) return fail(3, "plane_flux: null face / flux");
     PlaneFluxSet pf{};
     for (int q = 0; q < count; ++q) {
@@ -195,14 +195,14 @@ int asora_plane_flux(int count, const int32_t *face, const double *flux, const i
     }
     pf.count = count;
     if (int rc = require_init("plane_flux")) return rc;
-    st.plane = pf;
+    st.medium.plane = pf;
     return 0;
 }
 
 int asora_get_plane_flux(int *count, int32_t *face, double *flux, int32_t *spectrum)
 {
     clear_error();
-    const PlaneFluxSet &pf = state().plane;
+    const PlaneFluxSet &pf = state().medium.plane;
     if (count) *count = pf.count;
     for (int q = 0; q < pf.count; ++q) {
         if (face) face[q] = pf.face[q];

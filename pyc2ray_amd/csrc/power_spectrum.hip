@@ -245,11 +245,11 @@ static int ensure_ps_buffers(State &st, const PsLayout &lay, bool cross)
     const int N = st.N;
     const size_t nmodes = (size_t)N * N * (N / 2 + 1);
     for (int f = 0; f < (cross ? 2 : 1); ++f)
-        if (!st.ps_modes[f]) ASORA_HIP_TRY(hipMalloc(&st.ps_modes[f], sizeof(double2) * nmodes));
-    if (!st.ps_partial) ASORA_HIP_TRY(hipMalloc(&st.ps_partial, sizeof(double) * lay.words));
-    if (!st.ps_thresholds) ASORA_HIP_TRY(hipMalloc(&st.ps_thresholds, sizeof(unsigned) * (ASORA_BUBBLE_MAX_BINS + 1)));
-    if (!st.ps_host) ASORA_HIP_TRY(hipHostMalloc(&st.ps_host, sizeof(double) * PS_HOST_WORDS));
-    if (!st.ps_twiddle) {
+        if (int rc = st.spectrum.modes[f].allocate(nmodes)) return rc;
+    if (int rc = st.spectrum.partial.allocate(lay.words)) return rc;
+    if (int rc = st.spectrum.thresholds.allocate((ASORA_BUBBLE_MAX_BINS + 1))) return rc;
+    if (int rc = st.spectrum.host.allocate(PS_HOST_WORDS)) return rc;
+    if (!st.spectrum.twiddle) {
         // exp(-2 pi i r / N) from the first octant's cos and sin in extended precision, so that the symmetries hold to the bit
         std::vector<double2> tw((size_t)N);
         const long double two_pi = 6.283185307179586476925286766559005768L;
@@ -273,18 +273,13 @@ static int ensure_ps_buffers(State &st, const PsLayout &lay, bool cross)
             }
             tw[r] = make_double2((double)co, (double)(0.0L - si));
         }
-        ASORA_HIP_TRY(hipMalloc(&st.ps_twiddle, sizeof(double2) * N));
-        ASORA_HIP_TRY(hipMemcpy(st.ps_twiddle, tw.data(), sizeof(double2) * N, hipMemcpyHostToDevice));
+        if (int rc = st.spectrum.twiddle.allocate((size_t)N)) return rc;
+        ASORA_HIP_TRY(hipMemcpy(st.spectrum.twiddle, tw.data(), sizeof(double2) * N, hipMemcpyHostToDevice));
     }
     return 0;
 }
 
 using PsStopwatch = StageStopwatch<ASORA_PS_STAGES>;
-
-struct PsFieldCopy {                     // the formed field on the device, for field_out: freed when the call ends, however it ends
-    double *dev = nullptr;
-    ~PsFieldCopy() { (void)hipFree(dev); }
-};
 
 static bool ps_kind_uses(int kind, int grid, double t_gamma)
 {
@@ -298,7 +293,7 @@ static bool ps_kind_uses(int kind, int grid, double t_gamma)
 bool ps_needs_grid(int kind, int grid, double t_gamma) { return ps_kind_uses(kind, grid, t_gamma); }
 
 // The launches of stages a to c on the library's stream, for asora_power_spectrum and for ps_forward: field f of a kind goes into
-// st.ps_modes[f], its moments into the result words
+// st.spectrum.modes[f], its moments into the result words
 struct PsPasses {
     State &st;
     const int N, NZ, T, pitch;
@@ -309,8 +304,8 @@ struct PsPasses {
     explicit PsPasses(State &s)
         : st(s), N(s.N), NZ(s.N / 2 + 1), T(ps_tile(s.N)), pitch(s.N | 1), lay(s.N, ps_tile(s.N)), plan(ps_plan(s.N)),
           fft_lds(((size_t)2 * ps_tile(s.N) * (s.N | 1) + s.N) * sizeof(double2)) {}
-    double *partial() const { return st.ps_partial; }
-    double *result() const { return st.ps_partial + lay.result; }
+    double *partial() const { return st.spectrum.partial; }
+    double *result() const { return st.spectrum.partial + lay.result; }
     int prepare(bool cross)
     {
         if (int rc = ensure_ps_buffers(st, lay, cross)) return rc;
@@ -334,7 +329,7 @@ struct PsPasses {
         hipLaunchKernelGGL(ps_row_kernel, dim3((unsigned)lay.row_blocks), block, fft_lds, st.stream, kind,
                            x, (const double *)st.grid[ASORA_GRID_NDENS],
                            (const double *)st.grid[ASORA_GRID_TEMP], nbar ? (const double *)(result() + PS_RES_NBAR) : (const double *)nullptr,
-                           scale, t_gamma, N, pitch, T, plan, (const double2 *)st.ps_twiddle, st.ps_modes[f], partial() + lay.moments[f],
+                           scale, t_gamma, N, pitch, T, plan, (const double2 *)st.spectrum.twiddle, st.spectrum.modes[f], partial() + lay.moments[f],
                            field);
         ASORA_HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(ps_final_kernel, dim3(1), block, 0, st.stream, (const double *)(partial() + lay.moments[f]), (int)lay.row_blocks,
@@ -345,22 +340,22 @@ struct PsPasses {
     int lines_j(int f)                  // N blocks (the planes i) of N lines, NZ columns wide
     {
         const unsigned tiles = (unsigned)((NZ + T - 1) / T);
-        hipLaunchKernelGGL(ps_line_kernel, dim3((unsigned)N * tiles), block, fft_lds, st.stream, st.ps_modes[f], N, pitch, T, plan,
-                           (const double2 *)st.ps_twiddle, (size_t)N * NZ, (size_t)NZ, (size_t)NZ, tiles);
+        hipLaunchKernelGGL(ps_line_kernel, dim3((unsigned)N * tiles), block, fft_lds, st.stream, st.spectrum.modes[f], N, pitch, T, plan,
+                           (const double2 *)st.spectrum.twiddle, (size_t)N * NZ, (size_t)NZ, (size_t)NZ, tiles);
         ASORA_HIP_TRY(hipGetLastError());
         return 0;
     }
     int lines_i(int f)                  // one block of N lines, N NZ columns wide
     {
         const unsigned tiles = (unsigned)(((size_t)N * NZ + T - 1) / T);
-        hipLaunchKernelGGL(ps_line_kernel, dim3(tiles), block, fft_lds, st.stream, st.ps_modes[f], N, pitch, T, plan,
-                           (const double2 *)st.ps_twiddle, (size_t)0, (size_t)N * NZ, (size_t)N * NZ, tiles);
+        hipLaunchKernelGGL(ps_line_kernel, dim3(tiles), block, fft_lds, st.stream, st.spectrum.modes[f], N, pitch, T, plan,
+                           (const double2 *)st.spectrum.twiddle, (size_t)0, (size_t)N * NZ, (size_t)N * NZ, tiles);
         ASORA_HIP_TRY(hipGetLastError());
         return 0;
     }
 };
 
-// The forward half of asora_smooth_field (smooth_field.hip): stages a to c above for the one field of `kind`, into st.ps_modes[0] --
+// The forward half of asora_smooth_field (smooth_field.hip): stages a to c above for the one field of `kind`, into st.spectrum.modes[0] --
 // the launches of an auto-spectrum, so the modes and the moments are its bits.  The caller has checked the kind and its grids.
 // stage_done is called behind each of the four stages (mean density, along k, j, i); *moments_dev: where (sum g, sum g^2) lie on the
 // device once the stream has got there
@@ -443,14 +438,14 @@ int asora_power_spectrum(int kind_a, int kind_b, double scale, double t_gamma, i
     const size_t ncell = st.ncell, nmodes = (size_t)N * N * pass.NZ;
     const PsLayout &lay = pass.lay;
     if (int rc = pass.prepare(cross)) return rc;
-    PsFieldCopy field;
-    if (field_out) ASORA_HIP_TRY(hipMalloc(&field.dev, sizeof(double) * ncell));
+    Scoped<double> field;                // the formed field on the device, for field_out
+    if (field_out) { if (int rc = field.allocate(ncell)) return rc; }
 
     const size_t bin_lds = (size_t)PS_WAVES * PS_VALUES * n_bins * sizeof(double) + sizeof(unsigned) * (n_bins + 1);
     double *part = pass.partial(), *res = pass.result();
-    unsigned *thr_host = (unsigned *)(st.ps_host + PS_RES_WORDS);
+    unsigned *thr_host = (unsigned *)(st.spectrum.host + PS_RES_WORDS);
     std::memcpy(thr_host, thresholds, sizeof(unsigned) * (n_bins + 1));
-    ASORA_HIP_TRY(hipMemcpyAsync(st.ps_thresholds, thr_host, sizeof(unsigned) * (n_bins + 1), hipMemcpyHostToDevice, st.stream));
+    ASORA_HIP_TRY(hipMemcpyAsync(st.spectrum.thresholds, thr_host, sizeof(unsigned) * (n_bins + 1), hipMemcpyHostToDevice, st.stream));
     ASORA_HIP_TRY(hipMemsetAsync(res, 0, sizeof(double) * PS_RES_WORDS, st.stream));
     const dim3 block(PS_THREADS);
     PsStopwatch watch(st.opt[ASORA_OPT_TIMING] != 0, st.stream);
@@ -460,7 +455,7 @@ int asora_power_spectrum(int kind_a, int kind_b, double scale, double t_gamma, i
         if (int rc = pass.mean_density()) return rc;
     if (int rc = watch.mark()) return rc;
     for (int f = 0; f < nf; ++f)
-        if (int rc = pass.rows(f, kinds[f], need[1], scale, t_gamma, f == 0 ? field.dev : (double *)nullptr, st.grid[ASORA_GRID_XH])) return rc;
+        if (int rc = pass.rows(f, kinds[f], need[1], scale, t_gamma, f == 0 ? field.get() : (double *)nullptr, st.grid[ASORA_GRID_XH])) return rc;
     if (int rc = watch.mark()) return rc;
     for (int f = 0; f < nf; ++f)
         if (int rc = pass.lines_j(f)) return rc;
@@ -470,24 +465,24 @@ int asora_power_spectrum(int kind_a, int kind_b, double scale, double t_gamma, i
     if (int rc = watch.mark()) return rc;
     const int nv = cross ? PS_VALUES : PS_SUM_AA + 1;
     if (cross)
-        hipLaunchKernelGGL(ps_bin_kernel<true>, dim3((unsigned)N), block, bin_lds, st.stream, (const double2 *)st.ps_modes[0],
-                           (const double2 *)st.ps_modes[1], N, n_bins, (const unsigned *)st.ps_thresholds, part + lay.bins);
+        hipLaunchKernelGGL(ps_bin_kernel<true>, dim3((unsigned)N), block, bin_lds, st.stream, (const double2 *)st.spectrum.modes[0],
+                           (const double2 *)st.spectrum.modes[1], N, n_bins, (const unsigned *)st.spectrum.thresholds, part + lay.bins);
     else
-        hipLaunchKernelGGL(ps_bin_kernel<false>, dim3((unsigned)N), block, bin_lds, st.stream, (const double2 *)st.ps_modes[0],
-                           (const double2 *)nullptr, N, n_bins, (const unsigned *)st.ps_thresholds, part + lay.bins);
+        hipLaunchKernelGGL(ps_bin_kernel<false>, dim3((unsigned)N), block, bin_lds, st.stream, (const double2 *)st.spectrum.modes[0],
+                           (const double2 *)nullptr, N, n_bins, (const unsigned *)st.spectrum.thresholds, part + lay.bins);
     ASORA_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(ps_bin_final_kernel, dim3((unsigned)((nv * n_bins + PS_THREADS - 1) / PS_THREADS)), block, 0, st.stream,
                        (const double *)(part + lay.bins), N, n_bins, nv, res);
     ASORA_HIP_TRY(hipGetLastError());
     if (int rc = watch.mark()) return rc;
 
-    ASORA_HIP_TRY(hipMemcpyAsync(st.ps_host, res, sizeof(double) * PS_RES_WORDS, hipMemcpyDeviceToHost, st.stream));
-    if (field_out) ASORA_HIP_TRY(hipMemcpyAsync(field_out, field.dev, sizeof(double) * ncell, hipMemcpyDeviceToHost, st.stream));
-    if (modes_out) ASORA_HIP_TRY(hipMemcpyAsync(modes_out, st.ps_modes[0], sizeof(double2) * nmodes, hipMemcpyDeviceToHost, st.stream));
+    ASORA_HIP_TRY(hipMemcpyAsync(st.spectrum.host, res, sizeof(double) * PS_RES_WORDS, hipMemcpyDeviceToHost, st.stream));
+    if (field_out) ASORA_HIP_TRY(hipMemcpyAsync(field_out, field.get(), sizeof(double) * ncell, hipMemcpyDeviceToHost, st.stream));
+    if (modes_out) ASORA_HIP_TRY(hipMemcpyAsync(modes_out, st.spectrum.modes[0], sizeof(double2) * nmodes, hipMemcpyDeviceToHost, st.stream));
     ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
-    watch.read(st.ps_ms);
+    watch.read(st.spectrum.ms);
 
-    const double *h = st.ps_host;
+    const double *h = st.spectrum.host;
     std::memcpy(count, h + PS_COUNT * ASORA_BUBBLE_MAX_BINS, sizeof(unsigned long long) * n_bins);
     std::memcpy(sum_k, h + PS_SUM_K * ASORA_BUBBLE_MAX_BINS, sizeof(double) * n_bins);
     std::memcpy(sum_aa, h + PS_SUM_AA * ASORA_BUBBLE_MAX_BINS, sizeof(double) * n_bins);
@@ -504,7 +499,7 @@ int asora_debug_power_spectrum_ms(double *ms)
 {
     clear_error();
     if (!ms) return fail(3, "debug_power_spectrum_ms: null pointer");
-    for (int q = 0; q < ASORA_PS_STAGES; ++q) ms[q] = state().ps_ms[q];
+    for (int q = 0; q < ASORA_PS_STAGES; ++q) ms[q] = state().spectrum.ms[q];
     return 0;
 }
 

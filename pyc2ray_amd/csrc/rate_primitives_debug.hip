@@ -63,20 +63,6 @@ static void launch_prim(State &st, const RtParams *p, const PrimArgs &k)
     hipLaunchKernelGGL(rate_primitives_kernel<OP>, dim3((unsigned)blocks), dim3(PRIM_THREADS), 0, st.stream, p, k);
 }
 
-// device buffers of one call, released however the call ends
-struct PrimBuffers {
-    std::vector<void *> owned;
-    ~PrimBuffers() { for (void *q : owned) (void)hipFree(q); }
-    hipError_t get(double **q, size_t doubles)
-    {
-        void *v = nullptr;
-        const hipError_t e = hipMalloc(&v, doubles * sizeof(double));
-        if (e == hipSuccess) owned.push_back(v);
-        *q = static_cast<double *>(v);
-        return e;
-    }
-};
-
 } // namespace asora
 
 using namespace asora;
@@ -97,53 +83,51 @@ extern "C" int asora_debug_rate_primitives(int op, size_t n, const double *a, co
     if (tables) {
         if (which < 0 || which > 3) return fail(3, "debug_rate_primitives: which must be 0 ... 3 (thick, thin, heat thick, heat thin)");
         if (NumTau < 1) return fail(3, "debug_rate_primitives: NumTau must be >= 1");
-        if (!st.tables) return fail(4, "debug_rate_primitives: radiation tables not on device (photo_table_to_device)");
-        if ((op == ASORA_PRIM_HEAT || (op == ASORA_PRIM_LOOKUP && (which & 2))) && !st.have_heat_tables)
+        if (!st.sources.tables) return fail(4, "debug_rate_primitives: radiation tables not on device (photo_table_to_device)");
+        if ((op == ASORA_PRIM_HEAT || (op == ASORA_PRIM_LOOKUP && (which & 2))) && !st.sources.loaded.heat_tables)
             return fail(4, "debug_rate_primitives: heating tables not on device (heat_table_to_device)");
-        if (spectrum < 0 || spectrum >= st.num_spec)
-            return fail(4, "debug_rate_primitives: table set " + std::to_string(spectrum) + " but the device holds " + std::to_string(st.num_spec) +
+        if (spectrum < 0 || spectrum >= st.sources.loaded.num_spec)
+            return fail(4, "debug_rate_primitives: table set " + std::to_string(spectrum) + " but the device holds " + std::to_string(st.sources.loaded.num_spec) +
                                " (spectra_to_device)");
     }
     if (n == 0) return 0;
     if (int rc = ensure_logtab(st)) return rc;
 
     // the parameter block of a trace, as launch_raytrace completes it (this is no trace: the radius history stays as it was)
-    State::RadiusHistory history[2] = {st.rt_radius[0], st.rt_radius[1]};
+    State::RadiusHistory history[2] = {st.rt.radius[0], st.rt.radius[1]};
     RtParams p;
     fill_rt_params(p, 0.0, sig, 1.0, minlogtau, dlogtau, NumTau);
-    st.rt_radius[0] = history[0]; st.rt_radius[1] = history[1];
+    st.rt.radius[0] = history[0]; st.rt.radius[1] = history[1];
     const LutIndex lut = lut_index_constants(p.minlogtau, p.dlogtau);
     p.lut_k1 = lut.k1; p.lut_k0 = lut.k0; p.lut_kc = lut.kc;
     p.logtab = st.logtab_dev;
 
-    PrimBuffers buf;
+    Scoped<double> dev[4], d_out, d_out2, d_ramp, d_params;     // device buffers of this call, released however it ends
     PrimArgs k;
     std::memset(&k, 0, sizeof k);
     k.n = n; k.which = which;
-    double *dev[4] = {nullptr, nullptr, nullptr, nullptr};
     for (int q = 0; q < inputs; ++q) {
-        ASORA_HIP_TRY(buf.get(&dev[q], n));
+        if (int rc = dev[q].allocate(n)) return rc;
         ASORA_HIP_TRY(hipMemcpyAsync(dev[q], in[q], n * sizeof(double), hipMemcpyHostToDevice, st.stream));
     }
     k.a = dev[0]; k.b = dev[1]; k.c = dev[2]; k.d = dev[3];
-    ASORA_HIP_TRY(buf.get(&k.out, n));
-    if (op == ASORA_PRIM_LOOKUP) ASORA_HIP_TRY(buf.get(&k.out2, n));
+    if (int rc = d_out.allocate(n)) return rc;
+    if (op == ASORA_PRIM_LOOKUP) { if (int rc = d_out2.allocate(n)) return rc; }
+    k.out = d_out; k.out2 = d_out2;
     std::vector<double> ramp;
     if (tables) {
         k.tab = p.tables + (size_t)spectrum * p.spec_stride;
         if (op == ASORA_PRIM_LOOKUP) {
             ramp.resize((size_t)4 * table_stride(p.table_len));
             for (size_t j = 0; j < ramp.size(); ++j) ramp[j] = (double)j;
-            double *r = nullptr;
-            ASORA_HIP_TRY(buf.get(&r, ramp.size()));
-            ASORA_HIP_TRY(hipMemcpyAsync(r, ramp.data(), ramp.size() * sizeof(double), hipMemcpyHostToDevice, st.stream));
-            k.ramp = reinterpret_cast<const double2 *>(r);
+            if (int rc = d_ramp.allocate(ramp.size())) return rc;
+            ASORA_HIP_TRY(hipMemcpyAsync(d_ramp, ramp.data(), ramp.size() * sizeof(double), hipMemcpyHostToDevice, st.stream));
+            k.ramp = reinterpret_cast<const double2 *>(d_ramp.get());
         }
     }
-    double *p_dev = nullptr;
-    ASORA_HIP_TRY(buf.get(&p_dev, (sizeof(RtParams) + sizeof(double) - 1) / sizeof(double)));
-    ASORA_HIP_TRY(hipMemcpyAsync(p_dev, &p, sizeof(RtParams), hipMemcpyHostToDevice, st.stream));
-    const RtParams *pd = reinterpret_cast<const RtParams *>(p_dev);
+    if (int rc = d_params.allocate((sizeof(RtParams) + sizeof(double) - 1) / sizeof(double))) return rc;
+    ASORA_HIP_TRY(hipMemcpyAsync(d_params, &p, sizeof(RtParams), hipMemcpyHostToDevice, st.stream));
+    const RtParams *pd = reinterpret_cast<const RtParams *>(d_params.get());
     switch (op) {
     case ASORA_PRIM_LOG2: launch_prim<ASORA_PRIM_LOG2>(st, pd, k); break;
     case ASORA_PRIM_LOOKUP: launch_prim<ASORA_PRIM_LOOKUP>(st, pd, k); break;

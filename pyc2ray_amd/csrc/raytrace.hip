@@ -836,12 +836,16 @@ int check_open_boundaries(const State &st, const char *who, bool open, bool dump
 
 // Who shares a workgroup with whom when the tables are the aligned kind (pairs_by_class, raytrace_plan.hpp), and the dispatch
 // orders: cached on the device per (list, range), dropped with every change of the source lists
+static void release_order_lists(State &st)
+{
+    for (auto &e : st.order_lists) if (e.dev) (void)hipFree(e.dev);
+    st.order_lists.clear();
+}
 void release_pair_lists(State &st)
 {
     for (auto &e : st.pair_lists) for (int ft = 0; ft < 2; ++ft) if (e.dev[ft]) (void)hipFree(e.dev[ft]);
     st.pair_lists.clear();
-    for (auto &e : st.order_lists) if (e.dev) (void)hipFree(e.dev);
-    st.order_lists.clear();
+    release_order_lists(st);
 }
 
 static int source_pairs_by_class(State &st, const int32_t *host_pos, const void *list, int begin, int count, const State::PairList *&out)
@@ -855,7 +859,7 @@ static int source_pairs_by_class(State &st, const int32_t *host_pos, const void 
         std::vector<SrcPair> pairs;
         pairs_by_class(host_pos, begin, count, ft, pairs, e.cls[ft]);
         e.n[ft] = (int)pairs.size();
-        ASORA_HIP_TRY(hipMalloc(&e.dev[ft], std::max<size_t>(1, pairs.size()) * sizeof(int2)));
+        if (int rc = device_allocate(e.dev[ft], std::max<size_t>(1, pairs.size()))) return rc;
         ASORA_HIP_TRY(hipMemcpy(e.dev[ft], pairs.data(), pairs.size() * sizeof(int2), hipMemcpyHostToDevice));
     }
     st.pair_lists.push_back(e);
@@ -887,10 +891,7 @@ static int set_launch_grid(State &st, RtParams &q, int units, bool pairs, bool a
             q.order = e.dev; grid = e.grid;
             return 0;
         }
-    if (st.order_lists.size() >= 64) {
-        for (auto &e : st.order_lists) if (e.dev) (void)hipFree(e.dev);
-        st.order_lists.clear();
-    }
+    if (st.order_lists.size() >= 64) release_order_lists(st);
     std::vector<int> face_type((size_t)units);
     for (int u = 0; u < units; ++u) {
         face_type[(size_t)u] = ((st.geom_host[u].info >> 8) & 3) == 3 ? 1 : 0;
@@ -904,7 +905,7 @@ static int set_launch_grid(State &st, RtParams &q, int units, bool pairs, bool a
     e.grid = launch_block_order(host_pos, q.src_begin, q.src_count, units, face_type.data(), pairs, aligned, pl ? pl->n : none, pl ? pair_cls : no_cls, order);
     if (e.grid == 0 || e.grid > grid) return fail(11, "raytrace: dispatch order of " + std::to_string(e.grid) + " blocks (internal error)");
     static_assert(sizeof(int2) == 2 * sizeof(int32_t), "an entry of the dispatch order is {group, unit}");
-    ASORA_HIP_TRY(hipMalloc(&e.dev, order.size() * sizeof(int32_t)));
+    if (int rc = device_allocate(e.dev, (order.size() + 1) / 2)) return rc;
     ASORA_HIP_TRY(hipMemcpy(e.dev, order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     st.order_lists.push_back(e);
     q.order = e.dev; grid = e.grid;
@@ -936,21 +937,21 @@ static int decide_skip_zero(State &st, bool exists, bool &skip_zero, bool &probe
     const int skip_zero_opt = st.opt[ASORA_OPT_SKIP_ZERO_RATES];
     if (exists && skip_zero_opt == 1) skip_zero = true;
     else if (exists && skip_zero_opt == 0) {
-        if (!st.zero_probe_dev) {
-            ASORA_HIP_TRY(hipMalloc(&st.zero_probe_dev, 2 * ZERO_PROBE_SLOTS * sizeof(unsigned long long)));
-            ASORA_HIP_TRY(hipHostMalloc(&st.zero_probe_host, 2 * sizeof(unsigned long long), hipHostMallocDefault));
-            ASORA_HIP_TRY(hipEventCreateWithFlags(&st.zero_probe_done, hipEventDisableTiming));
+        if (!st.zero.dev) {
+            if (int rc = st.zero.dev.allocate(2 * ZERO_PROBE_SLOTS)) return rc;
+            if (int rc = st.zero.host.allocate(2)) return rc;
+            ASORA_HIP_TRY(hipEventCreateWithFlags(&st.zero.done, hipEventDisableTiming));
         }
-        if (st.zero_probe_pending && hipEventQuery(st.zero_probe_done) == hipSuccess) {
-            const double rated = (double)st.zero_probe_host[0], dark = (double)st.zero_probe_host[1];
-            st.zero_dark = rated > 0.0 && dark > 0.15 * rated;
-            st.zero_known = true;
-            st.zero_probe_pending = false;
+        if (st.zero.verdict.pending && hipEventQuery(st.zero.done) == hipSuccess) {
+            const double rated = (double)st.zero.host[0], dark = (double)st.zero.host[1];
+            st.zero.verdict.dark = rated > 0.0 && dark > 0.15 * rated;
+            st.zero.verdict.known = true;
+            st.zero.verdict.pending = false;
         }
         (void)hipGetLastError();      // (hipErrorNotReady from the query is not an error)
-        st.zero_since_probe += 1;
-        probe = !st.zero_probe_pending && (!st.zero_known || st.zero_since_probe >= 64 || st.zero_dark);
-        skip_zero = probe || st.zero_dark;
+        st.zero.verdict.since_probe += 1;
+        probe = !st.zero.verdict.pending && (!st.zero.verdict.known || st.zero.verdict.since_probe >= 64 || st.zero.verdict.dark);
+        skip_zero = probe || st.zero.verdict.dark;
     }
     return 0;
 }
@@ -958,11 +959,11 @@ static int decide_skip_zero(State &st, bool exists, bool &skip_zero, bool &probe
 static int launch_zero_probe_sum(State &st, hipStream_t stream)
 {
     hipLaunchKernelGGL(zero_probe_sum_kernel, dim3(1), dim3(ZERO_PROBE_SLOTS), 0, stream,
-                       (const unsigned long long *)st.zero_probe_dev, st.zero_probe_host);
+                       (const unsigned long long *)st.zero.dev, st.zero.host);
     ASORA_HIP_TRY(hipGetLastError());
-    ASORA_HIP_TRY(hipEventRecord(st.zero_probe_done, stream));
-    st.zero_probe_pending = true;
-    st.zero_since_probe = 0;
+    ASORA_HIP_TRY(hipEventRecord(st.zero.done, stream));
+    st.zero.verdict.pending = true;
+    st.zero.verdict.since_probe = 0;
     return 0;
 }
 
@@ -975,14 +976,7 @@ static int ensure_shell_scratch(State &st, int units, size_t shell_bytes, int &b
     int max_batch = (int)std::max<size_t>(8, (budget / per_src) / 8 * 8);
     batch = std::min(batch, max_batch);
     const size_t need = (size_t)8 * units * ((batch + 7) / 8) * shell_bytes;
-    if (need > st.shell_scratch_bytes) {
-        if (st.shell_scratch) ASORA_HIP_TRY(hipFree(st.shell_scratch));
-        st.shell_scratch = nullptr;
-        st.shell_scratch_bytes = 0;
-        ASORA_HIP_TRY(hipMalloc(&st.shell_scratch, need));
-        st.shell_scratch_bytes = need;
-    }
-    return 0;
+    return st.shell_scratch.reserve(need / sizeof(double));
 }
 
 // How the radius behaves from call to call (a call = one raytrace of the library's API, one time step of the evolve loop):
@@ -992,7 +986,7 @@ bool note_call_radius(State &st, double R, int path)
     // (one history per path -- 0: the whole-box ASORA trace and the evolve loop, 1: the sub-box sweep, whose R is R_max_LLS and
     //  whose calls alternate with the other's in a process that uses both: a shared history would see the radius "change" on
     //  every alternation and never let the aligned tables back in)
-    State::RadiusHistory &h = st.rt_radius[path ? 1 : 0];
+    State::RadiusHistory &h = st.rt.radius[path ? 1 : 0];
     if (R != h.last_R) {
         if (h.last_R >= 0.0) h.has_changed = true;
         h.last_R = R;
@@ -1016,8 +1010,8 @@ int launch_raytrace(State &st, RtParams &p, bool dump, bool heat, hipStream_t si
     // (per-source spectra: checked by the entry points already; here so that no launch can carry an unchecked index)
     if (p.src_spec) { if (int rc = check_source_spectra("raytrace")) return rc; }
     if (int rc = check_open_boundaries(st, "raytrace", p.open_bc != 0, dump)) return rc;
-    const int32_t *host_pos = p.src_pos == st.src_pos_sorted ? st.src_pos_sorted_host.data()
-                            : p.src_pos == st.src_pos ? st.src_pos_host.data() : nullptr;
+    const int32_t *host_pos = p.src_pos == st.sources.pos_sorted ? st.sources.loaded.pos_sorted_host.data()
+                            : p.src_pos == st.sources.pos ? st.sources.loaded.pos_host.data() : nullptr;
     RtPlanInput in{};
     plan_options(st, in);
     in.N = p.N; in.R = p.R; in.src_count = p.src_count; in.shape_src_count = p.shape_src_count;
@@ -1064,8 +1058,8 @@ int launch_raytrace(State &st, RtParams &p, bool dump, bool heat, hipStream_t si
         q.shell_scratch = plan.use_lds ? nullptr : st.shell_scratch;
         q.zero_probe = nullptr;
         if (probe && done == 0) {
-            ASORA_HIP_TRY(hipMemsetAsync(st.zero_probe_dev, 0, 2 * ZERO_PROBE_SLOTS * sizeof(unsigned long long), stream));
-            q.zero_probe = st.zero_probe_dev;
+            ASORA_HIP_TRY(hipMemsetAsync(st.zero.dev, 0, 2 * ZERO_PROBE_SLOTS * sizeof(unsigned long long), stream));
+            q.zero_probe = st.zero.dev;
         }
         unsigned grid = 0;
         if (int rc = set_launch_grid(st, q, sh.units, form.nsrc == 2, sh.aligned, host_pos, !dump, grid)) return rc;
@@ -1113,13 +1107,8 @@ int subbox_tables_prepare(State &st, RtParams &p, int ext_r, int ext_l, int subb
     if (const char *e = getenv("ASORA_SUBBOX_TRAIL_BUDGET")) trail_budget = std::max<size_t>(per_source, (size_t)atoll(e));   // tests: force several batches
     const int max_batch = (int)std::max<size_t>(1, std::min<size_t>((size_t)src_count, trail_budget / per_source));
     const size_t need = (size_t)max_batch * per_source;
-    if (need > st.sb_trail_bytes) {
-        if (st.sb_trail) ASORA_HIP_TRY(hipFree(st.sb_trail));
-        st.sb_trail = nullptr; st.sb_trail_bytes = 0;
-        ASORA_HIP_TRY(hipMalloc(&st.sb_trail, need));
-        st.sb_trail_bytes = need;
-    }
-    p.sb_trail = st.sb_trail;
+    if (int rc = st.subbox.trail.reserve(need / sizeof(double))) return rc;
+    p.sb_trail = st.subbox.trail;
     out.units = units; out.threads = threads; out.S = p.S; out.max_batch = max_batch; out.ok = true;
     // two sources per workgroup where the plan wants them and four shell buffers fit
     out.nsrc = (plan.nsrc == 2 && form_lds_bytes(subbox_form(threads, false, 2), p.max_cells) <= LDS_LIMIT_BYTES) ? 2 : 1;

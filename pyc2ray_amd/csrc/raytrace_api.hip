@@ -21,7 +21,7 @@ int require_raytrace_inputs(const char *who, double R, int NumTau, bool density,
     if (int rc = check_open_boundaries(st, who, st.opt[ASORA_OPT_OPEN_BOUNDARIES] != 0, false)) return rc;
     if (density && !st.grid_valid[ASORA_GRID_NDENS]) return fail(4, w + "density not on device (density_to_device)");
     if (xh_av && !st.grid_valid[ASORA_GRID_XH_AV]) return fail(4, w + "xh_av not on device");
-    if (!st.opt[ASORA_OPT_GREY_NOTABLES] && !st.tables) return fail(4, w + "radiation tables not on device (photo_table_to_device)");
+    if (!st.opt[ASORA_OPT_GREY_NOTABLES] && !st.sources.tables) return fail(4, w + "radiation tables not on device (photo_table_to_device)");
     if (!(R >= 0.0)) return fail(4, w + "R must be >= 0");
     if (NumTau < 1 && !st.opt[ASORA_OPT_GREY_NOTABLES]) return fail(4, w + "NumTau must be >= 1");
     return check_source_spectra(who);
@@ -30,7 +30,7 @@ int require_raytrace_inputs(const char *who, double R, int NumTau, bool density,
 static int check_rt_sources(int src_begin, int src_count)
 {
     return check_sources("raytrace", 4, "source range [" + std::to_string(src_begin) + "," + std::to_string(src_begin + src_count) +
-                         ") outside the " + std::to_string(state().num_src) + " uploaded sources (source_data_to_device)", src_begin, src_count);
+                         ") outside the " + std::to_string(state().sources.loaded.num) + " uploaded sources (source_data_to_device)", src_begin, src_count);
 }
 
 // The parameter block of a raytrace of the uploaded sources into PHI_ION (+ its [k][j][i] twin).  radius_path: which radius
@@ -43,7 +43,7 @@ void fill_rt_params(RtParams &p, double R, double sig, double dr, double minlogt
     p.N = st.N;
     p.R = R; p.sig = sig; p.dr = dr;
     p.minlogtau = minlogtau; p.dlogtau = dlogtau;
-    p.table_len = st.table_len > 0 ? st.table_len : 1;
+    p.table_len = st.sources.loaded.table_len > 0 ? st.sources.loaded.table_len : 1;
     p.NumTau = NumTau; p.numtau_f = lut_index_limit(NumTau, p.table_len);
     p.fortran_consts = st.opt[ASORA_OPT_FORTRAN_CONSTANTS];
     p.grey = st.opt[ASORA_OPT_GREY_NOTABLES];
@@ -51,15 +51,15 @@ void fill_rt_params(RtParams &p, double R, double sig, double dr, double minlogt
     p.ncell = (unsigned)st.ncell;
     p.nhi = st.nhi;
     p.phi = st.grid[ASORA_GRID_PHI_ION];
-    p.tables = st.tables;
+    p.tables = st.sources.tables;
     p.heat = st.grid[ASORA_GRID_PHI_HEAT];
     // (per-source spectra: the two fields every entry point built on this block inherits)
-    p.spec_stride = (unsigned)st.spec_stride;
+    p.spec_stride = (unsigned)st.sources.loaded.spec_stride;
     use_source_list(p, st, false);
     p.counters = st.counters;
     p.radius_stays = note_call_radius(st, R, radius_path) ? 1 : 0;
     p.open_bc = st.opt[ASORA_OPT_OPEN_BOUNDARIES] != 0 ? 1 : 0;
-    p.plane = st.plane;
+    p.plane = st.medium.plane;
 }
 
 // A raytrace call in three parts, so that a caller can overlap the multi-GPU sum of finished slabs of the
@@ -71,14 +71,14 @@ static int rt_begin(double R, double sig, double dr, double minlogtau, double dl
                     bool pipelined = false)
 {
     State &st = state();
-    st.rt_open = false;
+    st.rt.open = false;
     if (int rc = require_raytrace_inputs("raytrace", R, NumTau, true, true)) return rc;
 
     const bool zt = st.opt[ASORA_OPT_Z_TRANSPOSED] != 0;
     const bool heat = st.opt[ASORA_OPT_HEATING] != 0 && dump == nullptr;
-    if (heat && (!st.have_heat_tables || st.opt[ASORA_OPT_GREY_NOTABLES]))
+    if (heat && (!st.sources.loaded.heat_tables || st.opt[ASORA_OPT_GREY_NOTABLES]))
         return fail(4, "raytrace: heating requested but no heating tables on device (heat_table_to_device)");
-    if (int rc = check_plane_flux(st, st.plane, "raytrace", dump != nullptr, heat)) return rc;
+    if (int rc = check_plane_flux(st, st.medium.plane, "raytrace", dump != nullptr, heat)) return rc;
     const size_t bytes = st.ncell * sizeof(double);
     ASORA_HIP_TRY(hipMemsetAsync(st.grid[ASORA_GRID_PHI_ION], 0, bytes, st.stream));      // raytracing.cu:113
     if (zt) ASORA_HIP_TRY(hipMemsetAsync(st.phi_t, 0, bytes, st.stream));
@@ -106,23 +106,23 @@ static int rt_begin(double R, double sig, double dr, double minlogtau, double dl
         }
         st.side_next = 0;
     }
-    st.rt_open = true;
+    st.rt.open = true;
     return 0;
 }
 
 static int rt_range(int src_begin, int src_count)
 {
     State &st = state();
-    if (!st.rt_open) return fail(4, "raytrace_range: no raytrace in progress (call asora_raytrace_begin)");
+    if (!st.rt.open) return fail(4, "raytrace_range: no raytrace in progress (call asora_raytrace_begin)");
     if (int rc = check_rt_sources(src_begin, src_count)) return rc;
     if (src_count == 0) return 0;
     RtParams p = st.rt_params;
     // the whole list: in the spatially ordered copy (a column-density dump is of the caller's LAST source: caller's order)
-    use_source_list(p, st, src_begin == 0 && src_count == st.num_src && st.src_pos_sorted && !p.dump);
+    use_source_list(p, st, src_begin == 0 && src_count == st.sources.loaded.num && st.sources.pos_sorted && !p.dump);
     p.src_begin = src_begin; p.src_count = src_count;
     // one launch shape (one set of geometry tables) per call: a call that traces its sources in several ranges (pipelined
     // all-reduce, chunked slab exchange) is sized by all of the rank's sources
-    p.shape_src_count = (st.rt_pipelined || st.rt_by_planes) ? st.num_src : src_count;
+    p.shape_src_count = (st.rt_pipelined || st.rt_by_planes) ? st.sources.loaded.num : src_count;
     if (!st.rt_pipelined) return launch_raytrace(st, p, p.dump != nullptr, st.rt_heat);
     const int q = st.side_next;
     st.side_next ^= 1;
@@ -135,7 +135,7 @@ static int rt_range(int src_begin, int src_count)
 static int rt_fold(int i_begin, int i_count)
 {
     State &st = state();
-    if (!st.rt_open) return fail(4, "raytrace_fold: no raytrace in progress (call asora_raytrace_begin)");
+    if (!st.rt.open) return fail(4, "raytrace_fold: no raytrace in progress (call asora_raytrace_begin)");
     if (int rc = check_planes("raytrace_fold", 4, "bad plane range", i_begin, i_count)) return rc;
     for (int q = 0; q < 2; ++q)       // everything traced so far must have landed
         if (st.side_pending[q]) {
@@ -160,7 +160,7 @@ static int do_raytrace(double R, double sig, double dr, int src_begin, int src_c
     if (int rc = rt_begin(R, sig, dr, minlogtau, dlogtau, NumTau, dump)) return rc;
     if (int rc = rt_range(src_begin, src_count)) return rc;
     if (int rc = rt_fold(0, st.N)) return rc;
-    st.rt_open = false;
+    st.rt.open = false;
     return 0;
 }
 
@@ -187,8 +187,8 @@ static int do_all_sources_pipelined(double R, double sig, double dr, const doubl
     const char *kenv = getenv("ASORA_PIPELINE_SLABS");
     const int K = kenv ? std::max(2, std::min(KMAX, atoi(kenv))) : 8;
     if (!st.opt[ASORA_OPT_PIPELINED_COPIES] || !st.opt[ASORA_OPT_Z_TRANSPOSED] || st.opt[ASORA_OPT_HEATING]) return 0;
-    if (st.plane.count > 0) return 0;                       // a face's sweep needs nHI of the whole box before anything is traced
-    if (NumSrc != st.num_src || NumSrc < 1 || !st.src_pos_sorted || N < 8 * K) return 0;
+    if (st.medium.plane.count > 0) return 0;                       // a face's sweep needs nHI of the whole box before anything is traced
+    if (NumSrc != st.sources.loaded.num || NumSrc < 1 || !st.sources.pos_sorted || N < 8 * K) return 0;
     if (!std::isfinite(R) || !(R >= 0.0)) return 0;
     const int m = (int)std::floor(R);                       // a source rates the planes i0 - floor(R) ... i0 + floor(R)
     if (2 * m + N / K >= N) return 0;                       // every slab of sources reaches (nearly) every plane
@@ -223,7 +223,7 @@ static int do_all_sources_pipelined(double R, double sig, double dr, const doubl
     // sources of slab c: [sb[c], sb[c+1]) of the sorted list
     int sb[KMAX + 1];
     for (int c = 0; c <= K; ++c)
-        sb[c] = (int)(std::lower_bound(st.src_i0_sorted.begin(), st.src_i0_sorted.end(), lo[c]) - st.src_i0_sorted.begin());
+        sb[c] = (int)(std::lower_bound(st.sources.loaded.i0_sorted.begin(), st.sources.loaded.i0_sorted.end(), lo[c]) - st.sources.loaded.i0_sorted.begin());
     // reach[c][d]: do sources of slab c touch planes of slab d (within m planes, periodically)
     bool reach[KMAX][KMAX];
     for (int c = 0; c < K; ++c)
@@ -246,7 +246,7 @@ static int do_all_sources_pipelined(double R, double sig, double dr, const doubl
     fill_rt_params(base, R, sig, dr, minlogtau, dlogtau, NumTau);
     use_source_list(base, st, true);
     base.shape_src_count = NumSrc;
-    st.rt_open = false;
+    st.rt.open = false;
     // the copy streams start behind whatever the main stream has done so far (earlier calls may still own the grids)
     ASORA_HIP_TRY(hipEventRecord(st.main_ready, st.stream));
     ASORA_HIP_TRY(hipStreamWaitEvent(up, st.main_ready, 0));
@@ -357,16 +357,16 @@ int asora_raytrace_begin_planes(double R, double sig, double dr, double minlogta
     clear_error();
     if (int rc = require_init("raytrace_begin_planes")) return rc;
     State &st = state();
-    st.rt_open = false;
+    st.rt.open = false;
     if (int rc = require_raytrace_inputs("raytrace_begin_planes", R, NumTau, true, true)) return rc;
     if (!st.opt[ASORA_OPT_Z_TRANSPOSED]) return fail(4, "raytrace_begin_planes: needs the [k][j][i] twins (ASORA_OPT_Z_TRANSPOSED = 1)");
     if (st.opt[ASORA_OPT_HEATING]) return fail(4, "raytrace_begin_planes: no heating rates on this path");
     if (nruns < 0 || (nruns > 0 && !runs)) return fail(3, "raytrace_begin_planes: bad plane runs");
     for (int q = 0; q < nruns; ++q)
         if (int rc = check_planes("raytrace_begin_planes", 3, "plane run outside the mesh", runs[2 * q], runs[2 * q + 1])) return rc;
-    if (int rc = check_plane_flux(st, st.plane, "raytrace_begin_planes", false, false)) return rc;
+    if (int rc = check_plane_flux(st, st.medium.plane, "raytrace_begin_planes", false, false)) return rc;
     if (int rc = reset_counters()) return rc;
-    if (st.plane.count > 0) {      // a face's sweep reads nHI of, and rates, every plane: the runs become the whole box
+    if (st.medium.plane.count > 0) {      // a face's sweep reads nHI of, and rates, every plane: the runs become the whole box
         if (int rc = launch_prepare_range(st, 0, st.N, true, st.grid[ASORA_GRID_PHI_ION])) return rc;
     } else
         for (int q = 0; q < nruns; ++q)
@@ -376,7 +376,7 @@ int asora_raytrace_begin_planes(double R, double sig, double dr, double minlogta
     st.rt_heat = false;
     st.rt_pipelined = false;
     st.rt_by_planes = true;
-    st.rt_open = true;
+    st.rt.open = true;
     return 0;
 }
 
@@ -404,9 +404,9 @@ int asora_do_all_sources(double R, double *coldensh_out, double sig, double dr, 
     if (int rc = check_N("do_all_sources", m1)) return rc;
     if (!xh_av || !phi_ion) return fail(3, "do_all_sources: null xh_av / phi_ion");
     State &st = state();
-    if (NumSrc > st.num_src)
+    if (NumSrc > st.sources.loaded.num)
         return fail(3, "do_all_sources: NumSrc=" + std::to_string(NumSrc) + " exceeds the " +
-                           std::to_string(st.num_src) + " sources on the device");
+                           std::to_string(st.sources.loaded.num) + " sources on the device");
     const size_t bytes = st.ncell * sizeof(double);
     {
         bool done = false;
@@ -574,9 +574,9 @@ int asora_debug_coldens(double R, double sig, double dr, int source_index, doubl
     const size_t bytes = st.ncell * sizeof(double);
     ASORA_HIP_TRY(hipMemsetAsync(st.staging, 0, bytes, st.stream));
     // the column density does not depend on the tables: trace with whatever is loaded
-    const int numtau = st.table_len > 0 ? st.table_len : 1;
+    const int numtau = st.sources.loaded.table_len > 0 ? st.sources.loaded.table_len : 1;
     const int grey_save = st.opt[ASORA_OPT_GREY_NOTABLES];
-    if (!st.tables) { st.opt[ASORA_OPT_GREY_NOTABLES] = 1; st.coldens_only = true; }
+    if (!st.sources.tables) { st.opt[ASORA_OPT_GREY_NOTABLES] = 1; st.coldens_only = true; }
     int rc = do_raytrace(R, sig, dr, source_index, 1, -20.0, 1.0, numtau, st.staging);
     st.opt[ASORA_OPT_GREY_NOTABLES] = grey_save; st.coldens_only = false;
     if (rc) return rc;

@@ -325,10 +325,10 @@ static int rs_tile(int N, bool contiguous)
 static int ensure_rs_buffers(State &st, bool own_field)
 {
     const RsLayout lay(st.N);
-    if (own_field && !st.sm_field) ASORA_HIP_TRY(hipMalloc(&st.sm_field, sizeof(double) * st.ncell));
-    if (!st.rs_partial) ASORA_HIP_TRY(hipMalloc(&st.rs_partial, sizeof(double) * lay.words));
-    if (!st.rs_thresholds) ASORA_HIP_TRY(hipMalloc(&st.rs_thresholds, sizeof(double) * RS_THR_WORDS));
-    if (!st.rs_host) ASORA_HIP_TRY(hipHostMalloc(&st.rs_host, sizeof(double) * (RS_RES_WORDS + RS_THR_WORDS)));
+    if (own_field) { if (int rc = st.smoothing.field.allocate(st.ncell)) return rc; }
+    if (int rc = st.redshift.partial.allocate(lay.words)) return rc;
+    if (int rc = st.redshift.thresholds.allocate(RS_THR_WORDS)) return rc;
+    if (int rc = st.redshift.host.allocate((RS_RES_WORDS + RS_THR_WORDS))) return rc;
     return 0;
 }
 
@@ -345,8 +345,8 @@ static int rs_check(const char *who, State &st, int kind, double scale, double t
     *W = 0;
     if (use_velocity) {
         if (!std::isfinite(velocity_scale)) return fail(3, me + ": velocity_scale must be finite");
-        if (!st.rs_velocity) return fail(3, me + ": use_velocity without a velocity on the device (asora_los_velocity_to_device)");
-        const double w = std::floor(st.rs_vmax * std::fabs(velocity_scale)) + 1.0;
+        if (!st.redshift.velocity) return fail(3, me + ": use_velocity without a velocity on the device (asora_los_velocity_to_device)");
+        const double w = std::floor(st.redshift.vmax * std::fabs(velocity_scale)) + 1.0;
         if (!(2.0 * w + 1.0 <= (double)st.N))
             return fail(3, me + ": the window of 2 W + 1 cells, W = floor(max|v| |velocity_scale|) + 1, is wider than the N = " +
                                std::to_string(st.N) + " cells of a line");
@@ -413,27 +413,26 @@ int asora_los_velocity_to_device(const double *v, int N, char order, double *max
     State &st = state();
     const size_t bytes = st.ncell * sizeof(double);
     // into a buffer of its own first: a refused upload leaves the velocity of the last good one in place
-    struct Fresh { double *dev = nullptr; ~Fresh() { (void)hipFree(dev); } } fresh;
-    ASORA_HIP_TRY(hipMalloc(&fresh.dev, bytes));
-    if (!st.rs_vmax_dev) ASORA_HIP_TRY(hipMalloc(&st.rs_vmax_dev, sizeof(unsigned long long)));
+    Scoped<double> fresh;
+    if (int rc = fresh.allocate(st.ncell)) return rc;
+    if (int rc = st.redshift.vmax_dev.allocate(1)) return rc;
     if (c_order) {
-        ASORA_HIP_TRY(hipMemcpyAsync(fresh.dev, v, bytes, hipMemcpyHostToDevice, st.stream));
+        ASORA_HIP_TRY(hipMemcpyAsync(fresh.get(), v, bytes, hipMemcpyHostToDevice, st.stream));
     } else {
         ASORA_HIP_TRY(hipMemcpyAsync(st.staging, v, bytes, hipMemcpyHostToDevice, st.stream));
-        if (int rc = launch_transpose(st, st.staging, fresh.dev, N)) return rc;
+        if (int rc = launch_transpose(st, st.staging, fresh.get(), N)) return rc;
     }
-    ASORA_HIP_TRY(hipMemsetAsync(st.rs_vmax_dev, 0, sizeof(unsigned long long), st.stream));
-    hipLaunchKernelGGL(rs_vmax_kernel, dim3(PS_RED_BLOCKS), dim3(PS_THREADS), 0, st.stream, (const double *)fresh.dev, st.ncell, st.rs_vmax_dev);
+    ASORA_HIP_TRY(hipMemsetAsync(st.redshift.vmax_dev, 0, sizeof(unsigned long long), st.stream));
+    hipLaunchKernelGGL(rs_vmax_kernel, dim3(PS_RED_BLOCKS), dim3(PS_THREADS), 0, st.stream, (const double *)fresh.get(), st.ncell, st.redshift.vmax_dev);
     ASORA_HIP_TRY(hipGetLastError());
     unsigned long long bits = 0ull;
-    ASORA_HIP_TRY(hipMemcpyAsync(&bits, st.rs_vmax_dev, sizeof bits, hipMemcpyDeviceToHost, st.stream));
+    ASORA_HIP_TRY(hipMemcpyAsync(&bits, st.redshift.vmax_dev, sizeof bits, hipMemcpyDeviceToHost, st.stream));
     ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
     if (bits >= RS_INF_BITS) return fail(3, "los_velocity_to_device: the velocity has a non-finite entry");
-    if (st.rs_velocity) (void)hipFree(st.rs_velocity);
-    st.rs_velocity = fresh.dev;
-    fresh.dev = nullptr;
-    std::memcpy(&st.rs_vmax, &bits, sizeof bits);
-    if (max_abs) *max_abs = st.rs_vmax;
+    (void)st.redshift.velocity.release();
+    st.redshift.velocity.adopt(fresh.give(), bytes);
+    std::memcpy(&st.redshift.vmax, &bits, sizeof bits);
+    if (max_abs) *max_abs = st.redshift.vmax;
     return 0;
 }
 
@@ -441,8 +440,8 @@ int asora_los_velocity_clear(void)
 {
     clear_error();
     State &st = state();
-    if (st.rs_velocity) { (void)hipFree(st.rs_velocity); st.rs_velocity = nullptr; }
-    st.rs_vmax = 0.0;
+    (void)st.redshift.velocity.release();
+    st.redshift.vmax = 0.0;
     return 0;
 }
 
@@ -459,24 +458,24 @@ int asora_redshift_space_field(int kind, double scale, double t_gamma, int los_a
     if (int rc = ensure_rs_buffers(st, dst_grid < 0)) return rc;
     if (dst_grid >= 0)
         if (int rc = ensure_optional_grid(dst_grid)) return rc;
-    double *h = dst_grid >= 0 ? st.grid[dst_grid] : st.sm_field;
+    double *h = dst_grid >= 0 ? st.grid[dst_grid] : st.smoothing.field;
     const RsLayout lay(st.N);
-    double *part = st.rs_partial, *res = part + lay.result;
+    double *part = st.redshift.partial, *res = part + lay.result;
     const double *nbar_dev = nullptr;
     if (ps_needs_grid(kind, ASORA_GRID_NDENS, t_gamma))
         if (int rc = ps_mean_density(st, &nbar_dev)) return rc;
-    if (int rc = rs_launch_map(st, kind, nbar_dev, scale, t_gamma, use_velocity ? (const double *)st.rs_velocity : (const double *)nullptr,
+    if (int rc = rs_launch_map(st, kind, nbar_dev, scale, t_gamma, use_velocity ? (const double *)st.redshift.velocity : (const double *)nullptr,
                                velocity_scale, W, los_axis, h, part + lay.moments, res))
         return rc;
     if (dst_grid >= 0) {                                           // (as asora_grid_to_device leaves a grid)
         st.grid_valid[dst_grid] = true;
-        st.zero_since_probe = std::max(st.zero_since_probe, 48);
-        if (dst_grid == ASORA_GRID_TEMP) st.temp_probe_valid = false;
+        st.zero.verdict.since_probe = std::max(st.zero.verdict.since_probe, 48);
+        if (dst_grid == ASORA_GRID_TEMP) st.temp_probe.valid = false;
     }
-    ASORA_HIP_TRY(hipMemcpyAsync(st.rs_host, res, sizeof(double) * 2, hipMemcpyDeviceToHost, st.stream));
+    ASORA_HIP_TRY(hipMemcpyAsync(st.redshift.host, res, sizeof(double) * 2, hipMemcpyDeviceToHost, st.stream));
     if (field_out) ASORA_HIP_TRY(hipMemcpyAsync(field_out, h, sizeof(double) * st.ncell, hipMemcpyDeviceToHost, st.stream));
     ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
-    if (moments) std::memcpy(moments, st.rs_host, sizeof(double) * 2);
+    if (moments) std::memcpy(moments, st.redshift.host, sizeof(double) * 2);
     return 0;
 }
 
@@ -508,11 +507,11 @@ int asora_power_spectrum_los(int kind, double scale, double t_gamma, int los_axi
     const size_t ncell = st.ncell, nmodes = (size_t)N * N * NZ;
     if (int rc = ensure_rs_buffers(st, use_velocity || field_out)) return rc;
     const RsLayout lay(N);
-    double *part = st.rs_partial, *res = part + lay.result;
-    double *stage = st.rs_host + RS_RES_WORDS;
+    double *part = st.redshift.partial, *res = part + lay.result;
+    double *stage = st.redshift.host + RS_RES_WORDS;
     std::memcpy(stage + RS_THR_B, thr_b, sizeof(double) * (n_b + 1));
     std::memcpy(stage + RS_THR_A, thr_a, sizeof(unsigned) * (n_a + 1));
-    ASORA_HIP_TRY(hipMemcpyAsync(st.rs_thresholds, stage, sizeof(double) * RS_THR_WORDS, hipMemcpyHostToDevice, st.stream));
+    ASORA_HIP_TRY(hipMemcpyAsync(st.redshift.thresholds, stage, sizeof(double) * RS_THR_WORDS, hipMemcpyHostToDevice, st.stream));
     StageStopwatch<ASORA_PSLOS_STAGES> watch(st.opt[ASORA_OPT_TIMING] != 0, st.stream);
     auto mark = [&watch]() { return watch.mark(); };
 
@@ -524,15 +523,15 @@ int asora_power_spectrum_los(int kind, double scale, double t_gamma, int los_axi
     if (int rc = watch.mark()) return rc;
     if (use_velocity) {
         // the mapped field lies in sm_field and goes through the transform as kind ASORA_PS_XH
-        if (int rc = rs_launch_map(st, kind, nbar_dev, scale, t_gamma, (const double *)st.rs_velocity, velocity_scale, W, los_axis,
-                                   st.sm_field, part + lay.moments, res))
+        if (int rc = rs_launch_map(st, kind, nbar_dev, scale, t_gamma, (const double *)st.redshift.velocity, velocity_scale, W, los_axis,
+                                   st.smoothing.field, part + lay.moments, res))
             return rc;
         if (int rc = watch.mark()) return rc;
-        if (int rc = ps_transform(st, ASORA_PS_XH, st.sm_field, false, 1.0, 0.0, nullptr, mark, &moments_dev)) return rc;
+        if (int rc = ps_transform(st, ASORA_PS_XH, st.smoothing.field, false, 1.0, 0.0, nullptr, mark, &moments_dev)) return rc;
         ASORA_HIP_TRY(hipMemcpyAsync(res + 2, moments_dev, sizeof(double) * 2, hipMemcpyDeviceToDevice, st.stream));
     } else {
         if (int rc = watch.mark()) return rc;
-        if (int rc = ps_transform(st, kind, st.grid[ASORA_GRID_XH], nbar, scale, t_gamma, field_out ? st.sm_field : (double *)nullptr, mark,
+        if (int rc = ps_transform(st, kind, st.grid[ASORA_GRID_XH], nbar, scale, t_gamma, field_out ? st.smoothing.field : (double *)nullptr, mark,
                                   &moments_dev))
             return rc;
         ASORA_HIP_TRY(hipMemcpyAsync(res, moments_dev, sizeof(double) * 2, hipMemcpyDeviceToDevice, st.stream));
@@ -541,17 +540,17 @@ int asora_power_spectrum_los(int kind, double scale, double t_gamma, int los_axi
 
     const int waves = nb <= ASORA_ANISO_MAX_BINS / 2 ? PS_WAVES : PS_WAVES / 2;
     const size_t bin_lds = (size_t)waves * RS_VALUES * nb * sizeof(double) + sizeof(double) * (n_b + 1) + sizeof(unsigned) * (n_a + 1);
-    const unsigned *ta = (const unsigned *)(st.rs_thresholds + RS_THR_A);
-    const double *tb = st.rs_thresholds + RS_THR_B;
+    const unsigned *ta = (const unsigned *)(st.redshift.thresholds + RS_THR_A);
+    const double *tb = st.redshift.thresholds + RS_THR_B;
     if (mode == ASORA_ANISO_CYLINDRICAL) {
         ASORA_HIP_TRY(hipFuncSetAttribute((const void *)rs_bin_kernel<ASORA_ANISO_CYLINDRICAL>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                           (int)bin_lds));
         hipLaunchKernelGGL(rs_bin_kernel<ASORA_ANISO_CYLINDRICAL>, dim3((unsigned)N), dim3(64 * waves), bin_lds, st.stream,
-                           (const double2 *)st.ps_modes[0], N, los_axis, n_a, n_b, ta, tb, part + lay.bins);
+                           (const double2 *)st.spectrum.modes[0], N, los_axis, n_a, n_b, ta, tb, part + lay.bins);
     } else {
         ASORA_HIP_TRY(hipFuncSetAttribute((const void *)rs_bin_kernel<ASORA_ANISO_MU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bin_lds));
         hipLaunchKernelGGL(rs_bin_kernel<ASORA_ANISO_MU>, dim3((unsigned)N), dim3(64 * waves), bin_lds, st.stream,
-                           (const double2 *)st.ps_modes[0], N, los_axis, n_a, n_b, ta, tb, part + lay.bins);
+                           (const double2 *)st.spectrum.modes[0], N, los_axis, n_a, n_b, ta, tb, part + lay.bins);
     }
     ASORA_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(rs_bin_final_kernel, dim3((unsigned)((RS_VALUES * nb + PS_THREADS - 1) / PS_THREADS)), dim3(PS_THREADS), 0, st.stream,
@@ -559,13 +558,13 @@ int asora_power_spectrum_los(int kind, double scale, double t_gamma, int los_axi
     ASORA_HIP_TRY(hipGetLastError());
     if (int rc = watch.mark()) return rc;
 
-    ASORA_HIP_TRY(hipMemcpyAsync(st.rs_host, res, sizeof(double) * (RS_RES_BINS + (size_t)RS_VALUES * nb), hipMemcpyDeviceToHost, st.stream));
-    if (field_out) ASORA_HIP_TRY(hipMemcpyAsync(field_out, st.sm_field, sizeof(double) * ncell, hipMemcpyDeviceToHost, st.stream));
-    if (modes_out) ASORA_HIP_TRY(hipMemcpyAsync(modes_out, st.ps_modes[0], sizeof(double2) * nmodes, hipMemcpyDeviceToHost, st.stream));
+    ASORA_HIP_TRY(hipMemcpyAsync(st.redshift.host, res, sizeof(double) * (RS_RES_BINS + (size_t)RS_VALUES * nb), hipMemcpyDeviceToHost, st.stream));
+    if (field_out) ASORA_HIP_TRY(hipMemcpyAsync(field_out, st.smoothing.field, sizeof(double) * ncell, hipMemcpyDeviceToHost, st.stream));
+    if (modes_out) ASORA_HIP_TRY(hipMemcpyAsync(modes_out, st.spectrum.modes[0], sizeof(double2) * nmodes, hipMemcpyDeviceToHost, st.stream));
     ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
-    watch.read(st.rs_ms);
+    watch.read(st.redshift.ms);
 
-    const double *h = st.rs_host, *bins = h + RS_RES_BINS;
+    const double *h = st.redshift.host, *bins = h + RS_RES_BINS;
     std::memcpy(moments_real, h, sizeof(double) * 2);
     std::memcpy(moments_rs, h + 2, sizeof(double) * 2);
     std::memcpy(count, bins + (size_t)RS_COUNT * nb, sizeof(unsigned long long) * nb);
@@ -581,7 +580,7 @@ int asora_debug_power_spectrum_los_ms(double *ms)
 {
     clear_error();
     if (!ms) return fail(3, "debug_power_spectrum_los_ms: null pointer");
-    for (int q = 0; q < ASORA_PSLOS_STAGES; ++q) ms[q] = state().rs_ms[q];
+    for (int q = 0; q < ASORA_PSLOS_STAGES; ++q) ms[q] = state().redshift.ms[q];
     return 0;
 }
 

@@ -281,11 +281,11 @@ __global__ void __launch_bounds__(RG_THREADS) region_final_kernel(const unsigned
 
 int ensure_region_buffers(State &st)
 {
-    if (st.region_label && st.region_volume && st.region_result && st.region_flags) return 0;
-    if (!st.region_label) ASORA_HIP_TRY(hipMalloc(&st.region_label, sizeof(unsigned) * st.ncell));
-    if (!st.region_volume) ASORA_HIP_TRY(hipMalloc(&st.region_volume, sizeof(unsigned) * st.ncell));
-    if (!st.region_result) ASORA_HIP_TRY(hipMalloc(&st.region_result, sizeof(unsigned long long) * RG_WORDS));
-    if (!st.region_flags) ASORA_HIP_TRY(hipMalloc(&st.region_flags, sizeof(unsigned) * 3 * (size_t)st.N));
+    if (st.regions.label && st.regions.volume && st.regions.result && st.regions.flags) return 0;
+    if (int rc = st.regions.label.allocate(st.ncell)) return rc;
+    if (int rc = st.regions.volume.allocate(st.ncell)) return rc;
+    if (int rc = st.regions.result.allocate(RG_WORDS)) return rc;
+    if (int rc = st.regions.flags.allocate(3 * (size_t)st.N)) return rc;
     return 0;
 }
 
@@ -301,16 +301,16 @@ int launch_region_label(State &st, const unsigned long long *mask, int periodic,
     const int N = st.N, W = (N + 63) / 64;
     const size_t ncell = st.ncell;
     const dim3 grid(region_blocks(st)), block(RG_THREADS);
-    hipLaunchKernelGGL(region_init_kernel, grid, block, 0, st.stream, mask, N, W, ncell, st.region_label, st.region_volume);
+    hipLaunchKernelGGL(region_init_kernel, grid, block, 0, st.stream, mask, N, W, ncell, st.regions.label, st.regions.volume);
     ASORA_HIP_TRY(hipGetLastError());
     RegionMergeParams mp;
-    mp.mask = mask; mp.label = st.region_label; mp.N = N; mp.W = W; mp.periodic = periodic != 0; mp.ncell = ncell;
+    mp.mask = mask; mp.label = st.regions.label; mp.N = N; mp.W = W; mp.periodic = periodic != 0; mp.ncell = ncell;
     mp.nrows_fwd = connectivity == 6 ? 2 : 4;
     const int di[4] = {0, 1, 1, 1}, dj[4] = {1, 0, -1, 1};
     for (int q = 0; q < 4; ++q) { mp.di[q] = di[q]; mp.dj[q] = dj[q]; }
     hipLaunchKernelGGL(region_merge_kernel, grid, block, 0, st.stream, mp);
     ASORA_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(region_flatten_kernel, grid, block, 0, st.stream, mask, N, W, ncell, st.region_label, st.region_volume);
+    hipLaunchKernelGGL(region_flatten_kernel, grid, block, 0, st.stream, mask, N, W, ncell, st.regions.label, st.regions.volume);
     ASORA_HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -343,28 +343,28 @@ int asora_region_sizes(int which_grid, double threshold, int phase, int periodic
 
     const int N = st.N;
     const size_t ncell = st.ncell;
-    double *edges_host = reinterpret_cast<double *>(st.bubble_host + RG_WORDS);
+    double *edges_host = reinterpret_cast<double *>(st.bubbles.host + RG_WORDS);
     for (int b = 0; b <= n_bins; ++b) edges_host[b] = edges[b];
-    ASORA_HIP_TRY(hipMemcpyAsync(st.bubble_edges, edges_host, sizeof(double) * (n_bins + 1), hipMemcpyHostToDevice, st.stream));
-    ASORA_HIP_TRY(hipMemsetAsync(st.region_result, 0, sizeof(unsigned long long) * RG_WORDS, st.stream));
-    ASORA_HIP_TRY(hipMemsetAsync(st.region_flags, 0, sizeof(unsigned) * 3 * (size_t)N, st.stream));
+    ASORA_HIP_TRY(hipMemcpyAsync(st.bubbles.edges, edges_host, sizeof(double) * (n_bins + 1), hipMemcpyHostToDevice, st.stream));
+    ASORA_HIP_TRY(hipMemsetAsync(st.regions.result, 0, sizeof(unsigned long long) * RG_WORDS, st.stream));
+    ASORA_HIP_TRY(hipMemsetAsync(st.regions.flags, 0, sizeof(unsigned) * 3 * (size_t)N, st.stream));
     if (int rc = launch_bubble_mask(st, which_grid, threshold, phase, false)) return rc;
 
     const dim3 grid(region_blocks(st)), block(RG_THREADS);
-    if (int rc = launch_region_label(st, st.bubble_mask, periodic, connectivity)) return rc;
-    hipLaunchKernelGGL(region_roots_kernel, grid, block, 0, st.stream, (const unsigned *)st.region_label, (const unsigned *)st.region_volume,
-                       ncell, n_bins, (const double *)st.bubble_edges, st.region_result);
+    if (int rc = launch_region_label(st, st.bubbles.mask, periodic, connectivity)) return rc;
+    hipLaunchKernelGGL(region_roots_kernel, grid, block, 0, st.stream, (const unsigned *)st.regions.label, (const unsigned *)st.regions.volume,
+                       ncell, n_bins, (const double *)st.bubbles.edges, st.regions.result);
     ASORA_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(region_second_kernel, grid, block, 0, st.stream, (const unsigned *)st.region_label, (const unsigned *)st.region_volume,
-                       N, ncell, st.region_result, st.region_flags);
+    hipLaunchKernelGGL(region_second_kernel, grid, block, 0, st.stream, (const unsigned *)st.regions.label, (const unsigned *)st.regions.volume,
+                       N, ncell, st.regions.result, st.regions.flags);
     ASORA_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(region_final_kernel, dim3(1), block, 0, st.stream, (const unsigned *)st.region_flags, N, st.region_result);
+    hipLaunchKernelGGL(region_final_kernel, dim3(1), block, 0, st.stream, (const unsigned *)st.regions.flags, N, st.regions.result);
     ASORA_HIP_TRY(hipGetLastError());
-    ASORA_HIP_TRY(hipMemcpyAsync(st.bubble_host, st.region_result, sizeof(unsigned long long) * RG_WORDS, hipMemcpyDeviceToHost, st.stream));
-    if (labels) ASORA_HIP_TRY(hipMemcpyAsync(labels, st.region_label, sizeof(uint32_t) * ncell, hipMemcpyDeviceToHost, st.stream));
+    ASORA_HIP_TRY(hipMemcpyAsync(st.bubbles.host, st.regions.result, sizeof(unsigned long long) * RG_WORDS, hipMemcpyDeviceToHost, st.stream));
+    if (labels) ASORA_HIP_TRY(hipMemcpyAsync(labels, st.regions.label, sizeof(uint32_t) * ncell, hipMemcpyDeviceToHost, st.stream));
     ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
 
-    const unsigned long long *h = st.bubble_host;
+    const unsigned long long *h = st.bubbles.host;
     for (int b = 0; b < n_bins; ++b) { counts[b] = h[RG_COUNTS + b]; cells[b] = h[RG_CELLS + b]; }
     tallies[ASORA_REGION_N_PHASE] = h[RG_N_PHASE];
     tallies[ASORA_REGION_N_REGIONS] = h[RG_N_REGIONS];

@@ -259,11 +259,11 @@ struct SmLayout {
 
 static int ensure_sm_buffers(State &st, const SmLayout &lay, bool own_field)
 {
-    if (own_field && !st.sm_field) ASORA_HIP_TRY(hipMalloc(&st.sm_field, sizeof(double) * st.ncell));
-    if (!st.sm_tables) ASORA_HIP_TRY(hipMalloc(&st.sm_tables, sizeof(double) * lay.words));
-    if (!st.sm_partial) ASORA_HIP_TRY(hipMalloc(&st.sm_partial, sizeof(double) * lay.partial_words));
-    if (!st.sm_result) ASORA_HIP_TRY(hipMalloc(&st.sm_result, sizeof(double) * SM_RES_WORDS));
-    if (!st.sm_host) ASORA_HIP_TRY(hipHostMalloc(&st.sm_host, sizeof(double) * (SM_RES_WORDS + lay.words)));
+    if (own_field) { if (int rc = st.smoothing.field.allocate(st.ncell)) return rc; }
+    if (int rc = st.smoothing.tables.allocate(lay.words)) return rc;
+    if (int rc = st.smoothing.partial.allocate(lay.partial_words)) return rc;
+    if (int rc = st.smoothing.result.allocate(SM_RES_WORDS)) return rc;
+    if (int rc = st.smoothing.host.allocate((SM_RES_WORDS + lay.words))) return rc;
     return 0;
 }
 
@@ -329,7 +329,7 @@ int asora_smooth_field(int kind, double scale, double t_gamma, const double *w_i
     if (int rc = ensure_sm_buffers(st, lay, dst_grid < 0)) return rc;
     if (dst_grid >= 0)
         if (int rc = ensure_optional_grid(dst_grid)) return rc;
-    double *h = dst_grid >= 0 ? st.grid[dst_grid] : st.sm_field;
+    double *h = dst_grid >= 0 ? st.grid[dst_grid] : st.smoothing.field;
 
     const size_t fft_lds = ((size_t)2 * T * pitch + N) * sizeof(double2);
     const size_t filter_lds = fft_lds + 3 * (size_t)N * sizeof(double) + 3 * (size_t)T * sizeof(int);
@@ -340,7 +340,7 @@ int asora_smooth_field(int kind, double scale, double t_gamma, const double *w_i
     ASORA_HIP_TRY(hipFuncSetAttribute((const void *)sm_moment_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hist_lds));
 
     // the tables and the edges leave the host through the pinned area, one copy each
-    double *stage = st.sm_host + SM_RES_WORDS, *tab = st.sm_tables;
+    double *stage = st.smoothing.host + SM_RES_WORDS, *tab = st.smoothing.tables;
     auto upload = [&](const double *src, size_t at, size_t n) -> int {
         std::memcpy(stage + at, src, sizeof(double) * n);
         ASORA_HIP_TRY(hipMemcpyAsync(tab + at, stage + at, sizeof(double) * n, hipMemcpyHostToDevice, st.stream));
@@ -353,7 +353,7 @@ int asora_smooth_field(int kind, double scale, double t_gamma, const double *w_i
         if (int rc = upload(w_r, lay.w_r, want_r)) return rc;
     if (n_hist > 0)
         if (int rc = upload(edges, lay.edges, (size_t)n_hist + 1)) return rc;
-    double *res = st.sm_result, *part = st.sm_partial;
+    double *res = st.smoothing.result, *part = st.smoothing.partial;
     unsigned long long *hist_dev = (unsigned long long *)(res + SM_RES_HIST);
     if (n_hist > 0) ASORA_HIP_TRY(hipMemsetAsync(hist_dev, 0, sizeof(unsigned long long) * ((size_t)n_hist + 2), st.stream));
 
@@ -363,8 +363,8 @@ int asora_smooth_field(int kind, double scale, double t_gamma, const double *w_i
     const double *input_moments = nullptr;
     if (int rc = ps_forward(st, kind, scale, t_gamma, [&watch]() { return watch.mark(); }, &input_moments)) return rc;
 
-    double2 *modes = st.ps_modes[0];
-    const double2 *twiddle = st.ps_twiddle;
+    double2 *modes = st.spectrum.modes[0];
+    const double2 *twiddle = st.spectrum.twiddle;
     const unsigned tiles_j = (unsigned)((NZ + T - 1) / T), tiles_i = (unsigned)(((size_t)N * NZ + T - 1) / T);
     hipLaunchKernelGGL(sm_line_kernel<true>, dim3(tiles_i), block, filter_lds, st.stream, modes, N, pitch, T, plan, twiddle, (size_t)0,
                        (size_t)N * NZ, (size_t)N * NZ, tiles_i, w_i ? (const double *)(tab + lay.w[0]) : (const double *)nullptr,
@@ -393,18 +393,18 @@ int asora_smooth_field(int kind, double scale, double t_gamma, const double *w_i
     if (int rc = watch.mark()) return rc;
     if (dst_grid >= 0) {                                           // (as asora_grid_to_device leaves a grid)
         st.grid_valid[dst_grid] = true;
-        st.zero_since_probe = std::max(st.zero_since_probe, 48);
-        if (dst_grid == ASORA_GRID_TEMP) st.temp_probe_valid = false;
+        st.zero.verdict.since_probe = std::max(st.zero.verdict.since_probe, 48);
+        if (dst_grid == ASORA_GRID_TEMP) st.temp_probe.valid = false;
     }
 
     const size_t res_words = (size_t)SM_RES_HIST + (n_hist > 0 ? (size_t)n_hist + 2 : 0);
-    ASORA_HIP_TRY(hipMemcpyAsync(st.sm_host, res, sizeof(double) * res_words, hipMemcpyDeviceToHost, st.stream));
+    ASORA_HIP_TRY(hipMemcpyAsync(st.smoothing.host, res, sizeof(double) * res_words, hipMemcpyDeviceToHost, st.stream));
     if (field_out) ASORA_HIP_TRY(hipMemcpyAsync(field_out, h, sizeof(double) * ncell, hipMemcpyDeviceToHost, st.stream));
     ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
-    watch.read(st.sm_ms);
+    watch.read(st.smoothing.ms);
 
-    std::memcpy(stats, st.sm_host, sizeof(double) * ASORA_SMOOTH_STATS);
-    if (n_hist > 0) std::memcpy(hist, st.sm_host + SM_RES_HIST, sizeof(uint64_t) * ((size_t)n_hist + 2));
+    std::memcpy(stats, st.smoothing.host, sizeof(double) * ASORA_SMOOTH_STATS);
+    if (n_hist > 0) std::memcpy(hist, st.smoothing.host + SM_RES_HIST, sizeof(uint64_t) * ((size_t)n_hist + 2));
     return 0;
 }
 
@@ -412,7 +412,7 @@ int asora_debug_smooth_field_ms(double *ms)
 {
     clear_error();
     if (!ms) return fail(3, "debug_smooth_field_ms: null pointer");
-    for (int q = 0; q < ASORA_SMOOTH_STAGES; ++q) ms[q] = state().sm_ms[q];
+    for (int q = 0; q < ASORA_SMOOTH_STAGES; ++q) ms[q] = state().smoothing.ms[q];
     return 0;
 }
 

@@ -144,10 +144,10 @@ __global__ void __launch_bounds__(CH_THREADS) step_budget_final_kernel(const dou
 // the feature's own buffers: [12][red_blocks] partials and the 12 results behind them on the device, 12 doubles pinned
 static int ensure_budget_buffers(State &st)
 {
-    if (st.budget_partial && st.budget_host) return 0;
+    if (st.budget.partial && st.budget.host) return 0;
     const size_t entries = (size_t)ASORA_BUDGET_COUNT * ((size_t)st.red_blocks + 1);
-    if (!st.budget_partial) ASORA_HIP_TRY(hipMalloc(&st.budget_partial, sizeof(double) * entries));
-    if (!st.budget_host) ASORA_HIP_TRY(hipHostMalloc(&st.budget_host, sizeof(double) * ASORA_BUDGET_COUNT, hipHostMallocDefault));
+    if (int rc = st.budget.partial.allocate(entries)) return rc;
+    if (int rc = st.budget.host.allocate(ASORA_BUDGET_COUNT)) return rc;
     return 0;
 }
 
@@ -186,7 +186,7 @@ int asora_step_budget(double bh00, double albpow, double colh0, double temph0, d
         if (int rc = require_grids("step_budget", {ASORA_GRID_TEMP_END})) return rc;
         if (!st.grid[ASORA_GRID_TEMP_END]) return fail(4, "step_budget: use_temp_end without ASORA_GRID_TEMP_END on the device");
     }
-    if (st.clump_mode == 2) {
+    if (st.medium.clump_mode == 2) {
         if (int rc = require_grids("step_budget", {ASORA_GRID_CLUMP})) return rc;
         if (!st.grid[ASORA_GRID_CLUMP]) return fail(4, "step_budget: clumping mode 2 without ASORA_GRID_CLUMP on the device");
     }
@@ -199,16 +199,16 @@ int asora_step_budget(double bh00, double albpow, double colh0, double temph0, d
     p.ndens = st.grid[ASORA_GRID_NDENS]; p.xh = st.grid[ASORA_GRID_XH]; p.xh_intermed = st.grid[ASORA_GRID_XH_INTERMED];
     p.xh_av = st.grid[ASORA_GRID_XH_AV]; p.phi = st.grid[ASORA_GRID_PHI_ION]; p.temp = st.grid[ASORA_GRID_TEMP];
     p.temp_end = use_temp_end ? st.grid[ASORA_GRID_TEMP_END] : nullptr;
-    p.clump = st.clump_mode == 2 ? st.grid[ASORA_GRID_CLUMP] : nullptr;
-    p.clump_c = st.clump_mode == 1 ? st.clump_c : 1.0;
-    p.lls_a = st.lls_a; p.lls_b = st.lls_b;
+    p.clump = st.medium.clump_mode == 2 ? st.grid[ASORA_GRID_CLUMP] : nullptr;
+    p.clump_c = st.medium.clump_mode == 1 ? st.medium.clump_c : 1.0;
+    p.lls_a = st.medium.lls_a; p.lls_b = st.medium.lls_b;
     p.bh00 = bh00; p.albpow = albpow; p.colh0 = colh0; p.temph0 = temph0; p.abu_c = abu_c;
-    p.partial = st.budget_partial; p.nblocks = st.red_blocks;
+    p.partial = st.budget.partial; p.nblocks = st.red_blocks;
     if (int rc = launch_step_budget(st, p, p.clump != nullptr, use_temp_end != 0)) return rc;
-    ASORA_HIP_TRY(hipMemcpyAsync(st.budget_host, p.partial + (size_t)ASORA_BUDGET_COUNT * p.nblocks, sizeof(double) * ASORA_BUDGET_COUNT,
+    ASORA_HIP_TRY(hipMemcpyAsync(st.budget.host, p.partial + (size_t)ASORA_BUDGET_COUNT * p.nblocks, sizeof(double) * ASORA_BUDGET_COUNT,
                                  hipMemcpyDeviceToHost, st.stream));
     ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
-    for (int k = 0; k < ASORA_BUDGET_COUNT; ++k) sums[k] = st.budget_host[k];
+    for (int k = 0; k < ASORA_BUDGET_COUNT; ++k) sums[k] = st.budget.host[k];
     return 0;
 }
 

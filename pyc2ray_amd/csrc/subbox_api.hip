@@ -28,7 +28,7 @@ struct SubboxCall {
 // per source, so the calls fail while the uploaded sources carry table sets of their own.
 static int refuse_source_spectra(const char *who)
 {
-    if (!state().src_spec) return 0;
+    if (!state().sources.spec) return 0;
     return fail(4, std::string(who) + ": the sub-box raytracer has one spectrum for all sources, and the sources on the device "
                                       "carry table sets of their own (source_spectra_to_device); use raytrace_device / evolve3D");
 }
@@ -79,7 +79,7 @@ static int subbox_core(const SubboxCall &c, long long &total_nbox, double &total
     std::fill(st.sb_launch, st.sb_launch + ASORA_SUBBOX_LAUNCH_WORDS, 0);
     st.sb_launch[ASORA_SBL_VALID] = 1;
     // (pair lists are cached by the address of the source list: a caller's temporary list must not meet an older one's entries)
-    struct DropPairs { State &s; bool on; ~DropPairs() { if (on) release_pair_lists(s); } } drop_pairs{st, c.src_pos != st.src_pos};
+    struct DropPairs { State &s; bool on; ~DropPairs() { if (on) release_pair_lists(s); } } drop_pairs{st, c.src_pos != st.sources.pos};
     if (drop_pairs.on) release_pair_lists(st);
     // Round 3: the sources whose column densities do not go back to the caller are swept on the ASORA kernel's tabulated
     // geometry (cells within R_max_LLS only; raytrace.hip, SUBBOX) when that applies; the dumped source -- it needs the
@@ -109,17 +109,12 @@ static int subbox_core(const SubboxCall &c, long long &total_nbox, double &total
     const int max_batch = tab.ok ? (tab.max_batch >= table_sources ? std::max(c.src_count, 1) : tab.max_batch)
                                  : (int)std::max<size_t>(8, std::min<size_t>((budget / per_src) / 8 * 8, 1 << 20));
     const int cap = std::min(std::max(c.src_count, 1), max_batch);
-    if ((size_t)cap > st.subbox_cap) {                   // per-source bookkeeping of a batch, kept between calls
-        for (void *q : {(void *)st.sb_active, (void *)st.sb_nbox, (void *)st.sb_loss, (void *)st.sb_loss_final})
-            if (q) (void)hipFree(q);
-        st.sb_active = st.sb_nbox = nullptr; st.sb_loss = st.sb_loss_final = nullptr; st.subbox_cap = 0;
-        ASORA_HIP_TRY(hipMalloc(&st.sb_active, sizeof(int) * cap));
-        ASORA_HIP_TRY(hipMalloc(&st.sb_nbox, sizeof(int) * cap));
-        ASORA_HIP_TRY(hipMalloc(&st.sb_loss, sizeof(double) * cap));
-        ASORA_HIP_TRY(hipMalloc(&st.sb_loss_final, sizeof(double) * cap));
-        st.subbox_cap = (size_t)cap;
-    }
-    if (!st.sb_nactive) ASORA_HIP_TRY(hipMalloc(&st.sb_nactive, sizeof(int)));
+    // per-source bookkeeping of a batch, kept between calls
+    if (int rc = st.subbox.active.reserve((size_t)cap)) return rc;
+    if (int rc = st.subbox.nbox.reserve((size_t)cap)) return rc;
+    if (int rc = st.subbox.loss.reserve((size_t)cap)) return rc;
+    if (int rc = st.subbox.loss_final.reserve((size_t)cap)) return rc;
+    if (int rc = st.subbox.nactive.allocate(1)) return rc;
     std::vector<int> h_nbox((size_t)cap);
     std::vector<double> h_loss((size_t)cap);
 
@@ -130,22 +125,17 @@ static int subbox_core(const SubboxCall &c, long long &total_nbox, double &total
         const int fly_count = tab.ok ? (dump_here ? 1 : 0) : batch;
         const int fly_first = tab.ok ? batch - fly_count : 0;          // batch-local index of the first source swept on the fly
         const size_t need = (size_t)8 * ((std::max(fly_count, 1) + 7) / 8) * per_src;
-        if (need > st.shell_scratch_bytes) {
-            if (st.shell_scratch) ASORA_HIP_TRY(hipFree(st.shell_scratch));
-            st.shell_scratch = nullptr; st.shell_scratch_bytes = 0;
-            ASORA_HIP_TRY(hipMalloc(&st.shell_scratch, need));
-            st.shell_scratch_bytes = need;
-        }
+        if (int rc = st.shell_scratch.reserve(need / sizeof(double))) return rc;
         const int first = c.src_begin + done;
         p.scratch = st.shell_scratch;
         p.src_begin = first + fly_first; p.src_count = fly_count;
-        p.active = st.sb_active + fly_first; p.loss = st.sb_loss + fly_first;
+        p.active = st.subbox.active + fly_first; p.loss = st.subbox.loss + fly_first;
         tp.src_begin = first; tp.src_count = batch - fly_count;
-        tp.sb_active = st.sb_active; tp.sb_loss = st.sb_loss;
+        tp.sb_active = st.subbox.active; tp.sb_loss = st.subbox.loss;
         int n_active = 0;
         if (int rc = launch_subbox_decide(st, 0, batch, c.src_flux, first, (double)c.loss_fraction, range_open ? 1 : 0,
-                                          st.sb_active, st.sb_loss, st.sb_loss_final, st.sb_nbox, st.sb_nactive)) return rc;
-        ASORA_HIP_TRY(hipMemcpyAsync(&n_active, st.sb_nactive, sizeof(int), hipMemcpyDeviceToHost, st.stream));
+                                          st.subbox.active, st.subbox.loss, st.subbox.loss_final, st.subbox.nbox, st.subbox.nactive)) return rc;
+        ASORA_HIP_TRY(hipMemcpyAsync(&n_active, st.subbox.nactive, sizeof(int), hipMemcpyDeviceToHost, st.stream));
         ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
         long long box = 0;                                    // half-width of the current sub-box, f90:199-200
         while (n_active > 0) {
@@ -171,13 +161,13 @@ static int subbox_core(const SubboxCall &c, long long &total_nbox, double &total
             if (beside) ASORA_HIP_TRY(hipStreamWaitEvent(st.stream, st.side_done[0], 0));
             const int more_range = (box < ext_r && box < ext_l) ? 1 : 0;          // f90:194-195
             if (int rc = launch_subbox_decide(st, 1, batch, c.src_flux, first, (double)c.loss_fraction, more_range,
-                                              st.sb_active, st.sb_loss, st.sb_loss_final, st.sb_nbox, st.sb_nactive)) return rc;
-            ASORA_HIP_TRY(hipMemcpyAsync(&n_active, st.sb_nactive, sizeof(int), hipMemcpyDeviceToHost, st.stream));
+                                              st.subbox.active, st.subbox.loss, st.subbox.loss_final, st.subbox.nbox, st.subbox.nactive)) return rc;
+            ASORA_HIP_TRY(hipMemcpyAsync(&n_active, st.subbox.nactive, sizeof(int), hipMemcpyDeviceToHost, st.stream));
             ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
         }
         st.sb_launch[ASORA_SBL_BATCHES] += 1;
-        ASORA_HIP_TRY(hipMemcpy(h_nbox.data(), st.sb_nbox, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost));
-        ASORA_HIP_TRY(hipMemcpy(h_loss.data(), st.sb_loss_final, (size_t)batch * sizeof(double), hipMemcpyDeviceToHost));
+        ASORA_HIP_TRY(hipMemcpy(h_nbox.data(), st.subbox.nbox, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost));
+        ASORA_HIP_TRY(hipMemcpy(h_loss.data(), st.subbox.loss_final, (size_t)batch * sizeof(double), hipMemcpyDeviceToHost));
         for (int s = 0; s < batch; ++s) { total_nbox += h_nbox[s]; total_loss += h_loss[s]; }   // f90:246-247, in source order
         done += batch;
     }
@@ -193,21 +183,6 @@ static int subbox_core(const SubboxCall &c, long long &total_nbox, double &total
 }
 
 } // namespace asora
-
-namespace {
-struct DeviceBuffers {      // frees what the call allocated, on every exit path
-    std::vector<void *> ptrs;
-    ~DeviceBuffers() { for (void *q : ptrs) (void)hipFree(q); }
-    template <typename T> int alloc(T *&out, size_t count)
-    {
-        void *d = nullptr;
-        ASORA_HIP_TRY(hipMalloc(&d, std::max<size_t>(count, 1) * sizeof(T)));
-        ptrs.push_back(d);
-        out = static_cast<T *>(d);
-        return 0;
-    }
-};
-}
 
 using namespace asora;
 
@@ -230,7 +205,7 @@ int c2ray_do_all_sources(const double *normflux, const int32_t *srcpos, int max_
     clear_error();
     State &st = state();
     const char *who = "c2ray_do_all_sources";
-    if (st.plane.count > 0)
+    if (st.medium.plane.count > 0)
         return fail(4, std::string(who) + ": a plane-parallel flux (asora_plane_flux) has no sub-box sweep");
     if (st.opt[ASORA_OPT_OPEN_BOUNDARIES])
         return fail(4, std::string(who) + ": open boundaries (ASORA_OPT_OPEN_BOUNDARIES) have no sub-box sweep (the reference's Fortran has no such mode)");
@@ -259,21 +234,20 @@ int c2ray_do_all_sources(const double *normflux, const int32_t *srcpos, int max_
                 return fail(3, std::string(who) + ": source " + std::to_string(s + 1) + " lies outside the mesh (1-based " +
                                    std::to_string(srcpos[3 * s + ax]) + " on axis " + std::to_string(ax + 1) + ")");
 
-    DeviceBuffers tmp;
     const size_t bytes = st.ncell * sizeof(double);
     // inputs: grids in Fortran order, sources 1-based
     if (int rc = asora_grid_to_device(ASORA_GRID_NDENS, ndens, N, 'F')) return rc;
     if (int rc = asora_grid_to_device(ASORA_GRID_XH_AV, xh_av, N, 'F')) return rc;
     if (heat) { if (int rc = asora_grid_to_device(ASORA_GRID_PHI_HEAT, phi_heat, N, 'F')) return rc; }
 
-    int32_t *d_pos = nullptr; double *d_flux = nullptr; double2 *d_tables = nullptr;
+    Scoped<int32_t> d_pos; Scoped<double> d_flux; Scoped<double2> d_tables;     // (of this call: freed on every exit path)
     std::vector<int32_t> host_pos0;
     if (NumSrc > 0) {
         host_pos0.resize(3 * (size_t)NumSrc);
         std::vector<int32_t> &pos0 = host_pos0;
         for (size_t q = 0; q < pos0.size(); ++q) pos0[q] = srcpos[q] - 1;
-        if (int rc = tmp.alloc(d_pos, pos0.size())) return rc;
-        if (int rc = tmp.alloc(d_flux, (size_t)NumSrc)) return rc;
+        if (int rc = d_pos.allocate(pos0.size())) return rc;
+        if (int rc = d_flux.allocate((size_t)NumSrc)) return rc;
         ASORA_HIP_TRY(hipMemcpy(d_pos, pos0.data(), pos0.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         ASORA_HIP_TRY(hipMemcpy(d_flux, normflux, (size_t)NumSrc * sizeof(double), hipMemcpyHostToDevice));
     }
@@ -284,7 +258,7 @@ int c2ray_do_all_sources(const double *normflux, const int32_t *srcpos, int max_
                                 heat ? heat_thin_table : nullptr};
         for (int t = 0; t < 4 && !grey; ++t)
             if (src[t]) pack_rate_table(pairs.data(), t, src[t], len);
-        if (int rc = tmp.alloc(d_tables, pairs.size())) return rc;
+        if (int rc = d_tables.allocate(pairs.size())) return rc;
         ASORA_HIP_TRY(hipMemcpy(d_tables, pairs.data(), pairs.size() * sizeof(double2), hipMemcpyHostToDevice));
     }
 
@@ -333,7 +307,7 @@ int asora_subbox_raytrace_device(int max_subbox, int subboxsize, float loss_frac
     if (int rc = require_init("subbox_raytrace_device")) return rc;
     State &st = state();
     const char *who = "subbox_raytrace_device";
-    if (st.plane.count > 0)
+    if (st.medium.plane.count > 0)
         return fail(4, std::string(who) + ": a plane-parallel flux (asora_plane_flux) has no sub-box sweep");
     if (st.opt[ASORA_OPT_OPEN_BOUNDARIES])
         return fail(4, std::string(who) + ": open boundaries (ASORA_OPT_OPEN_BOUNDARIES) have no sub-box sweep (the reference's Fortran has no such mode)");
@@ -341,17 +315,17 @@ int asora_subbox_raytrace_device(int max_subbox, int subboxsize, float loss_frac
     if (!st.grid_valid[ASORA_GRID_XH_AV]) return fail(4, std::string(who) + ": xh_av not on device");
     if (subboxsize < 1) return fail(3, std::string(who) + ": subboxsize must be >= 1");
     const bool grey = st.opt[ASORA_OPT_GREY_NOTABLES] != 0;
-    if (!grey && (!st.tables || NumTau < 1)) return fail(4, std::string(who) + ": radiation tables not on device");
+    if (!grey && (!st.sources.tables || NumTau < 1)) return fail(4, std::string(who) + ": radiation tables not on device");
     if (int rc = check_sources(who, 4, "source range outside the uploaded sources", src_begin, src_count)) return rc;
     if (int rc = refuse_source_spectra(who)) return rc;
     const bool heat = !grey && st.opt[ASORA_OPT_HEATING] != 0;
-    if (heat && !st.have_heat_tables) return fail(4, std::string(who) + ": heating requested but no heating tables on device");
+    if (heat && !st.sources.loaded.heat_tables) return fail(4, std::string(who) + ": heating requested but no heating tables on device");
     SubboxCall c;
     c.max_subbox = max_subbox; c.subboxsize = subboxsize; c.loss_fraction = loss_fraction;
     c.sig = sig; c.dr = dr; c.R = R_max_LLS; c.minlogtau = minlogtau; c.dlogtau = dlogtau; c.NumTau = NumTau;
-    c.table_len = st.table_len > 0 ? st.table_len : 1; c.tables = st.tables;
-    c.src_pos = st.src_pos; c.src_flux = st.src_flux; c.src_begin = src_begin; c.src_count = src_count;
-    c.host_pos = st.src_pos_host.empty() ? nullptr : st.src_pos_host.data();
+    c.table_len = st.sources.loaded.table_len > 0 ? st.sources.loaded.table_len : 1; c.tables = st.sources.tables;
+    c.src_pos = st.sources.pos; c.src_flux = st.sources.flux; c.src_begin = src_begin; c.src_count = src_count;
+    c.host_pos = st.sources.loaded.pos_host.empty() ? nullptr : st.sources.loaded.pos_host.data();
     c.heat = heat; c.keep_heat = false; c.dump = nullptr;
     long long total_nbox = 0;
     double total_loss = 0.0;

@@ -171,40 +171,40 @@ int asora_topology(int which_grid, double threshold, int phase, int periodic, in
     if (int rc = ensure_region_buffers(st)) return rc;
     const int N = st.N, W = (N + 63) / 64;
     const size_t ncell = st.ncell, nwords = (size_t)N * N * W;
-    if (!st.topo_complement) ASORA_HIP_TRY(hipMalloc(&st.topo_complement, sizeof(unsigned long long) * nwords));
+    if (int rc = st.topology.complement.allocate(nwords)) return rc;
 
-    unsigned long long *res = st.region_result;
+    unsigned long long *res = st.regions.result;
     ASORA_HIP_TRY(hipMemsetAsync(res, 0, sizeof(unsigned long long) * ASORA_TOPO_TALLIES, st.stream));
     if (int rc = launch_bubble_mask(st, which_grid, threshold, phase, false)) return rc;
 
     TopoParams p;
-    p.mask = st.bubble_mask; p.result = res; p.N = N; p.W = W; p.periodic = periodic != 0;
+    p.mask = st.bubbles.mask; p.result = res; p.N = N; p.W = W; p.periodic = periodic != 0;
     p.span = p.periodic ? N : N + 1;
     p.WT = p.periodic ? W : N / 64 + 1;
     const dim3 block(TP_THREADS);
     hipLaunchKernelGGL(topology_count_kernel, dim3(topo_blocks(st, (size_t)p.span * p.span * p.WT)), block, 0, st.stream, p);
     ASORA_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(topology_complement_kernel, dim3(topo_blocks(st, nwords)), block, 0, st.stream,
-                       (const unsigned long long *)st.bubble_mask, N, W, nwords, st.topo_complement);
+                       (const unsigned long long *)st.bubbles.mask, N, W, nwords, st.topology.complement);
     ASORA_HIP_TRY(hipGetLastError());
 
     const dim3 cells(topo_blocks(st, ncell));
-    if (int rc = launch_region_label(st, st.bubble_mask, p.periodic, connectivity)) return rc;
-    hipLaunchKernelGGL(topology_roots_kernel, cells, block, 0, st.stream, (const unsigned *)st.region_label, (const unsigned *)st.region_volume,
+    if (int rc = launch_region_label(st, st.bubbles.mask, p.periodic, connectivity)) return rc;
+    hipLaunchKernelGGL(topology_roots_kernel, cells, block, 0, st.stream, (const unsigned *)st.regions.label, (const unsigned *)st.regions.volume,
                        ncell, res, (int)ASORA_TOPO_COMPONENTS, -1);
     ASORA_HIP_TRY(hipGetLastError());
-    if (int rc = launch_region_label(st, st.topo_complement, p.periodic, connectivity == 6 ? 26 : 6)) return rc;
+    if (int rc = launch_region_label(st, st.topology.complement, p.periodic, connectivity == 6 ? 26 : 6)) return rc;
     if (!p.periodic) {
-        hipLaunchKernelGGL(topology_faces_kernel, dim3(topo_blocks(st, 6 * (size_t)N * N)), block, 0, st.stream, (const unsigned *)st.region_label,
-                           N, st.region_volume);
+        hipLaunchKernelGGL(topology_faces_kernel, dim3(topo_blocks(st, 6 * (size_t)N * N)), block, 0, st.stream, (const unsigned *)st.regions.label,
+                           N, st.regions.volume);
         ASORA_HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(topology_roots_kernel, cells, block, 0, st.stream, (const unsigned *)st.region_label, (const unsigned *)st.region_volume,
+    hipLaunchKernelGGL(topology_roots_kernel, cells, block, 0, st.stream, (const unsigned *)st.regions.label, (const unsigned *)st.regions.volume,
                        ncell, res, (int)ASORA_TOPO_COMPLEMENT_COMPONENTS, p.periodic ? -1 : (int)ASORA_TOPO_CAVITIES);
     ASORA_HIP_TRY(hipGetLastError());
-    ASORA_HIP_TRY(hipMemcpyAsync(st.bubble_host, res, sizeof(unsigned long long) * ASORA_TOPO_TALLIES, hipMemcpyDeviceToHost, st.stream));
+    ASORA_HIP_TRY(hipMemcpyAsync(st.bubbles.host, res, sizeof(unsigned long long) * ASORA_TOPO_TALLIES, hipMemcpyDeviceToHost, st.stream));
     ASORA_HIP_TRY(hipStreamSynchronize(st.stream));
-    for (int t = 0; t < ASORA_TOPO_TALLIES; ++t) tallies[t] = st.bubble_host[t];
+    for (int t = 0; t < ASORA_TOPO_TALLIES; ++t) tallies[t] = st.bubbles.host[t];
     return 0;
 }
 

@@ -338,6 +338,13 @@ class _LibAsora:
         return {"candidates": n.value, "chosen_probe_ms": a.value, "slowest_probe_ms": b.value,
                 "device_init_ms": t.value, "probe_cost_ms": pr.value}
 
+    def live_buffers(self, lifetime):
+        """(count, bytes) of the device and pinned buffers the library holds: lifetime 0 = the mesh's (released by device_close),
+        1 = the process's (never released).  Host only."""
+        n, b = C.c_longlong(0), C.c_ulonglong(0)
+        _capi.check(self._lib.asora_debug_live_buffers(int(lifetime), C.byref(n), C.byref(b)), "debug_live_buffers")
+        return n.value, b.value
+
     def evolve_slab_fold_all(self):
         _capi.check(self._lib.asora_evolve_slab_fold_all(), "evolve_slab_fold_all")
 

@@ -98,6 +98,22 @@ def test_errors_come_back_as_runtime_errors_with_message(built):
     """)
 
 
+def test_live_buffers_before_any_device_init(built):
+    """asora_debug_live_buffers reads the registry of the library's buffers on the host: callable with no device, and a process
+    that never called device_init holds nothing of either lifetime."""
+    _without_a_gpu("""
+        from pyc2ray_amd.load_extensions import load_asora
+        lib = load_asora()
+        assert lib.live_buffers(0) == (0, 0)
+        assert lib.live_buffers(1) == (0, 0)
+        with pytest.raises(RuntimeError, match="lifetime"):
+            lib.live_buffers(2)
+        with pytest.raises(RuntimeError):          # no GPU here: a refused device_init leaves nothing of the mesh behind
+            lib.device_init(8, 1)
+        assert lib.live_buffers(0) == (0, 0)
+    """)
+
+
 def test_format_sources_layout():
     from pyc2ray_amd.utils.sourceutils import format_sources
     pos = np.array([[1, 4], [2, 5], [3, 6]], dtype=float)          # (3, 2), 1-based
