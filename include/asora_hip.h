@@ -753,6 +753,84 @@ int asora_los_velocity_clear(void);
 enum { ASORA_PSLOS_STAGES = 6 };
 int asora_debug_power_spectrum_los_ms(double *ms /* [ASORA_PSLOS_STAGES] */);
 
+/* The Lyman-alpha forest of the state: the optical depth tau and the transmitted flux F = exp(-tau) along each of the N^2 lines of one
+ * axis, every cell's neutral hydrogen spread over its displaced extent in velocity space and convolved with its thermal Doppler
+ * profile; the one-point statistics of F and tau, and the dark gaps.  The specification, which no
+ * implementation detail enters:
+ *   inputs     : x = ASORA_GRID_XH, n = ASORA_GRID_NDENS, T = ASORA_GRID_TEMP; v, the line-of-sight velocity buffer of
+ *                asora_los_velocity_to_device, with use_velocity = 0: u = 0, no velocity is needed and velocity_scale is not looked
+ *                at.  velocity_scale: cells per unit of v; b_scale: the Doppler parameter in cells per sqrt(K); tau_scale: the
+ *                Gunn-Peterson optical depth per unit neutral density, I_alpha / H(z), I_alpha = pi e^2 f_alpha lambda_alpha /
+ *                (m_e c), f_alpha = 0.4164, lambda_alpha = 1215.67 Angstrom;
+ *   per line   : each of the N^2 lines along los_axis is periodic with the cells q = 0 ... N - 1 and is handled alone.  Every
+ *                operation below is one IEEE double operation, in the order written; nothing is contracted into a fused
+ *                multiply-add; erf and exp are the device library's:
+ *                  u[q] = v[q] velocity_scale;  d[q] = 0.5 (u[q - 1] + u[q]);  a = d[q], b = 1.0 + d[q + 1] (the edges of
+ *                  asora_redshift_space_field);  lo = b < a ? b : a, hi = b < a ? a : b, width = hi - lo;
+ *                  bt[q] = b_scale sqrt(T[q]) where that is > 2^-10, else 2^-10 (so for T = 0 and for the NaN of a negative T);
+ *                  g[q] = tau_scale ((1.0 - x[q]) n[q]);
+ *   weight     : of cell q on the pixel p = q + o, o an integer, at the pixel centre s = (double)o + 0.5:
+ *                  width >= 2^-10 : w = 0 if (s - hi) > 6.0 bt or (lo - s) > 6.0 bt, else
+ *                                   w = 0.5 (erf((s - lo) / bt) - erf((s - hi) / bt)) / width;
+ *                  width <  2^-10 : (a degenerate cell) c = 0.5 (lo + hi), t = (s - c) / bt;  w = 0 if |t| > 6.0, else
+ *                                   w = (0.5641895835477563 / bt) exp(-(t t)).
+ *                The cut at six Doppler widths is part of the definition: skipping a term beyond it is exact, and the result does
+ *                not depend on W once W covers every cell's reach;
+ *   tau, F     : tau[p] = the sum over o = -W ... W, ascending, of w(q, o) g[q], q = (p - o) mod N, started from +0.0, each product
+ *                rounded before it is added; a term outside the cut, or with g[q] == 0, is left out (so a non-finite g[q] reaches the
+ *                pixels inside its cut only);  F[p] = exp(-tau[p]).  tau is sampled at the pixel centres, not averaged over the
+ *                pixels: a cell that is narrower than a pixel after the mapping and colder than the distance to the nearest
+ *                centre over six lies between two centres and adds to no pixel;
+ *   window     : reach[q] = max((6.0 bt - lo) + 0.5, (hi + 6.0 bt) - 0.5).  window > 0 is W, refused if 2 W + 1 > N.  window = 0:
+ *                W = max(1, ceil(max_q reach[q])), then capped at (N - 1) / 2; the maximum is reduced on the device (a maximum does
+ *                not depend on the order of its operands) and read back by the host, so the automatic form costs one more
+ *                synchronisation than the explicit one (two instead of one);
+ *   counts     : counts[ASORA_LYA_*]: NONFINITE, the tau that are not finite; WINDOW, the W used; CLIPPED, the cells with
+ *                ceil(reach[q]) > W (exact, never silently zero: 0 says that no term was cut off by the window); DEGENERATE, the
+ *                cells with width < 2^-10; and the dark gaps below;
+ *   statistics : stats[ASORA_LYA_*]: SUM_F and SUM_F2 over the cells, TAU_MIN and TAU_MAX (over the tau that are not NaN; +inf and
+ *                -inf if there is none);  pdf[n_bins] (uint64): F binned by edges[n_bins + 1], finite and non-decreasing, n_bins <=
+ *                ASORA_LYA_MAX_BINS, or n_bins = 0 with edges and pdf unused: edges[i] <= F < edges[i + 1], a cell outside every
+ *                bin (a NaN too) is dropped;
+ *   dark gaps  : exact integers.  On each periodic line a gap is a maximal run of pixels with F < gap_threshold; a run through the
+ *                end of the line joins the start; a wholly dark line is one gap of length N and adds to FULL_LINES.  gaps[N + 1]
+ *                (uint64): the number of gaps by length, gaps[0] = 0;  N_DARK the dark pixels, N_GAPS, LONGEST;
+ *   outputs    : tau_out [N^3] and flux_out [N^3] or NULL, in C order.  dst_grid >= 0 writes F (dst_what = ASORA_LYA_FLUX) or tau
+ *                (ASORA_LYA_TAU) into that grid under the rules of asora_redshift_space_field: allocated as asora_grid_to_device
+ *                would allocate it, marked as holding data, and it may be one of the three grids the call reads.  dst_grid = -1:
+ *                dst_what is not looked at.
+ * Every floating-point sum has an order fixed by (N, los_axis) and no floating-point atomic enters: the same call returns the same
+ * bits.  Device memory: tau lies in the buffer asora_smooth_field and asora_redshift_space_field keep their result in (each call
+ * overwrites the others'), unless dst_grid takes it; N^3 doubles more only for flux_out without a grid for F; 64 bytes per workgroup
+ * of the line kernel; kept until the device is closed.
+ * Fail with code 2 before device_init; 3 for: los_axis outside 0 ... 2, a b_scale or tau_scale that is not finite and > 0, with
+ * use_velocity a non-finite velocity_scale or no velocity on the device, a non-finite gap_threshold, n_bins outside 0 ...
+ * ASORA_LYA_MAX_BINS, with n_bins > 0 null edges or pdf and edges that are not finite and non-decreasing, null stats, counts or gaps,
+ * dst_grid outside -1 ... ASORA_GRID_COUNT - 1, with dst_grid >= 0 a dst_what that is neither, window < 0, 2 window + 1 > N; 4 for
+ * one of the three grids without data and for a mesh with N > ASORA_REGION_MAX_N; 10 for a failed allocation.  A refused call writes
+ * nothing, on the host or on the device. */
+enum { ASORA_LYA_FLUX = 0, ASORA_LYA_TAU = 1, ASORA_LYA_MAX_BINS = 1024 };
+enum { ASORA_LYA_SUM_F = 0, ASORA_LYA_SUM_F2 = 1, ASORA_LYA_TAU_MIN = 2, ASORA_LYA_TAU_MAX = 3, ASORA_LYA_STATS = 4 };
+enum { ASORA_LYA_NONFINITE = 0, ASORA_LYA_WINDOW = 1, ASORA_LYA_CLIPPED = 2, ASORA_LYA_DEGENERATE = 3, ASORA_LYA_N_DARK = 4,
+       ASORA_LYA_N_GAPS = 5, ASORA_LYA_LONGEST = 6, ASORA_LYA_FULL_LINES = 7, ASORA_LYA_COUNTS = 8 };
+int asora_lyman_alpha_forest(int los_axis, int use_velocity, double velocity_scale, double b_scale, double tau_scale,
+                             int window /* 0: automatic */, double gap_threshold,
+                             int n_bins, const double *edges,                     /* [n_bins + 1], or n_bins = 0 and NULL */
+                             int dst_grid /* -1, or a grid selector */, int dst_what /* ASORA_LYA_FLUX or ASORA_LYA_TAU */,
+                             double *stats /* [ASORA_LYA_STATS] */, unsigned long long *counts /* [ASORA_LYA_COUNTS] */,
+                             unsigned long long *pdf /* [n_bins], or NULL */, unsigned long long *gaps /* [N + 1] */,
+                             double *tau_out /* NULL, or host [N^3] */, double *flux_out /* NULL, or host [N^3] */);
+/* The durations (ms) of the stages of the last asora_lyman_alpha_forest call that ran with ASORA_OPT_TIMING = 1: ms[0] the staging
+ * of the lines for the largest reach with its read-back (0 with an explicit window), [1] the optical depth, the flux and -- in the
+ * same launch, on the lines where they lie -- the dark gaps, [2] the statistics, [3] the fold of the workgroups' partial results;
+ * zeros if no such call has run.  Code 3 for ms = NULL. */
+enum { ASORA_LYA_STAGES = 4 };
+int asora_debug_lya_forest_ms(double *ms /* [ASORA_LYA_STAGES] */);
+/* How asora_lyman_alpha_forest deals the N^2 lines along los_axis of a mesh of N cells a side to its workgroups (a host computation:
+ * callable without a device): tiles[0] the lines of a tile, [1] the work items of a workgroup, [2] the workgroups, [3] the bytes of
+ * LDS of one.  Code 3 for tiles = NULL, N outside 1 ... ASORA_REGION_MAX_N or los_axis outside 0 ... 2. */
+int asora_debug_lya_forest_tiles(int N, int los_axis, int *tiles /* [4] */);
+
 /* ------------------------------------------------------------------------------------------ */
 /* C. Options, measurement and diagnostics                                                     */
 /* ------------------------------------------------------------------------------------------ */

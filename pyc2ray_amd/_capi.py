@@ -60,6 +60,13 @@ ANISO_CYLINDRICAL, ANISO_MU = range(2)
 ANISO_MODES = 2
 ANISO_MAX_BINS = 1024
 PSLOS_STAGES = 6
+LYA_FLUX, LYA_TAU = range(2)
+LYA_MAX_BINS = 1024
+LYA_SUM_F, LYA_SUM_F2, LYA_TAU_MIN, LYA_TAU_MAX = range(4)
+LYA_STATS = 4
+(LYA_NONFINITE, LYA_WINDOW, LYA_CLIPPED, LYA_DEGENERATE, LYA_N_DARK, LYA_N_GAPS, LYA_LONGEST, LYA_FULL_LINES) = range(8)
+LYA_COUNTS = 8
+LYA_STAGES = 4
 (PRIM_LOG2, PRIM_LOOKUP, PRIM_DIV, PRIM_MUL, PRIM_ADD, PRIM_ABSORBER, PRIM_PHOTO, PRIM_HEAT, PRIM_GREY) = range(9)
 PRIM_COUNT = 9
 
@@ -166,6 +173,10 @@ SIGNATURES = {
     "asora_los_velocity_to_device": (C.c_int, [_dp, C.c_int, C.c_char, _dp]),
     "asora_los_velocity_clear": (C.c_int, []),
     "asora_debug_power_spectrum_los_ms": (C.c_int, [_dp]),
+    "asora_lyman_alpha_forest": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.c_int, _dp, C.c_int,
+                                           C.c_int, _dp, _u64p, _u64p, _u64p, _dp, _dp]),
+    "asora_debug_lya_forest_ms": (C.c_int, [_dp]),
+    "asora_debug_lya_forest_tiles": (C.c_int, [C.c_int, C.c_int, _ip]),
     "asora_set_option": (C.c_int, [C.c_int, C.c_int]),
     "asora_get_option": (C.c_int, [C.c_int]),
     "asora_kernel_time_ms": (C.c_int, [C.c_int, _dp, C.POINTER(C.c_long)]),

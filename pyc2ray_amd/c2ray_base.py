@@ -68,6 +68,12 @@ Differences from the reference:
     0|1`` (optional key, default 0; with ``redshift_space_binning``, ``redshift_space_bins``, ``redshift_space_los_axis``) and the
     attribute ``redshift_space_stats`` (a bool, assignable between steps) do that after every time step (use_gpu only):
     ``last_redshift_space`` and one line in the log.  Without a velocity the spectrum is the real-space one, and the line says so.
+  * ``lyman_alpha_forest()`` returns the Lyman-alpha forest of the current state along ``los_axis`` -- optical depth and transmitted
+    flux on every line of the box, the effective optical depth, the flux PDF and the dark gaps -- moved by ``los_velocity``, with
+    ``lyman_alpha_b_scale()`` and ``lyman_alpha_tau_scale()`` from the object's cosmology and redshift (pyc2ray_amd/lyman_alpha.py;
+    on the device-resident path from the grids where they lie).  ``Output: lyman_alpha: 0|1`` (optional key, default 0; with
+    ``lyman_alpha_gap_threshold``, ``lyman_alpha_bins``) and the attribute ``lyman_alpha_stats`` (a bool, assignable between steps)
+    do that after every time step (use_gpu only): ``last_lyman_alpha`` and one line in the log.
 """
 import atexit
 import math
@@ -92,6 +98,7 @@ from .granulometry import granulometry_spec, granulometry as field_granulometry,
 from .powerspec import powerspec_spec, powerspec_on_device
 from .smoothing import smoothing_spec, smoothing_on_device, telescope
 from .redshift_space import redshift_space_spec, spectrum_on_device, field_on_device
+from .lyman_alpha import lyman_alpha_spec, forest_on_device
 from .budget import StepBudget
 from .lls import LLSOpacity, LLSSchedule, lls_spec
 from .planeflux import PlaneFlux, plane_flux_spec
@@ -111,6 +118,14 @@ ev2k = 1.0 / 8.617e-05                  # eV to Kelvin
 kpc = 1e3 * pc
 Mpc = 1e6 * pc
 msun2g = 1.98892e33
+# cgs constants of the Lyman-alpha forest (CODATA 2018): lyman_alpha_b_scale, lyman_alpha_tau_scale
+K_BOLTZMANN = 1.380649e-16
+M_PROTON = 1.67262192369e-24
+M_ELECTRON = 9.1093837015e-28
+E_CHARGE = 4.80320471e-10
+C_LIGHT = 2.99792458e10
+LYA_F_ALPHA = 0.4164
+LYA_LAMBDA_ALPHA = 1215.67e-8
 
 
 class FlatLambdaCDMLite:
@@ -347,8 +362,25 @@ class C2Ray:
     #: the order in which __init__ reads their keys and a step writes their lines to the log
     _STEP_STATISTICS = ("photon_budget", "bubble_stats", "region_stats", "topology_stats", "granulometry_stats", "power_spectrum_stats",
                         "observed_stats")
+    # lyman_alpha_gap_threshold: a finite number, default 0.05; lyman_alpha_bins: an int n for n equal bins of the transmitted flux
+    # over [0, 1], or a list of non-decreasing edges, default 20 bins
+    lyman_alpha_stats = _StepStatistic(
+        "lyman_alpha", "last_lyman_alpha", "lyman_alpha_forest", "the optical depth, the statistics and the gaps run on the device",
+        """Does every time step end with the Lyman-alpha forest of its state (:meth:`lyman_alpha_forest` with the ``Output:
+        lyman_alpha_*`` keys and ``los_velocity``; use_gpu=True only: on an object without, True is refused at the assignment)?  A
+        driver may assign a bool between steps.  After a step ``last_lyman_alpha`` holds the result and rank 0 writes one line to
+        the log.""",
+        keys=(("lyman_alpha_gap_threshold", "gap_threshold"), ("lyman_alpha_bins", "bins")),
+        validate=lambda sim, kw: lyman_alpha_spec("Output: lyman_alpha_gap_threshold / lyman_alpha_bins", None, b_scale=1.0, tau_scale=1.0, **kw))
     #: the statistics declared since, behind those: read, computed and logged after them
     _STEP_STATISTICS_APPENDED = ("redshift_space_stats",)
+    #: ... and those declared since then, behind both (the two tuples above keep the contents their tests pin)
+    _STEP_STATISTICS_FURTHER = ("lyman_alpha_stats",)
+
+    @classmethod
+    def _step_statistics(cls):
+        """Every declared statistic, in the order in which __init__ reads their keys and a step computes and logs them."""
+        return cls._STEP_STATISTICS + cls._STEP_STATISTICS_APPENDED + cls._STEP_STATISTICS_FURTHER
 
     def __init__(self, paramfile, Nmesh, use_gpu, use_mpi):
         """Basis class of a C2Ray simulation (pyc2ray/c2ray_base.py:82-145).
@@ -396,7 +428,7 @@ class C2Ray:
         self._lls_init()
         self._boundaries_init()
         self._plane_flux_init()
-        for name in self._STEP_STATISTICS + self._STEP_STATISTICS_APPENDED:
+        for name in self._step_statistics():
             self._statistic_init(name)
         if self.rank == 0:
             if self.gpu:
@@ -580,7 +612,7 @@ class C2Ray:
             self.total_budget = self.__dict__.get("total_budget", StepBudget()) + budget
             if self.rank == 0:
                 self.printlog(budget.log_line())
-        for name in self._STEP_STATISTICS + self._STEP_STATISTICS_APPENDED:
+        for name in self._step_statistics():
             stat = getattr(type(self), name)
             if stat.method is not None and getattr(self, name):
                 result = getattr(self, stat.method)()
@@ -814,10 +846,15 @@ class C2Ray:
         vmax = None if v is None else (self.__dict__.get("_los_velocity_max") or float(np.max(np.abs(v))))
         spec = redshift_space_spec(who, self.N, max_velocity=vmax, **kw)
         lib = self._state_on_device(overwritten=spec["into"] is not None)
+        self._los_velocity_on_device(lib)
+        return lib, spec
+
+    def _los_velocity_on_device(self, lib):
+        """``los_velocity`` uploaded unless the device holds it since its assignment."""
+        v = self.los_velocity
         if v is not None and self.__dict__.get("_los_velocity_max") is None:
             _residency.register(self)                           # (whoever takes the device next says so: _leave_device)
             self.__dict__["_los_velocity_max"] = lib.los_velocity_to_device(np.asarray(v, dtype=np.float64))
-        return lib, spec
 
     def power_spectrum_los(self, **kw):
         """The power spectrum of the current state in redshift space, resolved in direction: a
@@ -846,6 +883,40 @@ class C2Ray:
         who = "C2Ray.redshift_space_field"
         lib, spec = self._redshift_space_call(who, dict(kw))
         return field_on_device(lib, spec)
+
+    # ---- the Lyman-alpha forest (pyc2ray_amd/lyman_alpha.py) ------------------------------------------
+    def lyman_alpha_b_scale(self):
+        """The Doppler parameter of hydrogen in cells of the mesh per sqrt(K) at ``self.zred``: sqrt(2 k_B / m_p) = 0.1284... km/s
+        per sqrt(K), times :meth:`velocity_scale`."""
+        return math.sqrt(2.0 * K_BOLTZMANN / M_PROTON) * 1.0e-5 * self.velocity_scale()
+
+    def lyman_alpha_tau_scale(self):
+        """The Gunn-Peterson optical depth per unit proper neutral hydrogen density (cm^-3) at ``self.zred``: I_alpha / H(z), with
+        I_alpha = pi e^2 f_alpha lambda_alpha / (m_e c) (f_alpha = 0.4164, lambda_alpha = 1215.67 Angstrom; cgs) and H(z) = 100 h
+        E(z) km/s/Mpc from the object's cosmology."""
+        z = float(self.zred)
+        hubble = 100.0 * float(self._ld['Cosmology']['h']) * float(self.cosmology.efunc(z)) * 1.0e5 / Mpc           # 1/s
+        return math.pi * E_CHARGE ** 2 * LYA_F_ALPHA * LYA_LAMBDA_ALPHA / (M_ELECTRON * C_LIGHT) / hubble
+
+    def lyman_alpha_forest(self, **kw):
+        """The Lyman-alpha forest of the current state along ``los_axis``: a :class:`pyc2ray_amd.lyman_alpha.LymanAlphaForest`; the
+        keywords of :func:`pyc2ray_amd.lyman_alpha.lyman_alpha_forest` but the host arrays and ``velocity``.  ``los_axis`` =
+        ``self.los_axis``, ``velocity_scale`` = :meth:`velocity_scale`, ``b_scale`` = :meth:`lyman_alpha_b_scale` and ``tau_scale`` =
+        :meth:`lyman_alpha_tau_scale` unless given, and the ``Output: lyman_alpha_*`` keys of the parameter file for
+        ``gap_threshold`` and ``bins``.  The gas is moved by ``los_velocity``; while that is None it is at rest.  The grids are
+        analysed where they lie, as in :meth:`power_spectrum`; the velocity crosses to the device once per assignment.  ``into``
+        writes a device grid behind the object's back: the object's own device copies come down first, and every grid and the
+        velocity go up again afterwards."""
+        who = "C2Ray.lyman_alpha_forest"
+        for name in ("xh", "ndens", "temp", "velocity", "device_velocity"):
+            if name in kw:
+                raise ValueError(f"{who}: {name} is not for the class (it analyses its own grids with its los_velocity)")
+        kw = {"los_axis": self.los_axis, "velocity_scale": self.velocity_scale(), "b_scale": self.lyman_alpha_b_scale(),
+              "tau_scale": self.lyman_alpha_tau_scale(), **C2Ray.lyman_alpha_stats.defaults(self), **kw}
+        spec = lyman_alpha_spec(who, self.N, device_velocity=self.los_velocity is not None, **kw)
+        lib = self._state_on_device(overwritten=spec["into"] is not None)
+        self._los_velocity_on_device(lib)
+        return forest_on_device(lib, spec)
 
     def evolve3D(self, dt, src_flux, src_pos, src_spectrum=None):
         """Evolve the grid over one time step (c2ray_base.py:170-226).  src_spectrum: with ``BlackBodySource: Teff`` a list, the

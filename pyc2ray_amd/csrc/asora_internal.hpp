@@ -347,6 +347,17 @@ struct State {
         double vmax = 0.0;                  // dies with the velocity
         double ms[ASORA_PSLOS_STAGES] = {0, 0, 0, 0, 0, 0};
     } redshift;
+    // the Lyman-alpha forest's own buffers (asora_lyman_alpha_forest, lya_forest.hip), allocated by the first call that needs them:
+    // F [N^3] of a call that returns the flux to the host without writing it into a grid; the result words with the gap and PDF
+    // counts behind them; the PDF's edges; the partials of the statistics' workgroups and of the line kernel's; the pinned area the
+    // edges leave through and the results arrive in.  tau lies in smoothing.field (either call overwrites the other's), the
+    // velocity is redshift.velocity.  ms: the stage times of the last call under ASORA_OPT_TIMING
+    struct Lyman {
+        MeshBuffer<double> flux, edges, stat_partial;
+        MeshBuffer<unsigned long long> result, block_partial;
+        MeshPinned<unsigned long long> host;
+        double ms[ASORA_LYA_STAGES] = {0, 0, 0, 0};
+    } lyman;
 
     ProcessBuffer<unsigned long long> counters;   // [COUNTER_FIELDS * COUNTER_SLOTS]: gamma cells, evaluated cells, exact zeros left out, spread over the slots
     long long last_gamma_cells = 0, last_eval_cells = 0;

@@ -686,6 +686,49 @@ class _LibAsora:
                     "redshift_space_field")
         return out
 
+    def lyman_alpha_forest(self, los_axis, velocity_scale, b_scale, tau_scale, window=0, gap_threshold=0.05, edges=None, dst_grid=None,
+                           dst_what=_capi.LYA_FLUX, tau=False, flux=False):
+        """The Lyman-alpha forest of the device grids along `los_axis`, moved by the velocity of los_velocity_to_device with
+        `velocity_scale` not None (include/asora_hip.h, asora_lyman_alpha_forest): a dict of ``stats`` (``_capi.LYA_STATS`` float64,
+        indexed by ``_capi.LYA_SUM_F`` ...), ``counts`` (``_capi.LYA_COUNTS`` uint64, indexed by ``_capi.LYA_NONFINITE`` ...), ``gaps``
+        (uint64, N + 1: the gaps by length), ``pdf`` (with `edges`: uint64, ``len(edges) - 1`` bins; else None), ``tau`` and ``flux``
+        (with `tau`, `flux`: (N, N, N) float64; else None).  `window`: W, or 0 for the automatic one; `dst_grid`: the grid F
+        (`dst_what` = ``_capi.LYA_FLUX``) or tau (``_capi.LYA_TAU``) is written into (None: none)."""
+        if self._N is None:
+            raise RuntimeError("lyman_alpha_forest needs a device initialised through device_init (the mesh size)")
+        e = None
+        if edges is not None:
+            e = np.ascontiguousarray(edges, dtype=np.float64)
+            if e.ndim != 1 or e.size < 2:
+                raise ValueError("lyman_alpha_forest: edges must be one-dimensional, two or more")
+        out = dict(stats=np.zeros(_capi.LYA_STATS), counts=np.zeros(_capi.LYA_COUNTS, dtype=np.uint64),
+                   gaps=np.zeros(self._N + 1, dtype=np.uint64), pdf=None if e is None else np.zeros(e.size - 1, dtype=np.uint64),
+                   tau=np.zeros((self._N,) * 3) if tau else None, flux=np.zeros((self._N,) * 3) if flux else None)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(_capi._dp)
+        uptr = lambda a: None if a is None else a.ctypes.data_as(_capi._u64p)
+        use = velocity_scale is not None
+        _capi.check(self._lib.asora_lyman_alpha_forest(int(los_axis), 1 if use else 0, float(velocity_scale) if use else 0.0, float(b_scale),
+                                                       float(tau_scale), int(window), float(gap_threshold), 0 if e is None else int(e.size) - 1,
+                                                       ptr(e), -1 if dst_grid is None else int(dst_grid), int(dst_what), ptr(out["stats"]),
+                                                       uptr(out["counts"]), uptr(out["pdf"]), uptr(out["gaps"]), ptr(out["tau"]),
+                                                       ptr(out["flux"])), "lyman_alpha_forest")
+        return out
+
+    def lyman_alpha_forest_ms(self):
+        """The stage times (ms) of the last lyman_alpha_forest call that ran with OPT_TIMING: the largest reach with its read-back,
+        the optical depth with the gaps, the statistics, the fold (include/asora_hip.h, asora_debug_lya_forest_ms)."""
+        ms = np.zeros(_capi.LYA_STAGES)
+        _capi.check(self._lib.asora_debug_lya_forest_ms(_capi.dptr(ms)), "debug_lya_forest_ms")
+        return ms
+
+    def lyman_alpha_forest_tiles(self, N, los_axis):
+        """How lyman_alpha_forest deals the lines along `los_axis` of a mesh of N cells a side to its workgroups: a dict of ``lines``
+        (of a tile), ``work_items`` (of a workgroup), ``workgroups`` and ``lds_bytes`` (include/asora_hip.h,
+        asora_debug_lya_forest_tiles); needs no device."""
+        t = np.zeros(4, dtype=np.int32)
+        _capi.check(self._lib.asora_debug_lya_forest_tiles(int(N), int(los_axis), _capi.iptr(t)), "debug_lya_forest_tiles")
+        return dict(lines=int(t[0]), work_items=int(t[1]), workgroups=int(t[2]), lds_bytes=int(t[3]))
+
     def thermal_stats(self):
         """(cells that hit max_substeps, cells clamped to t_floor, most substeps of one integration) since the last
         chemistry_device / evolve_begin."""
