@@ -831,6 +831,57 @@ int asora_debug_lya_forest_ms(double *ms /* [ASORA_LYA_STAGES] */);
  * LDS of one.  Code 3 for tiles = NULL, N outside 1 ... ASORA_REGION_MAX_N or los_axis outside 0 ... 2. */
 int asora_debug_lya_forest_tiles(int N, int los_axis, int *tiles /* [4] */);
 
+/* The bispectrum of the field of asora_power_spectrum by the FFT triangle estimator: for triangles of
+ * k-shells, the sum of ghat(n1) ghat(n2) ghat(n3) over the closed triples of modes and the number of those triples.  No grid is
+ * written.  The specification, which no implementation detail enters:
+ *   field      : g and ghat(n) are exactly those of asora_power_spectrum: the kinds ASORA_PS_*, the same order of operations, the
+ *                same mean density, the unnormalised transform;
+ *   shells     : n_shells in [1, ASORA_BISPEC_MAX_SHELLS] and thresholds[n_shells + 1], unsigned integers, non-decreasing, with
+ *                thresholds[0] >= 1.  S_a = { n in the full cube of N^3 modes : thresholds[a] <= n2 < thresholds[a + 1] }, with n2 =
+ *                m_x^2 + m_y^2 + m_z^2 of the folded indices m = min(n, N - n), as there.  A shell may be empty;
+ *   shell field: d_a(c) = N^-3 sum over n in S_a of ghat(n) exp(+2 pi i n.c / N), a real field: what asora_smooth_field returns for a
+ *                w_r that is 1 on the shell and 0 elsewhere and no other table (to rounding: columns outside the shell are not
+ *                transformed here).  i_a(c) is the same with ghat = 1;
+ *   triangles  : n_tri in [1, ASORA_BISPEC_MAX_TRIANGLES] and tri[3 n_tri], the shell indices (a, b, c) of each, in any order, with
+ *                repeats within a triangle and duplicates among them allowed (duplicates return equal bytes);
+ *   per triangle: sum_ggg[t] = ((S N^3) N^3) with S = the sum over the N^3 cells of (d_a d_b) d_c, the product formed in this order
+ *                and not contracted; sum_iii[t] the same of (i_a i_b) i_c.  Mathematically sum_ggg[t] is the sum of ghat(n1)
+ *                ghat(n2) ghat(n3) over the ORDERED triples n1 in S_a, n2 in S_b, n3 in S_c with n1 + n2 + n3 = 0 MODULO N on every
+ *                axis, and sum_iii[t] is the number of those triples -- an integer, returned as the double the transforms give
+ *                (the caller rounds, and sees how far it was from an integer).  Closure is modulo N: once a shell reaches beyond
+ *                (N - 1) / 3 in |n|, aliased triangles (n1 + n2 + n3 = a multiple of N that is not 0) are included;
+ *   per shell  : count, sum_k and sum_aa are what asora_power_spectrum returns for kind_a = kind, kind_b = -1 and the same
+ *                thresholds as bins, bit for bit; moments[2] = (sum of g, sum of g^2) likewise.
+ * Every sum over cells is formed in double-double in an order fixed by (N, thresholds, tri) only; no floating-point atomic enters
+ * any of them: the same call returns the same bits.  One synchronisation per call; 2 n_tri + 3 n_shells + 2 numbers cross to the host.
+ * sum_iii depends on (N, thresholds, tri) only: the values of the last call are kept (the values, not the cubes) and returned
+ * without recomputation when those three repeat, as the bytes they were computed as.
+ * Device memory beside the power spectrum's complex buffer, which holds the kept spectrum and is only read on the way back: a
+ * second complex buffer of N N (floor(N/2) + 1) entries, n_shells cubes of N^3 doubles (134 MB per shell at 256^3: 2.1 GB for 16,
+ * 4.3 GB for 32), and 8 KB of partial sums per triangle; allocated by the first call that needs them, the cubes and partials grown
+ * by a later call that needs more, kept until the device is closed.
+ * Fails with code 2 before device_init; 3 for: a bad kind, a non-finite scale, a non-finite or negative t_gamma, n_shells outside
+ * [1, ASORA_BISPEC_MAX_SHELLS], n_tri outside [1, ASORA_BISPEC_MAX_TRIANGLES], a shell index outside [0, n_shells), thresholds not
+ * non-decreasing or thresholds[0] = 0, a null pointer; 4 for a grid the kind needs that holds no data and for a mesh with
+ * N > ASORA_REGION_MAX_N; 10 for a failed allocation.  A refused call writes nothing. */
+enum { ASORA_BISPEC_MAX_SHELLS = 32, ASORA_BISPEC_MAX_TRIANGLES = 8192 };
+int asora_bispectrum(int kind, double scale, double t_gamma, int n_shells, const unsigned *thresholds /* [n_shells + 1] */,
+                     int n_tri, const int32_t *tri /* [3 n_tri] shell indices */,
+                     double *sum_ggg /* [n_tri] */, double *sum_iii /* [n_tri] */,
+                     unsigned long long *count, double *sum_k, double *sum_aa /* [n_shells] each */, double *moments /* [2] */);
+/* The durations (ms) of the stages of the last asora_bispectrum call that ran with ASORA_OPT_TIMING = 1: ms[0] the mean density,
+ * [1], [2], [3] the forward passes along k, j, i, [4] the per-shell binning, [5] the shell fields of g (three passes back per shell),
+ * [6] their triple products with the fold, [7] the shell fields of the indicator, [8] their triple products with the fold.  [7] and
+ * [8] are 0 for a call that returned the kept counts.  Zeros if no such call has run.  Code 3 for ms = NULL. */
+enum { ASORA_BISPEC_STAGES = 9 };
+int asora_debug_bispectrum_ms(double *ms /* [ASORA_BISPEC_STAGES] */);
+/* How asora_bispectrum's product stage deals n_tri triangles and the N^3 cells (a host computation: callable without a device):
+ * out[0] the triangles of one pass over the cubes (the chunk), [1] the passes, [2] the workgroups (a constant), [3] the most and [4]
+ * the fewest tiles a workgroup takes (its trips), [5] the triangles a wave accumulates in registers, [6] the cells of a tile, [7]
+ * the workgroups that take no tile.  Code 3 for out = NULL or N, n_shells, n_tri outside what asora_bispectrum takes. */
+enum { ASORA_BISPEC_PLAN_WORDS = 8 };
+int asora_debug_bispectrum_plan(int N, int n_shells, int n_tri, int32_t *out /* [ASORA_BISPEC_PLAN_WORDS] */);
+
 /* ------------------------------------------------------------------------------------------ */
 /* C. Options, measurement and diagnostics                                                     */
 /* ------------------------------------------------------------------------------------------ */

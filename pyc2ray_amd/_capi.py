@@ -67,6 +67,10 @@ LYA_STATS = 4
 (LYA_NONFINITE, LYA_WINDOW, LYA_CLIPPED, LYA_DEGENERATE, LYA_N_DARK, LYA_N_GAPS, LYA_LONGEST, LYA_FULL_LINES) = range(8)
 LYA_COUNTS = 8
 LYA_STAGES = 4
+BISPEC_MAX_SHELLS = 32
+BISPEC_MAX_TRIANGLES = 8192
+BISPEC_STAGES = 9
+BISPEC_PLAN_WORDS = 8
 (PRIM_LOG2, PRIM_LOOKUP, PRIM_DIV, PRIM_MUL, PRIM_ADD, PRIM_ABSORBER, PRIM_PHOTO, PRIM_HEAT, PRIM_GREY) = range(9)
 PRIM_COUNT = 9
 
@@ -177,6 +181,10 @@ SIGNATURES = {
                                            C.c_int, _dp, _u64p, _u64p, _u64p, _dp, _dp]),
     "asora_debug_lya_forest_ms": (C.c_int, [_dp]),
     "asora_debug_lya_forest_tiles": (C.c_int, [C.c_int, C.c_int, _ip]),
+    "asora_bispectrum": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_uint32), C.c_int, _ip, _dp, _dp, _u64p, _dp, _dp,
+                                   _dp]),
+    "asora_debug_bispectrum_ms": (C.c_int, [_dp]),
+    "asora_debug_bispectrum_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip]),
     "asora_set_option": (C.c_int, [C.c_int, C.c_int]),
     "asora_get_option": (C.c_int, [C.c_int]),
     "asora_kernel_time_ms": (C.c_int, [C.c_int, _dp, C.POINTER(C.c_long)]),

@@ -99,6 +99,7 @@ from .powerspec import powerspec_spec, powerspec_on_device
 from .smoothing import smoothing_spec, smoothing_on_device, telescope
 from .redshift_space import redshift_space_spec, spectrum_on_device, field_on_device
 from .lyman_alpha import lyman_alpha_spec, forest_on_device
+from .bispectrum import bispectrum_spec, bispectrum_on_device
 from .budget import StepBudget
 from .lls import LLSOpacity, LLSSchedule, lls_spec
 from .planeflux import PlaneFlux, plane_flux_spec
@@ -720,6 +721,22 @@ class C2Ray:
         kw = {"scale": self.brightness_temperature_scale(), "box_len": self.boxsize_c / Mpc, **kw}
         spec = powerspec_spec("C2Ray.power_spectrum", self.N, **kw)
         return powerspec_on_device(self._state_on_device(), spec)
+
+    def bispectrum(self, **kw):
+        """The bispectrum of the current state for triangles of k-shells, a :class:`pyc2ray_amd.bispectrum.Bispectrum`; the keywords
+        of :func:`pyc2ray_amd.bispectrum.bispectrum` but ``field``, and ``spin``.  ``kind`` is 'dtb' unless given: the brightness
+        temperature in mK, with ``scale`` = :meth:`brightness_temperature_scale` and ``box_len`` = the comoving side of the box in
+        Mpc unless given.  ``spin``: as in :meth:`power_spectrum`.  The grids are analysed where they lie under the conditions of
+        :meth:`power_spectrum`, else uploaded from the host arrays.
+        There is no per-step switch and no ``Output:`` key for it: the device keeps one N^3 field per shell while it runs, and a
+        driver that wants it calls ``sim.bispectrum()`` after a step."""
+        if "field" in kw:
+            raise ValueError("C2Ray.bispectrum: field is not for the class (it analyses its own grids)")
+        kw = dict(kw)
+        self._spin_t_gamma("C2Ray.bispectrum", kw)
+        kw = {"scale": self.brightness_temperature_scale(), "box_len": self.boxsize_c / Mpc, **kw}
+        spec = bispectrum_spec("C2Ray.bispectrum", self.N, **kw)
+        return bispectrum_on_device(self._state_on_device(), spec)
 
     @staticmethod
     def _observed_filter_spec(who, baseline_km, los_axis):

@@ -358,6 +358,20 @@ struct State {
         MeshPinned<unsigned long long> host;
         double ms[ASORA_LYA_STAGES] = {0, 0, 0, 0};
     } lyman;
+    // the bispectrum's own buffers (asora_bispectrum, bispectrum.hip), allocated by the first call that needs them: the complex
+    // half-space a shell's lines are filtered into on the way back (the kept spectrum is spectrum.modes[0], read only); the shell
+    // fields [n_shells][N^3]; the triangles, one packed word each; the workgroups' partial sums [n_tri][workgroups] (double-double)
+    // and the folded sums [2][n_tri]; the pinned area the triangles leave through and the results arrive in.  cache: the last
+    // call's sum_iii with the (N, thresholds, tri) it belongs to -- values, no device memory, so it may outlive the mesh.  ms: the
+    // stage times of the last call under ASORA_OPT_TIMING
+    struct Bispectrum {
+        MeshBuffer<double2> work;
+        MeshBuffer<double> cubes, partial, result;
+        MeshBuffer<int32_t> tri;
+        MeshPinned<double> host;
+        struct Cache { int N = 0; std::vector<unsigned> thresholds; std::vector<int32_t> tri; std::vector<double> sum_iii; } cache;
+        double ms[ASORA_BISPEC_STAGES] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    } bispectrum;
 
     ProcessBuffer<unsigned long long> counters;   // [COUNTER_FIELDS * COUNTER_SLOTS]: gamma cells, evaluated cells, exact zeros left out, spread over the slots
     long long last_gamma_cells = 0, last_eval_cells = 0;
@@ -688,5 +702,9 @@ int ps_forward(State &st, int kind, double scale, double t_gamma, const std::fun
 int ps_mean_density(State &st, const double **nbar_dev);
 int ps_transform(State &st, int kind, const double *x, bool nbar, double scale, double t_gamma, double *field,
                  const std::function<int()> &stage_done, const double **moments_dev);
+// the binning of asora_power_spectrum's auto-spectrum for what lies in State::spectrum.modes[0] (bispectrum.hip): the same two launches,
+// so count, sum_k and sum_aa are its bits; *count_dev, *sum_k_dev, *sum_aa_dev: where the n_bins values of each lie on the device
+int ps_bin_auto(State &st, int n_bins, const unsigned *thresholds, const unsigned long long **count_dev, const double **sum_k_dev,
+                const double **sum_aa_dev);
 
 } // namespace asora

@@ -397,6 +397,32 @@ int ps_transform(State &st, int kind, const double *x, bool nbar, double scale, 
     return 0;
 }
 
+// Stage d for the auto-spectrum of what ps_forward left in st.spectrum.modes[0], for asora_bispectrum (bispectrum.hip): the thresholds
+// leave through the pinned area as in asora_power_spectrum, and the two launches are its launches
+int ps_bin_auto(State &st, int n_bins, const unsigned *thresholds, const unsigned long long **count_dev, const double **sum_k_dev,
+                const double **sum_aa_dev)
+{
+    PsPasses pass(st);
+    if (int rc = pass.prepare(false)) return rc;
+    const int N = st.N;
+    const size_t bin_lds = (size_t)PS_WAVES * PS_VALUES * n_bins * sizeof(double) + sizeof(unsigned) * (n_bins + 1);
+    unsigned *thr_host = (unsigned *)(st.spectrum.host + PS_RES_WORDS);
+    std::memcpy(thr_host, thresholds, sizeof(unsigned) * (n_bins + 1));
+    ASORA_HIP_TRY(hipMemcpyAsync(st.spectrum.thresholds, thr_host, sizeof(unsigned) * (n_bins + 1), hipMemcpyHostToDevice, st.stream));
+    double *part = pass.partial(), *res = pass.result();
+    const int nv = PS_SUM_AA + 1;
+    hipLaunchKernelGGL(ps_bin_kernel<false>, dim3((unsigned)N), pass.block, bin_lds, st.stream, (const double2 *)st.spectrum.modes[0],
+                       (const double2 *)nullptr, N, n_bins, (const unsigned *)st.spectrum.thresholds, part + pass.lay.bins);
+    ASORA_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ps_bin_final_kernel, dim3((unsigned)((nv * n_bins + PS_THREADS - 1) / PS_THREADS)), pass.block, 0, st.stream,
+                       (const double *)(part + pass.lay.bins), N, n_bins, nv, res);
+    ASORA_HIP_TRY(hipGetLastError());
+    *count_dev = (const unsigned long long *)(res + PS_COUNT * ASORA_BUBBLE_MAX_BINS);
+    *sum_k_dev = res + PS_SUM_K * ASORA_BUBBLE_MAX_BINS;
+    *sum_aa_dev = res + PS_SUM_AA * ASORA_BUBBLE_MAX_BINS;
+    return 0;
+}
+
 } // namespace asora
 
 using namespace asora;

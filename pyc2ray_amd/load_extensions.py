@@ -729,6 +729,44 @@ class _LibAsora:
         _capi.check(self._lib.asora_debug_lya_forest_tiles(int(N), int(los_axis), _capi.iptr(t)), "debug_lya_forest_tiles")
         return dict(lines=int(t[0]), work_items=int(t[1]), workgroups=int(t[2]), lds_bytes=int(t[3]))
 
+    def bispectrum(self, kind, scale, t_gamma, thresholds, triangles):
+        """The triangle sums of the field of kind `kind` (``_capi.PS_*``) formed from the device grids, for the shells of the integer
+        `thresholds` on n^2 and the `triangles`, (n_tri, 3) shell indices (include/asora_hip.h, asora_bispectrum): a dict of
+        ``sum_ggg`` and ``sum_iii`` (float64, one per triangle), ``count`` (uint64), ``sum_k``, ``sum_aa`` (one per shell) and
+        ``moments`` = (sum g, sum g^2)."""
+        thr = np.ascontiguousarray(thresholds, dtype=np.uint32)
+        if thr.ndim != 1:
+            raise ValueError("bispectrum: thresholds must be one-dimensional")
+        tri = np.ascontiguousarray(triangles, dtype=np.int32)
+        if tri.ndim != 2 or tri.shape[1] != 3:
+            raise ValueError("bispectrum: triangles must have the shape (n_tri, 3)")
+        ns, nt = max(thr.size - 1, 1), max(tri.shape[0], 1)
+        out = dict(sum_ggg=np.zeros(nt), sum_iii=np.zeros(nt), count=np.zeros(ns, dtype=np.uint64), sum_k=np.zeros(ns), sum_aa=np.zeros(ns),
+                   moments=np.zeros(2))
+        _capi.check(self._lib.asora_bispectrum(int(kind), float(scale), float(t_gamma), int(thr.size) - 1,
+                                               thr.ctypes.data_as(C.POINTER(C.c_uint32)), int(tri.shape[0]), _capi.iptr(tri),
+                                               _capi.dptr(out["sum_ggg"]), _capi.dptr(out["sum_iii"]), out["count"].ctypes.data_as(_capi._u64p),
+                                               _capi.dptr(out["sum_k"]), _capi.dptr(out["sum_aa"]), _capi.dptr(out["moments"])), "bispectrum")
+        return out
+
+    def bispectrum_ms(self):
+        """The stage times (ms) of the last bispectrum call that ran with OPT_TIMING: mean density, forward along k, j, i, the
+        per-shell binning, the shell fields and the products of the field, the shell fields and the products of the counts (0, 0
+        when the kept counts were returned) (include/asora_hip.h, asora_debug_bispectrum_ms)."""
+        ms = np.zeros(_capi.BISPEC_STAGES)
+        _capi.check(self._lib.asora_debug_bispectrum_ms(_capi.dptr(ms)), "debug_bispectrum_ms")
+        return ms
+
+    def bispectrum_plan(self, N, n_shells, n_tri):
+        """How bispectrum's product stage deals `n_tri` triangles and the cells of a mesh of N a side: a dict of ``chunk`` (the
+        triangles of one pass over the cubes), ``passes``, ``workgroups``, ``trips_max`` and ``trips_min`` (the tiles a workgroup
+        takes), ``wave_chunk``, ``tile_cells`` and ``idle_workgroups`` (include/asora_hip.h, asora_debug_bispectrum_plan); needs no
+        device."""
+        t = np.zeros(_capi.BISPEC_PLAN_WORDS, dtype=np.int32)
+        _capi.check(self._lib.asora_debug_bispectrum_plan(int(N), int(n_shells), int(n_tri), _capi.iptr(t)), "debug_bispectrum_plan")
+        return dict(zip(("chunk", "passes", "workgroups", "trips_max", "trips_min", "wave_chunk", "tile_cells", "idle_workgroups"),
+                        (int(v) for v in t)))
+
     def thermal_stats(self):
         """(cells that hit max_substeps, cells clamped to t_floor, most substeps of one integration) since the last
         chemistry_device / evolve_begin."""
