@@ -882,6 +882,55 @@ int asora_debug_bispectrum_ms(double *ms /* [ASORA_BISPEC_STAGES] */);
 enum { ASORA_BISPEC_PLAN_WORDS = 8 };
 int asora_debug_bispectrum_plan(int N, int n_shells, int n_tri, int32_t *out /* [ASORA_BISPEC_PLAN_WORDS] */);
 
+/* Slices of a light cone, emitted while a run advances: along the line of sight the box is seen at another
+ * redshift in every plane, so a slice of the cone is a plane of the box interpolated between two consecutive states of the run.  The
+ * library knows nothing of cosmology: per slot it keeps one formed field from the previous call, g_prev, and blends planes of it
+ * with planes of the field formed from the present grids, g_now.  No grid is written.  The specification, which no implementation
+ * detail enters:
+ *   slot       : 0 ... ASORA_LC_SLOTS - 1, each with a kept field of its own; slots do not see each other;
+ *   field      : g_now(c), per cell c.  With src_grid = -1 it is the field of asora_power_spectrum for `kind` (ASORA_PS_*) with
+ *                scale = 1: the same order of operations, the same mean density, so the bits that asora_power_spectrum(kind, -1,
+ *                1.0, t_gamma, ..., field_out) returns.  With src_grid a grid selector (and kind = 0) it is that grid's cell
+ *                verbatim: a cube that asora_redshift_space_field, asora_smooth_field or asora_lyman_alpha_forest left in a grid
+ *                enters a cone this way;
+ *   slice t    : t = 0 ... n_slices - 1, n_slices in [0, ASORA_LC_MAX_SLICES].  p = plane[t] in [0, N) is taken along los_axis (0, 1
+ *                or 2); planes may come in any order and may repeat (a cone longer than the box wraps).  With (a, b) the indices on
+ *                the two remaining axes, in ascending order of the axes, and cell the cell with p on los_axis and (a, b) on those,
+ *                  out[t][a][b] = (w_prev[t] g_prev(cell)) + (w_now[t] g_now(cell)):
+ *                two products, each rounded, and one sum, nothing contracted into a fused multiply-add.  The weights (0, 1) and
+ *                (1, 0) therefore return a field's plane exactly (but for the sign of a zero);
+ *   moments    : moments[2 t] = the sum of out over slice t, moments[2 t + 1] = the sum of out^2 (each square rounded), formed in
+ *                double-double in an order that depends on N only, no floating-point atomic: two calls return the same bits.  A
+ *                sum whose terms overflow is not finite (an infinity or a NaN);
+ *   refresh    : 1: after the slices are emitted (stream order) g_prev <- g_now for all N^3 cells, and the slot remembers kind and
+ *                src_grid; 0: g_prev is left alone, so that a caller may split one step over several calls and refresh on the last;
+ *   first call : a slot without a kept field (never used, forgotten by asora_lightcone_reset, or after asora_device_close) takes
+ *                n_slices = 0 and refresh = 1 only: that call allocates the slot's N^3 doubles and stores the field.
+ * slices_out [n_slices N N] or NULL: the slices in C order (NULL: only the moments cross to the host, as on the ranks of a
+ * multi-rank run that keep no slices).  One synchronisation per call.  Device memory: N^3 doubles per slot in use (134 MB at
+ * 256^3), n_slices N^2 doubles of staging for the largest call so far, 0.6 MB of parameters and partial sums, and for
+ * ASORA_PS_DENSITY and ASORA_PS_HI the buffers of asora_power_spectrum, whose mean-density launches are used; kept until the device
+ * is closed.
+ * Fails with code 2 before device_init; 3 for: a slot, kind, src_grid or los_axis out of range, a kind other than 0 with a
+ * src_grid, a non-finite or negative t_gamma, n_slices outside [0, ASORA_LC_MAX_SLICES], a refresh other than 0 or 1, with
+ * n_slices > 0 a NULL plane, w_prev, w_now or moments, a plane outside [0, N) or a non-finite weight, a call other than the first
+ * call above on a slot without a kept field, a kind or src_grid other than the ones the slot's kept field was made with; 4 for a
+ * grid the field needs that holds no data (as asora_power_spectrum needs them; src_grid itself) and for a mesh with
+ * N > ASORA_REGION_MAX_N; 10 for a failed allocation.  A refused call writes nothing and leaves g_prev as it was. */
+enum { ASORA_LC_SLOTS = 4, ASORA_LC_MAX_SLICES = 1024, ASORA_LC_STAGES = 4 };
+int asora_lightcone_advance(int slot, int kind, int src_grid, double t_gamma, int los_axis,
+                            int n_slices, const int32_t *plane, const double *w_prev, const double *w_now,
+                            int refresh, double *slices_out /* NULL, or host [n_slices N N] */,
+                            double *moments /* NULL if n_slices == 0, else [2 n_slices] */);
+/* What a slot keeps: *has_prev 1 or 0, and with 1 the *kind and *src_grid its field was made with (else 0 and -1).  A host
+ * computation, callable without a device.  Code 3 for a bad slot or a null pointer. */
+int asora_lightcone_state(int slot, int *has_prev, int *kind, int *src_grid);
+/* Forgets the slot's kept field; its memory stays until asora_device_close.  Code 3 for a bad slot. */
+int asora_lightcone_reset(int slot);
+/* The durations (ms) of the stages of the last asora_lightcone_advance call that ran with ASORA_OPT_TIMING = 1: ms[0] the mean
+ * density, [1] the emitting of the slices, [2] their moments, [3] the refresh; zeros if no such call has run.  Code 3 for ms = NULL. */
+int asora_debug_lightcone_ms(double *ms /* [ASORA_LC_STAGES] */);
+
 /* ------------------------------------------------------------------------------------------ */
 /* C. Options, measurement and diagnostics                                                     */
 /* ------------------------------------------------------------------------------------------ */

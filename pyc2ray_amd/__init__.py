@@ -17,10 +17,11 @@ from .powerspec import *       # noqa: F401,F403  PowerSpectrum, power_spectrum
 from .smoothing import *       # noqa: F401,F403  SmoothedField, smoothed_field, Filter and the filter builders
 from .redshift_space import *  # noqa: F401,F403  AnisotropicSpectrum, power_spectrum_los, redshift_space_field
 from .lyman_alpha import *     # noqa: F401,F403  LymanAlphaForest, lyman_alpha_forest
+from .lightcone import *       # noqa: F401,F403  LightCone, LightConeStep, make_lightcone, slice_redshifts
 from .c2ray_base import *      # noqa: F401,F403
 from .c2ray_test import *      # noqa: F401,F403
 from . import evolve, raytracing, chemistry, asora_core, utils, dist, bubbles, regions, powerspec, smoothing, redshift_space   # noqa: F401
-from . import lyman_alpha      # noqa: F401
+from . import lyman_alpha, lightcone      # noqa: F401
 # (last, so that the package's `topology`, `granulometry` and `bispectrum` are the functions, not the modules of those names:
 # importlib.import_module finds the modules)
 from .topology import *        # noqa: F401,F403,E402  Topology, topology

@@ -71,6 +71,9 @@ BISPEC_MAX_SHELLS = 32
 BISPEC_MAX_TRIANGLES = 8192
 BISPEC_STAGES = 9
 BISPEC_PLAN_WORDS = 8
+LC_SLOTS = 4
+LC_MAX_SLICES = 1024
+LC_STAGES = 4
 (PRIM_LOG2, PRIM_LOOKUP, PRIM_DIV, PRIM_MUL, PRIM_ADD, PRIM_ABSORBER, PRIM_PHOTO, PRIM_HEAT, PRIM_GREY) = range(9)
 PRIM_COUNT = 9
 
@@ -185,6 +188,10 @@ SIGNATURES = {
                                    _dp]),
     "asora_debug_bispectrum_ms": (C.c_int, [_dp]),
     "asora_debug_bispectrum_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip]),
+    "asora_lightcone_advance": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, _ip, _dp, _dp, C.c_int, _dp, _dp]),
+    "asora_lightcone_state": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "asora_lightcone_reset": (C.c_int, [C.c_int]),
+    "asora_debug_lightcone_ms": (C.c_int, [_dp]),
     "asora_set_option": (C.c_int, [C.c_int, C.c_int]),
     "asora_get_option": (C.c_int, [C.c_int]),
     "asora_kernel_time_ms": (C.c_int, [C.c_int, _dp, C.POINTER(C.c_long)]),

@@ -74,6 +74,11 @@ Differences from the reference:
     on the device-resident path from the grids where they lie).  ``Output: lyman_alpha: 0|1`` (optional key, default 0; with
     ``lyman_alpha_gap_threshold``, ``lyman_alpha_bins``) and the attribute ``lyman_alpha_stats`` (a bool, assignable between steps)
     do that after every time step (use_gpu only): ``last_lyman_alpha`` and one line in the log.
+  * ``Output: lightcone: 0|1`` (optional key, default 0; with ``lightcone_kind``, ``lightcone_los_axis``, ``lightcone_first_plane``,
+    ``lightcone_spin``, ``lightcone_z_end``) and the attribute ``lightcone_stats`` (a bool, assignable between steps) build the light
+    cone of the run while it advances (pyc2ray_amd/lightcone.py; use_gpu and cosmological runs only): every step adds the slices
+    whose redshift it crossed, interpolated between the previous state and its own on the device, to ``lightcone``;
+    ``last_lightcone_step`` and one line in the log.  ``brightness_temperature_scale(z)`` takes a redshift.
 """
 import atexit
 import math
@@ -100,6 +105,7 @@ from .smoothing import smoothing_spec, smoothing_on_device, telescope
 from .redshift_space import redshift_space_spec, spectrum_on_device, field_on_device
 from .lyman_alpha import lyman_alpha_spec, forest_on_device
 from .bispectrum import bispectrum_spec, bispectrum_on_device
+from .lightcone import LightCone, lightcone_spec
 from .budget import StepBudget
 from .lls import LLSOpacity, LLSSchedule, lls_spec
 from .planeflux import PlaneFlux, plane_flux_spec
@@ -268,6 +274,22 @@ class _StepStatistic:
         return obj.__dict__.get(self.attr + "_defaults", {})
 
 
+class _LightConeStatistic(_StepStatistic):
+    """The switch of the light cone: on only where a redshift passes; switching it on begins a new cone -- the first step
+    afterwards keeps its field and emits nothing."""
+
+    def set(self, obj, value, who):
+        was = obj.__dict__.get(self.attr, False)
+        super().set(obj, value, who)
+        if value and not getattr(obj, "cosmological", False):
+            obj.__dict__[self.attr] = False
+            raise ValueError(f"{who}: {self.name} needs a cosmological run (Cosmology: cosmological: 1): no redshift passes without")
+        obj.__dict__.setdefault("lightcone", None)
+        if value and not was:                                  # (switched off, the cone stays where a driver can take it)
+            obj.__dict__["lightcone"] = None
+            obj.__dict__["_lightcone_z_prev"] = None
+
+
 class C2Ray:
     #: Default since round 6 (single GPU, use_gpu=True; set False on an instance for the reference's behaviour: every step uploads
     #: and downloads everything): ndens, temp, xh and phi_ion stay on the device between time steps.  evolve3D then uploads only
@@ -377,11 +399,32 @@ class C2Ray:
     _STEP_STATISTICS_APPENDED = ("redshift_space_stats",)
     #: ... and those declared since then, behind both (the two tuples above keep the contents their tests pin)
     _STEP_STATISTICS_FURTHER = ("lyman_alpha_stats",)
+    # lightcone_kind: 'dtb' (default), 'hi', 'xh', 'xhi' or 'density'; lightcone_los_axis: 0, 1 or 2, default the object's
+    # ``los_axis``; lightcone_first_plane: an int in [0, N), default 0; lightcone_spin: None (default) or 'kinetic';
+    # lightcone_z_end: the redshift below which no slice is emitted, default none
+    lightcone_stats = _LightConeStatistic(
+        "lightcone", "last_lightcone_step", "_lightcone_step", "the slices are formed and blended on the device",
+        """Does every time step add the slices it crossed to the light cone of the run (pyc2ray_amd.lightcone.LightCone with the
+        ``Output: lightcone_*`` keys; use_gpu=True and a cosmological run only: elsewhere True is refused at the assignment)?  A
+        driver may assign a bool between steps; switching on begins a new cone, whose first step keeps its field and emits
+        nothing.  ``lightcone`` is the cone (it stays after switching off); after a step ``last_lightcone_step`` holds what the
+        step emitted and rank 0 writes one line to the log.""",
+        keys=(("lightcone_kind", "kind"), ("lightcone_los_axis", "los_axis"), ("lightcone_first_plane", "first_plane"),
+              ("lightcone_spin", "spin"), ("lightcone_z_end", "z_end")),
+        validate=lambda sim, kw: lightcone_spec("Output: lightcone_kind / lightcone_los_axis / lightcone_first_plane / lightcone_spin / "
+                                                "lightcone_z_end", sim.N, **{"kind": "dtb", **kw}))
+    #: what closes a step without being a statistic of its state: the light cone, which accumulates over the steps
+    _STEP_ACCUMULATORS = ("lightcone_stats",)
 
     @classmethod
     def _step_statistics(cls):
-        """Every declared statistic, in the order in which __init__ reads their keys and a step computes and logs them."""
+        """Every declared statistic of a state, in the order in which __init__ reads their keys and a step computes and logs them."""
         return cls._STEP_STATISTICS + cls._STEP_STATISTICS_APPENDED + cls._STEP_STATISTICS_FURTHER
+
+    @classmethod
+    def _step_closers(cls):
+        """Everything the mechanism of _statistic_init and _close_step serves: the statistics, then the accumulators."""
+        return cls._step_statistics() + cls._STEP_ACCUMULATORS
 
     def __init__(self, paramfile, Nmesh, use_gpu, use_mpi):
         """Basis class of a C2Ray simulation (pyc2ray/c2ray_base.py:82-145).
@@ -429,7 +472,7 @@ class C2Ray:
         self._lls_init()
         self._boundaries_init()
         self._plane_flux_init()
-        for name in self._step_statistics():
+        for name in self._step_closers():
             self._statistic_init(name)
         if self.rank == 0:
             if self.gpu:
@@ -613,7 +656,7 @@ class C2Ray:
             self.total_budget = self.__dict__.get("total_budget", StepBudget()) + budget
             if self.rank == 0:
                 self.printlog(budget.log_line())
-        for name in self._step_statistics():
+        for name in self._step_closers():
             stat = getattr(type(self), name)
             if stat.method is not None and getattr(self, name):
                 result = getattr(self, stat.method)()
@@ -670,12 +713,13 @@ class C2Ray:
         return self._analyse_xh("granulometry", C2Ray.granulometry_stats.defaults(self), kw, granulometry_spec, granulometry_on_device,
                                 field_granulometry)
 
-    def brightness_temperature_scale(self):
-        """The prefactor of the 21-cm differential brightness temperature at ``self.zred`` in mK, from the object's own cosmology:
-        27 sqrt((1 + z) / 10  0.15 / (Omega_m h^2)) (Omega_b h^2 / 0.023)."""
+    def brightness_temperature_scale(self, z=None):
+        """The prefactor of the 21-cm differential brightness temperature at redshift `z` (None: ``self.zred``) in mK, from the
+        object's own cosmology: 27 sqrt((1 + z) / 10  0.15 / (Omega_m h^2)) (Omega_b h^2 / 0.023)."""
         cs = self._ld['Cosmology']
         h2 = float(cs['h']) ** 2
-        return 27.0 * math.sqrt((1.0 + float(self.zred)) / 10.0 * 0.15 / (float(cs['Omega0']) * h2)) * (float(cs['Omega_B']) * h2 / 0.023)
+        z = float(self.zred) if z is None else float(z)
+        return 27.0 * math.sqrt((1.0 + z) / 10.0 * 0.15 / (float(cs['Omega0']) * h2)) * (float(cs['Omega_B']) * h2 / 0.023)
 
     def _spin_t_gamma(self, who, kw):
         """``spin`` leaves the keywords `kw` of a transform analysis: 'kinetic' puts ``t_gamma``, the CMB temperature at
@@ -809,6 +853,8 @@ class C2Ray:
     def los_axis(self, value):
         if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or value not in (0, 1, 2):
             raise ValueError(f"C2Ray.los_axis: los_axis must be 0, 1 or 2, not {value!r}")
+        if self.lightcone_stats and self.__dict__.get("lightcone") is not None:
+            raise ValueError("C2Ray.los_axis: a light cone is open along the present axis (lightcone_stats = False ends it)")
         self.__dict__["_los_axis"] = int(value)
 
     @property
@@ -934,6 +980,28 @@ class C2Ray:
         lib = self._state_on_device(overwritten=spec["into"] is not None)
         self._los_velocity_on_device(lib)
         return forest_on_device(lib, spec)
+
+    # ---- the light cone (pyc2ray_amd/lightcone.py) ------------------------------------------------------
+    def _lightcone_step(self):
+        """What ``lightcone_stats`` does after a step: the slices between the previous state's redshift and this one's join
+        ``self.lightcone``; a :class:`pyc2ray_amd.lightcone.LightConeStep`.  The redshift of the state a step leaves is that of
+        ``self.time``: ``zred`` stays at the half step (cosmo_evolve).  The first step after switching on makes the cone -- slices a
+        comoving cell apart from that state's redshift down, ``los_axis`` the object's unless ``Output: lightcone_los_axis`` sets it
+        -- and keeps the field.  For 'dtb' a slice carries :meth:`brightness_temperature_scale` at its own redshift; with
+        ``lightcone_spin: kinetic`` ``t_gamma`` is the CMB temperature at the state's.  The grids are used where they lie, as in
+        :meth:`power_spectrum`; across ranks every rank advances its own slot and rank 0 alone keeps slices."""
+        d = {"kind": "dtb", "first_plane": 0, "spin": None, "z_end": None, **C2Ray.lightcone_stats.defaults(self)}
+        z_now = float(self.time2zred(self.time))
+        cone = self.__dict__.get("lightcone")
+        if cone is None:
+            cone = LightCone(self.N, self.cosmology, z_now, self.boxsize_c / Mpc / self.N, kind=d["kind"], los_axis=d.get("los_axis", self.los_axis),
+                             first_plane=d["first_plane"], z_end=d["z_end"], keep=self.rank == 0)
+            self.__dict__["lightcone"] = cone
+        t_gamma = float(self._ld['Cosmology']['cmbtemp']) * (1.0 + z_now) if d["spin"] == "kinetic" else 0.0
+        scale = self.brightness_temperature_scale if cone.kind == "dtb" else None
+        step = cone.advance(self._state_on_device(), self.__dict__.get("_lightcone_z_prev"), z_now, scale=scale, t_gamma=t_gamma)
+        self.__dict__["_lightcone_z_prev"] = z_now
+        return step
 
     def evolve3D(self, dt, src_flux, src_pos, src_spectrum=None):
         """Evolve the grid over one time step (c2ray_base.py:170-226).  src_spectrum: with ``BlackBodySource: Teff`` a list, the

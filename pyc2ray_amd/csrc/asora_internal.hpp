@@ -372,6 +372,17 @@ struct State {
         struct Cache { int N = 0; std::vector<unsigned> thresholds; std::vector<int32_t> tri; std::vector<double> sum_iii; } cache;
         double ms[ASORA_BISPEC_STAGES] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     } bispectrum;
+    // the light cone's own buffers (asora_lightcone_advance, lightcone.hip), allocated by the first call that needs them: per slot
+    // the formed field of the previous call [N^3]; the slices of a call [n_slices][N^2], grown on demand; the weights, planes, slice
+    // list and runs of a call with the moments behind them, on the device and in the pinned area they cross through; the moments'
+    // partials.  kept: what a slot's field was made with -- it counts only while the slot's buffer is there, so it needs no reset
+    // when the mesh goes.  ms: the stage times of the last call under ASORA_OPT_TIMING
+    struct Lightcone {
+        MeshBuffer<double> prev[ASORA_LC_SLOTS], stage, params, partial;
+        MeshPinned<double> host;
+        struct Kept { bool has = false; int kind = 0, src_grid = -1; } kept[ASORA_LC_SLOTS];
+        double ms[ASORA_LC_STAGES] = {0, 0, 0, 0};
+    } lightcone;
 
     ProcessBuffer<unsigned long long> counters;   // [COUNTER_FIELDS * COUNTER_SLOTS]: gamma cells, evaluated cells, exact zeros left out, spread over the slots
     long long last_gamma_cells = 0, last_eval_cells = 0;

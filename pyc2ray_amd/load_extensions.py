@@ -767,6 +767,46 @@ class _LibAsora:
         return dict(zip(("chunk", "passes", "workgroups", "trips_max", "trips_min", "wave_chunk", "tile_cells", "idle_workgroups"),
                         (int(v) for v in t)))
 
+    def lightcone_advance(self, slot, kind, src_grid, t_gamma, los_axis, planes, w_prev, w_now, refresh, slices=True):
+        """Slices of a light cone for `slot`: plane ``planes[t]`` along `los_axis` of the slot's kept field times ``w_prev[t]`` plus
+        the same plane of the field formed from the device grids now times ``w_now[t]`` -- the field of kind `kind` (``_capi.PS_*``),
+        or with `src_grid` (a ``_capi.GRID_*`` selector; None: none) that grid verbatim -- and with `refresh` the present field kept
+        for the next call (include/asora_hip.h, asora_lightcone_advance): a dict of ``slices`` ((n, N, N) float64; None with
+        ``slices=False``, when only the moments cross to the host) and ``moments`` ((n, 2): the sum and the sum of squares of each
+        slice)."""
+        if self._N is None:
+            raise RuntimeError("lightcone_advance needs a device initialised through device_init (the mesh size)")
+        p = np.ascontiguousarray(planes, dtype=np.int32)
+        wp, wn = np.ascontiguousarray(w_prev, dtype=np.float64), np.ascontiguousarray(w_now, dtype=np.float64)
+        if p.ndim != 1 or wp.shape != p.shape or wn.shape != p.shape:
+            raise ValueError("lightcone_advance: planes, w_prev and w_now must be one-dimensional and of one length")
+        n = int(p.size)
+        out = dict(slices=np.zeros((n, self._N, self._N)) if slices else None, moments=np.zeros((n, 2)))
+        some = n > 0
+        _capi.check(self._lib.asora_lightcone_advance(int(slot), int(kind), -1 if src_grid is None else int(src_grid), float(t_gamma),
+                                                      int(los_axis), n, _capi.iptr(p) if some else None, _capi.dptr(wp) if some else None,
+                                                      _capi.dptr(wn) if some else None, 1 if refresh else 0,
+                                                      _capi.dptr(out["slices"]) if slices and some else None,
+                                                      _capi.dptr(out["moments"]) if some else None), "lightcone_advance")
+        return out
+
+    def lightcone_state(self, slot):
+        """What `slot` keeps: a dict of ``has_prev`` (bool), ``kind`` and ``src_grid`` (None: none) of its kept field
+        (include/asora_hip.h, asora_lightcone_state)."""
+        has, kind, src = C.c_int(0), C.c_int(0), C.c_int(-1)
+        _capi.check(self._lib.asora_lightcone_state(int(slot), C.byref(has), C.byref(kind), C.byref(src)), "lightcone_state")
+        return dict(has_prev=bool(has.value), kind=int(kind.value), src_grid=None if src.value < 0 else int(src.value))
+
+    def lightcone_reset(self, slot):
+        _capi.check(self._lib.asora_lightcone_reset(int(slot)), "lightcone_reset")
+
+    def lightcone_ms(self):
+        """The stage times (ms) of the last lightcone_advance call that ran with OPT_TIMING: mean density, emit, moments, refresh
+        (include/asora_hip.h, asora_debug_lightcone_ms)."""
+        ms = np.zeros(_capi.LC_STAGES)
+        _capi.check(self._lib.asora_debug_lightcone_ms(_capi.dptr(ms)), "debug_lightcone_ms")
+        return ms
+
     def thermal_stats(self):
         """(cells that hit max_substeps, cells clamped to t_floor, most substeps of one integration) since the last
         chemistry_device / evolve_begin."""
