@@ -931,6 +931,61 @@ int asora_lightcone_reset(int slot);
  * density, [1] the emitting of the slices, [2] their moments, [3] the refresh; zeros if no such call has run.  Code 3 for ms = NULL. */
 int asora_debug_lightcone_ms(double *ms /* [ASORA_LC_STAGES] */);
 
+/* The sources of a time step from a halo catalogue, the low-mass haloes suppressed where the gas is ionised (DESIGN.md section 4.1e;
+ * Iliev et al. 2007, 2012; Dixon et al. 2016): a catalogue is uploaded once and binned into a table of its occupied cells; every
+ * step forms its source list from that table and a device grid (the ionised fraction).  The library knows nothing of cosmology or
+ * of photon budgets: the efficiencies g_hm, g_lm and `scale` are the caller's.  No grid is written.  The specification, which no
+ * implementation detail enters:
+ *   catalogue  : n haloes.  pos [n][3] in cell units, cell c covering [c, c + 1), 0-based; mass [n]; weight [n] >= 0 and finite.
+ *                The weight is what is summed, the mass only classifies;
+ *   cell       : a halo with a coordinate p that is not finite or has |p| >= 2^31 is dropped and counted in `nonfinite`.  Else
+ *                c_a = (int64)floor(p_a) per axis; wrap = 1: c_a <- c_a mod N with the sign of N (Python's %); wrap = 0: a halo
+ *                with a c_a outside [0, N) is dropped and counted in `outside`;
+ *   population : of the haloes that have a cell, HM if mass >= m_hm, LM if m_lm <= mass < m_hm, else dropped and counted in `below`
+ *                (a NaN mass: both comparisons are false).  A halo is counted in the first of the three it meets, in this order;
+ *   fixed point: unit = 2^unit_exponent; q = (uint64)rint(weight / unit), the division exact, the rounding to nearest even.  Per
+ *                cell Q_hm = sum of q over its HM haloes, Q_lm over its LM ones: integers, so any order gives the same sums.  A cell's
+ *                sum differs from the exact one by at most (haloes in the cell) unit / 2;
+ *   table      : the cells with Q_hm + Q_lm > 0 in ascending i N^2 + j N + k, each with (cell, Q_hm, Q_lm);
+ *   build      : per table row x = grid[cell] of which_grid; suppressed = model != NONE and x > x_suppress (strict; false for a NaN);
+ *                s = 1 unless suppressed, then 0 (FULL) or f_suppressed (PARTIAL);
+ *                  flux = (g_hm double(Q_hm) + (g_lm s) double(Q_lm)) scale:
+ *                the conversions round to nearest even, then three products, each rounded, their sum, rounded, and the product with
+ *                scale, rounded; nothing is contracted into a fused multiply-add.  A row is active when flux > 0;
+ *   list       : the active rows in table order -- the (x, y, z)-lexicographic order asora_source_data_to_device sorts into --
+ *                pos [n_active][3] int32 (0-based i, j, k) and flux [n_active];
+ *   summary    : [0] n_active, [1] n_suppressed = the suppressed rows with Q_lm > 0, [2] sum Q_hm over all rows, [3] sum Q_lm over the
+ *                rows that are not suppressed, [4] sum Q_lm over the suppressed ones; exact integers (times unit: weights).
+ * The device's table, list and summary equal the numpy statement's (tests/halo_sources_reference.py) bit for bit; a permuted
+ * catalogue and a repeated call give the same bits; no floating-point atomic enters.
+ * asora_halo_catalogue_to_device replaces the catalogue the device holds: counts_out = n_cells, outside, nonfinite, below.  Device
+ * memory while it runs: 40 n bytes of catalogue and 16 N^3 of sums (268 MB at 256^3), released before it returns; kept until the
+ * next catalogue, asora_halo_catalogue_clear or asora_device_close: 52 bytes per occupied cell.  Three synchronisations.
+ * asora_halo_sources_build: one synchronisation, the summary crosses; asora_halo_sources_to_host: the list of the last build, 20
+ * n_active bytes; asora_halo_table_to_host: the table (tests); asora_halo_catalogue_state: *n_cells of the catalogue held, -1
+ * without one, its *unit_exponent and its *generation -- every catalogue that goes up in the process takes the next number, from
+ * 1, so a caller can tell whether the table on the device is still the one it uploaded; 0 without a catalogue (host bookkeeping,
+ * callable without a device).  asora_halo_catalogue_clear releases everything the feature holds on the device.
+ * Fail with code 2 before device_init; 3 for: n < 0, a null pointer, a NaN threshold or m_lm > m_hm, a wrap other than 0 or 1, a
+ * negative or non-finite weight, a unit_exponent outside [-1000, 1000] or one with which sum weight / unit + n / 2 >= 2^62 (a cell's
+ * sum could overflow), no catalogue on the device, a model or which_grid out of range, g_hm, g_lm or scale negative or not finite, a
+ * NaN x_suppress, an f_suppressed outside [0, 1], a to_host before a build or with too small a capacity; 4 for a grid without
+ * data; 10 for a failed allocation.  A catalogue refused for its arguments leaves the one on the device as it was; a call that
+ * fails later leaves the device without one. */
+enum { ASORA_HALO_MODEL_NONE = 0, ASORA_HALO_MODEL_FULL = 1, ASORA_HALO_MODEL_PARTIAL = 2, ASORA_HALO_STAGES = 8, ASORA_HALO_SUMMARY = 5 };
+int asora_halo_catalogue_to_device(const double *pos /* [n][3] */, const double *mass, const double *weight, long long n,
+                                   double m_lm, double m_hm, int wrap, int unit_exponent, long long *counts_out /* [4] */);
+int asora_halo_catalogue_clear(void);
+int asora_halo_catalogue_state(long long *n_cells, int *unit_exponent, long long *generation);
+int asora_halo_table_to_host(int64_t *cell, uint64_t *q_hm, uint64_t *q_lm, long long capacity);
+int asora_halo_sources_build(int which_grid, double g_hm, double g_lm, double scale, int model, double x_suppress, double f_suppressed,
+                             unsigned long long *summary_out /* [ASORA_HALO_SUMMARY] */, long long *n_active);
+int asora_halo_sources_to_host(int32_t *pos /* [capacity][3] */, double *flux, long long capacity);
+/* The durations (ms) of the stages of the last catalogue call ([0] zeroing and upload, [1] bin, [2] row counts and scan, [3] the
+ * download of n_cells, its synchronisation and the allocations sized by it, [4] table) and of the last build ([5] flux, [6] scan,
+ * [7] emit) that ran with ASORA_OPT_TIMING = 1; zeros if none has.  Code 3 for NULL. */
+int asora_debug_halo_sources_ms(double *ms /* [ASORA_HALO_STAGES] */);
+
 /* ------------------------------------------------------------------------------------------ */
 /* C. Options, measurement and diagnostics                                                     */
 /* ------------------------------------------------------------------------------------------ */

@@ -22,8 +22,9 @@ from .c2ray_base import *      # noqa: F401,F403
 from .c2ray_test import *      # noqa: F401,F403
 from . import evolve, raytracing, chemistry, asora_core, utils, dist, bubbles, regions, powerspec, smoothing, redshift_space   # noqa: F401
 from . import lyman_alpha, lightcone      # noqa: F401
-# (last, so that the package's `topology`, `granulometry` and `bispectrum` are the functions, not the modules of those names:
-# importlib.import_module finds the modules)
+# (last, so that the package's `topology`, `granulometry`, `bispectrum` and `halo_sources` are the functions, not the modules of
+# those names: importlib.import_module finds the modules)
 from .topology import *        # noqa: F401,F403,E402  Topology, topology
 from .granulometry import *    # noqa: F401,F403,E402  Granulometry, granulometry
 from .bispectrum import *      # noqa: F401,F403,E402  Bispectrum, bispectrum
+from .halo_sources import *    # noqa: F401,F403,E402  HaloCatalogue, SourceModel, HaloSourceList, halo_sources, source_scale

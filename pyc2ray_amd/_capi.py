@@ -74,6 +74,9 @@ BISPEC_PLAN_WORDS = 8
 LC_SLOTS = 4
 LC_MAX_SLICES = 1024
 LC_STAGES = 4
+HALO_MODEL_NONE, HALO_MODEL_FULL, HALO_MODEL_PARTIAL = range(3)
+HALO_STAGES = 8
+HALO_SUMMARY = 5
 (PRIM_LOG2, PRIM_LOOKUP, PRIM_DIV, PRIM_MUL, PRIM_ADD, PRIM_ABSORBER, PRIM_PHOTO, PRIM_HEAT, PRIM_GREY) = range(9)
 PRIM_COUNT = 9
 
@@ -192,6 +195,14 @@ SIGNATURES = {
     "asora_lightcone_state": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "asora_lightcone_reset": (C.c_int, [C.c_int]),
     "asora_debug_lightcone_ms": (C.c_int, [_dp]),
+    "asora_halo_catalogue_to_device": (C.c_int, [_dp, _dp, _dp, C.c_longlong, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_longlong)]),
+    "asora_halo_catalogue_clear": (C.c_int, []),
+    "asora_halo_catalogue_state": (C.c_int, [C.POINTER(C.c_longlong), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
+    "asora_halo_table_to_host": (C.c_int, [C.POINTER(C.c_int64), _u64p, _u64p, C.c_longlong]),
+    "asora_halo_sources_build": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double,
+                                           C.POINTER(C.c_ulonglong), C.POINTER(C.c_longlong)]),
+    "asora_halo_sources_to_host": (C.c_int, [_ip, _dp, C.c_longlong]),
+    "asora_debug_halo_sources_ms": (C.c_int, [_dp]),
     "asora_set_option": (C.c_int, [C.c_int, C.c_int]),
     "asora_get_option": (C.c_int, [C.c_int]),
     "asora_kernel_time_ms": (C.c_int, [C.c_int, _dp, C.POINTER(C.c_long)]),

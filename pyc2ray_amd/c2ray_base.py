@@ -79,6 +79,11 @@ Differences from the reference:
     cone of the run while it advances (pyc2ray_amd/lightcone.py; use_gpu and cosmological runs only): every step adds the slices
     whose redshift it crossed, interpolated between the previous state and its own on the device, to ``lightcone``;
     ``last_lightcone_step`` and one line in the log.  ``brightness_temperature_scale(z)`` takes a redshift.
+  * Sources from a halo catalogue (pyc2ray_amd/halo_sources.py; use_gpu only): ``halo_catalogue`` (a HaloCatalogue, assigned at
+    every new snapshot) and ``source_model`` (a SourceModel; or the optional keys ``Sources: fgamma_hm / fgamma_lm / ts /
+    suppression / x_suppress / f_suppressed``, with ``Sources: m_lm / m_hm`` the thresholds of ``new_halo_catalogue``) make
+    ``evolve3D(dt)`` without a source list build the list of the step from the catalogue and the object's own ionised fraction --
+    on the device-resident path from the grid where it lies: ``halo_sources()``, ``last_halo_sources`` and one line in the log.
 """
 import atexit
 import math
@@ -106,6 +111,7 @@ from .redshift_space import redshift_space_spec, spectrum_on_device, field_on_de
 from .lyman_alpha import lyman_alpha_spec, forest_on_device
 from .bispectrum import bispectrum_spec, bispectrum_on_device
 from .lightcone import LightCone, lightcone_spec
+from .halo_sources import HaloCatalogue, SourceModel, halo_spec, halo_sources as catalogue_sources, sources_on_device
 from .budget import StepBudget
 from .lls import LLSOpacity, LLSSchedule, lls_spec
 from .planeflux import PlaneFlux, plane_flux_spec
@@ -472,6 +478,7 @@ class C2Ray:
         self._lls_init()
         self._boundaries_init()
         self._plane_flux_init()
+        self._halo_sources_init()
         for name in self._step_closers():
             self._statistic_init(name)
         if self.rank == 0:
@@ -1003,9 +1010,89 @@ class C2Ray:
         self.__dict__["_lightcone_z_prev"] = z_now
         return step
 
-    def evolve3D(self, dt, src_flux, src_pos, src_spectrum=None):
+    # ---- sources from a halo catalogue (pyc2ray_amd/halo_sources.py) -------------------------------------
+    def _halo_sources_init(self):
+        """The optional ``Sources:`` keys of the halo source model: with ``fgamma_hm`` there, ``source_model`` is made from
+        ``fgamma_hm``, ``fgamma_lm`` (default 0), ``ts`` (Myr), ``suppression``, ``x_suppress`` and ``f_suppressed``, checked now;
+        ``m_lm`` and ``m_hm`` are the mass thresholds of :meth:`new_halo_catalogue`."""
+        src = self._ld.get('Sources') or {}
+        d = self.__dict__
+        d["_halo_catalogue"], d["_source_model"], self.last_halo_sources = None, None, None
+        self.halo_mass_thresholds = {k: src[k] for k in ("m_lm", "m_hm") if k in src}
+        if "fgamma_hm" in src:
+            if "ts" not in src:
+                raise ValueError("Sources: fgamma_hm needs ts, the time in Myr over which the photons are released")
+            extra = {k: src[k] for k in ("suppression", "x_suppress", "f_suppressed") if k in src}
+            self.source_model = SourceModel(src["fgamma_hm"], src.get("fgamma_lm", 0.0), src["ts"], who="Sources", **extra)
+        HaloCatalogue(np.zeros((0, 3)), np.zeros(0), **self.halo_mass_thresholds)      # ValueError for bad thresholds, now
+
+    @property
+    def halo_catalogue(self):
+        """The halo catalogue the sources of a step are built from (a :class:`pyc2ray_amd.halo_sources.HaloCatalogue` or None):
+        assigned by the driver at every new snapshot; it is uploaded and binned when the next list is built."""
+        return self.__dict__.get("_halo_catalogue")
+
+    @halo_catalogue.setter
+    def halo_catalogue(self, value):
+        if value is not None and not isinstance(value, HaloCatalogue):
+            raise ValueError(f"C2Ray.halo_catalogue: halo_catalogue must be a HaloCatalogue or None, not {type(value).__name__}")
+        self.__dict__["_halo_catalogue"] = value
+
+    @property
+    def source_model(self):
+        """How the weights of ``halo_catalogue`` become photon rates (a :class:`pyc2ray_amd.halo_sources.SourceModel` or None)."""
+        return self.__dict__.get("_source_model")
+
+    @source_model.setter
+    def source_model(self, value):
+        if value is not None and not isinstance(value, SourceModel):
+            raise ValueError(f"C2Ray.source_model: source_model must be a SourceModel or None, not {type(value).__name__}")
+        self.__dict__["_source_model"] = value
+
+    def new_halo_catalogue(self, positions, masses, weights=None, **kw):
+        """``halo_catalogue`` <- HaloCatalogue(positions, masses, weights) with the parameter file's ``Sources: m_lm / m_hm``
+        unless given; returns it."""
+        self.halo_catalogue = HaloCatalogue(positions, masses, weights, **{**self.halo_mass_thresholds, **kw})
+        return self.halo_catalogue
+
+    def halo_sources(self):
+        """The source list that ``halo_catalogue`` and ``source_model`` give for the current ionised fraction, a
+        :class:`pyc2ray_amd.halo_sources.HaloSourceList`, with the scale of the object's cosmology and abundances.  While the
+        ionised fraction of the last step lives on the device only (``device_resident``), it is read there: only the list crosses
+        PCIe, and ``xh`` stays where it is.  Otherwise -- with ``use_mpi`` too -- the host array is uploaded; every rank builds the
+        same list from its own copy."""
+        cat, model = self.halo_catalogue, self.source_model
+        if cat is None or model is None:
+            raise ValueError("C2Ray.halo_sources: needs halo_catalogue (a HaloCatalogue) and source_model (a SourceModel, or the "
+                             "Sources: fgamma_hm / fgamma_lm / ts keys of the parameter file)")
+        if not self.gpu:
+            raise ValueError("C2Ray.halo_sources: halo_sources needs use_gpu=True (the list is built on the device)")
+        kw = dict(cosmology=self.cosmology, mean_molecular=self.mean_molecular)
+        if self.device_resident and not self.mpi and "xh" in self._device_newer and cuda_is_init():
+            return sources_on_device(load_asora(), _capi.GRID_XH, halo_spec("C2Ray.halo_sources", self.N, cat, model, **kw))
+        return catalogue_sources(cat, model, xh=self.xh, **kw)
+
+    def _step_sources(self, src_flux, src_pos):
+        """The source list of a step: the caller's, or with both left out the one of :meth:`halo_sources`, which becomes
+        ``last_halo_sources`` and a line of the log."""
+        if src_flux is not None and src_pos is not None:
+            return src_flux, src_pos
+        if (src_flux is None) != (src_pos is None):
+            raise ValueError("C2Ray.evolve3D: src_flux and src_pos come together or not at all")
+        if self.halo_catalogue is None or self.source_model is None:
+            raise ValueError("C2Ray.evolve3D: no sources: pass src_flux and src_pos, or assign halo_catalogue (a HaloCatalogue) and "
+                             "source_model (a SourceModel, or the Sources: keys of the parameter file) for evolve3D(dt)")
+        sources = self.halo_sources()
+        self.last_halo_sources = sources
+        if self.rank == 0:
+            self.printlog(sources.log_line())
+        return sources.src_flux, sources.src_pos
+
+    def evolve3D(self, dt, src_flux=None, src_pos=None, src_spectrum=None):
         """Evolve the grid over one time step (c2ray_base.py:170-226).  src_spectrum: with ``BlackBodySource: Teff`` a list, the
-        index into it of each source's temperature (None: every source the first one); see pyc2ray_amd.evolve3D."""
+        index into it of each source's temperature (None: every source the first one); see pyc2ray_amd.evolve3D.  With `src_flux`
+        and `src_pos` left out the sources are those of :meth:`halo_sources`."""
+        src_flux, src_pos = self._step_sources(src_flux, src_pos)
         if self.device_resident and self.gpu and not self.mpi:
             return self._evolve3D_resident(dt, src_flux, src_pos, src_spectrum)
         budget = {"budget": StepBudget()} if self.photon_budget else {}      # (off: the entry never hears of it)

@@ -383,8 +383,28 @@ struct State {
         struct Kept { bool has = false; int kind = 0, src_grid = -1; } kept[ASORA_LC_SLOTS];
         double ms[ASORA_LC_STAGES] = {0, 0, 0, 0};
     } lightcone;
+    // the halo catalogue's own buffers (asora_halo_catalogue_to_device, halo_sources.hip).  Of one catalogue call and released
+    // before it returns: the uploaded catalogue, the two N^3 grids of integer sums, the row counts and their scan.  Kept until the
+    // next catalogue, asora_halo_catalogue_clear or the end of the mesh: the table [3][n_cells] (cell, Q_hm, Q_lm) and, sized by
+    // it, what a build writes -- the flux of every row, the counts of the chunks and their scan, the list that crosses PCIe; the
+    // summary words on the device and in the pinned area.  loaded counts only while the table is there, so it needs no reset when
+    // the mesh goes.  generation: how many catalogues have gone up in this process, the name of the one the device holds.
+    // ms: the stage times of the last catalogue call ([0] ... [4]) and build ([5] ... [7]) under ASORA_OPT_TIMING
+    struct HaloSources {
+        MeshBuffer<double> cat_pos, cat_mass, cat_weight;
+        MeshBuffer<unsigned long long> q_hm, q_lm, row_scan;
+        MeshBuffer<unsigned> rows;
+        MeshBuffer<unsigned long long> table, chunk_scan, summary;
+        MeshBuffer<unsigned> chunk_count;
+        MeshBuffer<double> flux_all, out_flux;
+        MeshBuffer<int32_t> out_pos;
+        MeshPinned<unsigned long long> host;
+        struct Loaded { bool has = false, built = false; long long n_cells = 0, n_active = 0; int unit_exponent = 0; } loaded;
+        long long generation = 0;
+        double ms[ASORA_HALO_STAGES] = {0, 0, 0, 0, 0, 0, 0, 0};
+    } halo;
 
-    ProcessBuffer<unsigned long long> counters;   // [COUNTER_FIELDS * COUNTER_SLOTS]: gamma cells, evaluated cells, exact zeros left out, spread over the slots
+    ProcessBuffer<unsigned long long> counters;  // [COUNTER_FIELDS * COUNTER_SLOTS]: gamma cells, evaluated cells, exact zeros left out, spread over the slots
     long long last_gamma_cells = 0, last_eval_cells = 0;
 
     // the evolve step (asora_evolve_*): which accumulator set is which, the device-side convergence bookkeeping, what the step was

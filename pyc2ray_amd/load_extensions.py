@@ -807,6 +807,67 @@ class _LibAsora:
         _capi.check(self._lib.asora_debug_lightcone_ms(_capi.dptr(ms)), "debug_lightcone_ms")
         return ms
 
+    def halo_catalogue_to_device(self, pos, mass, weight, m_lm, m_hm, wrap, unit_exponent):
+        """Uploads a halo catalogue -- `pos` (n, 3) in cell units, `mass` and `weight` (n) -- and bins it on the device into the
+        table of its occupied cells with the unit 2^`unit_exponent` (include/asora_hip.h, asora_halo_catalogue_to_device): a dict
+        of ``n_cells``, ``outside``, ``nonfinite`` and ``below``.  It replaces the catalogue the device held."""
+        p = np.ascontiguousarray(pos, dtype=np.float64)
+        m, w = np.ascontiguousarray(mass, dtype=np.float64), np.ascontiguousarray(weight, dtype=np.float64)
+        if p.ndim != 2 or p.shape[1] != 3 or m.shape != (p.shape[0],) or w.shape != m.shape:
+            raise ValueError("halo_catalogue_to_device: pos must be (n, 3), mass and weight (n)")
+        n = int(m.size)
+        counts = (C.c_longlong * 4)()
+        some = n > 0
+        _capi.check(self._lib.asora_halo_catalogue_to_device(_capi.dptr(p) if some else None, _capi.dptr(m) if some else None,
+                                                             _capi.dptr(w) if some else None, n, float(m_lm), float(m_hm),
+                                                             1 if wrap else 0, int(unit_exponent), counts), "halo_catalogue_to_device")
+        return dict(zip(("n_cells", "outside", "nonfinite", "below"), (int(v) for v in counts)))
+
+    def halo_catalogue_clear(self):
+        _capi.check(self._lib.asora_halo_catalogue_clear(), "halo_catalogue_clear")
+
+    def halo_catalogue_state(self):
+        """(n_cells, unit_exponent) of the catalogue the device holds, or None without one.  Host only."""
+        n, e, g = C.c_longlong(0), C.c_int(0), C.c_longlong(0)
+        _capi.check(self._lib.asora_halo_catalogue_state(C.byref(n), C.byref(e), C.byref(g)), "halo_catalogue_state")
+        return None if n.value < 0 else (int(n.value), int(e.value))
+
+    def halo_catalogue_generation(self):
+        """The number of the catalogue the device holds -- every upload in this process takes the next one -- or None without
+        one.  Host only."""
+        n, e, g = C.c_longlong(0), C.c_int(0), C.c_longlong(0)
+        _capi.check(self._lib.asora_halo_catalogue_state(C.byref(n), C.byref(e), C.byref(g)), "halo_catalogue_state")
+        return None if n.value < 0 else int(g.value)
+
+    def halo_table_to_host(self):
+        """The table of the catalogue on the device: (cell int64, Q_hm uint64, Q_lm uint64), one entry per occupied cell in
+        ascending cell index (include/asora_hip.h, asora_halo_table_to_host)."""
+        state = self.halo_catalogue_state()
+        n = 0 if state is None else state[0]
+        cell, q_hm, q_lm = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+        _capi.check(self._lib.asora_halo_table_to_host(cell.ctypes.data_as(C.POINTER(C.c_int64)), q_hm.ctypes.data_as(_capi._u64p),
+                                                       q_lm.ctypes.data_as(_capi._u64p), n), "halo_table_to_host")
+        return cell, q_hm, q_lm
+
+    def halo_sources_build(self, which_grid, g_hm, g_lm, scale, model, x_suppress, f_suppressed):
+        """The source list of the catalogue on the device and device grid `which_grid` (include/asora_hip.h,
+        asora_halo_sources_build): a dict of ``pos`` ((n_active, 3) int32, 0-based), ``flux`` (n_active) and ``summary`` (five
+        Python ints: n_active, n_suppressed, sum Q_hm, sum Q_lm not suppressed, sum Q_lm suppressed)."""
+        summary = (C.c_ulonglong * _capi.HALO_SUMMARY)()
+        n = C.c_longlong(0)
+        _capi.check(self._lib.asora_halo_sources_build(int(which_grid), float(g_hm), float(g_lm), float(scale), int(model), float(x_suppress),
+                                                       float(f_suppressed), summary, C.byref(n)), "halo_sources_build")
+        pos, flux = np.zeros((n.value, 3), dtype=np.int32), np.zeros(n.value)
+        _capi.check(self._lib.asora_halo_sources_to_host(_capi.iptr(pos), _capi.dptr(flux), n.value), "halo_sources_to_host")
+        return dict(pos=pos, flux=flux, summary=[int(v) for v in summary])
+
+    def halo_sources_ms(self):
+        """The stage times (ms) of the last catalogue call (zeroing and upload, bin, row counts and scan, room, table) and of the last build
+        (flux, scan, emit) that ran with OPT_TIMING (include/asora_hip.h, asora_debug_halo_sources_ms)."""
+        ms = np.zeros(_capi.HALO_STAGES)
+        _capi.check(self._lib.asora_debug_halo_sources_ms(_capi.dptr(ms)), "debug_halo_sources_ms")
+        return ms
+
     def thermal_stats(self):
         """(cells that hit max_substeps, cells clamped to t_floor, most substeps of one integration) since the last
         chemistry_device / evolve_begin."""
