@@ -3,6 +3,7 @@ the per-line quantities, the weight with its cut at six Doppler widths, the opti
 window, the PDF and the dark gaps, operation by operation in the header's order.  ``erf`` and ``exp`` are scipy's and numpy's, the
 device's are the device library's: the optical depths agree to the bound of :func:`bound`, not bit for bit.  Nothing here runs on a
 device; tests/test_lyman_alpha_reference.py checks it against a 40-digit evaluation and known answers."""
+import fractions
 import math
 
 import numpy as np
@@ -108,6 +109,88 @@ def gap_statistics(flux, gap_threshold):
     lengths = np.nonzero(counts)[0]
     return dict(gaps=counts, n_dark=int(dark.sum()), n_gaps=int(counts.sum()), longest=int(lengths.max()) if lengths.size else 0,
                 full_lines=full)
+
+
+def gap_statistics_fast(flux, gap_threshold):
+    """:func:`gap_statistics` without a Python loop over the lines, for meshes of 10^5 lines: every line that is neither wholly dark
+    nor wholly bright is rolled to its first bright pixel, so that no run wraps, and the runs of all lines come from one difference
+    of the masks: a run starts where it rises and ends where it falls, and in row-major order the q-th rise belongs to the q-th fall."""
+    N = flux.shape[-1]
+    dark = (flux < gap_threshold).reshape(-1, N)
+    full = dark.all(axis=1)
+    mixed = dark[dark.any(axis=1) & ~full]
+    counts = np.zeros(N + 1, dtype=np.uint64)
+    counts[N] = int(full.sum())
+    if mixed.shape[0]:
+        first_bright = np.argmin(mixed, axis=1).astype(np.int32)
+        index = (np.arange(N, dtype=np.int32)[None, :] + first_bright[:, None]) % np.int32(N)
+        rolled = np.zeros((mixed.shape[0], N + 2), dtype=np.int8)
+        rolled[:, 1:-1] = np.take_along_axis(mixed, index, axis=1)
+        edges = np.diff(rolled, axis=1)
+        rise, fall = np.nonzero(edges == 1), np.nonzero(edges == -1)
+        assert np.array_equal(rise[0], fall[0])
+        counts += np.bincount(fall[1] - rise[1], minlength=N + 1).astype(np.uint64)
+    lengths = np.nonzero(counts)[0]
+    return dict(gaps=counts, n_dark=int(dark.sum()), n_gaps=int(counts.sum()), longest=int(lengths.max()) if lengths.size else 0,
+                full_lines=int(full.sum()))
+
+
+def fsum_of_values(a, values):
+    """math.fsum(a) for an array that holds nothing but the few `values`: the exact sum, counts times values in rational arithmetic,
+    correctly rounded once (as math.fsum rounds it), without a pass of Python floats over 10^7 cells"""
+    a = np.ravel(a)
+    counts = [int(np.count_nonzero(a == v)) for v in values]
+    assert sum(counts) == a.size and len(set(values)) == len(values)
+    return float(sum(fractions.Fraction(float(v)) * c for v, c in zip(values, counts)))
+
+
+def crafted_lines(N):
+    """Dark masks (True: dark) of a line of N pixels in mask words of 64, made for the word arithmetic of a gap walk: wholly dark and
+    wholly bright; all dark but one pixel and all bright but one pixel at 0, 63, 64 and N - 1 (one run of N - 1, joined through the wrap
+    unless the bright pixel is at an end); the runs [63, 64], [0, 63], [64, 127] and [1, N - 2]; from N = 192 on a run from inside
+    word 0 to inside word 2, word 1 wholly dark; a run from N - 3 through the wrap to 2; alternating pixels starting dark and starting
+    bright (at odd N the first and last join).  What does not fit a line of N (pixel 64 at N = 64) is left out."""
+    lines = [np.ones(N, dtype=bool), np.zeros(N, dtype=bool)]
+    places = [p for p in (0, 63, 64, N - 1) if 0 <= p < N]
+    places = [p for q, p in enumerate(places) if p not in places[:q]]
+    for base in (True, False):
+        for p in places:
+            line = np.full(N, base)
+            line[p] = not base
+            lines.append(line)
+    for a, b in ((63, 64), (0, 63), (64, 127), (1, N - 2)):
+        if 0 <= a <= b < N:
+            line = np.zeros(N, dtype=bool)
+            line[a:b + 1] = True
+            lines.append(line)
+    if N >= 192:
+        line = np.zeros(N, dtype=bool)
+        line[40:151] = True
+        lines.append(line)
+    if N >= 7:
+        line = np.zeros(N, dtype=bool)
+        line[[N - 3, N - 2, N - 1, 0, 1, 2]] = True
+        lines.append(line)
+    lines.append(np.arange(N) % 2 == 0)
+    lines.append(np.arange(N) % 2 == 1)
+    return lines
+
+
+def mask_field(N, axis, lines_at, seed=0):
+    """(x, n, T, dark): fields whose forest along `axis` has a known answer.  dark (N^2, N) is the designed mask of the lines in the
+    order of :func:`pick_lines`: line ``lines_at[q]`` is crafted line q mod their number, every other line is a Bernoulli line with
+    p = 0.02, 0.5 or 0.98 in turn.  x = 0 where dark and 1 where bright, n = 1, T = 0, no velocity: with tau_scale = 5 and any b_scale
+    every bt is the floor 2^-10 and every cell is one pixel wide, a cell's weight on its own pixel is (erf(512) - erf(-512)) / 2 = 1
+    and its neighbours lie outside the cut, so tau = 5 on the dark pixels and exactly 0 on the bright ones, W = 1, clipped = 0,
+    degenerate = 0, and F is exp(-5) or exactly 1: gap_threshold = 0.5 gives back the designed mask."""
+    rng = np.random.default_rng(1000 * N + 10 * axis + seed)
+    p = np.array([0.02, 0.5, 0.98])[np.arange(N * N) % 3]
+    dark = rng.random((N * N, N)) < p[:, None]
+    crafted = crafted_lines(N)
+    for q, at in enumerate(lines_at):
+        dark[at] = crafted[q % len(crafted)]
+    x = np.ascontiguousarray(np.moveaxis(np.where(dark, 0.0, 1.0).reshape(N, N, N), -1, axis))
+    return x, np.ones((N, N, N)), np.zeros((N, N, N)), dark
 
 
 def pdf_of(flux, edges):

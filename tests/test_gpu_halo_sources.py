@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import halo_sources_reference as R
+import untested_trips as UT
 
 pytestmark = pytest.mark.gpu
 
@@ -84,6 +85,7 @@ def _build(asora, table, x, g_hm, g_lm, scale, model, x_suppress, f, grid=None):
     if got["flux"].size:
         sorted_pos, sorted_flux, _ = lib.sort_sources(got["pos"].ravel(), got["flux"])
         assert sorted_pos.tobytes() == got["pos"].tobytes() and sorted_flux.tobytes() == got["flux"].tobytes()
+    got["statement"] = want
     return got
 
 
@@ -162,6 +164,42 @@ def test_mesh_of_67_clustered(asora):
     x = _field(N, 674)
     lib.grid_to_device(capi.GRID_XH, x)
     _build(asora, table, x, 2.0, 30.0, 1.25e-9, "full", 0.1, 0.0)
+
+
+def test_mesh_of_192_second_tile_of_the_chunk_scan(asora):
+    """N = 192 with a halo in every fifth cell and 300 000 more (tests/untested_trips.py): more than 4096 x 256 occupied cells, so the
+    scan of the chunk counts carries into a second tile and the emit kernel writes behind offsets taken from it; 36 864 rows of three
+    trips of 64 cells, more rows than the row kernel has waves where the device has fewer than 288 compute units."""
+    p, lib, capi = asora
+    import torch
+    N = UT.HS_MESH
+    _mesh(asora, N)
+    pos, mass = UT.halo_catalogue(N)
+    table = _table(asora, N, pos, mass, mass, True, R.unit_exponent(mass))
+    n_cells = table[3]["n_cells"]
+    assert lib.halo_catalogue_state()[0] == n_cells > UT.HS_CHUNK_SCAN_NEEDS == 4096 * 256      # the library's own count
+    chunks = -(-n_cells // UT.HS_THREADS)
+    assert UT.HS_SCAN_TILE < chunks < 2 * UT.HS_SCAN_TILE and N * N > 2 * UT.HS_SCAN_TILE       # two tiles of chunks; nine of rows
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    if UT.rows_second_trip(N, cus):
+        print(f"{cus} compute units: {N * N} rows for {cus * UT.HS_ROW_BLOCKS_PER_CU * UT.HS_WAVES} waves, a wave takes a second row")
+    else:
+        print(f"{cus} compute units: every wave of the row kernel has one row at the most; a wave's second row is NOT reached here")
+    assert N % 64 == 0 and N // 64 == 3
+    x = _field(N, 1921)
+    lib.grid_to_device(capi.GRID_XH, x)
+    edge = UT.HS_SCAN_TILE * UT.HS_THREADS                     # the first table row of chunk 4096
+    for model, f in (("none", 0.0), ("full", 0.0), ("partial", 0.25)):
+        got = _build(asora, table, x, 2.0, 30.0, 1.25e-9, model, 0.1, f)
+        want_pos, want_flux, _ = got["statement"]
+        # the last source before chunk 4096 of the table and the first one of it: where the list passes the carry of the scan
+        cells = (want_pos[:, 0].astype(np.int64) * N + want_pos[:, 1]) * N + want_pos[:, 2]
+        at = int(np.searchsorted(cells, table[0][edge]))
+        assert 0 < at < got["summary"][0] == cells.size and cells[at - 1] < table[0][edge] <= cells[at]
+        for q in (at - 1, at):
+            assert np.array_equal(got["pos"][q], want_pos[q]) and got["flux"][q] == want_flux[q] > 0.0, (model, q)
+        if model == "full":
+            assert 0 < got["summary"][1] and got["summary"][0] < n_cells
 
 
 @pytest.mark.parametrize("wrap", [True, False])

@@ -1,7 +1,8 @@
 """GPU: slices of a light cone (asora_lightcone_advance) against the numpy statement of
 tests/lightcone_reference.py -- exactly, as the blend is two rounded products and a sum -- on meshes of 24, 33 and 70 cells along
 all three axes; the moments against math.fsum of the device's own slices; the kept field, the slots, the refusals; a run of the class
-against make_lightcone on its downloaded states.  Every call is made twice and compared byte for byte."""
+against make_lightcone on its downloaded states; calls of the most slices the entry takes (tests/untested_trips.py).  Every call is
+made twice and compared byte for byte."""
 import functools
 import math
 import os
@@ -10,6 +11,7 @@ import numpy as np
 import pytest
 
 import lightcone_reference as R
+import untested_trips as UT
 
 pytestmark = pytest.mark.gpu
 
@@ -302,7 +304,48 @@ def test_a_mesh_of_five_tiles_along_axis_2(asora):
         _check_moments(got, N, ("N = 320", planes.size))
 
 
-DTS = (1.0e10, 2.0e11, 1.0e9, 5.0e10)     # the first state is kept; then 34 slices (more than N), none, 8
+@pytest.mark.parametrize("case", ["axis_0", "axis_1", "no_run", "runs_of_4", "mixed"])
+def test_the_most_slices_a_call_takes(asora, case):
+    """ASORA_LC_MAX_SLICES = 1024 slices in one call at N = 70 (tests/untested_trips.py): on the axes 0 and 1 and as a list without a
+    run on axis 2, 2.39 trips of lc_emit_kernel's grid-stride loop; on axis 2 in 256 runs of 4, the run table full to its last entry
+    with the moments directly behind it; and in 31 runs of 32 with 32 listed slices between.  The ionised fraction and a grid taken
+    as it is, byte for byte against the statement; the moments of all 1024 slices, eight workgroups of the fold."""
+    p, lib, capi = asora
+    N, most = UT.LC_MESH, capi.LC_MAX_SLICES
+    assert most == UT.LC_MAX_SLICES and UT.fold_workgroups(most) == 8
+    rng = np.random.default_rng(len(case) + 7000)
+    if case.startswith("axis"):
+        axis, planes = int(case[-1]), rng.integers(0, N, size=most)
+        assert UT.emit_trips(most * N * N) > 2.0
+    else:
+        axis = 2
+        planes, n_runs, n_listed, why = UT.plane_lists(N)[case]
+        runs, listed = UT.cut_runs(planes)
+        assert (len(runs), len(listed)) == (n_runs, n_listed) and n_listed + sum(r.len for r in runs) == most
+        if case == "no_run":
+            assert UT.emit_trips(len(listed) * N * N) > 2.0 and not np.any(np.abs(np.diff(planes)) == 1)
+        if case == "runs_of_4":
+            assert len(runs) == UT.LC_RUN_TABLE == most // UT.LC_RUN_MIN and all(r.len == UT.LC_RUN_MIN for r in runs)
+    assert planes.size == most
+    _mesh(asora, N)
+    before, after = _state(N, 1), _state(N, 2)
+    configs = [(0, capi.PS_XH, None, before[0], after[0]), (2, capi.PS_XH, capi.GRID_XH_AV, before[3], after[3])]
+    _upload(asora, before)
+    for slot, kind, src, _, _ in configs:
+        lib.lightcone_reset(slot)
+        lib.lightcone_advance(slot, kind, src, 0.0, axis, (), (), (), True)
+    _upload(asora, after)
+    w_prev, w_now = _weights(most, rng)
+    for slot, kind, src, prev, now in configs:
+        got = _advance(lib, slot, kind, src, 0.0, axis, planes, w_prev, w_now)
+        ref = R.blend(prev, now, planes, w_prev, w_now, axis)
+        assert got["slices"].shape == ref.shape == (most, N, N) and got["slices"].tobytes() == ref.tobytes(), (case, src)
+        assert got["moments"].shape == (most, 2)
+        worst = _check_moments(got, N, (case, src))
+        print(f"{case}, source grid {src}: the moments of {most} slices use at most {worst:.2e} of their bound")
+
+
+DTS = (1.0e10, 2.0e11, 1.0e9, 5.0e10)   # the first state is kept; then 34 slices (more than N), none, 8
 
 
 @pytest.mark.parametrize("resident", [True, False])

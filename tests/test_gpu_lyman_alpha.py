@@ -4,7 +4,11 @@ its numpy/scipy statement, tests/lyman_alpha_reference.py.  Every call is made t
 The optical depth carries the bound of the reference, (2 W + 16) eps S[p] (derived there: the device's erf and exp are the device
 library's, scipy's are the reference's); what is made of integers -- the window, clipped, degenerate, the PDF, the gaps -- is
 compared exactly, the PDF and the gaps with numpy on the device's own downloaded F; sum F and sum F^2 within (N^3 + 4) eps relative,
-the worst case of any summation order of non-negative terms plus exp."""
+the worst case of any summation order of non-negative terms plus exp.
+
+A second pass (tests/untested_trips.py; DESIGN.md 4.2k, "Which trips the second pass reaches") runs fields with a known answer made
+from crafted dark masks at N = 64, 128, 129, 192 and 320, the strict < of the threshold at equality, the PDF's limits, and a
+non-finite reach."""
 import ctypes as C
 import functools
 import math
@@ -14,6 +18,7 @@ import numpy as np
 import pytest
 
 import lyman_alpha_reference as R
+import untested_trips as UT
 
 pytestmark = pytest.mark.gpu
 
@@ -198,6 +203,165 @@ def test_tiles_of_8_columns(asora):
         assert int(got["counts"][capi.LYA_WINDOW]) == 1 and int(got["counts"][capi.LYA_CLIPPED]) > 0
         _within_bound(tau, ref, f"N = {N}, axis {axis}, {lines.size} lines")
         assert np.count_nonzero(ref["tau"]) > 0.2 * ref["tau"].size
+
+
+# ---- the second pass: the word arithmetic of the gap walk, the PDF's limits, whole meshes of other tile forms (tests/untested_trips.py)
+MASK_B_SCALE, MASK_TAU_SCALE, MASK_THRESHOLD = 0.37, 5.0, 0.5      # (b_scale is arbitrary: T = 0, every bt is the floor)
+GAP_COUNTS = ("n_dark", "n_gaps", "longest", "full_lines")
+
+
+def _mask_mesh(asora, N, axis):
+    """The crafted field of R.mask_field on the device, its crafted lines where the library's tiles of (N, axis) differ: (x, n, T,
+    dark, the placement).  Asserts, from the tiles the library reports, that the placement reaches what it is there for."""
+    p, lib, capi = asora
+    tiles = lib.lyman_alpha_forest_tiles(N, axis)
+    place = UT.lya_placement(N, axis, tiles["lines"], len(R.crafted_lines(N)))
+    starts, at = place["starts"], set(place["lines_at"])
+    assert len(starts) == tiles["workgroups"] and starts[0] == 0
+    assert {0, N * N - 1} <= at and set(range(starts[-1], N * N)) <= at               # the first tile's first line; the whole last tile
+    assert len(place["boundaries"]) >= 3 and all(b in starts and b - 1 in at and b in at for b in place["boundaries"])
+    ragged = N % tiles["lines"] if axis == 1 else N * N % tiles["lines"]
+    assert place["last_width"] == (ragged or tiles["lines"])
+    x, n, T, dark = R.mask_field(N, axis, place["lines_at"])
+    _mesh(asora, N)
+    for which, grid in ((capi.GRID_XH, x), (capi.GRID_NDENS, n), (capi.GRID_TEMP, T)):
+        lib.grid_to_device(which, grid)
+    return x, n, T, dark, place
+
+
+def _gaps_are(got, capi, want, what):
+    counts = got["counts"]
+    assert got["gaps"].tobytes() == want["gaps"].tobytes(), what
+    assert (int(counts[capi.LYA_N_DARK]), int(counts[capi.LYA_N_GAPS]), int(counts[capi.LYA_LONGEST]), int(counts[capi.LYA_FULL_LINES])) == \
+           tuple(want[k] for k in GAP_COUNTS), what
+
+
+def _known_answer(asora, got, N, axis, dark, what):
+    """What every crafted field gives: W = 1, nothing clipped, degenerate or non-finite; tau exactly 0 and F exactly 1 on the bright
+    pixels; F below the threshold on the dark ones.  Prints whether tau == g holds bit for bit (the device's erf(+-512) decides)."""
+    p, lib, capi = asora
+    counts = got["counts"]
+    assert int(counts[capi.LYA_WINDOW]) == 1 and int(counts[capi.LYA_CLIPPED]) == 0 and int(counts[capi.LYA_DEGENERATE]) == 0
+    assert int(counts[capi.LYA_NONFINITE]) == 0
+    cube = np.moveaxis(dark.reshape(N, N, N), -1, axis)
+    assert np.all(got["tau"][~cube] == 0.0) and np.all(got["flux"][~cube] == 1.0)
+    assert np.array_equal(got["flux"] < MASK_THRESHOLD, cube)
+    exact = bool(np.all(got["tau"][cube] == MASK_TAU_SCALE))
+    print(f"{what}: tau == g bit for bit on the device: {exact}")
+    return cube
+
+
+@pytest.mark.parametrize("N,axis", [(N, axis) for N in UT.LYA_MESHES for axis in (0, 1, 2)])
+def test_crafted_masks_across_words_and_tiles(asora, N, axis):
+    """Lines of one, two, two and a bit, and three mask words with runs made for the gap walk (R.crafted_lines) in the first tile, the
+    last and either side of tile boundaries: tau against the statement, the gaps against the statement's on the DESIGNED mask and
+    against numpy on the device's own F."""
+    p, lib, capi = asora
+    x, n, T, dark, place = _mask_mesh(asora, N, axis)
+    assert UT.mask_words(N) == {64: 1, 128: 2, 129: 3, 192: 3}[N] and (UT.pad_bits(N) == 0) == (N % 64 == 0)
+    ref = R.forest(x, n, T, None, axis, 0.0, MASK_B_SCALE, MASK_TAU_SCALE, gap_threshold=MASK_THRESHOLD)
+    assert (ref["window"], ref["clipped"], ref["degenerate"]) == (1, 0, 0)
+    assert np.array_equal(np.moveaxis(ref["flux"], axis, -1).reshape(-1, N) < MASK_THRESHOLD, dark)      # its gaps are the designed mask's
+    got = _twice(lib, axis, None, MASK_B_SCALE, MASK_TAU_SCALE, gap_threshold=MASK_THRESHOLD, tau=True, flux=True)
+    what = f"crafted masks, N = {N}, axis {axis}"
+    _within_bound(got["tau"], ref, what)
+    _known_answer(asora, got, N, axis, dark, what)
+    _gaps_are(got, capi, ref, what)
+    _gaps_are(got, capi, R.gap_statistics_fast(np.moveaxis(got["flux"], axis, -1), MASK_THRESHOLD), what + ", its own F")
+    assert ref["full_lines"] >= 2 and ref["longest"] == N and ref["gaps"][N - 1] >= 4 and ref["gaps"][1] > N
+
+
+def test_threshold_equality_and_pdf_limits(asora):
+    """The strict < of the dark mask at equality; the PDF with values ON its edges, with repeated edges and with one bin; and with
+    the 1024 bins of the limit on the forest of N = 70."""
+    p, lib, capi = asora
+    N, axis = 64, 2
+    x, n, T, dark, place = _mask_mesh(asora, N, axis)
+    call = lambda **kw: _twice(lib, axis, None, MASK_B_SCALE, MASK_TAU_SCALE, tau=True, flux=True, **kw)
+    plain = call(gap_threshold=MASK_THRESHOLD)
+    cube = _known_answer(asora, plain, N, axis, dark, "N = 64, axis 2")
+    values = np.unique(plain["flux"][cube])
+    assert values.size == 1 and 0.0 < values[0] < 0.01                 # one F for every dark pixel: exp(-5) as the device has it
+    f_dark = float(values[0])
+    n_dark, n_bright = int(dark.sum()), int((~dark).sum())
+    designed = R.gap_statistics(np.where(dark, 0.0, 1.0), MASK_THRESHOLD)
+    _gaps_are(plain, capi, designed, "threshold 0.5")
+    at = call(gap_threshold=f_dark)                                    # F < F is false: no dark pixel
+    _gaps_are(at, capi, dict(gaps=np.zeros(N + 1, dtype=np.uint64), n_dark=0, n_gaps=0, longest=0, full_lines=0), "threshold == F")
+    _gaps_are(call(gap_threshold=float(np.nextafter(f_dark, 1.0))), capi, designed, "threshold the next double above F")
+    # a value on an edge belongs to the bin above; between repeated edges lies nothing; F = 1 is outside [..., 1.0]
+    for edges, want in (([0.0, f_dark, 1.0, float(np.nextafter(1.0, 2.0))], [0, n_dark, n_bright]), ([f_dark, f_dark, 1.0], [0, n_dark]),
+                        ([f_dark, 1.0], [n_dark]), ([1.0, 2.0], [n_bright]), ([0.0, f_dark], [0])):
+        got = call(gap_threshold=MASK_THRESHOLD, edges=edges)
+        assert got["pdf"].tolist() == want == R.pdf_of(got["flux"], edges).tolist(), edges
+        assert got["tau"].tobytes() == plain["tau"].tobytes()
+    # the most bins the entry takes, on a forest whose F fills them
+    N = 70
+    _mesh(asora, N, _fields(N))
+    edges = np.linspace(0.0, 1.0, capi.LYA_MAX_BINS + 1)
+    assert edges.size - 1 == UT.LYA_MAX_BINS == R.MAX_BINS
+    got = _twice(lib, 0, VSCALE, B_SCALE, TAU_SCALE, edges=edges, flux=True)
+    flux = got["flux"]
+    assert got["pdf"].shape == (1024,) and got["pdf"].tobytes() == R.pdf_of(flux, edges).tobytes()
+    inside = np.isfinite(flux) & (flux >= edges[0]) & (flux < edges[-1])
+    assert int(got["pdf"].sum()) == int(inside.sum()) < N ** 3 and np.count_nonzero(got["pdf"]) > 1000 and got["pdf"][-1] > 0
+    assert any(np.any(flux == e) for e in edges[:-1])                  # (an F on an edge: exact 0 at the least)
+
+
+@pytest.mark.parametrize("axis", [0, 1, 2])
+def test_whole_mesh_of_8_column_and_4_row_tiles(asora, axis):
+    """The crafted field at N = 320 -- five exact mask words, tiles of 8 columns (axes 0 and 1) and of 4 rows (axis 2) -- with every
+    whole-mesh result: the gaps and counts against the vectorised statement on the designed mask, the sums against math.fsum of the
+    device's own F; tau against the statement on the crafted lines."""
+    p, lib, capi = asora
+    N = UT.LYA_MESH_OF_8_COLUMNS
+    assert lib.lyman_alpha_forest_tiles(N, axis)["lines"] == (4 if axis == 2 else 8) and UT.mask_words(N) == 5 and UT.pad_bits(N) == 0
+    x, n, T, dark, place = _mask_mesh(asora, N, axis)
+    got = _twice(lib, axis, None, MASK_B_SCALE, MASK_TAU_SCALE, gap_threshold=MASK_THRESHOLD, tau=True, flux=True)
+    what = f"crafted masks, N = {N}, axis {axis}"
+    _known_answer(asora, got, N, axis, dark, what)
+    lines = np.array(place["lines_at"])
+    ref = R.forest(x, n, T, None, axis, 0.0, MASK_B_SCALE, MASK_TAU_SCALE, lines=lines)
+    assert (ref["window"], ref["clipped"], ref["degenerate"]) == (1, 0, 0)
+    _within_bound(R.pick_lines(got["tau"], axis, lines), ref, what)
+    want = R.gap_statistics_fast(np.where(dark, 0.0, 1.0), MASK_THRESHOLD)
+    _gaps_are(got, capi, want, what)
+    assert want["full_lines"] >= 2 and want["longest"] == N and want["gaps"][111] >= 2 and want["gaps"][N - 1] >= 8
+    # math.fsum of the device's own F, which holds two values (_known_answer): the exact sum from their counts, rounded once
+    flux = got["flux"].ravel()
+    f_dark = float(flux.min())
+    assert 0.0 < f_dark < 0.01
+    sums = (R.fsum_of_values(flux, [f_dark, 1.0]), R.fsum_of_values(flux * flux, [f_dark * f_dark, 1.0]))
+    for key, exact in ((capi.LYA_SUM_F, sums[0]), (capi.LYA_SUM_F2, sums[1])):
+        rel = abs(got["stats"][key] - exact) / exact
+        print(f"{what}: sum {key} off by {rel / R.EPS:.3f} eps relative")
+        assert rel <= (float(N) ** 3 + 4.0) * R.EPS
+    assert got["stats"][capi.LYA_TAU_MIN] == 0.0 and got["stats"][capi.LYA_TAU_MAX] == got["tau"].max()
+
+
+@pytest.mark.parametrize("axis", [0, 2])
+def test_a_non_finite_reach_takes_the_whole_line(asora, axis):
+    """One cell at T = +inf: the largest reach is infinite, the automatic window falls back to the cap (N - 1) / 2 = 16, the cell
+    counts as clipped, and -- its weight being (erf(0) - erf(0)) / 2 = 0 everywhere -- tau stays finite."""
+    p, lib, capi = asora
+    N = 33
+    x, n, T, v = _fields(N)
+    T = T.copy()
+    T[4, 5, 6] = np.inf
+    ref = R.forest(x, n, T, v, axis, VSCALE, B_SCALE, TAU_SCALE, edges=EDGES)
+    assert ref["reach_max"] == math.inf and ref["window"] == 16 == (N - 1) // 2 and ref["clipped"] >= 1
+    assert _reference(N, axis)["window"] < 16 and _reference(N, axis)["clipped"] == 0      # (without the cell: no fallback)
+    _mesh(asora, N, (x, n, T, v))
+    got = _twice(lib, axis, VSCALE, B_SCALE, TAU_SCALE, edges=EDGES, tau=True, flux=True)
+    counts = got["counts"]
+    assert int(counts[capi.LYA_WINDOW]) == 16 and int(counts[capi.LYA_CLIPPED]) == ref["clipped"]
+    assert int(counts[capi.LYA_DEGENERATE]) == ref["degenerate"]
+    assert int(counts[capi.LYA_NONFINITE]) == int(np.sum(~np.isfinite(got["tau"]))) == ref["nonfinite"] == 0
+    finite = np.isfinite(ref["bound"])
+    assert np.all(finite)
+    _within_bound(got["tau"], ref, f"N = {N}, axis {axis}, one cell at T = inf")
+    assert got["pdf"].tobytes() == R.pdf_of(got["flux"], EDGES).tobytes()
+    _gaps_are(got, capi, R.gap_statistics(np.moveaxis(got["flux"], axis, -1), 0.05), "T = inf")
 
 
 def test_into_a_grid(asora):

@@ -152,3 +152,83 @@ def test_pdf_rule():
     edges = [0.0, 0.25, 0.25, 0.5, 1.0]
     f = np.array([-0.1, 0.0, 0.2, 0.25, 0.49, 0.5, 0.99, 1.0, np.nan])
     assert R.pdf_of(f, edges).tolist() == [2, 0, 2, 2]             # (the empty bin takes nothing; 1.0 and the NaN are dropped)
+
+
+@pytest.mark.parametrize("N", [64, 128, 129, 192, 320])
+def test_crafted_lines_are_what_they_say(N):
+    """The lines by their runs, counted by the brute-force walk; and the vectorised gap statistics against the per-line ones on them."""
+    lines = R.crafted_lines(N)
+    assert all(l.shape == (N,) and l.dtype == bool for l in lines)
+    runs = [sorted(_runs_brute_force(l.tolist())) for l in lines]
+    assert runs[0] == [N] and runs[1] == []
+    places = len({0, 63, 64, N - 1} & set(range(N)))              # (at N = 64 there is no pixel 64, and N - 1 is 63)
+    assert places == (2 if N == 64 else 4) and runs.count([N - 1]) == places and runs.count([1]) == places
+    assert [2] in runs or N == 64                                  # [63, 64]
+    assert [64] in runs and [N - 2] in runs and [6] in runs        # [0, 63] (and [64, 127]); [1, N - 2]; N - 3 through the wrap to 2
+    assert ([111] in runs) == (N >= 192)                           # 40 ... 150: 24 bits of word 0, word 1, 23 bits of word 2
+    even, odd = runs[-2], runs[-1]
+    assert even == ([1] * (N // 2) if N % 2 == 0 else [1] * (N // 2 - 1) + [2]) and odd == [1] * (N // 2)
+    # a run that fills exactly one word (where a line has more than one), and one through the wrap
+    assert N == 64 or any(l[:64].all() and not l[64] for l in lines)
+    assert any(l[0] and l[N - 1] and not l.all() for l in lines)
+    flux = np.where(np.stack(lines), 0.0, 1.0)
+    slow, fast = R.gap_statistics(flux, 0.5), R.gap_statistics_fast(flux, 0.5)
+    assert fast["gaps"].dtype == np.uint64 and fast["gaps"].tobytes() == slow["gaps"].tobytes()
+    assert {k: fast[k] for k in ("n_dark", "n_gaps", "longest", "full_lines")} == {k: slow[k] for k in ("n_dark", "n_gaps", "longest", "full_lines")}
+    assert slow["full_lines"] == (2 if N == 64 else 1) and slow["longest"] == N      # (at N = 64 the run [0, 63] is the line)
+    assert slow["n_gaps"] == sum(len(r) for r in runs)
+
+
+@pytest.mark.parametrize("N", [1, 2, 63, 64, 65, 129])
+def test_fast_gap_statistics_against_the_loop(N):
+    rng = np.random.default_rng(900 + N)
+    for fill in (0.0, 0.03, 0.5, 0.97, 1.0):
+        flux = np.where(rng.random((7, 9, N)) < fill, 0.0, 1.0)
+        flux[0, 0, 0] = np.nan                                      # (a NaN is bright)
+        slow, fast = R.gap_statistics(flux, 0.5), R.gap_statistics_fast(flux, 0.5)
+        assert fast["gaps"].tobytes() == slow["gaps"].tobytes(), (N, fill)
+        for key in ("n_dark", "n_gaps", "longest", "full_lines"):
+            assert fast[key] == slow[key], (N, fill, key)
+
+
+@pytest.mark.parametrize("N,axis", [(64, 2), (129, 0), (192, 1)])
+def test_mask_field_has_the_known_answer(N, axis):
+    """What tests/test_gpu_lyman_alpha.py rests on: on the fields of mask_field the statement gives tau == g bit for bit, W = 1,
+    nothing clipped or degenerate, and the designed mask back."""
+    lines_at = [0, 1, N + 3, N * N - 1]
+    x, n, T, dark = R.mask_field(N, axis, lines_at)
+    crafted = R.crafted_lines(N)
+    for q, at in enumerate(lines_at):
+        assert np.array_equal(dark[at], crafted[q]) and np.array_equal(R.pick_lines(x, axis, [at])[0] == 0.0, crafted[q])
+    r = R.forest(x, n, T, None, axis, 0.0, 0.37, 5.0, gap_threshold=0.5, lines=np.arange(0, N * N, 7))
+    want = np.where(dark[::7], 5.0, 0.0)
+    assert r["tau"].tobytes() == want.tobytes() and (r["window"], r["clipped"], r["degenerate"]) == (1, 0, 0)
+    assert np.array_equal(r["flux"] < 0.5, dark[::7]) and set(np.unique(r["flux"])) == {math.exp(-5.0), 1.0}
+    assert np.all(r["bound"][dark[::7]] > 0.0)
+
+
+def test_a_non_finite_reach_takes_the_whole_line():
+    """One cell at T = +inf: its bt and its reach are infinite, the automatic window is the cap (N - 1) // 2 and the cell counts as
+    clipped; its own weight is (erf(0) - erf(0)) / 2 = 0 on every pixel, so tau stays finite everywhere."""
+    N = 33
+    x, n, T, v = R.fields(N, 133)
+    T = T.copy()
+    T[4, 5, 6] = np.inf
+    b_scale = 0.5 / math.sqrt(3.0e4)
+    for axis in (0, 2):
+        r = R.forest(x, n, T, v, axis, 0.5, b_scale, 1.0)
+        assert r["window"] == 16 == (N - 1) // 2 and r["reach_max"] == math.inf and r["clipped"] >= 1
+        assert r["nonfinite"] == 0 and np.all(np.isfinite(r["tau"])) and np.all(np.isfinite(r["bound"]))
+        capped = R.forest(x, n, np.where(np.isinf(T), 1.0, T), v, axis, 0.5, b_scale, 1.0, window=16)
+        assert r["clipped"] == capped["clipped"] + 1
+
+
+def test_fsum_of_values_is_math_fsum():
+    rng = np.random.default_rng(4)
+    f = math.exp(-5.0)
+    for values in ([f, 1.0], [f * f, 1.0], [0.1, 0.3, 1.0e16]):
+        a = rng.choice(values, size=200_001, p=[0.3, 0.7] if len(values) == 2 else [0.5, 0.3, 0.2])
+        assert R.fsum_of_values(a, values) == math.fsum(a)
+        assert R.fsum_of_values(a.reshape(3, -1), values) == math.fsum(a)
+    with pytest.raises(AssertionError):
+        R.fsum_of_values(np.array([0.5, 0.25]), [0.5])
